@@ -2,7 +2,7 @@
 """Headline benchmark: teacher-forced Tacotron2 forward, mel-frames/s, plus the rest of BASELINE.json's metric
 (autoregressive RTF, batch 64 x 800, Postnet MFMA rate, Griffin-Lim) as extra keys of the same JSON line.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W --dump-outputs DIR]
 
 A "step" is one pass of the hot path (encoder -> Prenet -> T decoder steps -> projection -> Postnet -> padding mask,
 Prenet keep masks drawn on device) over one synthetic batch that is already resident in HBM.  Headline workload =
@@ -31,6 +31,9 @@ Rank 0 prints ONE JSON line.
   validated     the run checks what it times: device status words after the timed region and after every leg (a hand-off
                 time-out or a bad token id fails the run), and the last timed forward must equal an un-timed run with the
                 same Prenet-mask seed bit for bit.
+  --dump-outputs DIR   after the timed region rank 0 writes what its LAST timed forward returned (mel_outputs,
+                mel_outputs_postnet, gate_outputs, alignments) as DIR/<name>.npy, float32.  Weights, batch and the mask seed of
+                that forward are fixed by the arguments, so two builds run with the same arguments can be compared file by file.
   extra         (N = 1) the other BASELINE configurations, each timed like the headline (warm-up, then K runs bracketed by
                 synchronize) with its own roofline fraction and CPU-oracle figure: c1_b1x568 (configs[0]), tf_b64x800,
                 ar_b64_1000, ar_b1_1000, ar_b1_1000_L190 (a long sentence), postnet_b256x800, train_step_b32x200, gl_60it_b256x800.
@@ -53,6 +56,7 @@ sys.path.insert(0, REPO)
 
 HBM_PEAK_GBS = 8000.0        # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 GB/s is the measured copy ceiling
 MFMA_F32_PEAK_TFLOPS = 157.3  # dense fp32 matrix peak (same guide): v_mfma_f32_32x32x2_f32 at 64 FLOP/clk/SIMD
+DUMP_BUDGET_BYTES = 64 * 10**6  # --dump-outputs writes at most this much in all
 
 
 def algorithmic_bytes_lstm_launch(mc, B, L, persistent=False):
@@ -79,6 +83,22 @@ def flops_lstm_launch(mc, B):
 def algorithmic_bytes_decoder_step(mc, B, L):
     """SURVEY.md section 8d figure for one whole decoder step (weights once + per-row traffic)."""
     return 4 * (18103953 + B * (645 * L + 9553))
+
+
+def dump_outputs(path, out):
+    """The tensors of `out` as path/<name>.npy, float32.  The headline shape fits the budget whole (30 MB); a larger set is cut
+    to the same share of every array's elements, at flat positions drawn from a fixed seed (sorted, so the file keeps the
+    array's order) - the same positions in every run with the same shapes."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    total = 4 * sum(v.numel() for v in out.values())
+    rng = np.random.default_rng(0)
+    for name, v in sorted(out.items()):
+        a = v.detach().float().cpu().numpy()
+        if total > DUMP_BUDGET_BYTES:
+            a = a.reshape(-1)[np.sort(rng.integers(0, a.size, a.size * DUMP_BUDGET_BYTES // total))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def log(msg):
@@ -165,10 +185,14 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the secondary configurations (extra key)")
     ap.add_argument("--only-extra", default="", help="comma list of extra configurations to run (default: all)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed forward (rank 0) as DIR/<name>.npy")
     ap.add_argument("--rehearse-one-gpu", action="store_true",
                     help="N > 1 ranks share cuda:0 over the gloo backend: exercises the launcher / barrier / broadcast / JSON "
                          "flow on a 1-GPU box; the line is marked \"rehearsal\" and is not a scaling measurement")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1: the outputs of the last timed step are what the run validates")
 
     if "RANK" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args))
@@ -254,6 +278,9 @@ def main():
         raise SystemExit("bench.py: the last timed forward does not reproduce the un-timed reference run bit for bit")
     del ref
     log(f"timed region done: {elapsed:.3f} s for {args.steps} steps; outputs of the last timed forward validated")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
+        log(f"outputs of the last timed forward written to {args.dump_outputs}")
 
     def lstm_roofline(m, b, batch_b, loop_ms):
         """Roofline of the decoder loop's dominant kernel at batch b (instrumented pass, see module docstring)."""

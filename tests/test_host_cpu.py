@@ -230,3 +230,25 @@ def test_reference_written_config_loads():
     assert torch.equal(m.state_dict()["decoder.gate_layer.linear_layer.bias"], ckpt["model_statedict"]["decoder.gate_layer.linear_layer.bias"])
     blob = m.pack_weights_host()   # host-only packing of reference-initialised weights
     assert blob.numel() == m.blob_numel() and torch.isfinite(blob).all()
+
+
+def test_bench_output_dump_whole_and_sampled(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 .npy per output; whole arrays inside the byte budget, above it the same seeded
+    positions of every array in every run."""
+    import bench
+
+    out = {"a": torch.arange(6000, dtype=torch.float32).reshape(20, 300), "b": torch.arange(2000, dtype=torch.float64)}
+    bench.dump_outputs(str(tmp_path / "whole"), out)
+    for k, v in out.items():
+        a = np.load(tmp_path / "whole" / f"{k}.npy")
+        assert a.dtype == np.float32 and a.shape == tuple(v.shape) and np.array_equal(a, v.numpy())
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 8000)   # a quarter of the 32 000 bytes above
+    for run in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / run), out)
+    files = sorted(os.listdir(tmp_path / "s1"))
+    assert files == ["a.npy", "b.npy"] and sum(os.path.getsize(tmp_path / "s1" / f) for f in files) <= 8000 + 2 * 128
+    for k, v in out.items():
+        a = np.load(tmp_path / "s1" / f"{k}.npy")
+        assert a.dtype == np.float32 and a.shape == (v.numel() // 4,)
+        assert np.array_equal(a, np.load(tmp_path / "s2" / f"{k}.npy"))
+        assert np.all(np.diff(a) >= 0) and np.isin(a, v.numpy().reshape(-1)).all()   # values = positions here: sorted, from the array
