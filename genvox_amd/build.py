@@ -7,6 +7,7 @@ with the tree to the GPU box.
 """
 from __future__ import annotations
 
+import glob
 import os
 import subprocess
 import sys
@@ -15,7 +16,8 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgenvox_amd.so")
-SOURCES = ["gemm_f32.hip", "skinny.hip", "dec_resident.hip", "attention.hip", "attn_persist.hip", "misc.hip", "griffinlim.hip", "train.hip", "gvx_api.hip"]
+SOURCES = ["gemm_f32.hip", "skinny.hip", "dec_resident.hip", "attention.hip", "attn_persist.hip", "misc.hip", "griffinlim.hip", "train.hip", "gvx_pack.hip", "gvx_decoder.hip",
+           "gvx_api.hip"]
 ARCH = "gfx950"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
@@ -36,7 +38,8 @@ def build(force: bool = False, verbose: bool = True, stamps: bool = False) -> st
     sfx = ".stamps.o" if stamps else ".o"
     if os.environ.get("GVX_LIB_NAME"):
         sfx = "." + os.environ["GVX_LIB_NAME"] + ".o"
-    headers = [os.path.join(CSRC, "gvx_kernels.h"), os.path.join(CSRC, "attn_step_body.h"), os.path.join(os.path.dirname(HERE), "include", "genvox_amd.h")]
+    # every source depends on every header: all of csrc/*.h, and the public header (last: see the stale-variant check below)
+    headers = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(os.path.dirname(HERE), "include", "genvox_amd.h")]
     for src in SOURCES:
         s = os.path.join(CSRC, src)
         o = os.path.join(CSRC, src.replace(".hip", sfx))

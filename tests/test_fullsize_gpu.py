@@ -312,7 +312,7 @@ def test_north_star_batch_64x800(mode, monkeypatch):
     gives on a 100-frame run (the teacher-forced decoder is causal; the Postnet prefix is compared where its receptive
     field - 5 layers x 2 frames - lies inside the prefix)."""
     if mode == "one_call_64_rows":
-        monkeypatch.setenv("GVX_TF_ROWS64", "1")   # opt-in (the chunks are faster: gvx_api.hip)
+        monkeypatch.setenv("GVX_TF_ROWS64", "1")   # opt-in (the chunks are faster: gvx_model::tf_rows64, csrc/gvx_internal.h)
     if mode == "two_lanes_of_32":
         monkeypatch.setenv("GVX_TF_LANES", "1")
     mc, ac, tc = full_configs()

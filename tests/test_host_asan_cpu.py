@@ -1,7 +1,7 @@
 """CPU: AddressSanitizer run of the HOST side of the C-ABI (SURVEY.md section 5 plan): weight packing (BatchNorm folding, LSTM
 gate-row permutation, MFMA-fragment order), blob layout and workspace planning are plain host C++ that index into caller
-buffers with sizes derived from the dims - exactly what ASan is good at.  gvx_api.hip is compiled with -fsanitize=address for
-the host pass only (-fno-gpu-sanitize: GPU ASan is not available on this pool) and linked with the regular kernel objects;
+buffers with sizes derived from the dims - exactly what ASan is good at.  The C-ABI layer (gvx_api.hip, gvx_pack.hip,
+gvx_decoder.hip) is compiled with -fsanitize=address for the host pass only (-fno-gpu-sanitize: GPU ASan is not available on this pool) and linked with the regular kernel objects;
 tests/host_asan/driver.cpp feeds it weight tensors that are allocated with EXACTLY the element counts of the state_dict, so
 any read past a tensor or write past the blob aborts the run.  No GPU call is made."""
 import glob
@@ -39,12 +39,16 @@ def test_host_side_under_address_sanitizer(tmp_path):
     gbuild.build(verbose=False)   # the kernel objects the sanitized library links against
     out = str(tmp_path)
     san = ["-fsanitize=address", "-shared-libsan"]
-    api_o = os.path.join(out, "gvx_api.asan.o")
-    subprocess.run([gbuild.HIPCC, "-O1", "-g", "-std=c++17", "-fPIC", f"--offload-arch={gbuild.ARCH}", "-ffp-contract=off", *san,
-                    "-fno-gpu-sanitize", "-c", os.path.join(gbuild.CSRC, "gvx_api.hip"), "-o", api_o], check=True)
-    others = [os.path.join(gbuild.CSRC, s.replace(".hip", ".o")) for s in gbuild.SOURCES if s != "gvx_api.hip"]
+    host = [s for s in gbuild.SOURCES if s.startswith("gvx_")]   # the C-ABI layer; every other source is kernels + launch wrappers
+    assert host == ["gvx_pack.hip", "gvx_decoder.hip", "gvx_api.hip"], host
+    api_o = []
+    for src in host:
+        api_o.append(os.path.join(out, src.replace(".hip", ".asan.o")))
+        subprocess.run([gbuild.HIPCC, "-O1", "-g", "-std=c++17", "-fPIC", f"--offload-arch={gbuild.ARCH}", "-ffp-contract=off", *san,
+                        "-fno-gpu-sanitize", "-c", os.path.join(gbuild.CSRC, src), "-o", api_o[-1]], check=True)
+    others = [os.path.join(gbuild.CSRC, s.replace(".hip", ".o")) for s in gbuild.SOURCES if s not in host]
     lib = os.path.join(out, "libgenvox_amd_asan.so")
-    subprocess.run([gbuild.HIPCC, "-shared", "-fPIC", f"--offload-arch={gbuild.ARCH}", *san, api_o, *others, "-L/opt/rocm/lib", "-lrocfft",
+    subprocess.run([gbuild.HIPCC, "-shared", "-fPIC", f"--offload-arch={gbuild.ARCH}", *san, *api_o, *others, "-L/opt/rocm/lib", "-lrocfft",
                     "-Wl,-rpath,/opt/rocm/lib", "-o", lib], check=True)
     drv = os.path.join(out, "driver")
     subprocess.run([CLANG, "-O1", "-g", "-std=c++17", *san, "-I", os.path.join(REPO, "include"),

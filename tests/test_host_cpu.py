@@ -252,3 +252,79 @@ def test_bench_output_dump_whole_and_sampled(tmp_path, monkeypatch):
         assert a.dtype == np.float32 and a.shape == (v.numel() // 4,)
         assert np.array_equal(a, np.load(tmp_path / "s2" / f"{k}.npy"))
         assert np.all(np.diff(a) >= 0) and np.isin(a, v.numpy().reshape(-1)).all()   # values = positions here: sorted, from the array
+
+
+# ---- the decoder loops' decision table: which path every shape takes, and what workspace it needs -------------------------------
+PLAN_TABLE = os.path.join(REPO, "tests", "golden", "decoder_plan_table.json")
+PLAN_BATCHES = (1, 2, 3, 16, 17, 32, 33, 64, 65)
+PLAN_LENGTHS = (1, 128, 129, 190, 256, 257)
+PLAN_STEPS = 37   # decoder steps of the workspace queries
+# (name, environment around gvx_model_create, setter called on the new handle)
+PLAN_HANDLES = (
+    ("default", {}, None),
+    ("set_persistent_attention_0", {}, "gvx_model_set_persistent_attention"),
+    ("set_resident_kernels_0", {}, "gvx_model_set_resident_kernels"),
+    ("GVX_TF_ROWS64=1", {"GVX_TF_ROWS64": "1"}, None),
+    ("GVX_AR_RESIDENT=1", {"GVX_AR_RESIDENT": "1"}, None),
+    ("GVX_TF_RESIDENT=0", {"GVX_TF_RESIDENT": "0"}, None),
+)
+PLAN_DIMS = {"default": {}, "prenet_128": {"prenet_dim": 128}}   # the second set: resident attention yes, resident autoregressive pair no
+
+
+def decoder_plan_table():
+    """{dims: {handle: {"B,L": [loop_kind, ar_loop_kind, resident, workspace_bytes, workspace_bytes_autoregressive]},
+    "rows_per_call": {L: rows}}} as the library answers it."""
+    lib = _lib.load()
+    knobs = sorted({k for _, env, _ in PLAN_HANDLES for k in env})
+    saved = {k: os.environ.pop(k, None) for k in knobs}
+    table = {}
+    try:
+        for dims_name, overrides in PLAN_DIMS.items():
+            d = dims_from_configs(Tacotron2Config(**overrides), AudioConfig(), TextConfig(n_tokens=40))
+            for name, env, setter in PLAN_HANDLES:
+                h = C.c_void_p()
+                os.environ.update(env)
+                try:
+                    assert lib.gvx_model_create(C.byref(d), C.byref(h)) == 0
+                finally:
+                    for k in env:
+                        del os.environ[k]
+                if setter:
+                    assert getattr(lib, setter)(h, 0) == 0
+                rows = {f"{B},{L}": [lib.gvx_teacher_forced_loop_kind(h, B, L), lib.gvx_autoregressive_loop_kind(h, B, L),
+                                     lib.gvx_teacher_forced_resident(h, B, L), lib.gvx_workspace_bytes(h, B, L, PLAN_STEPS),
+                                     lib.gvx_workspace_bytes_autoregressive(h, B, L, PLAN_STEPS)]
+                        for B in PLAN_BATCHES for L in PLAN_LENGTHS}
+                rows["rows_per_call"] = {str(L): lib.gvx_teacher_forced_rows_per_call(h, L) for L in PLAN_LENGTHS}
+                table.setdefault(dims_name, {})[name] = rows
+                lib.gvx_model_destroy(h)
+    finally:
+        os.environ.update({k: v for k, v in saved.items() if v is not None})
+    return table
+
+
+def test_decoder_plan_table_is_pinned():
+    """Every (layer sizes, handle setting, B, L) takes the path, and needs the workspace, that the committed table records:
+    a change of the path selection is a deliberate edit of tests/golden/decoder_plan_table.json
+    (python -c "from tests.test_host_cpu import write_decoder_plan_table as w; w()"), never a side effect."""
+    import json
+    with open(PLAN_TABLE) as f:
+        want = json.load(f)
+    got = decoder_plan_table()
+    assert set(got) == set(want)
+    for dims_name in want:
+        assert set(got[dims_name]) == set(want[dims_name])
+        for handle in want[dims_name]:
+            diff = {k: (v, got[dims_name][handle].get(k)) for k, v in want[dims_name][handle].items() if got[dims_name][handle].get(k) != v}
+            assert not diff, (dims_name, handle, diff)
+    # the table is not trivially constant: all three kinds of both loops and both chunk sizes occur in it
+    rows = [v for hs in want.values() for h in hs.values() for k, v in h.items() if k != "rows_per_call"]
+    assert {r[0] for r in rows} == {0, 1, 2} and {r[1] for r in rows} == {0, 1, 2}
+    assert {r for hs in want.values() for h in hs.values() for r in h["rows_per_call"].values()} == {32, 64}
+
+
+def write_decoder_plan_table():
+    import json
+    with open(PLAN_TABLE, "w") as f:
+        json.dump(decoder_plan_table(), f, indent=0, sort_keys=True)
+        f.write("\n")

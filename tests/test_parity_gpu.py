@@ -659,7 +659,7 @@ def test_autoregressive_resident_attention_equals_per_step(monkeypatch):
             assert torch.equal(a[k], b[k]), k
         return a
 
-    monkeypatch.setenv("GVX_AR_RESIDENT", "1")   # opt-in path (off by default: no faster, see gvx_api.hip)
+    monkeypatch.setenv("GVX_AR_RESIDENT", "1")   # opt-in path (off by default: no faster, see gvx_model::ar_resident, csrc/gvx_internal.h)
     # pick a threshold between the rows' gate values so that rows stop at different steps
     probe = run(1.0)
     g = torch.sigmoid(probe["gate_outputs"][:, :8]).cpu()

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Developer diagnostic (GPU box): batched autoregressive decode (64 rows = two lanes) run several times; where do runs differ?"""
+"""Developer diagnostic (GPU box): batched autoregressive decode (64 rows = two lanes) run several times; where do runs differ?
+ar_determinism.py [B [steps [out.pt]]]: out.pt receives the first run's outputs (to compare two builds byte for byte)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -26,3 +27,5 @@ for i in range(1, 5):
     print(f"run {i}: differs in {len(rows)} rows (first {rows[:6]}), first differing step {int(steps[0])}, max diff {float(d.max()):.3e}; "
           f"mel diff {float((runs[0]['mel_outputs'] - runs[i]['mel_outputs']).abs().max()):.3e}")
 m.check_status()
+if len(sys.argv) > 3:
+    torch.save({k: v.cpu() for k, v in runs[0].items() if torch.is_tensor(v)}, sys.argv[3])

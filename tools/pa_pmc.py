@@ -3,7 +3,7 @@
 attention kernel).  rocprofv3 --pmc serialises kernels, so the loop itself cannot run as it does in production (its
 hand-offs need both kernels at once: they time out - quickly here, GVX_HANDOFF_SPIN_LIMIT - and the call's outputs are
 NaN by design).  What IS meaningful under the counters: the 64 back-to-back replays of a mid-sequence launch that the
-kernel-timing pass issues after the loop (gvx_api.hip, decoder_tf_impl: the context counter already stands at its final
+kernel-timing pass issues after the loop (gvx_decoder.hip, tf_time_step_launches: the context counter already stands at its final
 value, nothing waits) - the same launches bench.py's roofline figure times.  tools/pmc_pa_summary.py keeps only those.
 
     rocprofv3 --kernel-trace --output-format csv --pmc <counters> -d gpurun_out/pmc_pa/<set> -- python3 tools/pa_pmc.py [B]
