@@ -9,7 +9,7 @@ C ABI (include/genvox_amd.h, vocoder section; rocFFT underneath).  There is no C
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Sequence, Tuple, Union
+from typing import List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import scipy.signal
@@ -57,6 +57,12 @@ def get_inverse_mel_filter(mel_basis: np.ndarray) -> np.ndarray:
     return np.linalg.pinv(mel_basis)
 
 
+class _RowLengths(NamedTuple):
+    """Frame counts of a ragged batch that passed AudioProcessor._check_lengths: host ints and the device int32 [B] the kernels read."""
+    host: List[int]
+    dev: torch.Tensor
+
+
 class AudioProcessor:
     TRIM = 500          # samples dropped at both ends (core/processors.py:93)
     LOWPASS_HZ = 6000   # utils/audio/base.py:168-169
@@ -95,8 +101,9 @@ class AudioProcessor:
                                 torch.from_numpy(np.ascontiguousarray(self.inverse_mel_basis, dtype=np.float32)).to(self.device))
         return lib
 
-    def _workspace(self, B: int, T: int) -> torch.Tensor:
-        need = _lib.load().gvx_gl_workspace_bytes(self._plan, B, T, self.config.n_mels)
+    def _workspace(self, B: int, T: int, ragged: bool = False) -> torch.Tensor:
+        lib = _lib.load()
+        need = (lib.gvx_gl_workspace_bytes_ragged if ragged else lib.gvx_gl_workspace_bytes)(self._plan, B, T, self.config.n_mels)
         if need == 0:
             raise _lib.GvxError("could not plan the vocoder workspace: " + _lib.load().gvx_last_error().decode())
         if self._ws is None or self._ws.numel() < need:
@@ -105,6 +112,29 @@ class AudioProcessor:
 
     def _stream(self) -> int:
         return torch.cuda.current_stream(self.device).cuda_stream
+
+    def row_samples(self, frame_lengths: Sequence[int], trimmed: bool = True) -> List[int]:
+        """Samples of rows of the given frame counts: n_fft + (T_b-1)*hop, less the TRIM samples `finalize` drops at both ends."""
+        c = self.config
+        return [c.filter_length + (int(t) - 1) * c.hop_length - (2 * self.TRIM if trimmed else 0) for t in frame_lengths]
+
+    def _check_lengths(self, frame_lengths, B: int, T: int, trimmed: bool) -> _RowLengths:
+        """Validate per-row frame counts on the host (nothing is launched for a bad batch): (host list, device int32 [B])."""
+        if isinstance(frame_lengths, _RowLengths):   # checked by the caller (convert_mel2wav_batch), with trimmed=True
+            return frame_lengths
+        host = [int(v) for v in (frame_lengths.tolist() if isinstance(frame_lengths, (torch.Tensor, np.ndarray)) else frame_lengths)]
+        if len(host) != B:
+            raise ValueError(f"{len(host)} frame lengths for a batch of {B} rows")
+        for b, t in enumerate(host):
+            if not 1 <= t <= T:
+                raise ValueError(f"frame length {t} of row {b} is outside [1, {T}]")
+        if trimmed:
+            for b, n in enumerate(self.row_samples(host)):
+                if n <= 0:
+                    raise ValueError(f"row {b}: {host[b]} frames are {n + 2 * self.TRIM} samples, too short to drop {self.TRIM} at both ends")
+        if isinstance(frame_lengths, torch.Tensor) and frame_lengths.device == self.device and frame_lengths.dtype == torch.int32:
+            return _RowLengths(host, frame_lengths.contiguous())
+        return _RowLengths(host, torch.tensor(host, dtype=torch.int32, device=self.device))
 
     # ------------------------------------------------------------------ device stages (batched, reference layouts)
     def stft(self, signal: torch.Tensor) -> torch.Tensor:
@@ -146,30 +176,54 @@ class AudioProcessor:
         return out
 
     def griffin_lim(self, mag: torch.Tensor, n_iter: int = 32, momentum: float = 0.99, want_phase: bool = True,
-                    want_wav: bool = True) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
-        """[B, bins, T] magnitude -> (phase [B, bins, T], waveform [B, n]) (reference griffin_lim + final istft)."""
+                    want_wav: bool = True, frame_lengths=None) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+        """[B, bins, T] magnitude -> (phase [B, bins, T], waveform [B, n]) (reference griffin_lim + final istft).
+
+        ``frame_lengths`` ([B] ints, tensor or sequence, each in [1, T]): row b has only its first T_b frames; its phase and
+        waveform up to n_fft + (T_b-1)*hop samples equal a call on ``mag[b:b+1, :, :T_b]`` bit for bit, whatever the padded
+        frames hold, and are 0 behind."""
         lib = self._ensure()
         m = mag.to(self.device, torch.float32).contiguous()
         B, bins, T = m.shape
         c = self.config
+        lens = self._check_lengths(frame_lengths, B, T, trimmed=False).dev if frame_lengths is not None else None
         phase = torch.empty_like(m) if want_phase else None
         wav = torch.empty(B, c.filter_length + (T - 1) * c.hop_length, device=self.device) if want_wav else None
+        if lens is not None:
+            ws = self._workspace(B, T, ragged=True)
+            _lib.check(lib.gvx_griffin_lim_ragged(self._plan, m.data_ptr(), self._dev_consts[0].data_ptr(), B, T, lens.data_ptr(), n_iter,
+                                                  float(momentum), phase.data_ptr() if want_phase else None,
+                                                  wav.data_ptr() if want_wav else None, ws.data_ptr(), ws.numel(), self._stream()))
+            return phase, wav
         ws = self._workspace(B, T)
         _lib.check(lib.gvx_griffin_lim(self._plan, m.data_ptr(), self._dev_consts[0].data_ptr(), B, T, n_iter, float(momentum),
                                        phase.data_ptr() if want_phase else None, wav.data_ptr() if want_wav else None,
                                        ws.data_ptr(), ws.numel(), self._stream()))
         return phase, wav
 
-    def finalize(self, wav: torch.Tensor) -> torch.Tensor:
-        """clip / trim 500 / peak-normalise / Butterworth low-pass -> float64 [B, n - 1000] (core/processors.py:91-95)."""
+    def finalize(self, wav: torch.Tensor, frame_lengths=None) -> torch.Tensor:
+        """clip / trim 500 / peak-normalise / Butterworth low-pass -> float64 [B, n - 1000] (core/processors.py:91-95).
+
+        ``frame_lengths``: row b is the signal of T_b frames (n_fft + (T_b-1)*hop samples at the start of the padded row); it is
+        trimmed, normalised and filtered as a signal of that length and the result is 0 behind its n_b - 1000 samples."""
         lib = self._ensure()
         y = wav.to(self.device, torch.float32).contiguous()
         B, n = y.shape
+        c = self.config
+        lens = None
+        if frame_lengths is not None:
+            if n < c.filter_length or (n - c.filter_length) % c.hop_length:
+                raise ValueError(f"{n} samples per row are not n_fft + (T-1)*hop for any frame count T")
+            lens = self._check_lengths(frame_lengths, B, (n - c.filter_length) // c.hop_length + 1, trimmed=True).dev
         out = torch.empty(B, n - 2 * self.TRIM, dtype=torch.float64, device=self.device)
         scratch = torch.empty(B, dtype=torch.int32, device=self.device)
         nb = len(self._b)
         b = (C.c_double * nb)(*[float(v) for v in self._b])
         a = (C.c_double * nb)(*[float(v) for v in self._a])
+        if lens is not None:
+            _lib.check(lib.gvx_wav_finalize_ragged(y.data_ptr(), B, n, lens.data_ptr(), c.filter_length, c.hop_length, self.TRIM, b, a,
+                                                   nb - 1, out.data_ptr(), scratch.data_ptr(), self._stream()))
+            return out
         _lib.check(lib.gvx_wav_finalize(y.data_ptr(), B, n, self.TRIM, b, a, nb - 1, out.data_ptr(), scratch.data_ptr(), self._stream()))
         return out
 
@@ -201,8 +255,19 @@ class AudioProcessor:
         np.save(output_path, mel[0].cpu().numpy())
 
     # ------------------------------------------------------------------ reference surface
-    def convert_mel2wav_batch(self, mels: torch.Tensor, n_iter: int = 32) -> torch.Tensor:
-        """[B, n_mels, T] mel (dB) -> float64 waveforms [B, n_fft + (T-1)*hop - 1000] on the device."""
+    def convert_mel2wav_batch(self, mels: torch.Tensor, n_iter: int = 32, mel_lengths=None):
+        """[B, n_mels, T] mel (dB) -> float64 waveforms [B, n_fft + (T-1)*hop - 1000] on the device.
+
+        With ``mel_lengths`` ([B] frame counts in [1, T]) the rows are vocoded at their own lengths in the same launches and the
+        return value is ``(waveforms, sample_counts)``: row b is valid up to ``sample_counts[b] = n_fft + (T_b-1)*hop - 1000``
+        samples - bit for bit the result of a call on ``mels[b:b+1, :, :T_b]`` - and 0 behind.  The padded frames of ``mels`` may
+        hold anything.  Bad lengths raise ValueError before anything is launched."""
+        if mel_lengths is not None:
+            B, _, T = mels.shape
+            lens = self._check_lengths(mel_lengths, B, T, trimmed=True)
+            mag = self.mel_to_magnitude(mels)   # frame-wise: the padded frames' magnitudes are simply never used
+            _, wav = self.griffin_lim(mag, n_iter=n_iter, want_phase=False, frame_lengths=lens)
+            return self.finalize(wav, frame_lengths=lens), self.row_samples(lens.host)
         mag = self.mel_to_magnitude(mels)
         _, wav = self.griffin_lim(mag, n_iter=n_iter, want_phase=False)
         return self.finalize(wav)

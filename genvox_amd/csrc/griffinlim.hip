@@ -93,10 +93,11 @@ int get_plans(gvx_gl_plan* p, long batch, FftPair** out) {
 }
 
 struct GlWs {  // byte offsets
-    size_t mag, ang, reb0, reb1, fr, y, wss, amp, fft_work, total;
+    size_t mag, ang, reb0, reb1, fr, y, wss, amp, fft_work, wss_tail, total;
 };
 
-GlWs gl_plan_ws(const gvx_gl_plan* p, int B, int T, int M, size_t fft_work) {
+// ragged: room for the per-row tail of the window sum of squares behind everything else (the uniform layout is a prefix)
+GlWs gl_plan_ws(const gvx_gl_plan* p, int B, int T, int M, size_t fft_work, bool ragged = false) {
     GlWs w{};
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
@@ -111,6 +112,7 @@ GlWs gl_plan_ws(const gvx_gl_plan* p, int B, int T, int M, size_t fft_work) {
     w.wss = take(n * sizeof(float));
     w.amp = take(frames * (size_t)(M > 0 ? M : 1) * sizeof(float));
     w.fft_work = take(fft_work);
+    w.wss_tail = ragged ? take((size_t)B * (p->n_fft - p->hop) * sizeof(float)) : 0;
     w.total = off;
     return w;
 }
@@ -181,20 +183,62 @@ __global__ void wss_kernel(const float* win, float* wss, int n_fft, int hop, int
     wss[i] = s;
 }
 
+// ---- ragged batches: row b has T_b = frame_lengths[b] frames (clamped to [0, T], never trusted) and n_b = n_fft + (T_b-1)*hop
+// samples inside buffers that keep the strides of the padded T.  Kernels that know about lengths are the RAGGED = true
+// instantiation of the uniform kernel's body; RAGGED = false never touches `lens` and compiles to the uniform kernel.
+__device__ __forceinline__ int row_frames(const int32_t* __restrict__ lens, int b, int T) {
+    const int v = lens[b];
+    return v < 0 ? 0 : (v > T ? T : v);
+}
+__device__ __forceinline__ long row_samples(const int32_t* __restrict__ lens, int b, int n_fft, int hop, long n_cap) {
+    const long v = lens[b];
+    if (v < 1) return 0;
+    const long nb = (long)n_fft + (v - 1) * hop;
+    return nb < n_cap ? nb : n_cap;
+}
+
+// The window sum of squares of a row of T_b frames equals the padded table wss[i] for i < T_b*hop (there only the clip at frame
+// 0 matters); its last n_fft - hop samples, where the frames t >= T_b of the padded table are missing, come from this per-row
+// table: tail[b][q] = wss of sample T_b*hop + q at T = T_b, frames added in ascending order exactly as wss_kernel adds them
+// (rows shorter than the overlap, whose head and tail meet, included: the clip at frame 0 is the same expression).
+__global__ void wss_tail_kernel(const float* win, const int32_t* lens, float* tail, int n_fft, int hop, int T) {
+    const int b = blockIdx.y;
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n_fft - hop) return;
+    const int Tb = row_frames(lens, b, T);
+    const long i = (long)Tb * hop + q;
+    long t_lo = (i - n_fft + hop) / hop;
+    if (i - n_fft + 1 <= 0) t_lo = 0;
+    float s = 0.f;
+    for (long t = t_lo; t <= Tb - 1; ++t) {
+        const float w = win[i - t * hop];
+        s += w * w;
+    }
+    tail[(long)b * (n_fft - hop) + q] = s;
+}
+
 // angles = (mag, 0)   (utils/audio/base.py:151-154)
 __global__ void gl_init_kernel(const float* mag, float2* ang, long n) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) ang[i] = make_float2(mag[i], 0.f);
 }
 
 // y[b][i] = (sum_t win[i - t*hop] * fr[b][t][i - t*hop] / n_fft) / wss[i]      (utils/audio/base.py:71-88)
-__global__ void gl_ola_kernel(const float* fr, const float* win, const float* wss, float* y, int n_fft, int hop, int T, long n) {
+// RAGGED: frames t >= T_b are skipped, samples i >= n_b are left unwritten, the divisor of the last n_fft - hop samples is the row's
+template <bool RAGGED>
+__global__ void gl_ola_kernel(const float* fr, const float* win, const float* wss, float* y, int n_fft, int hop, int T, long n,
+                              const int32_t* lens, const float* wss_tail) {
     const int b = blockIdx.y;
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    int Tb = T;
+    if (RAGGED) {
+        Tb = row_frames(lens, b, T);
+        if (Tb == 0 || i >= (long)n_fft + (long)(Tb - 1) * hop) return;
+    }
     long t_lo = (i - n_fft + hop) / hop;
     if (i - n_fft + 1 <= 0) t_lo = 0;
     long t_hi = i / hop;
-    if (t_hi > T - 1) t_hi = T - 1;
+    if (t_hi > Tb - 1) t_hi = Tb - 1;
     const float inv_n = 1.f / (float)n_fft;
     const float* frb = fr + (long)b * T * n_fft;
     float s = 0.f;
@@ -202,7 +246,7 @@ __global__ void gl_ola_kernel(const float* fr, const float* win, const float* ws
         const long k = i - t * hop;
         s += win[k] * (frb[t * n_fft + k] * inv_n);
     }
-    const float w = wss[i];
+    const float w = (RAGGED && i >= (long)Tb * hop) ? wss_tail[(long)b * (n_fft - hop) + (i - (long)Tb * hop)] : wss[i];
     y[(long)b * n + i] = w > 1.17549435e-38f ? s / w : s;
 }
 
@@ -240,14 +284,39 @@ __global__ void gl_update_kernel(const float2* reb, const float2* prev, const fl
 }
 
 // phase = angle(angles); spec = mag * (cos phase + i sin phase)     (base.py:162, :54-56; core/processors.py:89-90)
-__global__ void gl_final_kernel(const float2* ang, const float* mag, float2* spec, float* phase_t, long n) {
+// RAGGED: one grid row per utterance, n = T * bins elements each (frame-major, so a row's valid frames are a prefix);
+// phase and final spectrum of frames t >= T_b are 0
+template <bool RAGGED>
+__global__ void gl_final_kernel(const float2* ang, const float* mag, float2* spec, float* phase_t, long n, int bins, int T,
+                                const int32_t* lens) {
+    long n_valid = n;
+    if (RAGGED) {
+        const long off = (long)blockIdx.y * n;
+        ang += off; mag += off;
+        if (spec) spec += off;
+        if (phase_t) phase_t += off;
+        n_valid = (long)row_frames(lens, blockIdx.y, T) * bins;
+    }
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        if (RAGGED && i >= n_valid) {
+            if (phase_t) phase_t[i] = 0.f;
+            if (spec) spec[i] = make_float2(0.f, 0.f);
+            continue;
+        }
         const float2 a = ang[i];
         const float ph = atan2f(a.y, a.x);
         const float m = mag[i];
         if (phase_t) phase_t[i] = ph;
         if (spec) spec[i] = make_float2(m * cosf(ph), m * sinf(ph));
     }
+}
+
+// ragged result rows: dst[b][i] = src[b][i] for i < n_b, 0 behind (src is not valid there)
+__global__ void copy_rows_ragged_kernel(const float* src, float* dst, long n, int n_fft, int hop, const int32_t* lens) {
+    const int b = blockIdx.y;
+    const long nb = row_samples(lens, b, n_fft, hop, n);
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
+        dst[(long)b * n + i] = i < nb ? src[(long)b * n + i] : 0.f;
 }
 
 // |spec| of a frame-major complex spectrum into rows padded to kp floats (kp % 4 == 0, pad = 0) for the GEMM
@@ -294,9 +363,12 @@ __global__ void amp_to_db_transpose_kernel(const float* mel_t, float* mel_db, in
 
 // clip spurious samples, trim, peak, normalise to float32, IIR low-pass in float64 (core/processors.py:91-95,
 // utils/audio/base.py:20-22, :164-169; scipy.signal.lfilter = direct form II transposed)
-__global__ void wav_peak_kernel(const float* y, long n, int trim, unsigned int* peak_bits) {
+// RAGGED: n is the row stride; row b holds n_b = n_fft + (T_b-1)*hop samples (row_samples) and everything - trim at both ends, peak,
+// filter, the chunks' warm-up positions - is counted within them, as in a call on that row alone; out is 0 past n_b - 2*trim
+template <bool RAGGED>
+__global__ void wav_peak_kernel(const float* y, long n, int trim, unsigned int* peak_bits, const int32_t* lens, int n_fft, int hop) {
     const int b = blockIdx.y;
-    const long n_out = n - 2L * trim;
+    const long n_out = (RAGGED ? row_samples(lens, b, n_fft, hop, n) : n) - 2L * trim;
     float m = 0.f;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n_out; i += (long)gridDim.x * blockDim.x) {
         float v = y[(long)b * n + trim + i];
@@ -309,14 +381,22 @@ __global__ void wav_peak_kernel(const float* y, long n, int trim, unsigned int* 
 
 struct IirCoef { double b[8], a[8]; int order; };
 
-__global__ void wav_filter_kernel(const float* y, long n, int trim, const unsigned int* peak_bits, IirCoef c, double* out, int B) {
+template <bool RAGGED>
+__global__ void wav_filter_kernel(const float* y, long n, int trim, const unsigned int* peak_bits, IirCoef c, double* out, int B,
+                                  const int32_t* lens, int n_fft, int hop) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    const long n_out = n - 2L * trim;
+    const long n_stride = n - 2L * trim;
+    long n_out = n_stride;
+    if (RAGGED) {
+        n_out = row_samples(lens, b, n_fft, hop, n) - 2L * trim;
+        if (n_out < 0) n_out = 0;
+        for (long i = n_out; i < n_stride; ++i) out[(long)b * n_stride + i] = 0.0;
+    }
     const float peak = __uint_as_float(peak_bits[b]);
     double z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const float* yb = y + (long)b * n + trim;
-    double* ob = out + (long)b * n_out;
+    double* ob = out + (long)b * n_stride;
     // the recurrence is strictly sequential per utterance; the loads are not: fetch the next 16 samples while the
     // current 16 go through the filter (one thread = one utterance, a wave = 64 utterances in lock step)
     constexpr int CH = 16;
@@ -350,18 +430,27 @@ __global__ void wav_filter_kernel(const float* y, long n, int trim, const unsign
 // so that this is below 1e-18 - far under a float64 ulp of the output - so the warm-up samples are simply filtered and
 // discarded (overlap-discard).  One thread = one chunk; no cross-chunk exchange, no extra buffers; a row's result does
 // not depend on the batch it is in.  Reference: scipy.signal.lfilter in butter_lowpass_filter (utils/audio/base.py:164-166).
+template <bool RAGGED>
 __global__ void wav_filter_chunked_kernel(const float* y, long n, int trim, const unsigned int* peak_bits, IirCoef c, double* out,
-                                          int chunk, int warm, int nch) {
+                                          int chunk, int warm, int nch, const int32_t* lens, int n_fft, int hop) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     const int b = blockIdx.y;
     if (k >= nch) return;
-    const long n_out = n - 2L * trim;
+    const long n_stride = n - 2L * trim;
+    long n_out = n_stride;
+    const long i_begin = (long)k * chunk;
+    double* ob = out + (long)b * n_stride;
+    if (RAGGED) {
+        n_out = row_samples(lens, b, n_fft, hop, n) - 2L * trim;
+        if (n_out < 0) n_out = 0;
+        for (long i = max(i_begin, n_out); i < min(n_stride, i_begin + chunk); ++i) ob[i] = 0.0;   // the chunk's share of the padding
+        if (i_begin >= n_out) return;
+    }
     const float peak = __uint_as_float(peak_bits[b]);
-    const long i_begin = (long)k * chunk, i_end = min(n_out, i_begin + chunk);
+    const long i_end = min(n_out, i_begin + chunk);
     const long i_start = max(0L, i_begin - warm);
     double z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const float* yb = y + (long)b * n + trim;
-    double* ob = out + (long)b * n_out;
     constexpr int CH = 16;
     float cur[CH], nxt[CH];
 #pragma unroll
@@ -511,15 +600,24 @@ constexpr int GLI_TAB_WIN = FN + 520;          // LDS tables of gl_iteration_ker
 constexpr int GLI_TAB = GLI_TAB_WIN + 512;
 
 // S [B*T][513] (frame-major) -> y [B][(T+3)*256]: y[i] = (sum_t win[k] * (irfft(S_t)[k] / 1024)) / wss[i], k = i - 256 t
+// RAGGED: only the frames t < T_b of row b exist; its samples i < (T_b+3)*256 are written (the last three hop blocks divided by the
+// row's own wss_tail [B][768]), the rest of the padded row is left as it was; a workgroup behind the row's end leaves at once
+template <bool RAGGED>
 __global__ __launch_bounds__(GLI_FRAMES * 64) void gl_inverse_ola_kernel(const float2* __restrict__ spec, const float* __restrict__ win,
                                                                          const float* __restrict__ wss, const float2* __restrict__ tw,
-                                                                         float* __restrict__ y, int T) {
+                                                                         float* __restrict__ y, int T, const int32_t* __restrict__ lens,
+                                                                         const float* __restrict__ wss_tail) {
     extern __shared__ __attribute__((aligned(16))) float2 fsm[];   // [GLI_FRAMES][FPAD] float2; reused as [GLI_FRAMES][1024] float
     const int b = blockIdx.y, h0 = blockIdx.x * GLI_BLOCKS;
+    int Tb = T;
+    if (RAGGED) {
+        Tb = row_frames(lens, b, T);
+        if (Tb == 0 || h0 >= Tb + 3) return;   // uniform over the workgroup, before any barrier
+    }
     const int tid = threadIdx.x, j = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int t = h0 - 3 + wave;
-    const bool valid = t >= 0 && t < T;       // wave-uniform; every wave still joins the barriers
+    const bool valid = t >= 0 && t < Tb;      // wave-uniform; every wave still joins the barriers
     float2* buf = fsm + wave * FPAD;
     float2 v[8];
     if (valid) {
@@ -556,19 +654,20 @@ __global__ __launch_bounds__(GLI_FRAMES * 64) void gl_inverse_ola_kernel(const f
     __syncthreads();
     // overlap-add of hop blocks h0 .. h0+12 (ascending frame order), divide by the window sum of squares
     const long n = (long)(T + 3) * 256;
+    const long n_row = RAGGED ? (long)(Tb + 3) * 256 : n;
     const float* fall = reinterpret_cast<const float*>(fsm);
     for (int idx = tid; idx < GLI_BLOCKS * 256; idx += GLI_FRAMES * 64) {
         const int hb = idx >> 8, q = idx & 255;
         const int h = h0 + hb;
         const long i = (long)h * 256 + q;
-        if (i >= n) break;
+        if (i >= n_row) break;
         float sacc = 0.f;
 #pragma unroll
         for (int d = 3; d >= 0; --d) {           // frames t = h-3 .. h  ->  waves hb .. hb+3
             const int tt = h - d;
-            if (tt >= 0 && tt < T) sacc += fall[(long)(hb + 3 - d) * (FPAD * 2) + d * 256 + q];
+            if (tt >= 0 && tt < Tb) sacc += fall[(long)(hb + 3 - d) * (FPAD * 2) + d * 256 + q];
         }
-        const float w = wss[i];
+        const float w = (RAGGED && h >= Tb) ? wss_tail[(long)b * 768 + (h - Tb) * 256 + q] : wss[i];
         y[(long)b * n + i] = w > 1.17549435e-38f ? sacc * __builtin_amdgcn_rcpf(w) : sacc;   // v_rcp_f32: 1 ulp
     }
 }
@@ -585,16 +684,25 @@ __global__ __launch_bounds__(GLI_FRAMES * 64) void gl_inverse_ola_kernel(const f
 // the workgroup (it writes their tprev / spectrum), the halo frames h0-3 .. h0-1 are recomputed from y_in and tprev_in, which
 // is why both are double buffered (a neighbour may still be reading what this workgroup would overwrite).  FPW = 2 (32 frames,
 // 29 blocks, 144 KB of rows + 12 KB of tables in LDS) recomputes 10 % of the frames instead of 23 %.
-template <int FPW>   // frames per wave: a workgroup covers 16 FPW frames = 16 FPW - 3 hop blocks (halo share 3/16 or 3/32)
+// RAGGED: as in gl_inverse_ola_kernel - frames t >= T_b are neither transformed nor added, samples of y_out past (T_b+3)*256 stay
+// unwritten (no valid frame reads them), and a workgroup whose hop blocks all lie behind the row's end returns before it loads the
+// tables, so the padding of a batch with spread lengths costs a launch slot and nothing else.
+template <int FPW, bool RAGGED>   // frames per wave: a workgroup covers 16 FPW frames = 16 FPW - 3 hop blocks (halo share 3/16 or 3/32)
 __global__ __launch_bounds__(GLI_FRAMES * 64) void gl_iteration_kernel(const float* __restrict__ y_in, float* __restrict__ y_out,
                                                                        const float* __restrict__ win_g, const float* __restrict__ wss,
                                                                        const float2* __restrict__ tw_g, const float* __restrict__ mag,
                                                                        const float2* __restrict__ tprev_in, float2* __restrict__ tprev_out,
                                                                        float2* __restrict__ spec_out, float c, int first, int do_inverse,
-                                                                       int T) {
+                                                                       int T, const int32_t* __restrict__ lens,
+                                                                       const float* __restrict__ wss_tail) {
     constexpr int NFR = GLI_FRAMES * FPW, NBL = NFR - 3;
     extern __shared__ __attribute__((aligned(16))) float2 fsm[];   // [NFR][FPAD] float2; reused as [NFR][1024+] float; then the tables
     const int b = blockIdx.y, h0 = blockIdx.x * NBL;
+    int Tb = T;
+    if (RAGGED) {
+        Tb = row_frames(lens, b, T);
+        if (Tb == 0 || h0 >= Tb + 3) return;   // uniform over the workgroup, before the tables and any barrier
+    }
     const int tid = threadIdx.x, jj = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const long n = (long)(T + 3) * 256;
@@ -611,7 +719,7 @@ __global__ __launch_bounds__(GLI_FRAMES * 64) void gl_iteration_kernel(const flo
     for (int f = 0; f < FPW; ++f) {
         const int slot = wave + GLI_FRAMES * f;   // the wave's frames are 16 apart so that all waves stay busy in the last group
         const int t = h0 - 3 + slot;
-        if (t < 0 || t >= T) continue;            // wave-uniform; the barrier below is outside the loop
+        if (t < 0 || t >= Tb) continue;           // wave-uniform; the barrier below is outside the loop
         const bool owner = slot >= 3;             // frames h0 .. h0+NBL-1
         float2* buf = fsm + slot * FPAD;
         float2 v[8];
@@ -718,18 +826,19 @@ __global__ __launch_bounds__(GLI_FRAMES * 64) void gl_iteration_kernel(const flo
     __syncthreads();
     // overlap-add of hop blocks h0 .. h0+NBL-1 (ascending frame order), divide by the window sum of squares
     const float* fall = reinterpret_cast<const float*>(fsm);
+    const long n_row = RAGGED ? (long)(Tb + 3) * 256 : n;
     for (int idx = tid; idx < NBL * 256; idx += GLI_FRAMES * 64) {
         const int hb = idx >> 8, q = idx & 255;
         const int h = h0 + hb;
         const long i = (long)h * 256 + q;
-        if (i >= n) break;
+        if (i >= n_row) break;
         float sacc = 0.f;
 #pragma unroll
         for (int d = 3; d >= 0; --d) {           // frames t = h-3 .. h  ->  rows hb .. hb+3
             const int tt = h - d;
-            if (tt >= 0 && tt < T) sacc += fall[(long)(hb + 3 - d) * (FPAD * 2) + d * 256 + q];
+            if (tt >= 0 && tt < Tb) sacc += fall[(long)(hb + 3 - d) * (FPAD * 2) + d * 256 + q];
         }
-        const float w = wss[i];
+        const float w = (RAGGED && h >= Tb) ? wss_tail[(long)b * 768 + (h - Tb) * 256 + q] : wss[i];
         y_out[(long)b * n + i] = w > 1.17549435e-38f ? sacc * __builtin_amdgcn_rcpf(w) : sacc;
     }
 }
@@ -880,12 +989,19 @@ inline int blocks_for(long n, int per = 256, int cap = 8192) {
 }
 
 // frame-major spectrum -> signal: C2R + overlap-add
-int istft_frames(gvx_gl_plan* p, FftPair* fp, float2* spec_t, const float* win, int B, int T, void* ws, const GlWs& w, hipStream_t s) {
+// (lens: per-row frame counts of a ragged batch, or null - every frame is transformed either way, the overlap-add skips the padded ones)
+int istft_frames(gvx_gl_plan* p, FftPair* fp, float2* spec_t, const float* win, int B, int T, void* ws, const GlWs& w, hipStream_t s,
+                 const int32_t* lens = nullptr) {
     const long n = (long)p->n_fft + (long)(T - 1) * p->hop;
     int rc = run_fft(p, fp->c2r, spec_t, wsp<float>(ws, w.fr), wsp<char>(ws, w.fft_work), fp->work_bytes, s);
     if (rc != GVX_OK) return rc;
-    gl_ola_kernel<<<dim3((unsigned)((n + 255) / 256), B), 256, 0, s>>>(wsp<float>(ws, w.fr), win, wsp<float>(ws, w.wss), wsp<float>(ws, w.y),
-                                                                     p->n_fft, p->hop, T, n);
+    const dim3 grid((unsigned)((n + 255) / 256), B);
+    if (lens)
+        gl_ola_kernel<true><<<grid, 256, 0, s>>>(wsp<float>(ws, w.fr), win, wsp<float>(ws, w.wss), wsp<float>(ws, w.y), p->n_fft, p->hop, T, n,
+                                                 lens, wsp<float>(ws, w.wss_tail));
+    else
+        gl_ola_kernel<false><<<grid, 256, 0, s>>>(wsp<float>(ws, w.fr), win, wsp<float>(ws, w.wss), wsp<float>(ws, w.y), p->n_fft, p->hop, T, n,
+                                                  nullptr, nullptr);
     GL_HIP(hipGetLastError());
     return GVX_OK;
 }
@@ -929,12 +1045,14 @@ int gvx_gl_plan_create(int n_fft, int hop, gvx_gl_plan** out) {
             delete p;
             return gl_fail(GVX_ERR_HIP, "twiddle table allocation failed");
         }
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(gl_inverse_ola_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                GLI_FRAMES * FPAD * (int)sizeof(float2)) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(gl_iteration_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (GLI_FRAMES * FPAD + GLI_TAB) * (int)sizeof(float2)) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(gl_iteration_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (2 * GLI_FRAMES * FPAD + GLI_TAB) * (int)sizeof(float2)) != hipSuccess) {
+        const int lds_inv = GLI_FRAMES * FPAD * (int)sizeof(float2), lds_it1 = (GLI_FRAMES * FPAD + GLI_TAB) * (int)sizeof(float2),
+                  lds_it2 = (2 * GLI_FRAMES * FPAD + GLI_TAB) * (int)sizeof(float2);
+        auto lds = [](auto* kernel, int bytes) {
+            return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
+        };
+        if (!lds(gl_inverse_ola_kernel<false>, lds_inv) || !lds(gl_inverse_ola_kernel<true>, lds_inv) ||
+            !lds(gl_iteration_kernel<1, false>, lds_it1) || !lds(gl_iteration_kernel<1, true>, lds_it1) ||
+            !lds(gl_iteration_kernel<2, false>, lds_it2) || !lds(gl_iteration_kernel<2, true>, lds_it2)) {
             delete p;
             return gl_fail(GVX_ERR_HIP, "hipFuncSetAttribute failed");
         }
@@ -1027,17 +1145,29 @@ int gvx_mel_to_magnitude(gvx_gl_plan* p, const float* mel_db, const float* inv_b
     return GVX_OK;
 }
 
-int gvx_griffin_lim(gvx_gl_plan* p, const float* mag, const float* window, int B, int T, int n_iter, float momentum, float* phase_out,
-                    float* wav_out, void* ws, size_t ws_bytes, void* stream) {
+}  // extern "C"
+
+namespace {
+
+// gvx_griffin_lim (lens == nullptr: every launch is the uniform one, unchanged) and gvx_griffin_lim_ragged
+int griffin_lim_impl(gvx_gl_plan* p, const float* mag, const float* window, int B, int T, const int32_t* lens, int n_iter, float momentum,
+                     float* phase_out, float* wav_out, void* ws, size_t ws_bytes, void* stream) {
     if (!p || !mag || !window) return gl_fail(GVX_ERR_INVALID_ARG, "null argument");
     if (n_iter < 0) return gl_fail(GVX_ERR_INVALID_ARG, "n_iter must be >= 0");
+    if (B < 1 || T < 1) return gl_fail(GVX_ERR_INVALID_ARG, "B and T must be >= 1");
     FftPair* fp = nullptr;
     int rc = get_plans(p, (long)B * T, &fp);
     if (rc != GVX_OK) return rc;
-    const GlWs w = gl_plan_ws(p, B, T, 0, fp->work_bytes);
+    const GlWs w = gl_plan_ws(p, B, T, 0, fp->work_bytes, lens != nullptr);
     rc = check_gl(p, B, T, ws, ws_bytes, w.total);
     if (rc != GVX_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
+    const float* tail = lens ? wsp<float>(ws, w.wss_tail) : nullptr;
+    if (lens && p->n_fft > p->hop) {
+        wss_tail_kernel<<<dim3((unsigned)((p->n_fft - p->hop + 255) / 256), B), 256, 0, s>>>(window, lens, wsp<float>(ws, w.wss_tail), p->n_fft,
+                                                                                           p->hop, T);
+        GL_HIP(hipGetLastError());
+    }
     const long n = (long)p->n_fft + (long)(T - 1) * p->hop;
     const long nbin = (long)B * T * p->bins;
     float* mag_t = wsp<float>(ws, w.mag);
@@ -1051,12 +1181,18 @@ int gvx_griffin_lim(gvx_gl_plan* p, const float* mag, const float* window, int B
     const float c = momentum / (1.f + momentum);
     const bool fused = p->tw != nullptr && !getenv_flag("GVX_GL_ROCFFT");
     auto inverse_ola = [&](const float2* spec) -> int {   // y = istft(spec), fused path
-        gl_inverse_ola_kernel<<<dim3((unsigned)((T + 3 + GLI_BLOCKS - 1) / GLI_BLOCKS), B), GLI_FRAMES * 64,
-                                GLI_FRAMES * FPAD * sizeof(float2), s>>>(spec, window, wsp<float>(ws, w.wss), p->tw, wsp<float>(ws, w.y), T);
+        const dim3 grid((unsigned)((T + 3 + GLI_BLOCKS - 1) / GLI_BLOCKS), B);
+        if (lens)
+            gl_inverse_ola_kernel<true><<<grid, GLI_FRAMES * 64, GLI_FRAMES * FPAD * sizeof(float2), s>>>(
+                spec, window, wsp<float>(ws, w.wss), p->tw, wsp<float>(ws, w.y), T, lens, tail);
+        else
+            gl_inverse_ola_kernel<false><<<grid, GLI_FRAMES * 64, GLI_FRAMES * FPAD * sizeof(float2), s>>>(
+                spec, window, wsp<float>(ws, w.wss), p->tw, wsp<float>(ws, w.y), T, nullptr, nullptr);
         GL_HIP(hipGetLastError());
         return GVX_OK;
     };
-    if (fused && n_iter > 0 && !getenv_flag("GVX_GL_TWO_KERNELS")) {
+    // (a ragged call always takes the one-launch iteration: the two-launch A/B variant walks all B*T frames)
+    if (fused && n_iter > 0 && (lens || !getenv_flag("GVX_GL_TWO_KERNELS"))) {
         // one launch per iteration: signal -> rebuilt -> update -> new spectrum -> its signal (gl_iteration_kernel); the signal
         // and tprev ping-pong between two buffers each (the framed-signal region of the rocFFT pipeline serves as the second y)
         float* ybuf[2] = {wsp<float>(ws, w.y), wsp<float>(ws, w.fr)};
@@ -1068,14 +1204,18 @@ int gvx_griffin_lim(gvx_gl_plan* p, const float* mag, const float* window, int B
         const dim3 grid((unsigned)((T + 3 + nbl - 1) / nbl), B);
         for (int it = 0; it < n_iter; ++it) {
             const bool last = it == n_iter - 1;
-            if (two)
-                gl_iteration_kernel<2><<<grid, GLI_FRAMES * 64, (2 * GLI_FRAMES * FPAD + GLI_TAB) * sizeof(float2), s>>>(
-                    ybuf[it & 1], ybuf[(it + 1) & 1], window, wsp<float>(ws, w.wss), p->tw, mag_t, reb[it & 1], reb[(it + 1) & 1],
-                    last ? ang : nullptr, c, it == 0, !last, T);
-            else
-                gl_iteration_kernel<1><<<grid, GLI_FRAMES * 64, (GLI_FRAMES * FPAD + GLI_TAB) * sizeof(float2), s>>>(
-                    ybuf[it & 1], ybuf[(it + 1) & 1], window, wsp<float>(ws, w.wss), p->tw, mag_t, reb[it & 1], reb[(it + 1) & 1],
-                    last ? ang : nullptr, c, it == 0, !last, T);
+            auto launch = [&](auto* kernel, size_t lds_bytes) {
+                kernel<<<grid, GLI_FRAMES * 64, lds_bytes, s>>>(ybuf[it & 1], ybuf[(it + 1) & 1], window, wsp<float>(ws, w.wss), p->tw, mag_t,
+                                                                reb[it & 1], reb[(it + 1) & 1], last ? ang : nullptr, c, it == 0, !last, T,
+                                                                lens, tail);
+            };
+            if (two) {
+                const size_t lds_bytes = (2 * GLI_FRAMES * FPAD + GLI_TAB) * sizeof(float2);
+                if (lens) launch(gl_iteration_kernel<2, true>, lds_bytes); else launch(gl_iteration_kernel<2, false>, lds_bytes);
+            } else {
+                const size_t lds_bytes = (GLI_FRAMES * FPAD + GLI_TAB) * sizeof(float2);
+                if (lens) launch(gl_iteration_kernel<1, true>, lds_bytes); else launch(gl_iteration_kernel<1, false>, lds_bytes);
+            }
             GL_HIP(hipGetLastError());
         }
     } else
@@ -1088,7 +1228,7 @@ int gvx_griffin_lim(gvx_gl_plan* p, const float* mag, const float* window, int B
         GL_HIP(hipGetLastError());
     }
     for (int it = 0; !fused && it < n_iter; ++it) {
-        rc = istft_frames(p, fp, ang, window, B, T, ws, w, s);  // inverse = istft(angles)
+        rc = istft_frames(p, fp, ang, window, B, T, ws, w, s, lens);  // inverse = istft(angles)
         if (rc != GVX_OK) return rc;
         gl_frame_kernel<<<dim3((unsigned)((long)B * T)), 256, 0, s>>>(wsp<float>(ws, w.y), window, wsp<float>(ws, w.fr), p->n_fft, p->hop, T, n);
         GL_HIP(hipGetLastError());
@@ -1101,19 +1241,30 @@ int gvx_griffin_lim(gvx_gl_plan* p, const float* mag, const float* window, int B
     // phase = angle(angles); final spectrum = mag * exp(i phase) (not `angles` itself: they differ where mag < 0)
     float2* spec_t = reb[1];
     float* phase_t = wsp<float>(ws, w.fr);   // frames * n_fft floats >= frames * bins
-    gl_final_kernel<<<blocks_for(nbin), 256, 0, s>>>(ang, mag_t, wav_out ? spec_t : nullptr, phase_out ? phase_t : nullptr, nbin);
+    if (lens)
+        gl_final_kernel<true><<<dim3(blocks_for((long)T * p->bins, 256, 1024), B), 256, 0, s>>>(
+            ang, mag_t, wav_out ? spec_t : nullptr, phase_out ? phase_t : nullptr, (long)T * p->bins, p->bins, T, lens);
+    else
+        gl_final_kernel<false><<<blocks_for(nbin), 256, 0, s>>>(ang, mag_t, wav_out ? spec_t : nullptr, phase_out ? phase_t : nullptr, nbin,
+                                                                p->bins, T, nullptr);
     GL_HIP(hipGetLastError());
     if (phase_out) GL_HIP(launch_transpose<float>(phase_t, phase_out, B, T, p->bins, s));
     if (wav_out) {
-        rc = fused ? inverse_ola(spec_t) : istft_frames(p, fp, spec_t, window, B, T, ws, w, s);
+        rc = fused ? inverse_ola(spec_t) : istft_frames(p, fp, spec_t, window, B, T, ws, w, s, lens);
         if (rc != GVX_OK) return rc;
-        GL_HIP(hipMemcpyAsync(wav_out, wsp<float>(ws, w.y), (size_t)B * n * sizeof(float), hipMemcpyDeviceToDevice, s));
+        if (lens) {   // the signal buffer is valid up to each row's n_b only: zeros behind it in the result
+            copy_rows_ragged_kernel<<<dim3(blocks_for(n, 256, 1024), B), 256, 0, s>>>(wsp<float>(ws, w.y), wav_out, n, p->n_fft, p->hop, lens);
+            GL_HIP(hipGetLastError());
+        } else {
+            GL_HIP(hipMemcpyAsync(wav_out, wsp<float>(ws, w.y), (size_t)B * n * sizeof(float), hipMemcpyDeviceToDevice, s));
+        }
     }
     return GVX_OK;
 }
 
-int gvx_wav_finalize(const float* wav, int B, long n_samples, int trim, const double* b_coef, const double* a_coef, int order,
-                     double* out, unsigned int* scratch_B, void* stream) {
+// shared by gvx_wav_finalize (lens == nullptr) and gvx_wav_finalize_ragged
+int wav_finalize_impl(const float* wav, int B, long n_samples, const int32_t* lens, int n_fft, int hop, int trim, const double* b_coef,
+                      const double* a_coef, int order, double* out, unsigned int* scratch_B, void* stream) {
     if (!wav || !b_coef || !a_coef || !out || !scratch_B) return gl_fail(GVX_ERR_INVALID_ARG, "null argument");
     if (order < 1 || order > 7) return gl_fail(GVX_ERR_UNSUPPORTED, "filter order %d not in [1, 7]", order);
     if (n_samples <= 2L * trim) return gl_fail(GVX_ERR_INVALID_ARG, "signal shorter than the trim");
@@ -1122,7 +1273,10 @@ int gvx_wav_finalize(const float* wav, int B, long n_samples, int trim, const do
     c.order = order;
     for (int k = 0; k <= order; ++k) { c.b[k] = b_coef[k] / a_coef[0]; c.a[k] = a_coef[k] / a_coef[0]; }
     GL_HIP(hipMemsetAsync(scratch_B, 0, (size_t)B * sizeof(unsigned int), s));
-    wav_peak_kernel<<<dim3(64, B), 256, 0, s>>>(wav, n_samples, trim, scratch_B);
+    if (lens)
+        wav_peak_kernel<true><<<dim3(64, B), 256, 0, s>>>(wav, n_samples, trim, scratch_B, lens, n_fft, hop);
+    else
+        wav_peak_kernel<false><<<dim3(64, B), 256, 0, s>>>(wav, n_samples, trim, scratch_B, nullptr, 0, 0);
     GL_HIP(hipGetLastError());
     const int warm = iir_warmup_length(c, 4096);
     if (warm > 0) {
@@ -1130,12 +1284,52 @@ int gvx_wav_finalize(const float* wav, int B, long n_samples, int trim, const do
         while (chunk < 8 * warm) chunk *= 2;   // warm-up work <= 1/8 of the total
         const long n_out = n_samples - 2L * trim;
         const int nch = (int)((n_out + chunk - 1) / chunk);
-        wav_filter_chunked_kernel<<<dim3((nch + 63) / 64, B), 64, 0, s>>>(wav, n_samples, trim, scratch_B, c, out, chunk, warm, nch);
+        const dim3 grid((nch + 63) / 64, B);
+        if (lens)
+            wav_filter_chunked_kernel<true><<<grid, 64, 0, s>>>(wav, n_samples, trim, scratch_B, c, out, chunk, warm, nch, lens, n_fft, hop);
+        else
+            wav_filter_chunked_kernel<false><<<grid, 64, 0, s>>>(wav, n_samples, trim, scratch_B, c, out, chunk, warm, nch, nullptr, 0, 0);
+    } else if (lens) {                          // slowly decaying filter: sequential
+        wav_filter_kernel<true><<<(B + 63) / 64, 64, 0, s>>>(wav, n_samples, trim, scratch_B, c, out, B, lens, n_fft, hop);
     } else {
-        wav_filter_kernel<<<(B + 63) / 64, 64, 0, s>>>(wav, n_samples, trim, scratch_B, c, out, B);   // slowly decaying filter: sequential
+        wav_filter_kernel<false><<<(B + 63) / 64, 64, 0, s>>>(wav, n_samples, trim, scratch_B, c, out, B, nullptr, 0, 0);
     }
     GL_HIP(hipGetLastError());
     return GVX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gvx_griffin_lim(gvx_gl_plan* p, const float* mag, const float* window, int B, int T, int n_iter, float momentum, float* phase_out,
+                    float* wav_out, void* ws, size_t ws_bytes, void* stream) {
+    return griffin_lim_impl(p, mag, window, B, T, nullptr, n_iter, momentum, phase_out, wav_out, ws, ws_bytes, stream);
+}
+
+size_t gvx_gl_workspace_bytes_ragged(gvx_gl_plan* p, int B, int T, int n_mels) {
+    if (!p || B < 1 || T < 1) return 0;
+    FftPair* fp = nullptr;
+    if (get_plans(p, (long)B * T, &fp) != GVX_OK) return 0;
+    return gl_plan_ws(p, B, T, n_mels, fp->work_bytes, true).total;
+}
+
+int gvx_griffin_lim_ragged(gvx_gl_plan* p, const float* mag, const float* window, int B, int T, const int32_t* frame_lengths, int n_iter,
+                           float momentum, float* phase_out, float* wav_out, void* ws, size_t ws_bytes, void* stream) {
+    if (!frame_lengths) return gl_fail(GVX_ERR_INVALID_ARG, "null frame_lengths (gvx_griffin_lim is the call for rows of one length)");
+    return griffin_lim_impl(p, mag, window, B, T, frame_lengths, n_iter, momentum, phase_out, wav_out, ws, ws_bytes, stream);
+}
+
+int gvx_wav_finalize_ragged(const float* wav, int B, long n_samples, const int32_t* frame_lengths, int n_fft, int hop, int trim,
+                            const double* b_coef, const double* a_coef, int order, double* out, unsigned int* scratch_B, void* stream) {
+    if (!frame_lengths) return gl_fail(GVX_ERR_INVALID_ARG, "null frame_lengths (gvx_wav_finalize is the call for rows of one length)");
+    if (B < 1 || n_fft < 1 || hop < 1 || trim < 0) return gl_fail(GVX_ERR_INVALID_ARG, "B, n_fft, hop must be >= 1 and trim >= 0");
+    return wav_finalize_impl(wav, B, n_samples, frame_lengths, n_fft, hop, trim, b_coef, a_coef, order, out, scratch_B, stream);
+}
+
+int gvx_wav_finalize(const float* wav, int B, long n_samples, int trim, const double* b_coef, const double* a_coef, int order,
+                     double* out, unsigned int* scratch_B, void* stream) {
+    return wav_finalize_impl(wav, B, n_samples, nullptr, 0, 0, trim, b_coef, a_coef, order, out, scratch_B, stream);
 }
 
 int gvx_wav_to_mel(gvx_gl_plan* p, const float* signal, const float* window, const float* mel_basis, int B, long n_samples, int n_mels,

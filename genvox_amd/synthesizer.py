@@ -2,13 +2,37 @@
 loading, text -> tokens, autoregressive Tacotron2 on the GPU, mel -> waveform on the GPU."""
 from __future__ import annotations
 
-from typing import Dict
+from typing import Dict, List, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from .audio import AudioProcessor
 from .text import TextProcessor
+
+
+def plan_tts_batches(token_lists: Sequence[Sequence[int]], batch_size: int = 32) -> List[Tuple[List[int], torch.Tensor, torch.Tensor]]:
+    """The host half of ``Synthesizer.tts_batch`` (no GPU needed): sentences as token-id lists -> decoder calls.
+
+    Returns one ``(indices, tokens, token_lengths)`` per call: ``indices`` are positions in ``token_lists``, ``tokens`` int32
+    [b, L] holds those sentences padded with 0 to the longest of the call, ``token_lengths`` int32 [b].  Sentences are sorted by
+    token length, longest first (ties in input order, like ``dist.plan_shards``), and dealt in runs of at most ``batch_size``,
+    so the rows of a call are of similar length.  A sentence without tokens raises ValueError naming its index."""
+    if batch_size < 1:
+        raise ValueError(f"batch_size must be >= 1, not {batch_size}")
+    for i, toks in enumerate(token_lists):
+        if len(toks) == 0:
+            raise ValueError(f"sentence {i} has no tokens after cleaning")
+    order = sorted(range(len(token_lists)), key=lambda i: -len(token_lists[i]))
+    calls = []
+    for lo in range(0, len(order), batch_size):
+        idx = order[lo:lo + batch_size]
+        lens = torch.tensor([len(token_lists[i]) for i in idx], dtype=torch.int32)
+        tokens = torch.zeros(len(idx), int(lens[0]), dtype=torch.int32)
+        for r, i in enumerate(idx):
+            tokens[r, :len(token_lists[i])] = torch.as_tensor(list(token_lists[i]), dtype=torch.int32)
+        calls.append((idx, tokens, lens))
+    return calls
 
 
 class Synthesizer:
@@ -36,3 +60,36 @@ class Synthesizer:
         result["waveform"] = wav[0].cpu().numpy()
         result["sampling_rate"] = self.audio_processor.config.sampling_rate
         return result
+
+    def tts_batch(self, texts: Sequence[str], batch_size: int = 32) -> List[Dict[str, np.ndarray]]:
+        """Many sentences per call: one dict per sentence, in input order, with the keys, dtypes and shapes ``tts(text)`` gives
+        for that sentence (every row trimmed to its own frames, tokens and samples).  Sentences are decoded as padded batches of
+        at most ``batch_size`` rows of similar token length (``plan_tts_batches``) and vocoded at their own lengths in one ragged
+        Griffin-Lim call per batch; the mels stay on the device in between.  A batch of one sentence is exactly the ``tts`` path,
+        torch RNG draws included."""
+        token_lists = [self.text_processor.tokens_to_indices(self.text_processor.tokenize(t)) for t in texts]
+        results: List[Dict[str, np.ndarray]] = [{} for _ in token_lists]
+        for idx, tokens, lens in plan_tts_batches(token_lists, batch_size):
+            inputs = {"tokens": tokens.to(self.device)}
+            if len(idx) > 1:
+                inputs["token_lengths"] = lens.to(self.device)
+            outputs = self.tts_model.inference(inputs=inputs)
+            mel = outputs["mel_outputs_postnet"]
+            if len(idx) > 1:
+                frames = outputs.pop("mel_lengths")
+                wav, samples = self.audio_processor.convert_mel2wav_batch(mel, mel_lengths=frames)
+                frames = frames.tolist()
+            else:
+                wav = self.audio_processor.convert_mel2wav_batch(mel)
+                frames, samples = [mel.shape[2]], [wav.shape[1]]
+            host = {key: val.cpu().numpy() for key, val in outputs.items()}
+            wav = wav.cpu().numpy()
+            for r, i in enumerate(idx):
+                t, n_tok = frames[r], int(lens[r])
+                results[i] = {"mel_outputs": host["mel_outputs"][r, :, :t].copy(),
+                              "mel_outputs_postnet": host["mel_outputs_postnet"][r, :, :t].copy(),
+                              "gate_outputs": host["gate_outputs"][r, :t].copy(),
+                              "alignments": host["alignments"][r, :t, :n_tok].copy(),
+                              "waveform": wav[r, :samples[r]].copy(),
+                              "sampling_rate": self.audio_processor.config.sampling_rate}
+        return results

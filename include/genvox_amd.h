@@ -414,6 +414,31 @@ int gvx_wav_to_mel(gvx_gl_plan* plan, const float* signal, const float* window, 
 int gvx_wav_finalize(const float* wav, int B, long n_samples, int trim, const double* b_coef, const double* a_coef, int order,
                      double* out, unsigned int* scratch_B, void* stream);
 
+/* ---- Ragged batches: the same stages for rows of different lengths in one call.  Buffers keep the strides of the padded T
+ * (mag / phase_out [B][bins][T], wav [B][n_fft + (T-1)*hop]); frame_lengths is a DEVICE int32 [B] (the call stays asynchronous
+ * on `stream`), row b having T_b = frame_lengths[b] frames and n_b = n_fft + (T_b-1)*hop samples.  The kernels clamp a length to
+ * [0, T] rather than trust it; a row of length 0 yields zeros.  frame_lengths == NULL is GVX_ERR_INVALID_ARG (the uniform calls
+ * above exist for that).  Row b's result is, to the bit, what the uniform call gives for that row alone at T = T_b: per frame
+ * and per sample the same operations in the same order, frames t >= T_b never added, the window sum of squares that divides the
+ * row's last n_fft - hop samples that of T_b frames.  Whatever the padded frames of `mag` hold (inf and NaN included) reaches
+ * no valid sample.  gvx_mel_to_magnitude is frame-wise and serves ragged batches as it is.
+ *
+ * gvx_griffin_lim_ragged: phase_out is 0 in frames t >= T_b, wav_out is 0 in samples i >= n_b (inside the workspace the signal
+ * behind n_b is left unwritten and never read).  With n_fft 1024 / hop 256 workgroups that lie wholly behind a row's end return
+ * at once, so the cost follows the sum of the rows' frames; other sizes (and GVX_GL_ROCFFT=1) transform the padded frames too
+ * and skip them in the overlap-add.  The workspace is that of the uniform call plus the per-row divisors:
+ * gvx_gl_workspace_bytes_ragged (a smaller one is GVX_ERR_WORKSPACE).
+ *
+ * gvx_wav_finalize_ragged: n_samples is the row stride of `wav`; per row the clip, the `trim` samples dropped at both ends of
+ * the row's own n_b samples, the peak and the filter (its chunks counted from the row's start) are those of a call on that row
+ * alone.  out: float64 [B][n_samples - 2*trim], 0 from n_b - 2*trim on (a row with n_b <= 2*trim is all zeros). */
+size_t gvx_gl_workspace_bytes_ragged(gvx_gl_plan* plan, int B, int T, int n_mels);
+int gvx_griffin_lim_ragged(gvx_gl_plan* plan, const float* mag, const float* window, int B, int T, const int32_t* frame_lengths,
+                           int n_iter, float momentum, float* phase_out, float* wav_out, void* workspace, size_t workspace_bytes,
+                           void* stream);
+int gvx_wav_finalize_ragged(const float* wav, int B, long n_samples, const int32_t* frame_lengths, int n_fft, int hop, int trim,
+                            const double* b_coef, const double* a_coef, int order, double* out, unsigned int* scratch_B, void* stream);
+
 /* ---- Per-kernel timing of the decoder step (measurement only): when enabled, a teacher-forced call replays the
  * mid-sequence LSTM-step launch and the attention launches 64 times each, back to back, between HIP events on
  * `stream` (after its loop; the call's outputs are not valid afterwards); gvx_kernel_times_ms synchronises and

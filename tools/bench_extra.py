@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Secondary measurements for DESIGN.md (BASELINE.json configs 2-4 beyond the headline line of bench.py):
-teacher-forced at B=64, autoregressive RTF (B=64, 1000 steps), Postnet-only MFMA rate, Griffin-Lim throughput."""
+teacher-forced at B=64, autoregressive RTF (B=64, 1000 steps), Postnet-only MFMA rate, Griffin-Lim throughput;
+`glr` (on request): the ragged Griffin-Lim call against the same rows padded through the uniform call."""
 import json
 import os
 import sys
@@ -81,6 +82,34 @@ def main():
         dt4 = timed(lambda: ap.wav_to_mel(sig), warm=1, reps=3)
         del os.environ["GVX_GL_ROCFFT"]
         res["wav_to_mel_b256x800"] = {"ms": round(dt3 * 1e3, 2), "frames_per_s": round(B * T / dt3), "ms_rocfft_pipeline": round(dt4 * 1e3, 2)}
+    if "glr" in which:
+        # ragged Griffin-Lim: 64 rows with frame counts spread evenly over 200-800, in one ragged call, against the same rows
+        # padded to 800 through the uniform call (the padding's workgroups return at once: time should follow the sum of frames)
+        ap = AudioProcessor(ac)
+        B, T, it = 64, 800, 60
+        lens = [200 + (600 * i) // (B - 1) for i in range(B)]
+        lens = [lens[(i * 29) % B] for i in range(B)]            # not sorted: neighbours in the grid differ in length
+        mag = ap.mel_to_magnitude(torch.randn(B, 80, T, device="cuda") * 1.5 - 4.0)
+        lens_dev = torch.tensor(lens, dtype=torch.int32, device="cuda")
+
+        def runs(fn, warm=2, reps=7):   # every run timed on its own: the spread goes next to the mean
+            for _ in range(warm):
+                fn()
+            out = []
+            for _ in range(reps):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                out.append((time.perf_counter() - t0) * 1e3)
+            return {"mean_ms": round(sum(out) / len(out), 2), "min_ms": round(min(out), 2), "max_ms": round(max(out), 2), "runs": reps}
+
+        padded = runs(lambda: ap.griffin_lim(mag, n_iter=it, want_phase=False))
+        ragged = runs(lambda: ap.griffin_lim(mag, n_iter=it, want_phase=False, frame_lengths=lens_dev))
+        full = runs(lambda: ap.griffin_lim(mag, n_iter=it, want_phase=False, frame_lengths=[T] * B))
+        res["griffin_lim_ragged_b64_200to800_60it"] = {
+            "padded_uniform": padded, "ragged": ragged, "ragged_all_rows_full_length": full,
+            "frames_share": round(sum(lens) / (B * T), 3), "time_share": round(ragged["mean_ms"] / padded["mean_ms"], 3)}
     if "cpu" in which:
         # CPU baselines for configs 3 and 4 (the oracle = CPU restatement of the reference, on this box's host cores):
         # bounded samples, reported beside the GPU figures above; bench.py carries the one for config 2.
