@@ -319,29 +319,34 @@ static bool four_waves() {
     return on;
 }
 
-hipError_t launch_gemm(const GemmParams& p, hipStream_t s) {
-    if (p.M <= 0 || p.N <= 0) return hipSuccess;
+// The whole choice of launch_gemm as host arithmetic: which tile shape runs the product, and whether the last rows go to a second
+// launch.  launch_gemm launches exactly this, and gvx_debug_gemm_plan reports it (the tests pin which shapes reach which branch).
+GemmPlan plan_gemm(const GemmParams& p) {
+    GemmPlan pl{hipSuccess, 0, 0};
+    if (p.M <= 0 || p.N <= 0) return pl;
     if (p.kmajor) {   // K-major operands (weight gradients): the two square-ish tile shapes only, any K; 16-byte pieces along m / n
-        if ((p.M & 3) || (p.N & 3) || p.M < 4 || p.N < 4 || ((p.amap.s0 | p.amap.s1 | p.wmap.s0 | p.wmap.s1) & 3)) return hipErrorInvalidValue;
+        if ((p.M & 3) || (p.N & 3) || p.M < 4 || p.N < 4 || ((p.amap.s0 | p.amap.s1 | p.wmap.s0 | p.wmap.s1) & 3)) { pl.err = hipErrorInvalidValue; return pl; }
         const long t128 = (long)((p.M + 127) / 128) * ((p.N + 127) / 128);
-        return t128 < 384 ? launch_cfg<2, 2, 1, 2, true>(p, s) : launch_cfg<2, 2, 2, 2, true>(p, s);
+        pl.tile = t128 < 384 ? 2212 : 2222;
+        return pl;
     }
-    if (p.K & 3) return hipErrorInvalidValue;
-    if (p.N <= 32) return launch_cfg<4, 1, 1, 1>(p, s);
+    if (p.K & 3) { pl.err = hipErrorInvalidValue; return pl; }
+    if (p.N <= 32) { pl.tile = 4111; return pl; }
     if (p.N <= 96) {
         // few rows (a single utterance: 568 frames = 5 tiles of 128 rows): the launch lasts as long as ONE wave's chain of dependent
         // MFMAs over K - three accumulators per wave in the 128 x 96 tile (151 us for the last Postnet convolution on 800 frames),
         // one in the 64 x 96 tile of six waves.  Many rows: the six-wave tile is no faster (MFMA busy 0.40 vs 0.44, round 4)
-        if (p.M - p.m_begin <= 4096) return launch_cfg<2, 3, 1, 1>(p, s);
-        return launch_cfg<4, 1, 1, 3>(p, s);
+        pl.tile = p.M - p.m_begin <= 4096 ? 2311 : 4113;
+        return pl;
     }
     // fewer than ~1.5 workgroups per CU with 128 x 128 tiles (encoder convolutions: 4096 x 512): halve the tile height so
     // that all 256 CUs get work
     const long n_tiles = (p.N + 127) / 128, tiles128 = (long)((p.M + 127) / 128) * n_tiles;
     // and below ~0.75 per CU (the encoder convolutions themselves: 128 tiles) 64 x 64 tiles, two workgroups per CU: one
     // 64 x 128 workgroup of four waves per CU left the matrix pipe waiting on its own loads (155 -> 115 us per convolution)
-    if (tiles128 < 192) return launch_cfg<2, 2, 1, 1>(p, s);
-    if (tiles128 < 384) return launch_cfg<2, 2, 1, 2>(p, s);
+    if (tiles128 < 192) { pl.tile = 2211; return pl; }
+    if (tiles128 < 384) { pl.tile = 2212; return pl; }
+    pl.tile = four_waves() ? 2222 : 4212;
     // Wave quantisation: a last round of 128 x 128 tiles with few tiles leaves most of the chip idle for a whole tile time (the
     // Postnet at 32 x 800 frames: 800 tiles = 3 per CU + 32).  When that remainder is at most a quarter of a round, the rows of
     // the full rounds get the big tiles and the remaining rows 64 x 64 tiles (four times as many workgroups, a quarter of the
@@ -351,16 +356,41 @@ hipError_t launch_gemm(const GemmParams& p, hipStream_t s) {
     const long rem = tiles128 % 256;
     if (p.splitk <= 1 && p.m_begin == 0 && rem > 0 && rem <= 64) {
         const long rows_big = ((tiles128 - rem) / n_tiles) * 128;   // whole row tiles of the full rounds
-        if (rows_big > 0 && rows_big < p.M) {
-            GemmParams a = p, b = p;
-            a.M = (int)rows_big;
-            b.m_begin = (int)rows_big;
-            const hipError_t e = four_waves() ? launch_cfg<2, 2, 2, 2>(a, s) : launch_cfg<4, 2, 1, 2>(a, s);
-            if (e != hipSuccess) return e;
-            return launch_cfg<2, 2, 1, 1>(b, s);
-        }
+        if (rows_big > 0 && rows_big < p.M) pl.rows_big = (int)rows_big;
     }
-    return four_waves() ? launch_cfg<2, 2, 2, 2>(p, s) : launch_cfg<4, 2, 1, 2>(p, s);
+    return pl;
+}
+
+static hipError_t launch_tile(int tile, const GemmParams& p, hipStream_t s) {
+    switch (tile) {
+        case 4111: return launch_cfg<4, 1, 1, 1>(p, s);
+        case 2311: return launch_cfg<2, 3, 1, 1>(p, s);
+        case 4113: return launch_cfg<4, 1, 1, 3>(p, s);
+        case 2211: return launch_cfg<2, 2, 1, 1>(p, s);
+        case 2212: return p.kmajor ? launch_cfg<2, 2, 1, 2, true>(p, s) : launch_cfg<2, 2, 1, 2>(p, s);
+        case 2222: return p.kmajor ? launch_cfg<2, 2, 2, 2, true>(p, s) : launch_cfg<2, 2, 2, 2>(p, s);
+        case 4212: return launch_cfg<4, 2, 1, 2>(p, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_gemm(const GemmParams& p, hipStream_t s) {
+    const GemmPlan pl = plan_gemm(p);
+    if (pl.err != hipSuccess || pl.tile == 0) return pl.err;
+    if (pl.rows_big == 0) return launch_tile(pl.tile, p, s);
+    GemmParams a = p, b = p;
+    a.M = pl.rows_big;
+    b.m_begin = pl.rows_big;
+    const hipError_t e = launch_tile(pl.tile, a, s);
+    if (e != hipSuccess) return e;
+    return launch_tile(2211, b, s);
+}
+
+// K cut into (at most) `splitk` pieces of whole k-tiles (of either size): the last piece may be short, and there may be fewer
+// pieces than asked for
+void set_splitk(GemmParams& p, int splitk) {
+    p.kchunk = ((p.K + splitk - 1) / splitk + 63) / 64 * 64;
+    p.splitk = (p.K + p.kchunk - 1) / p.kchunk;
 }
 
 // out[m][n] = sum_s part[s][m][n] (+ bias[n]), splits added in index order
@@ -379,9 +409,7 @@ hipError_t launch_gemm_splitk(const GemmParams& p0, int splitk, float* scratch, 
     if (p0.act != ACT_NONE || p0.keep || p0.row_len || p0.c_halo || p0.c_nblk != 8 || p0.cmap.s1 != 0 || p0.cmap.R < p0.M || !scratch)
         return hipErrorInvalidValue;   // plain row-major outputs only
     GemmParams p = p0;
-    const int kc = ((p.K + splitk - 1) / splitk + 63) / 64 * 64;   // (whole k-tiles of either size)
-    p.splitk = (p.K + kc - 1) / kc;
-    p.kchunk = kc;
+    set_splitk(p, splitk);
     p.C = scratch; p.cmap = RowMap{p.M, 0, (long)p.N};
     p.c_split = (long)p.M * p.N;
     p.bias = nullptr;

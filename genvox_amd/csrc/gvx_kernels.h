@@ -63,6 +63,12 @@ struct GemmParams {
                                        // (requires cmap.R >= c_halo)
 };
 hipError_t launch_gemm(const GemmParams& p, hipStream_t s);
+// What launch_gemm does with p, as host arithmetic (no device is touched).  tile: the <WR,WC,TM,TN> shape as the four digits
+// WR WC TM TN (4212 = <4,2,1,2>; 0: nothing to launch); rows_big > 0: rows [0, rows_big) take `tile`, the rest <2,2,1,1> in a
+// second launch.  err != hipSuccess: the shape is refused.
+struct GemmPlan { hipError_t err; int tile; int rows_big; };
+GemmPlan plan_gemm(const GemmParams& p);
+void set_splitk(GemmParams& p, int splitk);   // launch_gemm_splitk's cut of K: fills p.kchunk and p.splitk (pieces <= splitk)
 // plain row-major C [M][N] (ldc) = A W^T (+ bias) with K split over `splitk` workgroups per tile; partials [splitk][M][N] in scratch
 hipError_t launch_gemm_splitk(const GemmParams& p, int splitk, float* scratch, hipStream_t s);
 

@@ -537,10 +537,36 @@ __global__ void adam_many_kernel(const gvx_adam_ref* refs, float gscale, float l
     }
 }
 
+// The split gvx_train_gemm_nt / _tn ask launch_gemm_splitk for: what choose_splitk wants for the product's 64 x 128 tiles, as far
+// as the caller's scratch holds the partial tiles (1 = no split; no scratch, no split)
+inline int train_gemm_splitk(int M, int N, int K, bool have_scratch, size_t scratch_bytes) {
+    const long tiles = (long)((M + 63) / 64) * ((N + 127) / 128);
+    int splitk = have_scratch ? choose_splitk(tiles, K) : 1;
+    while (splitk > 1 && (size_t)splitk * M * N * sizeof(float) > scratch_bytes) --splitk;
+    return splitk;
+}
+
 }  // namespace
 }  // namespace gvx
 
 extern "C" {
+
+// Host-only query for the tests (not part of the public header; touches no device): how gvx_train_gemm_nt (kmajor == 0) or
+// gvx_train_gemm_tn (kmajor != 0, K = rows) runs an M x N x K product with dense leading dimensions - plan_gemm's tile shape and
+// two-launch split, and the number of K pieces (1 = no split-K).  Returns the status launch_gemm would return for the shape.
+int gvx_debug_gemm_plan(int M, int N, int K, int kmajor, int have_scratch, size_t scratch_bytes, int* tile_out, int* rows_big_out, int* k_pieces_out) {
+    if (!tile_out || !rows_big_out || !k_pieces_out || M < 1 || N < 1 || K < 1) return GVX_ERR_INVALID_ARG;
+    GemmParams g{};
+    g.kmajor = kmajor != 0;
+    g.amap = kmajor ? RowMap{K, 0, (long)M} : RowMap{M, 0, (long)K};
+    g.wmap = RowMap{K, 0, (long)N};
+    g.M = M; g.N = N; g.K = K;
+    const int splitk = train_gemm_splitk(M, N, K, have_scratch != 0, scratch_bytes);
+    if (splitk > 1) set_splitk(g, splitk);   // (what launch_gemm_splitk does before it plans)
+    const GemmPlan pl = plan_gemm(g);
+    *tile_out = pl.tile; *rows_big_out = pl.rows_big; *k_pieces_out = g.splitk;
+    return pl.err == hipSuccess ? GVX_OK : GVX_ERR_INVALID_ARG;
+}
 
 // C[m][n] = sum_k A[m*lda + k] * W[n*ldw + k] (+ bias[n]);  K % 4 == 0
 int gvx_train_gemm_nt(const float* A, long lda, const float* W, long ldw, float* C, long ldc, int M, int N, int K, const float* bias,
@@ -553,10 +579,7 @@ int gvx_train_gemm_nt(const float* A, long lda, const float* W, long ldw, float*
     g.bias = bias; g.M = M; g.N = N; g.K = K; g.act = ACT_NONE;
     // few output tiles and a long K (the per-step products of the backward: 32 rows x thousands of columns): split K over
     // enough workgroups to fill the chip, partial tiles in the caller's scratch, added in split order (deterministic)
-    const long tiles = (long)((M + 63) / 64) * ((N + 127) / 128);
-    int splitk = scratch ? choose_splitk(tiles, K) : 1;
-    while (splitk > 1 && (size_t)splitk * M * N * sizeof(float) > scratch_bytes) --splitk;
-    TR_TRY(launch_gemm_splitk(g, splitk, scratch, (hipStream_t)stream));
+    TR_TRY(launch_gemm_splitk(g, train_gemm_splitk(M, N, K, scratch != nullptr, scratch_bytes), scratch, (hipStream_t)stream));
     return GVX_OK;
 }
 // C[m][n] = sum_r A[r * lda + m] * Bm[r * ldb + n]: the weight-gradient form, both operands as they lie in memory
@@ -569,10 +592,7 @@ int gvx_train_gemm_tn(const float* A, long lda, const float* Bm, long ldb, float
     g.W = Bm; g.wmap = RowMap{(int)rows, 0, ldb};
     g.C = C; g.cmap = RowMap{M, 0, ldc};
     g.M = M; g.N = N; g.K = (int)rows; g.act = ACT_NONE;
-    const long tiles = (long)((M + 63) / 64) * ((N + 127) / 128);
-    int splitk = scratch ? choose_splitk(tiles, (int)rows) : 1;
-    while (splitk > 1 && (size_t)splitk * M * N * sizeof(float) > scratch_bytes) --splitk;
-    TR_TRY(launch_gemm_splitk(g, splitk, scratch, (hipStream_t)stream));
+    TR_TRY(launch_gemm_splitk(g, train_gemm_splitk(M, N, (int)rows, scratch != nullptr, scratch_bytes), scratch, (hipStream_t)stream));
     return GVX_OK;
 }
 // dst[c][r] = src[r * ld_src + c] for r < rows (0 for rows <= r < rows_p);  dst rows are rows_p long

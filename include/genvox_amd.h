@@ -199,7 +199,8 @@ int gvx_postnet_forward(gvx_model* model, const float* mel_in, const int32_t* me
                         void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- Output padding mask (models/tts/tacotron2.py:466-473): frames >= mel_lengths[b] get
- * mel = 0, mel_post = 0, gate = 1e3.  mel_lengths: int32 [B]. In place. */
+ * mel = 0, mel_post = 0, gate = 1e3.  mel_lengths: int32 [B], each >= 0 (0 masks the whole row, T or more nothing). In place;
+ * live frames are not touched.  mel, mel_post and gate may each be NULL: that tensor is skipped. */
 int gvx_mask_padding(float* mel, float* mel_post, float* gate, const int32_t* mel_lengths,
                      int B, int n_mels, int T, void* stream);
 

@@ -157,6 +157,41 @@ def test_training_entry_points_validate_their_arguments_on_the_host():
     assert lib.gvx_train_gemm_tn(None, 0, None, 0, None, 0, 4, 4, 8, None, 0, None) == -1
 
 
+def test_gemm_dispatch_plan_of_every_listed_shape(monkeypatch):
+    """launch_gemm's choice is host arithmetic; gvx_debug_gemm_plan reports it from the same function that launches.  Every
+    shape of the GPU GEMM tests (tests/helpers.py) must reach the branch its line names: tile shape, the two-launch split and
+    its first row, the number of K pieces for the scratch it hands over.  A retuned threshold fails here."""
+    from tests.helpers import GEMM_8W_CASES, GEMM_CASES, gemm_plan, gemm_scratch_bytes
+
+    if os.environ.get("GVX_GEMM_8W", "")[:1] == "0":
+        pytest.skip("the table is for the default eight-wave tile")
+    lib = _lib.load()
+    for c in GEMM_CASES:
+        assert gemm_plan(lib, c.M, c.N, c.K, c.kmajor, gemm_scratch_bytes(c)) == (0, c.tile, c.rows_big, c.pieces), c
+    # every tile shape of the header comment of gemm_f32.hip, the split, split-K on both forms and both K-major tiles are named
+    reached = {(c.kmajor, c.tile) for c in GEMM_CASES}
+    assert reached == {(0, 4111), (0, 2311), (0, 4113), (0, 2211), (0, 2212), (0, 4212), (1, 2212), (1, 2222)}
+    assert {c.kmajor for c in GEMM_CASES if c.pieces > 1} == {0, 1} and any(c.rows_big for c in GEMM_CASES)
+    assert len(GEMM_8W_CASES) >= 5 and sum(1 for c in GEMM_8W_CASES if c.rows_big) >= 3
+    # the edges of each threshold, one step to either side
+    plan = lambda *a, **k: gemm_plan(lib, *a, **k)[1:]
+    assert plan(4096, 32, 8) == (4111, 0, 1) and plan(4096, 33, 8) == (2311, 0, 1)
+    assert plan(4096, 96, 8) == (2311, 0, 1) and plan(4097, 96, 8) == (4113, 0, 1) and plan(4097, 97, 8) == (2211, 0, 1)
+    assert plan(6016, 512, 8) == (2211, 0, 1) and plan(6017, 512, 8) == (2212, 0, 1)         # 188 / 192 tiles of 128 x 128
+    assert plan(12160, 512, 8) == (2212, 0, 1) and plan(12161, 512, 8) == (4212, 0, 1)       # 380 / 384
+    assert plan(16384 + 2048, 512, 8) == (4212, 16384, 1) and plan(16384 + 2049, 512, 8) == (4212, 0, 1)   # remainder 64 / 68
+    assert plan(16384, 512, 8) == (4212, 0, 1) and plan(16385, 512, 8) == (4212, 16384, 1)   # remainder 0 / 4
+    assert plan(1536, 3968, 8, kmajor=1) == (2212, 0, 1) and plan(1536, 4096, 8, kmajor=1) == (2222, 0, 1)
+    # refused shapes: K % 4 for the row-major form, M / N % 4 or < 4 for the K-major one
+    for bad in ((8, 8, 6, 0), (6, 8, 8, 1), (8, 6, 8, 1), (2, 8, 8, 1)):
+        assert gemm_plan(lib, *bad)[0] != 0, bad
+    # split-K: at most 8 pieces of whole k-tiles, none without scratch, none at K < 512 or from 256 tiles of 64 x 128 on
+    big = 1 << 30
+    assert plan(32, 4096, 508, scratch_bytes=big)[2] == 1 and plan(32, 4096, 512, scratch_bytes=big)[2] == 2
+    assert plan(64 * 16, 128 * 16, 4096, scratch_bytes=big)[2] == 1 and plan(64 * 8, 128 * 16, 4096, scratch_bytes=big)[2] == 2
+    assert plan(32, 4096, 2560, scratch_bytes=32 * 4096 * 4 * 5 - 1)[2] == 4
+
+
 # ---- rows a16 / f1 / f2 pinned by files the reference itself produced (tests/golden/make_fixtures.py host) -----------
 GOLDEN = os.path.join(REPO, "tests", "golden")
 
