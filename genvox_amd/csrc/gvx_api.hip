@@ -534,6 +534,10 @@ int gvx_decoder_teacher_forced_train(gvx_model* m, const float* memory, const in
     if (rc != GVX_OK) return rc;
     if (!memory || !mel_in || !keep_masks || !att_keep || !dec_keep || !mel_out || !gate_out || !align_out) return fail(GVX_ERR_INVALID_ARG, "null argument");
     if (!(p_att >= 0.f && p_att < 1.f && p_dec >= 0.f && p_dec < 1.f)) return fail(GVX_ERR_INVALID_ARG, "dropout probabilities must be in [0, 1)");
+    // the 64-row loop (GVX_TF_ROWS64=1 handles, 33 .. 64 rows) wires neither the hidden-state dropout nor the tape: refused before
+    // anything is written, rather than an inference-mode result behind GVX_OK
+    if (plan_teacher_forced(m, B, L, TF_TRAIN_PARTIAL_TAPE).rows64)
+        return fail(GVX_ERR_UNSUPPORTED, "training mode with %d rows on a GVX_TF_ROWS64 handle: the 64-row loop has no dropout and no tape (at most 32 rows per call)", B);
     hipStream_t s = (hipStream_t)stream;
     const int A = m->d.att_rnn_dim, D = m->d.dec_rnn_dim, E = m->d.embed_dim;
     const LstmDropout tr{att_keep, dec_keep, 1.f / (1.f - p_att), 1.f / (1.f - p_dec), att_hidden_all, att_cell_all, dec_cell_all, att_preact_all, dec_preact_all};

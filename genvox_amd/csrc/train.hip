@@ -704,11 +704,16 @@ struct BpttAttn {
 // 32-iteration loop, its operands in registers / consecutive LDS words
 constexpr int BA_THREADS = 512;
 constexpr int BA_FS = 32;
+// items a thread of bptt_attention_kernel takes per pass: energies, dense-gradient groups (8 filters of one attention dim),
+// convolution-gradient items.  More than BA_NB* x BA_THREADS items: further passes, which reload their operands
+constexpr int BA_NBE = 8, BA_NBD = 2, BA_NBC = 4;
 inline size_t bptt_attn_lds_floats(int L, int E, int a, int F, int kl, int G) {
     const int CH = (L + G - 1) / G;
     return (size_t)E + 2 * L + BA_THREADS + 2 * (CH + kl - 1) + (size_t)2 * kl * (BA_FS + 1) + (size_t)a * (BA_FS + 1) + (size_t)CH * BA_FS + CH +
            (size_t)2 * CH * a + (size_t)CH * BA_FS + (size_t)CH * 2 * kl + 8;
 }
+
+constexpr size_t BA_LDS_LIMIT = 160 * 1024;
 
 __device__ __forceinline__ float fast_tanh(float x) { return 1.f - 2.f * __builtin_amdgcn_rcpf(__expf(2.f * x) + 1.f); }
 
@@ -737,7 +742,7 @@ __global__ __launch_bounds__(BA_THREADS) void bptt_attention_kernel(BpttAttn p) 
 
     // ---- every global operand that does not depend on this launch's arithmetic is requested up front (a dependent round trip
     // to memory the previous launch wrote costs ~1 us; the first version of this kernel had a dozen of them in a row)
-    constexpr int NBE = 8, NBD = 2, NBC = 4;   // items per thread and batch: energies, dense-gradient groups, conv-gradient items
+    constexpr int NBE = BA_NBE, NBD = BA_NBD, NBC = BA_NBC;   // items per thread and batch: energies, dense-gradient groups, conv-gradient items
     const int n_en = n * a, n_dg = a * (FS / 8), n_cv = F * 2 * kl;
     float e_pm[NBE], e_dpm[NBE];
 #pragma unroll
@@ -1125,7 +1130,7 @@ int check_bptt_args(const gvx_bptt_decoder_args* a) {
     for (const void* q : need)
         if (!q) return tfail(GVX_ERR_INVALID_ARG, "decoder_bptt: null pointer in the argument block");
     const size_t lds = bptt_attn_lds_floats(a->L, a->E, a->a, a->F, a->kl, bptt_chunks(a->L)) * sizeof(float);
-    if (lds > 160 * 1024) return tfail(GVX_ERR_UNSUPPORTED, "decoder_bptt: a row's attention chunk does not fit the LDS (L or E too large)");
+    if (lds > BA_LDS_LIMIT) return tfail(GVX_ERR_UNSUPPORTED, "decoder_bptt: a row's attention chunk does not fit the LDS (L or E too large)");
     return GVX_OK;
 }
 
@@ -1134,6 +1139,28 @@ int check_bptt_args(const gvx_bptt_decoder_args* a) {
 
 extern "C" {
 
+// Host-only query for the tests (not part of the public header; touches no device): where gvx_train_decoder_bptt's kernels
+// land for an argument block, from the functions and constants the launches use.  out[0..9] = position chunks G, positions per
+// chunk CH, chunks that hold positions, passes of bptt_attention_kernel over the energies of a full chunk / over the
+// dense-gradient groups / over the convolution-gradient items, 1 if a thread keeps its query and v element in registers
+// (BA_THREADS % a == 0), Na, Nd, LDS bytes of the attention launch.  Returns the status gvx_train_decoder_bptt's argument check
+// gives (out is filled whenever the sizes are positive, so that both sides of a limit can be read).
+int gvx_debug_bptt_plan(const gvx_bptt_decoder_args* a, int* out) {
+    if (!out) return GVX_ERR_INVALID_ARG;
+    for (int i = 0; i < 10; ++i) out[i] = 0;
+    const int rc = check_bptt_args(a);
+    if (!a || a->L < 1 || a->a < 1 || a->F < 1 || a->kl < 1 || a->E < 0 || a->A < 1 || a->D < 1) return rc;
+    auto passes = [](long items, int per_thread) { return (int)((items + (long)per_thread * BA_THREADS - 1) / ((long)per_thread * BA_THREADS)); };
+    const int G = bptt_chunks(a->L), CH = (a->L + G - 1) / G;
+    out[0] = G; out[1] = CH; out[2] = (a->L + CH - 1) / CH;
+    out[3] = passes((long)(CH < a->L ? CH : a->L) * a->a, BA_NBE);
+    out[4] = passes((long)a->a * (BA_FS / 8), BA_NBD);
+    out[5] = passes((long)a->F * 2 * a->kl, BA_NBC);
+    out[6] = BA_THREADS % a->a == 0 ? 1 : 0;
+    out[7] = round32(a->E + a->A); out[8] = round32(a->A + a->E + a->D);
+    out[9] = (int)(bptt_attn_lds_floats(a->L, a->E, a->a, a->F, a->kl, G) * sizeof(float));
+    return rc;
+}
 size_t gvx_train_decoder_bptt_workspace_bytes(const gvx_bptt_decoder_args* a) {
     if (check_bptt_args(a) != GVX_OK) return 0;
     return bptt_plan(*a).total * sizeof(float);
@@ -1515,6 +1542,12 @@ __global__ void transpose_batched_kernel(const float* src, float* dst, int n, in
     }
 }
 
+inline int enc_bptt_workgroups(int H) { return (H + EB_UJ - 1) / EB_UJ; }                       // per direction
+inline size_t enc_bptt_lds_bytes(int H) { return (size_t)(EB_UJ * 4 * H * 2) * sizeof(float); }   // EB_UJ columns and 4 EB_UJ rows of W_hh
+constexpr size_t EB_LDS_LIMIT = 160 * 1024;
+// one resident launch for the whole walk where all its workgroups fit on the GPU at once (default layer size: 128 of 256 CUs)
+inline bool enc_bptt_resident_serves(int H) { return 2 * enc_bptt_workgroups(H) <= 192 && enc_bptt_lds_bytes(H) <= 64 * 1024; }
+
 struct EncBpttPlan { size_t wt, dg, dpass, dc, sync, total; };
 constexpr int EB_SYNC_STATUS = 0, EB_SYNC_TMO = 32, EB_SYNC_FLAGS = 64;   // words inside the sync region (a 128-byte line each)
 EncBpttPlan enc_bptt_plan(int B, int H) {
@@ -1535,6 +1568,17 @@ EncBpttPlan enc_bptt_plan(int B, int H) {
 
 extern "C" {
 
+// Host-only query for the tests, like gvx_debug_bptt_plan: out[0..3] = workgroups per direction, LDS bytes, 1 if the entry point (resident != 0:
+// gvx_train_encoder_lstm_bptt_resident) takes the one resident launch, trips of the kernels' loop over batch rows.
+int gvx_debug_enc_bptt_plan(int B, int H, int resident, int* out) {
+    if (!out) return GVX_ERR_INVALID_ARG;
+    for (int i = 0; i < 4; ++i) out[i] = 0;
+    if (B < 1 || H < 8 || (H % 8)) return GVX_ERR_UNSUPPORTED;
+    out[0] = enc_bptt_workgroups(H); out[1] = (int)enc_bptt_lds_bytes(H);
+    out[2] = resident && enc_bptt_resident_serves(H) ? 1 : 0; out[3] = (B + 31) / 32;
+    return enc_bptt_lds_bytes(H) > EB_LDS_LIMIT ? GVX_ERR_UNSUPPORTED : GVX_OK;
+}
+
 size_t gvx_train_encoder_lstm_bptt_workspace_bytes(int B, int H) {
     if (B < 1 || H < 1) return 0;
     return enc_bptt_plan(B, H).total * sizeof(float);
@@ -1548,8 +1592,8 @@ static int encoder_lstm_bptt_impl(const float* xg, const float* memory, const fl
     if (B < 1 || L < 1 || H < 8 || (H % 8)) return tfail(GVX_ERR_UNSUPPORTED, "encoder_lstm_bptt: B, L >= 1, H a positive multiple of 8");
     const EncBpttPlan pl = enc_bptt_plan(B, H);
     if (workspace_bytes < pl.total * sizeof(float)) return tfail(GVX_ERR_WORKSPACE, "encoder_lstm_bptt: workspace too small");
-    const size_t lds = (size_t)(EB_UJ * 4 * H * 2) * sizeof(float);
-    if (lds > 160 * 1024) return tfail(GVX_ERR_UNSUPPORTED, "encoder_lstm_bptt: H too large for the LDS");
+    const size_t lds = enc_bptt_lds_bytes(H);
+    if (lds > EB_LDS_LIMIT) return tfail(GVX_ERR_UNSUPPORTED, "encoder_lstm_bptt: H too large for the LDS");
     hipStream_t s = (hipStream_t)stream;
     float* ws = reinterpret_cast<float*>(workspace);
     TR_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(encoder_bptt_step_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -1557,9 +1601,8 @@ static int encoder_lstm_bptt_impl(const float* xg, const float* memory, const fl
     TR_TRY(hipMemsetAsync(ws + pl.dg, 0, (pl.total - pl.dg) * sizeof(float), s));
     TR_TRY(hipMemsetAsync(dg_pos, 0, (size_t)2 * B * L * 4 * H * sizeof(float), s));
     TR_TRY(hipMemsetAsync(hprev_pos, 0, (size_t)2 * B * L * H * sizeof(float), s));
-    // one resident launch for the whole walk where all its workgroups fit on the GPU at once (default layer size: 128 of 256 CUs)
-    const int nwg = (H + EB_UJ - 1) / EB_UJ;
-    if (resident && 2 * nwg <= 192 && lds <= 64 * 1024) {
+    const int nwg = enc_bptt_workgroups(H);
+    if (resident && enc_bptt_resident_serves(H)) {
         TR_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(encoder_bptt_resident_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         unsigned* sync = reinterpret_cast<unsigned*>(ws + pl.sync);
         EncBpttRes a{};
@@ -1586,7 +1629,7 @@ static int encoder_lstm_bptt_impl(const float* xg, const float* memory, const fl
         q.dpass_in = ws + pl.dpass + (size_t)(par ^ 1) * 2 * B * H; q.dpass_out = ws + pl.dpass + (size_t)par * 2 * B * H;
         q.dc = ws + pl.dc; q.dg_pos = dg_pos; q.hprev_pos = hprev_pos;
         q.stamp = st == L / 2;
-        hipLaunchKernelGGL(encoder_bptt_step_kernel, dim3((H + EB_UJ - 1) / EB_UJ, 2), dim3(256), lds, s, q);
+        hipLaunchKernelGGL(encoder_bptt_step_kernel, dim3(nwg, 2), dim3(256), lds, s, q);
     }
     TR_TRY(hipGetLastError());
     return GVX_OK;

@@ -249,7 +249,9 @@ int gvx_tacotron2_loss(const float* mel_out, const float* mel_post_out, const fl
  *                                       as k-group-blocked vectors: element (b, k) at (k / 8) * B * 8 + b * 8 + k % 8;
  *   att_cell_all, dec_cell_all [T+1][B][H]   both cells' states (slot t + 1 = after step t);
  *   dec_hidden_context_all [T+1][(D+E)/8][B][8]   [h_d ; ctx] after every step, blocked as above;
- *   att_preact_all [T][B][A][4], dec_preact_all [T][B][D][4]   gate pre-activations i, f, g, o of every unit and step. */
+ *   att_preact_all [T][B][A][4], dec_preact_all [T][B][D][4]   gate pre-activations i, f, g, o of every unit and step.
+ * gvx_decoder_teacher_forced_train on a handle created under GVX_TF_ROWS64=1 takes at most 32 rows per call where 33 .. 64 rows
+ * would run on the 64-row loop (which has neither the dropout nor the tape): GVX_ERR_UNSUPPORTED, nothing written. */
 int gvx_encoder_lstm_forward(gvx_model* model, const float* conv_out, const int32_t* lengths, int B, int L, float* memory_out,
                              float* cell_states_out, float* input_preact_out, void* workspace, size_t workspace_bytes, void* stream);
 int gvx_decoder_teacher_forced_train(gvx_model* model, const float* memory, const int32_t* lengths, int B, int L, const float* mel_in,
@@ -314,9 +316,14 @@ int gvx_train_adam_step_many(const gvx_adam_ref* refs_device, int n_tensors, flo
  * queries, of the processed memory, of the memory through the contexts, and of v / location_dense / location_conv
  * (Decoder.forward backwards, models/tts/tacotron2.py:365-388 with :333-363 and Attention :89-129).  What is not on the
  * recurrence (weight gradients as whole-sequence products, the Prenet columns of the attention LSTM) stays with the caller.
- * All pointers device, fp32 row-major, gates in torch order i, f, g, o. */
+ * All pointers device, fp32 row-major, gates in torch order i, f, g, o.
+ * There is no `lengths` argument: the masking of padded positions rides on w_all, which must be exactly zero at and past a
+ * row's length at every step (as a softmax over -inf energies leaves it); dpm and dmemory are then exactly zero there, and
+ * memory / pm past the length are never seen in any output.  dpm is cleared by the call, which then accumulates into it; the
+ * workspace needs no clearing either.  L is limited by the LDS of the attention launch (160 KiB for a row's chunk: L <= 664
+ * at the default layer sizes); the size query returns 0 and the call GVX_ERR_UNSUPPORTED beyond it. */
 typedef struct gvx_bptt_decoder_args {
-    int32_t B, L, T;                    /* B <= 32 */
+    int32_t B, L, T;                    /* 1 <= B <= 32, L >= 1, T >= 1 */
     int32_t A, D, E, P, a, F, kl;       /* att_rnn_dim, dec_rnn_dim, embed_dim, prenet_dim, att_dim, location filters / kernel size */
     float att_scale, dec_scale;         /* 1 / (1 - p) of the dropout on each cell's hidden output */
     const float* dhc_all;               /* [T][B][D+E]  d loss / d [h_d(t) ; ctx(t)] through the mel / gate projection */
@@ -342,7 +349,7 @@ typedef struct gvx_bptt_decoder_args {
     float* dgd_all;                     /* out [T][B][4D] */
     float* dq_all;                      /* out [T][B][a] */
     float* dctx_all;                    /* out [T][B][E]   total d loss / d ctx(t) */
-    float* dpm;                         /* out [B][L][a] */
+    float* dpm;                         /* out [B][L][a]   cleared by the call */
     float* dmemory;                     /* out [B][L][E]   context path only: sum_t w_t (x) dctx_t */
     float* dv;                          /* out [a] */
     float* dloc_dense;                  /* out [a][F] */
@@ -354,7 +361,8 @@ int gvx_train_decoder_bptt(const gvx_bptt_decoder_args* args, void* workspace, s
  * one launch per time step for both directions.  xg [2][B][L][4H] = W_ih x + b_ih + b_hh per direction; memory / cell_states /
  * dmemory [B][L][2H] (forward direction in the first H channels); w_hh [2][4H][H].  Outputs, filed under the POSITION a step
  * belongs to (zeros past a row's length): dg_pos [2][B][L][4H] gate gradients, hprev_pos [2][B][L][H] the step's previous
- * hidden state - the operands of the weight gradients and of d loss / d x. */
+ * hidden state - the operands of the weight gradients and of d loss / d x.  Any B >= 1 (rows beyond 32 take further trips of
+ * the kernels' row loop), lengths in [1, L], H a multiple of 8 up to 1280 (LDS). */
 size_t gvx_train_encoder_lstm_bptt_workspace_bytes(int B, int H);
 int gvx_train_encoder_lstm_bptt(const float* xg, const float* memory, const float* cell_states, const float* dmemory, const float* w_hh,
                                 const int32_t* lengths, int B, int L, int H, float* dg_pos, float* hprev_pos, void* workspace,

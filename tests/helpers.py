@@ -123,3 +123,147 @@ def gemm_plan(lib, M, N, K, kmajor=0, scratch_bytes=None):
     tile, rows_big, pieces = C.c_int(-1), C.c_int(-1), C.c_int(-1)
     rc = fn(M, N, K, kmajor, scratch_bytes is not None, scratch_bytes or 0, C.byref(tile), C.byref(rows_big), C.byref(pieces))
     return rc, tile.value, rows_big.value, pieces.value
+
+
+# ---- back-propagation through the decoder loop (gvx_train_decoder_bptt, genvox_amd/csrc/train.hip): the shapes
+# tests/test_bptt_gpu.py runs, each with the branch of bptt_attention_kernel / bptt_chunks / bptt_plan it is there for.
+# tests/test_host_cpu.py pins every line against gvx_debug_bptt_plan on the CPU. --------------------------------------------------
+# sizes = (A, D, E, P, a, F, kl).  lengths: "full" (every row L), "ragged" (rows from 1 to L, both present when B >= 2), "short"
+# (every row shorter than L).  plan = (G, CH, chunks that hold positions, passes over the energies, over the dense-gradient
+# groups, over the convolution-gradient items, query / v in registers, Na, Nd) as gvx_debug_bptt_plan reports it.
+BpttCase = collections.namedtuple("BpttCase", "name B L T sizes lengths plan")
+BPTT_DEFAULT = (1024, 1024, 512, 256, 128, 32, 31)
+BPTT_ODD = (40, 56, 48, 20, 24, 12, 5)        # E + A = 88, A + E + D = 144: padded product columns; 512 % 24 != 0
+BPTT_EVEN = (32, 32, 32, 16, 16, 8, 3)        # 64 and 96 columns: no padding
+
+
+def _bp(name, B, L, T, sizes, lengths, plan):
+    return BpttCase(name, B, L, T, sizes, lengths, plan)
+
+
+_DEF_N = (1536, 2560)
+_ODD_N = (96, 160)
+BPTT_CASES = [
+    # default layer sizes.  One chunk and T = 1 (ya0 and w_prev both NULL, no products launch of the attention cell)
+    _bp("def_1x1x1", 1, 1, 1, BPTT_DEFAULT, "full", (1, 1, 1, 1, 1, 1, 1) + _DEF_N),
+    _bp("def_2x5x3", 2, 5, 3, BPTT_DEFAULT, "ragged", (2, 3, 2, 1, 1, 1, 1) + _DEF_N),
+    # L = 33: G = 8, CH = 5, the eighth chunk is empty; kl = 31 reaches three chunks to each side
+    _bp("def_3x33x4", 3, 33, 4, BPTT_DEFAULT, "ragged", (8, 5, 7, 1, 1, 1, 1) + _DEF_N),
+    _bp("def_32x128x3", 32, 128, 3, BPTT_DEFAULT, "ragged", (8, 16, 8, 1, 1, 1, 1) + _DEF_N),
+    # CH a = 32 x 128 = 4096: the last L of one energy pass; 257, 300: the reload of the second pass
+    _bp("def_5x256x3", 5, 256, 3, BPTT_DEFAULT, "ragged", (8, 32, 8, 1, 1, 1, 1) + _DEF_N),
+    _bp("def_3x257x3", 3, 257, 3, BPTT_DEFAULT, "ragged", (8, 33, 8, 2, 1, 1, 1) + _DEF_N),
+    _bp("def_2x300x3", 2, 300, 3, BPTT_DEFAULT, "short", (8, 38, 8, 2, 1, 1, 1) + _DEF_N),
+    # near the LDS limit, and the largest L the argument check accepts (162580 of 163840 bytes; 665 needs 164128)
+    _bp("def_2x600x2", 2, 600, 2, BPTT_DEFAULT, "ragged", (8, 75, 8, 3, 1, 1, 1) + _DEF_N),
+    _bp("def_1x664x2", 1, 664, 2, BPTT_DEFAULT, "full", (8, 83, 8, 3, 1, 1, 1) + _DEF_N),
+] + [
+    # L = 1 .. 4: one chunk; 5 .. 28: fewer than eight (CH = 4 at 8, 28; 3 at 9); 29, 31, 32: eight chunks of 4
+    _bp("odd_L%d" % L, 3, L, 3, BPTT_ODD, "ragged", plan + _ODD_N)
+    for L, plan in ((1, (1, 1, 1, 1, 1, 1, 0)), (2, (1, 2, 1, 1, 1, 1, 0)), (3, (1, 3, 1, 1, 1, 1, 0)), (4, (1, 4, 1, 1, 1, 1, 0)),
+                    (5, (2, 3, 2, 1, 1, 1, 0)), (8, (2, 4, 2, 1, 1, 1, 0)), (9, (3, 3, 3, 1, 1, 1, 0)), (28, (7, 4, 7, 1, 1, 1, 0)),
+                    (29, (8, 4, 8, 1, 1, 1, 0)), (31, (8, 4, 8, 1, 1, 1, 0)), (32, (8, 4, 8, 1, 1, 1, 0)))
+] + [
+    # every row shorter than L (the last chunk holds only padding), all rows full
+    _bp("odd_short", 4, 9, 3, BPTT_ODD, "short", (3, 3, 3, 1, 1, 1, 0) + _ODD_N),
+    _bp("odd_full", 4, 9, 3, BPTT_ODD, "full", (3, 3, 3, 1, 1, 1, 0) + _ODD_N),
+    # T = 1, T = 2 (one products launch of the attention cell), the longest T of the table
+    _bp("odd_T1", 3, 9, 1, BPTT_ODD, "ragged", (3, 3, 3, 1, 1, 1, 0) + _ODD_N),
+    _bp("odd_T2", 3, 9, 2, BPTT_ODD, "ragged", (3, 3, 3, 1, 1, 1, 0) + _ODD_N),
+    _bp("odd_T6", 3, 9, 6, BPTT_ODD, "ragged", (3, 3, 3, 1, 1, 1, 0) + _ODD_N),
+    # B = 1, 2, 31, 32 (3 above)
+    _bp("odd_B1", 1, 9, 2, BPTT_ODD, "full", (3, 3, 3, 1, 1, 1, 0) + _ODD_N),
+    _bp("odd_B2", 2, 9, 2, BPTT_ODD, "ragged", (3, 3, 3, 1, 1, 1, 0) + _ODD_N),
+    _bp("odd_B31", 31, 9, 2, BPTT_ODD, "ragged", (3, 3, 3, 1, 1, 1, 0) + _ODD_N),
+    _bp("odd_B32", 32, 9, 2, BPTT_ODD, "ragged", (3, 3, 3, 1, 1, 1, 0) + _ODD_N),
+    # attention dim, filters, kernel size.  a = 1 / F = 1 / kl = 1; a = 16 (divides 512) with the product columns unpadded
+    _bp("a1_F1_kl1", 3, 9, 3, (32, 32, 32, 16, 1, 1, 1), "ragged", (3, 3, 3, 1, 1, 1, 1, 64, 96)),
+    _bp("a16_F8_kl3", 3, 9, 3, BPTT_EVEN, "ragged", (3, 3, 3, 1, 1, 1, 1, 64, 96)),
+    # a = 100 (512 % 100 != 0): halo of kl = 31 over three chunks of 5; CH a = 42 x 100 > 4096: second energy pass with per-item q / v
+    _bp("a100_F32_kl31", 3, 33, 3, (40, 56, 48, 20, 100, 32, 31), "ragged", (8, 5, 7, 1, 1, 1, 0, 96, 160)),
+    _bp("a100_L330", 2, 330, 2, (40, 56, 48, 20, 100, 32, 31), "ragged", (8, 42, 8, 2, 1, 1, 0, 96, 160)),
+    # a = 256 fills the dense-gradient pass exactly (a x 4 groups = 2 x 512); F x 2 x kl = 2112 > 2048: second pass of the
+    # convolution gradient; CH a = 17 x 256 > 4096: second energy pass with a | 512
+    _bp("a256_F32_kl33", 3, 40, 3, (32, 32, 32, 16, 256, 32, 33), "ragged", (8, 5, 8, 1, 1, 2, 1, 64, 96)),
+    _bp("a256_L136", 2, 136, 2, (32, 32, 32, 16, 256, 32, 33), "ragged", (8, 17, 8, 2, 1, 2, 1, 64, 96)),
+    # padded product columns at large layer sizes (E + A = 1544 -> 1568, A + E + D = 2584 -> 2592)
+    _bp("big_odd_N", 2, 12, 2, (1032, 1040, 512, 256, 128, 32, 31), "ragged", (3, 4, 3, 1, 1, 1, 1, 1568, 2592)),
+]
+BPTT_BY_NAME = {c.name: c for c in BPTT_CASES}
+# the 32-row cases whose rows 0 .. 4 are recomputed as a call of their own (bit-equal: no summation order depends on B)
+BPTT_ROW_CASES = ["def_32x128x3", "odd_B32"]
+# handed over once more with a dense [T][B][E] copy of the contexts (ctx_ts = B E, ctx_bs = E)
+BPTT_STRIDE_CASES = ["def_3x33x4", "odd_L9", "a100_F32_kl31"]
+BPTT_L_LIMIT = 664   # default layer sizes: the largest L gvx_train_decoder_bptt accepts (the attention launch's 160 KiB of LDS)
+
+# encoder BiLSTM walk (gvx_train_encoder_lstm_bptt / _resident): plan = (workgroups per direction, LDS bytes, the resident entry
+# point takes the resident walk, trips of the kernels' loop over batch rows)
+EncBpttCase = collections.namedtuple("EncBpttCase", "name B L H lengths plan")
+ENC_BPTT_CASES = [
+    # H = 8 (two workgroups per direction, the scalar h_prev loop: H % 32 != 0), L = 1, B = 1
+    EncBpttCase("H8_1x1", 1, 1, 8, "full", (2, 1024, 1, 1)),
+    EncBpttCase("H8_3x2", 3, 2, 8, "ragged", (2, 1024, 1, 1)),
+    EncBpttCase("H8_64x150", 64, 150, 8, "short", (2, 1024, 1, 2)),
+    EncBpttCase("H24_3x21", 3, 21, 24, "ragged", (6, 3072, 1, 1)),
+    EncBpttCase("H24_32x21", 32, 21, 24, "full", (6, 3072, 1, 1)),
+    # B = 33, 64: the second trip of `for (b = b0; b < B; b += 32)`
+    EncBpttCase("H24_33x21", 33, 21, 24, "ragged", (6, 3072, 1, 2)),
+    EncBpttCase("H24_64x21", 64, 21, 24, "short", (6, 3072, 1, 2)),
+    # default size
+    EncBpttCase("H256_1x150", 1, 150, 256, "full", (64, 32768, 1, 1)),
+    EncBpttCase("H256_3x21", 3, 21, 256, "ragged", (64, 32768, 1, 1)),
+    EncBpttCase("H256_32x150", 32, 150, 256, "ragged", (64, 32768, 1, 1)),
+    EncBpttCase("H256_33x21", 33, 21, 256, "ragged", (64, 32768, 1, 2)),
+    EncBpttCase("H256_64x2", 64, 2, 256, "full", (64, 32768, 1, 2)),
+    # H = 384: the last size of the resident walk (192 workgroups, 48 KiB); 392: the launch per step from both entry points
+    EncBpttCase("H384_3x21", 3, 21, 384, "ragged", (96, 49152, 1, 1)),
+    EncBpttCase("H384_33x2", 33, 2, 384, "short", (96, 49152, 1, 2)),
+    EncBpttCase("H392_3x21", 3, 21, 392, "ragged", (98, 50176, 0, 1)),
+    EncBpttCase("H392_1x1", 1, 1, 392, "full", (98, 50176, 0, 1)),
+]
+
+
+def bptt_lengths(kind, B, L):
+    """Token lengths of a case, longest first (as the collate function sorts a batch)."""
+    if kind == "full" or L == 1:
+        return [L] * B
+    if kind == "short":
+        return sorted((max(1, (L - 1) - (i * 7) % max(1, L - 1)) for i in range(B)), reverse=True)
+    if B == 1:
+        return [L]
+    return sorted([L, 1] + [1 + (i * 5 + 3) % L for i in range(B - 2)], reverse=True)
+
+
+def bptt_args_for_plan(B, L, T, sizes):
+    """An argument block with the case's sizes and non-null dummy pointers: for the host-only queries, which never dereference."""
+    from genvox_amd import _lib
+
+    a = _lib.gvx_bptt_decoder_args()
+    a.B, a.L, a.T = B, L, T
+    a.A, a.D, a.E, a.P, a.a, a.F, a.kl = sizes
+    a.att_scale = a.dec_scale = 1.0
+    for n, t in _lib.gvx_bptt_decoder_args._fields_:
+        if t is C.c_void_p:
+            setattr(a, n, 256)
+    return a
+
+
+def bptt_plan(lib, args):
+    """(status, [G, CH, chunks, energy passes, dense passes, conv passes, q in registers, Na, Nd, LDS bytes]) of
+    gvx_debug_bptt_plan.  Host arithmetic only; the export is in neither the public header nor _lib.SIGNATURES."""
+    fn = lib.gvx_debug_bptt_plan
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+    out = (C.c_int * 10)()
+    rc = fn(C.byref(args) if args is not None else None, out)
+    return rc, list(out)
+
+
+def enc_bptt_plan(lib, B, H, resident):
+    """(status, [workgroups per direction, LDS bytes, resident walk taken, row trips]) of gvx_debug_enc_bptt_plan."""
+    fn = lib.gvx_debug_enc_bptt_plan
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int] * 3 + [C.POINTER(C.c_int)]
+    out = (C.c_int * 4)()
+    rc = fn(B, H, 1 if resident else 0, out)
+    return rc, list(out)

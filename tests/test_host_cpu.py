@@ -192,6 +192,62 @@ def test_gemm_dispatch_plan_of_every_listed_shape(monkeypatch):
     assert plan(32, 4096, 2560, scratch_bytes=32 * 4096 * 4 * 5 - 1)[2] == 4
 
 
+def test_bptt_plan_of_every_listed_shape():
+    """Where the two back-propagation calls land is host arithmetic; gvx_debug_bptt_plan / gvx_debug_enc_bptt_plan report it from
+    the functions and constants the launches use (bptt_chunks, bptt_attn_lds_floats, the per-thread item counts of
+    bptt_attention_kernel, the resident-walk condition).  Every shape of tests/test_bptt_gpu.py must still reach the branch its line
+    names, and each threshold is read one step to either side."""
+    from tests.helpers import (BPTT_CASES, BPTT_DEFAULT, BPTT_L_LIMIT, BPTT_ROW_CASES, BPTT_STRIDE_CASES, BPTT_BY_NAME, ENC_BPTT_CASES,
+                               bptt_args_for_plan, bptt_plan, enc_bptt_plan)
+
+    lib = _lib.load()
+    assert len({c.name for c in BPTT_CASES}) == len(BPTT_CASES) and set(BPTT_ROW_CASES + BPTT_STRIDE_CASES) <= set(BPTT_BY_NAME)
+    for c in BPTT_CASES:
+        rc, out = bptt_plan(lib, bptt_args_for_plan(c.B, c.L, c.T, c.sizes))
+        assert rc == 0 and tuple(out[:9]) == c.plan and 0 < out[9] <= 160 * 1024, (c, rc, out)
+        assert lib.gvx_train_decoder_bptt_workspace_bytes(C.byref(bptt_args_for_plan(c.B, c.L, c.T, c.sizes))) > 0, c
+    plans = [c.plan for c in BPTT_CASES]
+    # the table reaches: one chunk, fewer than eight, eight, an empty last chunk; one, two and three energy passes with and without
+    # the query in registers; the second pass of the convolution gradient; padded and unpadded product columns
+    assert {p[0] for p in plans} >= {1, 2, 3, 7, 8} and any(p[2] < p[0] for p in plans)
+    assert {(p[3], p[6]) for p in plans} >= {(1, 0), (1, 1), (2, 0), (2, 1), (3, 1)} and {p[5] for p in plans} == {1, 2}
+    assert any(c.sizes[2] + c.sizes[0] != c.plan[7] for c in BPTT_CASES) and any(c.sizes[2] + c.sizes[0] == c.plan[7] for c in BPTT_CASES)
+    assert {c.T for c in BPTT_CASES} >= {1, 2, 3} and {c.B for c in BPTT_CASES} >= {1, 2, 3, 31, 32}
+
+    def plan(L, sizes=BPTT_DEFAULT, B=2, T=2):
+        return bptt_plan(lib, bptt_args_for_plan(B, L, T, sizes))
+
+    # bptt_chunks: G = min(8, ceil(L / 4)); the first L with an empty chunk
+    assert [plan(L)[1][:3] for L in (4, 5, 28, 29, 32, 33, 36)] == [[1, 4, 1], [2, 3, 2], [7, 4, 7], [8, 4, 8], [8, 4, 8], [8, 5, 7], [8, 5, 8]]
+    # energies: 8 items per thread and pass, 512 threads
+    assert plan(256)[1][3] == 1 and plan(257)[1][3] == 2 and plan(512)[1][3] == 2 and plan(513)[1][3] == 3
+    a256 = lambda kl, F=32, a=256: (32, 32, 32, 16, a, F, kl)
+    assert plan(128, a256(33))[1][3] == 1 and plan(129, a256(33))[1][3] == 2
+    # dense-gradient groups: a x 4 against 2 x 512 (a <= 256: always one pass); convolution-gradient items: F x 2 x kl against 4 x 512
+    assert plan(9, a256(31))[1][4:6] == [1, 1] and plan(9, a256(33))[1][4:6] == [1, 2] and plan(9, a256(33, F=31))[1][5] == 1
+    assert [plan(9, a256(3, a=a))[1][6] for a in (1, 16, 24, 100, 128, 256)] == [1, 1, 0, 0, 1, 1]
+    # the LDS limit of the attention launch, from the formula: both sides
+    ok, refused = plan(BPTT_L_LIMIT), plan(BPTT_L_LIMIT + 1)
+    assert ok[0] == 0 and ok[1][9] == 162580 and refused[0] == -2 and refused[1][9] == 164128 and b"LDS" in lib.gvx_last_error()
+    assert lib.gvx_train_decoder_bptt_workspace_bytes(C.byref(bptt_args_for_plan(2, BPTT_L_LIMIT + 1, 2, BPTT_DEFAULT))) == 0
+    # refused sizes (the GPU tests hand the same blocks to the call itself)
+    for bad in (dict(B=0), dict(B=33), dict(T=0), dict(L=0), dict(A=1028), dict(D=1028), dict(a=257), dict(a=0), dict(F=33), dict(F=0), dict(kl=30), dict(kl=0)):
+        a = bptt_args_for_plan(2, 9, 2, BPTT_DEFAULT)
+        for k, v in bad.items():
+            setattr(a, k, v)
+        assert bptt_plan(lib, a)[0] == -2 and lib.gvx_train_decoder_bptt_workspace_bytes(C.byref(a)) == 0, bad
+    assert bptt_plan(lib, None)[0] == -1
+    # encoder walk
+    for c in ENC_BPTT_CASES:
+        assert enc_bptt_plan(lib, c.B, c.H, True) == (0, list(c.plan)), c
+        assert enc_bptt_plan(lib, c.B, c.H, False) == (0, [c.plan[0], c.plan[1], 0, c.plan[3]]), c
+        assert lib.gvx_train_encoder_lstm_bptt_workspace_bytes(c.B, c.H) > 0
+    assert {c.plan[2] for c in ENC_BPTT_CASES} == {0, 1} and {c.plan[3] for c in ENC_BPTT_CASES} == {1, 2}
+    assert enc_bptt_plan(lib, 32, 384, True)[1][2:] == [1, 1] and enc_bptt_plan(lib, 33, 392, True)[1][2:] == [0, 2]
+    assert enc_bptt_plan(lib, 1, 1280, True) == (0, [320, 160 * 1024, 0, 1]) and enc_bptt_plan(lib, 1, 1288, True)[0] == -2
+    assert enc_bptt_plan(lib, 1, 12, True)[0] == -2 and enc_bptt_plan(lib, 1, 0, True)[0] == -2 and enc_bptt_plan(lib, 0, 8, True)[0] == -2
+
+
 # ---- rows a16 / f1 / f2 pinned by files the reference itself produced (tests/golden/make_fixtures.py host) -----------
 GOLDEN = os.path.join(REPO, "tests", "golden")
 
