@@ -57,6 +57,12 @@ def get_inverse_mel_filter(mel_basis: np.ndarray) -> np.ndarray:
     return np.linalg.pinv(mel_basis)
 
 
+def keep_by_duration(durations: Sequence[float], config: AudioConfig) -> List[int]:
+    """Indices of the recordings whose duration (seconds, after trimming) lies in ``[min_wav_duration, max_wav_duration]``: the
+    filter of the reference's ``DataPreprocessor`` (core/processors.py:152)."""
+    return [i for i, d in enumerate(durations) if config.min_wav_duration <= d and d <= config.max_wav_duration]
+
+
 class _RowLengths(NamedTuple):
     """Frame counts of a ragged batch that passed AudioProcessor._check_lengths: host ints and the device int32 [B] the kernels read."""
     host: List[int]
@@ -253,6 +259,162 @@ class AudioProcessor:
             sig = (sig / max(np.abs(np.min(sig)), np.abs(np.max(sig)))).astype(np.float32)   # utils/audio/base.py:20-22
         mel = self.wav_to_mel(torch.from_numpy(np.ascontiguousarray(sig, dtype=np.float32))[None])
         np.save(output_path, mel[0].cpu().numpy())
+
+    # ------------------------------------------------------------------ recordings -> mel batch (rows of different lengths)
+    ROW_EMPTY, ROW_SHORT, ROW_SILENT, ROW_CUT = 1, 2, 4, 8   # GVX_WAV_ROW_* of include/genvox_amd.h
+    _ROW_WHY = {1: "nothing is left of it after trimming silence", 2: "it is shorter than one frame ({n_fft} samples)",
+                4: "every sample of it is zero", 8: "it has more frames than the output was sized for"}
+
+    def _pcm_batch(self, pcm, sample_lengths=None) -> Tuple[torch.Tensor, List[int]]:
+        """Padded PCM batch on the device and the rows' sample counts on the host.  ``pcm``: a [B, n_max] tensor / array (int16,
+        or floating point with full scale 1.0) with ``sample_lengths``, or a list of 1-D arrays of their own lengths."""
+        if isinstance(pcm, (list, tuple)):
+            rows = [np.asarray(r.cpu() if isinstance(r, torch.Tensor) else r) for r in pcm]
+            if not rows:
+                raise ValueError("an empty batch of recordings")
+            for b, r in enumerate(rows):
+                if r.ndim != 1:
+                    raise ValueError(f"row {b}: a recording is a 1-D array of samples, got shape {r.shape} (mix channels down first)")
+            kinds = {np.int16 if r.dtype == np.int16 else (np.float32 if r.dtype.kind == "f" else None) for r in rows}
+            if None in kinds or len(kinds) != 1:
+                raise ValueError("recordings must all be int16 or all be floating point, got " + ", ".join(sorted({str(r.dtype) for r in rows})))
+            if sample_lengths is not None:
+                raise ValueError("sample_lengths goes with a padded [B, n_max] batch; a list of arrays carries its own lengths")
+            lengths = [int(r.shape[0]) for r in rows]
+            host = np.zeros((len(rows), max(1, max(lengths))), dtype=kinds.pop())
+            for b, r in enumerate(rows):
+                host[b, : lengths[b]] = r
+            return torch.from_numpy(host).to(self.device), lengths
+        x = torch.as_tensor(pcm)
+        if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+            raise ValueError(f"a PCM batch is [B, n_max], got shape {tuple(x.shape)}")
+        if x.dtype != torch.int16:
+            if not x.dtype.is_floating_point:
+                raise ValueError(f"PCM samples must be int16 or floating point, got {x.dtype}")
+            x = x.to(torch.float32)
+        if sample_lengths is None:
+            raise ValueError("a padded PCM batch needs sample_lengths")
+        lengths = [int(v) for v in (sample_lengths.tolist() if isinstance(sample_lengths, (torch.Tensor, np.ndarray)) else sample_lengths)]
+        if len(lengths) != x.shape[0]:
+            raise ValueError(f"{len(lengths)} sample lengths for a batch of {x.shape[0]} rows")
+        for b, n in enumerate(lengths):
+            if not 0 <= n <= x.shape[1]:
+                raise ValueError(f"sample length {n} of row {b} is outside [0, {x.shape[1]}]")
+        return x.to(self.device).contiguous(), lengths
+
+    def _trim_bounds(self, x: torch.Tensor, lengths: List[int], trim: bool) -> torch.Tensor:
+        lib = self._ensure()
+        B, n_max = x.shape
+        lens = torch.tensor(lengths, dtype=torch.int32, device=self.device)
+        bounds = torch.empty(B, 2, dtype=torch.int32, device=self.device)
+        _lib.check(lib.gvx_wav_trim_bounds(x.data_ptr(), 0 if x.dtype == torch.int16 else 1, B, n_max, lens.data_ptr(),
+                                           int(self.config.sampling_rate), float(self.config.trim_dbfs) if trim else float("nan"),
+                                           bounds.data_ptr(), self._stream()))
+        return bounds
+
+    def trim_bounds(self, pcm, sample_lengths=None) -> torch.Tensor:
+        """Silence bounds of every row: int32 [B, 2] on the device, row b keeps ``pcm[b, left:right]``.
+
+        The reference's ``get_non_silent_boundary`` (utils/__init__.py:56-76) at ``config.trim_dbfs``: 20 ms chunks walked from the
+        row's start and, aligned to its last sample, from its end.  A row in which no chunk reaches the threshold comes back with
+        ``left >= right`` (the reference asserts on it).  Nothing synchronises."""
+        x, lengths = self._pcm_batch(pcm, sample_lengths)
+        return self._trim_bounds(x, lengths, True)
+
+    def wav_to_mel_ragged(self, pcm, sample_lengths=None, trim: Optional[bool] = None, normalize: Optional[bool] = None,
+                          drop_bad: bool = False, _durations: bool = False):
+        """Recordings of different lengths -> ``(mel_padded [B, n_mels, T], mel_lengths [B] int64, gate_padded [B, T])`` on the
+        device: the mel side of the batch ``Tacotron2.forward`` / ``train_step`` consume, in one set of launches.
+
+        ``pcm`` is a padded ``[B, n_max]`` batch with ``sample_lengths`` (what lies behind a row's length may hold anything), or a
+        list of 1-D arrays; int16 (full scale 32767, as ``scipy.io.wavfile.read`` gives) or floating point (full scale 1.0).
+        ``trim`` / ``normalize`` default to ``config.trim_silence`` / ``config.normalize``.  Per row: the reference's silence bounds
+        (see ``trim_bounds``), peak normalisation over the kept samples as ``float32(double(y) / double(peak))`` fused into the
+        STFT's loads (``normalize_signal``, utils/audio/base.py:20-22 - except that the peak of an int16 row that holds -32768 is
+        32768: the reference's int16 ``abs`` wraps to -32768 there and flips the signal, which is not reproduced), then the
+        ``convert_wav2mel`` chain.  Row b equals ``wav_to_mel`` on its own trimmed, normalised signal bit for bit; frames behind
+        ``mel_lengths[b]`` are exact zeros and ``gate_padded`` is 1 from each row's last frame on, as ``TextMelCollateFn`` lays them out.
+
+        The outputs' time stride is computed on the host from the UNTRIMMED lengths (an upper bound), so no launch waits for the
+        device; the one synchronisation of the call is the copy of the B frame counts and status words back to the host at the end,
+        after which the result is narrowed to the longest row.
+
+        A row that is empty after trimming, shorter than one frame or all zeros raises ``ValueError`` naming the row (its output is
+        zeros, never NaN).  With ``drop_bad=True`` such rows are left out instead and the return value gains a fourth member, the
+        list of their indices."""
+        lib = self._ensure()
+        c = self.config
+        x, lengths = self._pcm_batch(pcm, sample_lengths)
+        trim = c.trim_silence if trim is None else trim
+        normalize = c.normalize if normalize is None else normalize
+        B, n_max = x.shape
+        T = max(1, (max(lengths) - c.filter_length) // c.hop_length + 1)
+        if len(self._dev_consts) < 3:
+            self._dev_consts = self._dev_consts + (torch.from_numpy(np.ascontiguousarray(self.mel_basis)).to(self.device),)
+        bounds = self._trim_bounds(x, lengths, bool(trim))
+        need = lib.gvx_wav_to_mel_ragged_workspace_bytes(self._plan, B, n_max, c.n_mels)
+        if need == 0:
+            raise _lib.GvxError("could not plan the wav -> mel workspace: " + lib.gvx_last_error().decode())
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        mel = torch.empty(B, c.n_mels, T, device=self.device)
+        gate = torch.empty(B, T, device=self.device)
+        words = torch.empty(2, B, dtype=torch.int32, device=self.device)   # frame counts, status words
+        _lib.check(lib.gvx_wav_to_mel_ragged(self._plan, x.data_ptr(), 0 if x.dtype == torch.int16 else 1, self._dev_consts[0].data_ptr(),
+                                             self._dev_consts[2].data_ptr(), B, n_max, bounds.data_ptr(), int(bool(normalize)), c.n_mels,
+                                             0 if c.log_func == "np.log" else 1, float(c.ref_level_db), T, mel.data_ptr(), gate.data_ptr(),
+                                             words[0].data_ptr(), words[1].data_ptr(), self._ws.data_ptr(), self._ws.numel(), self._stream()))
+        host = torch.cat([words, bounds.t()]).cpu() if _durations else words.cpu()   # the call's one synchronisation
+        frames, status = host[0].tolist(), host[1].tolist()
+        bad = [b for b in range(B) if status[b] != 0]
+        if bad and not drop_bad:
+            b = bad[0]
+            why = self._ROW_WHY.get(status[b], f"status {status[b]}").format(n_fft=c.filter_length)
+            raise ValueError(f"row {b} of the batch gives no mel: {why}" + (f" (and {len(bad) - 1} more: rows {bad[1:]})" if len(bad) > 1 else ""))
+        keep = [b for b in range(B) if status[b] == 0]
+        if bad:
+            idx = torch.tensor(keep, dtype=torch.long, device=self.device)
+            mel, gate = mel.index_select(0, idx), gate.index_select(0, idx)
+        T_used = max([frames[b] for b in keep], default=0)
+        if T_used < T:
+            mel, gate = mel[:, :, :T_used].contiguous(), gate[:, :T_used].contiguous()
+        out = (mel, torch.tensor([frames[b] for b in keep], dtype=torch.long, device=self.device), gate)
+        if drop_bad:
+            out = out + (bad,)
+        if _durations:
+            out = out + ([(host[3][b].item() - host[2][b].item()) / c.sampling_rate for b in range(B)],)
+        return out
+
+    def convert_wav2mel_batch(self, inputs: Sequence, output_paths: Optional[Sequence[str]] = None, trim: Optional[bool] = None,
+                              normalize: Optional[bool] = None, drop_bad: bool = False):
+        """The many-files form of ``convert_wav2mel``: wav paths or sample arrays -> ``(mels, durations)``.
+
+        ``mels[i]`` is the float32 ``[n_mels, T_i]`` array ``convert_wav2mel`` would have written for recording i after the
+        reference's silence trimming (``None`` for a recording that gives no mel, with ``drop_bad=True``; otherwise such a
+        recording raises ``ValueError``), written to ``output_paths[i]`` as .npy when paths are given.  ``durations[i]`` is the
+        recording's length in seconds after trimming, the number the reference's ``DataPreprocessor`` holds against
+        ``min_wav_duration`` / ``max_wav_duration`` (core/processors.py:143-152): see ``keep_by_duration``.  All recordings go
+        through one ``wav_to_mel_ragged`` call."""
+        import scipy.io.wavfile
+
+        rows = []
+        for i, item in enumerate(inputs):
+            if isinstance(item, (str, bytes)) or hasattr(item, "__fspath__"):
+                fs, item = scipy.io.wavfile.read(item)
+                assert fs == self.config.sampling_rate, f"wav file ({inputs[i]}) sampling rate ({fs}) does not match with config ({self.config.sampling_rate})"
+            rows.append(item)
+        if output_paths is not None and len(output_paths) != len(rows):
+            raise ValueError(f"{len(output_paths)} output paths for {len(rows)} recordings")
+        mel, mel_lengths, _, dropped, durations = self.wav_to_mel_ragged(rows, trim=trim, normalize=normalize, drop_bad=True, _durations=True)
+        if dropped and not drop_bad:
+            raise ValueError(f"recordings {dropped} give no mel (empty after trimming, shorter than one frame, or all zeros)")
+        host, counts = mel.cpu().numpy(), mel_lengths.tolist()
+        mels: List[Optional[np.ndarray]] = [None] * len(rows)
+        for k, i in enumerate(i for i in range(len(rows)) if i not in set(dropped)):
+            mels[i] = np.ascontiguousarray(host[k, :, : counts[k]])
+            if output_paths is not None:
+                np.save(output_paths[i], mels[i])
+        return mels, durations
 
     # ------------------------------------------------------------------ reference surface
     def convert_mel2wav_batch(self, mels: torch.Tensor, n_iter: int = 32, mel_lengths=None):

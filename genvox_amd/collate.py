@@ -29,3 +29,27 @@ class TextMelCollateFn:
             out["gate_padded"][row, mel.shape[1] - 1:] = 1
             out["mel_lengths"][row] = mel.shape[1]
         return out
+
+
+class WavTextCollateFn:
+    """``TextMelCollateFn`` for items that carry the recording instead of its features: ``{"tokens", "wav"}`` (``wav`` a 1-D int16
+    or floating point array) -> the same dict, same row order, dtypes and shapes.  The mel side (``mel_padded``, ``gate_padded``,
+    ``mel_lengths``) comes from one ``AudioProcessor.wav_to_mel_ragged`` call - silence trimming and normalisation as the audio
+    config says - and stays on the processor's device; the token side is built on the host as before.  A recording that gives no
+    mel raises ``ValueError`` (the index it names is the row of the sorted batch)."""
+
+    def __init__(self, audio_processor):
+        self.audio_processor = audio_processor
+
+    def __call__(self, batch: List[Dict]) -> Dict[str, torch.Tensor]:
+        order = [int(i) for i in np.argsort([x["tokens"].shape[0] for x in batch])[::-1]]   # TextMelCollateFn's expression
+        L = batch[order[0]]["tokens"].shape[0]
+        B = len(batch)
+        out = {"token_padded": torch.zeros(B, L, dtype=torch.long), "token_lengths": torch.zeros(B, dtype=torch.long)}
+        for row, i in enumerate(order):
+            tok = torch.as_tensor(batch[i]["tokens"])
+            out["token_padded"][row, : tok.shape[0]] = tok
+            out["token_lengths"][row] = tok.shape[0]
+        mel, mel_lengths, gate = self.audio_processor.wav_to_mel_ragged([batch[i]["wav"] for i in order])[:3]
+        out.update(mel_padded=mel, gate_padded=gate, mel_lengths=mel_lengths)
+        return out

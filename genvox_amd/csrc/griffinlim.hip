@@ -250,8 +250,37 @@ __global__ void gl_ola_kernel(const float* fr, const float* win, const float* ws
     y[(long)b * n + i] = w > 1.17549435e-38f ? s / w : s;
 }
 
+// ---- rows of the ragged wav -> mel front-end (gvx_wav_to_mel_ragged) ------------------------------------------------------
+// A PCM row is int16 or float32.  wav_row_plan_kernel turns each row's bounds into rows[b] = {first sample, frames T_b} and its
+// peak into a double; every later kernel reads those, so all of them agree on which frames exist.
+struct WavRows {
+    const int32_t* rows;   // [B][2]: left_b, T_b (0 for a row that has no frame)
+    const double* peak;    // [B]: max |sample| over [left_b, right_b), as the divisor of normalize_signal
+    int normalize;
+};
+
+// normalize_signal (utils/audio/base.py:20-22): float32(double(y) / double(peak)); without it the sample as float32
+template <typename PCM>
+__device__ __forceinline__ float pcm_sample(PCM v, double peak, bool normalize) {
+    return normalize ? (float)((double)v / peak) : (float)v;
+}
+
 // xf[b][t][k] = win[k] * y[b][t*hop + k]      (utils/audio/base.py:58-69)
-__global__ void gl_frame_kernel(const float* y, const float* win, float* xf, int n_fft, int hop, int T, long n) {
+// RAGGED: grid (T, B); row b's frame t starts at sample left_b + t*hop and is read through pcm_sample; frames t >= T_b are zeros
+template <bool RAGGED, typename PCM>
+__global__ void gl_frame_kernel(const PCM* y, const float* win, float* xf, int n_fft, int hop, int T, long n, WavRows wr) {
+    if constexpr (RAGGED) {
+        const int b = blockIdx.y, t = blockIdx.x;
+        float* o = xf + ((long)b * T + t) * n_fft;
+        if (t >= wr.rows[2 * b + 1]) {
+            for (int k = threadIdx.x; k < n_fft; k += blockDim.x) o[k] = 0.f;
+            return;
+        }
+        const PCM* yb = y + (long)b * n + wr.rows[2 * b] + (long)t * hop;
+        const double peak = wr.peak[b];
+        for (int k = threadIdx.x; k < n_fft; k += blockDim.x) o[k] = win[k] * pcm_sample(yb[k], peak, wr.normalize != 0);
+        return;
+    } else {
     const long bt = blockIdx.x;  // b*T + t
     const int b = (int)(bt / T), t = (int)(bt - (long)b * T);
     const float* yb = y + (long)b * n + (long)t * hop;
@@ -264,6 +293,7 @@ __global__ void gl_frame_kernel(const float* y, const float* win, float* xf, int
         const float4 w = *reinterpret_cast<const float4*>(win + k);
         const float4 v = *reinterpret_cast<const float4*>(yb + k);  // hop % 4 == 0 and n_fft % 4 == 0 keep this aligned
         *reinterpret_cast<float4*>(o + k) = make_float4(w.x * v.x, w.y * v.y, w.z * v.z, w.w * v.w);
+    }
     }
 }
 
@@ -341,14 +371,19 @@ __global__ void pad_rows_kernel(const float* src, float* dst, int rows, int cols
 }
 
 // mel_db[b][m][t] = log(max(amin, mel_t[(b,t)][m])) - log(max(amin, ref))      (utils/audio/base.py:24-36, power=False, scale=1)
-__global__ void amp_to_db_transpose_kernel(const float* mel_t, float* mel_db, int M, int T, int log10_kind, float log_ref) {
+// RAGGED: frames t >= T_b = rows[b][1] of mel_db are exact zeros (the collate's padding, not log(amin)), and the workgroups of the
+// first mel tile also write the gate target of the batch: gate[b][t] = 1 from the row's last frame on, 0 before (gate may be null)
+template <bool RAGGED>
+__global__ void amp_to_db_transpose_kernel(const float* mel_t, float* mel_db, int M, int T, int log10_kind, float log_ref,
+                                           const int32_t* rows, float* gate) {
     __shared__ float tile[32][33];
     const int b = blockIdx.z, t0 = blockIdx.y * 32, m0 = blockIdx.x * 32;
     const int tx = threadIdx.x, ty = threadIdx.y;
+    const int Tb = RAGGED ? rows[2 * b + 1] : T;
     for (int r = ty; r < 32; r += 8) {
         const int t = t0 + r, m = m0 + tx;
         float v = 0.f;
-        if (t < T && m < M) {
+        if (t < Tb && m < M) {
             const float a = fmaxf(1e-5f, mel_t[((long)b * T + t) * M + m]);
             v = (log10_kind ? log10f(a) : logf(a)) - log_ref;
         }
@@ -359,6 +394,7 @@ __global__ void amp_to_db_transpose_kernel(const float* mel_t, float* mel_db, in
         const int m = m0 + r, t = t0 + tx;
         if (t < T && m < M) mel_db[((long)b * M + m) * T + t] = tile[tx][r];
     }
+    if (RAGGED && gate && m0 == 0 && ty == 0 && t0 + tx < T) gate[(long)b * T + t0 + tx] = t0 + tx >= Tb - 1 ? 1.f : 0.f;
 }
 
 // clip spurious samples, trim, peak, normalise to float32, IIR low-pass in float64 (core/processors.py:91-95,
@@ -923,16 +959,43 @@ __global__ __launch_bounds__(GLF_FRAMES * 64) void gl_forward_update_kernel(cons
 
 // frames of a signal -> |rfft(win * frame)| into rows padded to kp floats (kp >= 513, pad = 0): the magnitude input of the
 // mel GEMM (convert_wav2mel: stft + abs, core/processors.py:70-79) without the framed-signal and complex-spectrum round trips
-__global__ __launch_bounds__(GLF_FRAMES * 64) void stft_magnitude_kernel(const float* __restrict__ x, long n_samples, const float* __restrict__ win,
+// RAGGED: grid (ceil(T / 4), B), so a workgroup's four frames belong to one row; row b's frame t starts at sample left_b + t*256 of
+// its PCM row and is read through pcm_sample (the division by the peak happens in the load: no normalised copy of the batch exists).
+// Whether a frame exists is a test per wave (a frame is a wave): one with t >= T_b writes its padded magnitude row as zeros - the
+// GEMM reads every row - and leaves before it touches the twiddle table, so a workgroup wholly behind its row's end costs one store
+template <bool RAGGED, typename PCM>
+__global__ __launch_bounds__(GLF_FRAMES * 64) void stft_magnitude_kernel(const PCM* __restrict__ x, long n_samples, const float* __restrict__ win,
                                                                          const float2* __restrict__ tw, float* __restrict__ mag, int kp,
-                                                                         int T, long frames) {
+                                                                         int T, long frames, WavRows wr) {
     __shared__ __attribute__((aligned(16))) float2 fsm[GLF_FRAMES * FPAD];
     const int tid = threadIdx.x, j = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const long f = (long)blockIdx.x * GLF_FRAMES + wave;
-    const bool valid = f < frames;
+    long f;
+    bool valid;
     float2* buf = fsm + wave * FPAD;
     float2 v[8];
+    if constexpr (RAGGED) {
+        const int b = blockIdx.y, t = (int)blockIdx.x * GLF_FRAMES + wave;
+        if (t >= T) return;
+        f = (long)b * T + t;
+        if (t >= wr.rows[2 * b + 1]) {
+            float* row = mag + f * kp;
+            for (int k = j; k < kp; k += 64) row[k] = 0.f;
+            return;
+        }
+        valid = true;
+        const PCM* xb = x + (long)b * n_samples + wr.rows[2 * b] + (long)t * 256;
+        const double peak = wr.peak[b];
+        const bool norm = wr.normalize != 0;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const int n2 = 2 * (j + 64 * r);
+            const float2 w = *reinterpret_cast<const float2*>(win + n2);
+            v[r] = make_float2(w.x * pcm_sample(xb[n2], peak, norm), w.y * pcm_sample(xb[n2 + 1], peak, norm));
+        }
+    } else {
+    f = (long)blockIdx.x * GLF_FRAMES + wave;
+    valid = f < frames;
     if (valid) {
         const unsigned fu = (unsigned)f;
         const int b = (int)(fu / (unsigned)T), t = (int)(fu - (unsigned)b * (unsigned)T);
@@ -946,6 +1009,7 @@ __global__ __launch_bounds__(GLF_FRAMES * 64) void stft_magnitude_kernel(const f
     } else {
 #pragma unroll
         for (int r = 0; r < 8; ++r) v[r] = make_float2(0.f, 0.f);
+    }
     }
     fft512_wave<false>(v, buf, tw, j, true);
     wave_lds_fence();
@@ -966,6 +1030,114 @@ __global__ __launch_bounds__(GLF_FRAMES * 64) void stft_magnitude_kernel(const f
         }
         row[k] = out;
     }
+}
+
+// ---- silence bounds, peak and row plan of the ragged front-end --------------------------------------------------------------
+__device__ __forceinline__ long clamp_len(long v, long hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+
+// Is the chunk x[0, len) at or above the silence threshold?  dBFS (utils/__init__.py:44-54) is 20 log10(rms / full scale), so
+// dBFS >= trim_dbfs  <=>  sum x^2 >= len * thr with thr = full_scale^2 * 10^(trim_dbfs / 10).  int16: the sum is an exact 64-bit
+// integer (order independent) and the comparison is made once in double; float32 (full scale 1.0): double partial sums per lane,
+// added in a fixed butterfly.  One wave, every lane returns the same answer.
+template <typename PCM>
+__device__ __forceinline__ bool chunk_is_loud(const PCM* x, int len, double thr, int lane) {
+    if constexpr (sizeof(PCM) == 2) {
+        long long s = 0;
+        for (int i = lane; i < len; i += 64) { const int v = x[i]; s += (long long)(v * v); }
+        for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+        return (double)s >= (double)len * thr;
+    } else {
+        double s = 0.0;
+        for (int i = lane; i < len; i += 64) { const double v = (double)x[i]; s += v * v; }
+        for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+        return s >= (double)len * thr;
+    }
+}
+
+// get_non_silent_boundary (utils/__init__.py:56-76) per row, one workgroup of four waves per row: chunks of `chunk` samples are
+// walked from the row's start and - aligned to its last sample, as the reference walks the flipped signal - from its end, four at
+// a time (a wave takes a chunk of each walk), until both walks have met a chunk at or above the threshold.  bounds[b] = {start of
+// the first such chunk from the left, n_b - start of the first such chunk from the right}.  When no chunk passes, a walk ends on its
+// last chunk start like the reference's loop variable does (left >= right then: the caller's "empty row").  thr NaN: no trimming.
+template <typename PCM>
+__global__ __launch_bounds__(256) void wav_trim_bounds_kernel(const PCM* __restrict__ pcm, long n_max, const int32_t* __restrict__ sample_lengths,
+                                                              int chunk, double thr, int32_t* __restrict__ bounds) {
+    __shared__ int first[2];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const long n = clamp_len(sample_lengths[b], n_max);
+    if (thr != thr || n == 0) {
+        if (tid == 0) { bounds[2 * b] = 0; bounds[2 * b + 1] = (int32_t)n; }
+        return;
+    }
+    const PCM* x = pcm + (long)b * n_max;
+    const int nch = (int)((n + chunk - 1) / chunk);
+    if (tid < 2) first[tid] = nch;
+    __syncthreads();
+    bool done_l = false, done_r = false;
+    for (int c0 = 0; c0 < nch && !(done_l && done_r); c0 += 4) {
+        const int c = c0 + wave;
+        if (c < nch) {
+            const long lo = (long)c * chunk;
+            const int len = (int)(n - lo < chunk ? n - lo : chunk);
+            if (!done_l && chunk_is_loud(x + lo, len, thr, lane) && lane == 0) atomicMin(&first[0], c);
+            if (!done_r && chunk_is_loud(x + (n - lo - len), len, thr, lane) && lane == 0) atomicMin(&first[1], c);
+        }
+        __syncthreads();
+        done_l = first[0] < nch;
+        done_r = first[1] < nch;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const int cl = first[0] < nch ? first[0] : nch - 1, cr = first[1] < nch ? first[1] : nch - 1;
+        bounds[2 * b] = (int32_t)((long)cl * chunk);
+        bounds[2 * b + 1] = (int32_t)(n - (long)cr * chunk);
+    }
+}
+
+// max |sample| of row b over its clamped bounds (normalize_signal's max(|min|, |max|), utils/audio/base.py:20-22, without the
+// reference's int16 wrap of |-32768|): int16 as the integer, float32 as its bit pattern - both order like unsigned integers
+template <typename PCM>
+__global__ void wav_peak_bounds_kernel(const PCM* __restrict__ pcm, long n_max, const int32_t* __restrict__ bounds, unsigned int* peak_bits) {
+    const int b = blockIdx.y;
+    const long left = clamp_len(bounds[2 * b], n_max), right = clamp_len(bounds[2 * b + 1], n_max);
+    const PCM* x = pcm + (long)b * n_max;
+    unsigned int m = 0;
+    for (long i = left + (long)blockIdx.x * blockDim.x + threadIdx.x; i < right; i += (long)gridDim.x * blockDim.x) {
+        unsigned int a;
+        if constexpr (sizeof(PCM) == 2) { const int v = x[i]; a = (unsigned int)(v < 0 ? -v : v); }
+        else { const float v = fabsf(x[i]); a = v == v ? __float_as_uint(v) : 0u; }
+        m = a > m ? a : m;
+    }
+    for (int off = 32; off >= 1; off >>= 1) { const unsigned int o = __shfl_xor(m, off); m = o > m ? o : m; }
+    if ((threadIdx.x & 63) == 0 && m) atomicMax(peak_bits + b, m);
+}
+
+// one thread per row: bounds + peak -> rows[b] = {left, T_b}, the peak as a double, the frame count and the status word of the
+// row (GVX_WAV_ROW_* of the header).  A row with any of the first three bits has T_b = 0: nothing of it is read again.
+template <typename PCM>
+__global__ void wav_row_plan_kernel(const int32_t* __restrict__ bounds, const unsigned int* __restrict__ peak_bits, long n_max, int n_fft, int hop,
+                                    int T, int B, int32_t* __restrict__ rows, double* __restrict__ peak, int32_t* __restrict__ frame_lengths,
+                                    int32_t* __restrict__ status) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const long left = clamp_len(bounds[2 * b], n_max), right = clamp_len(bounds[2 * b + 1], n_max);
+    double pk;
+    if constexpr (sizeof(PCM) == 2) pk = (double)peak_bits[b]; else pk = (double)__uint_as_float(peak_bits[b]);
+    int32_t st = 0;
+    long Tb = 0;
+    if (left >= right) st = GVX_WAV_ROW_EMPTY;
+    else if (right - left < n_fft) st = GVX_WAV_ROW_SHORT;
+    else if (!(pk > 0.0)) st = GVX_WAV_ROW_SILENT;
+    else {
+        Tb = (right - left - n_fft) / hop + 1;
+        if (Tb > T) { Tb = T; st = GVX_WAV_ROW_CUT; }
+    }
+    rows[2 * b] = (int32_t)left;
+    rows[2 * b + 1] = (int32_t)Tb;
+    peak[b] = Tb > 0 ? pk : 1.0;
+    frame_lengths[b] = (int32_t)Tb;
+    status[b] = st;
 }
 
 bool getenv_flag(const char* name) {
@@ -1091,7 +1263,7 @@ int gvx_stft(gvx_gl_plan* p, const float* signal, const float* window, int B, lo
     rc = check_gl(p, B, T, ws, ws_bytes, w.total);
     if (rc != GVX_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    gl_frame_kernel<<<dim3((unsigned)((long)B * T)), 256, 0, s>>>(signal, window, wsp<float>(ws, w.fr), p->n_fft, p->hop, T, n_samples);
+    gl_frame_kernel<false, float><<<dim3((unsigned)((long)B * T)), 256, 0, s>>>(signal, window, wsp<float>(ws, w.fr), p->n_fft, p->hop, T, n_samples, WavRows{});
     GL_HIP(hipGetLastError());
     rc = run_fft(p, fp->r2c, wsp<float>(ws, w.fr), wsp<float2>(ws, w.reb0), wsp<char>(ws, w.fft_work), fp->work_bytes, s);
     if (rc != GVX_OK) return rc;
@@ -1230,7 +1402,7 @@ int griffin_lim_impl(gvx_gl_plan* p, const float* mag, const float* window, int 
     for (int it = 0; !fused && it < n_iter; ++it) {
         rc = istft_frames(p, fp, ang, window, B, T, ws, w, s, lens);  // inverse = istft(angles)
         if (rc != GVX_OK) return rc;
-        gl_frame_kernel<<<dim3((unsigned)((long)B * T)), 256, 0, s>>>(wsp<float>(ws, w.y), window, wsp<float>(ws, w.fr), p->n_fft, p->hop, T, n);
+        gl_frame_kernel<false, float><<<dim3((unsigned)((long)B * T)), 256, 0, s>>>(wsp<float>(ws, w.y), window, wsp<float>(ws, w.fr), p->n_fft, p->hop, T, n, WavRows{});
         GL_HIP(hipGetLastError());
         float2* cur = reb[it & 1];
         rc = run_fft(p, fp->r2c, wsp<float>(ws, w.fr), cur, wsp<char>(ws, w.fft_work), fp->work_bytes, s);  // rebuilt = stft(inverse)
@@ -1352,11 +1524,11 @@ int gvx_wav_to_mel(gvx_gl_plan* p, const float* signal, const float* window, con
     float* mag_p = wsp<float>(ws, w.ang);
     float* basis_p = wsp<float>(ws, w.reb1);
     if (p->tw && !getenv_flag("GVX_GL_ROCFFT")) {   // n_fft 1024 / hop 256: framing + window + FFT + magnitude in one kernel
-        stft_magnitude_kernel<<<dim3((unsigned)((frames + GLF_FRAMES - 1) / GLF_FRAMES)), GLF_FRAMES * 64, 0, s>>>(
-            signal, n_samples, window, p->tw, mag_p, kp, T, frames);
+        stft_magnitude_kernel<false, float><<<dim3((unsigned)((frames + GLF_FRAMES - 1) / GLF_FRAMES)), GLF_FRAMES * 64, 0, s>>>(
+            signal, n_samples, window, p->tw, mag_p, kp, T, frames, WavRows{});
         GL_HIP(hipGetLastError());
     } else {
-        gl_frame_kernel<<<dim3((unsigned)frames), 256, 0, s>>>(signal, window, wsp<float>(ws, w.fr), p->n_fft, p->hop, T, n_samples);
+        gl_frame_kernel<false, float><<<dim3((unsigned)frames), 256, 0, s>>>(signal, window, wsp<float>(ws, w.fr), p->n_fft, p->hop, T, n_samples, WavRows{});
         GL_HIP(hipGetLastError());
         rc = run_fft(p, fp->r2c, wsp<float>(ws, w.fr), wsp<float2>(ws, w.reb0), wsp<char>(ws, w.fft_work), fp->work_bytes, s);
         if (rc != GVX_OK) return rc;
@@ -1374,10 +1546,156 @@ int gvx_wav_to_mel(gvx_gl_plan* p, const float* signal, const float* window, con
     GL_HIP(gvx::launch_gemm(g, s));
     const float refc = ref > 1e-5f ? ref : 1e-5f;
     const float log_ref = log10_kind ? log10f(refc) : logf(refc);
-    amp_to_db_transpose_kernel<<<dim3((n_mels + 31) / 32, (T + 31) / 32, B), dim3(32, 8), 0, s>>>(wsp<float>(ws, w.amp), mel_db_out, n_mels, T,
-                                                                                                 log10_kind, log_ref);
+    amp_to_db_transpose_kernel<false><<<dim3((n_mels + 31) / 32, (T + 31) / 32, B), dim3(32, 8), 0, s>>>(wsp<float>(ws, w.amp), mel_db_out, n_mels,
+                                                                                                        T, log10_kind, log_ref, nullptr, nullptr);
     GL_HIP(hipGetLastError());
     return GVX_OK;
+}
+
+}  // extern "C"
+
+// ---- ragged wav -> mel: PCM rows of different lengths, trimmed and normalised per row, one launch set per batch ------------------
+namespace {
+
+struct WavWs {   // the uniform layout of T frames per row, then the padded mel basis and the per-row words
+    GlWs g;
+    size_t basis, rows, peak, peak_bits, total;
+};
+
+WavWs wav_plan_ws(const gvx_gl_plan* p, int B, int T, int M, size_t fft_work) {
+    WavWs w{};
+    w.g = gl_plan_ws(p, B, T, M, fft_work);
+    size_t off = w.g.total;
+    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
+    const size_t kp = (size_t)((p->bins + 3) & ~3);
+    w.basis = take((size_t)(M > 0 ? M : 1) * kp * sizeof(float));
+    w.rows = take((size_t)B * 2 * sizeof(int32_t));
+    w.peak = take((size_t)B * sizeof(double));
+    w.peak_bits = take((size_t)B * sizeof(unsigned int));
+    w.total = off;
+    return w;
+}
+
+inline bool wav_fused(const gvx_gl_plan* p) { return p->tw != nullptr && !getenv_flag("GVX_GL_ROCFFT"); }
+
+// the fused n_fft 1024 / hop 256 path needs no rocFFT plan (and so no plan per batch size)
+int wav_fft_plans(gvx_gl_plan* p, int B, int T, FftPair** fp) {
+    *fp = nullptr;
+    return wav_fused(p) ? GVX_OK : get_plans(p, (long)B * T, fp);
+}
+
+template <typename PCM>
+int wav_trim_bounds_impl(const PCM* pcm, int B, long n_max, const int32_t* sample_lengths, int chunk, double thr, int32_t* bounds_out,
+                         hipStream_t s) {
+    wav_trim_bounds_kernel<PCM><<<dim3((unsigned)B), 256, 0, s>>>(pcm, n_max, sample_lengths, chunk, thr, bounds_out);
+    GL_HIP(hipGetLastError());
+    return GVX_OK;
+}
+
+template <typename PCM>
+int wav_to_mel_ragged_impl(gvx_gl_plan* p, FftPair* fp, const PCM* pcm, const float* window, const float* mel_basis, int B, long n_max,
+                           const int32_t* bounds, int normalize, int n_mels, int log10_kind, float ref, int T, float* mel_db_out,
+                           float* gate_out, int32_t* frame_lengths_out, int32_t* row_status_out, void* ws, const WavWs& w, hipStream_t s) {
+    const long frames = (long)B * T;
+    const int kp = (p->bins + 3) & ~3;
+    unsigned int* peak_bits = wsp<unsigned int>(ws, w.peak_bits);
+    int32_t* rows = wsp<int32_t>(ws, w.rows);
+    GL_HIP(hipMemsetAsync(peak_bits, 0, (size_t)B * sizeof(unsigned int), s));
+    wav_peak_bounds_kernel<PCM><<<dim3(64, B), 256, 0, s>>>(pcm, n_max, bounds, peak_bits);
+    GL_HIP(hipGetLastError());
+    wav_row_plan_kernel<PCM><<<(B + 63) / 64, 64, 0, s>>>(bounds, peak_bits, n_max, p->n_fft, p->hop, T, B, rows, wsp<double>(ws, w.peak),
+                                                         frame_lengths_out, row_status_out);
+    GL_HIP(hipGetLastError());
+    const WavRows wr{rows, wsp<double>(ws, w.peak), normalize};
+    // workspace reuse as in gvx_wav_to_mel: fr = framed signal, reb0 = spectrum, ang = padded magnitudes, amp = mel amplitudes
+    float* mag_p = wsp<float>(ws, w.g.ang);
+    float* basis_p = wsp<float>(ws, w.basis);
+    if (wav_fused(p)) {
+        stft_magnitude_kernel<true, PCM><<<dim3((unsigned)((T + GLF_FRAMES - 1) / GLF_FRAMES), B), GLF_FRAMES * 64, 0, s>>>(
+            pcm, n_max, window, p->tw, mag_p, kp, T, frames, wr);
+        GL_HIP(hipGetLastError());
+    } else {
+        gl_frame_kernel<true, PCM><<<dim3((unsigned)T, B), 256, 0, s>>>(pcm, window, wsp<float>(ws, w.g.fr), p->n_fft, p->hop, T, n_max, wr);
+        GL_HIP(hipGetLastError());
+        const int rc = run_fft(p, fp->r2c, wsp<float>(ws, w.g.fr), wsp<float2>(ws, w.g.reb0), wsp<char>(ws, w.g.fft_work), fp->work_bytes, s);
+        if (rc != GVX_OK) return rc;
+        magnitude_kernel<<<blocks_for(frames * kp), 256, 0, s>>>(wsp<float2>(ws, w.g.reb0), mag_p, p->bins, kp, frames);
+        GL_HIP(hipGetLastError());
+    }
+    pad_rows_kernel<<<blocks_for((long)n_mels * kp), 256, 0, s>>>(mel_basis, basis_p, n_mels, p->bins, kp);
+    GL_HIP(hipGetLastError());
+    gvx::GemmParams g{};   // fft2mel over every padded frame: the rows of frames that do not exist are zeros
+    g.A = mag_p; g.amap = gvx::RowMap{(int)frames, 0, (long)kp};
+    g.W = basis_p; g.ldw = kp;
+    g.C = wsp<float>(ws, w.g.amp); g.cmap = gvx::RowMap{(int)frames, 0, (long)n_mels};
+    g.M = (int)frames; g.N = n_mels; g.K = kp; g.act = gvx::ACT_NONE;
+    GL_HIP(gvx::launch_gemm(g, s));
+    const float refc = ref > 1e-5f ? ref : 1e-5f;
+    const float log_ref = log10_kind ? log10f(refc) : logf(refc);
+    amp_to_db_transpose_kernel<true><<<dim3((n_mels + 31) / 32, (T + 31) / 32, B), dim3(32, 8), 0, s>>>(wsp<float>(ws, w.g.amp), mel_db_out, n_mels,
+                                                                                                       T, log10_kind, log_ref, rows, gate_out);
+    GL_HIP(hipGetLastError());
+    return GVX_OK;
+}
+
+int check_pcm(const void* pcm, int pcm_kind, int B, long n_max) {
+    if (!pcm) return gl_fail(GVX_ERR_INVALID_ARG, "null argument");
+    if (pcm_kind != GVX_PCM_INT16 && pcm_kind != GVX_PCM_FLOAT32) return gl_fail(GVX_ERR_INVALID_ARG, "pcm_kind %d is neither int16 (0) nor float32 (1)", pcm_kind);
+    if (B < 1 || n_max < 1 || n_max > 0x7fffffffL) return gl_fail(GVX_ERR_INVALID_ARG, "B and n_max must be >= 1 (n_max below 2^31)");
+    if (reinterpret_cast<uintptr_t>(pcm) & (pcm_kind == GVX_PCM_INT16 ? 1 : 3)) return gl_fail(GVX_ERR_INVALID_ARG, "pcm is not aligned to its sample type");
+    return GVX_OK;
+}
+
+inline int wav_frames_of(const gvx_gl_plan* p, long n) { return n >= p->n_fft ? (int)((n - p->n_fft) / p->hop + 1) : 1; }
+
+}  // namespace
+
+extern "C" {
+
+size_t gvx_wav_to_mel_ragged_workspace_bytes(gvx_gl_plan* p, int B, long n_max, int n_mels) {
+    if (!p || B < 1 || n_max < 1 || n_mels < 1) return 0;
+    const int T = wav_frames_of(p, n_max);
+    FftPair* fp = nullptr;
+    if (wav_fft_plans(p, B, T, &fp) != GVX_OK) return 0;
+    return wav_plan_ws(p, B, T, n_mels, fp ? fp->work_bytes : 0).total;
+}
+
+int gvx_wav_trim_bounds(const void* pcm, int pcm_kind, int B, long n_max, const int32_t* sample_lengths, int fs, float trim_dbfs,
+                        int32_t* bounds_out, void* stream) {
+    int rc = check_pcm(pcm, pcm_kind, B, n_max);
+    if (rc != GVX_OK) return rc;
+    if (!sample_lengths || !bounds_out) return gl_fail(GVX_ERR_INVALID_ARG, "null argument");
+    const int chunk = (int)(20 * 0.001 * fs);   // the reference's expression (utils/__init__.py:60-61)
+    if (fs < 1 || chunk < 1) return gl_fail(GVX_ERR_INVALID_ARG, "fs = %d gives no 20 ms chunk", fs);
+    if (trim_dbfs > 0.f) return gl_fail(GVX_ERR_INVALID_ARG, "trim_dbfs = %g is above full scale", (double)trim_dbfs);
+    hipStream_t s = (hipStream_t)stream;
+    // NaN stays NaN: no trimming.  Full scale is the reference's np.iinfo(int16).max, 1.0 for float32 samples.
+    const double rel = std::pow(10.0, (double)trim_dbfs / 10.0);
+    if (pcm_kind == GVX_PCM_INT16)
+        return wav_trim_bounds_impl(static_cast<const int16_t*>(pcm), B, n_max, sample_lengths, chunk, 32767.0 * 32767.0 * rel, bounds_out, s);
+    return wav_trim_bounds_impl(static_cast<const float*>(pcm), B, n_max, sample_lengths, chunk, rel, bounds_out, s);
+}
+
+int gvx_wav_to_mel_ragged(gvx_gl_plan* p, const void* pcm, int pcm_kind, const float* window, const float* mel_basis, int B, long n_max,
+                          const int32_t* bounds, int normalize, int n_mels, int log10_kind, float ref, int T_out, float* mel_db_out,
+                          float* gate_out, int32_t* frame_lengths_out, int32_t* row_status_out, void* ws, size_t ws_bytes, void* stream) {
+    if (!p || !window || !mel_basis || !bounds || !mel_db_out || !frame_lengths_out || !row_status_out) return gl_fail(GVX_ERR_INVALID_ARG, "null argument");
+    int rc = check_pcm(pcm, pcm_kind, B, n_max);
+    if (rc != GVX_OK) return rc;
+    if (n_mels < 1 || T_out < 1) return gl_fail(GVX_ERR_INVALID_ARG, "n_mels and T_out must be >= 1");
+    if ((long)B * T_out > 0x7fffffffL / ((p->bins + 3) & ~3)) return gl_fail(GVX_ERR_UNSUPPORTED, "%d x %d frames are too many for one call", B, T_out);
+    FftPair* fp = nullptr;
+    rc = wav_fft_plans(p, B, T_out, &fp);
+    if (rc != GVX_OK) return rc;
+    const WavWs w = wav_plan_ws(p, B, T_out, n_mels, fp ? fp->work_bytes : 0);
+    rc = check_gl(p, B, T_out, ws, ws_bytes, w.total);
+    if (rc != GVX_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (pcm_kind == GVX_PCM_INT16)
+        return wav_to_mel_ragged_impl(p, fp, static_cast<const int16_t*>(pcm), window, mel_basis, B, n_max, bounds, normalize, n_mels, log10_kind, ref,
+                                      T_out, mel_db_out, gate_out, frame_lengths_out, row_status_out, ws, w, s);
+    return wav_to_mel_ragged_impl(p, fp, static_cast<const float*>(pcm), window, mel_basis, B, n_max, bounds, normalize, n_mels, log10_kind, ref,
+                                  T_out, mel_db_out, gate_out, frame_lengths_out, row_status_out, ws, w, s);
 }
 
 }  // extern "C"

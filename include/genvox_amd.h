@@ -448,6 +448,41 @@ int gvx_griffin_lim_ragged(gvx_gl_plan* plan, const float* mag, const float* win
 int gvx_wav_finalize_ragged(const float* wav, int B, long n_samples, const int32_t* frame_lengths, int n_fft, int hop, int trim,
                             const double* b_coef, const double* a_coef, int order, double* out, unsigned int* scratch_B, void* stream);
 
+/* ---- Ragged wav -> mel: recordings of different lengths to the mel side of a training batch in one call (the many-files form of
+ * AudioProcessor.convert_wav2mel, core/processors.py:70-79, behind the reference's silence trimming, core/processors.py:136-164).
+ * pcm is a padded batch of PCM rows [B][n_max], int16 (GVX_PCM_INT16, full scale 32767: what scipy.io.wavfile.read gives) or
+ * float32 (GVX_PCM_FLOAT32, full scale 1.0); row b is valid in [0, sample_lengths[b]) and what lies behind is never read as
+ * signal.  Lengths and bounds are DEVICE int32 and are clamped to [0, n_max] on the device, so the calls stay asynchronous.
+ *
+ * gvx_wav_trim_bounds: get_non_silent_boundary (utils/__init__.py:56-76) per row.  Chunks of int(20 * 0.001 * fs) samples are
+ * walked from the row's start and, aligned to its last sample, from its end (the last chunk of a walk may be short);
+ * bounds_out[b] = {start of the first chunk from the left whose dBFS is >= trim_dbfs, n_b - start of the first such chunk from the
+ * right}.  When no chunk passes, a walk ends on its last chunk start as the reference's loop does, so left >= right marks the row
+ * as empty.  The decision is sum x^2 >= count * full_scale^2 * 10^(trim_dbfs / 10): for int16 an exact integer sum compared once
+ * in double (the reference's float64 decision except on an exact tie).  trim_dbfs NaN: no trimming, bounds_out[b] = {0, n_b}.
+ *
+ * gvx_wav_to_mel_ragged: row b is the signal pcm[b][left_b, right_b) of bounds [B][2]; with `normalize` every sample is
+ * float32(double(y) / double(peak_b)), peak_b = max |y| over the bounds (normalize_signal, utils/audio/base.py:20-22; |-32768| is
+ * 32768 here, where the reference's int16 abs wraps).  T_b = (right_b - left_b - n_fft) / hop + 1 frames; the outputs keep the
+ * stride T_out: mel_db_out [B][n_mels][T_out] with exact zeros in frames t >= T_b, gate_out [B][T_out] (may be NULL) 1 from
+ * frame T_b - 1 on and 0 before, frame_lengths_out [B] = T_b.  row_status_out [B] is 0 or one GVX_WAV_ROW_* word; a row that is
+ * EMPTY, SHORT or SILENT has T_b = 0 and zero output (no division by a zero peak, no NaN), a row with more frames than T_out is
+ * CUT to T_out.  Row b's mel equals, to the bit, gvx_wav_to_mel on that row's trimmed and normalised signal alone (per frame the
+ * same operations in the same order; the mel GEMM runs over all B * T_out padded frames, whose missing rows are zeros).
+ * Workspace: gvx_wav_to_mel_ragged_workspace_bytes for T_out <= the frames of n_max samples (a smaller one is GVX_ERR_WORKSPACE). */
+enum { GVX_PCM_INT16 = 0, GVX_PCM_FLOAT32 = 1 };
+enum { GVX_WAV_ROW_EMPTY = 1,    /* left >= right: nothing left after trimming              */
+       GVX_WAV_ROW_SHORT = 2,    /* fewer than n_fft samples: not one frame                 */
+       GVX_WAV_ROW_SILENT = 4,   /* every sample is zero: no peak to normalise by           */
+       GVX_WAV_ROW_CUT = 8 };    /* more frames than T_out: the first T_out were computed   */
+size_t gvx_wav_to_mel_ragged_workspace_bytes(gvx_gl_plan* plan, int B, long n_max, int n_mels);
+int gvx_wav_trim_bounds(const void* pcm, int pcm_kind, int B, long n_max, const int32_t* sample_lengths, int fs, float trim_dbfs,
+                        int32_t* bounds_out, void* stream);
+int gvx_wav_to_mel_ragged(gvx_gl_plan* plan, const void* pcm, int pcm_kind, const float* window, const float* mel_basis, int B,
+                          long n_max, const int32_t* bounds, int normalize, int n_mels, int log10_kind, float ref, int T_out,
+                          float* mel_db_out, float* gate_out, int32_t* frame_lengths_out, int32_t* row_status_out, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
 /* ---- Per-kernel timing of the decoder step (measurement only): when enabled, a teacher-forced call replays the
  * mid-sequence LSTM-step launch and the attention launches 64 times each, back to back, between HIP events on
  * `stream` (after its loop; the call's outputs are not valid afterwards); gvx_kernel_times_ms synchronises and

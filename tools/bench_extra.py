@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Secondary measurements for DESIGN.md (BASELINE.json configs 2-4 beyond the headline line of bench.py):
 teacher-forced at B=64, autoregressive RTF (B=64, 1000 steps), Postnet-only MFMA rate, Griffin-Lim throughput;
-`glr` (on request): the ragged Griffin-Lim call against the same rows padded through the uniform call."""
+`glr` (on request): the ragged Griffin-Lim call against the same rows padded through the uniform call;
+`w2mr` (on request): 64 recordings of 2-10 s through one ragged wav -> mel call against 64 single-row `wav_to_mel` calls."""
 import json
 import os
 import sys
@@ -110,6 +111,52 @@ def main():
         res["griffin_lim_ragged_b64_200to800_60it"] = {
             "padded_uniform": padded, "ragged": ragged, "ragged_all_rows_full_length": full,
             "frames_share": round(sum(lens) / (B * T), 3), "time_share": round(ragged["mean_ms"] / padded["mean_ms"], 3)}
+    if "w2mr" in which:
+        # ragged wav -> mel: 64 int16 recordings with lengths spread evenly over 2-10 s at 22 050 Hz, (a) through one
+        # wav_to_mel_ragged call (trimming and normalisation on the device, one synchronisation), (b) the per-file route: peak
+        # normalisation in NumPy on the host, one wav_to_mel call per recording, each result copied back like convert_wav2mel does.
+        # Both sides produce every mel on the host-visible side of one synchronisation per batch / per file; 7 runs each.
+        import statistics
+
+        import numpy as np
+
+        ap = AudioProcessor(AudioConfig(sampling_rate=22050, filter_length=1024, hop_length=256, log_func="np.log"))
+        B, fs = 64, 22050
+        rng = np.random.default_rng(0)
+        secs = [2.0 + 8.0 * i / (B - 1) for i in range(B)]
+        secs = [secs[(i * 29) % B] for i in range(B)]            # not sorted
+        rows = [rng.integers(-12000, 12001, size=int(s * fs)).astype(np.int16) for s in secs]
+        n_max = max(r.shape[0] for r in rows)
+        pcm = np.zeros((B, n_max), np.int16)
+        for b, r in enumerate(rows):
+            pcm[b, : r.shape[0]] = r
+        lengths = [r.shape[0] for r in rows]
+        pcm_dev = torch.from_numpy(pcm).cuda()
+
+        def runs(fn, warm=2, reps=7):
+            for _ in range(warm):
+                fn()
+            out = []
+            for _ in range(reps):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                out.append((time.perf_counter() - t0) * 1e3)
+            return {"median_ms": round(statistics.median(out), 2), "min_ms": round(min(out), 2), "max_ms": round(max(out), 2), "runs": reps}
+
+        def per_file():
+            for r in rows:
+                sig = (r / max(np.abs(np.min(r)), np.abs(np.max(r)))).astype(np.float32)
+                ap.wav_to_mel(torch.from_numpy(sig)[None])[0].cpu()
+
+        ragged_host = runs(lambda: ap.wav_to_mel_ragged(pcm, lengths))          # padded batch starts on the host (upload included)
+        ragged_dev = runs(lambda: ap.wav_to_mel_ragged(pcm_dev, lengths))       # padded batch already on the device
+        single = runs(per_file)
+        frames = sum((n - 1024) // 256 + 1 for n in lengths)
+        res["wav_to_mel_ragged_b64_2to10s"] = {
+            "ragged_from_host_int16": ragged_host, "ragged_from_device_int16": ragged_dev, "single_row_calls_x64": single,
+            "frames": frames, "padded_frames": B * ((n_max - 1024) // 256 + 1), "seconds_of_audio": round(sum(lengths) / fs, 1)}
     if "cpu" in which:
         # CPU baselines for configs 3 and 4 (the oracle = CPU restatement of the reference, on this box's host cores):
         # bounded samples, reported beside the GPU figures above; bench.py carries the one for config 2.
