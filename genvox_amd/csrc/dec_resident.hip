@@ -94,6 +94,7 @@ struct RsArgs {
     int B, T;
     unsigned spin_limit;
     int debug, layout;
+    int kg_pre;   // teacher-forced loop: k-groups of the Prenet columns in the packed attention-LSTM matrix (prenet_dim / 8)
 };
 
 #ifdef GVX_STAMPS
@@ -272,7 +273,7 @@ __device__ __forceinline__ void rs_body(const RsArgs& p, char* smem, const int b
     using Cfg = RsCfg<KIND>;
     constexpr bool XH = Cfg::XH, ATT = Cfg::ATT;
     constexpr int NN = Cfg::NN, NC = Cfg::NC, NRN = Cfg::NRN, NLN = Cfg::NLN;
-    constexpr int NKGW = ATT ? RS_NKGW_ATT : RS_NKGW_DEC;
+    constexpr int NKGW = ATT ? RS_NKGW_ATT : RS_NKGW_DEC;   // (the autoregressive loop, which runs at the default Prenet width only)
     constexpr int H = ATT ? RS_A : RS_D;
     constexpr int NRH = XH ? NRN : 1, NCH = XH ? NC : 1;   // half-tile fragments in registers
     constexpr int RT = Cfg::RT;
@@ -319,14 +320,19 @@ __device__ __forceinline__ void rs_body(const RsArgs& p, char* smem, const int b
     // per step wherever the part was placed, more than the 0.8 ms GEMM (which overlaps the encoder) costs (round 4, EXPERIMENTS.md)
     constexpr bool PP = AR && ATT;
     constexpr int NSUB = ARD ? 2 : 1;
-    const int kn0 = ATT ? RS_KG0_ATT + 64 + 16 * wave : (wave < 4 ? 32 * wave : 32 * wave + 64);
+    // The teacher-forced loop serves any Prenet width: the width moves the first k-group of the tile's other columns and the
+    // k-groups per tile of the packed matrix, which only this prologue looks at (with the constants of prenet_dim 256 a handle
+    // of prenet_dim 128 loaded the fragments of other columns and tiles: mel off by 2e-2 from step 1 on)
+    const int kg_pre = AR ? RS_KG0_ATT : __builtin_amdgcn_readfirstlane(p.kg_pre);
+    const int nkgw = ATT ? kg_pre + (RS_E + RS_A) / 8 : RS_NKGW_DEC;
+    const int kn0 = ATT ? kg_pre + 64 + 16 * wave : (wave < 4 ? 32 * wave : 32 * wave + 64);
     // k-group of the wave's i-th "early" fragment inside the packed matrix (ARD: 16 h_d k-groups 192 + 16 w + i, then 16 h_a k-groups 16 w + i)
     auto kni = [&](int i) -> int { return ARD ? (i < 16 ? 192 + 16 * wave + i : 16 * wave + (i - 16)) : kn0 + i; };
-    const int kc0 = ATT ? RS_KG0_ATT + 8 * wave : 128 + 8 * wave;
-    const float4* wt = wsrc + (long)tile * NKGW * 64 + lane;
-    const float4* wx = wsrc + (long)xt * NKGW * 64 + mlane;
+    const int kc0 = ATT ? kg_pre + 8 * wave : 128 + 8 * wave;
+    const float4* wt = wsrc + (long)tile * nkgw * 64 + lane;
+    const float4* wx = wsrc + (long)xt * nkgw * 64 + mlane;
     float4 wn[NRN], wc[NC], hn[NRH], hc[NCH], wn2[NR2], wc2[NC2];
-    const float4* wt2 = wt + (long)NKGW * 64;   // the pair's second tile
+    const float4* wt2 = wt + (long)nkgw * 64;   // the pair's second tile
 #pragma unroll
     for (int i = 0; i < NRN; ++i) wn[i] = wt[(long)kni(i) * 64];
 #pragma unroll
@@ -935,10 +941,13 @@ hipError_t launch_decoder_resident(const DecResidentParams& p, hipStream_t s) {
         !p.hc || !p.q_slab || !p.c_a || !p.c_d || !p.sync)
         return hipErrorInvalidValue;
     if (p.layout != 1 && p.layout != 2) return hipErrorInvalidValue;
+    // the prologue reads k-groups [kg_pre, kg_pre + 192) of 128 tiles of 1 KiB fragments: exactly the packed matrix
+    if (p.kg_pre < 1 || (size_t)p.att_frag_bytes != (size_t)128 * (size_t)(p.kg_pre + (RS_E + RS_A) / 8) * 1024) return hipErrorInvalidValue;
     RsArgs a{};
     a.att_frag = p.att_frag; a.att_bias = p.att_bias; a.wq_t = p.wq_t; a.dec_frag = p.dec_frag; a.dec_bias = p.dec_bias;
     a.pre_gate = p.pre_gate; a.h_a = p.h_a; a.hc = p.hc; a.q_slab = p.q_slab; a.c_a = p.c_a; a.c_d = p.c_d; a.sync = p.sync;
     a.att_frag_bytes = p.att_frag_bytes; a.B = p.B; a.T = p.T; a.spin_limit = p.spin_limit; a.debug = p.debug; a.layout = p.layout;
+    a.kg_pre = p.kg_pre;
     const dim3 grid(p.layout == 2 ? 192 : 224);
     if (p.tr_keep_a) {   // training mode: every tape pointer, or none
         if (!p.tr_keep_d || !p.tr_c_a || !p.tr_c_d || !p.tr_pre_a || !p.tr_pre_d) return hipErrorInvalidValue;
@@ -965,6 +974,7 @@ hipError_t launch_decoder_ar_resident(const ArResidentParams& p, hipStream_t s) 
     a.p_slab = p.p_slab; a.n_done = p.n_done; a.PSB = p.PSB;
     a.h_a = p.h_a; a.hc = p.hc; a.q_slab = p.q_slab; a.c_a = p.c_a; a.c_d = p.c_d; a.sync = p.sync;
     a.att_frag_bytes = p.att_frag_bytes; a.B = p.B; a.T = p.T; a.spin_limit = p.spin_limit; a.debug = p.debug; a.layout = 1;
+    a.kg_pre = RS_KG0_ATT;
     decoder_ar_resident_kernel<<<dim3(224), dim3(RS_THREADS), RS_LDS_BYTES, s>>>(a);
     return hipGetLastError();
 }

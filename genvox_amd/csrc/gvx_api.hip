@@ -458,6 +458,32 @@ int gvx_autoregressive_loop_kind(const gvx_model* m, int B, int L) {
     return plan_autoregressive(m, B, L).kind;
 }
 
+// Host-only queries for the tests, like gvx_debug_gemm_plan / gvx_debug_bptt_plan (not in the public header).  Every field of the
+// two loop plans for (B, L) on this handle - the same two functions the loops call, no device touched.  mode: 0 inference, 1 training
+// call with the whole tape, 2 training call with a partial tape.  out[0..7] = TfLoopPlan {kind, pa_layout, tile_layout, rows64,
+// pre_gate, timeout_check, side_stream, graph}; out[8..11] = ArLoopPlan {kind, split_h, fold, graph}.
+int gvx_debug_decoder_plan(const gvx_model* m, int mode, int B, int L, int* out) {
+    if (!m || !out) return fail(GVX_ERR_INVALID_ARG, "null argument");
+    if (mode < 0 || mode > 2 || B < 1 || L < 1) return fail(GVX_ERR_INVALID_ARG, "mode must be 0, 1 or 2 and B, L >= 1 (got %d, %d, %d)", mode, B, L);
+    const TfLoopPlan t = plan_teacher_forced(m, B, L, (TfMode)mode);
+    const ArLoopPlan a = plan_autoregressive(m, B, L);
+    const int v[12] = {t.kind, t.pa_layout, t.tile_layout, t.rows64, t.pre_gate, t.timeout_check, t.side_stream, t.graph,
+                       a.kind, a.split_h, a.fold, a.graph};
+    for (int i = 0; i < 12; ++i) out[i] = v[i];
+    return GVX_OK;
+}
+
+// hipGraph launches this handle has made since it was created (run_chunk: the encoder's launch-per-position loop, the
+// teacher-forced step loops, the 16-step chunks of the autoregressive loop).  An eager first sighting and a capture do not count.
+long long gvx_debug_graph_replays(const gvx_model* m) { return m ? (long long)m->graph_replays : -1; }
+
+// 1 if gvx_encoder_forward / gvx_encoder_lstm_forward run the recurrence of B rows as the one resident launch on this handle
+// (GVX_ENC_PERSISTENT and encoder_persistent_supported: B <= 32, H = 256), 0 for the launch per position.
+int gvx_debug_encoder_resident(const gvx_model* m, int B) {
+    if (!m || B < 1) return 0;
+    return m->enc_persistent && encoder_persistent_supported(B, m->H()) ? 1 : 0;
+}
+
 int gvx_model_set_persistent_attention(gvx_model* m, int enable) {
     if (!m) return fail(GVX_ERR_INVALID_ARG, "null argument");
     m->attn_persistent = enable != 0;

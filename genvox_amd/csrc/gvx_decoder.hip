@@ -452,6 +452,7 @@ int tf_loop_resident(const TfLoop& c, hipStream_t s, int* launches) {
     DecResidentParams rp{};
     fill_resident_common(m, c.db, c.sync, c.B, c.T, rp);
     rp.pre_gate = c.db.pre_gate;
+    rp.kg_pre = d.prenet_dim / 8;
     if (const LstmDropout* train = c.train) {
         rp.h_a = train->h_a_all;
         rp.tr_keep_a = train->att_keep; rp.tr_keep_d = train->dec_keep; rp.tr_scale_a = train->att_scale; rp.tr_scale_d = train->dec_scale;

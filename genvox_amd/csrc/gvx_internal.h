@@ -129,6 +129,7 @@ struct gvx_model {
     static constexpr size_t GRAPH_SETS = 4;
     std::vector<GraphSet> ar_graphs, loop_graphs, enc_graphs;
     uint64_t use_clock = 0;
+    uint64_t graph_replays = 0;   // hipGraphLaunch calls of run_chunk on this handle (gvx_debug_graph_replays: the tests of the replay path)
     hipStream_t pa_stream = nullptr;
     hipEvent_t pa_fork = nullptr, pa_join = nullptr, enc_mid = nullptr;
     // autoregressive loop: the all-rows-finished counter of chunk k is read (pinned slot k & 1, event k & 1) while chunk k + 1 runs
@@ -239,6 +240,7 @@ int run_chunk(gvx_model* m, gvx_model::GraphSet* gs, size_t chunk, hipStream_t s
         gs->execs[chunk] = exec;
     }
     HIP_TRY(hipGraphLaunch(exec, s));
+    ++m->graph_replays;
     return GVX_OK;
 }
 

@@ -287,6 +287,7 @@ struct DecResidentParams {
     int B, T;
     unsigned spin_limit;            // polls without progress before the poller gives up (0 = HANDOFF_SPIN_LIMIT)
     int debug;                      // timing experiments only (GVX_RS_DEBUG: sleeps between polls)
+    int kg_pre;                     // prenet_dim / 8: k-groups of the Prenet columns at the front of every tile of att_frag
     int layout;                     // 1: 224 workgroups beside one attention workgroup per row (L <= 128); 2: 192 workgroups - 64 pairs of
                                     // attention-LSTM tiles + 128 decoder-LSTM tiles - beside two per row (128 < L <= 256)
     // training mode (all or none): keep masks of the dropout on both cells' outputs [T][B][H] and their scales 1 / (1 - p), the

@@ -267,3 +267,210 @@ def enc_bptt_plan(lib, B, H, resident):
     out = (C.c_int * 4)()
     rc = fn(B, H, 1 if resident else 0, out)
     return rc, list(out)
+
+
+# ---- the forward recurrences (gvx_decoder_teacher_forced(_train), gvx_decoder_autoregressive, gvx_encoder_lstm_forward,
+# gvx_encoder_forward): the cases tests/test_forward_loops_gpu.py runs, each with the plan it is there for.
+# tests/test_host_cpu.py pins every line against gvx_debug_decoder_plan / gvx_debug_encoder_resident on the CPU, and both sides of
+# every threshold of plan_teacher_forced / plan_autoregressive, so a retuned plan fails there and the cases get re-aimed. -----------
+# dims: a key of FWD_DIMS.  env: GVX_* variables set while the handle is created (read_knobs reads them once).  setter: an export
+# called as setter(handle, 0) afterwards.  lengths: as bptt_lengths.  mode (teacher-forced): 0 inference, 1 training call with the
+# whole tape, 2 training call with a partial tape; drop: hidden-state dropout on (p_att 0.2, p_dec 0.5) in a training call.
+# plan: teacher-forced (kind, pa_layout, tile_layout, rows64, pre_gate, timeout_check, side_stream, graph);
+#       autoregressive (kind, split_h, fold, graph);  encoder: (resident,).
+# What the argument checks refuse of the shapes one would list (pinned in tests/test_host_cpu.py, FWD_REFUSED_DIMS): channel sizes
+# that are no multiple of 8 - n_mels 79 and 83, att_dim 1, prenet_dim 20 - are GVX_ERR_UNSUPPORTED at gvx_model_create, so the
+# padded projection stride is run at n_mels 72 / 88 and the odd layer sizes with P = 24, a = 8.
+FwdCase = collections.namedtuple("FwdCase", "name dims env setter B L T lengths mode drop plan")
+FWD_DIMS = {
+    "def": dict(model={}, n_mels=80),
+    "small": dict(model=dict(symbols_embedding_dim=32, encoder_embedding_dim=32, encoder_kernel_size=3, encoder_n_convolutions=2,
+                             decoder_rnn_dim=64, attention_rnn_dim=48, prenet_dim=24, attention_dim=16, attention_location_n_filters=8,
+                             attention_location_kernel_size=7, postnet_embedding_dim=40, postnet_kernel_size=5, postnet_n_convolutions=3),
+                  n_mels=24),   # SMALL of tests/golden/cases.py (kl = 7)
+    # the odd set of the BPTT table on multiples of 8: E + A = 88, A + E + D = 144 (padded product columns), kl = 5
+    "odd": dict(model=dict(symbols_embedding_dim=48, encoder_embedding_dim=48, encoder_kernel_size=3, encoder_n_convolutions=1,
+                           decoder_rnn_dim=56, attention_rnn_dim=40, prenet_dim=24, attention_dim=24, attention_location_n_filters=12,
+                           attention_location_kernel_size=5, postnet_embedding_dim=16, postnet_kernel_size=3, postnet_n_convolutions=1),
+                n_mels=16),
+    "a8_F1_kl1": dict(model=dict(symbols_embedding_dim=32, encoder_embedding_dim=32, encoder_kernel_size=3, encoder_n_convolutions=1,
+                                 decoder_rnn_dim=32, attention_rnn_dim=32, prenet_dim=16, attention_dim=8, attention_location_n_filters=1,
+                                 attention_location_kernel_size=1, postnet_embedding_dim=16, postnet_kernel_size=3, postnet_n_convolutions=1),
+                      n_mels=16),
+    "p128": dict(model=dict(prenet_dim=128), n_mels=80),
+    "mels72": dict(model={}, n_mels=72),    # PS() 76, PSB() 80
+    "mels88": dict(model={}, n_mels=88),    # PS() 92, PSB() 96: the resident autoregressive pair stops at n_mels 80
+    "att16": dict(model=dict(attention_dim=16), n_mels=80),
+    "att256": dict(model=dict(attention_dim=256), n_mels=80),
+    "dec512": dict(model=dict(decoder_rnn_dim=512), n_mels=80),   # E / 4 != D / 8: no fold
+}
+FWD_REFUSED_DIMS = [dict(n_mels=79), dict(n_mels=83), dict(attention_dim=1), dict(prenet_dim=20)]
+_PA0 = "gvx_model_set_persistent_attention"
+
+
+def _tf(name, B, L, T, plan, dims="def", env=None, setter=None, lengths="ragged", mode=0, drop=False):
+    return FwdCase(name, dims, env or {}, setter, B, L, T, lengths, mode, drop, plan)
+
+
+_K2L1 = (2, 1, 1, 0, 1, 1, 1, 0)
+_K2L2 = (2, 2, 2, 0, 1, 1, 1, 0)
+_K2L2_224 = (2, 2, 1, 0, 1, 1, 1, 0)
+_K1L1, _K1L2, _K1R64 = (1, 1, 1, 0, 1, 1, 1, 1), (1, 2, 2, 0, 1, 1, 1, 1), (1, 3, 3, 1, 1, 1, 1, 1)
+_K0 = lambda lay, pre=0: (0, lay, lay, 0, pre, pre, 0, 1)
+_R64 = {"GVX_TF_ROWS64": "1"}
+TF_CASES_FWD = (
+    # kind 2, layout 1 (224 workgroups beside <= 32 attention workgroups); L = 2, 15, 16: the halo of kl = 31 wider than the row
+    [_tf("k2_%dx%dx%d" % s, *s, _K2L1, lengths=ln) for s, ln in (((1, 1, 1), "full"), ((1, 128, 3), "full"), ((2, 5, 4), "ragged"), ((3, 33, 6), "ragged"),
+                                                                  ((17, 127, 5), "ragged"), ((31, 128, 3), "short"), ((32, 128, 12), "ragged"),
+                                                                  ((32, 1, 2), "full"), ((3, 2, 3), "ragged"), ((3, 15, 3), "ragged"), ((3, 16, 3), "full"))]
+    # kind 2, layout 2 on the 192-workgroup deal (B <= 2 or B > 16)
+    + [_tf("k2_%dx%dx%d" % s, *s, _K2L2) for s in ((1, 129, 3), (2, 256, 3), (17, 129, 3), (32, 190, 4), (32, 256, 3))]
+    # ... on the 224-workgroup deal (3 .. 16 rows), and the same shapes sent back to 192 workgroups
+    + [_tf("k2_%dx%dx%d" % s, *s, _K2L2_224) for s in ((3, 129, 3), (16, 190, 5), (16, 256, 3))]
+    + [_tf("k2_long192_%dx%dx%d" % s, *s, _K2L2, env={"GVX_TF_LONG_224": "0"}) for s in ((3, 129, 3), (16, 190, 5), (16, 256, 3))]
+    # kind 1: the weight-streaming launch per step beside the resident attention kernel
+    + [_tf("k1_5x77x4", 5, 77, 4, _K1L1, env={"GVX_TF_RESIDENT": "0"}), _tf("k1_32x128x3", 32, 128, 3, _K1L1, env={"GVX_TF_RESIDENT": "0"}),
+       _tf("k1_4x200x3", 4, 200, 3, _K1L2, env={"GVX_TF_RESIDENT": "0"}), _tf("k1_32x256x3", 32, 256, 3, _K1L2, env={"GVX_TF_RESIDENT": "0"})]
+    # ... on layout 3: 33 .. 64 rows in one call, two batch tiles per workgroup
+    + [_tf("rows64_%dx%dx%d" % s, *s, _K1R64, env=_R64) for s in ((33, 21, 3), (40, 50, 4), (64, 1, 2), (64, 128, 3))]
+    # kind 0 at the default sizes: L past 256, the handle that shares the chip, the two-launch attention, 33 .. 64 rows direct
+    + [_tf("k0_2x257x3", 2, 257, 3, _K0(0)), _tf("k0_3x300x3", 3, 300, 3, _K0(0)),
+       _tf("k0_pa0_5x40x4", 5, 40, 4, _K0(1), setter=_PA0), _tf("k0_pa0_32x128x3", 32, 128, 3, _K0(1), setter=_PA0),
+       _tf("k0_split_4x60x3", 4, 60, 3, _K0(1), env={"GVX_ATTN_SPLIT": "1"}), _tf("k0_split_3x200x3", 3, 200, 3, _K0(2), env={"GVX_ATTN_SPLIT": "1"}),
+       _tf("k0_40x30x3", 40, 30, 3, _K0(3)), _tf("k0_64x128x2", 64, 128, 2, _K0(3))]
+    # one case per layout under each of the remaining knobs
+    + [_tf("depth6_k1_6x90x3", 6, 90, 3, _K1L1, env={"GVX_PA_DEPTH": "6", "GVX_TF_RESIDENT": "0"}),
+       _tf("depth6_k1_6x140x3", 6, 140, 3, _K1L2, env={"GVX_PA_DEPTH": "6", "GVX_TF_RESIDENT": "0"}),
+       _tf("noprefetch_6x90x3", 6, 90, 3, _K0(1), env={"GVX_ATTN_PREFETCH": "0"}, setter=_PA0),
+       _tf("noprefetch_6x140x3", 6, 140, 3, _K0(2), env={"GVX_ATTN_PREFETCH": "0"}, setter=_PA0),
+       _tf("pool2_6x90x3", 6, 90, 3, _K2L1, env={"GVX_SIDE_POOL": "2"}), _tf("pool2_6x140x3", 6, 140, 3, _K2L2_224, env={"GVX_SIDE_POOL": "2"})]
+    # other layer sizes: launches per step
+    + [_tf("small_5x13x6", 5, 13, 6, _K0(1), dims="small"), _tf("small_33x9x2", 33, 9, 2, _K0(3), dims="small"),
+       _tf("odd_3x33x4", 3, 33, 4, _K0(1), dims="odd"), _tf("odd_32x9x3", 32, 9, 3, _K0(1), dims="odd"),
+       _tf("a8_F1_kl1_3x9x3", 3, 9, 3, _K0(1), dims="a8_F1_kl1")]
+    + [_tf("small_kl7_L%d" % L, 3, L, 3, _K0(1), dims="small") for L in (1, 2, 3, 4)]
+    + [_tf("mels72_4x20x3", 4, 20, 3, _K2L1, dims="mels72"), _tf("mels88_4x20x3", 4, 20, 3, _K2L1, dims="mels88"),
+       # prenet_dim 128: the resident tile kernel at another Prenet width (k-group offsets of its weight fragments; these two cases
+       # found it reading the fragments of prenet_dim 256 there), inference and training deals
+       _tf("p128_4x20x3", 4, 20, 3, _K2L1, dims="p128"), _tf("p128_5x150x3", 5, 150, 3, _K2L2_224, dims="p128"),
+       _tf("p128_20x150x3", 20, 150, 3, _K2L2, dims="p128"),
+       _tf("p128_tr_drop_4x20x3", 4, 20, 3, _K2L1, dims="p128", mode=1, drop=True),
+       _tf("p128_tr_drop_20x150x3", 20, 150, 3, _K2L2, dims="p128", mode=1, drop=True)]
+)
+_TR = dict(mode=1)
+TF_TRAIN_CASES_FWD = (
+    # whole tape on the resident kernel: both layouts, both deals; dropout off and on
+    [_tf("tr_k2_4x30x4", 4, 30, 4, _K2L1, **_TR), _tf("tr_k2_drop_32x128x3", 32, 128, 3, _K2L1, drop=True, **_TR),
+     _tf("tr_k2_drop_20x150x3", 20, 150, 3, _K2L2, drop=True, **_TR), _tf("tr_k2_2x256x3", 2, 256, 3, _K2L2, **_TR),
+     _tf("tr_k2_drop_9x190x3", 9, 190, 3, _K2L2_224, drop=True, **_TR),
+     # a partial tape, GVX_TRAIN_RESIDENT_LOOP=0: the launch per step beside the resident attention kernel (never replayed: the tape)
+     _tf("tr_part_k1_drop_4x30x4", 4, 30, 4, (1, 1, 1, 0, 1, 1, 1, 0), mode=2, drop=True),
+     _tf("tr_part_k1_5x200x3", 5, 200, 3, (1, 2, 2, 0, 1, 1, 1, 0), mode=2),
+     _tf("tr_loop0_k1_drop_6x40x3", 6, 40, 3, (1, 1, 1, 0, 1, 1, 1, 0), env={"GVX_TRAIN_RESIDENT_LOOP": "0"}, drop=True, **_TR),
+     # kind 0: L past 256, GVX_TRAIN_RESIDENT=0 (pre_gate stays: the shape could run beside the kernel in inference mode)
+     _tf("tr_k0_drop_3x257x3", 3, 257, 3, (0, 0, 0, 0, 0, 0, 0, 0), drop=True, **_TR),
+     _tf("tr_res0_k0_drop_6x40x3", 6, 40, 3, (0, 1, 1, 0, 1, 1, 0, 0), env={"GVX_TRAIN_RESIDENT": "0"}, drop=True, **_TR),
+     _tf("tr_small_drop_4x9x5", 4, 9, 5, (0, 1, 1, 0, 0, 0, 0, 0), dims="small", drop=True, **_TR),
+     _tf("tr_small_part_4x9x5", 4, 9, 5, (0, 1, 1, 0, 0, 0, 0, 0), dims="small", mode=2)]
+)
+
+
+def _ar(name, B, L, T, plan, dims="def", env=None, setter=None, lengths="ragged"):
+    return FwdCase(name, dims, env or {}, setter, B, L, T, lengths, 0, False, plan)
+
+
+_A2, _A1 = (2, 0, 1, 0), (1, 0, 1, 1)
+AR_CASES_FWD = (
+    # two resident kernels: layout 1 (1, 5, 32 rows; L 1, 77, 128), layout 2 (1, 16 rows; L 129, 256)
+    [_ar("ar2_1x1", 1, 1, 8, _A2, lengths="full"), _ar("ar2_5x77", 5, 77, 12, _A2), _ar("ar2_32x128", 32, 128, 10, _A2),
+     _ar("ar2_1x129", 1, 129, 8, _A2, lengths="full"), _ar("ar2_16x256", 16, 256, 8, _A2),
+     # launches per step: 17 .. 32 rows of 129 .. 256 tokens, L past 256, and every knob that leaves the pair
+     _ar("ar0_17x129", 17, 129, 8, (0, 1, 1, 1)), _ar("ar0_2x257", 2, 257, 8, (0, 1, 1, 1)),
+     _ar("ar1_5x77", 5, 77, 20, _A1, env={"GVX_AR_RESIDENT": "1", "GVX_AR_RESIDENT_LOOP": "0"}),
+     _ar("ar0_loop0_5x77", 5, 77, 20, (0, 1, 1, 1), env={"GVX_AR_RESIDENT_LOOP": "0"}),
+     _ar("ar0_nosplit_5x77", 5, 77, 8, (0, 0, 1, 1), env={"GVX_AR_RESIDENT_LOOP": "0", "GVX_AR_SPLIT_H": "0"}),
+     _ar("ar0_att16_3x40", 3, 40, 8, (0, 0, 1, 1), dims="att16"), _ar("ar0_att256_3x40", 3, 40, 8, (0, 0, 1, 1), dims="att256"),
+     # fold off: 36 rows in one call, a size with E / 4 != D / 8
+     _ar("ar0_36x30", 36, 30, 6, (0, 0, 0, 1)), _ar("ar0_dec512_3x40", 3, 40, 8, (0, 1, 0, 1), dims="dec512"),
+     _ar("ar0_p128_4x50", 4, 50, 8, (0, 1, 1, 1), dims="p128"), _ar("ar0_mels88_4x50", 4, 50, 8, (0, 1, 1, 1), dims="mels88"),
+     _ar("ar0_small_5x13", 5, 13, 20, (0, 0, 1, 1), dims="small")]
+)
+# both sides of every threshold of the two plan functions, default handle: (B, L) -> teacher-forced (kind, pa_layout, tile_layout),
+# autoregressive kind
+FWD_THRESHOLDS = {
+    (2, 200): ((2, 2, 2), 2), (3, 200): ((2, 2, 1), 2), (16, 200): ((2, 2, 1), 2), (17, 200): ((2, 2, 2), 0),
+    (32, 100): ((2, 1, 1), 2), (33, 100): ((0, 3, 3), 0), (64, 100): ((0, 3, 3), 0), (65, 100): ((0, 0, 0), 0),
+    (5, 128): ((2, 1, 1), 2), (5, 129): ((2, 2, 1), 2), (5, 256): ((2, 2, 1), 2), (5, 257): ((0, 0, 0), 0),
+}
+
+# encoder recurrence (gvx_encoder_lstm_forward): the (B, L, H) of ENC_BPTT_CASES, so forward and backward share shapes, plus the
+# launch-per-position loop at H = 256 by knob.  plan: 1 = the one resident launch (B <= 32, H = 256)
+EncFwdCase = collections.namedtuple("EncFwdCase", "name B L H lengths env plan")
+ENC_FWD_CASES = ([EncFwdCase(c.name, c.B, c.L, c.H, c.lengths, {}, 1 if (c.H == 256 and c.B <= 32) else 0) for c in ENC_BPTT_CASES]
+                 + [EncFwdCase("H256_3x21_per_position", 3, 21, 256, "ragged", {"GVX_ENC_PERSISTENT": "0"}, 0),
+                    EncFwdCase("H256_32x150_per_position", 32, 150, 256, "ragged", {"GVX_ENC_PERSISTENT": "0"}, 0)])
+# gvx_encoder_forward whole (embedding, convolutions, recurrence), default sizes: L shorter than the kernel of 5, 128, 300
+ENC_WHOLE_CASES = [(3, 1), (3, 2), (3, 4), (4, 128), (2, 300)]
+
+
+def fwd_configs(dims_name, n_tokens=40):
+    from genvox_amd.configs import AudioConfig, Tacotron2Config, TextConfig
+
+    d = FWD_DIMS[dims_name]
+    return (Tacotron2Config(**d["model"]), AudioConfig(filter_length=1024, hop_length=256, n_mels=d["n_mels"], log_func="np.log"),
+            TextConfig(n_tokens=n_tokens))
+
+
+def enc_fwd_configs(H):
+    """A model whose encoder BiLSTM has H units per direction; everything around it as small as the dims checks allow."""
+    from genvox_amd.configs import AudioConfig, Tacotron2Config, TextConfig
+
+    if H == 256:
+        return fwd_configs("def")
+    m = dict(FWD_DIMS["a8_F1_kl1"]["model"], symbols_embedding_dim=2 * H, encoder_embedding_dim=2 * H)
+    return Tacotron2Config(**m), AudioConfig(filter_length=1024, hop_length=256, n_mels=16, log_func="np.log"), TextConfig(n_tokens=40)
+
+
+def create_handle(lib, dims, env=None, setter=None):
+    """gvx_model_create under `env` (restored afterwards), then setter(handle, 0).  Host only: no blob is bound."""
+    h = C.c_void_p()
+    env = env or {}
+    saved = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        rc = lib.gvx_model_create(C.byref(dims), C.byref(h))
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                del os.environ[k]
+            else:
+                os.environ[k] = v
+    assert rc == 0, (rc, lib.gvx_last_error())
+    if setter:
+        assert getattr(lib, setter)(h, 0) == 0
+    return h
+
+
+def decoder_plan(lib, handle, mode, B, L):
+    """(status, teacher-forced plan (8 fields), autoregressive plan (4 fields)) of gvx_debug_decoder_plan.  Host arithmetic only; the
+    export is in neither the public header nor _lib.SIGNATURES."""
+    fn = lib.gvx_debug_decoder_plan
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+    out = (C.c_int * 12)(*([-1] * 12))
+    rc = fn(handle, mode, B, L, out)
+    return rc, tuple(out[:8]), tuple(out[8:])
+
+
+def graph_replays(lib, handle):
+    fn = lib.gvx_debug_graph_replays
+    fn.restype = C.c_longlong
+    fn.argtypes = [C.c_void_p]
+    return int(fn(handle))
+
+
+def encoder_resident(lib, handle, B):
+    fn = lib.gvx_debug_encoder_resident
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_int]
+    return int(fn(handle, B))

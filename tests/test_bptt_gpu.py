@@ -44,6 +44,7 @@ import torch
 import torch.nn.functional as F
 
 from genvox_amd import _lib
+from tests.forward_ref import decoder_step, lstm_cell as _lstm_cell   # (the forward both this file and test_forward_loops_gpu.py state once)
 from tests.helpers import (BPTT_BY_NAME, BPTT_CASES, BPTT_DEFAULT, BPTT_L_LIMIT, BPTT_ROW_CASES, BPTT_STRIDE_CASES, ENC_BPTT_CASES,
                            bptt_lengths)
 
@@ -110,12 +111,6 @@ def _track(x):
     return x
 
 
-def _lstm_cell(gates, c):
-    i, f, g, o = gates.chunk(4, dim=1)
-    c_new = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(g)
-    return torch.sigmoid(o) * torch.tanh(c_new), c_new
-
-
 # ------------------------------------------------------------------------------------------------------------ decoder loop
 _DEC_REF = {}
 
@@ -142,26 +137,16 @@ def decoder_reference(case):
     dec_keep = (torch.rand(T, B, D, generator=gen) < 0.8)
     att_keep[T // 2, 0] = False                                              # a whole row dropped at one step
     dec_keep[0, B - 1] = False
-    h_a, c_a, h_d, c_d = torch.zeros(B, A).double(), torch.zeros(B, A).double(), torch.zeros(B, D).double(), torch.zeros(B, D).double()
-    ctx, w, wcum = torch.zeros(B, E).double(), torch.zeros(B, L).double(), torch.zeros(B, L).double()
-    ga_l, gd_l, q_l, ctx_l, w_l, ca_l, cd_l = [], [], [], [], [], [c_a], [c_d]
+    W = {"w_ih_a": w_ih_a, "w_hh_a": w_hh_a, "b_a": b_a, "w_ih_d": w_ih_d, "w_hh_d": w_hh_d, "b_d": b_d, "wq": wq, "v": v, "loc_conv": loc_conv,
+         "loc_dense": loc_dense}
+    z = lambda n: torch.zeros(B, n).double()
+    st = {"h_a": z(A), "c_a": z(A), "h_d": z(D), "c_d": z(D), "ctx": z(E), "w": z(L), "wcum": z(L)}
+    ga_l, gd_l, q_l, ctx_l, w_l, ca_l, cd_l = [], [], [], [], [], [st["c_a"]], [st["c_d"]]
     loss = 0.0
     for t in range(T):
-        ga = _track(torch.cat((x_p[t], ctx), 1) @ w_ih_a.t() + h_a @ w_hh_a.t() + b_a)
-        h, c_a = _lstm_cell(ga, c_a)
-        h_a = h * (att_keep[t].double() * ATT_SCALE)
-        q = _track(h_a @ wq.t())
-        locf = F.conv1d(torch.stack((w, wcum), 1), loc_conv, padding=(kl - 1) // 2)      # [B, F, L]
-        loc = locf.transpose(1, 2) @ loc_dense.t()                                           # [B, L, a]
-        e = torch.tanh(q[:, None, :] + loc + pm) @ v
-        w = torch.softmax(e.masked_fill(mask, float("-inf")), dim=1)
-        ctx = _track((w[:, None, :] @ memory)[:, 0])
-        wcum = wcum + w
-        gd = _track(torch.cat((h_a, ctx), 1) @ w_ih_d.t() + h_d @ w_hh_d.t() + b_d)
-        h, c_d = _lstm_cell(gd, c_d)
-        h_d = h * (dec_keep[t].double() * DEC_SCALE)
-        loss = loss + (dhc[t] * torch.cat((h_d, ctx), 1)).sum()
-        ga_l.append(ga); gd_l.append(gd); q_l.append(q); ctx_l.append(ctx); w_l.append(w); ca_l.append(c_a); cd_l.append(c_d)
+        r = decoder_step(W, st, x_p[t], memory, pm, mask, att_keep[t].double() * ATT_SCALE, dec_keep[t].double() * DEC_SCALE, track=_track)
+        loss = loss + (dhc[t] * torch.cat((r["h_d"], r["ctx"]), 1)).sum()
+        ga_l.append(r["ga"]); gd_l.append(r["gd"]); q_l.append(r["q"]); ctx_l.append(r["ctx"]); w_l.append(r["w"]); ca_l.append(r["c_a"]); cd_l.append(r["c_d"])
     loss.backward()
     st = lambda xs: torch.stack([x.detach() for x in xs])
     unit_major = lambda g, H: g.detach().reshape(B, 4, H).permute(0, 2, 1)                    # [B][H][4]: unit-major, gate-minor

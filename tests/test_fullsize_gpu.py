@@ -9,13 +9,13 @@ import numpy as np
 import pytest
 import torch
 
-from genvox_amd import weights as gw
+from genvox_amd import _lib, weights as gw
 from genvox_amd.audio import AudioProcessor
 from genvox_amd.configs import AudioConfig, Tacotron2Config, TextConfig
 from genvox_amd.tacotron2 import Tacotron2
 from oracle import audio_ref, tacotron2_ref
 from tests.golden.cases import AR_CASES, TF_CASES, case_configs
-from tests.helpers import TOL, case_state_dict, load_fixture, max_abs_diff, tf_batch, unpack_masks
+from tests.helpers import TOL, case_state_dict, graph_replays, load_fixture, max_abs_diff, tf_batch, unpack_masks
 
 pytestmark = pytest.mark.gpu
 KEYS = ("alignments", "gate_outputs", "mel_outputs", "mel_outputs_postnet")
@@ -24,6 +24,20 @@ KEYS = ("alignments", "gate_outputs", "mel_outputs", "mel_outputs_postnet")
 def full_configs(**over):
     mc = Tacotron2Config(**over)
     return mc, AudioConfig(filter_length=1024, hop_length=256, log_func="np.log"), TextConfig(n_tokens=40)
+
+
+def _launch_per_step(m):
+    """The model's handle switched to the loops that replay hipGraphs (gvx_model_set_resident_kernels(handle, 0): a launch pair per
+    decoder step, a launch per encoder position - what every handle runs after a hand-off time-out, and what rows past 256 tokens
+    and other layer sizes always run).  At the default layer sizes and B <= 4, L <= 40 both loops would otherwise run on the
+    resident kernels, whose plan replays nothing, and the two tests below would compare those with themselves."""
+    m._ensure_packed()
+    _lib.check(_lib.load().gvx_model_set_resident_kernels(m._handle, 0))
+    return m
+
+
+def _replays(m):
+    return graph_replays(_lib.load(), m._handle)
 
 
 # --------------------------------------------------------------------------------------------------------------------
@@ -47,19 +61,22 @@ def test_rebinding_weights_never_replays_stale_graphs(monkeypatch):
 
     m = Tacotron2(mc, ac, tc)
     m.load_state_dict(sd_a)
-    m = m.to("cuda:0")
+    m = _launch_per_step(m.to("cuda:0"))
     out_a = m.forward(batch)
     ar_a = m.inference(ar_in)
+    replays_a = _replays(m)
+    assert replays_a > 0, "the first round replayed no graph: the second could not replay a stale one"
     blob_a = m._blob.data_ptr()
     m.load_state_dict(sd_b)                      # checkpoint B into the same object (Synthesizer / evaluation flow)
     out_b = m.forward(batch)
     ar_b = m.inference(ar_in)
     mem_b = m.encode(tok, None)
+    assert _replays(m) > replays_a, "the second round replayed no graph"
     del blob_a   # the allocator may or may not hand the new blob the old address; both cases must work
 
     fresh = Tacotron2(mc, ac, tc)
     fresh.load_state_dict(sd_b)
-    fresh = fresh.to("cuda:0")
+    fresh = _launch_per_step(fresh.to("cuda:0"))
     want, ar_want, mem_want = fresh.forward(batch), fresh.inference(ar_in), fresh.encode(tok, None)
     for k in KEYS:
         assert torch.equal(out_b[k], want[k]), f"teacher-forced {k} differs after re-binding"
@@ -89,7 +106,7 @@ def test_graph_replay_equals_eager(name, monkeypatch):
         mc.max_decoder_steps, mc.gate_threshold = steps, float(fx["gate_threshold"])
         m = Tacotron2(mc, ac, tc)
         m.load_state_dict(case_state_dict(name))
-        m = m.to("cuda:0")
+        m = _launch_per_step(m.to("cuda:0"))
         masks = unpack_masks(fx["keep_masks_packed"], (2, steps, mc.prenet_dim)).reshape(2, steps, 1, mc.prenet_dim)
         run = lambda: m.inference({"tokens": torch.from_numpy(fx["tokens"]).int(), "prenet_keep_masks": masks})
     else:
@@ -97,10 +114,14 @@ def test_graph_replay_equals_eager(name, monkeypatch):
         mc, ac, tc = case_configs(case)
         m = Tacotron2(mc, ac, tc)
         m.load_state_dict(case_state_dict(name))
-        m = m.to("cuda:0")
+        m = _launch_per_step(m.to("cuda:0"))
         masks = unpack_masks(fx["keep_masks_packed"], (2, (case["T"] + 1) * case["B"], mc.prenet_dim))
         run = lambda: m.forward({**tf_batch(fx), "prenet_keep_masks": masks})
-    first, second, third = run(), run(), run()
+    counts = [_replays(m)]
+    first = run(); counts.append(_replays(m))
+    second = run(); counts.append(_replays(m))
+    third = run(); counts.append(_replays(m))
+    assert counts[0] == 0 and counts[1] == 0 and counts[1] < counts[2] < counts[3], counts   # eager, captured + replayed, replayed
     for k in KEYS:
         assert torch.equal(first[k], second[k]) and torch.equal(second[k], third[k]), k
         assert max_abs_diff(third[k], fx[k]) <= TOL, k

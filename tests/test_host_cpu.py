@@ -419,3 +419,60 @@ def write_decoder_plan_table():
     with open(PLAN_TABLE, "w") as f:
         json.dump(decoder_plan_table(), f, indent=0, sort_keys=True)
         f.write("\n")
+
+
+# ---- the forward recurrences' case tables (tests/helpers.py) against the host-only plan queries
+def test_forward_loop_plan_of_every_listed_case():
+    """Every line of TF_CASES_FWD / TF_TRAIN_CASES_FWD / AR_CASES_FWD takes the plan it is listed for (gvx_debug_decoder_plan: the
+    two functions the loops themselves call), every value a plan field can take is reached by some case, and both sides of every
+    threshold of the two plan functions sit where the table says.  Channel sizes the library refuses are refused at creation."""
+    from tests import helpers as H
+
+    lib = _lib.load()
+    seen_tf, seen_ar = [set() for _ in range(8)], [set() for _ in range(4)]
+    names = set()
+    for table, ar in ((H.TF_CASES_FWD, False), (H.TF_TRAIN_CASES_FWD, False), (H.AR_CASES_FWD, True)):
+        for c in table:
+            assert c.name not in names, c.name
+            names.add(c.name)
+            h = H.create_handle(lib, dims_from_configs(*H.fwd_configs(c.dims)), c.env, c.setter)
+            rc, tf, arp = H.decoder_plan(lib, h, c.mode, c.B, c.L)
+            lib.gvx_model_destroy(h)
+            assert rc == 0 and (arp if ar else tf) == tuple(c.plan), (c.name, rc, tf, arp)
+            for s, v in zip(seen_ar if ar else seen_tf, arp if ar else tf):
+                s.add(v)
+    assert seen_tf == [{0, 1, 2}, {0, 1, 2, 3}, {0, 1, 2, 3}, {0, 1}, {0, 1}, {0, 1}, {0, 1}, {0, 1}], seen_tf
+    assert seen_ar == [{0, 1, 2}, {0, 1}, {0, 1}, {0, 1}], seen_ar
+    h = H.create_handle(lib, dims_from_configs(*H.fwd_configs("def")))
+    for (B, L), (tf_want, ar_kind) in H.FWD_THRESHOLDS.items():
+        rc, tf, arp = H.decoder_plan(lib, h, 0, B, L)
+        assert rc == 0 and tf[:3] == tf_want and arp[0] == ar_kind, (B, L, tf, arp)
+        assert tf[0] == lib.gvx_teacher_forced_loop_kind(h, B, L) and arp[0] == lib.gvx_autoregressive_loop_kind(h, B, L)
+    # the training modes: the whole tape keeps the resident kernel, a partial one the launch per step beside the attention kernel
+    assert H.decoder_plan(lib, h, 1, 32, 128)[1][0] == 2 and H.decoder_plan(lib, h, 2, 32, 128)[1] == (1, 1, 1, 0, 1, 1, 1, 0)
+    out = (C.c_int * 12)(*([-7] * 12))
+    for bad in ((3, 4, 4), (-1, 4, 4), (0, 0, 4), (0, 4, 0)):
+        assert lib.gvx_debug_decoder_plan(h, *bad, out) == -1 and list(out) == [-7] * 12, bad
+    assert lib.gvx_debug_decoder_plan(None, 0, 4, 4, out) == -1 and H.graph_replays(lib, h) == 0 and H.graph_replays(lib, None) == -1
+    lib.gvx_model_destroy(h)
+    for over in H.FWD_REFUSED_DIMS:
+        mk = {k: v for k, v in over.items() if k != "n_mels"}
+        d = dims_from_configs(Tacotron2Config(**mk), AudioConfig(n_mels=over.get("n_mels", 80)), TextConfig(n_tokens=40))
+        hh = C.c_void_p()
+        assert lib.gvx_model_create(C.byref(d), C.byref(hh)) == -2 and not hh.value, over
+
+
+def test_encoder_recurrence_plan_of_every_listed_case():
+    """ENC_FWD_CASES: the one resident launch for B <= 32 at H = 256 unless GVX_ENC_PERSISTENT=0, the launch per position otherwise
+    (gvx_debug_encoder_resident); both sides of B 32 | 33."""
+    from tests import helpers as H
+
+    lib = _lib.load()
+    for c in H.ENC_FWD_CASES:
+        h = H.create_handle(lib, dims_from_configs(*H.enc_fwd_configs(c.H)), c.env)
+        assert H.encoder_resident(lib, h, c.B) == c.plan, c.name
+        lib.gvx_model_destroy(h)
+    assert {c.plan for c in H.ENC_FWD_CASES} == {0, 1}
+    h = H.create_handle(lib, dims_from_configs(*H.enc_fwd_configs(256)))
+    assert [H.encoder_resident(lib, h, B) for B in (1, 32, 33, 64, 0)] == [1, 1, 0, 0, 0] and H.encoder_resident(lib, None, 4) == 0
+    lib.gvx_model_destroy(h)

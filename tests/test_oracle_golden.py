@@ -169,3 +169,79 @@ def test_training_step_oracle_matches_reference_backward():
         ref = z["grad." + k]
         scale = max(float(np.abs(ref).max()), 1e-6)
         assert max_abs_diff(grads[k], ref) <= max(1e-4 * scale, 2e-6), k
+
+
+# ---- tests/forward_ref.py: the float64 reference of the forward loops (what tests/test_forward_loops_gpu.py holds the kernels to)
+def _ref_encoder_and_weights(sd, tokens, lengths):
+    from tests import forward_ref as fr
+
+    sd64 = fr.to_f64(sd)
+    return fr, fr.decoder_weights(sd), fr.whole_encoder(sd64, tokens, lengths)
+
+
+@pytest.mark.parametrize("name", list(TF_CASES))
+def test_float64_forward_reference_matches_the_teacher_forced_fixtures(name):
+    """whole_encoder + teacher_forced in float64 against the reference's own fp32 outputs, at the bound the fp32 oracle meets."""
+    case, fx = TF_CASES[name], load_fixture(name)
+    mc, ac, tc = case_configs(case)
+    B, T = case["B"], case["T"]
+    fr, W, enc = _ref_encoder_and_weights(case_state_dict(name), torch.from_numpy(fx["token_padded"]), fx["token_lengths"])
+    masks = unpack_masks(fx["keep_masks_packed"], (2, (T + 1) * B, mc.prenet_dim))
+    out = fr.teacher_forced(W, enc["memory"], fx["token_lengths"], torch.from_numpy(fx["mel_padded"]).double(), masks)
+    pad = torch.arange(T)[None, :] >= torch.from_numpy(fx["mel_lengths"])[:, None]
+    got = {"encoder_outputs": enc["memory"], "processed_memory": out["pm"], "attention_contexts": out["ctx"].transpose(0, 1),
+           "alignments": out["w"].transpose(0, 1), "gate_outputs": out["gate"].t().masked_fill(pad, 1e3),
+           "mel_outputs": out["mel"].permute(1, 2, 0).masked_fill(pad[:, None, :], 0.0), "prenet_outputs": out["prenet"]}
+    for key, g in got.items():
+        want = fx[key][:T] if key == "prenet_outputs" else fx[key]
+        assert max_abs_diff(g, want) <= ORACLE_TOL, f"{name}/{key}"
+    assert out["ga"].dtype == torch.float64 and out["w"].dtype == torch.float64
+    assert max_abs_diff(out["w"].sum(-1), torch.ones(T, B)) <= 1e-12
+
+
+@pytest.mark.parametrize("name", list(AR_CASES))
+def test_float64_forward_reference_matches_the_autoregressive_fixtures(name):
+    """autoregressive() against the reference's free-running decode: the stop step exactly, every frame at the oracle's bound."""
+    case, fx = AR_CASES[name], load_fixture(name)
+    mc, ac, tc = case_configs(case)
+    steps, thr = int(fx["max_decoder_steps"]), float(fx["gate_threshold"])
+    fr, W, enc = _ref_encoder_and_weights(case_state_dict(name), torch.from_numpy(fx["tokens"]), None)
+    masks = unpack_masks(fx["keep_masks_packed"], (2, steps, mc.prenet_dim)).reshape(2, steps, 1, mc.prenet_dim)
+    out = fr.autoregressive(W, enc["memory"], [case["L"]], steps, thr, masks)
+    n = fx["mel_outputs"].shape[2]
+    assert int(out["n_frames"][0]) == n and (n < steps) == case["gate_fires"]
+    assert 0.0 < out["margin"] < 1.0   # (reported, not bounded: the fixtures' thresholds were not chosen for a margin - ar_small_gate passes 5e-6 from its own)
+    assert max_abs_diff(out["mel_out"][:, :, :n], fx["mel_outputs"]) <= ORACLE_TOL
+    assert max_abs_diff(out["gate_out"][:, :n], fx["gate_outputs"]) <= ORACLE_TOL
+    assert max_abs_diff(out["align_out"][:, :n], fx["alignments"]) <= ORACLE_TOL
+    assert bool((out["mel_out"][:, :, n:] == 0).all()) and bool((out["gate_out"][:, n:] == 1e3).all()) and bool((out["align_out"][:, n:] == 0).all())
+
+
+def test_float64_forward_reference_matches_the_training_fixture():
+    """encoder_bilstm + teacher_forced with the hidden-state dropout masks against the reference's .train() forward
+    (tests/golden/train_small.npz); the training-mode convolution stack in front is oracle/train_ref.py's."""
+    from genvox_amd import weights as gw
+    from oracle import train_ref as tr
+    from tests import forward_ref as fr
+    from tests.golden.cases import TRAIN_CASE
+
+    z = load_fixture("train_small")
+    mc, ac, tc = case_configs(TRAIN_CASE)
+    sd = gw.generate_state_dict(mc, ac, tc, seed=TRAIN_CASE["weight_seed"], peaky_attention=True)
+    B, L, T = TRAIN_CASE["B"], TRAIN_CASE["L"], TRAIN_CASE["T"]
+    E, A, D, P, ne = mc.encoder_embedding_dim, mc.attention_rnn_dim, mc.decoder_rnn_dim, mc.prenet_dim, mc.encoder_n_convolutions
+
+    def unpack(packed, shape):
+        k = int(np.prod(shape))
+        return torch.from_numpy(np.unpackbits(packed, axis=1)[:, :k].reshape((packed.shape[0],) + tuple(shape)))
+
+    emb = sd["embedding.weight"][torch.from_numpy(z["token_padded"])].transpose(1, 2)
+    conv, _ = tr.convstack_train_forward(sd, "encoder.convolutions", ne, tr.encoder_acts(ne), emb, list(unpack(z["enc_keep_packed"], (B, E, L))))
+    enc = fr.encoder_bilstm(fr.to_f64(sd), conv.double(), z["token_lengths"])
+    out = fr.teacher_forced(fr.decoder_weights(sd), enc["memory"], z["token_lengths"], torch.from_numpy(z["mel_padded"]).double(),
+                            unpack(z["prenet_keep_packed"], (T + 1, B, P)), unpack(z["att_keep_packed"], (B, A)), unpack(z["dec_keep_packed"], (B, D)),
+                            1.0 / (1.0 - mc.p_attention_dropout), 1.0 / (1.0 - mc.p_decoder_dropout))
+    assert max_abs_diff(out["mel"].permute(1, 2, 0), z["decoder_mel_unmasked"]) <= ORACLE_TOL
+    assert max_abs_diff(out["w"].transpose(0, 1), z["alignments"]) <= ORACLE_TOL
+    pad = torch.arange(T)[None, :] >= torch.from_numpy(z["mel_lengths"])[:, None]
+    assert max_abs_diff(out["gate"].t().masked_fill(pad, 1e3), z["gate_outputs"]) <= ORACLE_TOL
