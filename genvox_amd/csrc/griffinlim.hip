@@ -93,10 +93,12 @@ int get_plans(gvx_gl_plan* p, long batch, FftPair** out) {
 }
 
 struct GlWs {  // byte offsets
-    size_t mag, ang, reb0, reb1, fr, y, wss, amp, fft_work, wss_tail, total;
+    size_t mag, ang, reb0, reb1, fr, y, wss, amp, fft_work, basis, wss_tail, total;
 };
 
-// ragged: room for the per-row tail of the window sum of squares behind everything else (the uniform layout is a prefix)
+// basis: the mel basis of the wav -> mel calls in rows padded for the GEMM (its size does not depend on the frame count, so it
+// has a region of its own: no call with M mels is too short for it).  ragged: room for the per-row tail of the window sum of
+// squares behind everything else (the uniform layout is a prefix)
 GlWs gl_plan_ws(const gvx_gl_plan* p, int B, int T, int M, size_t fft_work, bool ragged = false) {
     GlWs w{};
     size_t off = 0;
@@ -112,6 +114,7 @@ GlWs gl_plan_ws(const gvx_gl_plan* p, int B, int T, int M, size_t fft_work, bool
     w.wss = take(n * sizeof(float));
     w.amp = take(frames * (size_t)(M > 0 ? M : 1) * sizeof(float));
     w.fft_work = take(fft_work);
+    w.basis = take((size_t)(M > 0 ? M : 0) * (size_t)((p->bins + 3) & ~3) * sizeof(float));
     w.wss_tail = ragged ? take((size_t)B * (p->n_fft - p->hop) * sizeof(float)) : 0;
     w.total = off;
     return w;
@@ -1508,6 +1511,7 @@ int gvx_wav_to_mel(gvx_gl_plan* p, const float* signal, const float* window, con
                    int log10_kind, float ref, float* mel_db_out, void* ws, size_t ws_bytes, void* stream) {
     if (!p || !signal || !window || !mel_basis || !mel_db_out) return gl_fail(GVX_ERR_INVALID_ARG, "null argument");
     if (n_samples < p->n_fft) return gl_fail(GVX_ERR_INVALID_ARG, "signal shorter than one frame");
+    if (n_mels < 1) return gl_fail(GVX_ERR_INVALID_ARG, "n_mels must be >= 1");
     const int T = (int)((n_samples - p->n_fft) / p->hop + 1);
     FftPair* fp = nullptr;
     int rc = get_plans(p, (long)B * T, &fp);
@@ -1518,11 +1522,10 @@ int gvx_wav_to_mel(gvx_gl_plan* p, const float* signal, const float* window, con
     hipStream_t s = (hipStream_t)stream;
     const long frames = (long)B * T;
     const int kp = (p->bins + 3) & ~3;                     // GEMM K must be a multiple of 4: 513 -> 516, zero padded
-    // workspace reuse: fr = framed signal, reb0 = spectrum, ang = padded magnitudes, reb1 = padded basis, amp = mel amplitudes
-    if ((size_t)frames * kp * sizeof(float) > (size_t)frames * p->bins * sizeof(float2) || (size_t)n_mels * kp > (size_t)frames * p->bins * 2)
-        return gl_fail(GVX_ERR_WORKSPACE, "workspace regions too small for the padded operands");
+    // workspace reuse: fr = framed signal, reb0 = spectrum, ang = padded magnitudes (kp floats per frame inside bins float2: kp <= 2 bins
+    // for every n_fft), amp = mel amplitudes; the padded basis has its own region
     float* mag_p = wsp<float>(ws, w.ang);
-    float* basis_p = wsp<float>(ws, w.reb1);
+    float* basis_p = wsp<float>(ws, w.basis);
     if (p->tw && !getenv_flag("GVX_GL_ROCFFT")) {   // n_fft 1024 / hop 256: framing + window + FFT + magnitude in one kernel
         stft_magnitude_kernel<false, float><<<dim3((unsigned)((frames + GLF_FRAMES - 1) / GLF_FRAMES)), GLF_FRAMES * 64, 0, s>>>(
             signal, n_samples, window, p->tw, mag_p, kp, T, frames, WavRows{});
@@ -1557,9 +1560,9 @@ int gvx_wav_to_mel(gvx_gl_plan* p, const float* signal, const float* window, con
 // ---- ragged wav -> mel: PCM rows of different lengths, trimmed and normalised per row, one launch set per batch ------------------
 namespace {
 
-struct WavWs {   // the uniform layout of T frames per row, then the padded mel basis and the per-row words
+struct WavWs {   // the uniform layout of T frames per row (the padded mel basis included), then the per-row words
     GlWs g;
-    size_t basis, rows, peak, peak_bits, total;
+    size_t rows, peak, peak_bits, total;
 };
 
 WavWs wav_plan_ws(const gvx_gl_plan* p, int B, int T, int M, size_t fft_work) {
@@ -1567,8 +1570,6 @@ WavWs wav_plan_ws(const gvx_gl_plan* p, int B, int T, int M, size_t fft_work) {
     w.g = gl_plan_ws(p, B, T, M, fft_work);
     size_t off = w.g.total;
     auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    const size_t kp = (size_t)((p->bins + 3) & ~3);
-    w.basis = take((size_t)(M > 0 ? M : 1) * kp * sizeof(float));
     w.rows = take((size_t)B * 2 * sizeof(int32_t));
     w.peak = take((size_t)B * sizeof(double));
     w.peak_bits = take((size_t)B * sizeof(unsigned int));
@@ -1609,7 +1610,7 @@ int wav_to_mel_ragged_impl(gvx_gl_plan* p, FftPair* fp, const PCM* pcm, const fl
     const WavRows wr{rows, wsp<double>(ws, w.peak), normalize};
     // workspace reuse as in gvx_wav_to_mel: fr = framed signal, reb0 = spectrum, ang = padded magnitudes, amp = mel amplitudes
     float* mag_p = wsp<float>(ws, w.g.ang);
-    float* basis_p = wsp<float>(ws, w.basis);
+    float* basis_p = wsp<float>(ws, w.g.basis);
     if (wav_fused(p)) {
         stft_magnitude_kernel<true, PCM><<<dim3((unsigned)((T + GLF_FRAMES - 1) / GLF_FRAMES), B), GLF_FRAMES * 64, 0, s>>>(
             pcm, n_max, window, p->tw, mag_p, kp, T, frames, wr);

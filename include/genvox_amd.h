@@ -396,6 +396,10 @@ int gvx_stage_times_ms(gvx_model* model, float* times5_out, int* decoder_launche
 typedef struct gvx_gl_plan gvx_gl_plan;
 int gvx_gl_plan_create(int n_fft, int hop, gvx_gl_plan** out);
 void gvx_gl_plan_destroy(gvx_gl_plan* plan);
+/* Bytes every uniform call below needs for B rows of T frames.  n_mels > 0 includes the amplitudes of gvx_mel_to_magnitude /
+ * gvx_wav_to_mel and a region of n_mels * ((bins + 3) & ~3) floats for gvx_wav_to_mel's zero-padded mel basis, whose size does
+ * not depend on B*T: gvx_wav_to_mel serves any B*T >= 1 (one file of one frame included).  n_mels = 0 sizes the calls that take
+ * no mel (gvx_stft, gvx_istft, gvx_griffin_lim). */
 size_t gvx_gl_workspace_bytes(gvx_gl_plan* plan, int B, int T, int n_mels);
 
 /* stft (utils/audio/base.py:58-69): signal [B][n_samples] -> spec_out complex [B][bins][T], T = (n_samples-n_fft)/hop+1 */

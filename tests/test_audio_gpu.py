@@ -5,7 +5,11 @@ Griffin-Lim is an iterative phase retrieval: in bins that carry no energy the ph
 oracle run in float64 instead of float32 flips such bins by up to pi after 8 iterations), so phases are compared on
 the unit circle weighted by magnitude, with tolerances taken from that float32-vs-float64 self-drift
 (8e-5 / 1.4e-4 / 1.9e-2 after 1 / 2 / 32 iterations), and the spectral-convergence metric of the result is compared
-as well (it agrees to 1e-5 between float32 and float64)."""
+as well (it agrees to 1e-5 between float32 and float64).
+
+These are parity claims against the reference's fixture, one number per call.  Element-wise bounds - every bin, sample and mel
+element against a float64 computation, at the workgroup edges of the kernels and on every Griffin-Lim path - are in
+tests/test_vocoder_kernels_gpu.py."""
 import numpy as np
 import pytest
 import torch

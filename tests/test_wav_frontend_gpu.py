@@ -37,14 +37,8 @@ def fx():
 
 
 def alone(ap, signal: np.ndarray) -> torch.Tensor:
-    """``wav_to_mel`` on one normalised signal.  The uniform call lays its padded mel basis into a workspace region sized by the
-    frame count and refuses batches of fewer than ~41 frames, so a short signal is sent as several identical rows (rows of a
-    uniform batch do not see each other) and the first is taken."""
-    c = ap.config
-    T = frames_of(signal.shape[0], c.filter_length, c.hop_length)
-    bins = c.filter_length // 2 + 1
-    reps = -(-(c.n_mels * ((bins + 3) & ~3)) // (2 * bins * T))
-    return ap.wav_to_mel(torch.from_numpy(signal)[None].repeat(reps, 1))[0]
+    """``wav_to_mel`` on one normalised signal, as one row (however short: the padded mel basis has a workspace region of its own)."""
+    return ap.wav_to_mel(torch.from_numpy(signal)[None])[0]
 
 
 def recording(rng, frames, n_fft, hop, front_chunks=0, back_chunks=0, extra=0):
@@ -118,6 +112,19 @@ def test_ragged_rows_equal_single_row_calls(n_fft, hop):
     for b, r in enumerate(as_float):
         left, right = silence_bounds(r, AUDIO_CASE["fs"], ap.config.trim_dbfs, 1.0)
         assert torch.equal(mel_n[b, :, : counts[b]], alone(ap, r[left:right] / np.abs(r[left:right]).max())), b
+
+
+def test_one_row_alone_equals_the_first_of_identical_rows(ap):
+    """Rows of a uniform batch do not see each other: a short signal alone (one frame, and 3 frames - fewer than a workgroup of the
+    fused STFT takes) equals the first of several identical rows bit for bit, also where the frames of two rows share a workgroup."""
+    rng = np.random.default_rng(12)
+    for frames, reps in ((1, 41), (3, 14), (5, 9), (40, 2)):
+        sig = (rng.standard_normal(1024 + (frames - 1) * 256 + 7) * 0.2).astype(np.float32)
+        one = alone(ap, sig)
+        many = ap.wav_to_mel(torch.from_numpy(sig)[None].repeat(reps, 1))
+        assert one.shape == (ap.config.n_mels, frames)
+        for r in range(reps):
+            assert torch.equal(many[r], one), (frames, r)
 
 
 def test_rows_of_a_large_batch_equal_single_row_calls(ap):
