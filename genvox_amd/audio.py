@@ -4,7 +4,8 @@ One-off host work stays on the host exactly as in the reference: the Slaney mel 
 (utils/audio/base.py:90-137; float64 intermediates, float32 result), the Hann window and the Butterworth
 coefficients (scipy.signal.butter, base.py:164-166).  Everything per utterance - dB->amplitude, pseudo-inverse
 projection, fast Griffin-Lim, inverse STFT, clip/trim/normalise/low-pass - runs batched on the GPU through the
-C ABI (include/genvox_amd.h, vocoder section; rocFFT underneath).  There is no CPU fallback.
+C ABI (include/genvox_amd.h, vocoder section; FFTs in LDS at n_fft 1024 / hop 256, rocFFT at other sizes).  There is no
+CPU fallback.
 """
 from __future__ import annotations
 
@@ -63,6 +64,11 @@ def keep_by_duration(durations: Sequence[float], config: AudioConfig) -> List[in
     return [i for i, d in enumerate(durations) if config.min_wav_duration <= d and d <= config.max_wav_duration]
 
 
+def _int_list(x) -> List[int]:
+    """A [B] tensor, array or sequence of counts as host ints."""
+    return [int(v) for v in (x.tolist() if isinstance(x, (torch.Tensor, np.ndarray)) else x)]
+
+
 class _RowLengths(NamedTuple):
     """Frame counts of a ragged batch that passed AudioProcessor._check_lengths: host ints and the device int32 [B] the kernels read."""
     host: List[int]
@@ -84,7 +90,7 @@ class AudioProcessor:
         self.device = torch.device(device)
         self._plan: Optional[int] = None
         self._ws: Optional[torch.Tensor] = None
-        self._dev_consts = None
+        self._window_dev = self._inv_basis_dev = self._mel_basis_dev = None   # device copies, made in _ensure
 
     def __del__(self):
         try:
@@ -102,19 +108,34 @@ class AudioProcessor:
             h = C.c_void_p()
             _lib.check(lib.gvx_gl_plan_create(self.config.filter_length, self.config.hop_length, C.byref(h)))
             self._plan = h.value
-        if self._dev_consts is None:
-            self._dev_consts = (torch.from_numpy(self.window).to(self.device),
-                                torch.from_numpy(np.ascontiguousarray(self.inverse_mel_basis, dtype=np.float32)).to(self.device))
+        if self._window_dev is None:
+            self._window_dev = torch.from_numpy(self.window).to(self.device)
+            self._inv_basis_dev = torch.from_numpy(np.ascontiguousarray(self.inverse_mel_basis, dtype=np.float32)).to(self.device)
+            self._mel_basis_dev = torch.from_numpy(np.ascontiguousarray(self.mel_basis)).to(self.device)
         return lib
 
-    def _workspace(self, B: int, T: int, ragged: bool = False) -> torch.Tensor:
-        lib = _lib.load()
-        need = (lib.gvx_gl_workspace_bytes_ragged if ragged else lib.gvx_gl_workspace_bytes)(self._plan, B, T, self.config.n_mels)
+    def _workspace_for(self, what: str, size_fn, *args) -> torch.Tensor:
+        """The shared workspace, grown to what ``size_fn(plan, *args)`` of the C ABI asks for."""
+        need = size_fn(self._plan, *args)
         if need == 0:
-            raise _lib.GvxError("could not plan the vocoder workspace: " + _lib.load().gvx_last_error().decode())
+            raise _lib.GvxError(f"could not plan the {what} workspace: " + _lib.load().gvx_last_error().decode())
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._ws
+
+    def _workspace(self, B: int, T: int, ragged: bool = False) -> torch.Tensor:
+        lib = _lib.load()
+        return self._workspace_for("vocoder", lib.gvx_gl_workspace_bytes_ragged if ragged else lib.gvx_gl_workspace_bytes, B, T, self.config.n_mels)
+
+    @property
+    def _dev_consts(self) -> Tuple[Optional[torch.Tensor], ...]:
+        """(window, inverse mel basis, mel basis) on the device: the tuple earlier callers indexed, kept readable for them."""
+        return self._window_dev, self._inv_basis_dev, self._mel_basis_dev
+
+    @property
+    def _log_kind(self) -> int:
+        """log10_kind of the C ABI: 0 natural logarithm, 1 base 10."""
+        return 0 if self.config.log_func == "np.log" else 1
 
     def _stream(self) -> int:
         return torch.cuda.current_stream(self.device).cuda_stream
@@ -128,7 +149,7 @@ class AudioProcessor:
         """Validate per-row frame counts on the host (nothing is launched for a bad batch): (host list, device int32 [B])."""
         if isinstance(frame_lengths, _RowLengths):   # checked by the caller (convert_mel2wav_batch), with trimmed=True
             return frame_lengths
-        host = [int(v) for v in (frame_lengths.tolist() if isinstance(frame_lengths, (torch.Tensor, np.ndarray)) else frame_lengths)]
+        host = _int_list(frame_lengths)
         if len(host) != B:
             raise ValueError(f"{len(host)} frame lengths for a batch of {B} rows")
         for b, t in enumerate(host):
@@ -152,7 +173,7 @@ class AudioProcessor:
         T = (n - c.filter_length) // c.hop_length + 1
         out = torch.empty(B, c.filter_length // 2 + 1, T, 2, device=self.device)
         ws = self._workspace(B, T)
-        _lib.check(lib.gvx_stft(self._plan, x.data_ptr(), self._dev_consts[0].data_ptr(), B, n, out.data_ptr(), ws.data_ptr(),
+        _lib.check(lib.gvx_stft(self._plan, x.data_ptr(), self._window_dev.data_ptr(), B, n, out.data_ptr(), ws.data_ptr(),
                                 ws.numel(), self._stream()))
         return torch.view_as_complex(out)
 
@@ -164,7 +185,7 @@ class AudioProcessor:
         c = self.config
         out = torch.empty(B, c.filter_length + (T - 1) * c.hop_length, device=self.device)
         ws = self._workspace(B, T)
-        _lib.check(lib.gvx_istft(self._plan, z.data_ptr(), self._dev_consts[0].data_ptr(), B, T, out.data_ptr(), ws.data_ptr(),
+        _lib.check(lib.gvx_istft(self._plan, z.data_ptr(), self._window_dev.data_ptr(), B, T, out.data_ptr(), ws.data_ptr(),
                                  ws.numel(), self._stream()))
         return out
 
@@ -176,9 +197,8 @@ class AudioProcessor:
         c = self.config
         out = torch.empty(B, c.filter_length // 2 + 1, T, device=self.device)
         ws = self._workspace(B, T)
-        _lib.check(lib.gvx_mel_to_magnitude(self._plan, x.data_ptr(), self._dev_consts[1].data_ptr(), B, M, T,
-                                            0 if c.log_func == "np.log" else 1, float(c.ref_level_db), out.data_ptr(),
-                                            ws.data_ptr(), ws.numel(), self._stream()))
+        _lib.check(lib.gvx_mel_to_magnitude(self._plan, x.data_ptr(), self._inv_basis_dev.data_ptr(), B, M, T, self._log_kind,
+                                            float(c.ref_level_db), out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
         return out
 
     def griffin_lim(self, mag: torch.Tensor, n_iter: int = 32, momentum: float = 0.99, want_phase: bool = True,
@@ -195,16 +215,11 @@ class AudioProcessor:
         lens = self._check_lengths(frame_lengths, B, T, trimmed=False).dev if frame_lengths is not None else None
         phase = torch.empty_like(m) if want_phase else None
         wav = torch.empty(B, c.filter_length + (T - 1) * c.hop_length, device=self.device) if want_wav else None
-        if lens is not None:
-            ws = self._workspace(B, T, ragged=True)
-            _lib.check(lib.gvx_griffin_lim_ragged(self._plan, m.data_ptr(), self._dev_consts[0].data_ptr(), B, T, lens.data_ptr(), n_iter,
-                                                  float(momentum), phase.data_ptr() if want_phase else None,
-                                                  wav.data_ptr() if want_wav else None, ws.data_ptr(), ws.numel(), self._stream()))
-            return phase, wav
-        ws = self._workspace(B, T)
-        _lib.check(lib.gvx_griffin_lim(self._plan, m.data_ptr(), self._dev_consts[0].data_ptr(), B, T, n_iter, float(momentum),
-                                       phase.data_ptr() if want_phase else None, wav.data_ptr() if want_wav else None,
-                                       ws.data_ptr(), ws.numel(), self._stream()))
+        ws = self._workspace(B, T, ragged=lens is not None)
+        call, rows = (lib.gvx_griffin_lim, ()) if lens is None else (lib.gvx_griffin_lim_ragged, (lens.data_ptr(),))
+        _lib.check(call(self._plan, m.data_ptr(), self._window_dev.data_ptr(), B, T, *rows, n_iter, float(momentum),
+                        phase.data_ptr() if want_phase else None, wav.data_ptr() if want_wav else None, ws.data_ptr(), ws.numel(),
+                        self._stream()))
         return phase, wav
 
     def finalize(self, wav: torch.Tensor, frame_lengths=None) -> torch.Tensor:
@@ -226,11 +241,8 @@ class AudioProcessor:
         nb = len(self._b)
         b = (C.c_double * nb)(*[float(v) for v in self._b])
         a = (C.c_double * nb)(*[float(v) for v in self._a])
-        if lens is not None:
-            _lib.check(lib.gvx_wav_finalize_ragged(y.data_ptr(), B, n, lens.data_ptr(), c.filter_length, c.hop_length, self.TRIM, b, a,
-                                                   nb - 1, out.data_ptr(), scratch.data_ptr(), self._stream()))
-            return out
-        _lib.check(lib.gvx_wav_finalize(y.data_ptr(), B, n, self.TRIM, b, a, nb - 1, out.data_ptr(), scratch.data_ptr(), self._stream()))
+        call, rows = (lib.gvx_wav_finalize, ()) if lens is None else (lib.gvx_wav_finalize_ragged, (lens.data_ptr(), c.filter_length, c.hop_length))
+        _lib.check(call(y.data_ptr(), B, n, *rows, self.TRIM, b, a, nb - 1, out.data_ptr(), scratch.data_ptr(), self._stream()))
         return out
 
     def wav_to_mel(self, signal: torch.Tensor) -> torch.Tensor:
@@ -240,13 +252,10 @@ class AudioProcessor:
         B, n = x.shape
         c = self.config
         T = (n - c.filter_length) // c.hop_length + 1
-        if len(self._dev_consts) < 3:
-            self._dev_consts = self._dev_consts + (torch.from_numpy(np.ascontiguousarray(self.mel_basis)).to(self.device),)
         out = torch.empty(B, c.n_mels, T, device=self.device)
         ws = self._workspace(B, T)
-        _lib.check(lib.gvx_wav_to_mel(self._plan, x.data_ptr(), self._dev_consts[0].data_ptr(), self._dev_consts[2].data_ptr(), B, n,
-                                      c.n_mels, 0 if c.log_func == "np.log" else 1, float(c.ref_level_db), out.data_ptr(),
-                                      ws.data_ptr(), ws.numel(), self._stream()))
+        _lib.check(lib.gvx_wav_to_mel(self._plan, x.data_ptr(), self._window_dev.data_ptr(), self._mel_basis_dev.data_ptr(), B, n, c.n_mels,
+                                      self._log_kind, float(c.ref_level_db), out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
         return out
 
     def convert_wav2mel(self, input_path: str, output_path: str) -> None:
@@ -294,7 +303,7 @@ class AudioProcessor:
             x = x.to(torch.float32)
         if sample_lengths is None:
             raise ValueError("a padded PCM batch needs sample_lengths")
-        lengths = [int(v) for v in (sample_lengths.tolist() if isinstance(sample_lengths, (torch.Tensor, np.ndarray)) else sample_lengths)]
+        lengths = _int_list(sample_lengths)
         if len(lengths) != x.shape[0]:
             raise ValueError(f"{len(lengths)} sample lengths for a batch of {x.shape[0]} rows")
         for b, n in enumerate(lengths):
@@ -349,21 +358,15 @@ class AudioProcessor:
         normalize = c.normalize if normalize is None else normalize
         B, n_max = x.shape
         T = max(1, (max(lengths) - c.filter_length) // c.hop_length + 1)
-        if len(self._dev_consts) < 3:
-            self._dev_consts = self._dev_consts + (torch.from_numpy(np.ascontiguousarray(self.mel_basis)).to(self.device),)
         bounds = self._trim_bounds(x, lengths, bool(trim))
-        need = lib.gvx_wav_to_mel_ragged_workspace_bytes(self._plan, B, n_max, c.n_mels)
-        if need == 0:
-            raise _lib.GvxError("could not plan the wav -> mel workspace: " + lib.gvx_last_error().decode())
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = self._workspace_for("wav -> mel", lib.gvx_wav_to_mel_ragged_workspace_bytes, B, n_max, c.n_mels)
         mel = torch.empty(B, c.n_mels, T, device=self.device)
         gate = torch.empty(B, T, device=self.device)
         words = torch.empty(2, B, dtype=torch.int32, device=self.device)   # frame counts, status words
-        _lib.check(lib.gvx_wav_to_mel_ragged(self._plan, x.data_ptr(), 0 if x.dtype == torch.int16 else 1, self._dev_consts[0].data_ptr(),
-                                             self._dev_consts[2].data_ptr(), B, n_max, bounds.data_ptr(), int(bool(normalize)), c.n_mels,
-                                             0 if c.log_func == "np.log" else 1, float(c.ref_level_db), T, mel.data_ptr(), gate.data_ptr(),
-                                             words[0].data_ptr(), words[1].data_ptr(), self._ws.data_ptr(), self._ws.numel(), self._stream()))
+        _lib.check(lib.gvx_wav_to_mel_ragged(self._plan, x.data_ptr(), 0 if x.dtype == torch.int16 else 1, self._window_dev.data_ptr(),
+                                             self._mel_basis_dev.data_ptr(), B, n_max, bounds.data_ptr(), int(bool(normalize)), c.n_mels,
+                                             self._log_kind, float(c.ref_level_db), T, mel.data_ptr(), gate.data_ptr(),
+                                             words[0].data_ptr(), words[1].data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
         host = torch.cat([words, bounds.t()]).cpu() if _durations else words.cpu()   # the call's one synchronisation
         frames, status = host[0].tolist(), host[1].tolist()
         bad = [b for b in range(B) if status[b] != 0]
@@ -424,15 +427,14 @@ class AudioProcessor:
         return value is ``(waveforms, sample_counts)``: row b is valid up to ``sample_counts[b] = n_fft + (T_b-1)*hop - 1000``
         samples - bit for bit the result of a call on ``mels[b:b+1, :, :T_b]`` - and 0 behind.  The padded frames of ``mels`` may
         hold anything.  Bad lengths raise ValueError before anything is launched."""
+        lens = None
         if mel_lengths is not None:
             B, _, T = mels.shape
             lens = self._check_lengths(mel_lengths, B, T, trimmed=True)
-            mag = self.mel_to_magnitude(mels)   # frame-wise: the padded frames' magnitudes are simply never used
-            _, wav = self.griffin_lim(mag, n_iter=n_iter, want_phase=False, frame_lengths=lens)
-            return self.finalize(wav, frame_lengths=lens), self.row_samples(lens.host)
-        mag = self.mel_to_magnitude(mels)
-        _, wav = self.griffin_lim(mag, n_iter=n_iter, want_phase=False)
-        return self.finalize(wav)
+        mag = self.mel_to_magnitude(mels)   # frame-wise: the padded frames' magnitudes of a ragged batch are simply never used
+        _, wav = self.griffin_lim(mag, n_iter=n_iter, want_phase=False, frame_lengths=lens)
+        out = self.finalize(wav, frame_lengths=lens)
+        return out if lens is None else (out, self.row_samples(lens.host))
 
     def convert_mel2wav(self, mel: Union[np.ndarray, str, torch.Tensor], n_iter: int = 32) -> Tuple[int, np.ndarray]:
         """Reference signature (core/processors.py:81-96): one mel [n_mels, T] (array or .npy path) -> (fs, float64 signal)."""

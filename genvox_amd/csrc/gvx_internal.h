@@ -27,8 +27,6 @@ int fail(int code, const char* fmt, ...);   // sets gvx_last_error() of this thr
 constexpr int MAX_CONV = 8;
 constexpr double BN_EPS = 1e-5;
 
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 struct Blob {  // offsets in floats into the packed weight blob
     size_t emb;
     size_t enc_w[MAX_CONV], enc_b[MAX_CONV];

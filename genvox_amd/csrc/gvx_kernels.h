@@ -2,6 +2,7 @@
 // gfx950 only. All device data is fp32 unless noted.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 // Diagnostic build only (-DGVX_STAMPS, python -m genvox_amd.build --stamps): workgroup (0,0), thread 0 records the
@@ -22,6 +23,8 @@ namespace gvx {
 
 // error reporting shared by every translation unit of the C ABI (thread-local message, returns `code`)
 int set_error(int code, const char* msg);
+
+inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2 };
 

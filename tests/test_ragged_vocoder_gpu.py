@@ -247,7 +247,7 @@ def test_bad_arguments_are_refused_and_launch_nothing(ap):
     s = torch.cuda.current_stream().cuda_stream
     small = lib.gvx_gl_workspace_bytes(ap._plan, B, T, 0)       # what the uniform Griffin-Lim call needs: no room for the divisors
     assert 0 < small < lib.gvx_gl_workspace_bytes_ragged(ap._plan, B, T, 0) <= ws.numel()
-    win = ap._dev_consts[0].data_ptr()
+    win = ap._window_dev.data_ptr()
     assert lib.gvx_griffin_lim_ragged(ap._plan, mag.data_ptr(), win, B, T, None, 1, 0.99, None, wav.data_ptr(), ws.data_ptr(),
                                       ws.numel(), s) == -1
     assert b"frame_lengths" in lib.gvx_last_error()

@@ -1,5 +1,5 @@
-"""The vocoder's HIP kernels (genvox_amd/csrc/griffinlim.hip) against the float64 restatement tests/audio_ref64.py, element by
-element, at the edges of their workgroups.
+"""The vocoder's HIP kernels (genvox_amd/csrc/griffinlim.hip, wav_to_mel.hip) against the float64 restatement
+tests/audio_ref64.py, element by element, at the edges of their workgroups.
 
 tests/test_audio_gpu.py holds the same calls to the reference's fixture with aggregates (one number per call); here every bin,
 sample and mel element is checked on its own with the metrics of tests/audio_ref64.py, and the assertion message names the worst
@@ -77,7 +77,7 @@ class Call:
         self.ap, self.lib = ap, ap._ensure()
         self.c = ap.config
         self.bins = self.c.filter_length // 2 + 1
-        self.window = ap._dev_consts[0]
+        self.window = ap._window_dev
         self.stream = torch.cuda.current_stream().cuda_stream
 
     def samples(self, T):
@@ -147,7 +147,7 @@ class Call:
         x = torch.from_numpy(np.ascontiguousarray(mel_db, np.float32)).cuda()
         out = _Out((B, self.bins, T))
         ws = self.ap._workspace(B, T)
-        rc = self.lib.gvx_mel_to_magnitude(self.ap._plan, x.data_ptr(), self.ap._dev_consts[1].data_ptr(), B, n_mels or M, T,
+        rc = self.lib.gvx_mel_to_magnitude(self.ap._plan, x.data_ptr(), self.ap._inv_basis_dev.data_ptr(), B, n_mels or M, T,
                                            0 if self.c.log_func == "np.log" else 1, float(self.c.ref_level_db), out.t.data_ptr(),
                                            ws.data_ptr(), ws.numel(), self.stream)
         if check:

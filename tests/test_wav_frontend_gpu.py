@@ -276,14 +276,12 @@ def test_status_words_and_clamped_bounds_of_the_c_call(ap):
     n_max, T_out, c = 1024 + 9 * 256, 6, ap.config
     pcm = torch.from_numpy(rng.integers(-9000, 9001, size=(3, n_max)).astype(np.int16)).cuda()
     bounds = torch.tensor([[-50, 10 ** 6], [100, 100 + 1024 + 3 * 256 + 5], [700, 300]], dtype=torch.int32).cuda()
-    if len(ap._dev_consts) < 3:
-        ap.wav_to_mel_ragged([pcm[0].cpu().numpy()])
     need = lib.gvx_wav_to_mel_ragged_workspace_bytes(ap._plan, 3, 1024 + (T_out - 1) * 256, c.n_mels)   # what T_out frames per row take
     assert 0 < need <= lib.gvx_wav_to_mel_ragged_workspace_bytes(ap._plan, 3, n_max, c.n_mels)
     ws = torch.empty(need, dtype=torch.uint8, device="cuda")
     mel = torch.full((3, c.n_mels, T_out), float("nan"), device="cuda")
     frames, status = torch.zeros(3, dtype=torch.int32).cuda(), torch.zeros(3, dtype=torch.int32).cuda()
-    args = [ap._plan, pcm.data_ptr(), 0, ap._dev_consts[0].data_ptr(), ap._dev_consts[2].data_ptr(), 3, n_max, bounds.data_ptr(), 1, c.n_mels,
+    args = [ap._plan, pcm.data_ptr(), 0, ap._window_dev.data_ptr(), ap._mel_basis_dev.data_ptr(), 3, n_max, bounds.data_ptr(), 1, c.n_mels,
             0, 1.0, T_out, mel.data_ptr(), None, frames.data_ptr(), status.data_ptr(), ws.data_ptr()]
     assert lib.gvx_wav_to_mel_ragged(*args, need - 256, ap._stream()) == -5          # GVX_ERR_WORKSPACE, nothing launched
     assert torch.isnan(mel).all()
