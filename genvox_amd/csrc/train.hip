@@ -279,6 +279,51 @@ T* at(void* base, size_t off) { return reinterpret_cast<T*>(reinterpret_cast<cha
 template <typename T>
 const T* at(const void* base, size_t off) { return reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + off); }
 
+// The three products of one layer as launch_gemm / launch_gemm_splitk get them, buffers left open: the two entry points fill in the
+// pointers and launch exactly these, and gvx_debug_conv_train_plan reports what plan_gemm / choose_splitk / set_splitk make of them
+// (tests/test_host_cpu.py pins which layer shape takes which tile and how its weight gradient is cut).
+// forward: z[(b, t)][co] = sum_{j, ci} xcl[b][t + j][ci] * wk[co][j][ci] + bias - implicit GEMM on the halo-padded input
+GemmParams conv_forward_gemm(int B, int Cin, int Cout, int T, int k) {
+    const int pad = (k - 1) / 2;
+    const long rows = (long)B * T;
+    GemmParams g{};
+    g.amap = RowMap{T, (long)(T + 2 * pad) * Cin, (long)Cin};
+    g.ldw = (long)k * Cin;
+    g.cmap = RowMap{(int)rows, 0, (long)Cout};
+    g.M = (int)rows; g.N = Cout; g.K = k * Cin; g.act = ACT_NONE;
+    return g;
+}
+// weight gradient: dwk[co][(j, ci)] = sum over the rows r = (b, t) of dz[r][co] * xcl[b][t + j][ci]: both operands K-major as they
+// lie in memory (the im2col row of r is the k * Cin contiguous floats at padded row t) - no transposed copies
+GemmParams conv_wgrad_gemm(int B, int Cin, int Cout, int T, int k) {
+    const int pad = (k - 1) / 2;
+    const long rows = (long)B * T;
+    GemmParams g{};
+    g.kmajor = true;
+    g.amap = RowMap{(int)rows, 0, (long)Cout};
+    g.wmap = RowMap{T, (long)(T + 2 * pad) * Cin, (long)Cin};
+    g.cmap = RowMap{Cout, 0, (long)k * Cin};
+    g.M = Cout; g.N = k * Cin; g.K = (int)rows; g.act = ACT_NONE;
+    return g;
+}
+// few output tiles, thousands of rows to sum over: K split over enough workgroups to fill the chip (the Postnet's 512 x 2560
+// gradients are 160 tiles, its first layer's 32: 290 / 330 us each as one round)
+int conv_wgrad_splitk(int B, int Cin, int Cout, int T, int k) {
+    const long tiles = (long)((Cout + 63) / 64) * ((k * Cin + 127) / 128);
+    return choose_splitk(tiles, (int)((long)B * T));
+}
+// data gradient: flipped-tap implicit GEMM on the halo-padded dz
+GemmParams conv_dgrad_gemm(int B, int Cin, int Cout, int T, int k) {
+    const int pad = (k - 1) / 2;
+    const long rows = (long)B * T;
+    GemmParams g{};
+    g.amap = RowMap{T, (long)(T + 2 * pad) * Cout, (long)Cout};
+    g.ldw = (long)k * Cout;
+    g.cmap = RowMap{(int)rows, 0, (long)Cin};
+    g.M = (int)rows; g.N = Cin; g.K = k * Cout; g.act = ACT_NONE;
+    return g;
+}
+
 int check_conv_args(int B, int Cin, int Cout, int T, int k) {
     if (B < 1 || T < 1 || Cin < 8 || Cout < 8 || (Cin % 8) || (Cout % 8) || k < 1 || !(k & 1))
         return tfail(GVX_ERR_UNSUPPORTED, "conv training op: channels must be positive multiples of 8, kernel size odd");
@@ -322,11 +367,8 @@ int gvx_conv_bn_act_train_forward(const float* x, const float* w, const float* b
     float* wk = at<float>(workspace, pl.wk);
     hipLaunchKernelGGL(repack_conv_kernel, dim3(blocks_for((long)Cout * Cin * k)), dim3(256), 0, s, w, wk, (float*)nullptr, Cout, Cin, k);
     float* z = at<float>(workspace, pl.z);
-    GemmParams g{};
-    g.A = xcl; g.amap = RowMap{T, (long)(T + 2 * pad) * Cin, (long)Cin};
-    g.W = wk; g.ldw = (long)k * Cin;
-    g.C = z; g.cmap = RowMap{(int)rows, 0, (long)Cout};
-    g.bias = bias; g.M = (int)rows; g.N = Cout; g.K = k * Cin; g.act = ACT_NONE;
+    GemmParams g = conv_forward_gemm(B, Cin, Cout, T, k);
+    g.A = xcl; g.W = wk; g.C = z; g.bias = bias;
     TR_TRY(launch_gemm(g, s));
     float* mean = at<float>(saved, pl.mean);
     float* invstd = at<float>(saved, pl.invstd);
@@ -344,8 +386,11 @@ int gvx_conv_bn_act_train_backward(const float* dy, const void* saved, size_t sa
     int rc = check_conv_args(B, Cin, Cout, T, k);
     if (rc != GVX_OK) return rc;
     if (!dy || !saved || !w || !gamma || !dw || !dbias || !dgamma || !dbeta || !workspace) return tfail(GVX_ERR_INVALID_ARG, "null argument");
+    if (act != ACT_NONE && act != ACT_RELU && act != ACT_TANH) return tfail(GVX_ERR_INVALID_ARG, "activation must be 0 (none), 1 (relu) or 2 (tanh)");
+    if (keep && !(p_drop >= 0.f && p_drop < 1.f)) return tfail(GVX_ERR_INVALID_ARG, "dropout probability must be in [0, 1)");
     const ConvTrainPlan pl = conv_train_plan(B, Cin, Cout, T, k);
     if (saved_bytes < pl.saved_total || workspace_bytes < pl.ws_total) return tfail(GVX_ERR_WORKSPACE, "saved / workspace buffer too small");
+    if ((reinterpret_cast<uintptr_t>(saved) | reinterpret_cast<uintptr_t>(workspace)) & 255) return tfail(GVX_ERR_WORKSPACE, "buffers must be 256-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     const int pad = (k - 1) / 2;
     const long rows = (long)B * T;
@@ -371,29 +416,18 @@ int gvx_conv_bn_act_train_backward(const float* dy, const void* saved, size_t sa
         xcl_w = x2;
     }
     float* dwk = at<float>(workspace, pl.dwk);
-    {   // dwk[co][(j, ci)] = sum over the rows r = (b, t) of dz[r][co] * xcl[b][t + j][ci]: both operands K-major as they lie in
-        // memory (the im2col row of r is the k * Cin contiguous floats at padded row t) - no transposed copies
-        GemmParams g{};
-        g.kmajor = true;
-        g.A = dz; g.amap = RowMap{(int)rows, 0, (long)Cout};
-        g.W = xcl_w; g.wmap = RowMap{T, (long)(T + 2 * pad) * Cin, (long)Cin};
-        g.C = dwk; g.cmap = RowMap{Cout, 0, (long)k * Cin};
-        g.M = Cout; g.N = k * Cin; g.K = (int)rows; g.act = ACT_NONE;
-        // few output tiles, thousands of rows to sum over: K split over enough workgroups to fill the chip (the Postnet's 512 x 2560
-        // gradients are 160 tiles, its first layer's 32: 290 / 330 us each as one round)
-        const long tiles = (long)((Cout + 63) / 64) * ((k * Cin + 127) / 128);
-        TR_TRY(launch_gemm_splitk(g, choose_splitk(tiles, (int)rows), at<float>(workspace, pl.dwk_part), s));
+    {
+        GemmParams g = conv_wgrad_gemm(B, Cin, Cout, T, k);
+        g.A = dz; g.W = xcl_w; g.C = dwk;
+        TR_TRY(launch_gemm_splitk(g, conv_wgrad_splitk(B, Cin, Cout, T, k), at<float>(workspace, pl.dwk_part), s));
     }
     hipLaunchKernelGGL(unpack_dw_kernel, dim3(blocks_for((long)Cout * Cin * k)), dim3(256), 0, s, dwk, dw, Cout, Cin, k);
     if (dx) {   // data gradient: flipped-tap implicit GEMM on the halo-padded dz
         float* w2 = at<float>(workspace, pl.w2);
         hipLaunchKernelGGL(repack_conv_kernel, dim3(blocks_for((long)Cout * Cin * k)), dim3(256), 0, s, w, (float*)nullptr, w2, Cout, Cin, k);
         float* dxcl = at<float>(workspace, pl.dxcl);
-        GemmParams g{};
-        g.A = dzh; g.amap = RowMap{T, (long)(T + 2 * pad) * Cout, (long)Cout};
-        g.W = w2; g.ldw = (long)k * Cout;
-        g.C = dxcl; g.cmap = RowMap{(int)rows, 0, (long)Cin};
-        g.M = (int)rows; g.N = Cin; g.K = k * Cout; g.act = ACT_NONE;
+        GemmParams g = conv_dgrad_gemm(B, Cin, Cout, T, k);
+        g.A = dzh; g.W = w2; g.C = dxcl;
         TR_TRY(launch_gemm(g, s));
         hipLaunchKernelGGL(to_channels_first_kernel, dim3(blocks_for(rows * Cin)), dim3(256), 0, s, dxcl, dx, B, Cin, T);
     }
@@ -566,6 +600,24 @@ int gvx_debug_gemm_plan(int M, int N, int K, int kmajor, int have_scratch, size_
     const GemmPlan pl = plan_gemm(g);
     *tile_out = pl.tile; *rows_big_out = pl.rows_big; *k_pieces_out = g.splitk;
     return pl.err == hipSuccess ? GVX_OK : GVX_ERR_INVALID_ARG;
+}
+
+// Host-only query for the tests (not part of the public header; touches no device): how one gvx_conv_bn_act_train_forward /
+// _backward pair runs its three products, from the functions the two entry points launch through.  out[0 .. 7] = forward tile,
+// forward rows_big, data-gradient tile, data-gradient rows_big, weight-gradient tile (K-major), weight-gradient rows_big, the K
+// pieces of the weight gradient (1 = no split-K) and the length of a piece (0 without a split).  Tiles and rows_big as GemmPlan.
+int gvx_debug_conv_train_plan(int B, int Cin, int Cout, int T, int k, int* out) {
+    if (!out) return GVX_ERR_INVALID_ARG;
+    const int rc = check_conv_args(B, Cin, Cout, T, k);
+    if (rc != GVX_OK) return rc;
+    GemmParams w = conv_wgrad_gemm(B, Cin, Cout, T, k);
+    const int splitk = conv_wgrad_splitk(B, Cin, Cout, T, k);
+    if (splitk > 1) set_splitk(w, splitk);   // (what launch_gemm_splitk does before it plans)
+    const GemmPlan pf = plan_gemm(conv_forward_gemm(B, Cin, Cout, T, k)), pd = plan_gemm(conv_dgrad_gemm(B, Cin, Cout, T, k)), pw = plan_gemm(w);
+    if (pf.err != hipSuccess || pd.err != hipSuccess || pw.err != hipSuccess) return GVX_ERR_INVALID_ARG;
+    out[0] = pf.tile; out[1] = pf.rows_big; out[2] = pd.tile; out[3] = pd.rows_big;
+    out[4] = pw.tile; out[5] = pw.rows_big; out[6] = w.splitk; out[7] = w.splitk > 1 ? w.kchunk : 0;
+    return GVX_OK;
 }
 
 // C[m][n] = sum_k A[m*lda + k] * W[n*ldw + k] (+ bias[n]);  K % 4 == 0

@@ -266,7 +266,15 @@ int gvx_train_export(const gvx_model* model, const void* workspace, size_t works
 size_t gvx_conv_train_saved_bytes(int B, int Cin, int Cout, int T, int k);
 size_t gvx_conv_train_workspace_bytes(int B, int Cin, int Cout, int T, int k);
 /* y = dropout(act(BatchNorm_train(conv1d(x, w, bias, padding (k-1)/2)))).  running_mean / running_var (may be NULL) get the
- * momentum-0.1 update of torch.nn.BatchNorm1d (unbiased variance), in place. */
+ * momentum-0.1 update of torch.nn.BatchNorm1d (unbiased variance), in place.
+ * One value per channel (B * T == 1), where torch.nn.BatchNorm1d raises: the batch variance is 0 and the normalised value 0,
+ * so y = dropout(act(beta)), running_mean moves towards the one value and running_var is multiplied by 0.9 (the unbiased
+ * variance of one value is taken as 0); the backward then gives dbeta = d loss / d (BatchNorm output) and exact zeros for dx,
+ * dw, dbias and dgamma.
+ * Both calls and both size queries refuse the same shapes (the queries return 0): GVX_ERR_UNSUPPORTED for B or T < 1, channels
+ * that are no positive multiple of 8, an even or non-positive k, B * T above 2^30; GVX_ERR_INVALID_ARG for a NULL argument that
+ * may not be NULL, an unknown act, p_drop outside [0, 1) with a mask; GVX_ERR_WORKSPACE for a buffer that is too small or not
+ * 256-byte aligned.  Nothing is launched then. */
 int gvx_conv_bn_act_train_forward(const float* x, const float* w, const float* bias, const float* gamma, const float* beta,
                                   float* running_mean, float* running_var, int B, int Cin, int Cout, int T, int k, int act,
                                   const uint8_t* keep, float p_drop, float* y, void* saved, size_t saved_bytes, void* workspace,

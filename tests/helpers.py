@@ -269,6 +269,141 @@ def enc_bptt_plan(lib, B, H, resident):
     return rc, list(out)
 
 
+# ---- the training-mode convolution layer (gvx_conv_bn_act_train_forward / _backward, genvox_amd/csrc/train.hip): the shapes
+# tests/test_conv_train_gpu.py runs, each group with the branch it is there for.  tests/test_host_cpu.py pins every line against
+# gvx_debug_conv_train_plan on the CPU, so a retuned threshold fails there and the cases get re-aimed. ---------------------------------
+# act: none / relu / tanh.  p: None (keep = NULL), else the dropout probability handed over with a keep mask (0.0: a mask, scale 1).
+# running: running_mean / running_var given.  offset: size of the channel means of the pre-BatchNorm values (through the bias).
+# plan = (forward tile, forward rows_big, data-gradient tile, data-gradient rows_big, weight-gradient tile, K pieces of the weight
+# gradient, length of a piece or 0) as gvx_debug_conv_train_plan reports it; tiles as the four digits of <WR,WC,TM,TN>.
+ConvTrainCase = collections.namedtuple("ConvTrainCase", "name B Cin Cout T k act p plan running offset")
+
+
+def _cv(name, B, Cin, Cout, T, k, act, p, plan, running=True, offset=0.0):
+    return ConvTrainCase(name, B, Cin, Cout, T, k, act, p, plan, running, offset)
+
+
+CONV_TRAIN_CASES = [
+    # T against the halo (pad = 0 .. 3 rows: T = 1, 2 are shorter than it) and against the K-major loader's (group, index) increments
+    # under wmap = {R = T, ...}: every k a new group (T = 1), a quad of k across groups (T = 2, 3), several groups per k-tile of 32
+    # (T < 32), T around 32 and 64; B = 1 is one group.  Fewer than 512 rows: the weight gradient in one piece
+    _cv("t_37x1_8to24_k5", 37, 8, 24, 1, 5, "none", None, (4111, 0, 4111, 0, 2212, 1, 0)),
+    _cv("t_1x1_24to40_k7", 1, 24, 40, 1, 7, "relu", 0.5, (2311, 0, 4111, 0, 2212, 1, 0)),
+    _cv("t_50x2_40to8_k5", 50, 40, 8, 2, 5, "tanh", 0.0, (4111, 0, 2311, 0, 2212, 1, 0)),
+    _cv("t_1x2_24to24_k5", 1, 24, 24, 2, 5, "none", 0.9, (4111, 0, 4111, 0, 2212, 1, 0)),
+    _cv("t_33x3_8to40_k7", 33, 8, 40, 3, 7, "relu", None, (2311, 0, 4111, 0, 2212, 1, 0)),
+    _cv("t_1x3_40to24_k3", 1, 40, 24, 3, 3, "tanh", 0.5, (4111, 0, 2311, 0, 2212, 1, 0)),
+    _cv("t_19x4_8to24_k3", 19, 8, 24, 4, 3, "none", 0.0, (4111, 0, 4111, 0, 2212, 1, 0)),
+    _cv("t_13x5_24to40_k5", 13, 24, 40, 5, 5, "relu", 0.9, (2311, 0, 4111, 0, 2212, 1, 0)),
+    _cv("t_1x5_40to8_k7", 1, 40, 8, 5, 7, "tanh", None, (4111, 0, 2311, 0, 2212, 1, 0)),
+    _cv("t_11x7_24to24_k7", 11, 24, 24, 7, 7, "none", 0.5, (4111, 0, 4111, 0, 2212, 1, 0)),
+    _cv("t_9x7_8to40_k1", 9, 8, 40, 7, 1, "relu", 0.0, (2311, 0, 4111, 0, 2212, 1, 0)),
+    _cv("t_5x31_40to24_k5", 5, 40, 24, 31, 5, "tanh", 0.9, (4111, 0, 2311, 0, 2212, 1, 0)),
+    _cv("t_5x32_8to24_k3", 5, 8, 24, 32, 3, "none", None, (4111, 0, 4111, 0, 2212, 1, 0)),
+    _cv("t_1x32_24to40_k5", 1, 24, 40, 32, 5, "relu", 0.5, (2311, 0, 4111, 0, 2212, 1, 0)),
+    _cv("t_5x33_40to8_k7", 5, 40, 8, 33, 7, "tanh", 0.0, (4111, 0, 2311, 0, 2212, 1, 0)),
+    _cv("t_3x63_24to24_k5", 3, 24, 24, 63, 5, "none", 0.9, (4111, 0, 4111, 0, 2212, 1, 0)),
+    _cv("t_3x64_8to40_k1", 3, 8, 40, 64, 1, "relu", None, (2311, 0, 4111, 0, 2212, 1, 0)),
+    _cv("t_1x64_40to24_k5", 1, 40, 24, 64, 5, "tanh", 0.5, (4111, 0, 2311, 0, 2212, 1, 0)),
+    _cv("t_3x65_8to24_k5", 3, 8, 24, 65, 5, "none", 0.0, (4111, 0, 4111, 0, 2212, 1, 0)),
+    _cv("t_1x65_24to40_k7", 1, 24, 40, 65, 7, "relu", 0.9, (2311, 0, 4111, 0, 2212, 1, 0)),
+    # split-K weight gradient, few tiles: from 512 rows on, one more piece per 256 rows up to 8.  T = 1 (600 groups); T = 3, 5, 37, 50,
+    # 27, 59, 89: every piece begins inside a sequence (kchunk % T != 0); T = 64, 128, 96, 512, 2048: at a sequence's first frame or in
+    # the only sequence.  rows = 511 | 512, 513 (320 + 193) | 767 (2 pieces of 384, the last 383) | 768 | 2047 (7 pieces of 320, the
+    # last 127) | 2048 (8 of 256)
+    _cv("sk_600x1_40to8_k5", 600, 40, 8, 1, 5, "tanh", None, (4111, 0, 2311, 0, 2212, 2, 320)),
+    _cv("sk_171x3_24to24_k3", 171, 24, 24, 3, 3, "none", 0.5, (4111, 0, 4111, 0, 2212, 2, 320)),
+    _cv("sk_103x5_8to40_k5", 103, 8, 40, 5, 5, "relu", 0.0, (2311, 0, 4111, 0, 2212, 2, 320)),
+    _cv("sk_14x37_40to24_k5", 14, 40, 24, 37, 5, "tanh", 0.9, (4111, 0, 2311, 0, 2212, 2, 320)),
+    _cv("sk_11x50_8to24_k7", 11, 8, 24, 50, 7, "none", None, (4111, 0, 4111, 0, 2212, 2, 320)),
+    _cv("sk_8x64_24to40_k5", 8, 24, 40, 64, 5, "relu", 0.5, (2311, 0, 4111, 0, 2212, 2, 256)),
+    _cv("sk_4x128_40to8_k3", 4, 40, 8, 128, 3, "tanh", 0.0, (4111, 0, 2311, 0, 2212, 2, 256)),
+    _cv("sk_7x73_24to24_k5", 7, 24, 24, 73, 5, "none", 0.9, (4111, 0, 4111, 0, 2212, 1, 0)),
+    _cv("sk_1x512_8to40_k5", 1, 8, 40, 512, 5, "relu", None, (2311, 0, 4111, 0, 2212, 2, 256)),
+    _cv("sk_19x27_40to24_k5", 19, 40, 24, 27, 5, "tanh", 0.5, (4111, 0, 2311, 0, 2212, 2, 320)),
+    _cv("sk_13x59_8to24_k3", 13, 8, 24, 59, 3, "none", 0.0, (4111, 0, 4111, 0, 2212, 2, 384)),
+    _cv("sk_12x64_24to40_k5", 12, 24, 40, 64, 5, "relu", 0.9, (2311, 0, 4111, 0, 2212, 3, 256)),
+    _cv("sk_8x96_40to8_k1", 8, 40, 8, 96, 1, "tanh", None, (4111, 0, 2311, 0, 2212, 3, 256)),
+    _cv("sk_23x89_24to24_k5", 23, 24, 24, 89, 5, "none", 0.5, (4111, 0, 4111, 0, 2212, 7, 320)),
+    _cv("sk_16x128_8to40_k5", 16, 8, 40, 128, 5, "relu", 0.0, (2311, 0, 4111, 0, 2212, 8, 256)),
+    _cv("sk_1x2048_40to24_k3", 1, 40, 24, 2048, 3, "tanh", 0.9, (4111, 0, 2311, 0, 2212, 8, 256)),
+    # the 160-tile shape 512 x 2560: whole up to 767 rows, 3 pieces from 768 (2047: 704 + 704 + 639), 8 from 2048
+    _cv("sk_13x59_512to512_k5", 13, 512, 512, 59, 5, "none", None, (2211, 0, 2211, 0, 2212, 1, 0)),
+    _cv("sk_12x64_512to512_k5", 12, 512, 512, 64, 5, "relu", 0.5, (2211, 0, 2211, 0, 2212, 3, 256)),
+    _cv("sk_23x89_512to512_k5", 23, 512, 512, 89, 5, "tanh", 0.0, (2211, 0, 2211, 0, 2212, 3, 704)),
+    _cv("sk_16x128_512to512_k5", 16, 512, 512, 128, 5, "none", 0.9, (2211, 0, 2211, 0, 2212, 8, 256)),
+    # rows against the walk of bn_stats_kernel / col_reduce_kernel (32 row lanes, four rows each per trip: 128 rows, then a tail loop)
+    # and Cout against its 32 columns per workgroup (8: a quarter block; 40, 136: a partial last block); rows = 1, 2: the unbiased
+    # factor's guard and rows / (rows - 1) = 2
+    _cv("r_1x1_8to8_k3", 1, 8, 8, 1, 3, "relu", None, (4111, 0, 4111, 0, 2212, 1, 0)),
+    _cv("r_1x1_24to40_k3", 1, 24, 40, 1, 3, "tanh", 0.5, (2311, 0, 4111, 0, 2212, 1, 0)),
+    _cv("r_1x1_8to136_k3", 1, 8, 136, 1, 3, "none", 0.0, (2211, 0, 4111, 0, 2212, 1, 0)),
+    _cv("r_2x1_8to8_k3", 2, 8, 8, 1, 3, "relu", 0.9, (4111, 0, 4111, 0, 2212, 1, 0)),
+    _cv("r_2x1_24to40_k3", 2, 24, 40, 1, 3, "tanh", None, (2311, 0, 4111, 0, 2212, 1, 0)),
+    _cv("r_2x1_8to136_k3", 2, 8, 136, 1, 3, "none", 0.5, (2211, 0, 4111, 0, 2212, 1, 0)),
+    _cv("r_1x31_8to8_k3", 1, 8, 8, 31, 3, "relu", 0.0, (4111, 0, 4111, 0, 2212, 1, 0)),
+    _cv("r_1x31_24to40_k3", 1, 24, 40, 31, 3, "tanh", 0.9, (2311, 0, 4111, 0, 2212, 1, 0)),
+    _cv("r_1x31_8to136_k3", 1, 8, 136, 31, 3, "none", None, (2211, 0, 4111, 0, 2212, 1, 0)),
+    _cv("r_4x8_8to8_k3", 4, 8, 8, 8, 3, "relu", 0.5, (4111, 0, 4111, 0, 2212, 1, 0)),
+    _cv("r_4x8_24to40_k3", 4, 24, 40, 8, 3, "tanh", 0.0, (2311, 0, 4111, 0, 2212, 1, 0)),
+    _cv("r_4x8_8to136_k3", 4, 8, 136, 8, 3, "none", 0.9, (2211, 0, 4111, 0, 2212, 1, 0)),
+    _cv("r_3x11_8to8_k3", 3, 8, 8, 11, 3, "relu", None, (4111, 0, 4111, 0, 2212, 1, 0)),
+    _cv("r_3x11_24to40_k3", 3, 24, 40, 11, 3, "tanh", 0.5, (2311, 0, 4111, 0, 2212, 1, 0)),
+    _cv("r_3x11_8to136_k3", 3, 8, 136, 11, 3, "none", 0.0, (2211, 0, 4111, 0, 2212, 1, 0)),
+    _cv("r_1x127_8to8_k3", 1, 8, 8, 127, 3, "relu", 0.9, (4111, 0, 4111, 0, 2212, 1, 0)),
+    _cv("r_1x127_24to40_k3", 1, 24, 40, 127, 3, "tanh", None, (2311, 0, 4111, 0, 2212, 1, 0)),
+    _cv("r_1x127_8to136_k3", 1, 8, 136, 127, 3, "none", 0.5, (2211, 0, 4111, 0, 2212, 1, 0)),
+    _cv("r_2x64_8to8_k3", 2, 8, 8, 64, 3, "relu", 0.0, (4111, 0, 4111, 0, 2212, 1, 0)),
+    _cv("r_2x64_24to40_k3", 2, 24, 40, 64, 3, "tanh", 0.9, (2311, 0, 4111, 0, 2212, 1, 0)),
+    _cv("r_2x64_8to136_k3", 2, 8, 136, 64, 3, "none", None, (2211, 0, 4111, 0, 2212, 1, 0)),
+    _cv("r_3x43_8to8_k3", 3, 8, 8, 43, 3, "relu", 0.5, (4111, 0, 4111, 0, 2212, 1, 0)),
+    _cv("r_3x43_24to40_k3", 3, 24, 40, 43, 3, "tanh", 0.0, (2311, 0, 4111, 0, 2212, 1, 0)),
+    _cv("r_3x43_8to136_k3", 3, 8, 136, 43, 3, "none", 0.9, (2211, 0, 4111, 0, 2212, 1, 0)),
+    _cv("r_5x51_8to8_k3", 5, 8, 8, 51, 3, "relu", None, (4111, 0, 4111, 0, 2212, 1, 0)),
+    _cv("r_5x51_24to40_k3", 5, 24, 40, 51, 3, "tanh", 0.5, (2311, 0, 4111, 0, 2212, 1, 0)),
+    _cv("r_5x51_8to136_k3", 5, 8, 136, 51, 3, "none", 0.0, (2211, 0, 4111, 0, 2212, 1, 0)),
+    _cv("r_1x257_8to8_k3", 1, 8, 8, 257, 3, "relu", 0.9, (4111, 0, 4111, 0, 2212, 1, 0)),
+    _cv("r_1x257_24to40_k3", 1, 24, 40, 257, 3, "tanh", None, (2311, 0, 4111, 0, 2212, 1, 0)),
+    _cv("r_1x257_8to136_k3", 1, 8, 136, 257, 3, "none", 0.5, (2211, 0, 4111, 0, 2212, 1, 0)),
+    # the model's own layers at the benchmark's training shape 32 x 200 (<4,1,1,3> for 80 channels above 4096 rows, <2,2,1,2>, the
+    # elementwise kernels' grid-stride loops: 6400 x 512 > 4096 x 256), once at 32 x 800 (<4,2,1,2> plus the second launch of 64 x 64
+    # tiles from row 24576 = sequence 30, frame 576), at one utterance of 568 frames and at 3 x 50 (<2,3,1,1> for the data gradient)
+    _cv("m_32x200_80to512_k5", 32, 80, 512, 200, 5, "tanh", 0.5, (2212, 0, 4113, 0, 2212, 8, 832)),
+    _cv("m_32x200_512to512_k5", 32, 512, 512, 200, 5, "relu", 0.5, (2212, 0, 2212, 0, 2212, 8, 832)),
+    _cv("m_32x200_512to80_k5", 32, 512, 80, 200, 5, "none", 0.5, (4113, 0, 2212, 0, 2212, 6, 1088)),
+    _cv("m_32x800_512to512_k5", 32, 512, 512, 800, 5, "tanh", 0.5, (4212, 24576, 4212, 24576, 2212, 8, 3200)),
+    _cv("m_1x568_512to512_k5", 1, 512, 512, 568, 5, "tanh", 0.5, (2211, 0, 2211, 0, 2212, 1, 0)),
+    _cv("m_3x50_80to512_k5", 3, 80, 512, 50, 5, "tanh", 0.5, (2211, 0, 2311, 0, 2212, 1, 0)),
+    _cv("m_1x568_512to80_k5", 1, 512, 80, 568, 5, "none", None, (2311, 0, 2211, 0, 2212, 2, 320)),
+    # 12 x 36 = 432 tiles of 128 x 128 in the weight gradient: the <2,2,2,2> K-major tile under a two-level map (the model never
+    # reaches it; the code can)
+    _cv("big_2x37_512to1536_k9", 2, 512, 1536, 37, 9, "tanh", 0.5, (2211, 0, 2211, 0, 2222, 1, 0)),
+    # options on small shapes: no running statistics; channel means of order 1e3 (forward and backward)
+    _cv("norun_5x13_24to40_k5", 5, 24, 40, 13, 5, "tanh", 0.5, (2311, 0, 4111, 0, 2212, 1, 0), running=False),
+    _cv("norun_7x80_8to24_k3", 7, 8, 24, 80, 3, "relu", None, (4111, 0, 4111, 0, 2212, 2, 320), running=False),
+    _cv("off_5x31_24to40_k5", 5, 24, 40, 31, 5, "tanh", 0.5, (2311, 0, 4111, 0, 2212, 1, 0), offset=1000.0),
+    _cv("off_9x64_40to24_k3", 9, 40, 24, 64, 3, "relu", None, (4111, 0, 2311, 0, 2212, 2, 320), offset=1000.0),
+    _cv("off_3x3_8to136_k5", 3, 8, 136, 3, 5, "none", 0.0, (2211, 0, 4111, 0, 2212, 1, 0), offset=1000.0),
+]
+CONV_TRAIN_BY_NAME = {c.name: c for c in CONV_TRAIN_CASES}
+# run once more with dx = NULL (everything else bit-equal) and with x_wgrad given (only dw changes, bit-equal elsewhere)
+CONV_TRAIN_OPTION_CASES = ["t_50x2_40to8_k5", "t_5x33_40to8_k7", "sk_103x5_8to40_k5"]
+# B sequences of T frames against one sequence of B T frames: the same rows, other halos - the row maps' R matters
+CONV_TRAIN_REGROUP_CASES = ["t_13x5_24to40_k5", "sk_14x37_40to24_k5", "sk_600x1_40to8_k5"]
+CONV_TRAIN_BIG = "m_32x800_512to512_k5"   # its float64 reference is 2 x 10^11 flops on the CPU: one such case
+
+
+def conv_train_plan(lib, B, Cin, Cout, T, k):
+    """(status, (forward tile, rows_big, data-gradient tile, rows_big, weight-gradient tile, K pieces, piece length)) of
+    gvx_debug_conv_train_plan.  Host arithmetic only; the export is in neither the public header nor _lib.SIGNATURES."""
+    fn = lib.gvx_debug_conv_train_plan
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int] * 5 + [C.POINTER(C.c_int)]
+    out = (C.c_int * 8)(*([-1] * 8))
+    rc = fn(B, Cin, Cout, T, k, out)
+    return rc, (out[0], out[1], out[2], out[3], out[4], out[6], out[7]), out[5]
+
+
 # ---- the forward recurrences (gvx_decoder_teacher_forced(_train), gvx_decoder_autoregressive, gvx_encoder_lstm_forward,
 # gvx_encoder_forward): the cases tests/test_forward_loops_gpu.py runs, each with the plan it is there for.
 # tests/test_host_cpu.py pins every line against gvx_debug_decoder_plan / gvx_debug_encoder_resident on the CPU, and both sides of

@@ -476,3 +476,116 @@ def test_encoder_recurrence_plan_of_every_listed_case():
     h = H.create_handle(lib, dims_from_configs(*H.enc_fwd_configs(256)))
     assert [H.encoder_resident(lib, h, B) for B in (1, 32, 33, 64, 0)] == [1, 1, 0, 0, 0] and H.encoder_resident(lib, None, 4) == 0
     lib.gvx_model_destroy(h)
+
+
+def test_conv_train_plan_of_every_listed_case():
+    """How a convolution layer's three products run is host arithmetic; gvx_debug_conv_train_plan reports it from the functions the
+    two entry points launch through (conv_forward_gemm / conv_dgrad_gemm / conv_wgrad_gemm, plan_gemm, choose_splitk, set_splitk).
+    Every case of tests/test_conv_train_gpu.py must reach the tiles and the cut of K its line names, and the table as a whole every
+    tile shape the layer can take, 1, 2, 3, 7 and 8 pieces, a short last piece, pieces that begin inside a sequence and at a
+    sequence's first frame."""
+    from tests.helpers import (CONV_TRAIN_BIG, CONV_TRAIN_BY_NAME, CONV_TRAIN_CASES, CONV_TRAIN_OPTION_CASES, CONV_TRAIN_REGROUP_CASES,
+                               conv_train_plan)
+
+    if os.environ.get("GVX_GEMM_8W", "")[:1] == "0":
+        pytest.skip("the table is for the default eight-wave tile")
+    lib = _lib.load()
+    assert len(CONV_TRAIN_BY_NAME) == len(CONV_TRAIN_CASES)
+    assert set(CONV_TRAIN_OPTION_CASES + CONV_TRAIN_REGROUP_CASES + [CONV_TRAIN_BIG]) <= set(CONV_TRAIN_BY_NAME)
+    for c in CONV_TRAIN_CASES:
+        rc, plan, wgrad_rows_big = conv_train_plan(lib, c.B, c.Cin, c.Cout, c.T, c.k)
+        assert rc == 0 and plan == c.plan and wgrad_rows_big == 0, (c, rc, plan)
+        assert c.name.endswith("_%dx%d_%dto%d_k%d" % (c.B, c.T, c.Cin, c.Cout, c.k)), c.name
+    cases, plans = CONV_TRAIN_CASES, [c.plan for c in CONV_TRAIN_CASES]
+    assert {p[0] for p in plans} == {4111, 2311, 4113, 2211, 2212, 4212} and {p[2] for p in plans} == {4111, 2311, 4113, 2211, 2212, 4212}
+    assert {p[4] for p in plans} == {2212, 2222}
+    assert any(p[1] > 0 and p[1] % c.T for c, p in zip(cases, plans)) and any(p[3] > 0 for p in plans)   # a second launch, from inside a sequence
+    assert {p[5] for p in plans} >= {1, 2, 3, 7, 8}
+    split = [(c, p) for c, p in zip(cases, plans) if p[5] > 1]
+    assert all(p[6] % 64 == 0 and (p[5] - 1) * p[6] < c.B * c.T <= p[5] * p[6] for c, p in split)
+    assert any(c.B * c.T % p[6] for c, p in split) and any(c.B * c.T % p[6] == 0 for c, p in split)       # a short last piece, and none
+    assert any(p[6] % c.T and c.B > 1 for c, p in split) and any(p[6] % c.T == 0 and c.B > 1 for c, p in split)
+    assert any(c.T == 1 for c, p in split) and any(c.B == 1 for c, p in split)
+    # T against the halo and the k-tile, the rows against the reduction walk, the options
+    whole = [c for c, p in zip(cases, plans) if p[5] == 1]
+    assert {c.T for c in whole} >= {1, 2, 3, 4, 5, 7, 31, 32, 33, 63, 64, 65} and {c.k for c in whole} >= {1, 3, 5, 7}
+    assert any(c.T < (c.k - 1) // 2 for c in cases) and any(c.T == 1 and c.k == 7 for c in cases)
+    for co in (8, 40, 136):
+        assert {c.B * c.T for c in cases if c.Cout == co} >= {1, 2, 31, 32, 33, 127, 128, 129, 255, 257}, co
+    assert {c.B * c.T for c in cases} >= {511, 512, 513, 767, 768, 2047, 2048}
+    assert {(c.act, c.p) for c in cases} >= {(a, p) for a in ("none", "relu", "tanh") for p in (None, 0.0, 0.5, 0.9)}
+    assert any(not c.running for c in cases) and any(c.offset >= 1e3 for c in cases)
+    assert sum(1 for c in cases if c.B * c.T * c.Cout * c.k * c.Cin > 1e10) == 1 and CONV_TRAIN_BY_NAME[CONV_TRAIN_BIG].plan[1] > 0
+    # choose_splitk's thresholds, one step to either side: few tiles split from 512 rows on, one more piece per 256 rows up to 8; the
+    # 160 tiles of 512 x 2560 take 3 pieces from 768 rows and 8 from 2048; from 256 tiles of 64 x 128 on nothing is split
+    pieces = lambda rows, ci=24, co=24, k=5: conv_train_plan(lib, 1, ci, co, rows, k)[1][5:]
+    assert pieces(511) == (1, 0) and pieces(512) == (2, 256) and pieces(513) == (2, 320) and pieces(767) == (2, 384) and pieces(768) == (3, 256)
+    assert pieces(1791) == (6, 320) and pieces(1792) == (7, 256) and pieces(2047) == (7, 320) and pieces(2048) == (8, 256) and pieces(6400) == (8, 832)
+    assert pieces(767, 512, 512) == (1, 0) and pieces(768, 512, 512) == (3, 256) and pieces(2047, 512, 512) == (3, 704) and pieces(2048, 512, 512) == (8, 256)
+    assert pieces(6400, 512, 1024, 3) == (4, 1600) and pieces(6400, 512, 1024, 5) == (1, 0)   # 16 x 12 = 192 tiles: 3 rounds of 256 for 4 pieces; 320 tiles: whole
+    # refused exactly where the entry points refuse
+    out = (C.c_int * 8)()
+    fn = lib.gvx_debug_conv_train_plan
+    fn.restype, fn.argtypes = C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_int)]
+    assert fn(1, 8, 8, 1, 1, out) == 0 and fn(1, 8, 8, 1, 1, None) == -1 and fn(1, 12, 8, 1, 1, out) == -2 and fn(1, 8, 8, 1, 2, out) == -2
+
+
+CONV_BAD_SHAPES = [
+    (3, 12, 24, 5, 3), (3, 24, 20, 5, 3), (3, 4, 24, 5, 3), (3, 24, 4, 5, 3), (3, 0, 24, 5, 3), (3, 24, 0, 5, 3), (3, -8, 24, 5, 3),   # channels
+    (3, 24, 24, 5, 2), (3, 24, 24, 5, 4), (3, 24, 24, 5, 0), (3, 24, 24, 5, -1), (3, 24, 24, 5, -3),                                   # kernel size
+    (0, 24, 24, 5, 3), (-1, 24, 24, 5, 3), (3, 24, 24, 0, 3), (3, 24, 24, -2, 3),                                                      # B, T
+    (32768, 8, 8, 32769, 1), (1, 8, 8, (1 << 30) + 1, 1), ((1 << 30) + 1, 8, 8, 1, 1),                                                 # B T above 2^30
+]
+
+
+def test_conv_train_entry_points_validate_their_arguments_on_the_host():
+    """Every check of gvx_conv_bn_act_train_forward / _backward and of the two size queries runs before the first HIP call, so it is
+    tested here: the shapes the header lists as refused (the queries return 0 exactly there), NULL arguments, buffers one byte too
+    small, misaligned buffers, an unknown activation, a dropout probability outside [0, 1) with a mask.  The pointers are made-up
+    addresses: a call that got past its checks would launch on them, and without a device fail with GVX_ERR_HIP, never 0."""
+    lib = _lib.load()
+    P = 1 << 20                                          # any 256-byte aligned non-null address
+    B, Cin, Cout, T, k = 3, 24, 40, 5, 5
+    sb, wb = lib.gvx_conv_train_saved_bytes(B, Cin, Cout, T, k), lib.gvx_conv_train_workspace_bytes(B, Cin, Cout, T, k)
+    assert sb > 0 and wb > 0 and sb % 256 == 0 and wb % 256 == 0
+    # saved: the halo-padded input, xhat and the activation, mean and invstd, each rounded up to 256 bytes
+    up = lambda n: (4 * n + 255) // 256 * 256
+    assert sb == up(B * (T + 4) * Cin) + 2 * up(B * T * Cout) + 2 * up(Cout)
+    assert lib.gvx_conv_train_saved_bytes(1, 8, 8, 1, 1) > 0 and lib.gvx_conv_train_workspace_bytes(1, 8, 8, 1, 1) > 0
+    assert lib.gvx_conv_train_saved_bytes(1, 8, 8, 1 << 30, 1) > 0          # the largest B T the row index holds
+
+    def fwd(shape=(B, Cin, Cout, T, k), act=2, keep=P, p=0.5, sbytes=sb, wbytes=wb, **ptr):
+        a = dict(x=P, w=P, bias=P, gamma=P, beta=P, rm=P, rv=P, y=P, saved=P, ws=P)
+        a.update(ptr)
+        return lib.gvx_conv_bn_act_train_forward(a["x"], a["w"], a["bias"], a["gamma"], a["beta"], a["rm"], a["rv"], *shape, act, keep, p,
+                                                 a["y"], a["saved"], sbytes, a["ws"], wbytes, None)
+
+    def bwd(shape=(B, Cin, Cout, T, k), act=2, keep=P, p=0.5, sbytes=sb, wbytes=wb, **ptr):
+        a = dict(dy=P, saved=P, w=P, gamma=P, xw=None, dx=P, dw=P, dbias=P, dgamma=P, dbeta=P, ws=P)
+        a.update(ptr)
+        return lib.gvx_conv_bn_act_train_backward(a["dy"], a["saved"], sbytes, a["w"], a["gamma"], a["xw"], *shape, act, keep, p, a["dx"],
+                                                  a["dw"], a["dbias"], a["dgamma"], a["dbeta"], a["ws"], wbytes, None)
+
+    for shape in CONV_BAD_SHAPES:
+        assert lib.gvx_conv_train_saved_bytes(*shape) == 0 and lib.gvx_conv_train_workspace_bytes(*shape) == 0, shape
+        for call in (fwd, bwd):
+            assert call(shape=shape, sbytes=1 << 40, wbytes=1 << 40) == -2, (call.__name__, shape)
+            msg = lib.gvx_last_error()
+            assert b"conv training op" in msg and (b"multiples of 8" in msg or b"B * T exceeds" in msg), msg
+    for call, names in ((fwd, ("x", "w", "bias", "gamma", "beta", "y", "saved", "ws")),
+                        (bwd, ("dy", "saved", "w", "gamma", "dw", "dbias", "dgamma", "dbeta", "ws"))):
+        for n in names:
+            assert call(**{n: None}) == -1 and b"null argument" in lib.gvx_last_error(), (call.__name__, n)
+        for act in (-1, 3, 7):
+            assert call(act=act) == -1 and b"activation must be" in lib.gvx_last_error(), (call.__name__, act)
+        for p in (1.0, 1.5, -0.1, float("nan"), float("inf")):
+            assert call(p=p) == -1 and b"dropout probability" in lib.gvx_last_error(), (call.__name__, p)
+        assert call(sbytes=sb - 1) == -5 and b"too small" in lib.gvx_last_error(), call.__name__
+        assert call(wbytes=wb - 1) == -5 and b"too small" in lib.gvx_last_error(), call.__name__
+        assert call(sbytes=0) == -5 and call(wbytes=0) == -5
+        for off in (4, 16, 128, 255):
+            assert call(saved=P + off) == -5 and b"256-byte aligned" in lib.gvx_last_error(), (call.__name__, off)
+            assert call(ws=P + off) == -5 and b"256-byte aligned" in lib.gvx_last_error(), (call.__name__, off)
+    # the order of the checks: the shape first, then NULL, then the options, then the buffers
+    assert fwd(shape=CONV_BAD_SHAPES[0], x=None, act=9, sbytes=0) == -2 and fwd(x=None, act=9, sbytes=0) == -1 and fwd(act=9, sbytes=0) == -1
+    assert bwd(shape=CONV_BAD_SHAPES[0], dy=None, act=9, sbytes=0) == -2 and bwd(dy=None, act=9, sbytes=0) == -1 and bwd(act=9, sbytes=0) == -1
