@@ -36,7 +36,9 @@ class WavTextCollateFn:
     or floating point array) -> the same dict, same row order, dtypes and shapes.  The mel side (``mel_padded``, ``gate_padded``,
     ``mel_lengths``) comes from one ``AudioProcessor.wav_to_mel_ragged`` call - silence trimming and normalisation as the audio
     config says - and stays on the processor's device; the token side is built on the host as before.  A recording that gives no
-    mel raises ``ValueError`` (the index it names is the row of the sorted batch)."""
+    mel raises ``ValueError`` (the index it names is the row of the sorted batch).  An item may carry ``"wav_rate"`` (Hz) when its
+    recording is not at the model's rate, and its ``wav`` may be ``(n, channels)``: such recordings are mixed down and resampled on
+    the device inside the same call."""
 
     def __init__(self, audio_processor):
         self.audio_processor = audio_processor
@@ -50,6 +52,9 @@ class WavTextCollateFn:
             tok = torch.as_tensor(batch[i]["tokens"])
             out["token_padded"][row, : tok.shape[0]] = tok
             out["token_lengths"][row] = tok.shape[0]
-        mel, mel_lengths, gate = self.audio_processor.wav_to_mel_ragged([batch[i]["wav"] for i in order])[:3]
+        rates = {}
+        if any("wav_rate" in x for x in batch):
+            rates["sample_rates"] = [int(batch[i].get("wav_rate", self.audio_processor.config.sampling_rate)) for i in order]
+        mel, mel_lengths, gate = self.audio_processor.wav_to_mel_ragged([batch[i]["wav"] for i in order], **rates)[:3]
         out.update(mel_padded=mel, gate_padded=gate, mel_lengths=mel_lengths)
         return out

@@ -2,7 +2,7 @@
 loading, text -> tokens, autoregressive Tacotron2 on the GPU, mel -> waveform on the GPU."""
 from __future__ import annotations
 
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -50,23 +50,28 @@ class Synthesizer:
         self.text_processor = TextProcessor(config=self.tts_model.text_config)
         self.audio_processor = AudioProcessor(config=self.tts_model.audio_config, device=self.device)
 
-    def tts(self, text: str) -> Dict[str, np.ndarray]:
+    def _out_rate(self, sampling_rate: Optional[int]) -> int:
+        return self.audio_processor.config.sampling_rate if sampling_rate is None else int(sampling_rate)
+
+    def tts(self, text: str, sampling_rate: Optional[int] = None) -> Dict[str, np.ndarray]:
+        """``sampling_rate`` (Hz; default: the model's): the waveform is resampled on the device before it is copied to the host,
+        and ``"sampling_rate"`` of the result is the rate delivered."""
         tokens = self.text_processor.tokens_to_indices(self.text_processor.tokenize(text))
         tokens = torch.IntTensor(tokens).unsqueeze(0).to(self.device)
         outputs = self.tts_model.inference(inputs={"tokens": tokens})
         mel = outputs["mel_outputs_postnet"]
-        wav = self.audio_processor.convert_mel2wav_batch(mel)  # stays on the device until the end
+        wav = self.audio_processor.convert_mel2wav_batch(mel, out_rate=sampling_rate)  # stays on the device until the end
         result = {key: val.squeeze(0).cpu().numpy() for key, val in outputs.items()}
         result["waveform"] = wav[0].cpu().numpy()
-        result["sampling_rate"] = self.audio_processor.config.sampling_rate
+        result["sampling_rate"] = self._out_rate(sampling_rate)
         return result
 
-    def tts_batch(self, texts: Sequence[str], batch_size: int = 32) -> List[Dict[str, np.ndarray]]:
+    def tts_batch(self, texts: Sequence[str], batch_size: int = 32, sampling_rate: Optional[int] = None) -> List[Dict[str, np.ndarray]]:
         """Many sentences per call: one dict per sentence, in input order, with the keys, dtypes and shapes ``tts(text)`` gives
         for that sentence (every row trimmed to its own frames, tokens and samples).  Sentences are decoded as padded batches of
         at most ``batch_size`` rows of similar token length (``plan_tts_batches``) and vocoded at their own lengths in one ragged
         Griffin-Lim call per batch; the mels stay on the device in between.  A batch of one sentence is exactly the ``tts`` path,
-        torch RNG draws included."""
+        torch RNG draws included.  ``sampling_rate`` as in ``tts``: every row is resampled at its own sample count."""
         token_lists = [self.text_processor.tokens_to_indices(self.text_processor.tokenize(t)) for t in texts]
         results: List[Dict[str, np.ndarray]] = [{} for _ in token_lists]
         for idx, tokens, lens in plan_tts_batches(token_lists, batch_size):
@@ -77,10 +82,10 @@ class Synthesizer:
             mel = outputs["mel_outputs_postnet"]
             if len(idx) > 1:
                 frames = outputs.pop("mel_lengths")
-                wav, samples = self.audio_processor.convert_mel2wav_batch(mel, mel_lengths=frames)
+                wav, samples = self.audio_processor.convert_mel2wav_batch(mel, mel_lengths=frames, out_rate=sampling_rate)
                 frames = frames.tolist()
             else:
-                wav = self.audio_processor.convert_mel2wav_batch(mel)
+                wav = self.audio_processor.convert_mel2wav_batch(mel, out_rate=sampling_rate)
                 frames, samples = [mel.shape[2]], [wav.shape[1]]
             host = {key: val.cpu().numpy() for key, val in outputs.items()}
             wav = wav.cpu().numpy()
@@ -91,5 +96,5 @@ class Synthesizer:
                               "gate_outputs": host["gate_outputs"][r, :t].copy(),
                               "alignments": host["alignments"][r, :t, :n_tok].copy(),
                               "waveform": wav[r, :samples[r]].copy(),
-                              "sampling_rate": self.audio_processor.config.sampling_rate}
+                              "sampling_rate": self._out_rate(sampling_rate)}
         return results

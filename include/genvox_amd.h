@@ -495,6 +495,40 @@ int gvx_wav_to_mel_ragged(gvx_gl_plan* plan, const void* pcm, int pcm_kind, cons
                           float* mel_db_out, float* gate_out, int32_t* frame_lengths_out, int32_t* row_status_out, void* workspace,
                           size_t workspace_bytes, void* stream);
 
+/* ---- Sample-rate conversion and channel mix-down of PCM batches: the first stage of the reference's data path (format_audio2wav,
+ * there an ffmpeg process per file) and the way synthesised audio leaves at another rate.  Asynchronous on `stream`, caller-allocated
+ * buffers, no workspace.  GVX_PCM_FLOAT64 (float64 samples, full scale 1.0) is accepted by the calls of this section only.
+ *
+ * The resampler is filter-agnostic: the caller designs a low-pass prototype h at the rate src * up = dst * down (up / down = dst / src,
+ * reduced), centred on index 0, and hands it over as a polyphase table [up][taps_per_phase] (K = taps_per_phase, a multiple of 4 in
+ * [4, GVX_RESAMPLE_MAX_TAPS]; float32 for int16 and float32 samples, float64 for float64 samples; 16-byte aligned).  Row b is the
+ * signal x = pcm[b][left_b, right_b) of bounds [B][2] (DEVICE int32, clamped to [0, n_max] on the device, as the ragged wav -> mel
+ * call takes them), zero outside; with n_b = right_b - left_b it becomes n_out_b = ceil(n_b * up / down) samples.  For output m,
+ * 0 <= m < n_out_b, let q = (m * down) / up and p = (m * down) % up:
+ *
+ *     out[b][m] = sum over k = 0 .. K-1, in ascending k, of  table[p * K + k] * x[q - (K / 2 - 1) + k]
+ *
+ * (accumulated in the output type, each step one fused multiply-add), which is y[m] = sum_j x[j] * h[m * down - j * up] when
+ * table[p * K + k] = h[p + (K / 2 - 1 - k) * up], 0 outside the prototype.  Output 0 sits on input 0: there is no delay.  int16
+ * samples are not scaled (full scale stays 32767).  out keeps the stride n_out_stride >= ceil(n_max * up / down) (a smaller one is
+ * GVX_ERR_INVALID_ARG): float32 [B][n_out_stride], float64 for float64 samples, exact zeros in [n_out_b, n_out_stride), and
+ * out_lengths [B] = n_out_b.  Nothing outside a row's bounds is used as signal, whatever it holds.  A row's result does not depend on
+ * the batch it sits in.  up above GVX_RESAMPLE_MAX_UP or down above GVX_RESAMPLE_MAX_DOWN: GVX_ERR_UNSUPPORTED; a NULL pointer, an
+ * unknown pcm_kind, up or down < 1, a bad taps_per_phase: GVX_ERR_INVALID_ARG; all of it checked before anything is launched.
+ * The kernel stages the table in LDS when it fits beside its input tile and reads it through the cache from global memory when
+ * not; the resample_uses_lds_table query says which (1 / 0) for a table of `up` rows and the output type of pcm_kind, and returns -1
+ * for an up, taps_per_phase or pcm_kind the call would refuse.
+ *
+ * The mix-down call: interleaved pcm [B][n_max][channels] (what scipy.io.wavfile.read gives per file), channels in [2, 8], to
+ * float32 mono_out [B][n_max]: the arithmetic mean of a frame's channels, summed in double in ascending channel order and
+ * rounded once (int16 keeps its full scale of 32767). */
+enum { GVX_PCM_FLOAT64 = 2 };
+enum { GVX_RESAMPLE_MAX_UP = 2048, GVX_RESAMPLE_MAX_DOWN = 2048, GVX_RESAMPLE_MAX_TAPS = 1024 };
+int gvx_resample_uses_lds_table(int up, int taps_per_phase, int pcm_kind);
+int gvx_wav_mixdown(const void* pcm, int pcm_kind, int B, long n_max, int channels, float* mono_out, void* stream);
+int gvx_wav_resample_ragged(const void* pcm, int pcm_kind, int B, long n_max, const int32_t* bounds, int up, int down,
+                            const void* table, int taps_per_phase, void* out, long n_out_stride, int32_t* out_lengths, void* stream);
+
 /* ---- Per-kernel timing of the decoder step (measurement only): when enabled, a teacher-forced call replays the
  * mid-sequence LSTM-step launch and the attention launches 64 times each, back to back, between HIP events on
  * `stream` (after its loop; the call's outputs are not valid afterwards); gvx_kernel_times_ms synchronises and

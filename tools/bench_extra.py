@@ -2,7 +2,9 @@
 """Secondary measurements for DESIGN.md (BASELINE.json configs 2-4 beyond the headline line of bench.py):
 teacher-forced at B=64, autoregressive RTF (B=64, 1000 steps), Postnet-only MFMA rate, Griffin-Lim throughput;
 `glr` (on request): the ragged Griffin-Lim call against the same rows padded through the uniform call;
-`w2mr` (on request): 64 recordings of 2-10 s through one ragged wav -> mel call against 64 single-row `wav_to_mel` calls."""
+`w2mr` (on request): 64 recordings of 2-10 s through one ragged wav -> mel call against 64 single-row `wav_to_mel` calls;
+`w2m48` (on request): 32 recordings of 10 s at 48 kHz through `convert_wav2mel_batch` (resampled on the device) against the same
+batch delivered at the model's rate."""
 import json
 import os
 import sys
@@ -157,6 +159,41 @@ def main():
         res["wav_to_mel_ragged_b64_2to10s"] = {
             "ragged_from_host_int16": ragged_host, "ragged_from_device_int16": ragged_dev, "single_row_calls_x64": single,
             "frames": frames, "padded_frames": B * ((n_max - 1024) // 256 + 1), "seconds_of_audio": round(sum(lengths) / fs, 1)}
+    if "w2m48" in which:
+        # resample + wav -> mel: 32 int16 recordings of 10 s, (a) at 48 kHz through convert_wav2mel_batch (resampled to 22 050 Hz on the
+        # device, then one ragged wav -> mel call), (b) the same durations delivered at 22 050 Hz (today's path), (c) the resampler alone
+        # on a batch that is already on the device.  Host arrays in, host mels out, as a preprocessing job calls it; 7 runs each.
+        import statistics
+
+        import numpy as np
+
+        ap = AudioProcessor(AudioConfig(sampling_rate=22050, filter_length=1024, hop_length=256, log_func="np.log"))
+        B, seconds = 32, 10
+        rng = np.random.default_rng(0)
+        at48 = [rng.integers(-12000, 12001, size=seconds * 48000).astype(np.int16) for _ in range(B)]
+        at22 = [rng.integers(-12000, 12001, size=seconds * 22050).astype(np.int16) for _ in range(B)]
+        dev48 = torch.from_numpy(np.stack(at48)).cuda()
+
+        def runs(fn, warm=2, reps=7):
+            for _ in range(warm):
+                fn()
+            out = []
+            for _ in range(reps):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                out.append((time.perf_counter() - t0) * 1e3)
+            return {"median_ms": round(statistics.median(out), 2), "min_ms": round(min(out), 2), "max_ms": round(max(out), 2), "runs": reps}
+
+        foreign = runs(lambda: ap.convert_wav2mel_batch(at48, sample_rates=48000))
+        native = runs(lambda: ap.convert_wav2mel_batch(at22))
+        alone = runs(lambda: ap.resample(dev48, 48000, sample_lengths=[seconds * 48000] * B))
+        outputs, taps = B * seconds * 22050, ap._resample_table(48000, 22050, False)[2]
+        res["convert_wav2mel_batch_b32_10s"] = {
+            "at_48k_resampled_on_device": foreign, "at_model_rate": native, "resample_kernel_alone_device_batch": alone,
+            "cost_ratio": round(foreign["median_ms"] / native["median_ms"], 2), "outputs": outputs, "taps_per_phase": taps,
+            "resample_gflop": round(2e-9 * outputs * taps, 2)}
     if "cpu" in which:
         # CPU baselines for configs 3 and 4 (the oracle = CPU restatement of the reference, on this box's host cores):
         # bounded samples, reported beside the GPU figures above; bench.py carries the one for config 2.
