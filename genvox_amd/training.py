@@ -405,9 +405,7 @@ def _recurrent_backward(model, ops: "_Ops", ch: dict, dmel: torch.Tensor, dgate:
     walk = lib.gvx_train_encoder_lstm_bptt_resident if getattr(model, "_enc_bptt_resident", True) else lib.gvx_train_encoder_lstm_bptt
     _lib.check(walk(_p(xg), _p(memory.contiguous()), _p(c_enc.contiguous()), _p(dmemory.contiguous()), _p(w_hh2), _p(tl32),
                     B, L, H, _p(dg_pos), _p(hprev_pos), _p(wse), wse.numel(), st))
-    if not hasattr(model, "_enc_bptt_workspaces"):
-        model._enc_bptt_workspaces = []
-    model._enc_bptt_workspaces.append((wse, B, H))   # (kept until the step's gradients have been looked at)
+    model._enc_bptt_workspaces.append((wse, B, H))   # (one per chunk; train_backward starts the list afresh on every call)
     for d_, sfx in enumerate(sfxs):
         dg2 = dg_pos[d_]
         g["encoder.lstm.weight_ih_l0" + sfx] = ops.mm_tn(dg2, x.reshape(B * L, E))
@@ -428,6 +426,7 @@ def train_backward(model, batch: Dict[str, torch.Tensor], outputs: Dict[str, tor
     dev = outputs["mel_outputs"].device
     ops = _Ops(dev)
     lib, st = ops.lib, ops.st
+    model._enc_bptt_workspaces = []   # only this call's: what encoder_bptt_timed_out looks at
     P_ = dict(model.named_parameters())
     tok = batch["token_padded"].to(device=dev, dtype=torch.int64).contiguous()
     B, L = tok.shape

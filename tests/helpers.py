@@ -609,3 +609,73 @@ def encoder_resident(lib, handle, B):
     fn.restype = C.c_int
     fn.argtypes = [C.c_void_p, C.c_int]
     return int(fn(handle, B))
+
+
+# ---- the whole training step (Tacotron2._forward_train + training.train_backward + train_step): the cases
+# tests/test_train_step_gpu.py runs against the float64 autograd of tests/train_ref64.py, each with what it is there for.
+# tests/test_host_cpu.py pins every line's chunk list and, through gvx_teacher_forced_loop_kind / gvx_teacher_forced_rows_per_call and
+# the training plan of gvx_debug_decoder_plan, the decoder loop each chunk is meant to reach. ---------------------------------------
+# dims: a key of TRAIN_STEP_DIMS.  Token lengths as bptt_lengths("ragged"): rows from L down to 1; mel lengths as
+# train_step_mel_lengths: one row of T frames, one of 1 frame (B >= 2).  forced: None, "resident_off"
+# (gvx_model_set_resident_kernels(handle, 0)) or "enc_walk_per_step" (model._enc_bptt_resident = False).
+# chunks: the row ranges of the recurrent part.  kinds: per chunk (loop kind of the training call, loop kind of an inference call).
+TrainStepCase = collections.namedtuple("TrainStepCase", "name dims B L T mask_padding forced chunks kinds why")
+TRAIN_STEP_DIMS = dict(FWD_DIMS, unusual=dict(
+    model=dict(symbols_embedding_dim=48, encoder_embedding_dim=48, encoder_kernel_size=5, encoder_n_convolutions=2, decoder_rnn_dim=56,
+               attention_rnn_dim=40, prenet_dim=16, attention_dim=24, attention_location_n_filters=12, attention_location_kernel_size=9,
+               postnet_embedding_dim=32, postnet_kernel_size=3, postnet_n_convolutions=3), n_mels=16))
+
+
+def _ts(name, dims, B, L, T, kinds, why, mask_padding=True, forced=None):
+    chunks = tuple((lo, min(B, lo + 32)) for lo in range(0, B, 32))
+    return TrainStepCase(name, dims, B, L, T, mask_padding, forced, chunks, tuple(kinds), why)
+
+
+_S, _D2 = ((0, 0),), ((2, 2),)
+TRAIN_STEP_CASES = [
+    _ts("fixture_4x9x10", "small", 4, 9, 10, _S, "the shape of the reference's own fixture, reduced sizes"),
+    # chunk edges at reduced sizes: 1, 2, 31, 32 rows in one chunk; 33 = 32 + 1, 64 = 32 + 32, 65 = 32 + 32 + 1
+    _ts("small_1x9x6", "small", 1, 9, 6, _S, "one row"),
+    _ts("small_2x9x6", "small", 2, 9, 6, _S, "two rows: token lengths 9 and 1, mel lengths 6 and 1"),
+    _ts("small_31x9x5", "small", 31, 9, 5, _S, "one row short of a chunk"),
+    _ts("small_32x9x5", "small", 32, 9, 5, _S, "a full chunk"),
+    _ts("small_33x9x5", "small", 33, 9, 5, _S * 2, "a second chunk of one row: _accumulate, row offsets"),
+    _ts("small_64x9x4", "small", 64, 9, 4, _S * 2, "two full chunks"),
+    _ts("small_65x9x4", "small", 65, 9, 4, _S * 3, "three chunks, the last of one row"),
+    _ts("small_5x9x1", "small", 5, 9, 1, _S, "T = 1: the tape's slot shifts with a single step"),
+    _ts("small_5x1x6", "small", 5, 1, 6, _S, "L = 1: one token per row"),
+    _ts("small_nomask_4x9x10", "small", 4, 9, 10, _S, "mask_padding = False", mask_padding=False),
+    _ts("unusual_6x19x8", "unusual", 6, 19, 8, _S, "layer sizes no fast path is built for"),
+    # default layer sizes
+    _ts("def_3x24x12", "def", 3, 24, 12, _D2, "default sizes, one small chunk on the resident loop"),
+    _ts("def_32x128x20", "def", 32, 128, 20, _D2, "the benchmark's rows and tokens"),
+    _ts("def_37x40x8", "def", 37, 40, 8, _D2 * 2, "two chunks of different size (32 + 5) at default sizes"),
+    _ts("def_4x129x5", "def", 4, 129, 5, _D2, "first L of the deal for rows above 128 tokens"),
+    _ts("def_5x150x6", "def", 5, 150, 6, _D2, "rows above 128 tokens"),
+    _ts("def_3x300x5", "def", 3, 300, 5, ((0, 0),), "L past the resident limit: a launch pair per step"),
+    _ts("def_32x60x200", "def", 32, 60, 200, _D2, "many addends: 6400 (t, b) rows per weight gradient"),
+    _ts("def_resident_off_3x24x12", "def", 3, 24, 12, ((0, 0),), "forced: launch-per-step kernels", forced="resident_off"),
+    _ts("def_enc_walk_3x24x12", "def", 3, 24, 12, _D2, "forced: encoder BiLSTM backward as a launch per time step", forced="enc_walk_per_step"),
+]
+TRAIN_STEP_BY_NAME = {c.name: c for c in TRAIN_STEP_CASES}
+TRAIN_STEP_MANY = "def_32x60x200"
+# the four consecutive steps of the trajectory tests: (B, L, T) per step, other rows and frames each time
+TRAIN_TRAJECTORY = {"small": [(5, 9, 7), (33, 11, 4), (3, 6, 9), (34, 9, 5)], "def": [(3, 24, 6), (33, 20, 4), (2, 30, 8), (5, 16, 5)]}
+
+
+def train_step_configs(case):
+    from genvox_amd.configs import AudioConfig, Tacotron2Config, TextConfig
+
+    d = TRAIN_STEP_DIMS[case.dims if isinstance(case, TrainStepCase) else case]
+    mc = Tacotron2Config(**d["model"])
+    if isinstance(case, TrainStepCase):
+        mc.mask_padding = case.mask_padding
+    return mc, AudioConfig(filter_length=1024, hop_length=256, n_mels=d["n_mels"], log_func="np.log"), TextConfig(n_tokens=40)
+
+
+def train_step_mel_lengths(B, T):
+    """Mel lengths of a case: spread over 1 .. T, the last row with one frame (B >= 2), row (B - 1) // 2 with all T."""
+    ml = [1 + (i * 7 + 3) % T for i in range(B)]
+    ml[-1] = 1
+    ml[(B - 1) // 2] = T
+    return ml
