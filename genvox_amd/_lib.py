@@ -113,6 +113,11 @@ SIGNATURES = {
     "gvx_resample_uses_lds_table": (_i, [_i, _i, _i]),
     "gvx_wav_mixdown": (_i, [_vp, _i, _i, C.c_long, _i, _vp, _vp]),
     "gvx_wav_resample_ragged": (_i, [_vp, _i, _i, C.c_long, _vp, _i, _i, _vp, _i, _vp, C.c_long, _vp, _vp]),
+    "gvx_alignment_stats": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gvx_mel_project": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "gvx_dtw_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "gvx_dtw_uses_lds_tables": (_i, [_i, _i, _i]),
+    "gvx_dtw_distance": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "gvx_kernel_timing_enable": (_i, [_vp, _i]),
     "gvx_model_set_persistent_attention": (_i, [_vp, _i]),
     "gvx_model_set_resident_kernels": (_i, [_vp, _i]),

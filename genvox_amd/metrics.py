@@ -1,0 +1,145 @@
+"""Evaluation by synthesis on the device: statistics of an attention alignment and the DTW mel-cepstral distance between a
+free-running mel and its target (C ABI: gvx_alignment_stats, gvx_mel_project, gvx_dtw_distance; definitions in
+include/genvox_amd.h, float64 restatement in tests/metrics_ref64.py).
+
+Every function takes and returns device tensors and enqueues on the current stream; none of them synchronises with the host.
+"""
+from __future__ import annotations
+
+import math
+from typing import Dict, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+
+ROW_INT_NAMES = ("monotonic", "max_jump", "covered", "first_pos", "last_pos")   # GVX_ALIGN_* of include/genvox_amd.h, in order
+
+
+def _stream(dev) -> int:
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+def _need_gpu(t: torch.Tensor, what: str) -> torch.device:
+    if t.device.type != "cuda":
+        raise RuntimeError(f"genvox_amd.metrics: {what} must be a GPU tensor (there is no CPU path)")
+    return t.device
+
+
+def _lengths(lens: Optional[torch.Tensor], B: int, dev) -> Optional[torch.Tensor]:
+    if lens is None:
+        return None
+    lens = lens.to(device=dev, dtype=torch.int32).contiguous()
+    if lens.shape != (B,):
+        raise ValueError(f"lengths of shape {tuple(lens.shape)} for a batch of {B} rows")
+    return lens
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return None if t is None or t.numel() == 0 else t.data_ptr()
+
+
+def alignment_stats(alignments: torch.Tensor, mel_lengths: Optional[torch.Tensor] = None,
+                    token_lengths: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """Per-row statistics of attention alignments [B, T, L] (what ``Tacotron2.inference`` / ``forward`` return), each row at
+    its own ``mel_lengths[b]`` frames and ``token_lengths[b]`` tokens (None: all of them).
+
+    Returns ``positions`` int32 [B, T] (the token each frame attends most, lowest index on a tie, -1 behind the row's frames),
+    ``durations`` int32 [B, L] (frames per token), ``peaks`` fp32 [B, T], and per row: ``focus`` (mean peak weight),
+    ``monotonic``, ``max_jump``, ``covered``, ``first_pos``, ``last_pos`` (int32), ``monotonic_fraction`` =
+    monotonic / max(T_b - 1, 1) and ``coverage`` = covered / L_b (fp32; NaN for a row without tokens)."""
+    dev = _need_gpu(alignments, "alignments")
+    a = alignments.to(dtype=torch.float32).contiguous()
+    if a.dim() != 3:
+        raise ValueError(f"alignments must be [B, T, L], got {tuple(a.shape)}")
+    B, T, L = a.shape
+    ml, tl = _lengths(mel_lengths, B, dev), _lengths(token_lengths, B, dev)
+    positions = torch.empty(B, T, dtype=torch.int32, device=dev)
+    durations = torch.empty(B, L, dtype=torch.int32, device=dev)
+    peaks = torch.empty(B, T, dtype=torch.float32, device=dev)
+    ints = torch.empty(B, len(ROW_INT_NAMES), dtype=torch.int32, device=dev)
+    focus = torch.empty(B, dtype=torch.float32, device=dev)
+    _lib.check(_lib.load().gvx_alignment_stats(a.data_ptr(), _ptr(ml), _ptr(tl), B, T, L, positions.data_ptr(), durations.data_ptr(),
+                                               peaks.data_ptr(), ints.data_ptr(), focus.data_ptr(), _stream(dev)))
+    out = {"positions": positions, "durations": durations, "peaks": peaks, "focus": focus}
+    for i, name in enumerate(ROW_INT_NAMES):
+        out[name] = ints[:, i]
+    Tb = (ml.clamp(0, T) if ml is not None else torch.full((B,), T, dtype=torch.int32, device=dev)).to(torch.float32)
+    Lb = (tl.clamp(0, L) if tl is not None else torch.full((B,), L, dtype=torch.int32, device=dev)).to(torch.float32)
+    out["monotonic_fraction"] = out["monotonic"].to(torch.float32) / (Tb - 1).clamp(min=1)
+    out["coverage"] = out["covered"].to(torch.float32) / Lb
+    return out
+
+
+def dct_rows(n_mels: int, n_cepstra: int) -> np.ndarray:
+    """Rows 1 .. n_cepstra of the orthonormal DCT-II of size n_mels, float64 [n_cepstra, n_mels]:
+    P[k][m] = sqrt(2 / M) cos(pi (k + 1) (2 m + 1) / (2 M)) - the mel cepstra without the energy term."""
+    if not 1 <= n_cepstra <= n_mels - 1:
+        raise ValueError(f"n_cepstra = {n_cepstra} is outside [1, n_mels - 1 = {n_mels - 1}]")
+    k = np.arange(1, n_cepstra + 1, dtype=np.float64)[:, None]
+    m = np.arange(n_mels, dtype=np.float64)[None, :]
+    return np.sqrt(2.0 / n_mels) * np.cos(np.pi * k * (2.0 * m + 1.0) / (2.0 * n_mels))
+
+
+_dct_cache: Dict[Tuple[int, int, str], torch.Tensor] = {}
+
+
+def _dct_on(dev, n_mels: int, n_cepstra: int) -> torch.Tensor:
+    key = (n_mels, n_cepstra, str(dev))
+    if key not in _dct_cache:
+        _dct_cache[key] = torch.from_numpy(dct_rows(n_mels, n_cepstra).astype(np.float32)).to(dev)
+    return _dct_cache[key]
+
+
+def project(mel: torch.Tensor, P: torch.Tensor) -> torch.Tensor:
+    """c[b, t, k] = sum_m P[k, m] * mel[b, m, t]: [B, M, T] -> [B, T, K] for any fp32 projection P [K, M], K <= M."""
+    dev = _need_gpu(mel, "mel")
+    mel = mel.to(dtype=torch.float32).contiguous()
+    P = P.to(device=dev, dtype=torch.float32).contiguous()
+    if mel.dim() != 3 or P.dim() != 2 or P.shape[1] != mel.shape[1]:
+        raise ValueError(f"mel {tuple(mel.shape)} must be [B, M, T] and P {tuple(P.shape)} [K, M]")
+    B, M, T = mel.shape
+    out = torch.empty(B, T, P.shape[0], dtype=torch.float32, device=dev)
+    _lib.check(_lib.load().gvx_mel_project(mel.data_ptr(), B, M, T, P.data_ptr(), P.shape[0], out.data_ptr(), _stream(dev)))
+    return out
+
+
+def mel_cepstra(mel: torch.Tensor, n_cepstra: int = 13) -> torch.Tensor:
+    """Mel cepstra 1 .. n_cepstra of every frame of mel [B, n_mels, T] (log-mels, as the model produces them): fp32 [B, T, n_cepstra]."""
+    return project(mel, _dct_on(_need_gpu(mel, "mel"), mel.shape[1], n_cepstra))
+
+
+def dtw_distance(cp: torch.Tensor, cg: torch.Tensor, pred_lengths: Optional[torch.Tensor] = None,
+                 target_lengths: Optional[torch.Tensor] = None, return_accumulated: bool = False):
+    """The warp alone, on features cp [B, Tp, K] and cg [B, Tg, K]: fp32 [B] (NaN for a row without frames on either side); with
+    ``return_accumulated`` also the accumulated-cost table [B, Tp, Tg] (defined inside each row's Tp_b x Tg_b rectangle only)."""
+    dev = _need_gpu(cp, "cp")
+    cp, cg = cp.to(dtype=torch.float32).contiguous(), cg.to(device=dev, dtype=torch.float32).contiguous()
+    if cp.dim() != 3 or cg.dim() != 3 or cp.shape[0] != cg.shape[0] or cp.shape[2] != cg.shape[2]:
+        raise ValueError(f"features {tuple(cp.shape)} and {tuple(cg.shape)} must be [B, Tp, K] and [B, Tg, K]")
+    B, Tp, K = cp.shape
+    Tg = cg.shape[1]
+    pl, tl = _lengths(pred_lengths, B, dev), _lengths(target_lengths, B, dev)
+    lib = _lib.load()
+    dist = torch.empty(B, dtype=torch.float32, device=dev)
+    acc = torch.empty(B, Tp, Tg, dtype=torch.float32, device=dev) if return_accumulated else None
+    ws = torch.empty(lib.gvx_dtw_workspace_bytes(B, Tp, Tg, K), dtype=torch.uint8, device=dev)
+    _lib.check(lib.gvx_dtw_distance(cp.data_ptr(), cg.data_ptr(), _ptr(pl), _ptr(tl), B, Tp, Tg, K, dist.data_ptr(), _ptr(acc),
+                                    _ptr(ws), ws.numel(), _stream(dev)))
+    return (dist, acc) if return_accumulated else dist
+
+
+def dtw_mel_distance(mel_pred: torch.Tensor, mel_target: torch.Tensor, pred_lengths: Optional[torch.Tensor] = None,
+                     target_lengths: Optional[torch.Tensor] = None, n_cepstra: int = 13, return_accumulated: bool = False):
+    """DTW distance between the mel cepstra of mel_pred [B, M, Tp] and mel_target [B, M, Tg], each row at its own lengths:
+    accumulated cost of the best symmetric warp over (Tp_b + Tg_b), in the mels' own log units (``mcd_db`` turns it into dB)."""
+    return dtw_distance(mel_cepstra(mel_pred, n_cepstra), mel_cepstra(mel_target, n_cepstra), pred_lengths, target_lengths,
+                        return_accumulated)
+
+
+def mcd_db(dist: torch.Tensor, audio_config) -> torch.Tensor:
+    """Mel-cepstral distortion in dB of a ``dtw_mel_distance``: (10 / ln 10) * sqrt(2) * s * dist, s = ln 10 for log10-mels
+    (AudioConfig.log_func "np.log10") and 1 for natural-log mels."""
+    s = math.log(10.0) if audio_config.log_func == "np.log10" else 1.0
+    return dist * (10.0 / math.log(10.0) * math.sqrt(2.0) * s)

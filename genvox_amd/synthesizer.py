@@ -53,25 +53,48 @@ class Synthesizer:
     def _out_rate(self, sampling_rate: Optional[int]) -> int:
         return self.audio_processor.config.sampling_rate if sampling_rate is None else int(sampling_rate)
 
-    def tts(self, text: str, sampling_rate: Optional[int] = None) -> Dict[str, np.ndarray]:
+    def _diagnose(self, outputs: Dict[str, torch.Tensor], frames: Optional[torch.Tensor], token_lengths: Optional[torch.Tensor]) -> List[Dict]:
+        """Per row of a decoded batch: {"alignment_stats": {...Python numbers}, "stopped": bool}.  The statistics are computed on the
+        device from the alignments already there; what comes to the host is one small table per batch."""
+        from . import metrics
+
+        st = metrics.alignment_stats(outputs["alignments"], frames, token_lengths)
+        n = st["focus"].shape[0]
+        if frames is None:
+            frames = torch.full((n,), outputs["alignments"].shape[1], dtype=torch.int32, device=st["focus"].device)
+        stopped = frames < self.tts_model.model_config.max_decoder_steps
+        floats = torch.stack([st["focus"], st["monotonic_fraction"], st["coverage"]]).cpu().tolist()
+        ints = torch.stack([st["max_jump"], st["first_pos"], st["last_pos"], stopped.to(torch.int32)]).cpu().tolist()
+        return [{"alignment_stats": {"focus": floats[0][r], "monotonic_fraction": floats[1][r], "max_jump": ints[0][r],
+                                     "coverage": floats[2][r], "first_pos": ints[1][r], "last_pos": ints[2][r]},
+                 "stopped": bool(ints[3][r])} for r in range(n)]
+
+    def tts(self, text: str, sampling_rate: Optional[int] = None, diagnostics: bool = False) -> Dict[str, np.ndarray]:
         """``sampling_rate`` (Hz; default: the model's): the waveform is resampled on the device before it is copied to the host,
-        and ``"sampling_rate"`` of the result is the rate delivered."""
+        and ``"sampling_rate"`` of the result is the rate delivered.  ``diagnostics``: the result gains ``"alignment_stats"``
+        (focus, monotonic_fraction, max_jump, coverage, first_pos, last_pos of the sentence's alignment, as Python numbers) and
+        ``"stopped"`` (did the gate fire before max_decoder_steps?): a collapsed attention or a run-away decode shows without
+        looking at a picture.  Every other key is what it is without them."""
         tokens = self.text_processor.tokens_to_indices(self.text_processor.tokenize(text))
         tokens = torch.IntTensor(tokens).unsqueeze(0).to(self.device)
         outputs = self.tts_model.inference(inputs={"tokens": tokens})
+        extra = self._diagnose(outputs, None, None)[0] if diagnostics else {}
         mel = outputs["mel_outputs_postnet"]
         wav = self.audio_processor.convert_mel2wav_batch(mel, out_rate=sampling_rate)  # stays on the device until the end
         result = {key: val.squeeze(0).cpu().numpy() for key, val in outputs.items()}
         result["waveform"] = wav[0].cpu().numpy()
         result["sampling_rate"] = self._out_rate(sampling_rate)
+        result.update(extra)
         return result
 
-    def tts_batch(self, texts: Sequence[str], batch_size: int = 32, sampling_rate: Optional[int] = None) -> List[Dict[str, np.ndarray]]:
+    def tts_batch(self, texts: Sequence[str], batch_size: int = 32, sampling_rate: Optional[int] = None,
+                  diagnostics: bool = False) -> List[Dict[str, np.ndarray]]:
         """Many sentences per call: one dict per sentence, in input order, with the keys, dtypes and shapes ``tts(text)`` gives
         for that sentence (every row trimmed to its own frames, tokens and samples).  Sentences are decoded as padded batches of
         at most ``batch_size`` rows of similar token length (``plan_tts_batches``) and vocoded at their own lengths in one ragged
         Griffin-Lim call per batch; the mels stay on the device in between.  A batch of one sentence is exactly the ``tts`` path,
-        torch RNG draws included.  ``sampling_rate`` as in ``tts``: every row is resampled at its own sample count."""
+        torch RNG draws included.  ``sampling_rate`` as in ``tts``: every row is resampled at its own sample count.
+        ``diagnostics`` as in ``tts``: every sentence's alignment at its own frames and tokens."""
         token_lists = [self.text_processor.tokens_to_indices(self.text_processor.tokenize(t)) for t in texts]
         results: List[Dict[str, np.ndarray]] = [{} for _ in token_lists]
         for idx, tokens, lens in plan_tts_batches(token_lists, batch_size):
@@ -80,6 +103,7 @@ class Synthesizer:
                 inputs["token_lengths"] = lens.to(self.device)
             outputs = self.tts_model.inference(inputs=inputs)
             mel = outputs["mel_outputs_postnet"]
+            extras = self._diagnose(outputs, outputs.get("mel_lengths"), inputs.get("token_lengths")) if diagnostics else None
             if len(idx) > 1:
                 frames = outputs.pop("mel_lengths")
                 wav, samples = self.audio_processor.convert_mel2wav_batch(mel, mel_lengths=frames, out_rate=sampling_rate)
@@ -97,4 +121,6 @@ class Synthesizer:
                               "alignments": host["alignments"][r, :t, :n_tok].copy(),
                               "waveform": wav[r, :samples[r]].copy(),
                               "sampling_rate": self._out_rate(sampling_rate)}
+                if extras is not None:
+                    results[i].update(extras[r])
         return results

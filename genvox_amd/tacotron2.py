@@ -800,7 +800,8 @@ class Tacotron2(nn.Module):
     def eval_step(self, batch: Dict, criterion: Optional[Dict] = None, eval_outdir: Optional[str] = None) -> Dict[str, torch.Tensor]:
         """Forward + criterion under no_grad (reference: tacotron2.py:524-529): fills `loss_items_eval` with
         loss_eval / mel_loss_eval / gate_loss_eval like the reference and returns the forward outputs.  The plots the
-        reference writes to `eval_outdir` are out of scope."""
+        reference writes to `eval_outdir` are out of scope; what a person reads off them - has attention become a sharp,
+        monotonic diagonal, does free-running synthesis resemble the target - is what `eval_synthesis` gives as numbers."""
         with torch.no_grad():
             outputs = self.forward(batch)
             loss = (criterion or self.get_criterion())["loss"](batch, outputs)
@@ -808,9 +809,53 @@ class Tacotron2(nn.Module):
         self.check_status()   # the .item() calls above have synchronised: a bad token id raises here like nn.Embedding does
         return outputs
 
-    def get_eval_priority(self) -> float:
-        """Reference: tacotron2.py:550-551."""
-        return self.loss_items_eval["loss_eval"]
+    def get_eval_priority(self, kind: str = "loss") -> float:
+        """Reference: tacotron2.py:550-551 (the teacher-forced loss of the last `eval_step`).  ``kind="mcd_dtw"``: the mean DTW
+        mel-cepstral distortion of the last `eval_synthesis` instead - lower is better for both."""
+        if kind == "loss":
+            return self.loss_items_eval["loss_eval"]
+        if kind == "mcd_dtw":
+            return self.synthesis_items_eval["mcd_dtw_eval"]
+        raise ValueError(f"unknown eval priority {kind!r}: 'loss' or 'mcd_dtw'")
+
+    def eval_synthesis(self, batch: Dict, prenet_keep_masks: Optional[torch.Tensor] = None) -> Dict:
+        """Validation by synthesis: `inference` on the batch's tokens (free-running, under no_grad), then on the device the
+        statistics of every row's alignment (genvox_amd.metrics.alignment_stats) and the DTW mel-cepstral distortion of its
+        postnet mel against the batch's target mel, each row at its own lengths.  Any batch size.
+
+        Fills ``synthesis_items_eval`` with batch means - mcd_dtw_eval (dB), align_focus_eval, align_monotonic_eval,
+        align_coverage_eval, stopped_fraction_eval (rows whose gate fired before max_decoder_steps), frame_ratio_eval
+        (predicted over target frames) - from one small copy to the host, and returns the inference outputs (``mel_lengths``
+        also for a batch of one row) with the per-row device tensors ``alignment_stats`` (dict), ``dtw_distance``, ``mcd_dtw``,
+        ``stopped`` and ``frame_ratio``.  ``prenet_keep_masks``: as `inference` takes them (repeatable runs)."""
+        from . import metrics
+
+        with torch.no_grad():
+            inputs = {"tokens": batch["token_padded"], "token_lengths": batch["token_lengths"]}
+            if prenet_keep_masks is not None:
+                inputs["prenet_keep_masks"] = prenet_keep_masks
+            outputs = self.inference(inputs)
+            mel = outputs["mel_outputs_postnet"]
+            dev, B = mel.device, mel.shape[0]
+            frames = outputs.get("mel_lengths")
+            if frames is None:
+                frames = torch.full((B,), mel.shape[2], dtype=torch.int32, device=dev)
+            target_frames = batch["mel_lengths"].to(device=dev, dtype=torch.int32)
+            stats = metrics.alignment_stats(outputs["alignments"], frames, batch["token_lengths"])
+            dist = metrics.dtw_mel_distance(mel, batch["mel_padded"].to(dev), frames, target_frames)
+            mcd = metrics.mcd_db(dist, self.audio_config)
+            stopped = frames < self.model_config.max_decoder_steps
+            ratio = frames.to(torch.float32) / target_frames.to(torch.float32)
+            rows = torch.stack([mcd, stats["focus"], stats["monotonic_fraction"], stats["coverage"], stopped.to(torch.float32), ratio])
+            means = rows.mean(dim=1).cpu().tolist()
+        names = ("mcd_dtw", "align_focus", "align_monotonic", "align_coverage", "stopped_fraction", "frame_ratio")
+        self.synthesis_items_eval = {name + "_eval": val for name, val in zip(names, means)}
+        return {**outputs, "mel_lengths": frames, "alignment_stats": stats, "dtw_distance": dist, "mcd_dtw": mcd, "stopped": stopped,
+                "frame_ratio": ratio}
+
+    def get_synthesis_logs(self) -> Dict:
+        """The batch means of the last `eval_synthesis`."""
+        return dict(self.synthesis_items_eval)
 
 
 def Tacotron2Loss(batch: Dict[str, torch.Tensor], outputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:

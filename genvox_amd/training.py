@@ -525,3 +525,40 @@ class Adam:
                                                 float(self.betas[1]), float(self.eps), self.step_count, torch.cuda.current_stream(dev).cuda_stream))
         # the parameters changed through raw pointers: the packed blob of the forward kernels is stale
         self.model._packed_key = None
+
+    def state_dict(self) -> Dict:
+        """torch.optim.Adam's layout, so that a checkpoint moves both ways between the reference's optimizer and this one:
+        ``state[i]`` = {"step", "exp_avg", "exp_avg_sq"} with i in ``model.parameters()`` order (empty before the first step; the
+        moments are this optimizer's own tensors, not copies), one parameter group over all of them."""
+        names = [name for name, _ in self.model.named_parameters()]
+        state = {i: {"step": torch.tensor(float(self.step_count)), "exp_avg": self.state[name][0], "exp_avg_sq": self.state[name][1]}
+                 for i, name in enumerate(names) if name in self.state}
+        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.wd, "amsgrad": False, "maximize": False,
+                 "foreach": None, "capturable": False, "differentiable": False, "fused": None, "decoupled_weight_decay": False,
+                 "params": list(range(len(names)))}
+        return {"state": state, "param_groups": [group]}
+
+    def load_state_dict(self, state_dict: Dict) -> None:
+        """Accepts what ``state_dict()`` or ``torch.optim.Adam.state_dict()`` wrote for the same parameters: the moments are copied
+        to each parameter's device, ``step`` may be a tensor or a number.  This optimizer counts one step for all parameters and
+        implements neither amsgrad nor maximize: a dict that says otherwise is refused."""
+        params = list(self.model.named_parameters())
+        groups = state_dict["param_groups"]
+        if len(groups) != 1 or list(groups[0]["params"]) != list(range(len(params))):
+            raise ValueError(f"expected one parameter group over parameters 0 .. {len(params) - 1} in model.parameters() order")
+        g = groups[0]
+        if g.get("amsgrad") or g.get("maximize") or g.get("decoupled_weight_decay"):
+            raise ValueError("genvox_amd.training.Adam implements neither amsgrad, maximize nor decoupled weight decay")
+        new_state, steps = {}, set()
+        for i, st in state_dict["state"].items():
+            name, p = params[int(i)]
+            m, v = st["exp_avg"], st["exp_avg_sq"]
+            if m.shape != p.shape or v.shape != p.shape:
+                raise ValueError(f"state {i} has shapes {tuple(m.shape)}, {tuple(v.shape)} for parameter {name} of shape {tuple(p.shape)}")
+            new_state[name] = (m.detach().to(device=p.device, dtype=p.dtype, copy=True).contiguous(),
+                               v.detach().to(device=p.device, dtype=p.dtype, copy=True).contiguous())
+            steps.add(int(st["step"]))
+        if len(steps) > 1:
+            raise ValueError(f"parameters at different step counts ({sorted(steps)}): this optimizer keeps one count for all")
+        self.lr, self.betas, self.eps, self.wd = float(g["lr"]), tuple(g["betas"]), float(g["eps"]), float(g["weight_decay"])
+        self.state, self.step_count = new_state, (steps.pop() if steps else 0)

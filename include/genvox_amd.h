@@ -529,6 +529,68 @@ int gvx_wav_mixdown(const void* pcm, int pcm_kind, int B, long n_max, int channe
 int gvx_wav_resample_ragged(const void* pcm, int pcm_kind, int B, long n_max, const int32_t* bounds, int up, int down,
                             const void* table, int taps_per_phase, void* out, long n_out_stride, int32_t* out_lengths, void* stream);
 
+/* ---- Evaluation by synthesis: has the model learned to speak?  Two device computations over what the model already leaves on the
+ * device (inference: alignments [B][T][L], mel_lengths, padded mels; the batch: target mels and lengths).  Asynchronous on `stream`,
+ * caller-allocated outputs, the same bits every run.  Lengths are DEVICE int32 [B], NULL for "every row is full", and are clamped to
+ * their range on the device like the ragged vocoder's; nothing behind a row's lengths is read, whatever it holds.
+ *
+ * Alignment statistics.  alignments is fp32 [B][T][L], dense; T_b = mel_lengths[b] clamped to [0, T], L_b = token_lengths[b] clamped
+ * to [0, L].  Per frame t < T_b: peak[t] = max over l < L_b of a[b][t][l] and pos[t] = the LOWEST l that attains it - comparisons of
+ * the given values, no arithmetic, so pos is exact.  A NaN never wins a comparison: NaN entries are passed over, and a frame that
+ * holds nothing but NaNs yields pos = 0 and peak = NaN (so the row's focus is NaN; its integers stay defined).  Infinities compare
+ * as numbers.  Outputs:
+ *     positions_out  int32 [B][T]   pos[t]; -1 for t >= T_b
+ *     durations_out  int32 [B][L]   #{t < T_b : pos[t] == l}, the frames-per-token table; 0 for l >= L_b
+ *     peaks_out      fp32  [B][T]   peak[t]; 0 for t >= T_b
+ *     row_ints_out   int32 [B][GVX_ALIGN_ROW_INTS]:
+ *         [GVX_ALIGN_MONOTONIC]  #{1 <= t < T_b : pos[t] >= pos[t-1]}
+ *         [GVX_ALIGN_MAX_JUMP]   max over 1 <= t < T_b of |pos[t] - pos[t-1]|, 0 if T_b <= 1
+ *         [GVX_ALIGN_COVERED]    #{l < L_b : durations[b][l] > 0}
+ *         [GVX_ALIGN_FIRST_POS], [GVX_ALIGN_LAST_POS]   pos[0], pos[T_b - 1]
+ *     focus_out      fp32  [B]      (sum over t < T_b of peak[t]) / T_b.  The sum has a fixed order: 256 partial sums, number i over
+ *                                   the frames i, i + 256, ... in ascending order, then added pairwise at strides 128, 64, ..., 1.
+ * A row with T_b == 0 or L_b == 0: its integers 0, its positions -1, its peaks 0, its focus NaN.  Two launches. */
+enum { GVX_ALIGN_MONOTONIC = 0, GVX_ALIGN_MAX_JUMP = 1, GVX_ALIGN_COVERED = 2, GVX_ALIGN_FIRST_POS = 3, GVX_ALIGN_LAST_POS = 4,
+       GVX_ALIGN_ROW_INTS = 5 };
+int gvx_alignment_stats(const float* alignments, const int32_t* mel_lengths, const int32_t* token_lengths, int B, int T, int L,
+                        int32_t* positions_out, int32_t* durations_out, float* peaks_out, int32_t* row_ints_out, float* focus_out,
+                        void* stream);
+
+/* Features of the warp: out[b][t][k] = sum over m = 0 .. M-1, in ascending m, one fused multiply-add per term, of
+ * P[k][m] * mel[b][m][t] - from the [B][M][T] layout the model produces to the [B][T][K] layout the warp reads.  P is any fp32
+ * [K][M], 1 <= K <= M (genvox_amd/metrics.py passes rows 1 .. K of the orthonormal DCT-II of size M: mel cepstra without the energy
+ * term).  Every frame is projected on its own, so what lies behind a row's length stays behind it.  A P beyond the kernel's LDS tile
+ * (K * (M + 1) + 64 * M floats above 160 KiB) is GVX_ERR_UNSUPPORTED. */
+int gvx_mel_project(const float* mel, int B, int M, int T, const float* P, int K, float* out, void* stream);
+
+/* Distance under dynamic time warping.  cp is fp32 [B][Tp_max][K], cg fp32 [B][Tg_max][K].  For row b with
+ * Tp = pred_lengths[b] (clamped to [0, Tp_max]) frames of cp and Tg = target_lengths[b] (clamped to [0, Tg_max]) frames of cg:
+ *
+ *     d(i, j) = sqrt( sum over k, in ascending k, of (cp[i][k] - cg[j][k])^2 )       (each term one fused multiply-add)
+ *     A[0][0] = 2 d(0, 0)
+ *     A[i][0] = A[i-1][0] + d(i, 0)             A[0][j] = A[0][j-1] + d(0, j)
+ *     A[i][j] = min( A[i-1][j] + d(i, j),  A[i][j-1] + d(i, j),  A[i-1][j-1] + 2 d(i, j) )
+ *     dist_out[b] = A[Tp-1][Tg-1] / (Tp + Tg)
+ *
+ * the symmetric step pattern, whose normaliser Tp + Tg does not depend on the path taken (a mean over the path jumps where two
+ * branches tie to within rounding; this form is continuous in its inputs).  Tp == 0 or Tg == 0: dist_out[b] = NaN.  acc_out, fp32
+ * [B][Tp_max][Tg_max] or NULL, receives A[i][j] for i < Tp, j < Tg and is not touched elsewhere; dist_out has the same bits with
+ * and without it.  fp32 throughout.
+ *
+ * One workgroup per row walks the Tp + Tg - 1 anti-diagonals with one barrier each; no workgroup waits for another, and every
+ * loop is bounded by Tp + Tg.  When both feature tables and three diagonals fit a CU's LDS
+ * (3 * Tp_max + (Tp_max + Tg_max) * (K | 1) floats within 160 KiB; 1000 x 1000 frames of 13 features do) they live there and the
+ * call needs no workspace: the size function returns 0 and workspace may be NULL.  Otherwise the features are read through the
+ * cache and the diagonals live in the workspace (256-byte aligned, sized by the function below).  The uses_lds_tables query says which
+ * (1 / 0; -1 for a shape the call would refuse).  Frames above GVX_DTW_MAX_FRAMES or K above GVX_DTW_MAX_FEATURES:
+ * GVX_ERR_UNSUPPORTED (the size function then returns 0); a NULL cp, cg or dist_out, or B, Tp_max, Tg_max or K below 1:
+ * GVX_ERR_INVALID_ARG; a missing or short workspace: GVX_ERR_WORKSPACE; all of it checked before anything is launched. */
+enum { GVX_DTW_MAX_FRAMES = 32768, GVX_DTW_MAX_FEATURES = 256 };
+size_t gvx_dtw_workspace_bytes(int B, int Tp_max, int Tg_max, int K);
+int gvx_dtw_uses_lds_tables(int Tp_max, int Tg_max, int K);
+int gvx_dtw_distance(const float* cp, const float* cg, const int32_t* pred_lengths, const int32_t* target_lengths, int B, int Tp_max,
+                     int Tg_max, int K, float* dist_out, float* acc_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Per-kernel timing of the decoder step (measurement only): when enabled, a teacher-forced call replays the
  * mid-sequence LSTM-step launch and the attention launches 64 times each, back to back, between HIP events on
  * `stream` (after its loop; the call's outputs are not valid afterwards); gvx_kernel_times_ms synchronises and

@@ -4,7 +4,10 @@ teacher-forced at B=64, autoregressive RTF (B=64, 1000 steps), Postnet-only MFMA
 `glr` (on request): the ragged Griffin-Lim call against the same rows padded through the uniform call;
 `w2mr` (on request): 64 recordings of 2-10 s through one ragged wav -> mel call against 64 single-row `wav_to_mel` calls;
 `w2m48` (on request): 32 recordings of 10 s at 48 kHz through `convert_wav2mel_batch` (resampled on the device) against the same
-batch delivered at the model's rate."""
+batch delivered at the model's rate;
+`dtw` / `align` (on request): the evaluation metrics' C-ABI calls alone between device events - gvx_dtw_distance on 32 rows of
+1000 x 1000 and 800 x 800 frames of 13 cepstra (and 1000 x 1000 of 80 features, the form without LDS tables), gvx_alignment_stats
+on 32 x 1000 x 128 - and the Python entry points around them by the host clock."""
 import json
 import os
 import sys
@@ -194,6 +197,68 @@ def main():
             "at_48k_resampled_on_device": foreign, "at_model_rate": native, "resample_kernel_alone_device_batch": alone,
             "cost_ratio": round(foreign["median_ms"] / native["median_ms"], 2), "outputs": outputs, "taps_per_phase": taps,
             "resample_gflop": round(2e-9 * outputs * taps, 2)}
+    if which & {"dtw", "align"}:
+        import statistics
+
+        from genvox_amd import _lib, metrics
+
+        lib = _lib.load()
+        stream = torch.cuda.current_stream().cuda_stream
+
+        def event_runs(fn, warm=3, reps=20):   # one C-ABI call per run, between device events: its launches and nothing else
+            for _ in range(warm):
+                fn()
+            out = []
+            for _ in range(reps):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                e1.synchronize()
+                out.append(e0.elapsed_time(e1))
+            return {"median_ms": round(statistics.median(out), 3), "min_ms": round(min(out), 3), "max_ms": round(max(out), 3), "runs": reps}
+
+        def host_runs(fn, warm=2, reps=7):
+            for _ in range(warm):
+                fn()
+            out = []
+            for _ in range(reps):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                out.append((time.perf_counter() - t0) * 1e3)
+            return {"median_ms": round(statistics.median(out), 3), "min_ms": round(min(out), 3), "max_ms": round(max(out), 3), "runs": reps}
+
+        gen = torch.Generator(device="cuda").manual_seed(0)
+    if "dtw" in which:
+        B = 32
+        for Tp, Tg, K in ((1000, 1000, 13), (800, 800, 13), (1000, 1000, 80)):
+            # random walks: neighbouring frames are close, as cepstra of speech are
+            cp = torch.randn(B, Tp, K, device="cuda", generator=gen).mul_(0.3).cumsum(dim=1).contiguous()
+            cg = torch.randn(B, Tg, K, device="cuda", generator=gen).mul_(0.3).cumsum(dim=1).contiguous()
+            dist = torch.empty(B, device="cuda")
+            ws = torch.empty(lib.gvx_dtw_workspace_bytes(B, Tp, Tg, K), dtype=torch.uint8, device="cuda")
+            call = lambda: _lib.check(lib.gvx_dtw_distance(cp.data_ptr(), cg.data_ptr(), None, None, B, Tp, Tg, K, dist.data_ptr(), None,
+                                                           ws.data_ptr() if ws.numel() else None, ws.numel(), stream))
+            r = event_runs(call)
+            r.update(lds_tables=lib.gvx_dtw_uses_lds_tables(Tp, Tg, K), cells=B * Tp * Tg, finite=bool(torch.isfinite(dist).all()))
+            res[f"gvx_dtw_distance_b32_{Tp}x{Tg}_k{K}"] = r
+        mel_p = torch.randn(B, 80, 1000, device="cuda", generator=gen).mul_(0.2).cumsum(dim=2)
+        mel_g = torch.randn(B, 80, 1000, device="cuda", generator=gen).mul_(0.2).cumsum(dim=2)
+        res["dtw_mel_distance_b32_1000x1000_with_projection"] = host_runs(lambda: metrics.dtw_mel_distance(mel_p, mel_g))
+    if "align" in which:
+        B, T, L = 32, 1000, 128
+        a = torch.softmax(torch.randn(B, T, L, device="cuda", generator=gen) * 4.0, dim=-1).contiguous()
+        pos, dur = torch.empty(B, T, dtype=torch.int32, device="cuda"), torch.empty(B, L, dtype=torch.int32, device="cuda")
+        peaks, ints, focus = torch.empty(B, T, device="cuda"), torch.empty(B, 5, dtype=torch.int32, device="cuda"), torch.empty(B, device="cuda")
+        call = lambda: _lib.check(lib.gvx_alignment_stats(a.data_ptr(), None, None, B, T, L, pos.data_ptr(), dur.data_ptr(), peaks.data_ptr(),
+                                                          ints.data_ptr(), focus.data_ptr(), stream))
+        r = event_runs(call)
+        r.update(input_mb=round(a.numel() * 4 / 1e6, 1), gb_per_s=None)
+        r["gb_per_s"] = round(a.numel() * 4 / 1e9 / (r["median_ms"] * 1e-3), 1)
+        res[f"gvx_alignment_stats_b{B}_{T}x{L}"] = r
+        res[f"alignment_stats_python_b{B}_{T}x{L}"] = host_runs(lambda: metrics.alignment_stats(a))
     if "cpu" in which:
         # CPU baselines for configs 3 and 4 (the oracle = CPU restatement of the reference, on this box's host cores):
         # bounded samples, reported beside the GPU figures above; bench.py carries the one for config 2.
