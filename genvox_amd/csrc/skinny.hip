@@ -884,7 +884,7 @@ __global__ __launch_bounds__(SK_THREADS, 4) void ar_attn_tiles_kernel(SkinnyJobs
 }
 // autoregressive launch C beside the resident attention kernel: the context of the step arrives inside the launch (deferred segment)
 __global__ __launch_bounds__(SK_THREADS) void ar_lstm_defer_kernel(SkinnyJobs jobs) { skinny_body<1, SK_DEPTH1, false, true>(jobs); }
-// training step, back-propagation through the decoder loop: dgates x transposed recurrent matrices as partial sums (mode 2 jobs, train.hip)
+// training step, back-propagation through the decoder loop: dgates x transposed recurrent matrices as partial sums (mode 2 jobs, train_bptt_decoder.hip)
 __global__ __launch_bounds__(SK_THREADS) void train_bptt_products_kernel(SkinnyJobs jobs) { skinny_body<1, SK_DEPTH1>(jobs); }
 template <int MT> __global__ __launch_bounds__(SK_THREADS) void encoder_lstm_step_kernel(SkinnyJobs jobs) { skinny_body<MT, (MT == 1 ? SK_DEPTH1 : SK_DEPTH2)>(jobs); }
 

@@ -103,6 +103,8 @@ class Tacotron2(nn.Module):
         self._sticky_bad = False        # host-side copies of the device status words (a replaced workspace takes its words with it)
         self._sticky_stalled = False
         self._resident_off = False      # a hand-off timed out once: this model runs on the launch-per-step kernels from then on
+        self._enc_bptt_resident = True  # train_step clears it after a time-out of the resident encoder-BiLSTM backward; training.py picks the walk by it
+        self._enc_bptt_workspaces = []  # training.train_backward files one per chunk; training.encoder_bptt_timed_out reads their status words
         self.eval()
 
     # child() for the root, which is not a _Node
@@ -771,7 +773,6 @@ class Tacotron2(nn.Module):
             # (a token id outside the table raised before the forward touched anything; a hand-off time-out was caught - and the
             # recurrent part re-run - before the Postnet's BatchNorm update; this is the last look before gradients reach the weights)
             self.check_status()
-            self._enc_bptt_workspaces = []
             grads = training.train_backward(self, batch, outputs, tape)
             self.grad_norm_val, scale = training.clip_grad_norm(grads, self.model_config.grad_clip_thresh)
             if not math.isfinite(self.grad_norm_val) and training.encoder_bptt_timed_out(self):

@@ -6,8 +6,8 @@ There is no autograd here.  The forward (``Tacotron2._forward_train``) records a
 backwards in explicit formulas - criterion, Postnet, projections, BPTT over the decoder loop (both LSTM cells with their
 output dropout, the location-sensitive attention with its previous / cumulative-weights path), Prenet, encoder BiLSTM with
 packed-sequence semantics, encoder convolutions, embedding - exactly as ``oracle/train_ref.py`` states them, and every
-formula runs in a HIP kernel behind the C ABI (csrc/train.hip: ``gvx_conv_bn_act_train_*``, ``gvx_train_*``; the dense
-products on the exact-fp32 MFMA GEMM of the forward path).  The two recurrences are one C-ABI call each
+formula runs in a HIP kernel behind the C ABI (csrc/train_conv.hip: ``gvx_conv_bn_act_train_*``; csrc/train_ops.hip and the
+two csrc/train_bptt_*.hip: ``gvx_train_*``; the dense products on the exact-fp32 MFMA GEMM of the forward path).  The two recurrences are one C-ABI call each
 (``gvx_train_decoder_bptt``: three launches per decoder step, ``gvx_train_encoder_lstm_bptt``: one per time step); torch
 allocates, slices and reshapes around them.  Parameters are updated in
 place in the reference's own layouts (``Adam``); the packed blob of the forward kernels is re-built before the next forward.
@@ -23,7 +23,7 @@ from __future__ import annotations
 import contextlib
 import os
 import ctypes as C
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -160,7 +160,8 @@ def postnet_train_step_slice(model, decoder_mel: torch.Tensor, batch: Dict[str, 
 # =====================================================================================================================
 # The whole backward of the training step (loss.backward() of the reference, models/tts/tacotron2.py:519): host side.
 # Walks the decoder loop and the encoder BiLSTM backwards exactly as oracle/train_ref.py::train_backward states it; every
-# formula runs in a HIP kernel behind the C ABI (csrc/train.hip: gvx_train_*), torch only allocates, slices and reshapes.
+# formula runs in a HIP kernel behind the C ABI (csrc/train_ops.hip, csrc/train_bptt_*.hip: gvx_train_*), torch only allocates,
+# slices and reshapes.
 # =====================================================================================================================
 class _Ops:
     """Thin wrappers over the gvx_train_* primitives (row-major fp32 tensors whose last stride is 1)."""
@@ -262,58 +263,69 @@ def _accumulate(ops: "_Ops", total: Dict[str, torch.Tensor], part: Dict[str, tor
             total[k] = v.contiguous()
 
 
-def _recurrent_backward(model, ops: "_Ops", ch: dict, dmel: torch.Tensor, dgate: torch.Tensor, x: torch.Tensor, align: torch.Tensor
-                        ) -> Tuple[Dict[str, torch.Tensor], torch.Tensor]:
-    """The part of the backward that never mixes batch rows, for one chunk of at most 32 rows: projection, decoder loop
-    (gvx_train_decoder_bptt), Prenet, memory layer, encoder BiLSTM (gvx_train_encoder_lstm_bptt).  dmel [Bc, M, T] and dgate
-    [Bc, T] are d loss / d of the decoder's mel / gate outputs, x [Bc, L, E] the BiLSTM's input, align [Bc, T, L] the
-    alignments.  Returns (parameter gradients of this chunk's rows, d loss / d x as [Bc * L, E])."""
-    mc = model.model_config
-    dev = dmel.device
-    lib, st = ops.lib, ops.st
-    P_ = dict(model.named_parameters())
-    W = lambda name: P_[name].data
-    att = "decoder.attention_layer."
+class _LoopBptt(NamedTuple):
+    """What gvx_train_decoder_bptt wrote for one chunk (rows (t, b) of T steps), and the inputs of the two cells at every step,
+    which the weight gradients of the loop read again."""
+    dga_all: torch.Tensor    # [T, B, 4A]  gate gradients of the attention cell
+    dgd_all: torch.Tensor    # [T, B, 4D]  ... of the decoder cell
+    dq_all: torch.Tensor     # [T, B, a]   d loss / d query
+    dctx_all: torch.Tensor   # [T, B, E]   d loss / d ctx(t)
+    dpm: torch.Tensor        # [B, L, a]   d loss / d processed memory
+    dmemory: torch.Tensor    # [B, L, E]   context path of the memory gradient
+    dv: torch.Tensor         # [a]
+    dld: torch.Tensor        # [a, F]      location_dense
+    dlw: torch.Tensor        # [F, 2, kl]  location_conv
+    xa: torch.Tensor         # [T B, P+E]  [p2(t) ; ctx(t-1)]
+    ha_prev: torch.Tensor    # [T B, A]    h_a(t-1)
+    xd: torch.Tensor         # [T B, A+E]  [h_a(t) ; ctx(t)]
+    hd_prev: torch.Tensor    # [T B, D]    h_d(t-1)
+
+
+def _projection_backward(ops: "_Ops", W, ch: dict, dmel: torch.Tensor, dgate: torch.Tensor) -> Tuple[Dict[str, torch.Tensor], torch.Tensor]:
+    """Mel / gate projection of one chunk, rows (t, b): [dmel | dgate | 0-pad] [T B, Mp] x [Wp ; Wg].  Returns (gradients of both
+    layers, dhc_all [T, B, D+E] = d loss / d [h_d(t) ; ctx(t)] through the projection)."""
     B, M, T = dmel.shape
-    L = x.shape[1]
-    A, D, E, Pn, a = mc.attention_rnn_dim, mc.decoder_rnn_dim, mc.encoder_embedding_dim, mc.prenet_dim, mc.attention_dim
-    F_, kl = mc.attention_location_n_filters, mc.attention_location_kernel_size
     g: Dict[str, torch.Tensor] = {}
-    # ---- projection: rows (t, b); [dmel | dgate | 0-pad] [T B, Mp] x [Wp ; Wg]
     Mp = -(-(M + 1) // 4) * 4
     dmg = ops.zeros(T * B, Mp)
     dmg[:, :M] = dmel.permute(2, 0, 1).reshape(T * B, M)          # (torch: layout plumbing only)
     dmg[:, M] = dgate.t().reshape(T * B)
     hc = ch["hc_all"]                                             # [T+1, B, D+E] rows: slot t + 1 = [h_d(t) ; ctx(t)]
-    hc_t = hc[1:].reshape(T * B, D + E)
-    Wpg = ops.zeros(Mp, D + E)
+    DE = hc.shape[2]
+    hc_t = hc[1:].reshape(T * B, DE)
+    Wpg = ops.zeros(Mp, DE)
     Wpg[:M] = W("decoder.linear_projection.linear_layer.weight")
     Wpg[M] = W("decoder.gate_layer.linear_layer.weight")[0]
     dWpg = ops.mm_tn(dmg, hc_t)                                   # [Mp, D+E]
     g["decoder.linear_projection.linear_layer.weight"], g["decoder.gate_layer.linear_layer.weight"] = dWpg[:M].contiguous(), dWpg[M:M + 1].contiguous()
     db = ops.colsum(dmg)
     g["decoder.linear_projection.linear_layer.bias"], g["decoder.gate_layer.linear_layer.bias"] = db[:M].contiguous(), db[M:M + 1].contiguous()
-    dhc_all = ops.gemm_nt(dmg, ops.transpose(Wpg)).reshape(T, B, D + E)       # d loss / d [h_d(t) ; ctx(t)] through the projection
+    return g, ops.gemm_nt(dmg, ops.transpose(Wpg)).reshape(T, B, DE)
 
+
+def _decoder_bptt(mc, ops: "_Ops", W, ch: dict, dhc_all: torch.Tensor, align: torch.Tensor) -> _LoopBptt:
+    """Back-propagation through the decoder loop of one chunk: one C-ABI call (three launches per step,
+    csrc/train_bptt_decoder.hip).  align [B, T, L] are the alignments."""
+    dev = dhc_all.device
+    lib = ops.lib
+    att = "decoder.attention_layer."
+    T, B = dhc_all.shape[:2]
+    L = align.shape[2]
+    A, D, E, Pn, a = mc.attention_rnn_dim, mc.decoder_rnn_dim, mc.encoder_embedding_dim, mc.prenet_dim, mc.attention_dim
+    F_, kl = mc.attention_location_n_filters, mc.attention_location_kernel_size
     # ---- operands of the weight gradients (inputs of both cells at every step) and the attention queries
+    hc = ch["hc_all"]                                             # [T+1, B, D+E] rows: slot t + 1 = [h_d(t) ; ctx(t)]
     p2 = ch["p2"]                                                 # [T+1, B, P]
     ha = ch["h_a_all"]                                            # [T+1, B, A]  slot t + 1 = dropped h_a(t)
     ctx_prev = hc[:T, :, D:]                                      # ctx(t-1), slot t
     xa = torch.cat((p2[:T], ctx_prev), dim=2).reshape(T * B, Pn + E).contiguous()
     ha_prev = ha[:T].reshape(T * B, A)
-    Wia, Wha = W("decoder.attention_rnn.weight_ih"), W("decoder.attention_rnn.weight_hh")
-    Wid, Whd = W("decoder.decoder_rnn.weight_ih"), W("decoder.decoder_rnn.weight_hh")
     xd = torch.cat((ha[1:], hc[1:, :, D:]), dim=2).reshape(T * B, A + E).contiguous()   # [h_a(t) ; ctx(t)]
     hd_prev = hc[:T, :, :D].reshape(T * B, D).contiguous()
-    pre_a, pre_d = ch["pre_a"], ch["pre_d"]                       # [T, B, H, 4]: the gate pre-activations the forward computed
-    wq, v = W(att + "query_layer.linear_layer.weight"), W(att + "v.linear_layer.weight")
-    lw, ld = W(att + "location_layer.location_conv.conv.weight").contiguous(), W(att + "location_layer.location_dense.linear_layer.weight")
-    wm = W(att + "memory_layer.linear_layer.weight")
+    wq = W(att + "query_layer.linear_layer.weight")
     q_all = ops.gemm_nt(ha[1:].reshape(T * B, A), wq).reshape(T, B, a)
-    memory, pm = ch["memory"], ch["pm"]
     w_all = align.permute(1, 0, 2).contiguous()                   # [T, B, L]
-    c_a, c_d = ch["c_a_all"], ch["c_d_all"]                       # [T+1, B, H]
-    # ---- back-propagation through the decoder loop: one C-ABI call (three launches per step, csrc/train.hip)
+    # ---- outputs, the argument block, the call
     dga_all, dgd_all = ops.new(T, B, 4 * A), ops.new(T, B, 4 * D)
     dq_all, dctx_all = ops.new(T, B, a), ops.new(T, B, E)
     dpm, dmemory = ops.new(B, L, a), ops.new(B, L, E)
@@ -326,68 +338,76 @@ def _recurrent_backward(model, ops: "_Ops", ch: dict, dmel: torch.Tensor, dgate:
         t = t.contiguous()
         keep.append(t)
         return t.data_ptr()
-    ba_.dhc_all, ba_.pre_a, ba_.pre_d = ptr(dhc_all), ptr(pre_a), ptr(pre_d)
-    ba_.c_a_all, ba_.c_d_all = ptr(c_a), ptr(c_d)
+    ba_.dhc_all, ba_.pre_a, ba_.pre_d = ptr(dhc_all), ptr(ch["pre_a"]), ptr(ch["pre_d"])   # pre_*: [T, B, H, 4] gate pre-activations of the forward
+    ba_.c_a_all, ba_.c_d_all = ptr(ch["c_a_all"]), ptr(ch["c_d_all"])                       # [T+1, B, H]
     ba_.att_keep, ba_.dec_keep, ba_.q_all = ptr(ch["att_keep"]), ptr(ch["dec_keep"]), ptr(q_all)
     ba_.ctx_all = hc.data_ptr() + 4 * (B * (D + E) + D)          # ctx(t) = hc[t + 1, b, D:]
     ba_.ctx_ts, ba_.ctx_bs = B * (D + E), D + E
-    ba_.w_all, ba_.memory, ba_.pm = ptr(w_all), ptr(memory), ptr(pm)
-    ba_.w_ih_a, ba_.w_hh_a, ba_.w_ih_d, ba_.w_hh_d = ptr(Wia), ptr(Wha), ptr(Wid), ptr(Whd)
-    ba_.wq, ba_.v, ba_.loc_conv, ba_.loc_dense = ptr(wq), ptr(v), ptr(lw), ptr(ld)
+    ba_.w_all, ba_.memory, ba_.pm = ptr(w_all), ptr(ch["memory"]), ptr(ch["pm"])
+    ba_.w_ih_a, ba_.w_hh_a = ptr(W("decoder.attention_rnn.weight_ih")), ptr(W("decoder.attention_rnn.weight_hh"))
+    ba_.w_ih_d, ba_.w_hh_d = ptr(W("decoder.decoder_rnn.weight_ih")), ptr(W("decoder.decoder_rnn.weight_hh"))
+    ba_.wq, ba_.v = ptr(wq), ptr(W(att + "v.linear_layer.weight"))
+    ba_.loc_conv, ba_.loc_dense = ptr(W(att + "location_layer.location_conv.conv.weight")), ptr(W(att + "location_layer.location_dense.linear_layer.weight"))
     ba_.dga_all, ba_.dgd_all, ba_.dq_all, ba_.dctx_all = dga_all.data_ptr(), dgd_all.data_ptr(), dq_all.data_ptr(), dctx_all.data_ptr()
     ba_.dpm, ba_.dmemory, ba_.dv, ba_.dloc_dense, ba_.dloc_conv = dpm.data_ptr(), dmemory.data_ptr(), dv.data_ptr(), dld.data_ptr(), dlw.data_ptr()
     wsb = lib.gvx_train_decoder_bptt_workspace_bytes(C.byref(ba_))
     if wsb == 0:
         _lib.check(1)
     ws_bptt = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    _lib.check(lib.gvx_train_decoder_bptt(C.byref(ba_), ws_bptt.data_ptr(), wsb, st))
-    # ---- Off the chain to the encoder: the loop's weight gradients and the whole Prenet backward (dense products, ~5 ms at
-    # 32 x 200 frames) go to a second stream; the caller's stream goes on with the memory gradient and the encoder's BiLSTM walk
-    # (a launch per position on a quarter of the chip) and waits for them at the end.  One fork and one join per chunk (an edge
-    # costs ~5 us: tools/micro/chain_sidestream_bench.hip); every tensor is produced by the same launches in the same order as on
-    # one stream, so results do not change.  GVX_TRAIN_SIDE_STREAM=0: everything on the caller's stream.
-    main_stream = torch.cuda.current_stream(dev)
-    side = _side_stream(dev)
-    if side is not None:
-        fork = torch.cuda.Event(); fork.record(main_stream)
-        side.wait_event(fork)
-    with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
-        ops_s = _side_ops(dev) if side is not None else ops
-        st_s = ops_s.st
-        dpm2 = dpm.reshape(B * L, a)
-        # the Prenet columns of the attention LSTM are not on the recurrence: one product over all steps
-        dp2 = ops_s.zeros(T + 1, B, Pn)
-        ops_s.gemm_nt(dga_all.reshape(T * B, 4 * A), ops_s.transpose(Wia)[:Pn], out=dp2[:T].reshape(T * B, Pn))
-        # ---- weight gradients of the loop, one product over all (t, b) rows each
-        dga2, dgd2 = dga_all.reshape(T * B, 4 * A), dgd_all.reshape(T * B, 4 * D)
-        g["decoder.attention_rnn.weight_ih"], g["decoder.attention_rnn.weight_hh"] = ops_s.mm_tn(dga2, xa), ops_s.mm_tn(dga2, ha_prev.contiguous())
-        g["decoder.attention_rnn.bias_ih"] = ops_s.colsum(dga2)
-        g["decoder.attention_rnn.bias_hh"] = g["decoder.attention_rnn.bias_ih"].clone()
-        g["decoder.decoder_rnn.weight_ih"], g["decoder.decoder_rnn.weight_hh"] = ops_s.mm_tn(dgd2, xd), ops_s.mm_tn(dgd2, hd_prev)
-        g["decoder.decoder_rnn.bias_ih"] = ops_s.colsum(dgd2)
-        g["decoder.decoder_rnn.bias_hh"] = g["decoder.decoder_rnn.bias_ih"].clone()
-        g[att + "query_layer.linear_layer.weight"] = ops_s.mm_tn(dq_all.reshape(T * B, a), ha[1:].reshape(T * B, A).contiguous())
-        g[att + "v.linear_layer.weight"] = dv[None, :]
-        g[att + "location_layer.location_dense.linear_layer.weight"] = dld
-        g[att + "location_layer.location_conv.conv.weight"] = dlw
-        g[att + "memory_layer.linear_layer.weight"] = ops_s.mm_tn(dpm2, memory.reshape(B * L, E))
-        # ---- Prenet (relu then dropout, twice; models/tts/tacotron2.py:140-144)
-        pk = ch["prenet_keep"]                                        # [2, T+1, B, P] uint8
-        p1 = ch["p1"]
-        w1 = W("decoder.prenet.layers.1.linear_layer.weight")
-        n_rows = (T + 1) * B
-        dz2 = ops_s.new(n_rows, Pn)
-        _lib.check(lib.gvx_train_relu_dropout_backward(_p(dp2), _p(p2.contiguous()), _p(pk[1].contiguous()), 2.0, n_rows * Pn, _p(dz2), st_s))
-        g["decoder.prenet.layers.1.linear_layer.weight"] = ops_s.mm_tn(dz2, p1.reshape(n_rows, Pn).contiguous())
-        dp1 = ops_s.gemm_nt(dz2, ops_s.transpose(w1))
-        dz1 = ops_s.new(n_rows, Pn)
-        _lib.check(lib.gvx_train_relu_dropout_backward(_p(dp1), _p(p1.contiguous()), _p(pk[0].contiguous()), 2.0, n_rows * Pn, _p(dz1), st_s))
-        g["decoder.prenet.layers.0.linear_layer.weight"] = ops_s.mm_tn(dz1, ch["frames"].reshape(n_rows, M).contiguous())
-        if side is not None:
-            join = torch.cuda.Event(); join.record(side)
-    dmemory = ops.axpby(dmemory.reshape(B * L, E), 1.0, ops.gemm_nt(dpm2, ops.transpose(wm)), 1.0).reshape(B, L, E)
-    # ---- encoder BiLSTM, packed-sequence semantics (models/tts/tacotron2.py:239-245): one C-ABI call, a launch per time step
+    _lib.check(lib.gvx_train_decoder_bptt(C.byref(ba_), ws_bptt.data_ptr(), wsb, ops.st))
+    return _LoopBptt(dga_all, dgd_all, dq_all, dctx_all, dpm, dmemory, dv, dld, dlw, xa, ha_prev, xd, hd_prev)
+
+
+def _loop_weight_grads_and_prenet(mc, ops_s: "_Ops", W, ch: dict, bp: _LoopBptt) -> Dict[str, torch.Tensor]:
+    """What of the decoder's backward is off the chain to the encoder, launched through ``ops_s`` on the current stream: the
+    loop's weight gradients (one product over all (t, b) rows each) and the whole Prenet backward."""
+    lib, st_s = ops_s.lib, ops_s.st
+    att = "decoder.attention_layer."
+    T, B = bp.dga_all.shape[:2]
+    L = bp.dpm.shape[1]
+    A, D, E, Pn, a = mc.attention_rnn_dim, mc.decoder_rnn_dim, mc.encoder_embedding_dim, mc.prenet_dim, mc.attention_dim
+    g: Dict[str, torch.Tensor] = {}
+    p2, ha = ch["p2"], ch["h_a_all"]                              # [T+1, B, P], [T+1, B, A]
+    # the Prenet columns of the attention LSTM are not on the recurrence: one product over all steps
+    dp2 = ops_s.zeros(T + 1, B, Pn)
+    ops_s.gemm_nt(bp.dga_all.reshape(T * B, 4 * A), ops_s.transpose(W("decoder.attention_rnn.weight_ih"))[:Pn], out=dp2[:T].reshape(T * B, Pn))
+    # ---- weight gradients of the loop
+    dga2, dgd2 = bp.dga_all.reshape(T * B, 4 * A), bp.dgd_all.reshape(T * B, 4 * D)
+    g["decoder.attention_rnn.weight_ih"], g["decoder.attention_rnn.weight_hh"] = ops_s.mm_tn(dga2, bp.xa), ops_s.mm_tn(dga2, bp.ha_prev.contiguous())
+    g["decoder.attention_rnn.bias_ih"] = ops_s.colsum(dga2)
+    g["decoder.attention_rnn.bias_hh"] = g["decoder.attention_rnn.bias_ih"].clone()
+    g["decoder.decoder_rnn.weight_ih"], g["decoder.decoder_rnn.weight_hh"] = ops_s.mm_tn(dgd2, bp.xd), ops_s.mm_tn(dgd2, bp.hd_prev)
+    g["decoder.decoder_rnn.bias_ih"] = ops_s.colsum(dgd2)
+    g["decoder.decoder_rnn.bias_hh"] = g["decoder.decoder_rnn.bias_ih"].clone()
+    g[att + "query_layer.linear_layer.weight"] = ops_s.mm_tn(bp.dq_all.reshape(T * B, a), ha[1:].reshape(T * B, A).contiguous())
+    g[att + "v.linear_layer.weight"] = bp.dv[None, :]
+    g[att + "location_layer.location_dense.linear_layer.weight"] = bp.dld
+    g[att + "location_layer.location_conv.conv.weight"] = bp.dlw
+    g[att + "memory_layer.linear_layer.weight"] = ops_s.mm_tn(bp.dpm.reshape(B * L, a), ch["memory"].reshape(B * L, E))
+    # ---- Prenet (relu then dropout, twice; models/tts/tacotron2.py:140-144)
+    pk = ch["prenet_keep"]                                        # [2, T+1, B, P] uint8
+    p1 = ch["p1"]
+    w1 = W("decoder.prenet.layers.1.linear_layer.weight")
+    n_rows = (T + 1) * B
+    dz2 = ops_s.new(n_rows, Pn)
+    _lib.check(lib.gvx_train_relu_dropout_backward(_p(dp2), _p(p2.contiguous()), _p(pk[1].contiguous()), 2.0, n_rows * Pn, _p(dz2), st_s))
+    g["decoder.prenet.layers.1.linear_layer.weight"] = ops_s.mm_tn(dz2, p1.reshape(n_rows, Pn).contiguous())
+    dp1 = ops_s.gemm_nt(dz2, ops_s.transpose(w1))
+    dz1 = ops_s.new(n_rows, Pn)
+    _lib.check(lib.gvx_train_relu_dropout_backward(_p(dp1), _p(p1.contiguous()), _p(pk[0].contiguous()), 2.0, n_rows * Pn, _p(dz1), st_s))
+    g["decoder.prenet.layers.0.linear_layer.weight"] = ops_s.mm_tn(dz1, ch["frames"].reshape(n_rows, -1).contiguous())
+    return g
+
+
+def _encoder_bilstm_backward(model, ops: "_Ops", W, ch: dict, x: torch.Tensor, dmemory: torch.Tensor) -> Tuple[Dict[str, torch.Tensor], torch.Tensor]:
+    """Encoder BiLSTM of one chunk, packed-sequence semantics (models/tts/tacotron2.py:239-245): one C-ABI call
+    (csrc/train_bptt_encoder.hip).  x [B, L, E] is the BiLSTM's input, dmemory [B, L, E] d loss / d of its output.  Returns
+    (gradients of its parameters, d loss / d x as [B * L, E])."""
+    dev = x.device
+    lib = ops.lib
+    B, L, E = x.shape
     H = E // 2
+    g: Dict[str, torch.Tensor] = {}
     x = x.contiguous()
     c_enc = ch["enc_cell_states"]                                 # [B, L, E] (forward direction in channels [0, H))
     dx_enc = ops.zeros(B * L, E)
@@ -402,9 +422,9 @@ def _recurrent_backward(model, ops: "_Ops", ch: dict, dmel: torch.Tensor, dgate:
     wse = torch.empty(lib.gvx_train_encoder_lstm_bptt_workspace_bytes(B, H), dtype=torch.uint8, device=dev)
     tl32 = ch["token_lengths"].to(device=dev, dtype=torch.int32).contiguous()
     # (one resident launch for the whole walk unless the model has seen it time out: encoder_bptt_timed_out below)
-    walk = lib.gvx_train_encoder_lstm_bptt_resident if getattr(model, "_enc_bptt_resident", True) else lib.gvx_train_encoder_lstm_bptt
-    _lib.check(walk(_p(xg), _p(memory.contiguous()), _p(c_enc.contiguous()), _p(dmemory.contiguous()), _p(w_hh2), _p(tl32),
-                    B, L, H, _p(dg_pos), _p(hprev_pos), _p(wse), wse.numel(), st))
+    walk = lib.gvx_train_encoder_lstm_bptt_resident if model._enc_bptt_resident else lib.gvx_train_encoder_lstm_bptt
+    _lib.check(walk(_p(xg), _p(ch["memory"].contiguous()), _p(c_enc.contiguous()), _p(dmemory.contiguous()), _p(w_hh2), _p(tl32),
+                    B, L, H, _p(dg_pos), _p(hprev_pos), _p(wse), wse.numel(), ops.st))
     model._enc_bptt_workspaces.append((wse, B, H))   # (one per chunk; train_backward starts the list afresh on every call)
     for d_, sfx in enumerate(sfxs):
         dg2 = dg_pos[d_]
@@ -413,6 +433,40 @@ def _recurrent_backward(model, ops: "_Ops", ch: dict, dmel: torch.Tensor, dgate:
         g["encoder.lstm.bias_ih_l0" + sfx] = ops.colsum(dg2)
         g["encoder.lstm.bias_hh_l0" + sfx] = g["encoder.lstm.bias_ih_l0" + sfx].clone()
         dx_enc = ops.axpby(dx_enc, 1.0, ops.gemm_nt(dg2, ops.transpose(w_ih2[d_])), 1.0)
+    return g, dx_enc
+
+
+def _recurrent_backward(model, ops: "_Ops", ch: dict, dmel: torch.Tensor, dgate: torch.Tensor, x: torch.Tensor, align: torch.Tensor
+                        ) -> Tuple[Dict[str, torch.Tensor], torch.Tensor]:
+    """The part of the backward that never mixes batch rows, for one chunk of at most 32 rows: projection, decoder loop
+    (gvx_train_decoder_bptt), Prenet, memory layer, encoder BiLSTM (gvx_train_encoder_lstm_bptt).  dmel [Bc, M, T] and dgate
+    [Bc, T] are d loss / d of the decoder's mel / gate outputs, x [Bc, L, E] the BiLSTM's input, align [Bc, T, L] the
+    alignments.  Returns (parameter gradients of this chunk's rows, d loss / d x as [Bc * L, E])."""
+    mc = model.model_config
+    dev = dmel.device
+    P_ = dict(model.named_parameters())
+    W = lambda name: P_[name].data
+    g, dhc_all = _projection_backward(ops, W, ch, dmel, dgate)
+    bp = _decoder_bptt(mc, ops, W, ch, dhc_all, align)
+    # ---- Off the chain to the encoder: the loop's weight gradients and the whole Prenet backward (dense products, ~5 ms at
+    # 32 x 200 frames) go to a second stream; the caller's stream goes on with the memory gradient and the encoder's BiLSTM walk
+    # (a launch per position on a quarter of the chip) and waits for them at the end.  One fork and one join per chunk (an edge
+    # costs ~5 us: tools/micro/chain_sidestream_bench.hip); every tensor is produced by the same launches in the same order as on
+    # one stream, so results do not change.  GVX_TRAIN_SIDE_STREAM=0: everything on the caller's stream.
+    main_stream = torch.cuda.current_stream(dev)
+    side = _side_stream(dev)
+    if side is not None:
+        fork = torch.cuda.Event(); fork.record(main_stream)
+        side.wait_event(fork)
+    with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
+        g.update(_loop_weight_grads_and_prenet(mc, _side_ops(dev) if side is not None else ops, W, ch, bp))
+        if side is not None:
+            join = torch.cuda.Event(); join.record(side)
+    B, L, E = bp.dmemory.shape
+    wm = W("decoder.attention_layer.memory_layer.linear_layer.weight")
+    dmemory = ops.axpby(bp.dmemory.reshape(B * L, E), 1.0, ops.gemm_nt(bp.dpm.reshape(B * L, -1), ops.transpose(wm)), 1.0).reshape(B, L, E)
+    eg, dx_enc = _encoder_bilstm_backward(model, ops, W, ch, x, dmemory)
+    g.update(eg)
     if side is not None:
         main_stream.wait_event(join)
     return g, dx_enc
@@ -465,7 +519,7 @@ def encoder_bptt_timed_out(model) -> bool:
 
     lib = _lib.load()
     hit = False
-    for wse, B, H in getattr(model, "_enc_bptt_workspaces", []):
+    for wse, B, H in model._enc_bptt_workspaces:
         code = C.c_int(0)
         _lib.check(lib.gvx_train_encoder_lstm_bptt_status(_p(wse), wse.numel(), B, H, C.byref(code), torch.cuda.current_stream(wse.device).cuda_stream))
         hit = hit or code.value != 0

@@ -125,7 +125,7 @@ def gemm_plan(lib, M, N, K, kmajor=0, scratch_bytes=None):
     return rc, tile.value, rows_big.value, pieces.value
 
 
-# ---- back-propagation through the decoder loop (gvx_train_decoder_bptt, genvox_amd/csrc/train.hip): the shapes
+# ---- back-propagation through the decoder loop (gvx_train_decoder_bptt, genvox_amd/csrc/train_bptt_decoder.hip): the shapes
 # tests/test_bptt_gpu.py runs, each with the branch of bptt_attention_kernel / bptt_chunks / bptt_plan it is there for.
 # tests/test_host_cpu.py pins every line against gvx_debug_bptt_plan on the CPU. --------------------------------------------------
 # sizes = (A, D, E, P, a, F, kl).  lengths: "full" (every row L), "ragged" (rows from 1 to L, both present when B >= 2), "short"
@@ -269,7 +269,7 @@ def enc_bptt_plan(lib, B, H, resident):
     return rc, list(out)
 
 
-# ---- the training-mode convolution layer (gvx_conv_bn_act_train_forward / _backward, genvox_amd/csrc/train.hip): the shapes
+# ---- the training-mode convolution layer (gvx_conv_bn_act_train_forward / _backward, genvox_amd/csrc/train_conv.hip): the shapes
 # tests/test_conv_train_gpu.py runs, each group with the branch it is there for.  tests/test_host_cpu.py pins every line against
 # gvx_debug_conv_train_plan on the CPU, so a retuned threshold fails there and the cases get re-aimed. ---------------------------------
 # act: none / relu / tanh.  p: None (keep = NULL), else the dropout probability handed over with a keep mask (0.0: a mask, scale 1).

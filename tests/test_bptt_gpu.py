@@ -1,5 +1,6 @@
 """GPU: the two recurrences of the training step's backward as the operations they are - gvx_train_decoder_bptt and
-gvx_train_encoder_lstm_bptt(_resident) (genvox_amd/csrc/train.hip) through ctypes, every direct output against float64 autograd.
+gvx_train_encoder_lstm_bptt(_resident) (genvox_amd/csrc/train_bptt_decoder.hip, train_bptt_encoder.hip) through ctypes, every
+direct output against float64 autograd.
 
 The reference here is NOT oracle/train_ref.py: the FORWARD of the operation is written plainly in torch float64 (the decoder loop of
 DESIGN.md section 1: attention LSTM cell, location-sensitive attention, decoder LSTM cell; the BiLSTM with packed-sequence

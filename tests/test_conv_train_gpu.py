@@ -1,10 +1,10 @@
 """GPU: the training-mode convolution layer as the operation it is - gvx_conv_bn_act_train_forward / _backward
-(genvox_amd/csrc/train.hip) through ctypes, every element of every output against float64 autograd.
+(genvox_amd/csrc/train_conv.hip) through ctypes, every element of every output against float64 autograd.
 
 The reference here is NOT oracle/train_ref.py: F.conv1d -> F.batch_norm(training=True, momentum 0.1, eps 1e-5) -> none / relu / tanh
 -> * keep / (1 - p) in torch float64 on the CPU, gradients by autograd from a given dy.  Every leaf is the fp32 number the kernel
 gets, so the only difference is the kernel's arithmetic.  With x_wgrad, dw is conv1d_weight(x_wgrad, dz): the weight gradient's
-input is x_wgrad while dz (and with it dx, dbias, dgamma, dbeta) stays that of the layer's own input, as train.hip's backward
+input is x_wgrad while dz (and with it dx, dbias, dgamma, dbeta) stays that of the layer's own input, as train_conv.hip's backward
 states it.  torch refuses one value per channel in training mode, so rows = B T = 1 takes the explicit form the header documents
 (xhat = 0, y = act(beta); dx, dw, dbias, dgamma zero, dbeta = du; running_var times 0.9).
 relu: a pre-activation within a few u of 0 has no stable gradient.  The elements where the kernel's y and float64 fall on different

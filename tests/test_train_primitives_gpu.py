@@ -1,4 +1,4 @@
-"""GPU: the small training kernels of genvox_amd/csrc/train.hip (and the criterion / mask kernels of misc.hip) that
+"""GPU: the small training kernels of genvox_amd/csrc/train_ops.hip (and the criterion / mask kernels of misc.hip) that
 genvox_amd/training.py strings together, each against its plain definition in float64 (or exactly, where the kernel moves or
 selects values), at the sizes where their loops change shape: chunk and pass boundaries of the embedding gradient, the
 two-stride loop of the squared norm, grid-stride tails.  Regions a kernel must not read hold NaN, regions it must not write a
