@@ -1,6 +1,7 @@
 """genvox_amd: MI355X-native Tacotron2 text->mel forward path and Griffin-Lim vocoder behind GenVox's Python surface.
 
     from genvox_amd import Tacotron2, Synthesizer, AudioProcessor, Tacotron2Config, AudioConfig, TextConfig
+    from genvox_amd import Tacotron2GuidedLoss    # training criterion: Tacotron2Loss + alpha x guided attention loss
 """
 from .configs import AudioConfig, BaseConfig, Tacotron2Config, TextConfig  # noqa: F401
 
@@ -9,6 +10,9 @@ def __getattr__(name):  # torch-dependent classes are imported lazily
     if name == "Tacotron2":
         from .tacotron2 import Tacotron2
         return Tacotron2
+    if name == "Tacotron2GuidedLoss":
+        from .tacotron2 import Tacotron2GuidedLoss
+        return Tacotron2GuidedLoss
     if name == "Synthesizer":
         from .synthesizer import Synthesizer
         return Synthesizer

@@ -88,6 +88,9 @@ SIGNATURES = {
     "gvx_train_adam_step_many": (_i, [_vp, _i, _f, _f, _f, _f, _f, _f, _i, _vp]),
     "gvx_train_decoder_bptt_workspace_bytes": (_sz, [C.POINTER(gvx_bptt_decoder_args)]),
     "gvx_train_decoder_bptt": (_i, [C.POINTER(gvx_bptt_decoder_args), _vp, _sz, _vp]),
+    "gvx_train_decoder_bptt_ext": (_i, [C.POINTER(gvx_bptt_decoder_args), _vp, C.c_int64, C.c_int64, _vp, _sz, _vp]),
+    "gvx_guided_attention_loss_scratch_bytes": (_sz, [_i, _i, _i]),
+    "gvx_guided_attention_loss": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _sz, _vp]),
     "gvx_train_encoder_lstm_bptt_workspace_bytes": (_sz, [_i, _i]),
     "gvx_train_encoder_lstm_bptt": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "gvx_train_encoder_lstm_bptt_resident": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),

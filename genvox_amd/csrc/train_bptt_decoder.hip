@@ -11,8 +11,10 @@
 //      mode 2) with the matrices transposed and packed in MFMA-fragment order on the device at the start of the call; K
 //      is cut in two so that the default layer sizes give 256 equal tiles (48 + 80 row tiles x 2 K halves, 256 KB each).
 // The softmax term sum_l w_l dw_l is taken as  w . (dw_next + G) + dctx . ctx(t)  (ctx(t) = sum_l w_l memory_l is on the
-// tape): a chunk does not need the other chunks' dw.  The context path of the memory gradient, sum_t w_t (x) dctx_t, is one
-// kernel after the loop.  What is not on the recurrence - the Prenet columns of the attention LSTM, all weight gradients -
+// tape): a chunk does not need the other chunks' dw.  A loss that looks at the alignments themselves (the guided attention loss,
+// train_guided.hip) hands its d loss / d w_t to gvx_train_decoder_bptt_ext, where it joins dw_next + G of step t - in the softmax
+// backward only, not in what the location convolution passes to earlier steps.  The context path of the memory gradient,
+// sum_t w_t (x) dctx_t, is one kernel after the loop.  What is not on the recurrence - the Prenet columns of the attention LSTM, all weight gradients -
 // stays with the host mirror as whole-sequence GEMMs.
 #include "train_internal.h"
 
@@ -43,6 +45,7 @@ struct BpttAttn {
     float* dpm;                               // [B][L][a]  accumulated
     float* dv_acc; float* dld_acc; float* dlw_acc;   // [B][G][a], [B][G][a][F], [B][G][F * 2 * kl]  accumulated
     int stamp;                                // stamps build: this launch records its phase times
+    const float* dw_ext; long dw_ext_bs;      // bptt_attention_kernel<true> only: d loss / d w_t taken directly on the alignments, row b at dw_ext + b * dw_ext_bs
 };
 
 // LDS rows of the location filters are FS = 32 floats whatever F is (zeros past F): every loop over filters is a compile-time
@@ -62,6 +65,9 @@ constexpr size_t BA_LDS_LIMIT = 160 * 1024;
 
 __device__ __forceinline__ float fast_tanh(float x) { return 1.f - 2.f * __builtin_amdgcn_rcpf(__expf(2.f * x) + 1.f); }
 
+// EXT: a gradient on the alignments themselves (gvx_train_decoder_bptt_ext) joins dw_next + G.  A template parameter, not a branch:
+// the instantiation without it is the kernel as it was, instruction for instruction.
+template <bool EXT>
 __global__ __launch_bounds__(BA_THREADS) void bptt_attention_kernel(BpttAttn p) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int g = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
@@ -73,7 +79,7 @@ __global__ __launch_bounds__(BA_THREADS) void bptt_attention_kernel(BpttAttn p) 
     float* locf = sm;                  // [CH][FS]        zeros past F          (16-byte aligned rows: read as float4)
     float* dlocf = locf + CH * FS;     // [CH][FS]
     float* dc = dlocf + CH * FS;       // [E]
-    float* dwg = dc + E;               // [L]   dw_next + G of the whole row
+    float* dwg = dc + E;               // [L]   dw_next + G (+ the external term) of the whole row
     float* wrow = dwg + L;             // [L]   alignment of step t
     float* red = wrow + L;             // [BA_THREADS]
     float* win = red + BA_THREADS;     // [2][LW] previous / cumulative weights at positions l0 - pad ...
@@ -125,9 +131,14 @@ __global__ __launch_bounds__(BA_THREADS) void bptt_attention_kernel(BpttAttn p) 
             pd[gg] = gg < G ? p.dw_in[((long)b * G + gg) * L + l] : 0.f;
             pg[gg] = gg < G ? p.gc_in[((long)b * G + gg) * L + l] : 0.f;
         }
+        float ex = 0.f;
+        if (EXT) ex = p.dw_ext[(long)b * p.dw_ext_bs + l];
         float s = 0.f;
 #pragma unroll
         for (int gg = 0; gg < BP_GMAX; ++gg) s += pd[gg] + pg[gg];
+        // the external term enters here and nowhere else: ssum and des read dwg, dw_out / gc_out (the location convolution's
+        // gradient to earlier steps) do not
+        if (EXT) s += ex;
         dwg[l] = s;
         wrow[l] = p.w[(long)b * L + l];
     }
@@ -510,9 +521,17 @@ size_t gvx_train_decoder_bptt_workspace_bytes(const gvx_bptt_decoder_args* a) {
 }
 
 int gvx_train_decoder_bptt(const gvx_bptt_decoder_args* ap, void* workspace, size_t workspace_bytes, void* stream) {
+    return gvx_train_decoder_bptt_ext(ap, nullptr, 0, 0, workspace, workspace_bytes, stream);
+}
+
+int gvx_train_decoder_bptt_ext(const gvx_bptt_decoder_args* ap, const float* dw_ext, int64_t dw_ext_ts, int64_t dw_ext_bs, void* workspace,
+                               size_t workspace_bytes, void* stream) {
     int rc = check_bptt_args(ap);
     if (rc != GVX_OK) return rc;
     const gvx_bptt_decoder_args& a = *ap;
+    // (rows of dw_ext may not overlap: a stride below L between two steps or two batch rows is a mistake of the caller's)
+    if (dw_ext && ((a.T > 1 && dw_ext_ts < a.L) || (a.B > 1 && dw_ext_bs < a.L) || dw_ext_ts < 0 || dw_ext_bs < 0))
+        return tfail(GVX_ERR_INVALID_ARG, "decoder_bptt: dw_ext strides must be >= L between steps and between batch rows");
     const BpttPlan pl = bptt_plan(a);
     if (!workspace || workspace_bytes < pl.total * sizeof(float)) return tfail(GVX_ERR_WORKSPACE, "decoder_bptt: workspace too small");
     if (reinterpret_cast<uintptr_t>(workspace) & 255) return tfail(GVX_ERR_WORKSPACE, "decoder_bptt: workspace must be 256-byte aligned");
@@ -521,7 +540,8 @@ int gvx_train_decoder_bptt(const gvx_bptt_decoder_args* ap, void* workspace, siz
     const int B = a.B, L = a.L, T = a.T, A = a.A, D = a.D, E = a.E, P = a.P, G = pl.G, Na = pl.Na, Nd = pl.Nd;
     const int Ka = 4 * A, Kd = 4 * D;
     // (per call, not once per process: the attribute belongs to the current device)
-    TR_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(bptt_attention_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    auto attention_kernel = dw_ext ? bptt_attention_kernel<true> : bptt_attention_kernel<false>;
+    TR_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     const size_t lds_attn = bptt_attn_lds_floats(L, E, a.a, a.F, a.kl, G) * sizeof(float);
 
     // ---- before the loop: transposed matrices in fragment order, cumulative weights, cleared state and accumulators
@@ -562,7 +582,8 @@ int gvx_train_decoder_bptt(const gvx_bptt_decoder_args* ap, void* workspace, siz
             q.dctx_out = a.dctx_all + (size_t)t * B * E;
             q.dpm = a.dpm; q.dv_acc = ws + pl.dv_acc; q.dld_acc = ws + pl.dld_acc; q.dlw_acc = ws + pl.dlw_acc;
             q.stamp = t == T / 2;
-            hipLaunchKernelGGL(bptt_attention_kernel, dim3(G, B), dim3(BA_THREADS), lds_attn, s, q);
+            if (dw_ext) { q.dw_ext = dw_ext + (long)t * (long)dw_ext_ts; q.dw_ext_bs = (long)dw_ext_bs; }
+            hipLaunchKernelGGL(attention_kernel, dim3(G, B), dim3(BA_THREADS), lds_attn, s, q);
         }
         {
             BpttCells c{};

@@ -759,7 +759,13 @@ class Tacotron2(nn.Module):
         behind the C ABI; the formulas are pinned to the reference's loss.backward() through oracle/train_ref.py).  Fills
         ``loss_items`` and ``grad_norm_val`` like the reference.  Any batch size (the recurrent part runs in chunks of at most
         32 rows); both recurrences are walked back inside single C-ABI calls and the packed blob is re-built on the device:
-        27 ms per step at 32 x 200 frames, reproducible bit for bit (profiles/r04_train_step_timing.txt)."""
+        27 ms per step at 32 x 200 frames, reproducible bit for bit (profiles/r04_train_step_timing.txt).
+
+        Which criteria the step can differentiate: ``Tacotron2Loss`` (``get_criterion()``) and ``Tacotron2GuidedLoss``
+        (``get_criterion(guided_attention_alpha=...)``), whose gradient on the alignments comes out of the launch that computes
+        its loss and enters the decoder's back-propagation (at alpha == 0 no such gradient is passed at all: the step is the
+        unguided one bit for bit, and ``guided_attention_loss`` is still logged).  There being no autograd, any other callable
+        under ``criterion["loss"]`` only changes ``loss_items``: the gradients stay those of ``Tacotron2Loss``."""
         from . import training
 
         if optimizer is None:
@@ -768,19 +774,24 @@ class Tacotron2(nn.Module):
         self.train()
         try:
             outputs, tape = self._forward_train(batch)
-            loss = (criterion or self.get_criterion())["loss"](batch, outputs)
+            crit = (criterion or self.get_criterion())["loss"]
+            dalign = None
+            if hasattr(crit, "loss_and_alignment_grad"):   # Tacotron2GuidedLoss: loss and d loss / d alignments from one launch
+                loss, dalign = crit.loss_and_alignment_grad(batch, outputs)
+            else:
+                loss = crit(batch, outputs)
             self.loss_items = {key: val.item() for key, val in loss.items()}
             # (a token id outside the table raised before the forward touched anything; a hand-off time-out was caught - and the
             # recurrent part re-run - before the Postnet's BatchNorm update; this is the last look before gradients reach the weights)
             self.check_status()
-            grads = training.train_backward(self, batch, outputs, tape)
+            grads = training.train_backward(self, batch, outputs, tape, dalign=dalign)
             self.grad_norm_val, scale = training.clip_grad_norm(grads, self.model_config.grad_clip_thresh)
             if not math.isfinite(self.grad_norm_val) and training.encoder_bptt_timed_out(self):
                 # the resident walk of the encoder BiLSTM gave up on a hand-off (NaN gradients): from now on a launch per time
                 # step for this model, and the backward once more - nothing has touched the weights yet
                 warnings.warn("genvox_amd: the resident encoder-BiLSTM backward timed out; re-running the backward with a launch per time step")
                 self._enc_bptt_resident = False
-                grads = training.train_backward(self, batch, outputs, tape)
+                grads = training.train_backward(self, batch, outputs, tape, dalign=dalign)
                 self.grad_norm_val, scale = training.clip_grad_norm(grads, self.model_config.grad_clip_thresh)
             self._enc_bptt_workspaces = []
             optimizer["optimizer"].step(grads, scale)
@@ -791,16 +802,21 @@ class Tacotron2(nn.Module):
                 self.eval()
 
     def get_train_step_logs(self) -> Dict:
-        """Reference: tacotron2.py:553-560."""
+        """Reference: tacotron2.py:553-560 (with ``guided_attention_loss`` when the step's criterion was a `Tacotron2GuidedLoss`)."""
         return {**self.loss_items, "grad_norm": self.grad_norm_val}
 
-    def get_criterion(self) -> Dict:
-        """Reference: tacotron2.py:501-504."""
-        return {"loss": Tacotron2Loss}
+    def get_criterion(self, guided_attention_alpha: float = 0.0, guided_attention_sigma: float = 0.4) -> Dict:
+        """Reference: tacotron2.py:501-504.  ``guided_attention_alpha`` > 0: ``Tacotron2GuidedLoss`` with that weight and
+        ``guided_attention_sigma`` - Tacotron2Loss + alpha x the diagonal guided attention loss, which ``train_step``
+        differentiates through the decoder loop.  At 0.0 (the default) the reference's criterion, ``Tacotron2Loss`` itself."""
+        if guided_attention_alpha == 0.0:
+            return {"loss": Tacotron2Loss}
+        return {"loss": Tacotron2GuidedLoss(alpha=guided_attention_alpha, sigma=guided_attention_sigma)}
 
     def eval_step(self, batch: Dict, criterion: Optional[Dict] = None, eval_outdir: Optional[str] = None) -> Dict[str, torch.Tensor]:
         """Forward + criterion under no_grad (reference: tacotron2.py:524-529): fills `loss_items_eval` with
-        loss_eval / mel_loss_eval / gate_loss_eval like the reference and returns the forward outputs.  The plots the
+        loss_eval / mel_loss_eval / gate_loss_eval like the reference (and guided_attention_loss_eval under a
+        `Tacotron2GuidedLoss`) and returns the forward outputs.  The plots the
         reference writes to `eval_outdir` are out of scope; what a person reads off them - has attention become a sharp,
         monotonic diagonal, does free-running synthesis resemble the target - is what `eval_synthesis` gives as numbers."""
         with torch.no_grad():
@@ -880,3 +896,59 @@ def Tacotron2Loss(batch: Dict[str, torch.Tensor], outputs: Dict[str, torch.Tenso
                                       B, M, T, out.data_ptr(), scratch.data_ptr(), scratch.numel(),
                                       torch.cuda.current_stream(dev).cuda_stream))
     return {"loss": out[0], "mel_loss": out[1], "gate_loss": out[2]}
+
+
+class Tacotron2GuidedLoss:
+    """``Tacotron2Loss`` + alpha x the diagonal guided attention loss (Tachibana et al. 2017; the masked mean of ESPnet's Tacotron2
+    recipe) on ``outputs["alignments"]`` [B, T, L].  With L_b = token_lengths[b], T_b = mel_lengths[b]:
+
+        G[b, t, l] = 1 - exp(-(l / L_b - t / T_b)^2 / (2 sigma^2))   for t < T_b and l < L_b (other cells are skipped),
+        guided_attention_loss = sum G A / sum_b T_b L_b,   loss = mel_loss + gate_loss + alpha * guided_attention_loss.
+
+    A callable criterion, ``(batch, outputs) -> {"loss", "mel_loss", "gate_loss", "guided_attention_loss"}`` (0-dim float32 tensors
+    on the outputs' device), for ``train_step`` and ``eval_step``: ``{"loss": Tacotron2GuidedLoss(alpha=1.0)}`` or
+    ``Tacotron2.get_criterion(guided_attention_alpha=1.0)``.  ``alpha`` and ``sigma`` are plain attributes that a training loop
+    may change between steps (decay schedules).  One HIP pass over the alignments (gvx_guided_attention_loss) gives the loss and,
+    for ``train_step``, its gradient on the alignments."""
+
+    def __init__(self, alpha: float = 1.0, sigma: float = 0.4) -> None:
+        self._check(alpha, sigma)
+        self.alpha, self.sigma = alpha, sigma
+
+    @staticmethod
+    def _check(alpha, sigma) -> None:
+        if not (math.isfinite(alpha) and alpha >= 0.0):
+            raise ValueError(f"guided attention alpha must be a finite number >= 0, got {alpha!r}")
+        if not (math.isfinite(sigma) and sigma > 0.0):
+            raise ValueError(f"guided attention sigma must be a finite number > 0, got {sigma!r}")
+
+    def __call__(self, batch: Dict[str, torch.Tensor], outputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        return self._run(batch, outputs, want_grad=False)[0]
+
+    def loss_and_alignment_grad(self, batch: Dict[str, torch.Tensor], outputs: Dict[str, torch.Tensor]):
+        """(loss items, d loss / d alignments [B, T, L]) from the same launch - what ``train_step`` hands to
+        ``training.train_backward(dalign=...)``.  At ``alpha == 0`` the gradient is None (nothing to pass on)."""
+        return self._run(batch, outputs, want_grad=self.alpha > 0.0)
+
+    def _run(self, batch, outputs, want_grad: bool):
+        self._check(self.alpha, self.sigma)   # (attributes may have been changed since the constructor looked)
+        lib = _lib.load()
+        base = Tacotron2Loss(batch, outputs)
+        align = outputs["alignments"]
+        dev = align.device
+        align = align.to(torch.float32).contiguous()
+        B, T, L = align.shape
+        i32 = lambda t: torch.as_tensor(t).to(device=dev, dtype=torch.int32).contiguous()
+        tl, ml = i32(batch["token_lengths"]), i32(batch["mel_lengths"])
+        if tl.shape != (B,) or ml.shape != (B,):
+            raise ValueError(f"token_lengths / mel_lengths must hold one length per row of the alignments ({B}), got {tuple(tl.shape)}, {tuple(ml.shape)}")
+        out = torch.empty(1, dtype=torch.float32, device=dev)
+        dalign = torch.empty_like(align) if want_grad else None
+        scratch = torch.empty(lib.gvx_guided_attention_loss_scratch_bytes(B, T, L), dtype=torch.uint8, device=dev)
+        _lib.check(lib.gvx_guided_attention_loss(align.data_ptr(), tl.data_ptr(), ml.data_ptr(), B, T, L, float(self.sigma), float(self.alpha),
+                                                 out.data_ptr(), None if dalign is None else dalign.data_ptr(), scratch.data_ptr(), scratch.numel(),
+                                                 torch.cuda.current_stream(dev).cuda_stream))
+        ga = out[0]
+        items = {"loss": base["loss"] + float(self.alpha) * ga, "mel_loss": base["mel_loss"], "gate_loss": base["gate_loss"],
+                 "guided_attention_loss": ga}
+        return items, dalign

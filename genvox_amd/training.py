@@ -9,7 +9,8 @@ packed-sequence semantics, encoder convolutions, embedding - exactly as ``oracle
 formula runs in a HIP kernel behind the C ABI (csrc/train_conv.hip: ``gvx_conv_bn_act_train_*``; csrc/train_ops.hip and the
 two csrc/train_bptt_*.hip: ``gvx_train_*``; the dense products on the exact-fp32 MFMA GEMM of the forward path).  The two recurrences are one C-ABI call each
 (``gvx_train_decoder_bptt``: three launches per decoder step, ``gvx_train_encoder_lstm_bptt``: one per time step); torch
-allocates, slices and reshapes around them.  Parameters are updated in
+allocates, slices and reshapes around them.  A criterion that looks at the alignments (``Tacotron2GuidedLoss``) hands its gradient
+on them to ``train_backward(dalign=...)``, which enters the decoder's walk through ``gvx_train_decoder_bptt_ext``.  Parameters are updated in
 place in the reference's own layouts (``Adam``); the packed blob of the forward kernels is re-built before the next forward.
 
 Pinned by ``tests/golden/train_small.npz`` - the reference's own train step (all 48 parameter gradients, the gradient norm,
@@ -303,9 +304,10 @@ def _projection_backward(ops: "_Ops", W, ch: dict, dmel: torch.Tensor, dgate: to
     return g, ops.gemm_nt(dmg, ops.transpose(Wpg)).reshape(T, B, DE)
 
 
-def _decoder_bptt(mc, ops: "_Ops", W, ch: dict, dhc_all: torch.Tensor, align: torch.Tensor) -> _LoopBptt:
+def _decoder_bptt(mc, ops: "_Ops", W, ch: dict, dhc_all: torch.Tensor, align: torch.Tensor, dalign: Optional[torch.Tensor] = None) -> _LoopBptt:
     """Back-propagation through the decoder loop of one chunk: one C-ABI call (three launches per step,
-    csrc/train_bptt_decoder.hip).  align [B, T, L] are the alignments."""
+    csrc/train_bptt_decoder.hip).  align [B, T, L] are the alignments, dalign (or None) a gradient taken directly on them: the
+    chunk's rows of a [B, T, L] tensor, read through its strides (gvx_train_decoder_bptt_ext)."""
     dev = dhc_all.device
     lib = ops.lib
     att = "decoder.attention_layer."
@@ -354,7 +356,11 @@ def _decoder_bptt(mc, ops: "_Ops", W, ch: dict, dhc_all: torch.Tensor, align: to
     if wsb == 0:
         _lib.check(1)
     ws_bptt = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    _lib.check(lib.gvx_train_decoder_bptt(C.byref(ba_), ws_bptt.data_ptr(), wsb, ops.st))
+    if dalign is None:
+        _lib.check(lib.gvx_train_decoder_bptt(C.byref(ba_), ws_bptt.data_ptr(), wsb, ops.st))
+    else:
+        assert dalign.shape == align.shape and dalign.dtype == torch.float32 and dalign.stride(2) == 1, (dalign.shape, dalign.stride(), dalign.dtype)
+        _lib.check(lib.gvx_train_decoder_bptt_ext(C.byref(ba_), dalign.data_ptr(), dalign.stride(1), dalign.stride(0), ws_bptt.data_ptr(), wsb, ops.st))
     return _LoopBptt(dga_all, dgd_all, dq_all, dctx_all, dpm, dmemory, dv, dld, dlw, xa, ha_prev, xd, hd_prev)
 
 
@@ -436,18 +442,19 @@ def _encoder_bilstm_backward(model, ops: "_Ops", W, ch: dict, x: torch.Tensor, d
     return g, dx_enc
 
 
-def _recurrent_backward(model, ops: "_Ops", ch: dict, dmel: torch.Tensor, dgate: torch.Tensor, x: torch.Tensor, align: torch.Tensor
-                        ) -> Tuple[Dict[str, torch.Tensor], torch.Tensor]:
+def _recurrent_backward(model, ops: "_Ops", ch: dict, dmel: torch.Tensor, dgate: torch.Tensor, x: torch.Tensor, align: torch.Tensor,
+                        dalign: Optional[torch.Tensor] = None) -> Tuple[Dict[str, torch.Tensor], torch.Tensor]:
     """The part of the backward that never mixes batch rows, for one chunk of at most 32 rows: projection, decoder loop
     (gvx_train_decoder_bptt), Prenet, memory layer, encoder BiLSTM (gvx_train_encoder_lstm_bptt).  dmel [Bc, M, T] and dgate
     [Bc, T] are d loss / d of the decoder's mel / gate outputs, x [Bc, L, E] the BiLSTM's input, align [Bc, T, L] the
-    alignments.  Returns (parameter gradients of this chunk's rows, d loss / d x as [Bc * L, E])."""
+    alignments, dalign (or None) d loss / d of the alignments themselves for these rows.  Returns (parameter gradients of this
+    chunk's rows, d loss / d x as [Bc * L, E])."""
     mc = model.model_config
     dev = dmel.device
     P_ = dict(model.named_parameters())
     W = lambda name: P_[name].data
     g, dhc_all = _projection_backward(ops, W, ch, dmel, dgate)
-    bp = _decoder_bptt(mc, ops, W, ch, dhc_all, align)
+    bp = _decoder_bptt(mc, ops, W, ch, dhc_all, align, dalign)
     # ---- Off the chain to the encoder: the loop's weight gradients and the whole Prenet backward (dense products, ~5 ms at
     # 32 x 200 frames) go to a second stream; the caller's stream goes on with the memory gradient and the encoder's BiLSTM walk
     # (a launch per position on a quarter of the chip) and waits for them at the end.  One fork and one join per chunk (an edge
@@ -472,11 +479,17 @@ def _recurrent_backward(model, ops: "_Ops", ch: dict, dmel: torch.Tensor, dgate:
     return g, dx_enc
 
 
-def train_backward(model, batch: Dict[str, torch.Tensor], outputs: Dict[str, torch.Tensor], tape: dict) -> Dict[str, torch.Tensor]:
+def train_backward(model, batch: Dict[str, torch.Tensor], outputs: Dict[str, torch.Tensor], tape: dict,
+                   dalign: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
     """Gradients of loss = Tacotron2Loss(batch, outputs) w.r.t. every parameter (keys = the reference's state_dict names),
     from the tape of ``Tacotron2._forward_train``.  What mixes batch rows - the criterion's means and the BatchNorm batch
     statistics of both convolution stacks - runs on the whole batch; the recurrent part runs per chunk of at most 32 rows
-    (``_recurrent_backward``), its parameter gradients added in chunk order."""
+    (``_recurrent_backward``), its parameter gradients added in chunk order.
+
+    dalign [B, T, L] (cuda, fp32, last stride 1; finite everywhere) adds a term to the loss that looks at the alignments
+    themselves: d term / d ``outputs["alignments"]``, as ``Tacotron2GuidedLoss.loss_and_alignment_grad`` gives it for
+    alpha x the guided attention loss.  Its mean is over the whole batch, so it is computed once, before the chunks, and each
+    chunk reads its rows in place."""
     dev = outputs["mel_outputs"].device
     ops = _Ops(dev)
     lib, st = ops.lib, ops.st
@@ -496,9 +509,13 @@ def train_backward(model, batch: Dict[str, torch.Tensor], outputs: Dict[str, tor
     # ---- the recurrent part, chunk by chunk
     x_all = tape["enc_conv_out"].permute(0, 2, 1).contiguous()    # [B, L, E]: the BiLSTM's input
     dx_enc = ops.new(B * L, E)
+    if dalign is not None:
+        if dalign.shape != outputs["alignments"].shape or dalign.device != dev or dalign.dtype != torch.float32 or dalign.stride(2) != 1:
+            raise ValueError(f"dalign must be a float32 tensor of the alignments' shape {tuple(outputs['alignments'].shape)} on {dev}, last stride 1")
     for ch in tape["chunks"]:
         lo, hi = ch["rows"]
-        cg, dxe = _recurrent_backward(model, ops, ch, dmel[lo:hi], dgate[lo:hi], x_all[lo:hi], outputs["alignments"][lo:hi])
+        cg, dxe = _recurrent_backward(model, ops, ch, dmel[lo:hi], dgate[lo:hi], x_all[lo:hi], outputs["alignments"][lo:hi],
+                                      None if dalign is None else dalign[lo:hi])
         _accumulate(ops, g, cg)
         dx_enc[lo * L:hi * L] = dxe
     # ---- encoder convolution stack and embedding (whole batch)

@@ -365,6 +365,31 @@ typedef struct gvx_bptt_decoder_args {
 } gvx_bptt_decoder_args;
 size_t gvx_train_decoder_bptt_workspace_bytes(const gvx_bptt_decoder_args* args);
 int gvx_train_decoder_bptt(const gvx_bptt_decoder_args* args, void* workspace, size_t workspace_bytes, void* stream);
+/* The same call with a gradient taken DIRECTLY on the alignments (a loss that looks at them, such as the guided attention loss
+ * below): dw_ext holds d loss / d w_t[b][l], element (t, b, l) at dw_ext + t * dw_ext_ts + b * dw_ext_bs + l (strides in floats,
+ * as ctx_all has them: a row slice of a [B][T][L] tensor goes in with ts = L, bs = T L, a time-major array with ts = B L,
+ * bs = L; both >= L where T > 1 / B > 1, GVX_ERR_INVALID_ARG otherwise).  The term enters the softmax backward of step t,
+ *   de_l = w_l (dctx . memory_l + dw_l - sum_k w_k dw_k),   dw = previous-weights path + cumulative path + dw_ext[t],
+ * and nothing else: the location convolution's gradient to earlier steps is that of the energies alone.  Values at and past a
+ * row's length are never seen in an output (they meet w = 0) but must be FINITE - 0 x NaN is NaN.  dw_ext == NULL is
+ * gvx_train_decoder_bptt, bit for bit; same argument block, workspace size and limits. */
+int gvx_train_decoder_bptt_ext(const gvx_bptt_decoder_args* args, const float* dw_ext, int64_t dw_ext_ts, int64_t dw_ext_bs,
+                               void* workspace, size_t workspace_bytes, void* stream);
+/* ---- Diagonal guided attention loss (Tachibana et al. 2017; masked mean as in ESPnet's Tacotron2 recipe) on the alignments
+ * align [B][T][L] of the teacher-forced forward, and its gradient.  With L_b = token_lengths[b], T_b = mel_lengths[b] (device
+ * int32, clamped to [0, L] / [0, T]; summed on the device, no host synchronisation) and N = sum_b T_b L_b:
+ *   G[b][t][l] = 1 - exp(-(l / L_b - t / T_b)^2 / (2 sigma^2))   for t < T_b and l < L_b,
+ *   loss_out[0] = sum G align / N                                (device fp32; WITHOUT alpha),
+ *   dalign[b][t][l] = alpha G[b][t][l] / N                       (may be NULL: loss only; the loss is the same either way).
+ * Cells outside a row's T_b x L_b are skipped - align may hold anything there, NaN included - and dalign is exactly 0 in them.
+ * N = 0 gives loss 0 and a zero gradient.  Every element of dalign is good to 9 x 2^-24 of ITSELF (l / L_b - t / T_b is formed
+ * from the exact integer l T_b - t L_b, G as -expm1(-x)) and exactly 0 on a row's diagonal; the sum runs over float64 partials
+ * in a fixed order: two calls are bit-equal.  sigma > 0, alpha >= 0, B, T, L >= 1 (GVX_ERR_INVALID_ARG otherwise, also for a NULL
+ * pointer other than dalign); scratch: gvx_guided_attention_loss_scratch_bytes, 8-byte aligned (GVX_ERR_WORKSPACE). */
+size_t gvx_guided_attention_loss_scratch_bytes(int B, int T, int L);
+int gvx_guided_attention_loss(const float* align, const int32_t* token_lengths, const int32_t* mel_lengths, int B, int T, int L,
+                              float sigma, float alpha, float* loss_out, float* dalign, void* scratch, size_t scratch_bytes,
+                              void* stream);
 /* Back-propagation through the encoder BiLSTM (Encoder.forward, models/tts/tacotron2.py:239-245, packed-sequence semantics),
  * one launch per time step for both directions.  xg [2][B][L][4H] = W_ih x + b_ih + b_hh per direction; memory / cell_states /
  * dmemory [B][L][2H] (forward direction in the first H channels); w_hh [2][4H][H].  Outputs, filed under the POSITION a step
