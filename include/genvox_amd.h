@@ -22,6 +22,27 @@
  *  - A gvx_model handle is not thread-safe; distinct handles may be used concurrently.
  *  - All floating point data is fp32 (the reference's dtype).  Channel dims must be
  *    multiples of 8 (GVX_ERR_UNSUPPORTED otherwise).
+ *  - Workspaces and scratch.  Every `workspace`, `saved`, `scratch` and `scratch_B` argument is memory the CALLER owns and the
+ *    library only borrows for the call (and for the replays of a graph captured over it).  What the caller owes:
+ *      * a model workspace (the ones sized by gvx_workspace_bytes, gvx_workspace_bytes_autoregressive and
+ *        gvx_postnet_workspace_bytes): its first GVX_WORKSPACE_CLEAR_BYTES bytes are zeroed ONCE, before the first call that
+ *        sees the buffer.  They hold the sticky status words of gvx_workspace_status (bytes 0 .. 11), which the kernels only
+ *        ever raise and gvx_workspace_status clears, and the hand-off time-out word of the call in flight (bytes 12800 ..
+ *        12803).  That word is NOT sticky: every decoder loop and every resident encoder launch zeroes it at its start and
+ *        copies it into status word [1] at its end; the caller's clear of it only matters to a gvx_workspace_status that runs
+ *        before any such call has, so do not look for a status there.  Clearing more is harmless (the host mirror clears
+ *        64 KiB); clearing the front again later loses a status that was not read yet;
+ *      * nothing else.  Every other byte of a model workspace, and every byte of any other workspace, `saved` buffer or
+ *        scratch, may hold ANY bit pattern when a call starts - NaN, the leftovers of a call of another shape, of another
+ *        entry point or of another handle.  Each call clears what it accumulates into, inside the call and inside the graph
+ *        it captures, and reads no byte it (or, for `saved`, the matching forward call) has not written.
+ *    What the library owes: no call writes outside [buffer, buffer + declared bytes), where the declared bytes are the
+ *    `*_bytes` argument (for scratch arguments without one: what the matching size query or the parameter's comment states).
+ *    A buffer smaller than the size query for the call's shape - by one byte - is GVX_ERR_WORKSPACE, checked before anything is
+ *    launched or written; so is a NULL or misaligned one (256 bytes for workspaces and `saved`, 8 for the float64 scratches).
+ *    The layout inside a workspace is a function of the call's shape: a buffer that served one shape serves any other shape
+ *    it is large enough for, but sizes are NOT monotone in B or L (a region exists only where the shape's plan uses it), so
+ *    "large enough" is only ever established by calling the size query for the shape at hand.
  */
 #ifndef GENVOX_AMD_H
 #define GENVOX_AMD_H
@@ -72,6 +93,9 @@ typedef struct gvx_weight_desc {
 
 typedef struct gvx_model gvx_model;
 
+/* Bytes at the front of a model workspace the caller zeroes once before first use (Conventions, "Workspaces and scratch"). */
+#define GVX_WORKSPACE_CLEAR_BYTES 12804
+
 const char* gvx_last_error(void);
 int gvx_version(void);
 
@@ -95,7 +119,9 @@ int gvx_model_pack_weights_device(gvx_model* model, const gvx_weight_desc* table
 
 /* Bytes of scratch the calls below need for batch B, L tokens and up to T frames.  gvx_workspace_bytes covers every call;
  * gvx_workspace_bytes_autoregressive is the (smaller) amount gvx_encoder_forward + gvx_decoder_autoregressive +
- * gvx_postnet_forward need for max_steps frames (it leaves out the per-step buffers only the teacher-forced loop uses). */
+ * gvx_postnet_forward need for max_steps frames (it leaves out the per-step buffers only the teacher-forced loop uses).
+ * 0 for B, L or T below 1.  Contents and clearing: Conventions, "Workspaces and scratch" (GVX_WORKSPACE_CLEAR_BYTES once; the
+ * rest may hold anything).  Positive multiples of 256 that never shrink with T - and are not monotone in B or L. */
 size_t gvx_workspace_bytes(const gvx_model* model, int B, int L, int T);
 size_t gvx_workspace_bytes_autoregressive(const gvx_model* model, int B, int L, int max_steps);
 
@@ -193,7 +219,8 @@ int gvx_decoder_autoregressive(gvx_model* model, const float* memory, const int3
  * path, no per-call batch limit).  mel_lengths: int32 [B] or NULL.  With lengths, row b is processed as a
  * sequence of mel_lengths[b] frames (the convolutions see zeros from that frame on, as a batch-1 run of the
  * reference sees its zero padding) and mel_post_out is 0 there.  The workspace needs
- * gvx_postnet_workspace_bytes(B, T) bytes (a gvx_workspace_bytes(B, L, T) workspace is always large enough). */
+ * gvx_postnet_workspace_bytes(B, T) bytes (a gvx_workspace_bytes(B, L, T) workspace is always large enough); a model workspace
+ * in the sense of the Conventions ("Workspaces and scratch"): GVX_WORKSPACE_CLEAR_BYTES zeroed once, the rest may hold anything. */
 size_t gvx_postnet_workspace_bytes(const gvx_model* model, int B, int T);
 int gvx_postnet_forward(gvx_model* model, const float* mel_in, const int32_t* mel_lengths, int B, int T, float* mel_post_out,
                         void* workspace, size_t workspace_bytes, void* stream);
@@ -219,7 +246,8 @@ int gvx_tacotron2_forward(gvx_model* model, const int64_t* tokens, const int32_t
  *   gate_loss = mean(BCE-with-logits(gate_out, gate_target))                          over all B*T elements,
  *   loss = mel_loss + gate_loss.
  * All tensors are the [B, n_mels, T] / [B, T] device arrays of the forward call; forward only (no gradients).
- * scratch: >= 6144 bytes of device memory, 8-byte aligned (float64 partial sums of the two-stage reduction). */
+ * scratch: >= 6144 bytes of device memory, 8-byte aligned (float64 partial sums of the two-stage reduction); it may hold
+ * anything and needs no clearing (Conventions, "Workspaces and scratch"); 6143 bytes are GVX_ERR_WORKSPACE. */
 int gvx_tacotron2_loss(const float* mel_out, const float* mel_post_out, const float* gate_out, const float* mel_target,
                        const float* gate_target, int B, int n_mels, int T, float* loss_out, void* scratch, size_t scratch_bytes,
                        void* stream);
@@ -263,6 +291,8 @@ int gvx_decoder_teacher_forced_train(gvx_model* model, const float* memory, cons
  * same (B, L, T), row-major: what 0 = decoder input frames [(T+1) B, n_mels] (row t B + b; frame 0 = zeros), 1 = Prenet layer-1
  * output [(T+1) B, prenet_dim], 2 = Prenet output [(T+1) B, prenet_dim], 3 = processed memory [B, L, att_dim]. */
 int gvx_train_export(const gvx_model* model, const void* workspace, size_t workspace_bytes, int B, int L, int T, int what, float* dst, void* stream);
+/* `saved` and the workspace of the two calls below: no clearing, any contents (Conventions, "Workspaces and scratch"); the backward
+ * reads of `saved` only what the forward of the same shape wrote there. */
 size_t gvx_conv_train_saved_bytes(int B, int Cin, int Cout, int T, int k);
 size_t gvx_conv_train_workspace_bytes(int B, int Cin, int Cout, int T, int k);
 /* y = dropout(act(BatchNorm_train(conv1d(x, w, bias, padding (k-1)/2)))).  running_mean / running_var (may be NULL) get the
@@ -296,7 +326,8 @@ int gvx_tacotron2_loss_backward(const float* mel_out, const float* mel_post_out,
  * the two recurrences are single calls (gvx_train_decoder_bptt, gvx_train_encoder_lstm_bptt below).  Row-major fp32 with
  * explicit leading dimensions; LSTM gates in torch order i, f, g, o. */
 /* C[m][n] = sum_k A[m * lda + k] W[n * ldw + k] (+ bias[n]), K % 4 == 0.  scratch (may be NULL): device scratch for split-K
- * partial tiles, used when the product has few output tiles and a long K. */
+ * partial tiles, used when the product has few output tiles and a long K.  It may hold anything; the call writes at most
+ * scratch_bytes of it and takes fewer K pieces (down to no split) when it is small: a short scratch is no error here. */
 int gvx_train_gemm_nt(const float* A, long lda, const float* W, long ldw, float* C, long ldc, int M, int N, int K, const float* bias,
                       float* scratch, size_t scratch_bytes, void* stream);
 /* C[m][n] = sum_r A[r * lda + m] Bm[r * ldb + n] (a weight gradient: the sum over the rows of two activation matrices, no
@@ -314,7 +345,7 @@ int gvx_train_embedding_backward(const int64_t* tokens, const float* dx, long n_
  * update of all of them. */
 typedef struct gvx_tensor_ref { const float* data; int64_t numel; } gvx_tensor_ref;
 typedef struct gvx_adam_ref { float* param; const float* grad; float* exp_avg; float* exp_avg_sq; int64_t numel; } gvx_adam_ref;
-size_t gvx_train_sqnorm_scratch_bytes(int n_tensors);
+size_t gvx_train_sqnorm_scratch_bytes(int n_tensors);   /* any contents, no clearing; the call writes exactly these bytes */
 int gvx_train_sqnorm_many(const gvx_tensor_ref* refs_device, int n_tensors, double* scratch, double* sumsq_out, void* stream);
 int gvx_train_adam_step_many(const gvx_adam_ref* refs_device, int n_tensors, float grad_scale, float lr, float weight_decay, float beta1,
                              float beta2, float eps, int step, void* stream);
@@ -363,7 +394,7 @@ typedef struct gvx_bptt_decoder_args {
     float* dloc_dense;                  /* out [a][F] */
     float* dloc_conv;                   /* out [F][2][kl] */
 } gvx_bptt_decoder_args;
-size_t gvx_train_decoder_bptt_workspace_bytes(const gvx_bptt_decoder_args* args);
+size_t gvx_train_decoder_bptt_workspace_bytes(const gvx_bptt_decoder_args* args);   /* any contents, no clearing (Conventions) */
 int gvx_train_decoder_bptt(const gvx_bptt_decoder_args* args, void* workspace, size_t workspace_bytes, void* stream);
 /* The same call with a gradient taken DIRECTLY on the alignments (a loss that looks at them, such as the guided attention loss
  * below): dw_ext holds d loss / d w_t[b][l], element (t, b, l) at dw_ext + t * dw_ext_ts + b * dw_ext_bs + l (strides in floats,
@@ -386,7 +417,7 @@ int gvx_train_decoder_bptt_ext(const gvx_bptt_decoder_args* args, const float* d
  * from the exact integer l T_b - t L_b, G as -expm1(-x)) and exactly 0 on a row's diagonal; the sum runs over float64 partials
  * in a fixed order: two calls are bit-equal.  sigma > 0, alpha >= 0, B, T, L >= 1 (GVX_ERR_INVALID_ARG otherwise, also for a NULL
  * pointer other than dalign); scratch: gvx_guided_attention_loss_scratch_bytes, 8-byte aligned (GVX_ERR_WORKSPACE). */
-size_t gvx_guided_attention_loss_scratch_bytes(int B, int T, int L);
+size_t gvx_guided_attention_loss_scratch_bytes(int B, int T, int L);   /* any contents, no clearing (Conventions) */
 int gvx_guided_attention_loss(const float* align, const int32_t* token_lengths, const int32_t* mel_lengths, int B, int T, int L,
                               float sigma, float alpha, float* loss_out, float* dalign, void* scratch, size_t scratch_bytes,
                               void* stream);
@@ -396,7 +427,7 @@ int gvx_guided_attention_loss(const float* align, const int32_t* token_lengths, 
  * belongs to (zeros past a row's length): dg_pos [2][B][L][4H] gate gradients, hprev_pos [2][B][L][H] the step's previous
  * hidden state - the operands of the weight gradients and of d loss / d x.  Any B >= 1 (rows beyond 32 take further trips of
  * the kernels' row loop), lengths in [1, L], H a multiple of 8 up to 1280 (LDS). */
-size_t gvx_train_encoder_lstm_bptt_workspace_bytes(int B, int H);
+size_t gvx_train_encoder_lstm_bptt_workspace_bytes(int B, int H);   /* any contents, no clearing: both calls reset their flag lines and status word */
 int gvx_train_encoder_lstm_bptt(const float* xg, const float* memory, const float* cell_states, const float* dmemory, const float* w_hh,
                                 const int32_t* lengths, int B, int L, int H, float* dg_pos, float* hprev_pos, void* workspace,
                                 size_t workspace_bytes, void* stream);
@@ -433,7 +464,7 @@ void gvx_gl_plan_destroy(gvx_gl_plan* plan);
  * gvx_wav_to_mel and a region of n_mels * ((bins + 3) & ~3) floats for gvx_wav_to_mel's zero-padded mel basis, whose size does
  * not depend on B*T: gvx_wav_to_mel serves any B*T >= 1 (one file of one frame included).  n_mels = 0 sizes the calls that take
  * no mel (gvx_stft, gvx_istft, gvx_griffin_lim). */
-size_t gvx_gl_workspace_bytes(gvx_gl_plan* plan, int B, int T, int n_mels);
+size_t gvx_gl_workspace_bytes(gvx_gl_plan* plan, int B, int T, int n_mels);   /* any contents, no clearing (Conventions, "Workspaces and scratch") */
 
 /* stft (utils/audio/base.py:58-69): signal [B][n_samples] -> spec_out complex [B][bins][T], T = (n_samples-n_fft)/hop+1 */
 int gvx_stft(gvx_gl_plan* plan, const float* signal, const float* window, int B, long n_samples, float* spec_out,
@@ -456,7 +487,7 @@ int gvx_wav_to_mel(gvx_gl_plan* plan, const float* signal, const float* window, 
                    int n_mels, int log10_kind, float ref, float* mel_db_out, void* workspace, size_t workspace_bytes, void* stream);
 /* tail of convert_mel2wav (core/processors.py:91-95): samples with |y| > 1 -> 0, drop `trim` samples at both ends,
  * divide by the peak (float32), IIR filter b/a (HOST doubles, order+1 each; scipy.signal.lfilter semantics, float64).
- * out: float64 [B][n_samples - 2*trim]; scratch_B: B uint32 of device scratch. */
+ * out: float64 [B][n_samples - 2*trim]; scratch_B: B uint32 of device scratch (any contents; the call clears and writes exactly B words). */
 int gvx_wav_finalize(const float* wav, int B, long n_samples, int trim, const double* b_coef, const double* a_coef, int order,
                      double* out, unsigned int* scratch_B, void* stream);
 
@@ -611,7 +642,7 @@ int gvx_mel_project(const float* mel, int B, int M, int T, const float* P, int K
  * GVX_ERR_UNSUPPORTED (the size function then returns 0); a NULL cp, cg or dist_out, or B, Tp_max, Tg_max or K below 1:
  * GVX_ERR_INVALID_ARG; a missing or short workspace: GVX_ERR_WORKSPACE; all of it checked before anything is launched. */
 enum { GVX_DTW_MAX_FRAMES = 32768, GVX_DTW_MAX_FEATURES = 256 };
-size_t gvx_dtw_workspace_bytes(int B, int Tp_max, int Tg_max, int K);
+size_t gvx_dtw_workspace_bytes(int B, int Tp_max, int Tg_max, int K);   /* any contents, no clearing; 0: not needed OR refused (uses_lds_tables: 1 / -1) */
 int gvx_dtw_uses_lds_tables(int Tp_max, int Tg_max, int K);
 int gvx_dtw_distance(const float* cp, const float* cg, const int32_t* pred_lengths, const int32_t* target_lengths, int B, int Tp_max,
                      int Tg_max, int K, float* dist_out, float* acc_out, void* workspace, size_t workspace_bytes, void* stream);

@@ -173,9 +173,22 @@ def _dec_shapes(B, L, T, sizes):
             "dv": (a,), "dloc_dense": (a, Fn), "dloc_conv": (Fn, 2, kl)}
 
 
-def run_decoder(lib, B, L, T, sizes, inputs, dense_ctx=True, expect=0, ws_mutate=None, args_mutate=None):
+def _junk_workspace(nbytes, slack):
+    """nbytes of finite junk with `slack` words of sentinel behind them (_slack_intact)."""
+    ws = torch.linspace(-3.0, 5.0, nbytes // 4 + slack, device="cuda")
+    ws.view(torch.int32)[nbytes // 4:] = SENTINEL
+    return ws
+
+
+def _slack_intact(ws, nbytes):
+    return bool((ws.view(torch.int32).flatten()[nbytes // 4:] == SENTINEL).all())
+
+
+def run_decoder(lib, B, L, T, sizes, inputs, dense_ctx=True, expect=0, ws_mutate=None, args_mutate=None, ws=None, dw_ext=None):
     """One gvx_train_decoder_bptt call.  ctx_all goes in as a dense [T][B][E] array (dense_ctx) or as the columns D .. D + E of a
     [T][B][D + E] array, the layout of the training forward's tape.  dpm and the workspace are handed over full of finite junk.
+    ws: a workspace of the caller's (a byte tensor of at least the queried size) in place of the junk-filled one.  dw_ext [T][B][L]:
+    the call goes through gvx_train_decoder_bptt_ext with that gradient on the alignments.
     Returns (status, outputs as {name: _Out}, workspace bytes the size query gave)."""
     A, D, E, P, a, Fn, kl = sizes
     dev = {k: x.cuda() for k, x in inputs.items()}
@@ -200,13 +213,19 @@ def run_decoder(lib, B, L, T, sizes, inputs, dense_ctx=True, expect=0, ws_mutate
         ap = None                                                            # (a NULL argument block)
     wsb = lib.gvx_train_decoder_bptt_workspace_bytes(ap)
     ws_n = max(wsb, 256)
-    ws = torch.linspace(-3.0, 5.0, ws_n // 4 + 128, device="cuda")          # finite junk: the call clears what it accumulates into
+    if ws is None:
+        ws = _junk_workspace(ws_n, 128)                                      # finite junk: the call clears what it accumulates into
     ws_ptr, ws_bytes = ws.data_ptr(), wsb
     if ws_mutate:
         ws_ptr, ws_bytes = ws_mutate(ws_ptr, wsb)
-    rc = lib.gvx_train_decoder_bptt(ap, ws_ptr, ws_bytes, _stream())
+    if dw_ext is None:
+        rc = lib.gvx_train_decoder_bptt(ap, ws_ptr, ws_bytes, _stream())
+    else:
+        dw_dev = dw_ext.cuda()
+        rc = lib.gvx_train_decoder_bptt_ext(ap, dw_dev.data_ptr(), B * L, L, ws_ptr, ws_bytes, _stream())
     torch.cuda.synchronize()
     assert rc == expect, (rc, lib.gvx_last_error())
+    assert _slack_intact(ws, ws_n), "the call wrote behind its workspace"
     return rc, outs, wsb
 
 
@@ -387,19 +406,21 @@ def encoder_reference(case):
     return _ENC_REF[case.name]
 
 
-def run_encoder(lib, case, inputs, resident, expect=0, B=None, L=None, H=None, short_ws=0):
+def run_encoder(lib, case, inputs, resident, expect=0, B=None, L=None, H=None, short_ws=0, ws=None):
     B0, L0, H0 = case.B, case.L, case.H
     dev = {k: x.cuda() for k, x in inputs.items()}
     outs = {"dg_pos": _Out((2, B0, L0, 4 * H0)), "hprev_pos": _Out((2, B0, L0, H0))}
     wsb = lib.gvx_train_encoder_lstm_bptt_workspace_bytes(B0, H0)
     assert wsb > 0
-    ws = torch.linspace(-3.0, 5.0, wsb // 4 + 64, device="cuda")
+    if ws is None:
+        ws = _junk_workspace(wsb, 64)
     fn = lib.gvx_train_encoder_lstm_bptt_resident if resident else lib.gvx_train_encoder_lstm_bptt
     rc = fn(dev["xg"].data_ptr(), dev["memory"].data_ptr(), dev["cell_states"].data_ptr(), dev["dmemory"].data_ptr(), dev["w_hh"].data_ptr(),
             dev["lengths"].data_ptr(), B0 if B is None else B, L0 if L is None else L, H0 if H is None else H, outs["dg_pos"].t.data_ptr(),
             outs["hprev_pos"].t.data_ptr(), ws.data_ptr(), wsb - short_ws, _stream())
     torch.cuda.synchronize()
     assert rc == expect, (rc, lib.gvx_last_error())
+    assert _slack_intact(ws, wsb), "the call wrote behind its workspace"
     if rc == 0:
         code = C.c_int(-1)
         assert lib.gvx_train_encoder_lstm_bptt_status(ws.data_ptr(), wsb, B0, H0, C.byref(code), _stream()) == 0 and code.value == 0, code.value

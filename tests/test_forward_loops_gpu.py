@@ -114,7 +114,15 @@ def _handle(lib, cfgs_key, cfgs, wset, env, setter=None):
 
 
 def _workspace(nbytes):
-    return torch.zeros(nbytes // 4 + 64, dtype=torch.float32, device="cuda")
+    """A fresh zero-filled workspace of nbytes with 256 bytes of sentinel behind it (_slack_intact)."""
+    ws = torch.zeros(nbytes // 4 + 64, dtype=torch.float32, device="cuda")
+    ws.view(torch.int32)[nbytes // 4:] = SENTINEL
+    return ws
+
+
+def _slack_intact(ws, nbytes):
+    """Nothing was written behind the nbytes the call was told about (a workspace handed in from outside may end right there)."""
+    return bool((ws.view(torch.int32).flatten()[nbytes // 4:] == SENTINEL).all())
 
 
 def _status_clean(lib, h, ws, nbytes):
@@ -218,28 +226,33 @@ def _tf_shapes(mc, ac, B, L, T, mode):
     return s
 
 
-def run_tf(lib, h, cfgs, case, dev, ws=None, expect=0):
-    """One gvx_decoder_teacher_forced(_train) call into fresh junk-filled outputs.  Returns ({name: _Out}, workspace)."""
+def run_tf(lib, h, cfgs, case, dev, ws=None, expect=0, ws_bytes=None):
+    """One gvx_decoder_teacher_forced(_train) call into fresh junk-filled outputs.  Returns ({name: _Out}, workspace).  ws_bytes: the
+    size the call is told (default: what the query gives); a refused call (expect != 0) returns behind the border checks."""
     mc, ac, _ = cfgs
     B, L, T = case.B, case.L, case.T
     outs = {k: _Out(s, junk=True) for k, s in _tf_shapes(mc, ac, B, L, T, case.mode).items()}
     nbytes = lib.gvx_workspace_bytes(h, B, L, T)
     assert nbytes > 0
     ws = _workspace(nbytes) if ws is None else ws
+    told = nbytes if ws_bytes is None else ws_bytes
     p = lambda k: outs[k].t.data_ptr() if k in outs else None
     if case.mode:
         p_att, p_dec = (P_ATT, P_DEC) if case.drop else (0.0, 0.0)
         rc = lib.gvx_decoder_teacher_forced_train(h, dev["memory"].data_ptr(), dev["lengths"].data_ptr(), B, L, dev["mel_in"].data_ptr(), T,
                                                   dev["keep"].data_ptr(), dev["att_keep"].data_ptr(), dev["dec_keep"].data_ptr(), p_att, p_dec,
                                                   p("mel"), p("gate"), p("align"), p("h_a"), p("c_a"), p("c_d"), p("hc"), p("pre_a"), p("pre_d"),
-                                                  ws.data_ptr(), nbytes, _stream())
+                                                  ws.data_ptr(), told, _stream())
     else:
         rc = lib.gvx_decoder_teacher_forced(h, dev["memory"].data_ptr(), dev["lengths"].data_ptr(), B, L, dev["mel_in"].data_ptr(), T,
-                                            dev["keep"].data_ptr(), p("mel"), p("gate"), p("align"), ws.data_ptr(), nbytes, _stream())
+                                            dev["keep"].data_ptr(), p("mel"), p("gate"), p("align"), ws.data_ptr(), told, _stream())
     torch.cuda.synchronize()
     assert rc == expect, (case.name, rc, lib.gvx_last_error())
     for k, o in outs.items():
         assert o.border_intact(), f"{case.name}: the call wrote outside {k}"
+    assert _slack_intact(ws, nbytes), f"{case.name}: the call wrote behind its workspace"
+    if expect:
+        return outs, ws
     assert _status_clean(lib, h, ws, nbytes), f"{case.name}: a status word of the workspace is set"
     return outs, ws
 
@@ -335,7 +348,7 @@ def _ar_reference(case, cfgs, wset):
     return _REF[key]
 
 
-def run_ar(lib, h, cfgs, case, dev, thr, ws=None):
+def run_ar(lib, h, cfgs, case, dev, thr, ws=None, expect=0, ws_bytes=None):
     mc, ac, _ = cfgs
     B, L, S, M = case.B, case.L, case.T, ac.n_mels
     outs = {"mel": _Out((B, M, S), junk=True), "gate": _Out((B, S), junk=True), "align": _Out((B, S, L), junk=True)}
@@ -346,12 +359,15 @@ def run_ar(lib, h, cfgs, case, dev, thr, ws=None):
     steps = C.c_int(-1)
     rc = lib.gvx_decoder_autoregressive(h, dev["memory"].data_ptr(), dev["lengths"].data_ptr(), B, L, S, thr, dev["keep"].data_ptr(),
                                         outs["mel"].t.data_ptr(), outs["gate"].t.data_ptr(), outs["align"].t.data_ptr(),
-                                        nf[GUARD:].data_ptr(), C.byref(steps), ws.data_ptr(), nbytes, _stream())
+                                        nf[GUARD:].data_ptr(), C.byref(steps), ws.data_ptr(), nbytes if ws_bytes is None else ws_bytes, _stream())
     torch.cuda.synchronize()
-    assert rc == 0, (case.name, rc, lib.gvx_last_error())
+    assert rc == expect, (case.name, rc, lib.gvx_last_error())
     for k, o in outs.items():
         assert o.border_intact(), f"{case.name}: the call wrote outside {k}"
     assert bool((nf[:GUARD] == SENTINEL).all()) and bool((nf[GUARD + B:] == SENTINEL).all()), f"{case.name}: the call wrote outside n_frames_out"
+    assert _slack_intact(ws, nbytes), f"{case.name}: the call wrote behind its workspace"
+    if expect:
+        return outs, nf[GUARD:GUARD + B].cpu(), steps.value, ws
     assert _status_clean(lib, h, ws, nbytes), f"{case.name}: a status word of the workspace is set"
     return outs, nf[GUARD:GUARD + B].cpu(), steps.value, ws
 
@@ -423,7 +439,7 @@ def _enc_reference(case, wset):
     return _REF[key]
 
 
-def run_encoder_lstm(lib, h, case, dev, tapes, ws=None):
+def run_encoder_lstm(lib, h, case, dev, tapes, ws=None, expect=0, ws_bytes=None):
     B, L, H = case.B, case.L, case.H
     outs = {"memory": _Out((B, L, 2 * H), junk=True)}
     if tapes:
@@ -432,11 +448,14 @@ def run_encoder_lstm(lib, h, case, dev, tapes, ws=None):
     ws = _workspace(nbytes) if ws is None else ws
     rc = lib.gvx_encoder_lstm_forward(h, dev["conv"].data_ptr(), dev["lengths"].data_ptr(), B, L, outs["memory"].t.data_ptr(),
                                       outs["cells"].t.data_ptr() if tapes else None, outs["xg"].t.data_ptr() if tapes else None,
-                                      ws.data_ptr(), nbytes, _stream())
+                                      ws.data_ptr(), nbytes if ws_bytes is None else ws_bytes, _stream())
     torch.cuda.synchronize()
-    assert rc == 0, (case.name, rc, lib.gvx_last_error())
+    assert rc == expect, (case.name, rc, lib.gvx_last_error())
     for k, o in outs.items():
         assert o.border_intact(), f"{case.name}: the call wrote outside {k}"
+    assert _slack_intact(ws, nbytes), f"{case.name}: the call wrote behind its workspace"
+    if expect:
+        return outs, ws
     assert _status_clean(lib, h, ws, nbytes), case.name
     return outs, ws
 
@@ -482,6 +501,7 @@ def test_whole_encoder_against_float64(lib, B, L):
         rc = lib.gvx_encoder_forward(h, tok.data_ptr(), ln.data_ptr(), B, L, out.t.data_ptr(), ws.data_ptr(), nbytes, _stream())
         torch.cuda.synchronize()
         assert rc == 0 and out.border_intact() and _status_clean(lib, h, ws, nbytes), (rc, lib.gvx_last_error())
+        assert _slack_intact(ws, nbytes), "gvx_encoder_forward wrote behind its workspace"
         _compare("enc_whole", out.t.transpose(0, 1), want.transpose(0, 1), f"whole_{B}x{L}/{wset[0]}")
         assert bool((out.t[fr.pad_mask(lengths, L).cuda()] == 0).all())
 
