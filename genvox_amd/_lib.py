@@ -62,6 +62,7 @@ SIGNATURES = {
     "gvx_encoder_forward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
     "gvx_decoder_teacher_forced": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "gvx_decoder_autoregressive": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i), _vp, _sz, _vp]),
+    "gvx_decoder_autoregressive_windowed": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i), _vp, _sz, _vp, _i, _i, _vp]),
     "gvx_postnet_workspace_bytes": (_sz, [_vp, _i, _i]),
     "gvx_postnet_forward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
     "gvx_mask_padding": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
@@ -128,6 +129,7 @@ SIGNATURES = {
     "gvx_teacher_forced_resident": (_i, [_vp, _i, _i]),
     "gvx_teacher_forced_loop_kind": (_i, [_vp, _i, _i]),
     "gvx_autoregressive_loop_kind": (_i, [_vp, _i, _i]),
+    "gvx_autoregressive_windowed_loop_kind": (_i, [_vp, _i, _i]),
     "gvx_kernel_times_ms": (_i, [_vp, C.POINTER(_f), C.POINTER(_f), C.POINTER(_i)]),
 }
 

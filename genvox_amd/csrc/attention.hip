@@ -54,7 +54,8 @@ __host__ __device__ inline EnergyLds energy_lds_layout(int a) {
 // loc were produced by extra workgroups of the preceding LSTM launch (skinny.hip, loc_body); q is the sum of that
 // launch's per-tile partial slabs.  What is left here is one round trip of coalesced loads, a+L tanh per position and
 // a 64-lane reduction.
-template <int DPL>
+// WIN: the monotonic attention window of the autoregressive decode (AttnParams.c_out, attn_step_body.h).
+template <int DPL, bool WIN = false>
 __global__ __launch_bounds__(EN_THREADS) void attn_energy_kernel(AttnParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int L = p.L, a = p.a;
@@ -69,6 +70,11 @@ __global__ __launch_bounds__(EN_THREADS) void attn_energy_kernel(AttnParams p) {
     const int l_begin = g * Lg, l_end = min(L, l_begin + Lg);
     if (l_begin >= l_end) return;  // uniform per workgroup
     const int len = p.lengths ? p.lengths[b] : L;
+    int w_lo = 0, w_hi = 0;   // (WIN) first and last position of the window
+    if (WIN) {
+        const int c = p.c_prev ? p.c_prev[(long)b * p.c_bs] : 0;
+        w_lo = c - p.win_back; w_hi = c + p.win_ahead;
+    }
     GVX_STAMP(1, 0);
 
     // ---- issue all loads of the first pass up front (each dependent round trip to fresh data costs ~1 us)
@@ -157,7 +163,8 @@ __global__ __launch_bounds__(EN_THREADS) void attn_energy_kernel(AttnParams p) {
             s += __shfl_xor(s, 4);
             s += __shfl_xor(s, 8);
             const int l = l0 + ll;
-            if (sg == 0 && ll < lc) p.energies[(long)b * L + l] = l < len ? s : -INFINITY;
+            if (WIN) { if (sg == 0 && ll < lc) p.energies[(long)b * L + l] = (l < len && l >= w_lo && l <= w_hi) ? s : -INFINITY; }
+            else if (sg == 0 && ll < lc) p.energies[(long)b * L + l] = l < len ? s : -INFINITY;
         }
         __syncthreads();
         GVX_STAMP(1, 4);
@@ -177,6 +184,7 @@ __host__ __device__ inline ContextLds context_lds_layout(int L) {
 constexpr int CX_EV = 4;    // energies per lane held in registers (rows up to 256 positions; longer rows re-read)
 constexpr int CX_MV = 16;   // memory float4 loads in flight per thread
 
+template <bool WIN>   // WIN: slice 0 also stores the row's next centre, the lowest index at which the new weights are largest
 __global__ __launch_bounds__(AT_THREADS) void attn_context_kernel(AttnParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int L = p.L, E = p.E, B = p.B;
@@ -225,6 +233,8 @@ __global__ __launch_bounds__(AT_THREADS) void attn_context_kernel(AttnParams p) 
         s = wave_sum(s);
         const float inv = 1.f / s;
         if (wave == 0) {
+            float bw = -1.f;
+            int bl = 0;
 #pragma unroll
             for (int i = 0; i < CX_EV; ++i) {
                 const int l = lane + 64 * i;
@@ -235,6 +245,7 @@ __global__ __launch_bounds__(AT_THREADS) void attn_context_kernel(AttnParams p) 
                         p.w_out[(long)b * p.w_out_bs + l] = w;
                         p.w_cum[(long)b * L + l] += w;
                     }
+                    if (WIN && w > bw) { bw = w; bl = l; }
                 }
             }
             for (int l = lane + 64 * CX_EV; l < L; l += 64) {
@@ -244,6 +255,11 @@ __global__ __launch_bounds__(AT_THREADS) void attn_context_kernel(AttnParams p) 
                     p.w_out[(long)b * p.w_out_bs + l] = w;
                     p.w_cum[(long)b * L + l] += w;
                 }
+                if (WIN && w > bw) { bw = w; bl = l; }
+            }
+            if (WIN && g == 0) {
+                const int cn = wave_argmax_first(bw, bl);
+                if (lane == 0) p.c_out[(long)b * p.c_bs] = cn;
             }
         }
     }
@@ -290,6 +306,8 @@ __global__ __launch_bounds__(AT_THREADS) void attn_context_kernel(AttnParams p) 
 // workgroups of a weight-streaming launch (skinny.hip, ar_attn_tiles_kernel).
 template <int NJ>
 __global__ __launch_bounds__(MA_THREADS) void attn_step_kernel(AttnParams p) { attn_step_body<NJ>(p, (int)blockIdx.x); }
+template <int NJ>   // the step of a decode with a monotonic attention window
+__global__ __launch_bounds__(MA_THREADS) void attn_step_win_kernel(AttnParams p) { attn_step_body<NJ, MA_MV, true>(p, (int)blockIdx.x); }
 
 // context-column slices per row for the one-launch step: aim at one workgroup per CU (256), at least 8 float4 columns each
 int attention_slices(int B, int E) {
@@ -311,8 +329,18 @@ bool attention_supported(int L, int a, int F, int kl, int E) {
     return lds_c <= 160 * 1024 && lds_s <= 160 * 1024 && (size_t)(2 * (L + kl) + 2 * kl * 32 + 32 * 32 + 8) * sizeof(float) <= 160 * 1024;
 }
 
+template <typename K>
+static hipError_t at_set_lds(K kern) {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+}
+
 hipError_t attention_init() {
     hipError_t e;
+    if ((e = at_set_lds(attn_energy_kernel<1, true>)) != hipSuccess || (e = at_set_lds(attn_energy_kernel<2, true>)) != hipSuccess ||
+        (e = at_set_lds(attn_energy_kernel<4, true>)) != hipSuccess || (e = at_set_lds(attn_context_kernel<true>)) != hipSuccess ||
+        (e = at_set_lds(attn_step_win_kernel<1>)) != hipSuccess || (e = at_set_lds(attn_step_win_kernel<4>)) != hipSuccess ||
+        (e = at_set_lds(attn_step_win_kernel<8>)) != hipSuccess)
+        return e;
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_energy_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_energy_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -325,14 +353,18 @@ hipError_t attention_init() {
     if (e != hipSuccess) return e;
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_step_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(attn_context_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(attn_context_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
 
 hipError_t launch_attention_step(const AttnParams& p, hipStream_t s) {
     if (!attention_supported(p.L, p.a, p.F, p.kl, p.E) || p.G < 1) return hipErrorInvalidValue;
     const size_t lds = (size_t)step_lds_layout(p.a, p.L).total * sizeof(float);
     const dim3 grid(8 * ((p.B + 7) / 8) * p.G), block(MA_THREADS);
-    if (p.a <= 32) attn_step_kernel<1><<<grid, block, lds, s>>>(p);
+    if (p.c_out) {
+        if (p.a <= 32) attn_step_win_kernel<1><<<grid, block, lds, s>>>(p);
+        else if (p.a <= 128) attn_step_win_kernel<4><<<grid, block, lds, s>>>(p);
+        else attn_step_win_kernel<8><<<grid, block, lds, s>>>(p);
+    } else if (p.a <= 32) attn_step_kernel<1><<<grid, block, lds, s>>>(p);
     else if (p.a <= 128) attn_step_kernel<4><<<grid, block, lds, s>>>(p);
     else attn_step_kernel<8><<<grid, block, lds, s>>>(p);
     return hipGetLastError();
@@ -344,12 +376,17 @@ hipError_t launch_attention(const AttnParams& p, hipStream_t s) {
     const size_t lds_c = (size_t)context_lds_layout(p.L).total * sizeof(float);
     const dim3 grid(p.G, p.B), block(AT_THREADS), eblock(EN_THREADS);
     const int dpl = (p.a + 63) / 64;
-    if (dpl == 1) attn_energy_kernel<1><<<grid, eblock, lds_e, s>>>(p);
+    if (p.c_out) {
+        if (dpl == 1) attn_energy_kernel<1, true><<<grid, eblock, lds_e, s>>>(p);
+        else if (dpl == 2) attn_energy_kernel<2, true><<<grid, eblock, lds_e, s>>>(p);
+        else attn_energy_kernel<4, true><<<grid, eblock, lds_e, s>>>(p);
+    } else if (dpl == 1) attn_energy_kernel<1><<<grid, eblock, lds_e, s>>>(p);
     else if (dpl == 2) attn_energy_kernel<2><<<grid, eblock, lds_e, s>>>(p);
     else attn_energy_kernel<4><<<grid, eblock, lds_e, s>>>(p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    attn_context_kernel<<<grid, block, lds_c, s>>>(p);
+    if (p.c_out) attn_context_kernel<true><<<grid, block, lds_c, s>>>(p);
+    else attn_context_kernel<false><<<grid, block, lds_c, s>>>(p);
     return hipGetLastError();
 }
 

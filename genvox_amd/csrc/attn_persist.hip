@@ -98,6 +98,13 @@ __device__ __forceinline__ float wave_max_dpp(float v) {
     return fmaxf(fmaxf(lane_bcast(v, 0), lane_bcast(v, 16)), fmaxf(lane_bcast(v, 32), lane_bcast(v, 48)));
 }
 
+__device__ __forceinline__ int wave_argmax_first(float bw, int bl) {   // as attn_step_body.h: the lowest index of the largest weight
+    const float m = wave_max_dpp(bw);
+    int cand = bw == m ? bl : 0x7fffffff;
+    for (int off = 32; off > 0; off >>= 1) cand = min(cand, __shfl_xor(cand, off, 64));
+    return cand;
+}
+
 // One WAVE waits until every one of the n (<= 128) flag words (one per 128-byte line) reads >= target: two words per lane per look.  Bounded like
 // handoff_wait<true>; returns false (wave-uniform) when the wait was given up, by a time-out here or anywhere else, or by the
 // host's stop word.  (Two looks in flight half a round trip apart were measured: no gain - 22.07 vs 21.68 us per autoregressive step.)
@@ -146,8 +153,13 @@ namespace { __device__ unsigned long long pa_row_stamps[64][8]; __device__ unsig
 // projection slabs of the decoder-LSTM tiles into the frame + gate of the step (Decoder.decode's linear projection and gate
 // layer, models/tts/tacotron2.py:360-362), runs the stop test (:401-406) and Prenet layer 1 on the frame (:176-179) and hands
 // that to the 8 workgroups of layer 2.  Same arithmetic and summation orders as ar_project_fast_kernel (misc.hip).
-template <int SPG, bool SPLIT, bool AR = false>
+// WIN (autoregressive role, one workgroup per row): the decode's monotonic attention window.  Position l takes part in the softmax iff
+// l < len and c - back <= l <= c + ahead; the row's centre c (0 at step 0) lives in LDS - word 1 of the flag words - for the whole
+// decode: wave 0 takes the argmax in the pass that writes the alignment row, stores it there and to centres[b][t].  A variant of
+// its own: the kernels without a window are the instantiations they were.
+template <int SPG, bool SPLIT, bool AR = false, bool WIN = false>
 __global__ __launch_bounds__(PA_THREADS) void attn_persistent_kernel(AttnPersistParams p) {
+    static_assert(!WIN || (AR && !SPLIT), "the window: autoregressive role, one workgroup per row");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* locf = smem + PA_OFF_LOC;
     float* fb = smem + PA_OFF_FB;
@@ -172,6 +184,7 @@ __global__ __launch_bounds__(PA_THREADS) void attn_persistent_kernel(AttnPersist
     unsigned* const tmo = p.sync + HANDOFF_TIMEOUT;
     const unsigned* const stop = p.sync + HANDOFF_STOP;
     if (tid == 0) *leave = 0;
+    if (WIN && tid == 0) leave[1] = 0;   // the row's centre
     if (tid == 0) __hip_atomic_fetch_add(p.sync + HANDOFF_READY, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // resident
 
     // ---- resident operands
@@ -396,7 +409,13 @@ __global__ __launch_bounds__(PA_THREADS) void attn_persistent_kernel(AttnPersist
             }
             float pe = pe2.x + pe2.y;
             pe = sum8(pe);
-            if (dg == 0) es[el] = el < len ? pe : -INFINITY;
+            if (WIN) {   // (the window's widths from the kernel-argument segment, like the role's other parameters)
+                typedef const __attribute__((address_space(4))) AttnPersistParams* KargPtr;
+                KargPtr kw = (KargPtr)__builtin_amdgcn_kernarg_segment_ptr();
+                asm volatile("" : "+s"(kw));
+                const int c = leave[1];
+                if (dg == 0) es[el] = (el < len && el >= c - kw->win_back && el <= c + kw->win_ahead) ? pe : -INFINITY;
+            } else if (dg == 0) es[el] = el < len ? pe : -INFINITY;
         }
         __syncthreads();
         PA_STAMP(3);
@@ -435,11 +454,18 @@ __global__ __launch_bounds__(PA_THREADS) void attn_persistent_kernel(AttnPersist
             o_ctx = acc;
         }
         if (!SPLIT && wave == 0) {   // alignment row out; previous / cumulative weights for the next location features
+            float bw = -1.f;
+            int bl = 0;
             for (int l = lane; l < L; l += 64) {
                 const float w = __expf(es[l] - mx) * inv;
                 p.w_out[(long)t * p.w_out_ts + (long)b * p.w_out_bs + l] = w;
                 wc[pad + l] = w;
                 wc[PA_WC_S + pad + l] += w;
+                if (WIN && w > bw) { bw = w; bl = l; }
+            }
+            if (WIN) {   // the next step's centre: kept in LDS (read behind the step's barriers), and out
+                const int cn = wave_argmax_first(bw, bl);
+                if (lane == 0) { leave[1] = cn; p.centres[(long)b * p.T + t] = cn; }
             }
         }
         PA_STAMP(4);
@@ -681,6 +707,7 @@ hipError_t attention_persistent_init() {
     if ((e = pa_set_lds(attn_persistent_kernel<3, false>)) != hipSuccess) return e;
     if ((e = pa_set_lds(attn_persistent_kernel<4, false>)) != hipSuccess) return e;
     if ((e = pa_set_lds(attn_persistent_kernel<3, false, true>)) != hipSuccess) return e;
+    if ((e = pa_set_lds(attn_persistent_kernel<3, false, true, true>)) != hipSuccess) return e;
     if ((e = pa_set_lds(attn_persistent_kernel<3, true, true>)) != hipSuccess) return e;
     if ((e = pa_set_lds(attn_persistent_kernel<3, true>)) != hipSuccess) return e;
     return pa_set_lds(attn_persistent_kernel<2, true>);
@@ -715,10 +742,14 @@ hipError_t launch_attention_persistent(const AttnPersistParams& p, hipStream_t s
         if (p.n_slabs != PA_SLABS || !p.q_flags || !p.ctx_flags || !p.p_flags || !p.y1_flags || !p.proj_b || !p.proj_out || !p.pre_w0_t || !p.keep0 ||
             !p.y1 || !p.n_frames || !p.n_done || p.n_mels < 1 || p.n_mels > 16 * PA_KPT || p.PSB < p.n_mels + 1 || p.PSB > 96 || (p.PSB & 3))
             return hipErrorInvalidValue;
+        if (p.centres && (p.L > PA_L || p.win_back < 0 || p.win_ahead < 0)) return hipErrorInvalidValue;   // (the window: one workgroup per row)
         if (p.L > PA_L) {
             if (!p.xchg || p.B > 16) return hipErrorInvalidValue;
             attn_persistent_kernel<3, true, true><<<dim3(2 * p.B), dim3(PA_THREADS), lds, s>>>(p);
-        } else attn_persistent_kernel<3, false, true><<<dim3(p.B), dim3(PA_THREADS), lds, s>>>(p);
+        } else if (p.centres) attn_persistent_kernel<3, false, true, true><<<dim3(p.B), dim3(PA_THREADS), lds, s>>>(p);
+        else attn_persistent_kernel<3, false, true><<<dim3(p.B), dim3(PA_THREADS), lds, s>>>(p);
+    } else if (p.centres) {
+        return hipErrorInvalidValue;
     } else if (p.L > PA_L) {
         if (!p.xchg) return hipErrorInvalidValue;
         if (p.n_slabs == 64) attn_persistent_kernel<2, true><<<dim3(2 * p.B), dim3(PA_THREADS), lds, s>>>(p);

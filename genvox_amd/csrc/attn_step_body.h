@@ -55,6 +55,16 @@ __device__ __forceinline__ float wave_max_dpp(float v) {
     return fmaxf(fmaxf(lane_bcast(v, 0), lane_bcast(v, 16)), fmaxf(lane_bcast(v, 32), lane_bcast(v, 48)));
 }
 
+// Lowest index at which a row's weights are largest (the tie rule of `positions`, eval_metrics.hip): every lane brings the best
+// (weight, index) of the positions it walked in ascending order; the result is uniform.  Weights are >= 0: a lane that walked
+// none brings -1.
+__device__ __forceinline__ int wave_argmax_first(float bw, int bl) {
+    const float m = wave_max_dpp(bw);
+    int cand = bw == m ? bl : 0x7fffffff;
+    for (int off = 32; off > 0; off >>= 1) cand = min(cand, __shfl_xor(cand, off, 64));
+    return cand;
+}
+
 struct StepLds { int qp_off, q_off, e_off, red_off, total; };
 __host__ __device__ inline StepLds step_lds_layout(int a, int L) {
     StepLds o;
@@ -68,7 +78,10 @@ __host__ __device__ inline StepLds step_lds_layout(int a, int L) {
     return o;
 }
 
-template <int NJ, int MV = MA_MV>   // NJ: float4 groups of the attention dim per lane (8 lanes share a position): a <= 32 * NJ;
+// WIN (autoregressive decode with a monotonic attention window, AttnParams.c_out): position l takes part in the softmax iff
+// l < len and c - back <= l <= c + ahead, c = the row's centre (the argmax of the previous step's weights, 0 at step 0); the
+// workgroup that writes the alignment row also stores the new centre.
+template <int NJ, int MV = MA_MV, bool WIN = false>   // NJ: float4 groups of the attention dim per lane (8 lanes share a position): a <= 32 * NJ;
                                     // MV: memory float4 loads per thread in flight (the launch shared with tiles keeps fewer registers)
 __device__ __forceinline__ void attn_step_body(const AttnParams& p, const int block_id) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -101,6 +114,11 @@ __device__ __forceinline__ void attn_step_body(const AttnParams& p, const int bl
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int len = p.lengths ? p.lengths[b] : L;
+    int w_lo = 0, w_hi = 0;   // (WIN) first and last position of the window
+    if (WIN) {
+        const int c = p.c_prev ? p.c_prev[(long)b * p.c_bs] : 0;
+        w_lo = c - p.win_back; w_hi = c + p.win_ahead;
+    }
     GVX_STAMP(1, 0);
 
     // ---- loads: query slabs.  thread = (grp, d4): slabs grp, grp + qg, ... of float4 column d4
@@ -200,7 +218,8 @@ __device__ __forceinline__ void attn_step_body(const AttnParams& p, const int bl
             }
             pe = sum8(pe);
             const int l = l0 + 8 * (wave + MA_WAVES * i) + (int)p8;
-            if (a8 == 0 && l < L) es[l] = l < len ? pe : -INFINITY;
+            if (WIN) { if (a8 == 0 && l < L) es[l] = (l < len && l >= w_lo && l <= w_hi) ? pe : -INFINITY; }
+            else if (a8 == 0 && l < L) es[l] = l < len ? pe : -INFINITY;
         }
     }
     __syncthreads();
@@ -215,10 +234,17 @@ __device__ __forceinline__ void attn_step_body(const AttnParams& p, const int bl
     sum = wave_sum_dpp(sum);
     const float inv = 1.f / sum;
     if (g == 0 && wave == 0) {
+        float bw = -1.f;
+        int bl = 0;
         for (int l = lane; l < L; l += 64) {
             const float w = __expf(es[l] - mx) * inv;
             p.w_out[(long)b * p.w_out_bs + l] = w;
             p.w_cum[(long)b * L + l] += w;
+            if (WIN && w > bw) { bw = w; bl = l; }
+        }
+        if (WIN) {   // the next step's centre
+            const int cn = wave_argmax_first(bw, bl);
+            if (lane == 0) p.c_out[(long)b * p.c_bs] = cn;
         }
     }
     GVX_STAMP(1, 4);

@@ -458,6 +458,21 @@ int gvx_autoregressive_loop_kind(const gvx_model* m, int B, int L) {
     return plan_autoregressive(m, B, L).kind;
 }
 
+int gvx_autoregressive_windowed_loop_kind(const gvx_model* m, int B, int L) {
+    if (!m || B < 1 || L < 1) return 0;
+    return plan_autoregressive(m, B, L, true).kind;
+}
+
+// Host-only query for the tests (not in the public header): the ArLoopPlan of a windowed autoregressive call,
+// out[0..3] = {kind, split_h, fold, graph} - plan_autoregressive(m, B, L, true), the function gvx_decoder_autoregressive_windowed calls.
+int gvx_debug_decoder_plan_windowed(const gvx_model* m, int B, int L, int* out) {
+    if (!m || !out) return fail(GVX_ERR_INVALID_ARG, "null argument");
+    if (B < 1 || L < 1) return fail(GVX_ERR_INVALID_ARG, "B, L >= 1 (got %d, %d)", B, L);
+    const ArLoopPlan a = plan_autoregressive(m, B, L, true);
+    out[0] = a.kind; out[1] = a.split_h; out[2] = a.fold; out[3] = a.graph;
+    return GVX_OK;
+}
+
 // Host-only queries for the tests, like gvx_debug_gemm_plan / gvx_debug_bptt_plan (not in the public header).  Every field of the
 // two loop plans for (B, L) on this handle - the same two functions the loops call, no device touched.  mode: 0 inference, 1 training
 // call with the whole tape, 2 training call with a partial tape.  out[0..7] = TfLoopPlan {kind, pa_layout, tile_layout, rows64,

@@ -40,7 +40,7 @@ TfLoopPlan plan_teacher_forced(const gvx_model* m, int B, int L, TfMode mode) {
     return p;
 }
 
-ArLoopPlan plan_autoregressive(const gvx_model* m, int B, int L) {
+ArLoopPlan plan_autoregressive(const gvx_model* m, int B, int L, bool windowed) {
     ArLoopPlan p{};
     const gvx_dims& d = m->d;
     const int E = d.embed_dim, D = d.dec_rnn_dim, lay = attention_persistent_layout(B, L);
@@ -56,6 +56,10 @@ ArLoopPlan plan_autoregressive(const gvx_model* m, int B, int L) {
                       decoder_resident_supported(B, L) && (lay == 1 || (lay == 2 && B <= 16)) && d.prenet_dim == 256 && d.n_mels <= 80 &&
                       m->PSB() <= 96 && d.att_dim == 128;
     p.kind = pair ? 2 : (pa_any && lay == 1 && m->ar_resident ? 1 : 0);
+    // A monotonic attention window lives in the resident pair's one-workgroup-per-row attention kernel and in the attention step of the
+    // launches per step: rows of 129-256 tokens (two workgroups per row) and the step launches beside the resident attention kernel go
+    // to kind 0 when the call carries one
+    if (windowed && !(p.kind == 2 && lay == 1)) p.kind = 0;
     // The projection's context columns ride on the decoder-LSTM tiles' projection slabs, so that launch C is exactly 256 tiles.
     p.fold = B <= 32 && E / 4 == D / 8;
     // h_a(t) exists when launch A ends, the context only after the attention step: the h_a columns of both cells (two thirds of
@@ -665,6 +669,7 @@ struct ArLoop {   // one autoregressive call: what its loop kinds share
     int32_t* n_done; int32_t* n_frames_ws;
     int B, L, T;
     float gate_threshold;
+    int32_t* centres; int win_back, win_ahead;   // monotonic attention window (centres == nullptr: none): the caller's [B][T] buffer is the steps' state
 };
 
 void print_ws_plan_once(const WsPlan& wp) {   // (diagnostics, tools/ar_ws_diff.py: byte offsets of the workspace buffers)
@@ -746,6 +751,10 @@ int ar_launch_a(const ArLoop& c, const ArStep& q, int t, hipStream_t st) {
     HIP_TRY(launch_skinny(ja, 2, SK_AR, st, &lq));
     AttnParams ap;
     fill_attn(m, ap, c.memory_ws, c.len_ws, t, B, L, db.align_tm, (long)L, (long)B * L, db);
+    if (c.centres) {   // step t reads the centres step t - 1 stored and stores its own: two addresses, no hand-off inside a launch
+        ap.c_prev = t > 0 ? c.centres + (t - 1) : nullptr; ap.c_out = c.centres + t; ap.c_bs = (long)c.T;
+        ap.win_back = c.win_back; ap.win_ahead = c.win_ahead;
+    }
     if (!c.plan.split_h) {
         HIP_TRY(launch_attn(m, ap, st));
         return GVX_OK;
@@ -866,6 +875,7 @@ int ar_loop_resident(const ArLoop& c, hipStream_t s, int* steps) {
     pp.pre_w0_t = m->dev_blob + m->blob.pre_w0_t; pp.keep0 = c.masks_ws; pp.y1 = db.pre1;
     pp.n_frames = c.n_frames_ws; pp.n_done = c.n_done; pp.gate_threshold = c.gate_threshold;
     pp.p_flags = c.sync + RS_FLAG_P; pp.y1_flags = c.sync + RS_FLAG_Y1;
+    pp.centres = c.centres; pp.win_back = c.win_back; pp.win_ahead = c.win_ahead;
     rc = launch_resident_attention(m, pp, s);
     if (rc != GVX_OK) return rc;
     ArResidentParams rp{};
@@ -917,6 +927,7 @@ int ar_loop_chunked(const ArLoop& c, hipStream_t s, int* steps) {
         gvx_model::LoopKey key{c.ws, c.memory_ws, m->dev_blob, B, L, T, c.len_ws != nullptr};
         key.threshold = c.gate_threshold;
         key.variant = c.plan.kind == 1 ? 1 : (c.plan.split_h ? 2 : 0);
+        key.centres = c.centres; key.win_back = c.win_back; key.win_ahead = c.win_ahead;
         gset = touch_graph_set(m, m->ar_graphs, key);
     }
     // One chunk of look-ahead: chunk k + 1 is enqueued BEFORE the host reads chunk k's all-rows-finished counter (pinned slot,
@@ -956,12 +967,10 @@ int ar_loop_chunked(const ArLoop& c, hipStream_t s, int* steps) {
     return GVX_OK;
 }
 
-}  // namespace
-}  // namespace gvx
-
-extern "C" int gvx_decoder_autoregressive(gvx_model* m, const float* memory, const int32_t* lengths, int B, int L, int max_steps,
-                                          float gate_threshold, const uint8_t* keep_masks, float* mel_out, float* gate_out, float* align_out,
-                                          int32_t* n_frames_out, int* steps_run_out, void* ws, size_t ws_bytes, void* stream) {
+// both exports of the autoregressive decode; centres_out == nullptr: no window
+int decoder_ar_impl(gvx_model* m, const float* memory, const int32_t* lengths, int B, int L, int max_steps, float gate_threshold,
+                    const uint8_t* keep_masks, float* mel_out, float* gate_out, float* align_out, int32_t* n_frames_out, int* steps_run_out,
+                    void* ws, size_t ws_bytes, void* stream, int window_back, int window_ahead, int32_t* centres_out) {
     int rc = check_common(m, B, L, max_steps, ws, ws_bytes, WS_AUTOREGRESSIVE);
     if (rc != GVX_OK) return rc;
     if (!memory || !keep_masks || !mel_out || !gate_out || !align_out || !n_frames_out)
@@ -990,8 +999,8 @@ extern "C" int gvx_decoder_autoregressive(gvx_model* m, const float* memory, con
     }
     rc = decoder_init_states(m, memory_ws, B, L, db, s);
     if (rc != GVX_OK) return rc;
-    const ArLoop c{m, plan_autoregressive(m, B, L), db, memory_ws, len_ws, masks_ws, ws, sync, ws_ptr<float>(ws, wp.xchg), flags + FLAG_AR_DONE, flags + FLAG_AR_FRAMES,
-                   B, L, T, gate_threshold};
+    const ArLoop c{m, plan_autoregressive(m, B, L, centres_out != nullptr), db, memory_ws, len_ws, masks_ws, ws, sync, ws_ptr<float>(ws, wp.xchg),
+                   flags + FLAG_AR_DONE, flags + FLAG_AR_FRAMES, B, L, T, gate_threshold, centres_out, window_back, window_ahead};
     if (c.plan.kind != 0) {
         rc = ensure_side_stream(m);
         if (rc != GVX_OK) return rc;
@@ -1010,6 +1019,7 @@ extern "C" int gvx_decoder_autoregressive(gvx_model* m, const float* memory, con
     // padding values (mel 0, gate 1e3, alignment 0 - mask_padding, models/tts/tacotron2.py:466-473)
     HIP_TRY(launch_ar_emit_all(db.proj, mel_out, gate_out, B, M, T, t, c.n_frames_ws, s));
     HIP_TRY(launch_permute01_partial(db.align_tm, align_out, t, T, B, L, c.n_frames_ws, s));
+    if (centres_out) HIP_TRY(launch_ar_centres_finish(centres_out, c.n_frames_ws, c.plan.kind != 0 ? sync + HANDOFF_TIMEOUT : nullptr, B, T, s));
     if (c.plan.kind != 0) {   // a hand-off that timed out must not leave numbers that look like results
         float* outs[3] = {mel_out, gate_out, align_out};
         const size_t counts[3] = {(size_t)B * M * T, (size_t)B * T, (size_t)B * T * L};
@@ -1018,4 +1028,29 @@ extern "C" int gvx_decoder_autoregressive(gvx_model* m, const float* memory, con
     HIP_TRY(hipStreamSynchronize(s));
     if (steps_run_out) *steps_run_out = t;
     return GVX_OK;
+}
+
+}  // namespace
+}  // namespace gvx
+
+extern "C" int gvx_decoder_autoregressive(gvx_model* m, const float* memory, const int32_t* lengths, int B, int L, int max_steps,
+                                          float gate_threshold, const uint8_t* keep_masks, float* mel_out, float* gate_out, float* align_out,
+                                          int32_t* n_frames_out, int* steps_run_out, void* ws, size_t ws_bytes, void* stream) {
+    return decoder_ar_impl(m, memory, lengths, B, L, max_steps, gate_threshold, keep_masks, mel_out, gate_out, align_out, n_frames_out,
+                           steps_run_out, ws, ws_bytes, stream, 0, 0, nullptr);
+}
+
+extern "C" int gvx_decoder_autoregressive_windowed(gvx_model* m, const float* memory, const int32_t* lengths, int B, int L, int max_steps,
+                                                   float gate_threshold, const uint8_t* keep_masks, float* mel_out, float* gate_out,
+                                                   float* align_out, int32_t* n_frames_out, int* steps_run_out, void* ws, size_t ws_bytes,
+                                                   void* stream, int window_back, int window_ahead, int32_t* centres_out) {
+    if (window_back < 0 || window_ahead < 0)
+        return fail(GVX_ERR_INVALID_ARG, "window_back and window_ahead must be >= 0 (got %d, %d)", window_back, window_ahead);
+    if (!centres_out) return fail(GVX_ERR_INVALID_ARG, "null argument: centres_out is the window's state and is mandatory");
+    if (L > 0) {   // (widths past the row change nothing; the kernels add them to a centre)
+        window_back = window_back < L ? window_back : L;
+        window_ahead = window_ahead < L ? window_ahead : L;
+    }
+    return decoder_ar_impl(m, memory, lengths, B, L, max_steps, gate_threshold, keep_masks, mel_out, gate_out, align_out, n_frames_out,
+                           steps_run_out, ws, ws_bytes, stream, window_back, window_ahead, centres_out);
 }

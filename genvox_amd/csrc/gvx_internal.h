@@ -109,9 +109,12 @@ struct gvx_model {
         const void* ws; const void* memory; const void* blob; int B, L, T; bool has_len;
         float threshold = 0.f;   // autoregressive graphs only
         int variant = 0;         // teacher-forced loop: 1 = with the persistent attention kernel
+        // autoregressive graphs of a windowed decode: the caller's centre buffer (the steps' state, baked into the launches) and the window
+        const void* centres = nullptr; int win_back = 0, win_ahead = 0;
         bool operator==(const LoopKey& o) const {
             return ws == o.ws && memory == o.memory && blob == o.blob && B == o.B && L == o.L && T == o.T &&
-                   has_len == o.has_len && threshold == o.threshold && variant == o.variant;
+                   has_len == o.has_len && threshold == o.threshold && variant == o.variant && centres == o.centres &&
+                   win_back == o.win_back && win_ahead == o.win_ahead;
         }
     };
     // One entry per key: the graphs of its chunks (one for the encoder / teacher-forced loop, one per 16-step chunk of the
@@ -191,7 +194,9 @@ struct ArLoopPlan {
     bool graph;     // the 16-step chunks may be replayed from hipGraphs
 };
 TfLoopPlan plan_teacher_forced(const gvx_model* m, int B, int L, TfMode mode);
-ArLoopPlan plan_autoregressive(const gvx_model* m, int B, int L);
+// windowed: the call carries a monotonic attention window (gvx_decoder_autoregressive_windowed).  The resident pair serves it with one
+// attention workgroup per row (L <= 128); every other shape takes the launches per step (kind 0), whose attention step applies it
+ArLoopPlan plan_autoregressive(const gvx_model* m, int B, int L, bool windowed = false);
 
 enum WsMode : int { WS_TEACHER_FORCED = 0, WS_AUTOREGRESSIVE = 1 };
 

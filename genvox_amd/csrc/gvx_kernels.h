@@ -201,6 +201,10 @@ struct AttnParams {
     // block with the same index (blocks of both launches are dealt round-robin over the XCDs): fragment-packed matrices of that
     // launch's jobs 0 / 1, their k-groups per tile, tiles of job 0, tiles in all
     const float* pf_w[2]; int pf_nkg[2]; int pf_tiles0, pf_tiles;
+    // autoregressive decode with a monotonic attention window (c_out == nullptr: none): row b's centre of this step at
+    // c_prev[b * c_bs] (nullptr at step 0: centre 0), its next centre - the lowest index at which the new alignment row is
+    // largest - to c_out[b * c_bs]; positions outside [centre - win_back, centre + win_ahead] are masked like those past the length
+    const int32_t* c_prev; int32_t* c_out; long c_bs; int win_back, win_ahead;
 };
 hipError_t launch_attention(const AttnParams& p, hipStream_t s);   // energy + context kernels (p.loc = location features)
 // one launch: energies of the whole row (redundantly per slice), softmax, context slice; p.loc = pm + location features
@@ -250,6 +254,10 @@ struct AttnPersistParams {
     int32_t* n_frames; int32_t* n_done; float gate_threshold;
     const unsigned* p_flags;                  // decoder-LSTM workgroup i's flag for the rows of replica r at p_flags[(r * 128 + i) * 32], r < RS_REP_P
     unsigned* y1_flags;                       // row b's flag at y1_flags[b * 32]
+    // autoregressive role with a monotonic attention window (centres == nullptr: none; one workgroup per row only): the row keeps its
+    // centre in LDS for the whole decode and stores the centre after step t - the lowest index at which the step's alignment row is
+    // largest - to centres[b * T + t]
+    int32_t* centres; int win_back, win_ahead;
 };
 // ---------------------------------------------------------------------------------------------
 // Teacher-forced decoder loop as ONE resident weight-streaming kernel beside the resident attention kernel (dec_resident.hip):
@@ -423,6 +431,8 @@ hipError_t launch_ar_project(const float* p_slab, int n_slabs, const float* p_ct
                              const uint8_t* keep1, float* prenet_out, hipStream_t s);
 // AR: scatter the blocked per-step projections proj[t][PSB/8][B][8], t < steps, into mel_out [B][M][Tmax], gate_out [B][Tmax]
 // frames t >= n_frames[b] get the padding values of the reference's mask_padding: mel 0, gate 1e3
+// AR with an attention window: centres [B][T] of frames t >= n_frames[b] = -1; INT32_MIN everywhere if *tmo != 0 (tmo may be nullptr)
+hipError_t launch_ar_centres_finish(int32_t* centres, const int32_t* n_frames, const unsigned* tmo, int B, int T, hipStream_t s);
 hipError_t launch_ar_emit_all(const float* proj, float* mel_out, float* gate_out, int B, int M, int Tmax, int steps,
                               const int32_t* n_frames, hipStream_t s);
 // dst[b][t][:] = src[t][b][:] for t < steps (0 for t >= n_frames[b]), dst rows have Tdst time slots

@@ -587,6 +587,21 @@ __global__ void permute01_partial_kernel(const float* src, float* dst, int steps
     }
 }
 
+// Autoregressive decode with an attention window, after the loop: the centres of frames a row never emitted (t >= n_frames[b], steps
+// that did not run among them) become -1 - what `positions` of gvx_alignment_stats gives there.  A hand-off that timed out (*tmo != 0)
+// leaves no number that looks like a centre: INT32_MIN in every entry, beside the NaN outputs of launch_poison_on_timeout.
+__global__ void ar_centres_finish_kernel(int32_t* centres, const int32_t* n_frames, const unsigned* tmo, int T) {
+    const int b = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= T) return;
+    const bool timed_out = tmo && __hip_atomic_load(tmo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
+    if (timed_out) centres[(long)b * T + t] = INT32_MIN;
+    else if (t >= n_frames[b]) centres[(long)b * T + t] = -1;
+}
+hipError_t launch_ar_centres_finish(int32_t* centres, const int32_t* n_frames, const unsigned* tmo, int B, int T, hipStream_t s) {
+    hipLaunchKernelGGL(ar_centres_finish_kernel, dim3((T + 255) / 256, B), dim3(256), 0, s, centres, n_frames, tmo, T);
+    return hipGetLastError();
+}
+
 hipError_t launch_permute01_partial(const float* src, float* dst, int steps, int Tdst, int B, int n, const int32_t* n_frames,
                                     hipStream_t s) {
     const long rows = (long)steps * B;

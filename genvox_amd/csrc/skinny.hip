@@ -882,6 +882,11 @@ __global__ __launch_bounds__(SK_THREADS, 4) void ar_attn_tiles_kernel(SkinnyJobs
     if ((int)blockIdx.x < jobs.block0) { attn_step_body<4, 4>(ap, (int)blockIdx.x); return; }   // uniform per workgroup
     skinny_body<1, SK_DEPTH1, false, false, 1, true>(jobs);
 }
+// ... of a decode with a monotonic attention window (AttnParams.c_out): an instantiation of its own, the one above is untouched
+__global__ __launch_bounds__(SK_THREADS, 4) void ar_attn_tiles_win_kernel(SkinnyJobs jobs, AttnParams ap) {
+    if ((int)blockIdx.x < jobs.block0) { attn_step_body<4, 4, true>(ap, (int)blockIdx.x); return; }
+    skinny_body<1, SK_DEPTH1, false, false, 1, true>(jobs);
+}
 // autoregressive launch C beside the resident attention kernel: the context of the step arrives inside the launch (deferred segment)
 __global__ __launch_bounds__(SK_THREADS) void ar_lstm_defer_kernel(SkinnyJobs jobs) { skinny_body<1, SK_DEPTH1, false, true>(jobs); }
 // training step, back-propagation through the decoder loop: dgates x transposed recurrent matrices as partial sums (mode 2 jobs, train_bptt_decoder.hip)
@@ -914,6 +919,7 @@ hipError_t skinny_init() {
     if ((e = set_lds(decoder_lstm_step_pa64_kernel, 2)) != hipSuccess) return e;
     if ((e = set_lds(ar_lstm_defer_kernel, 1)) != hipSuccess) return e;
     if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(ar_attn_tiles_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(ar_attn_tiles_win_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
     if ((e = set_lds(train_bptt_products_kernel, 1)) != hipSuccess) return e;
     if ((e = set_lds(encoder_lstm_step_kernel<1>, 1)) != hipSuccess) return e;
     if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(encoder_lstm_persistent_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * SK_WAVES * 16 * 64 * (int)sizeof(float))) != hipSuccess) return e;
@@ -1047,7 +1053,8 @@ hipError_t launch_skinny_attn(const SkinnyJob* jobs, int njobs, const AttnParams
     const size_t lds_a = (size_t)step_lds_layout(ap.a, ap.L).total * sizeof(float);
     if (lds_a > lds) lds = lds_a;
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    ar_attn_tiles_kernel<<<dim3(js.block0 + js.tiles), dim3(SK_THREADS), lds, s>>>(js, ap);
+    if (ap.c_out) ar_attn_tiles_win_kernel<<<dim3(js.block0 + js.tiles), dim3(SK_THREADS), lds, s>>>(js, ap);
+    else ar_attn_tiles_kernel<<<dim3(js.block0 + js.tiles), dim3(SK_THREADS), lds, s>>>(js, ap);
     return hipGetLastError();
 }
 

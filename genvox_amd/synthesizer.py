@@ -69,16 +69,25 @@ class Synthesizer:
                                      "coverage": floats[2][r], "first_pos": ints[1][r], "last_pos": ints[2][r]},
                  "stopped": bool(ints[3][r])} for r in range(n)]
 
-    def tts(self, text: str, sampling_rate: Optional[int] = None, diagnostics: bool = False) -> Dict[str, np.ndarray]:
+    def tts(self, text: str, sampling_rate: Optional[int] = None, diagnostics: bool = False,
+            attention_window: Optional[Tuple[int, int]] = None) -> Dict[str, np.ndarray]:
         """``sampling_rate`` (Hz; default: the model's): the waveform is resampled on the device before it is copied to the host,
         and ``"sampling_rate"`` of the result is the rate delivered.  ``diagnostics``: the result gains ``"alignment_stats"``
         (focus, monotonic_fraction, max_jump, coverage, first_pos, last_pos of the sentence's alignment, as Python numbers) and
         ``"stopped"`` (did the gate fire before max_decoder_steps?): a collapsed attention or a run-away decode shows without
-        looking at a picture.  Every other key is what it is without them."""
+        looking at a picture.  Every other key is what it is without them.  ``attention_window`` = (back, ahead): decode with
+        the monotonic attention window of ``Tacotron2.inference`` - for a checkpoint that skips, repeats or wanders on this text;
+        the result gains ``"attention_centres"`` (the token every frame attended most) and, with ``diagnostics``,
+        ``"attention_window"`` records the window used (without a window the result has neither key)."""
         tokens = self.text_processor.tokens_to_indices(self.text_processor.tokenize(text))
         tokens = torch.IntTensor(tokens).unsqueeze(0).to(self.device)
-        outputs = self.tts_model.inference(inputs={"tokens": tokens})
+        inputs = {"tokens": tokens}
+        if attention_window is not None:
+            inputs["attention_window"] = attention_window
+        outputs = self.tts_model.inference(inputs=inputs)
         extra = self._diagnose(outputs, None, None)[0] if diagnostics else {}
+        if diagnostics and attention_window is not None:
+            extra["attention_window"] = tuple(int(v) for v in attention_window)
         mel = outputs["mel_outputs_postnet"]
         wav = self.audio_processor.convert_mel2wav_batch(mel, out_rate=sampling_rate)  # stays on the device until the end
         result = {key: val.squeeze(0).cpu().numpy() for key, val in outputs.items()}
@@ -88,19 +97,22 @@ class Synthesizer:
         return result
 
     def tts_batch(self, texts: Sequence[str], batch_size: int = 32, sampling_rate: Optional[int] = None,
-                  diagnostics: bool = False) -> List[Dict[str, np.ndarray]]:
+                  diagnostics: bool = False, attention_window: Optional[Tuple[int, int]] = None) -> List[Dict[str, np.ndarray]]:
         """Many sentences per call: one dict per sentence, in input order, with the keys, dtypes and shapes ``tts(text)`` gives
         for that sentence (every row trimmed to its own frames, tokens and samples).  Sentences are decoded as padded batches of
         at most ``batch_size`` rows of similar token length (``plan_tts_batches``) and vocoded at their own lengths in one ragged
         Griffin-Lim call per batch; the mels stay on the device in between.  A batch of one sentence is exactly the ``tts`` path,
         torch RNG draws included.  ``sampling_rate`` as in ``tts``: every row is resampled at its own sample count.
-        ``diagnostics`` as in ``tts``: every sentence's alignment at its own frames and tokens."""
+        ``diagnostics`` as in ``tts``: every sentence's alignment at its own frames and tokens.  ``attention_window`` as in
+        ``tts``: every sentence is decoded with it and carries its own ``"attention_centres"``."""
         token_lists = [self.text_processor.tokens_to_indices(self.text_processor.tokenize(t)) for t in texts]
         results: List[Dict[str, np.ndarray]] = [{} for _ in token_lists]
         for idx, tokens, lens in plan_tts_batches(token_lists, batch_size):
             inputs = {"tokens": tokens.to(self.device)}
             if len(idx) > 1:
                 inputs["token_lengths"] = lens.to(self.device)
+            if attention_window is not None:
+                inputs["attention_window"] = attention_window
             outputs = self.tts_model.inference(inputs=inputs)
             mel = outputs["mel_outputs_postnet"]
             extras = self._diagnose(outputs, outputs.get("mel_lengths"), inputs.get("token_lengths")) if diagnostics else None
@@ -121,6 +133,10 @@ class Synthesizer:
                               "alignments": host["alignments"][r, :t, :n_tok].copy(),
                               "waveform": wav[r, :samples[r]].copy(),
                               "sampling_rate": self._out_rate(sampling_rate)}
+                if attention_window is not None:
+                    results[i]["attention_centres"] = host["attention_centres"][r, :t].copy()
                 if extras is not None:
                     results[i].update(extras[r])
+                    if attention_window is not None:
+                        results[i]["attention_window"] = tuple(int(v) for v in attention_window)
         return results

@@ -368,6 +368,25 @@ class Tacotron2(nn.Module):
         self._ensure_packed()
         return int(_lib.load().gvx_autoregressive_loop_kind(self._handle, B, L))
 
+    def ar_windowed_loop_kind(self, B: int, L: int) -> int:
+        """... of a call with an ``attention_window`` (gvx_autoregressive_windowed_loop_kind): 2 where one resident attention workgroup
+        holds a row (L <= 128), otherwise 0."""
+        self._ensure_packed()
+        return int(_lib.load().gvx_autoregressive_windowed_loop_kind(self._handle, B, L))
+
+    @staticmethod
+    def _check_window(window):
+        """(back, ahead) as two non-negative ints, or None."""
+        if window is None:
+            return None
+        try:
+            back, ahead = (int(v) for v in window)
+        except (TypeError, ValueError):
+            raise ValueError(f"attention_window must be a pair (back, ahead) of non-negative integers, got {window!r}") from None
+        if back < 0 or ahead < 0 or (back, ahead) != tuple(window):
+            raise ValueError(f"attention_window must be a pair (back, ahead) of non-negative integers, got {window!r}")
+        return back, ahead
+
     def kernel_times_ms(self):
         a, b, n = C.c_float(), C.c_float(), C.c_int()
         _lib.check(_lib.load().gvx_kernel_times_ms(self._handle, C.byref(a), C.byref(b), C.byref(n)))
@@ -590,6 +609,12 @@ class Tacotron2(nn.Module):
         ``mel_lengths`` holds every row's frame count and frames past it carry the padding values of the reference's
         mask_padding (mel / mel_postnet / alignment 0, gate 1e3) - row b up to its length is what a batch-1 run gives.
 
+        Optional ``attention_window`` = (back, ahead), two non-negative integers: a monotonic attention window
+        (gvx_decoder_autoregressive_windowed).  Every step's softmax only sees the tokens from ``back`` before to ``ahead`` after the
+        token the previous step attended most (token 0 at the first step), so the attended token moves by at most max(back, ahead)
+        per frame and, with back = 0, never backwards.  Such calls add ``attention_centres`` int32 [B, T]: the token every frame
+        attended most (the ``positions`` of `metrics.alignment_stats`), -1 past a row's frames.  Off by default; nothing else changes.
+
         Batches above STREAM_ROWS rows are decoded as chunks of at most that many rows: one after the other when a chunk decodes as
         two resident kernels that fill the chip (``ar_loop_kind`` 2: default layer sizes, rows of <= 128 tokens), otherwise on two
         streams at once (each chunk a C-ABI call of its own, driven by its own host thread because the call polls the stop flags):
@@ -606,6 +631,9 @@ class Tacotron2(nn.Module):
         if given is not None:
             given = given.to(device=dev, dtype=torch.uint8).reshape(2, S, B, P)
         lib = _lib.load()
+        window = self._check_window(inputs.get("attention_window"))
+        centres = torch.full((B, S), -1, dtype=torch.int32, device=dev) if window is not None else None
+        kind_of = lib.gvx_autoregressive_loop_kind if window is None else lib.gvx_autoregressive_windowed_loop_kind
         mel_out = torch.zeros(B, M, S, device=dev)
         gate_out = torch.zeros(B, S, device=dev)
         align = torch.zeros(B, S, L, device=dev)
@@ -624,10 +652,13 @@ class Tacotron2(nn.Module):
             steps = C.c_int(0)
             st = self._stream()
             _lib.check(lib.gvx_encoder_forward(handle, tokens[lo:hi].data_ptr(), ln, n, L, memory.data_ptr(), ws.data_ptr(), ws.numel(), st))
-            _lib.check(lib.gvx_decoder_autoregressive(
-                handle, memory.data_ptr(), ln, n, L, S, float(mc.gate_threshold), masks.data_ptr(), mel_out[lo:hi].data_ptr(),
-                gate_out[lo:hi].data_ptr(), align[lo:hi].data_ptr(), n_frames[lo:hi].data_ptr(), C.byref(steps), ws.data_ptr(),
-                ws.numel(), st))
+            args = (handle, memory.data_ptr(), ln, n, L, S, float(mc.gate_threshold), masks.data_ptr(), mel_out[lo:hi].data_ptr(),
+                    gate_out[lo:hi].data_ptr(), align[lo:hi].data_ptr(), n_frames[lo:hi].data_ptr(), C.byref(steps), ws.data_ptr(),
+                    ws.numel(), st)
+            if window is None:
+                _lib.check(lib.gvx_decoder_autoregressive(*args))
+            else:
+                _lib.check(lib.gvx_decoder_autoregressive_windowed(*args, window[0], window[1], centres[lo:hi].data_ptr()))
             steps_run.append(steps.value)
 
         n_chunks = -(-B // STREAM_ROWS)
@@ -636,7 +667,7 @@ class Tacotron2(nn.Module):
         chunks = list(zip(bounds, bounds[1:]))
         if n_chunks == 1:
             run(0, B, self._handle, self._workspace_of(lib.gvx_workspace_bytes_autoregressive(self._handle, B, L, S)), seeds[0])
-        elif all(lib.gvx_autoregressive_loop_kind(self._handle, hi - lo, L) == 2 for lo, hi in chunks):
+        elif all(kind_of(self._handle, hi - lo, L) == 2 for lo, hi in chunks):
             # every chunk decodes as two resident kernels that fill the chip: one after the other on this stream (two such loops
             # cannot share the device; 2 x 25 us per step pair against 61 us for two concurrent lanes of launch-per-step loops)
             ws = self._workspace_of(lib.gvx_workspace_bytes_autoregressive(self._handle, max(hi - lo for lo, hi in chunks), L, S))
@@ -687,6 +718,8 @@ class Tacotron2(nn.Module):
                "gate_outputs": gate_out[:, :Tn].contiguous(), "alignments": align[:, :Tn].contiguous()}
         if B > 1:
             out["mel_lengths"] = n_frames
+        if centres is not None:
+            out["attention_centres"] = centres[:, :Tn].contiguous()
         return out
 
     # ---- stage-level entry points (used by the parity tests to localise failures)
@@ -835,7 +868,7 @@ class Tacotron2(nn.Module):
             return self.synthesis_items_eval["mcd_dtw_eval"]
         raise ValueError(f"unknown eval priority {kind!r}: 'loss' or 'mcd_dtw'")
 
-    def eval_synthesis(self, batch: Dict, prenet_keep_masks: Optional[torch.Tensor] = None) -> Dict:
+    def eval_synthesis(self, batch: Dict, prenet_keep_masks: Optional[torch.Tensor] = None, attention_window=None) -> Dict:
         """Validation by synthesis: `inference` on the batch's tokens (free-running, under no_grad), then on the device the
         statistics of every row's alignment (genvox_amd.metrics.alignment_stats) and the DTW mel-cepstral distortion of its
         postnet mel against the batch's target mel, each row at its own lengths.  Any batch size.
@@ -844,13 +877,17 @@ class Tacotron2(nn.Module):
         align_coverage_eval, stopped_fraction_eval (rows whose gate fired before max_decoder_steps), frame_ratio_eval
         (predicted over target frames) - from one small copy to the host, and returns the inference outputs (``mel_lengths``
         also for a batch of one row) with the per-row device tensors ``alignment_stats`` (dict), ``dtw_distance``, ``mcd_dtw``,
-        ``stopped`` and ``frame_ratio``.  ``prenet_keep_masks``: as `inference` takes them (repeatable runs)."""
+        ``stopped`` and ``frame_ratio``.  ``prenet_keep_masks``: as `inference` takes them (repeatable runs).
+        ``attention_window``: (back, ahead) as `inference` takes it, so that a validation run can compare the free decode with the
+        windowed one; the outputs then carry ``attention_centres`` too."""
         from . import metrics
 
         with torch.no_grad():
             inputs = {"tokens": batch["token_padded"], "token_lengths": batch["token_lengths"]}
             if prenet_keep_masks is not None:
                 inputs["prenet_keep_masks"] = prenet_keep_masks
+            if attention_window is not None:
+                inputs["attention_window"] = attention_window
             outputs = self.inference(inputs)
             mel = outputs["mel_outputs_postnet"]
             dev, B = mel.device, mel.shape[0]

@@ -180,6 +180,10 @@ int gvx_teacher_forced_loop_kind(const gvx_model* model, int B, int L);
  *     share the chip): no launch per step, the kernels end the loop themselves,
  * 1 = launches per step beside the resident attention kernel (opt-in, GVX_AR_RESIDENT=1), 0 = launches per step. */
 int gvx_autoregressive_loop_kind(const gvx_model* model, int B, int L);
+/* ... and how gvx_decoder_autoregressive_windowed runs it.  The resident pair applies the window where one attention workgroup
+ * holds a row (L <= 128): 2 there; every other shape - rows of 129-256 tokens, GVX_AR_RESIDENT=1 handles - takes the launches
+ * per step, 0, whose attention step applies it.  Never 1. */
+int gvx_autoregressive_windowed_loop_kind(const gvx_model* model, int B, int L);
 
 /* ---- Encoder: embedding + conv/BN/relu stack + BiLSTM with packed-sequence semantics.
  * Replaces nn.Embedding + Encoder.forward / Encoder.inference (models/tts/tacotron2.py:459,
@@ -213,6 +217,28 @@ int gvx_decoder_autoregressive(gvx_model* model, const float* memory, const int3
                                int max_steps, float gate_threshold, const uint8_t* keep_masks,
                                float* mel_out, float* gate_out, float* align_out, int32_t* n_frames_out,
                                int* steps_run_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- The same decode with a monotonic attention window: the softmax of every step only sees the tokens near the one the
+ * previous step attended most, so a decode cannot skip, repeat or wander by more than the window allows.  Not in the reference;
+ * an inference-time device only (teacher-forced and training calls have none).
+ *   Row b has a centre c_b(t), c_b(0) = 0.  At step t position l takes part in the softmax iff l < lengths[b] and
+ *   c_b(t) - window_back <= l <= c_b(t) + window_ahead; every other position has energy -inf and weight exactly 0.
+ *   c_b(t+1) = the lowest index at which the weights of step t are largest (the tie rule of gvx_alignment_stats' positions), so a
+ *   centre is always inside its own window and below lengths[b]: no softmax is empty.
+ * The cumulative weights, the location features and the context use the windowed weights; nothing else in the step changes, and
+ * a window that covers the whole row gives gvx_decoder_autoregressive's mel, gate and alignments bit for bit where both calls
+ * take the same loop kind (gvx_autoregressive_windowed_loop_kind / gvx_autoregressive_loop_kind).
+ * centres_out: device int32 [B, max_steps], mandatory - it is also where the decode keeps the centres between the steps of the
+ * launch-per-step loop (no workspace bytes are added; contents on entry do not matter).  On return centres_out[b][t] = c_b(t+1)
+ * for t < n_frames_out[b] and -1 behind: what gvx_alignment_stats gives as positions for the same alignments.  If a hand-off of
+ * the resident kernels timed out (gvx_workspace_status), every entry is INT32_MIN beside the NaN outputs.
+ * window_back / window_ahead < 0 or centres_out == NULL: GVX_ERR_INVALID_ARG, nothing is launched.  Every other argument, the
+ * workspace size and the synchronisation are those of gvx_decoder_autoregressive, which this call leaves as it was. */
+int gvx_decoder_autoregressive_windowed(gvx_model* model, const float* memory, const int32_t* lengths, int B, int L,
+                                        int max_steps, float gate_threshold, const uint8_t* keep_masks,
+                                        float* mel_out, float* gate_out, float* align_out, int32_t* n_frames_out,
+                                        int* steps_run_out, void* workspace, size_t workspace_bytes, void* stream,
+                                        int window_back, int window_ahead, int32_t* centres_out);
 
 /* ---- Postnet + residual: mel_post_out = mel_in + Postnet(mel_in).  Replaces Postnet.forward and the
  * residual add (models/tts/tacotron2.py:194-200, :464/:491).  Tensors are [B, n_mels, T]; any B (GEMM-only
