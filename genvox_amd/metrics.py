@@ -1,6 +1,7 @@
-"""Evaluation by synthesis on the device: statistics of an attention alignment and the DTW mel-cepstral distance between a
-free-running mel and its target (C ABI: gvx_alignment_stats, gvx_mel_project, gvx_dtw_distance; definitions in
-include/genvox_amd.h, float64 restatement in tests/metrics_ref64.py).
+"""Evaluation by synthesis on the device: statistics of an attention alignment, the DTW mel-cepstral distance between a
+free-running mel and its target, and the monotonic alignment search that turns an alignment into frames per token (C ABI:
+gvx_alignment_stats, gvx_mel_project, gvx_dtw_distance, gvx_monotonic_align; definitions in include/genvox_amd.h, restatements in
+tests/metrics_ref64.py and tests/mas_ref.py).
 
 Every function takes and returns device tensors and enqueues on the current stream; none of them synchronises with the host.
 """
@@ -69,6 +70,52 @@ def alignment_stats(alignments: torch.Tensor, mel_lengths: Optional[torch.Tensor
     Lb = (tl.clamp(0, L) if tl is not None else torch.full((B,), L, dtype=torch.int32, device=dev)).to(torch.float32)
     out["monotonic_fraction"] = out["monotonic"].to(torch.float32) / (Tb - 1).clamp(min=1)
     out["coverage"] = out["covered"].to(torch.float32) / Lb
+    return out
+
+
+MAS_STATUS_NAMES = ("ok", "empty", "infeasible")   # GVX_MAS_* of include/genvox_amd.h, in order
+
+_mas_ws: Dict[str, torch.Tensor] = {}   # device -> the search's workspace, grown to the largest call seen
+
+
+def _mas_workspace(need: int, dev) -> Optional[torch.Tensor]:
+    if need == 0:
+        return None
+    ws = _mas_ws.get(str(dev))
+    if ws is None or ws.numel() < need:
+        ws = _mas_ws[str(dev)] = torch.empty(need, dtype=torch.uint8, device=dev)
+    return ws
+
+
+def monotonic_align(alignments: torch.Tensor, mel_lengths: Optional[torch.Tensor] = None, token_lengths: Optional[torch.Tensor] = None,
+                    floor: float = 1e-8, want_scores: bool = False) -> Dict[str, torch.Tensor]:
+    """Monotonic alignment search over alignments [B, T, L], each row at its own ``mel_lengths[b]`` frames and ``token_lengths[b]``
+    tokens (None: all of them): the best path that starts on the first token, ends on the last and stays or advances by one token
+    per frame, under the score log(max(a, floor)) (gvx_monotonic_align of include/genvox_amd.h; a tie stays).
+
+    Returns ``path`` int32 [B, T] (the token of every frame, -1 behind the row's frames), ``durations`` int32 [B, L] (frames per
+    token: >= 1 inside the row, summing to its frames, 0 behind its tokens), ``starts`` int32 [B, L] (first frame of every token,
+    -1 behind), ``score`` fp32 [B] and ``status`` int32 [B] (index into ``MAS_STATUS_NAMES``: a row without frames or tokens is
+    "empty", one with fewer frames than tokens "infeasible"; both have path -1, durations 0, starts -1, score NaN).  With
+    ``want_scores`` also ``scores`` fp32 [B, T, L], the score table the search ran on (defined inside each row's lengths only).
+    One launch; the workspace of long rows is kept and grown by size."""
+    dev = _need_gpu(alignments, "alignments")
+    a = alignments.to(dtype=torch.float32).contiguous()
+    if a.dim() != 3:
+        raise ValueError(f"alignments must be [B, T, L], got {tuple(a.shape)}")
+    B, T, L = a.shape
+    ml, tl = _lengths(mel_lengths, B, dev), _lengths(token_lengths, B, dev)
+    lib = _lib.load()
+    out = {"path": torch.empty(B, T, dtype=torch.int32, device=dev), "durations": torch.empty(B, L, dtype=torch.int32, device=dev),
+           "starts": torch.empty(B, L, dtype=torch.int32, device=dev), "score": torch.empty(B, dtype=torch.float32, device=dev),
+           "status": torch.empty(B, dtype=torch.int32, device=dev)}
+    scores = torch.empty(B, T, L, dtype=torch.float32, device=dev) if want_scores else None
+    ws = _mas_workspace(lib.gvx_monotonic_align_workspace_bytes(B, T, L), dev)
+    _lib.check(lib.gvx_monotonic_align(a.data_ptr(), _ptr(ml), _ptr(tl), B, T, L, float(floor), out["path"].data_ptr(),
+                                       out["durations"].data_ptr(), out["starts"].data_ptr(), out["score"].data_ptr(),
+                                       out["status"].data_ptr(), _ptr(scores), _ptr(ws), 0 if ws is None else ws.numel(), _stream(dev)))
+    if want_scores:
+        out["scores"] = scores
     return out
 
 

@@ -35,6 +35,36 @@ def plan_tts_batches(token_lists: Sequence[Sequence[int]], batch_size: int = 32)
     return calls
 
 
+def group_words(tokens: Sequence[str], starts: Sequence[float], ends: Sequence[float]) -> List[Tuple[str, float, float]]:
+    """Token timings -> word timings (no GPU needed).  ``tokens`` are the characters of the cleaned text with their ``starts`` and
+    ``ends``; a word is a maximal run of non-space tokens (punctuation stays on the word it touches) and lasts from its first
+    token's start to its last token's end.  Spaces, and the silence they carry, belong to no word: leading, trailing and
+    repeated spaces produce nothing."""
+    if not len(tokens) == len(starts) == len(ends):
+        raise ValueError(f"{len(tokens)} tokens with {len(starts)} starts and {len(ends)} ends")
+    words: List[Tuple[str, float, float]] = []
+    first = None
+    for i, tok in enumerate(tokens):
+        if tok.isspace():
+            if first is not None:
+                words.append(("".join(tokens[first:i]), starts[first], ends[i - 1]))
+                first = None
+        elif first is None:
+            first = i
+    if first is not None:
+        words.append(("".join(tokens[first:]), starts[first], ends[-1]))
+    return words
+
+
+def token_times(start_frames: Sequence[int], hop_length: int, trim: int, n_samples: int, model_rate: int, end_s: float):
+    """Seconds in the delivered waveform from the first frame of every token (no GPU needed): ``(starts, ends)``.  Frame f begins at
+    sample ``f * hop_length - trim`` of the model-rate signal of ``n_samples`` samples (the vocoder drops ``trim`` samples at both
+    ends), clamped to ``[0, n_samples]`` and divided by ``model_rate`` - a time, so it holds at whatever rate the waveform is
+    delivered.  A token ends where the next starts; the last ends at ``end_s``, the delivered waveform's own duration."""
+    starts = [min(max(int(f) * hop_length - trim, 0), n_samples) / model_rate for f in start_frames]
+    return starts, starts[1:] + [end_s]
+
+
 class Synthesizer:
     def __init__(self, tts_model_class, tts_config_path: str, tts_checkpoint_path: str, use_cuda: bool = True) -> None:
         if not (use_cuda and torch.cuda.is_available()):
@@ -69,8 +99,28 @@ class Synthesizer:
                                      "coverage": floats[2][r], "first_pos": ints[1][r], "last_pos": ints[2][r]},
                  "stopped": bool(ints[3][r])} for r in range(n)]
 
+    def _align(self, outputs: Dict[str, torch.Tensor], frames: Optional[torch.Tensor], token_lengths: Optional[torch.Tensor]):
+        """Monotonic alignment search over a decoded batch, on the device from the alignments already there: per row the first frame
+        of every token and the row's status, as host lists (one small copy)."""
+        from . import metrics
+
+        al = metrics.monotonic_align(outputs["alignments"], frames, token_lengths)
+        host = torch.cat([al["starts"], al["status"][:, None]], dim=1).cpu().tolist()
+        return [row[:-1] for row in host], [row[-1] for row in host]
+
+    def _timings(self, token_strs: Sequence[str], start_frames: Sequence[int], status: int, n_frames: int, n_delivered: int,
+                 out_rate: int) -> Dict:
+        """The three timing keys of one sentence: ``start_frames`` and ``status`` from ``_align``, ``n_delivered`` samples at ``out_rate``."""
+        if status != 0:   # fewer frames than tokens: a collapsed decode is for the diagnostics to report, not an error here
+            return {"token_timings": [], "word_timings": [], "timings_status": "infeasible"}
+        ap = self.audio_processor
+        starts, ends = token_times(start_frames[:len(token_strs)], ap.config.hop_length, ap.TRIM, ap.row_samples([n_frames])[0],
+                                   ap.config.sampling_rate, n_delivered / out_rate)
+        return {"token_timings": list(zip(token_strs, starts, ends)), "word_timings": group_words(token_strs, starts, ends),
+                "timings_status": "ok"}
+
     def tts(self, text: str, sampling_rate: Optional[int] = None, diagnostics: bool = False,
-            attention_window: Optional[Tuple[int, int]] = None) -> Dict[str, np.ndarray]:
+            attention_window: Optional[Tuple[int, int]] = None, timings: bool = False) -> Dict[str, np.ndarray]:
         """``sampling_rate`` (Hz; default: the model's): the waveform is resampled on the device before it is copied to the host,
         and ``"sampling_rate"`` of the result is the rate delivered.  ``diagnostics``: the result gains ``"alignment_stats"``
         (focus, monotonic_fraction, max_jump, coverage, first_pos, last_pos of the sentence's alignment, as Python numbers) and
@@ -78,8 +128,14 @@ class Synthesizer:
         looking at a picture.  Every other key is what it is without them.  ``attention_window`` = (back, ahead): decode with
         the monotonic attention window of ``Tacotron2.inference`` - for a checkpoint that skips, repeats or wanders on this text;
         the result gains ``"attention_centres"`` (the token every frame attended most) and, with ``diagnostics``,
-        ``"attention_window"`` records the window used (without a window the result has neither key)."""
-        tokens = self.text_processor.tokens_to_indices(self.text_processor.tokenize(text))
+        ``"attention_window"`` records the window used (without a window the result has neither key).  ``timings``: the result
+        gains ``"token_timings"`` - one ``(token, start_s, end_s)`` per input token, from a monotonic alignment search over the
+        sentence's alignment (``metrics.monotonic_align``), in seconds of the delivered waveform whatever its rate, each token
+        ending where the next starts and the last at the waveform's end - ``"word_timings"`` (``group_words`` of them) and
+        ``"timings_status"``: ``"ok"``, or ``"infeasible"`` with both lists empty when the decode stopped with fewer frames than
+        tokens."""
+        token_strs = self.text_processor.tokenize(text)
+        tokens = self.text_processor.tokens_to_indices(token_strs)
         tokens = torch.IntTensor(tokens).unsqueeze(0).to(self.device)
         inputs = {"tokens": tokens}
         if attention_window is not None:
@@ -89,23 +145,29 @@ class Synthesizer:
         if diagnostics and attention_window is not None:
             extra["attention_window"] = tuple(int(v) for v in attention_window)
         mel = outputs["mel_outputs_postnet"]
+        aligned = self._align(outputs, None, None) if timings else None
         wav = self.audio_processor.convert_mel2wav_batch(mel, out_rate=sampling_rate)  # stays on the device until the end
         result = {key: val.squeeze(0).cpu().numpy() for key, val in outputs.items()}
         result["waveform"] = wav[0].cpu().numpy()
         result["sampling_rate"] = self._out_rate(sampling_rate)
         result.update(extra)
+        if aligned is not None:
+            result.update(self._timings(token_strs, aligned[0][0], aligned[1][0], mel.shape[2], wav.shape[1], result["sampling_rate"]))
         return result
 
     def tts_batch(self, texts: Sequence[str], batch_size: int = 32, sampling_rate: Optional[int] = None,
-                  diagnostics: bool = False, attention_window: Optional[Tuple[int, int]] = None) -> List[Dict[str, np.ndarray]]:
+                  diagnostics: bool = False, attention_window: Optional[Tuple[int, int]] = None,
+                  timings: bool = False) -> List[Dict[str, np.ndarray]]:
         """Many sentences per call: one dict per sentence, in input order, with the keys, dtypes and shapes ``tts(text)`` gives
         for that sentence (every row trimmed to its own frames, tokens and samples).  Sentences are decoded as padded batches of
         at most ``batch_size`` rows of similar token length (``plan_tts_batches``) and vocoded at their own lengths in one ragged
         Griffin-Lim call per batch; the mels stay on the device in between.  A batch of one sentence is exactly the ``tts`` path,
         torch RNG draws included.  ``sampling_rate`` as in ``tts``: every row is resampled at its own sample count.
         ``diagnostics`` as in ``tts``: every sentence's alignment at its own frames and tokens.  ``attention_window`` as in
-        ``tts``: every sentence is decoded with it and carries its own ``"attention_centres"``."""
-        token_lists = [self.text_processor.tokens_to_indices(self.text_processor.tokenize(t)) for t in texts]
+        ``tts``: every sentence is decoded with it and carries its own ``"attention_centres"``.  ``timings`` as in ``tts``: every
+        sentence aligned at its own frames and tokens, timed against its own waveform."""
+        token_strs = [self.text_processor.tokenize(t) for t in texts]
+        token_lists = [self.text_processor.tokens_to_indices(toks) for toks in token_strs]
         results: List[Dict[str, np.ndarray]] = [{} for _ in token_lists]
         for idx, tokens, lens in plan_tts_batches(token_lists, batch_size):
             inputs = {"tokens": tokens.to(self.device)}
@@ -116,6 +178,7 @@ class Synthesizer:
             outputs = self.tts_model.inference(inputs=inputs)
             mel = outputs["mel_outputs_postnet"]
             extras = self._diagnose(outputs, outputs.get("mel_lengths"), inputs.get("token_lengths")) if diagnostics else None
+            aligned = self._align(outputs, outputs.get("mel_lengths"), inputs.get("token_lengths")) if timings else None
             if len(idx) > 1:
                 frames = outputs.pop("mel_lengths")
                 wav, samples = self.audio_processor.convert_mel2wav_batch(mel, mel_lengths=frames, out_rate=sampling_rate)
@@ -139,4 +202,6 @@ class Synthesizer:
                     results[i].update(extras[r])
                     if attention_window is not None:
                         results[i]["attention_window"] = tuple(int(v) for v in attention_window)
+                if aligned is not None:
+                    results[i].update(self._timings(token_strs[i], aligned[0][r], aligned[1][r], t, samples[r], self._out_rate(sampling_rate)))
         return results

@@ -907,6 +907,22 @@ class Tacotron2(nn.Module):
         return {**outputs, "mel_lengths": frames, "alignment_stats": stats, "dtw_distance": dist, "mcd_dtw": mcd, "stopped": stopped,
                 "frame_ratio": ratio}
 
+    def token_durations(self, batch: Dict, prenet_keep_masks: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """Duration targets from teacher-forced alignments: `forward` on the batch (under no_grad, in whatever mode the model is
+        in), then on the device a monotonic alignment search over every row's alignment at its own ``mel_lengths`` and
+        ``token_lengths`` (genvox_amd.metrics.monotonic_align).  Returns ``durations`` int32 [B, L] - frames per token, at least
+        one inside a row, summing to its mel length, 0 behind its tokens - and ``status`` int32 [B] (0 ok, 1 empty, 2 infeasible:
+        fewer frames than tokens; such a row's durations are 0).  ``prenet_keep_masks``: as `forward` takes them in the batch
+        (repeatable runs)."""
+        from . import metrics
+
+        with torch.no_grad():
+            if prenet_keep_masks is not None:
+                batch = {**batch, "prenet_keep_masks": prenet_keep_masks}
+            outputs = self.forward(batch)
+            found = metrics.monotonic_align(outputs["alignments"], batch["mel_lengths"], batch["token_lengths"])
+        return {"durations": found["durations"], "status": found["status"]}
+
     def get_synthesis_logs(self) -> Dict:
         """The batch means of the last `eval_synthesis`."""
         return dict(self.synthesis_items_eval)

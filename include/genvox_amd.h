@@ -673,6 +673,46 @@ int gvx_dtw_uses_lds_tables(int Tp_max, int Tg_max, int K);
 int gvx_dtw_distance(const float* cp, const float* cg, const int32_t* pred_lengths, const int32_t* target_lengths, int B, int Tp_max,
                      int Tg_max, int K, float* dist_out, float* acc_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Monotonic alignment search: which frames belong to which token.  alignments is fp32 [B][T][L] (what the decoder loops write).  For
+ * row b with T_b = mel_lengths[b] frames (clamped to [0, T]; NULL: T) and L_b = token_lengths[b] tokens (clamped to [0, L]; NULL: L),
+ * the path of the highest score among those that start at (0, 0), end at (T_b - 1, L_b - 1) and stay on their token or advance by
+ * exactly one token from one frame to the next:
+ *
+ *     s[t][l] = logf( fmaxf( a[b][t][l], floor ) )          floor in (0, 1]; fmaxf passes over a NaN, which so scores logf(floor)
+ *     Q[0][0] = s[0][0]
+ *     Q[t][l] = s[t][l] + max( Q[t-1][l], Q[t-1][l-1] )     fp32, plain adds; on a tie the path STAYS (Q[t-1][l] wins)
+ *
+ * where a predecessor outside the row, or one that no path from (0, 0) reaches (l > t), counts as -inf.  The exact zeros an
+ * attention window writes get the finite score logf(floor): no -inf enters a sum from the data.  The path is read back from
+ * (T_b - 1, L_b - 1) along the choices made.  Nothing behind a row's lengths is read, whatever it holds.  Outputs:
+ *     path_out        int32 [B][T]   the token of frame t: non-decreasing in steps of 0 or 1, 0 at frame 0, L_b - 1 at frame
+ *                                    T_b - 1; -1 for t >= T_b                                                       (or NULL)
+ *     durations_out   int32 [B][L]   frames on token l: >= 1 for l < L_b, summing to T_b; 0 for l >= L_b
+ *     starts_out      int32 [B][L]   first frame of token l; -1 for l >= L_b                                         (or NULL)
+ *     score_out       fp32  [B]      Q[T_b - 1][L_b - 1]                                                             (or NULL)
+ *     row_status_out  int32 [B]      GVX_MAS_OK; GVX_MAS_EMPTY for T_b == 0 or L_b == 0; GVX_MAS_INFEASIBLE for T_b < L_b (fewer
+ *                                    frames than one per token).  A row without a path has path -1, durations 0, starts -1 and
+ *                                    score NaN, and nothing of its alignment is read.
+ *     scores_out      fp32  [B][T][L] or NULL: receives s[t][l] for t < T_b, l < L_b and is not touched elsewhere; every other
+ *                                    output has the same bits with and without it (it lets a test restate the recurrence exactly).
+ *
+ * One launch, one workgroup per row: the tokens are dealt to the threads, Q of two frames lives in LDS with one barrier per frame,
+ * the choices are one bit per cell (a wave's ballot: 64 tokens per 64-bit word, [T][ceil(L / 64)]), and the same workgroup reads the
+ * path back and counts the durations.  No workgroup waits for another, and every loop is bounded by T.  When the two Q rows and the
+ * bit table fit a CU's LDS (8 L + 8 T ceil(L / 64) bytes within 160 KiB; T = 2000, L = 256 does) the call needs no workspace: the
+ * size function returns 0 and workspace may be NULL.  Otherwise the bit table lives in the workspace (256-byte aligned, sized by
+ * the function below; any contents).  The uses_lds query says which (1 / 0; -1 for a shape the call would refuse).  T above
+ * GVX_MAS_MAX_FRAMES or L above GVX_MAS_MAX_TOKENS: GVX_ERR_UNSUPPORTED (the size function then returns 0); a NULL alignments,
+ * durations_out or row_status_out, B, T or L below 1, or a floor outside (0, 1]: GVX_ERR_INVALID_ARG; a missing, misaligned or short
+ * workspace: GVX_ERR_WORKSPACE; all of it checked before anything is launched.  Two calls give the same bits. */
+enum { GVX_MAS_OK = 0, GVX_MAS_EMPTY = 1, GVX_MAS_INFEASIBLE = 2 };
+enum { GVX_MAS_MAX_FRAMES = 32768, GVX_MAS_MAX_TOKENS = 4096 };
+size_t gvx_monotonic_align_workspace_bytes(int B, int T, int L);   /* any contents, no clearing; 0: not needed OR refused (uses_lds: 1 / -1) */
+int gvx_monotonic_align_uses_lds(int T, int L);
+int gvx_monotonic_align(const float* alignments, const int32_t* mel_lengths, const int32_t* token_lengths, int B, int T, int L,
+                        float floor, int32_t* path_out, int32_t* durations_out, int32_t* starts_out, float* score_out,
+                        int32_t* row_status_out, float* scores_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Per-kernel timing of the decoder step (measurement only): when enabled, a teacher-forced call replays the
  * mid-sequence LSTM-step launch and the attention launches 64 times each, back to back, between HIP events on
  * `stream` (after its loop; the call's outputs are not valid afterwards); gvx_kernel_times_ms synchronises and
