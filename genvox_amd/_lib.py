@@ -125,6 +125,8 @@ SIGNATURES = {
     "gvx_monotonic_align_workspace_bytes": (_sz, [_i, _i, _i]),
     "gvx_monotonic_align_uses_lds": (_i, [_i, _i]),
     "gvx_monotonic_align": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gvx_duration_scale": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
+    "gvx_mel_time_warp": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "gvx_kernel_timing_enable": (_i, [_vp, _i]),
     "gvx_model_set_persistent_attention": (_i, [_vp, _i]),
     "gvx_model_set_resident_kernels": (_i, [_vp, _i]),

@@ -1,7 +1,8 @@
 """Evaluation by synthesis on the device: statistics of an attention alignment, the DTW mel-cepstral distance between a
-free-running mel and its target, and the monotonic alignment search that turns an alignment into frames per token (C ABI:
-gvx_alignment_stats, gvx_mel_project, gvx_dtw_distance, gvx_monotonic_align; definitions in include/genvox_amd.h, restatements in
-tests/metrics_ref64.py and tests/mas_ref.py).
+free-running mel and its target, the monotonic alignment search that turns an alignment into frames per token, and the speaking
+rate control built on those frame counts - the plan and the token-wise time warp of a mel (C ABI: gvx_alignment_stats,
+gvx_mel_project, gvx_dtw_distance, gvx_monotonic_align, gvx_duration_scale, gvx_mel_time_warp; definitions in include/genvox_amd.h,
+restatements in tests/metrics_ref64.py, tests/mas_ref.py and tests/warp_ref.py).
 
 Every function takes and returns device tensors and enqueues on the current stream; none of them synchronises with the host.
 """
@@ -116,6 +117,76 @@ def monotonic_align(alignments: torch.Tensor, mel_lengths: Optional[torch.Tensor
                                        out["status"].data_ptr(), _ptr(scores), _ptr(ws), 0 if ws is None else ws.numel(), _stream(dev)))
     if want_scores:
         out["scores"] = scores
+    return out
+
+
+WARP_STATUS_NAMES = ("ok", "empty", "bad", "cut")   # GVX_WARP_* of include/genvox_amd.h, in order
+
+
+def _token_table(t: torch.Tensor, what: str, dev, dtype) -> torch.Tensor:
+    t = t.to(device=dev, dtype=dtype).contiguous()
+    if t.dim() != 2:
+        raise ValueError(f"{what} must be [B, L], got {tuple(t.shape)}")
+    return t
+
+
+def scale_durations(durations: torch.Tensor, token_lengths: Optional[torch.Tensor] = None, speed: float = 1.0,
+                    rates: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """The plan of a change of speaking rate: durations int32 [B, L] (frames per token, as ``monotonic_align`` gives them) ->
+    frames per token when token l is spoken ``speed * rates[b, l]`` times as fast (``rates`` fp32 [B, L]; None: all 1), each row at
+    its own ``token_lengths[b]`` tokens (gvx_duration_scale of include/genvox_amd.h: the rounding error is carried from token to
+    token, a spoken token keeps at least one frame).
+
+    Returns ``durations`` int32 [B, L] (0 behind the row's tokens), ``starts`` int32 [B, L] (-1 behind), ``out_lengths`` int32 [B]
+    (the row's new frame count) and ``status`` int32 [B] (index into ``WARP_STATUS_NAMES``: "empty" for a row without tokens or
+    frames, "bad" for a negative duration, a ``speed * rate`` outside [0.125, 8] or not finite, or more than 32768 frames; both
+    have durations 0, starts -1 and length 0).  One launch, no workspace."""
+    dev = _need_gpu(durations, "durations")
+    d = _token_table(durations, "durations", dev, torch.int32)
+    B, L = d.shape
+    tl = _lengths(token_lengths, B, dev)
+    r = None
+    if rates is not None:
+        r = _token_table(rates, "rates", dev, torch.float32)
+        if r.shape != d.shape:
+            raise ValueError(f"rates of shape {tuple(r.shape)} for durations of shape {tuple(d.shape)}")
+    out = {"durations": torch.empty(B, L, dtype=torch.int32, device=dev), "starts": torch.empty(B, L, dtype=torch.int32, device=dev),
+           "out_lengths": torch.empty(B, dtype=torch.int32, device=dev), "status": torch.empty(B, dtype=torch.int32, device=dev)}
+    _lib.check(_lib.load().gvx_duration_scale(d.data_ptr(), _ptr(tl), _ptr(r), B, L, float(speed), out["durations"].data_ptr(),
+                                              out["starts"].data_ptr(), out["out_lengths"].data_ptr(), out["status"].data_ptr(), _stream(dev)))
+    return out
+
+
+def time_warp(mel: torch.Tensor, durations: torch.Tensor, target_durations: torch.Tensor, token_lengths: Optional[torch.Tensor] = None,
+              T_out: Optional[int] = None) -> Dict[str, torch.Tensor]:
+    """Token-wise time warp of mel fp32 [B, M, T]: token l of row b, ``durations[b, l]`` frames of the input, becomes
+    ``target_durations[b, l]`` frames of the output, frame centres mapped linearly inside the token and the mel interpolated
+    linearly between the two source frames (gvx_mel_time_warp of include/genvox_amd.h; equal tables return the input bits).
+
+    ``T_out``: frames of the output; None reads the rows' new lengths once (the one host synchronisation of this function) and
+    takes their maximum.  Returns ``mel`` fp32 [B, M, T_out] (zeros behind a row's new length), ``src_frame`` int32 [B, T_out] and
+    ``src_frac`` fp32 [B, T_out] (the map: out[u] = x[src_frame[u]] + src_frac[u] * (x[src_frame[u] + 1] - x[src_frame[u]]); -1 and
+    0 behind) and ``status`` int32 [B] (index into ``WARP_STATUS_NAMES``: "cut" for a row longer than ``T_out``, "bad" for tables
+    that contradict each other or the mel; a "bad" or "empty" row comes out all zero).  One launch, no workspace."""
+    dev = _need_gpu(mel, "mel")
+    x = mel.to(dtype=torch.float32).contiguous()
+    if x.dim() != 3:
+        raise ValueError(f"mel must be [B, M, T], got {tuple(x.shape)}")
+    B, M, T = x.shape
+    d = _token_table(durations, "durations", dev, torch.int32)
+    dp = _token_table(target_durations, "target_durations", dev, torch.int32)
+    if d.shape != dp.shape or d.shape[0] != B:
+        raise ValueError(f"durations {tuple(d.shape)} and target_durations {tuple(dp.shape)} for a batch of {B} rows")
+    L = d.shape[1]
+    tl = _lengths(token_lengths, B, dev)
+    if T_out is None:
+        inside = dp if tl is None else dp * (torch.arange(L, device=dev)[None, :] < tl[:, None])
+        T_out = max(1, int(inside.to(torch.int64).sum(dim=1).max().item()))
+    T_out = int(T_out)
+    out = {"mel": torch.empty(B, M, T_out, dtype=torch.float32, device=dev), "src_frame": torch.empty(B, T_out, dtype=torch.int32, device=dev),
+           "src_frac": torch.empty(B, T_out, dtype=torch.float32, device=dev), "status": torch.empty(B, dtype=torch.int32, device=dev)}
+    _lib.check(_lib.load().gvx_mel_time_warp(x.data_ptr(), d.data_ptr(), dp.data_ptr(), _ptr(tl), B, M, T, L, T_out, out["mel"].data_ptr(),
+                                             out["src_frame"].data_ptr(), out["src_frac"].data_ptr(), out["status"].data_ptr(), _stream(dev)))
     return out
 
 

@@ -2,7 +2,8 @@
 loading, text -> tokens, autoregressive Tacotron2 on the GPU, mel -> waveform on the GPU."""
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Sequence, Tuple
+import math
+from typing import Dict, List, Mapping, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -65,6 +66,46 @@ def token_times(start_frames: Sequence[int], hop_length: int, trim: int, n_sampl
     return starts, starts[1:] + [end_s]
 
 
+RATE_MIN, RATE_MAX = 0.125, 8.0   # GVX_RATE_MIN / GVX_RATE_MAX of include/genvox_amd.h: the range of speed and of speed * rate
+
+
+def _check_rate(rate, what: str) -> float:
+    if isinstance(rate, bool) or not isinstance(rate, (int, float, np.integer, np.floating)) or not math.isfinite(rate) or rate <= 0:
+        raise ValueError(f"{what} must be a finite number above 0, not {rate!r}")
+    return float(rate)
+
+
+def token_rates(token_strs: Sequence[str], word_speed: Union[Sequence[float], Mapping[int, float], None]) -> List[float]:
+    """Rates per word -> rates per token (no GPU needed).  Words are ``group_words``' segmentation of ``token_strs``: maximal runs of
+    non-space tokens, counted from 0.  ``word_speed`` is a sequence with one rate per word or a ``{word_index: rate}`` dict (None:
+    no word is named); every token of a word gets the word's rate, spaces and unnamed words get 1.0.  A wrong count, an index that
+    is not the number of a word, or a rate that is not a finite number above 0 raises ValueError."""
+    word_of: List[int] = []   # per token: its word's number, -1 for a space
+    n_words, inside = 0, False
+    for tok in token_strs:
+        if tok.isspace():
+            word_of.append(-1)
+            inside = False
+        else:
+            if not inside:
+                n_words, inside = n_words + 1, True
+            word_of.append(n_words - 1)
+    by_word = [1.0] * n_words
+    if word_speed is None:
+        pass
+    elif isinstance(word_speed, Mapping):
+        for w, rate in word_speed.items():
+            if isinstance(w, bool) or not isinstance(w, (int, np.integer)) or not 0 <= w < n_words:
+                raise ValueError(f"word index {w!r} is outside the sentence's {n_words} words")
+            by_word[int(w)] = _check_rate(rate, f"the rate of word {w}")
+    else:
+        rates = list(word_speed)
+        if len(rates) != n_words:
+            raise ValueError(f"{len(rates)} word rates for a sentence of {n_words} words")
+        by_word = [_check_rate(rate, f"the rate of word {w}") for w, rate in enumerate(rates)]
+    return [1.0 if w < 0 else by_word[w] for w in word_of]
+
+
 class Synthesizer:
     def __init__(self, tts_model_class, tts_config_path: str, tts_checkpoint_path: str, use_cuda: bool = True) -> None:
         if not (use_cuda and torch.cuda.is_available()):
@@ -119,8 +160,60 @@ class Synthesizer:
         return {"token_timings": list(zip(token_strs, starts, ends)), "word_timings": group_words(token_strs, starts, ends),
                 "timings_status": "ok"}
 
+    @staticmethod
+    def _sentence_rates(token_strs: Sequence[str], word_speed, token_speed) -> List[float]:
+        """One rate per token of a sentence: ``token_rates`` of ``word_speed`` times ``token_speed`` (a sequence per token, or None)."""
+        rates = token_rates(token_strs, word_speed)
+        if token_speed is not None:
+            per_token = list(token_speed)
+            if len(per_token) != len(token_strs):
+                raise ValueError(f"{len(per_token)} token rates for a sentence of {len(token_strs)} tokens")
+            rates = [a * _check_rate(b, f"the rate of token {l}") for l, (a, b) in enumerate(zip(rates, per_token))]
+        return rates
+
+    @staticmethod
+    def _check_speed(speed) -> float:
+        speed = _check_rate(speed, "speed")
+        if not RATE_MIN <= speed <= RATE_MAX:
+            raise ValueError(f"speed = {speed} is outside [{RATE_MIN}, {RATE_MAX}]")
+        return speed
+
+    def _rate_control(self, outputs: Dict[str, torch.Tensor], frames: Optional[torch.Tensor], token_lengths: Optional[torch.Tensor],
+                      speed: float, rates: Sequence[Sequence[float]], names: Sequence[str]):
+        """The rate-controlled mel of a decoded batch, on the device: monotonic alignment search over the alignments already there,
+        the plan at ``speed`` times the rows' per-token ``rates`` (``metrics.scale_durations``), the token-wise time warp of
+        ``mel_outputs_postnet`` (``metrics.time_warp``).  A row whose search is infeasible (fewer frames than tokens) is warped as
+        one token of all its frames at ``speed`` alone.  Returns ``(mel [B, M, max T'], T' int32 [B] on the device, host)``, host =
+        per row (target start frames, status of the search, T') from one small copy.  A row the plan refuses raises ValueError with
+        its name from ``names``."""
+        from . import metrics
+
+        mel, a = outputs["mel_outputs_postnet"], outputs["alignments"]
+        B, L, dev = a.shape[0], a.shape[2], a.device
+        al = metrics.monotonic_align(a, frames, token_lengths)
+        feasible = al["status"] == 0
+        Tb = frames.to(torch.int32) if frames is not None else torch.full((B,), a.shape[1], dtype=torch.int32, device=dev)
+        Lb = token_lengths.to(torch.int32) if token_lengths is not None else torch.full((B,), L, dtype=torch.int32, device=dev)
+        whole = torch.zeros(B, L, dtype=torch.int32, device=dev)
+        whole[:, 0] = Tb
+        table = torch.ones(B, L, dtype=torch.float32)
+        for r, row in enumerate(rates):
+            table[r, :len(row)] = torch.tensor(row, dtype=torch.float32)
+        durations = torch.where(feasible[:, None], al["durations"], whole)
+        n_tokens = torch.where(feasible, Lb, torch.ones_like(Lb))
+        table = torch.where(feasible[:, None], table.to(dev), torch.ones((), dtype=torch.float32, device=dev))
+        plan = metrics.scale_durations(durations, n_tokens, speed, table)
+        host = torch.cat([plan["starts"], al["status"][:, None], plan["status"][:, None], plan["out_lengths"][:, None]], dim=1).cpu().tolist()
+        for r, row in enumerate(host):
+            if row[-2] != 0:
+                raise ValueError(f"{names[r]}: the rate plan is {metrics.WARP_STATUS_NAMES[row[-2]]} - speed {speed} times a token's rate "
+                                 f"is outside [{RATE_MIN}, {RATE_MAX}], or the result is longer than the warp's limit of frames")
+        warped = metrics.time_warp(mel, durations, plan["durations"], n_tokens, T_out=max(row[-1] for row in host))
+        return warped["mel"], plan["out_lengths"], [(row[:-3], row[-3], row[-1]) for row in host]
+
     def tts(self, text: str, sampling_rate: Optional[int] = None, diagnostics: bool = False,
-            attention_window: Optional[Tuple[int, int]] = None, timings: bool = False) -> Dict[str, np.ndarray]:
+            attention_window: Optional[Tuple[int, int]] = None, timings: bool = False, speed: float = 1.0,
+            word_speed=None, token_speed=None) -> Dict[str, np.ndarray]:
         """``sampling_rate`` (Hz; default: the model's): the waveform is resampled on the device before it is copied to the host,
         and ``"sampling_rate"`` of the result is the rate delivered.  ``diagnostics``: the result gains ``"alignment_stats"``
         (focus, monotonic_fraction, max_jump, coverage, first_pos, last_pos of the sentence's alignment, as Python numbers) and
@@ -133,8 +226,19 @@ class Synthesizer:
         sentence's alignment (``metrics.monotonic_align``), in seconds of the delivered waveform whatever its rate, each token
         ending where the next starts and the last at the waveform's end - ``"word_timings"`` (``group_words`` of them) and
         ``"timings_status"``: ``"ok"``, or ``"infeasible"`` with both lists empty when the decode stopped with fewer frames than
-        tokens."""
+        tokens.  ``speed`` (in [0.125, 8]; 2 = twice as fast), ``word_speed`` (one rate per word, or ``{word_index: rate}``: see
+        ``token_rates``) and ``token_speed`` (one rate per token) set the speaking rate: token l is spoken ``speed`` times its
+        word's rate times its own rate as fast.  With all three at their defaults nothing changes.  Otherwise the decoded mel is
+        warped along time token by token on the device (the search of ``timings``, ``metrics.scale_durations``,
+        ``metrics.time_warp``) and the waveform is vocoded from the warped mel: the result gains ``"mel_outputs_warped"``
+        [n_mels, T'] and ``"speed"``, every other mel, gate and alignment key is the decode as it was, and ``timings`` are read off
+        the plan's own frame counts - exact for the delivered waveform.  A decode with fewer frames than tokens is warped as a whole
+        at ``speed``; a rate outside [0.125, 8] after multiplication, or a result above 32768 frames, raises ValueError."""
         token_strs = self.text_processor.tokenize(text)
+        paced = speed != 1.0 or word_speed is not None or token_speed is not None
+        if paced:
+            speed = self._check_speed(speed)
+            rates = [self._sentence_rates(token_strs, word_speed, token_speed)]
         tokens = self.text_processor.tokens_to_indices(token_strs)
         tokens = torch.IntTensor(tokens).unsqueeze(0).to(self.device)
         inputs = {"tokens": tokens}
@@ -145,19 +249,26 @@ class Synthesizer:
         if diagnostics and attention_window is not None:
             extra["attention_window"] = tuple(int(v) for v in attention_window)
         mel = outputs["mel_outputs_postnet"]
-        aligned = self._align(outputs, None, None) if timings else None
+        if paced:
+            mel, _, plan = self._rate_control(outputs, None, None, speed, rates, ["sentence 0"])
+            aligned = ([plan[0][0]], [plan[0][1]]) if timings else None
+        else:
+            aligned = self._align(outputs, None, None) if timings else None
         wav = self.audio_processor.convert_mel2wav_batch(mel, out_rate=sampling_rate)  # stays on the device until the end
         result = {key: val.squeeze(0).cpu().numpy() for key, val in outputs.items()}
         result["waveform"] = wav[0].cpu().numpy()
         result["sampling_rate"] = self._out_rate(sampling_rate)
         result.update(extra)
+        if paced:
+            result["mel_outputs_warped"] = mel[0].cpu().numpy()
+            result["speed"] = speed
         if aligned is not None:
             result.update(self._timings(token_strs, aligned[0][0], aligned[1][0], mel.shape[2], wav.shape[1], result["sampling_rate"]))
         return result
 
     def tts_batch(self, texts: Sequence[str], batch_size: int = 32, sampling_rate: Optional[int] = None,
                   diagnostics: bool = False, attention_window: Optional[Tuple[int, int]] = None,
-                  timings: bool = False) -> List[Dict[str, np.ndarray]]:
+                  timings: bool = False, speed: float = 1.0, word_speed=None, token_speed=None) -> List[Dict[str, np.ndarray]]:
         """Many sentences per call: one dict per sentence, in input order, with the keys, dtypes and shapes ``tts(text)`` gives
         for that sentence (every row trimmed to its own frames, tokens and samples).  Sentences are decoded as padded batches of
         at most ``batch_size`` rows of similar token length (``plan_tts_batches``) and vocoded at their own lengths in one ragged
@@ -165,9 +276,19 @@ class Synthesizer:
         torch RNG draws included.  ``sampling_rate`` as in ``tts``: every row is resampled at its own sample count.
         ``diagnostics`` as in ``tts``: every sentence's alignment at its own frames and tokens.  ``attention_window`` as in
         ``tts``: every sentence is decoded with it and carries its own ``"attention_centres"``.  ``timings`` as in ``tts``: every
-        sentence aligned at its own frames and tokens, timed against its own waveform."""
+        sentence aligned at its own frames and tokens, timed against its own waveform.  ``speed`` as in ``tts``, for every
+        sentence; ``word_speed`` and ``token_speed`` are lists with one entry per sentence, each as in ``tts`` (None: no rates
+        for that sentence): every sentence is warped at its own frames, tokens and rates and vocoded at its own new length."""
         token_strs = [self.text_processor.tokenize(t) for t in texts]
         token_lists = [self.text_processor.tokens_to_indices(toks) for toks in token_strs]
+        paced = speed != 1.0 or word_speed is not None or token_speed is not None
+        if paced:
+            speed = self._check_speed(speed)
+            for what, per in (("word_speed", word_speed), ("token_speed", token_speed)):
+                if per is not None and len(per) != len(token_strs):
+                    raise ValueError(f"{what} has {len(per)} entries for {len(token_strs)} sentences")
+            rates = [self._sentence_rates(toks, word_speed[i] if word_speed is not None else None,
+                                          token_speed[i] if token_speed is not None else None) for i, toks in enumerate(token_strs)]
         results: List[Dict[str, np.ndarray]] = [{} for _ in token_lists]
         for idx, tokens, lens in plan_tts_batches(token_lists, batch_size):
             inputs = {"tokens": tokens.to(self.device)}
@@ -178,15 +299,25 @@ class Synthesizer:
             outputs = self.tts_model.inference(inputs=inputs)
             mel = outputs["mel_outputs_postnet"]
             extras = self._diagnose(outputs, outputs.get("mel_lengths"), inputs.get("token_lengths")) if diagnostics else None
-            aligned = self._align(outputs, outputs.get("mel_lengths"), inputs.get("token_lengths")) if timings else None
+            warped = None
+            if paced:
+                warped, new_frames, plan = self._rate_control(outputs, outputs.get("mel_lengths"), inputs.get("token_lengths"), speed,
+                                                              [rates[i] for i in idx], [f"sentence {i}" for i in idx])
+                aligned = ([p[0] for p in plan], [p[1] for p in plan]) if timings else None
+                new_frames_host = [p[2] for p in plan]
+            else:
+                aligned = self._align(outputs, outputs.get("mel_lengths"), inputs.get("token_lengths")) if timings else None
             if len(idx) > 1:
                 frames = outputs.pop("mel_lengths")
-                wav, samples = self.audio_processor.convert_mel2wav_batch(mel, mel_lengths=frames, out_rate=sampling_rate)
+                wav, samples = self.audio_processor.convert_mel2wav_batch(mel if warped is None else warped, out_rate=sampling_rate,
+                                                                          mel_lengths=frames if warped is None else new_frames)
                 frames = frames.tolist()
             else:
-                wav = self.audio_processor.convert_mel2wav_batch(mel, out_rate=sampling_rate)
+                wav = self.audio_processor.convert_mel2wav_batch(mel if warped is None else warped, out_rate=sampling_rate)
                 frames, samples = [mel.shape[2]], [wav.shape[1]]
             host = {key: val.cpu().numpy() for key, val in outputs.items()}
+            if warped is not None:
+                warped = warped.cpu().numpy()
             wav = wav.cpu().numpy()
             for r, i in enumerate(idx):
                 t, n_tok = frames[r], int(lens[r])
@@ -202,6 +333,10 @@ class Synthesizer:
                     results[i].update(extras[r])
                     if attention_window is not None:
                         results[i]["attention_window"] = tuple(int(v) for v in attention_window)
+                if warped is not None:
+                    t = new_frames_host[r]   # the frames of the delivered waveform
+                    results[i]["mel_outputs_warped"] = warped[r, :, :t].copy()
+                    results[i]["speed"] = speed
                 if aligned is not None:
                     results[i].update(self._timings(token_strs[i], aligned[0][r], aligned[1][r], t, samples[r], self._out_rate(sampling_rate)))
         return results

@@ -713,6 +713,71 @@ int gvx_monotonic_align(const float* alignments, const int32_t* mel_lengths, con
                         float floor, int32_t* path_out, int32_t* durations_out, int32_t* starts_out, float* score_out,
                         int32_t* row_status_out, float* scores_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Speaking rate control: a token-wise time warp of a mel, in two calls - the plan (how many frames every token gets) and the warp.
+ * Both are asynchronous on `stream`, write caller-allocated outputs only, need no workspace and give the same bits every run; no
+ * workgroup waits for another and every loop is bounded by L or M.  For row b, L_b = token_lengths[b] clamped to [0, L] (NULL: L);
+ * nothing behind a row's L_b tokens is read, whatever it holds.
+ *
+ * gvx_duration_scale - the plan.  durations is int32 [B][L] (frames per token, as gvx_monotonic_align writes them), rates fp32
+ * [B][L] or NULL for all 1, speed a host float.  Token l is to be spoken e_l = (double)speed * (double)rates[b][l] times as fast:
+ *
+ *     E_l      = E_{l-1} + (double)d_l / e_l                ascending l from E_{-1} = 0, IEEE double, one rounding per operation
+ *     c_l      = llrint(E_l)                                round half to even
+ *     S'_0     = 0
+ *     S'_{l+1} = max( S'_l + (d_l > 0 ? 1 : 0), c_l )       64-bit integers
+ *     d'_l     = S'_{l+1} - S'_l                            T'_b = S'_{L_b}
+ *
+ * so a spoken token keeps at least one frame, a token without frames gets none, and the rounding error is carried forward
+ * instead of piling up: T'_b = llrint(sum d_l / e_l) unless the one-frame minimum binds.  Outputs:
+ *     target_durations_out  int32 [B][L]   d'_l; 0 for l >= L_b
+ *     target_starts_out     int32 [B][L]   S'_l; -1 for l >= L_b                                                     (or NULL)
+ *     out_lengths_out       int32 [B]      T'_b
+ *     row_status_out        int32 [B]      decided in this order: GVX_WARP_EMPTY for L_b == 0; GVX_WARP_BAD for a token l < L_b with a
+ *                                          negative duration or an e_l that is not inside [GVX_RATE_MIN, GVX_RATE_MAX] = [0.125, 8]
+ *                                          (which a non-finite or non-positive rate never is); GVX_WARP_EMPTY for a duration sum
+ *                                          of 0; GVX_WARP_BAD for T'_b above GVX_MAS_MAX_FRAMES; else GVX_WARP_OK.  EMPTY and BAD
+ *                                          rows have durations 0, starts -1 and length 0.
+ * One workgroup per row: the quotients are formed by all threads into LDS (8 L + 4 (L + 1) bytes), one lane walks the sum, the
+ * workgroup writes the outputs.  Refused before anything is launched: L above GVX_MAS_MAX_TOKENS: GVX_ERR_UNSUPPORTED; B or L
+ * below 1, a speed that is not inside [GVX_RATE_MIN, GVX_RATE_MAX] (NaN and inf are not), a NULL durations, target_durations_out,
+ * out_lengths_out or row_status_out: GVX_ERR_INVALID_ARG.
+ *
+ * gvx_mel_time_warp - the warp.  mel is fp32 [B][M][T], durations and target_durations int32 [B][L].  With the source starts S_l
+ * (prefix sums of d, T_b = S_{L_b}) and the target starts S'_l (of d', T'_b = S'_{L_b}), all sums in 64 bits, output frame
+ * u < T'_b lies in the token l with S'_l <= u < S'_{l+1} at j = u - S'_l, and maps centre to centre in exact integers:
+ *
+ *     n    = (2 j + 1) d_l - d'_l
+ *     i0   = S_l + floor( n / (2 d'_l) )           rem = n mod 2 d'_l  (in [0, 2 d'_l))
+ *     frac = (float)( (double)rem / (double)(2 d'_l) )
+ *     i0 < 0: i0 = 0, frac = 0;   i0 >= T_b - 1: i0 = T_b - 1, frac = 0
+ *     out[b][m][u] = frac == 0 ? x[b][m][i0] : fmaf( frac, x[b][m][i0 + 1] - x[b][m][i0], x[b][m][i0] )
+ *
+ * A frame with frac == 0 never reads its neighbour, d' == d returns the input bits, and whatever lies at and behind T_b reaches
+ * no output.  Outputs:
+ *     mel_out         fp32  [B][M][T_out]  exact zeros for u >= T'_b
+ *     src_frame_out   int32 [B][T_out]     i0; -1 for u >= T'_b                                                      (or NULL)
+ *     src_frac_out    fp32  [B][T_out]     frac; 0 for u >= T'_b                                                     (or NULL)
+ *     row_status_out  int32 [B]            decided in this order: GVX_WARP_BAD for a negative entry of either table, a token with
+ *                                          d_l > 0 and d'_l == 0 or the converse, or T_b > T; GVX_WARP_EMPTY for L_b == 0 or
+ *                                          T'_b == 0; GVX_WARP_CUT for T'_b > T_out (the first T_out frames are computed); else
+ *                                          GVX_WARP_OK.  BAD and EMPTY rows come out as rows of length 0: mel 0, frames -1, fracs 0.
+ * mel_out has the same bits with and without the two map outputs; they let a caller warp anything else by the same map, and a
+ * test restate the interpolation exactly.  One launch; a workgroup owns a row and GVX_WARP_TILE_FRAMES output frames for all M
+ * channels: it builds both prefix sums in LDS (8 (L + 1) bytes), finds every frame's token by bisection once, and streams the
+ * channels with loads and stores that run along t.  Refused before anything is launched: L above GVX_MAS_MAX_TOKENS, T or T_out
+ * above GVX_MAS_MAX_FRAMES: GVX_ERR_UNSUPPORTED; B, M, T, L or T_out below 1, a NULL mel, durations, target_durations, mel_out or
+ * row_status_out: GVX_ERR_INVALID_ARG. */
+enum { GVX_WARP_OK = 0, GVX_WARP_EMPTY = 1, GVX_WARP_BAD = 2, GVX_WARP_CUT = 3 };
+enum { GVX_WARP_TILE_FRAMES = 64 };
+#define GVX_RATE_MIN 0.125f
+#define GVX_RATE_MAX 8.0f
+int gvx_duration_scale(const int32_t* durations, const int32_t* token_lengths, const float* rates, int B, int L, float speed,
+                       int32_t* target_durations_out, int32_t* target_starts_out, int32_t* out_lengths_out, int32_t* row_status_out,
+                       void* stream);
+int gvx_mel_time_warp(const float* mel, const int32_t* durations, const int32_t* target_durations, const int32_t* token_lengths, int B,
+                      int M, int T, int L, int T_out, float* mel_out, int32_t* src_frame_out, float* src_frac_out,
+                      int32_t* row_status_out, void* stream);
+
 /* ---- Per-kernel timing of the decoder step (measurement only): when enabled, a teacher-forced call replays the
  * mid-sequence LSTM-step launch and the attention launches 64 times each, back to back, between HIP events on
  * `stream` (after its loop; the call's outputs are not valid afterwards); gvx_kernel_times_ms synchronises and
