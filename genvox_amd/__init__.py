@@ -1,9 +1,10 @@
 """genvox_amd: MI355X-native Tacotron2 text->mel forward path and Griffin-Lim vocoder behind GenVox's Python surface.
 
     from genvox_amd import Tacotron2, Synthesizer, AudioProcessor, Tacotron2Config, AudioConfig, TextConfig
+    from genvox_amd import MelGANGenerator, MelGANConfig   # neural vocoder: Synthesizer(..., vocoder_model_class=MelGANGenerator, ...)
     from genvox_amd import Tacotron2GuidedLoss    # training criterion: Tacotron2Loss + alpha x guided attention loss
 """
-from .configs import AudioConfig, BaseConfig, Tacotron2Config, TextConfig  # noqa: F401
+from .configs import AudioConfig, BaseConfig, MelGANConfig, Tacotron2Config, TextConfig  # noqa: F401
 
 
 def __getattr__(name):  # torch-dependent classes are imported lazily
@@ -13,6 +14,9 @@ def __getattr__(name):  # torch-dependent classes are imported lazily
     if name == "Tacotron2GuidedLoss":
         from .tacotron2 import Tacotron2GuidedLoss
         return Tacotron2GuidedLoss
+    if name == "MelGANGenerator":
+        from .melgan import MelGANGenerator
+        return MelGANGenerator
     if name == "Synthesizer":
         from .synthesizer import Synthesizer
         return Synthesizer

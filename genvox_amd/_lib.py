@@ -28,6 +28,11 @@ class gvx_weight_desc(C.Structure):
 _vp, _i, _sz, _f, _l = C.c_void_p, C.c_int, C.c_size_t, C.c_float, C.c_long
 
 
+class gvx_melgan_dims(C.Structure):
+    _fields_ = [("n_mels", C.c_int32), ("base_channels", C.c_int32), ("n_stages", C.c_int32), ("ratios", C.c_int32 * 8),
+                ("n_residual_layers", C.c_int32), ("dilation_base", C.c_int32), ("slope", C.c_float)]
+
+
 class gvx_tensor_ref(C.Structure):
     _fields_ = [("data", C.c_void_p), ("numel", C.c_int64)]
 
@@ -127,6 +132,15 @@ SIGNATURES = {
     "gvx_monotonic_align": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "gvx_duration_scale": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
     "gvx_mel_time_warp": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "gvx_melgan_blob_floats": (_sz, [C.POINTER(gvx_melgan_dims)]),
+    "gvx_melgan_workspace_bytes": (_sz, [C.POINTER(gvx_melgan_dims), _i, _i]),
+    "gvx_melgan_pack_weights_device": (_i, [C.POINTER(gvx_melgan_dims), C.POINTER(gvx_weight_desc), _i, _vp, _vp]),
+    "gvx_melgan_create": (_i, [C.POINTER(gvx_melgan_dims), C.POINTER(_vp)]),
+    "gvx_melgan_destroy": (None, [_vp]),
+    "gvx_melgan_bind": (_i, [_vp, _vp]),
+    "gvx_melgan_forward": (_i, [_vp, _vp, _vp, _i, _i, _vp, C.POINTER(_vp), _vp, _sz, _vp]),
+    "gvx_melgan_timing_enable": (_i, [_vp, _i]),
+    "gvx_melgan_stage_times_ms": (_i, [_vp, C.POINTER(_f), C.POINTER(_i)]),
     "gvx_kernel_timing_enable": (_i, [_vp, _i]),
     "gvx_model_set_persistent_attention": (_i, [_vp, _i]),
     "gvx_model_set_resident_kernels": (_i, [_vp, _i]),

@@ -156,3 +156,61 @@ class Tacotron2Config(BaseConfig):
         "beta1": (0.9, (0, 1)),
         "beta2": (0.999, (0, 1)),
     }
+
+
+class MelGANConfig(BaseConfig):
+    """reference: configs/models.py:89-121 (the eight training fields: same names, defaults and ranges), followed by the generator's
+    own shape, which the reference's config does not carry (it ships no vocoder model): a yaml written from the reference's
+    ``MelGANConfig`` loads with these at their defaults.  ``upsample_ratios`` must multiply to the audio config's ``hop_length``
+    (``check_hop``: the config alone does not know it)."""
+
+    _FIELDS = {
+        "train_repeat_discriminator": (1, (1, None)),
+        "max_frames": (200, (100, None)),
+        "feat_match": (10.0, (1, None)),
+        "learning_rate": (1e-4, (1e-5, None)),
+        "weight_decay": (0, (0, None)),
+        "grad_clip_thresh": (1.0, (0, None)),
+        "beta1": (0.5, (0, 1)),
+        "beta2": (0.9, (0, 1)),
+        "base_channels": (512, None),
+        "upsample_ratios": ((8, 8, 2, 2), None),
+        "n_residual_layers": (3, None),
+        "dilation_base": (3, None),
+        "leaky_slope": (0.2, None),
+    }
+
+    def _normalise(self) -> None:
+        try:
+            self.upsample_ratios = [int(r) for r in self.upsample_ratios]   # a list: what a yaml file holds
+        except (TypeError, ValueError):
+            raise ValueError(f"upsample_ratios must be a sequence of integers, not {self.upsample_ratios!r}") from None
+        ints = {"base_channels": self.base_channels, "n_residual_layers": self.n_residual_layers, "dilation_base": self.dilation_base}
+        for name, v in ints.items():
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError(f"{name} must be an integer >= 1, not {v!r}")
+        if not 1 <= len(self.upsample_ratios) <= 8:
+            raise ValueError(f"upsample_ratios must name 1 to 8 stages, not {len(self.upsample_ratios)}")
+        for r in self.upsample_ratios:
+            if r < 2 or r % 2:
+                raise ValueError(f"every upsampling ratio must be even and >= 2 (kernel 2r, stride r, padding r/2), not {r}")
+        if self.base_channels % (1 << len(self.upsample_ratios)):
+            raise ValueError(f"base_channels = {self.base_channels} is not divisible by 2^{len(self.upsample_ratios)}: every stage halves the channels")
+        if self.n_residual_layers > 8:
+            raise ValueError(f"n_residual_layers = {self.n_residual_layers} is above 8")
+        if self.dilation_base ** (self.n_residual_layers - 1) >= 4 * self.upsample_ratios[0]:
+            raise ValueError(f"the largest dilation {self.dilation_base ** (self.n_residual_layers - 1)} must be below 4 * {self.upsample_ratios[0]}, "
+                             f"the shortest row of the first stage")
+        if not 0.0 <= float(self.leaky_slope) <= 1.0:
+            raise ValueError(f"leaky_slope = {self.leaky_slope} is outside [0, 1]")
+
+    @property
+    def hop(self) -> int:
+        hop = 1
+        for r in self.upsample_ratios:
+            hop *= r
+        return hop
+
+    def check_hop(self, hop_length: int) -> None:
+        if self.hop != int(hop_length):
+            raise ValueError(f"upsample_ratios {tuple(self.upsample_ratios)} multiply to {self.hop}, the audio config's hop_length is {hop_length}")

@@ -8,6 +8,7 @@ from typing import Dict, List, Mapping, Optional, Sequence, Tuple, Union
 import numpy as np
 import torch
 
+from . import resample as rs
 from .audio import AudioProcessor
 from .text import TextProcessor
 
@@ -107,7 +108,11 @@ def token_rates(token_strs: Sequence[str], word_speed: Union[Sequence[float], Ma
 
 
 class Synthesizer:
-    def __init__(self, tts_model_class, tts_config_path: str, tts_checkpoint_path: str, use_cuda: bool = True) -> None:
+    def __init__(self, tts_model_class, tts_config_path: str, tts_checkpoint_path: str, use_cuda: bool = True, vocoder_model_class=None,
+                 vocoder_config_path: Optional[str] = None, vocoder_checkpoint_path: Optional[str] = None) -> None:
+        """``vocoder_model_class`` (``MelGANGenerator``) with its config and checkpoint paths: ``tts`` and ``tts_batch`` vocode the mel
+        through that model instead of Griffin-Lim.  The waveform is then float32 of exactly ``frames * hop_length`` samples (no trim,
+        no low-pass), and every result carries ``"vocoder"``: the model's name.  All three or none: with none nothing changes."""
         if not (use_cuda and torch.cuda.is_available()):
             raise RuntimeError("genvox_amd.Synthesizer needs an MI355X (use_cuda=True and a visible GPU); it has no CPU path")
         self.device = "cuda:0"
@@ -120,6 +125,20 @@ class Synthesizer:
         self.tts_model.load_checkpoint_statedicts(statedicts=ckpt, save_optimizer_dict=False, optimizer=None)
         self.text_processor = TextProcessor(config=self.tts_model.text_config)
         self.audio_processor = AudioProcessor(config=self.tts_model.audio_config, device=self.device)
+        given = [vocoder_model_class, vocoder_config_path, vocoder_checkpoint_path]
+        self.vocoder = None
+        if any(g is not None for g in given):
+            if any(g is None for g in given):
+                raise ValueError("a vocoder needs vocoder_model_class, vocoder_config_path and vocoder_checkpoint_path, all three")
+            voc = vocoder_model_class.load_from_config(config_path=vocoder_config_path)
+            ac, mine = voc.audio_config, self.tts_model.audio_config
+            for field in ("n_mels", "hop_length", "sampling_rate"):
+                if getattr(ac, field) != getattr(mine, field):
+                    raise ValueError(f"the vocoder's {field} = {getattr(ac, field)} is not the text-to-mel model's {getattr(mine, field)}")
+            voc.to(self.device)
+            voc.eval()
+            voc.load_checkpoint_statedicts(statedicts=torch.load(vocoder_checkpoint_path, map_location="cpu"), save_optimizer_dict=False, optimizer=None)
+            self.vocoder = voc
 
     def _out_rate(self, sampling_rate: Optional[int]) -> int:
         return self.audio_processor.config.sampling_rate if sampling_rate is None else int(sampling_rate)
@@ -155,10 +174,36 @@ class Synthesizer:
         if status != 0:   # fewer frames than tokens: a collapsed decode is for the diagnostics to report, not an error here
             return {"token_timings": [], "word_timings": [], "timings_status": "infeasible"}
         ap = self.audio_processor
-        starts, ends = token_times(start_frames[:len(token_strs)], ap.config.hop_length, ap.TRIM, ap.row_samples([n_frames])[0],
-                                   ap.config.sampling_rate, n_delivered / out_rate)
+        # a neural vocoder delivers frames * hop samples untrimmed: frame f starts at sample f * hop
+        trim, n_samples = (ap.TRIM, ap.row_samples([n_frames])[0]) if self.vocoder is None else (0, n_frames * ap.config.hop_length)
+        starts, ends = token_times(start_frames[:len(token_strs)], ap.config.hop_length, trim, n_samples, ap.config.sampling_rate, n_delivered / out_rate)
         return {"token_timings": list(zip(token_strs, starts, ends)), "word_timings": group_words(token_strs, starts, ends),
                 "timings_status": "ok"}
+
+    def _vocode(self, mel: torch.Tensor, frames, sampling_rate: Optional[int]):
+        """mel [B, M, T] on the device -> ``(waveforms on the device, sample counts per row or None)``; ``frames`` (None: all T) are the
+        rows' own lengths.  Without a vocoder model this is ``AudioProcessor.convert_mel2wav_batch`` (Griffin-Lim), call for call.
+        With one, the rows go through it in one ragged call - float32 [B, T * hop], row b of ``frames[b] * hop`` samples - and are
+        resampled like Griffin-Lim's, every row at its own sample count."""
+        ap = self.audio_processor
+        if self.vocoder is None:
+            if frames is None:
+                return ap.convert_mel2wav_batch(mel, out_rate=sampling_rate), None
+            return ap.convert_mel2wav_batch(mel, out_rate=sampling_rate, mel_lengths=frames)
+        hop, rate = self.vocoder.hop, int(ap.config.sampling_rate)
+        host = None if frames is None else [int(t) for t in (frames.tolist() if isinstance(frames, torch.Tensor) else frames)]
+        wav = self.vocoder.vocode(mel.contiguous(), host)
+        counts = None if host is None else [t * hop for t in host]
+        if sampling_rate is not None and int(sampling_rate) != rate:
+            up, down = rs.resample_ratio(rate, int(sampling_rate))
+            rs.check_ratio(up, down)
+            rows = counts if counts is not None else [wav.shape[1]] * wav.shape[0]
+            bounds = torch.tensor([[0, n] for n in rows], dtype=torch.int32, device=self.device)
+            out = torch.empty(wav.shape[0], rs.resampled_length(wav.shape[1], up, down), dtype=torch.float32, device=self.device)
+            ap._resample_into(wav, bounds, rate, int(sampling_rate), out)
+            wav = out
+            counts = None if counts is None else [rs.resampled_length(n, up, down) for n in counts]
+        return wav, counts
 
     @staticmethod
     def _sentence_rates(token_strs: Sequence[str], word_speed, token_speed) -> List[float]:
@@ -254,10 +299,12 @@ class Synthesizer:
             aligned = ([plan[0][0]], [plan[0][1]]) if timings else None
         else:
             aligned = self._align(outputs, None, None) if timings else None
-        wav = self.audio_processor.convert_mel2wav_batch(mel, out_rate=sampling_rate)  # stays on the device until the end
+        wav, _ = self._vocode(mel, None, sampling_rate)  # stays on the device until the end
         result = {key: val.squeeze(0).cpu().numpy() for key, val in outputs.items()}
         result["waveform"] = wav[0].cpu().numpy()
         result["sampling_rate"] = self._out_rate(sampling_rate)
+        if self.vocoder is not None:
+            result["vocoder"] = self.vocoder.model_name
         result.update(extra)
         if paced:
             result["mel_outputs_warped"] = mel[0].cpu().numpy()
@@ -309,11 +356,10 @@ class Synthesizer:
                 aligned = self._align(outputs, outputs.get("mel_lengths"), inputs.get("token_lengths")) if timings else None
             if len(idx) > 1:
                 frames = outputs.pop("mel_lengths")
-                wav, samples = self.audio_processor.convert_mel2wav_batch(mel if warped is None else warped, out_rate=sampling_rate,
-                                                                          mel_lengths=frames if warped is None else new_frames)
+                wav, samples = self._vocode(mel if warped is None else warped, frames if warped is None else new_frames, sampling_rate)
                 frames = frames.tolist()
             else:
-                wav = self.audio_processor.convert_mel2wav_batch(mel if warped is None else warped, out_rate=sampling_rate)
+                wav, _ = self._vocode(mel if warped is None else warped, None, sampling_rate)
                 frames, samples = [mel.shape[2]], [wav.shape[1]]
             host = {key: val.cpu().numpy() for key, val in outputs.items()}
             if warped is not None:
@@ -327,6 +373,8 @@ class Synthesizer:
                               "alignments": host["alignments"][r, :t, :n_tok].copy(),
                               "waveform": wav[r, :samples[r]].copy(),
                               "sampling_rate": self._out_rate(sampling_rate)}
+                if self.vocoder is not None:
+                    results[i]["vocoder"] = self.vocoder.model_name
                 if attention_window is not None:
                     results[i]["attention_centres"] = host["attention_centres"][r, :t].copy()
                 if extras is not None:

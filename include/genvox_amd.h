@@ -778,6 +778,80 @@ int gvx_mel_time_warp(const float* mel, const int32_t* durations, const int32_t*
                       int M, int T, int L, int T_out, float* mel_out, int32_t* src_frame_out, float* src_frac_out,
                       int32_t* row_status_out, void* stream);
 
+/* ---- Neural vocoder: MelGAN generator inference, mel -> waveform.  The reference promises a vocoder model and ships only its config
+ * (configs/models.py:89-121, MelGANConfig); the network below is this project's statement of the MelGAN generator.
+ *
+ * Input: mel fp32 [B][n_mels][T], as the Tacotron2 calls deliver mel_outputs_postnet (no conversion).  Output: wav fp32 [B][T * hop],
+ * hop = the product of the ratios, every sample in (-1, 1).  lrelu(v) = v > 0 ? v : slope * v; "reflect p" mirrors p positions at both
+ * ends of the time axis without repeating the edge (torch.nn.functional.pad(mode="reflect")).  C_0 = base_channels, C_{i+1} = C_i / 2.
+ *
+ *     x = Conv1d(n_mels -> C_0, k = 7)(reflect 3 (mel))
+ *     for stage i, r = ratios[i]:
+ *         x = ConvTranspose1d(C_i -> C_{i+1}, kernel 2 r, stride r, padding r / 2)(lrelu(x))                 length times r
+ *         for j in 0 .. n_residual_layers - 1, d = dilation_base^j:
+ *             h = Conv1d(C_{i+1} -> C_{i+1}, k = 3, dilation d)(reflect d (lrelu(x)))
+ *             x = Conv1d(k = 1)(x) + Conv1d(k = 1)(lrelu(h))                                                 shortcut + mix
+ *     wav = tanh(Conv1d(C_last -> 1, k = 7)(reflect 3 (lrelu(x))))
+ *
+ * Ragged batches: frame_lengths is int32 [B] on the device, or NULL for all T.  Row b is computed at T_b = min(frame_lengths[b], T)
+ * frames: every reflection happens at the row's own end of that stage, so row b has the bits of that row run alone; nothing of mel at
+ * or behind frame T_b is read, and wav is exactly 0 from sample T_b * hop on.  A row needs T_b >= GVX_MELGAN_MIN_FRAMES (the first
+ * reflection); the host cannot see device lengths, so the CALLER checks them - a shorter row comes out as silence of length 0.
+ *
+ * Dims are refused (GVX_ERR_INVALID_ARG from create and pack, 0 from the size functions) unless: n_mels, base_channels >= 1; n_stages in
+ * [1, GVX_MELGAN_MAX_STAGES]; every ratio even and >= 2, their product <= GVX_MELGAN_MAX_HOP; base_channels divisible by 2^n_stages;
+ * n_residual_layers in [1, 8]; dilation_base >= 1 with dilation_base^(n_residual_layers - 1) < 4 * ratios[0] (a reflection stays inside
+ * the shortest row); slope in [0, 1].
+ *
+ * Weights.  gvx_melgan_pack_weights_device reads PyTorch-layout tensors from DEVICE pointers, by name:
+ *     pre.weight [C_0][n_mels][7], pre.bias;  ups.<i>.weight [C_i][C_{i+1}][2 r] (ConvTranspose1d: in, out, k), ups.<i>.bias;
+ *     res.<i>.<j>.conv.weight [C][C][3], res.<i>.<j>.shortcut.weight [C][C][1], res.<i>.<j>.mix.weight [C][C][1] and their .bias;
+ *     post.weight [1][C_last][7], post.bias
+ * and writes the blob the kernels read: K-contiguous rows [C_out][taps * C_in] (the first convolution's channels padded with zeros to a
+ * multiple of 4), the transposed convolutions split into their r phases [r][C_out][2 C_in], shortcut and mix side by side as one
+ * [C][2 C] matrix.  Every tensor of the blob starts at a multiple of 64 floats, so gvx_melgan_blob_floats = the parameter count
+ * + 7 * C_0 * (round4(n_mels) - n_mels) + what rounds each of its tensors (the 2 + 2 * n_stages + 5 * n_stages * n_residual_layers + 2
+ * listed above, shortcut and mix weights counting as one) up to a multiple of 64 floats.  A missing name is GVX_ERR_MISSING_WEIGHT, a
+ * wrong element count GVX_ERR_SHAPE, both before anything is launched.  The blob must be 256-byte aligned; the handle keeps the pointer.
+ *
+ * Workspace: gvx_melgan_workspace_bytes is host arithmetic (no device, no handle):
+ *     B * ( round256(4 * T * round4(n_mels)) + 3 * round256(4 * T * W) ),   W = max(C_0, max_i ratios[0] * .. * ratios[i] * C_{i+1})
+ * - the transposed mel and three activation tensors of the widest stage, which the layers rotate through.  With the defaults W = 8192:
+ * 98,624 bytes per frame and row.  Linear in B, monotone in T; any contents when the call starts, nothing is cleared; 256-byte aligned;
+ * a NULL, misaligned or short one is GVX_ERR_WORKSPACE before anything is launched (the conventions at the top of this header).
+ *
+ * gvx_melgan_forward is a feed-forward chain of ordinary launches on `stream` (2 + n_stages * (1 + 2 * n_residual_layers) + 1): every
+ * layer is one implicit GEMM over channels-last activations on v_mfma_f32_32x32x2_f32 (C_out >= 32) or fmaf dot products (narrower layers
+ * and the output layer).  No workgroup waits for another; two calls give the same bits.  stage_out is NULL or a HOST array of n_stages
+ * device pointers (16-byte aligned): stage_out[i] receives x after stage i's residual stack, fp32 [B][T * ratios[0] * .. * ratios[i]][C_{i+1}],
+ * exact zeros behind a row's own length - for tests that localise a wrong layer; it changes no bit of wav.  T below GVX_MELGAN_MIN_FRAMES,
+ * B outside [1, 65535] or a NULL mel / wav_out: GVX_ERR_INVALID_ARG; T above GVX_MELGAN_MAX_FRAMES: GVX_ERR_UNSUPPORTED; no blob bound:
+ * GVX_ERR_STATE.
+ *
+ * Timing (measurement only): with gvx_melgan_timing_enable, a forward records HIP events between the parts; gvx_melgan_stage_times_ms
+ * synchronises on the last and returns n_stages + 2 durations: first convolution (with the mel transpose), every stage, output layer. */
+enum { GVX_MELGAN_MAX_STAGES = 8, GVX_MELGAN_MIN_FRAMES = 4, GVX_MELGAN_MAX_FRAMES = 32768, GVX_MELGAN_MAX_HOP = 4096 };
+typedef struct gvx_melgan_dims {
+    int32_t n_mels;
+    int32_t base_channels;
+    int32_t n_stages;
+    int32_t ratios[GVX_MELGAN_MAX_STAGES];
+    int32_t n_residual_layers;
+    int32_t dilation_base;
+    float slope;
+} gvx_melgan_dims;
+typedef struct gvx_melgan gvx_melgan;
+size_t gvx_melgan_blob_floats(const gvx_melgan_dims* dims);
+size_t gvx_melgan_workspace_bytes(const gvx_melgan_dims* dims, int B, int T);
+int gvx_melgan_pack_weights_device(const gvx_melgan_dims* dims, const gvx_weight_desc* table, int n, float* device_blob, void* stream);
+int gvx_melgan_create(const gvx_melgan_dims* dims, gvx_melgan** out);
+void gvx_melgan_destroy(gvx_melgan* handle);
+int gvx_melgan_bind(gvx_melgan* handle, const float* device_blob);
+int gvx_melgan_forward(gvx_melgan* handle, const float* mel, const int32_t* frame_lengths, int B, int T, float* wav_out,
+                       float* const* stage_out, void* workspace, size_t workspace_bytes, void* stream);
+int gvx_melgan_timing_enable(gvx_melgan* handle, int enable);
+int gvx_melgan_stage_times_ms(gvx_melgan* handle, float* ms_out, int* n_out);
+
 /* ---- Per-kernel timing of the decoder step (measurement only): when enabled, a teacher-forced call replays the
  * mid-sequence LSTM-step launch and the attention launches 64 times each, back to back, between HIP events on
  * `stream` (after its loop; the call's outputs are not valid afterwards); gvx_kernel_times_ms synchronises and

@@ -1,0 +1,86 @@
+"""The MelGAN generator of include/genvox_amd.h ("Neural vocoder") restated with torch's own convolutions, for the tests of the device
+kernels.  Written from the definition alone: it imports nothing from genvox_amd.  Every function computes in the dtype of the state
+dict it is given - float64 for the reference, float32 for the reference's own rounding error, which sets the tests' tolerance."""
+import torch
+import torch.nn.functional as F
+
+DEFAULT = dict(n_mels=80, base_channels=512, ratios=(8, 8, 2, 2), n_res=3, dil_base=3, slope=0.2)
+NARROW = dict(n_mels=10, base_channels=32, ratios=(4, 2), n_res=3, dil_base=3, slope=0.2)    # channels 16 and 8: below a matrix tile; K = 70
+SHALLOW = dict(n_mels=20, base_channels=128, ratios=(4, 2), n_res=1, dil_base=2, slope=0.2)  # layer count and dilation come from the dims
+TWO_DEEP = dict(n_mels=20, base_channels=128, ratios=(4, 2), n_res=2, dil_base=2, slope=0.2)
+
+
+def hop(cfg) -> int:
+    out = 1
+    for r in cfg["ratios"]:
+        out *= r
+    return out
+
+
+def random_state(cfg, seed: int):
+    """Weights N(0, 1 / fan_in), biases 0.1 N(0, 1), float64, in PyTorch's layouts under the names the packer reads."""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+
+    def layer(name, shape, fan_in, n_out):
+        sd[name + ".weight"] = torch.randn(*shape, generator=g, dtype=torch.float64) * fan_in ** -0.5
+        sd[name + ".bias"] = 0.1 * torch.randn(n_out, generator=g, dtype=torch.float64)
+
+    c = cfg["base_channels"]
+    layer("pre", (c, cfg["n_mels"], 7), 7 * cfg["n_mels"], c)
+    for i, r in enumerate(cfg["ratios"]):
+        layer(f"ups.{i}", (c, c // 2, 2 * r), 2 * c, c // 2)   # ConvTranspose1d [in, out, k]: two taps reach an output
+        c //= 2
+        for j in range(cfg["n_res"]):
+            layer(f"res.{i}.{j}.conv", (c, c, 3), 3 * c, c)
+            layer(f"res.{i}.{j}.shortcut", (c, c, 1), c, c)
+            layer(f"res.{i}.{j}.mix", (c, c, 1), c, c)
+    layer("post", (1, c, 7), 7 * c, 1)
+    return sd
+
+
+def random_mel(cfg, B: int, T: int, seed: int) -> torch.Tensor:
+    g = torch.Generator().manual_seed(seed)
+    return 0.5 * torch.randn(B, cfg["n_mels"], T, generator=g, dtype=torch.float64) - 0.5
+
+
+def generator(sd, mel, cfg):
+    """mel [B, n_mels, T] -> (wav [B, T * hop], [x after every stage, [B, C_i, len_i]])."""
+    s = cfg["slope"]
+    x = F.conv1d(F.pad(mel, (3, 3), mode="reflect"), sd["pre.weight"], sd["pre.bias"])
+    stages = []
+    for i, r in enumerate(cfg["ratios"]):
+        x = F.conv_transpose1d(F.leaky_relu(x, s), sd[f"ups.{i}.weight"], sd[f"ups.{i}.bias"], stride=r, padding=r // 2)
+        for j in range(cfg["n_res"]):
+            d = cfg["dil_base"] ** j
+            p = f"res.{i}.{j}."
+            h = F.conv1d(F.pad(F.leaky_relu(x, s), (d, d), mode="reflect"), sd[p + "conv.weight"], sd[p + "conv.bias"], dilation=d)
+            x = F.conv1d(x, sd[p + "shortcut.weight"], sd[p + "shortcut.bias"]) + F.conv1d(F.leaky_relu(h, s), sd[p + "mix.weight"], sd[p + "mix.bias"])
+        stages.append(x)
+    wav = torch.tanh(F.conv1d(F.pad(F.leaky_relu(x, s), (3, 3), mode="reflect"), sd["post.weight"], sd["post.bias"]))
+    return wav[:, 0], stages
+
+
+def generator_ragged(sd, mel, lengths, cfg):
+    """Every row alone at its own length, zero-filled to the batch's shapes.  Frames at and behind a row's length are never touched."""
+    B, _, T = mel.shape
+    wav, stages, mul, c = torch.zeros(B, T * hop(cfg), dtype=mel.dtype), [], 1, cfg["base_channels"]
+    for r in cfg["ratios"]:
+        mul, c = mul * r, c // 2
+        stages.append(torch.zeros(B, c, T * mul, dtype=mel.dtype))
+    for b, t in enumerate(lengths):
+        w, st = generator(sd, mel[b:b + 1, :, :t], cfg)
+        wav[b, :w.shape[1]] = w[0]
+        for full, one in zip(stages, st):
+            full[b, :, :one.shape[2]] = one[0]
+    return wav, stages
+
+
+def reference_pair(sd, mel, lengths, cfg):
+    """(float64 outputs, per tensor the largest |float32 restatement - float64|): wav first, then the stages.  The second depends on
+    the reference alone; the tests allow the device 8 times it, tensor by tensor."""
+    run = (lambda s, m: generator(s, m, cfg)) if lengths is None else (lambda s, m: generator_ragged(s, m, lengths, cfg))
+    w64, s64 = run(sd, mel)
+    w32, s32 = run({k: v.float() for k, v in sd.items()}, mel.float())
+    errs = [(w32.double() - w64).abs().max().item()] + [(a.double() - b).abs().max().item() for a, b in zip(s32, s64)]
+    return (w64, s64), errs

@@ -7,7 +7,9 @@ teacher-forced at B=64, autoregressive RTF (B=64, 1000 steps), Postnet-only MFMA
 batch delivered at the model's rate;
 `dtw` / `align` (on request): the evaluation metrics' C-ABI calls alone between device events - gvx_dtw_distance on 32 rows of
 1000 x 1000 and 800 x 800 frames of 13 cepstra (and 1000 x 1000 of 80 features, the form without LDS tables), gvx_alignment_stats
-on 32 x 1000 x 128 - and the Python entry points around them by the host clock."""
+on 32 x 1000 x 128 - and the Python entry points around them by the host clock;
+`melgan` (on request): the MelGAN generator at 1 x 568 and 32 x 800 frames between device events, with the time per stage, against the
+same float32 network through torch's own ROCm convolutions and against Griffin-Lim (32 iterations) on the same mels."""
 import json
 import os
 import sys
@@ -259,6 +261,72 @@ def main():
         r["gb_per_s"] = round(a.numel() * 4 / 1e9 / (r["median_ms"] * 1e-3), 1)
         res[f"gvx_alignment_stats_b{B}_{T}x{L}"] = r
         res[f"alignment_stats_python_b{B}_{T}x{L}"] = host_runs(lambda: metrics.alignment_stats(a))
+    if "melgan" in which:
+        import statistics
+
+        import torch.nn.functional as F
+
+        from genvox_amd.configs import MelGANConfig
+        from genvox_amd.melgan import MelGANGenerator
+
+        def ev_runs(fn, warm=2, reps=7):
+            for _ in range(warm):
+                fn()
+            out = []
+            for _ in range(reps):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                e1.synchronize()
+                out.append(e0.elapsed_time(e1))
+            return {"median_ms": round(statistics.median(out), 3), "min_ms": round(min(out), 3), "max_ms": round(max(out), 3), "runs": reps}
+
+        gmc = MelGANConfig()
+        voc = MelGANGenerator(gmc, ac).to("cuda:0")
+        with torch.no_grad():
+            for name, p in voc.named_parameters():
+                if name.endswith("bias"):
+                    p.copy_(0.1 * torch.randn_like(p))
+        sd = {k: v.detach() for k, v in voc.state_dict().items()}
+
+        def torch_net(mel):   # the same float32 network through torch's own convolutions
+            x = F.conv1d(F.pad(mel, (3, 3), mode="reflect"), sd["pre.weight"], sd["pre.bias"])
+            for i, r in enumerate(gmc.upsample_ratios):
+                x = F.conv_transpose1d(F.leaky_relu(x, 0.2), sd[f"ups.{i}.weight"], sd[f"ups.{i}.bias"], stride=r, padding=r // 2)
+                for j in range(gmc.n_residual_layers):
+                    d, p = gmc.dilation_base ** j, f"res.{i}.{j}."
+                    h = F.conv1d(F.pad(F.leaky_relu(x, 0.2), (d, d), mode="reflect"), sd[p + "conv.weight"], sd[p + "conv.bias"], dilation=d)
+                    x = F.conv1d(x, sd[p + "shortcut.weight"], sd[p + "shortcut.bias"]) + F.conv1d(F.leaky_relu(h, 0.2), sd[p + "mix.weight"], sd[p + "mix.bias"])
+            return torch.tanh(F.conv1d(F.pad(F.leaky_relu(x, 0.2), (3, 3), mode="reflect"), sd["post.weight"], sd["post.bias"]))[:, 0]
+
+        ap = AudioProcessor(ac, device="cuda:0")
+        gen = torch.Generator(device="cuda").manual_seed(0)
+        for B, T in ((1, 568), (32, 800)):
+            key = f"melgan_{B}x{T}"
+            mel = (0.5 * torch.randn(B, 80, T, device="cuda", generator=gen) - 0.5).contiguous()
+            res[key] = {"as_delivered": ev_runs(lambda: voc.vocode(mel)), "rows_per_call_as_delivered": None}
+            rows = B
+            while rows > 1 and voc.workspace_bytes(rows, T) > voc.WORKSPACE_CAP_BYTES:
+                rows = (rows + 1) // 2
+            res[key]["rows_per_call_as_delivered"] = rows
+            cap, voc.WORKSPACE_CAP_BYTES = voc.WORKSPACE_CAP_BYTES, 1 << 40   # one call for all rows: the stage times are of one call
+            res[key]["one_call"] = ev_runs(lambda: voc.vocode(mel))
+            voc.enable_stage_timing(True)
+            per = []
+            for _ in range(5):
+                wav = voc.vocode(mel)
+                per.append(voc.stage_times_ms())
+            voc.enable_stage_timing(False)
+            res[key]["stage_ms_median"] = [round(statistics.median(col), 3) for col in zip(*per)]   # first conv, stages 0 .. 3, output layer
+            voc.WORKSPACE_CAP_BYTES, voc._workspace = cap, None
+            print(json.dumps({key: res[key]}), flush=True)
+            res[key]["griffin_lim_32it"] = ev_runs(lambda: ap.convert_mel2wav_batch(mel), warm=1, reps=5)
+            print(json.dumps({key: res[key]["griffin_lim_32it"]}), flush=True)
+            with torch.no_grad():
+                res[key]["torch_convolutions"] = ev_runs(lambda: torch_net(mel), warm=2, reps=5)
+                res[key]["max_abs_difference_from_torch"] = float((torch_net(mel) - wav).abs().max())
+            print(json.dumps({key: res[key]["torch_convolutions"]}), flush=True)
     if "cpu" in which:
         # CPU baselines for configs 3 and 4 (the oracle = CPU restatement of the reference, on this box's host cores):
         # bounded samples, reported beside the GPU figures above; bench.py carries the one for config 2.
