@@ -33,6 +33,11 @@ class gvx_melgan_dims(C.Structure):
                 ("n_residual_layers", C.c_int32), ("dilation_base", C.c_int32), ("slope", C.c_float)]
 
 
+class gvx_pitch_params(C.Structure):
+    _fields_ = [("sampling_rate", C.c_int32), ("hop", C.c_int32), ("window", C.c_int32), ("lag_min", C.c_int32), ("lag_max", C.c_int32),
+                ("threshold", C.c_float), ("first_centre", C.c_int32)]
+
+
 class gvx_tensor_ref(C.Structure):
     _fields_ = [("data", C.c_void_p), ("numel", C.c_int64)]
 
@@ -132,7 +137,11 @@ SIGNATURES = {
     "gvx_monotonic_align": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "gvx_duration_scale": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
     "gvx_mel_time_warp": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "gvx_melgan_blob_floats": (_sz, [C.POINTER(gvx_melgan_dims)]),
+    "gvx_pitch_frames": (_i, [_l, _i]),
+    "gvx_pitch_tile_frames": (_i, [C.POINTER(gvx_pitch_params)]),
+    "gvx_pitch_yin": (_i, [_vp, _vp, _i, _l, C.POINTER(gvx_pitch_params), _vp, _vp, _vp, _vp, _vp]),
+    "gvx_f0_compare": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "gvx_melgan_blob_floats":(_sz, [C.POINTER(gvx_melgan_dims)]),
     "gvx_melgan_workspace_bytes": (_sz, [C.POINTER(gvx_melgan_dims), _i, _i]),
     "gvx_melgan_pack_weights_device": (_i, [C.POINTER(gvx_melgan_dims), C.POINTER(gvx_weight_desc), _i, _vp, _vp]),
     "gvx_melgan_create": (_i, [C.POINTER(gvx_melgan_dims), C.POINTER(_vp)]),

@@ -680,16 +680,25 @@ class AudioProcessor:
         _, wav = self.griffin_lim(mag, n_iter=n_iter, want_phase=False, frame_lengths=lens)
         out = self.finalize(wav, frame_lengths=lens)
         samples = self.row_samples(lens.host) if lens is not None else None
-        if out_rate is not None and int(out_rate) != self.config.sampling_rate:
-            up, down = rs.resample_ratio(self.config.sampling_rate, int(out_rate))
-            rs.check_ratio(up, down)
-            counts = samples if samples is not None else [out.shape[1]] * out.shape[0]
-            bounds = torch.tensor([[0, n] for n in counts], dtype=torch.int32, device=self.device)
-            resampled = torch.empty(out.shape[0], rs.resampled_length(out.shape[1], up, down), dtype=torch.float64, device=self.device)
-            self._resample_into(out, bounds, self.config.sampling_rate, int(out_rate), resampled)
-            out = resampled
-            samples = [rs.resampled_length(n, up, down) for n in samples] if samples is not None else None
+        out, samples = self.deliver_at(out, samples, out_rate)
         return out if lens is None else (out, samples)
+
+    def deliver_at(self, wav: torch.Tensor, samples: Optional[List[int]], out_rate: Optional[int]):
+        """The last stage of ``convert_mel2wav_batch`` on its own: waveforms [B, n] at ``config.sampling_rate`` (float64 or float32; row
+        b of ``samples[b]`` samples, None: all n) -> ``(waveforms at out_rate, their sample counts or None)``, resampled on the device
+        in the waveforms' own dtype.  ``out_rate`` None or the model's: both come back as they are.  A caller that needs the
+        model-rate waveform as well (``Synthesizer`` tracks pitch on it) vocodes without ``out_rate`` and calls this: the same
+        launches as the one call, hence the same bits."""
+        if out_rate is None or int(out_rate) == self.config.sampling_rate:
+            return wav, samples
+        up, down = rs.resample_ratio(self.config.sampling_rate, int(out_rate))
+        rs.check_ratio(up, down)
+        counts = samples if samples is not None else [wav.shape[1]] * wav.shape[0]
+        bounds = torch.tensor([[0, n] for n in counts], dtype=torch.int32, device=self.device)
+        resampled = torch.empty(wav.shape[0], rs.resampled_length(wav.shape[1], up, down), dtype=wav.dtype, device=self.device)
+        self._resample_into(wav, bounds, self.config.sampling_rate, int(out_rate), resampled)
+        samples = [rs.resampled_length(n, up, down) for n in samples] if samples is not None else None
+        return resampled, samples
 
     def convert_mel2wav(self, mel: Union[np.ndarray, str, torch.Tensor], n_iter: int = 32) -> Tuple[int, np.ndarray]:
         """Reference signature (core/processors.py:81-96): one mel [n_mels, T] (array or .npy path) -> (fs, float64 signal)."""

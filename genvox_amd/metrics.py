@@ -190,6 +190,96 @@ def time_warp(mel: torch.Tensor, durations: torch.Tensor, target_durations: torc
     return out
 
 
+F0_ROW_INT_NAMES = ("frames", "voiced_both", "voiced_one", "gross")   # GVX_F0_* of include/genvox_amd.h, in order
+
+
+def pitch_params(sampling_rate: int, hop_length: int, fmin: float = 60.0, fmax: float = 500.0, window: int = 1024, threshold: float = 0.15,
+                 first_centre: int = 0) -> "_lib.gvx_pitch_params":
+    """The parameter block of ``pitch_track`` (host arithmetic, no GPU needed): ``lag_min = floor(sampling_rate / fmax)`` and
+    ``lag_max = ceil(sampling_rate / fmin)`` - 44 and 368 at 22050 Hz with the defaults.  Whatever gvx_pitch_yin would refuse raises
+    ValueError here, by name."""
+    for name, v in (("sampling_rate", sampling_rate), ("hop_length", hop_length), ("window", window), ("first_centre", first_centre)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name} must be an integer, not {v!r}")
+    if sampling_rate < 1 or hop_length < 1:
+        raise ValueError(f"sampling_rate = {sampling_rate} and hop_length = {hop_length} must be >= 1")
+    if not (math.isfinite(fmin) and math.isfinite(fmax) and 0 < fmin < fmax):
+        raise ValueError(f"0 < fmin < fmax is required, not fmin = {fmin!r}, fmax = {fmax!r}")
+    lag_min, lag_max = int(math.floor(sampling_rate / fmax)), int(math.ceil(sampling_rate / fmin))
+    if not 1 <= lag_min < lag_max <= 1024:
+        raise ValueError(f"fmin = {fmin} and fmax = {fmax} at {sampling_rate} Hz are the lags {lag_min} .. {lag_max}: outside 1 <= lag_min < lag_max <= 1024")
+    if not 32 <= window <= 2048:
+        raise ValueError(f"window = {window} is outside [32, 2048]")
+    if not 0.0 < threshold <= 1.0:
+        raise ValueError(f"threshold = {threshold!r} is outside (0, 1]")
+    if not -2 ** 31 <= first_centre < 2 ** 31:
+        raise ValueError(f"first_centre = {first_centre} is not a 32-bit integer")
+    return _lib.gvx_pitch_params(int(sampling_rate), int(hop_length), int(window), lag_min, lag_max, float(threshold), int(first_centre))
+
+
+def pitch_frames(n_samples: int, hop_length: int) -> int:
+    """Frames of a row of ``n_samples`` samples: ceil(n_samples / hop_length) (gvx_pitch_frames; host arithmetic)."""
+    return int(_lib.load().gvx_pitch_frames(int(n_samples), int(hop_length)))
+
+
+def pitch_track(wav: torch.Tensor, sample_lengths: Optional[torch.Tensor] = None, *, sampling_rate: int, hop_length: int,
+                fmin: float = 60.0, fmax: float = 500.0, window: int = 1024, threshold: float = 0.15, first_centre: int = 0,
+                want_table: bool = False) -> Dict[str, torch.Tensor]:
+    """YIN F0 contours of waveforms [B, N] (float32, or float64, which is converted), each row at its own ``sample_lengths[b]``
+    samples (None: all N): one decision per ``hop_length`` samples, frame f centred on sample ``first_centre + f * hop_length``
+    (gvx_pitch_yin of include/genvox_amd.h: difference function over ``window`` terms, cumulative-mean normalisation, the first lag
+    between ``sampling_rate / fmax`` and ``sampling_rate / fmin`` under ``threshold`` walked down to its local minimum, parabolic
+    refinement; no smoothing).  ``first_centre`` puts the frames on another grid: ``-AudioProcessor.TRIM`` tracks a Griffin-Lim
+    waveform on the frames of the mel it came from.
+
+    Returns ``f0`` fp32 [B, F] (Hz; 0 = unvoiced and behind a row's frames), ``lag`` int32 [B, F] (-1 there), ``aperiodicity`` fp32
+    [B, F] (the normalised difference at the lag, or its minimum over the search range for an unvoiced frame; 1 behind the row) and
+    ``frames`` int32 [B] (ceil(samples / hop_length) per row); with ``want_table`` also ``cmnd`` fp32 [B, F, lag_max + 1], the table
+    the decisions ran on.  One launch, no workspace."""
+    params = pitch_params(sampling_rate, hop_length, fmin, fmax, window, threshold, first_centre)
+    dev = _need_gpu(wav, "wav")
+    if wav.dim() != 2 or wav.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"wav must be float32 or float64 [B, N], got {wav.dtype} {tuple(wav.shape)}")
+    x = wav.to(dtype=torch.float32).contiguous()
+    B, N = x.shape
+    sl = _lengths(sample_lengths, B, dev)
+    lib = _lib.load()
+    F = lib.gvx_pitch_frames(N, params.hop)
+    out = {"f0": torch.empty(B, F, dtype=torch.float32, device=dev), "lag": torch.empty(B, F, dtype=torch.int32, device=dev),
+           "aperiodicity": torch.empty(B, F, dtype=torch.float32, device=dev)}
+    table = torch.empty(B, F, params.lag_max + 1, dtype=torch.float32, device=dev) if want_table else None
+    _lib.check(lib.gvx_pitch_yin(x.data_ptr(), _ptr(sl), B, N, params, out["f0"].data_ptr(), out["lag"].data_ptr(),
+                                 out["aperiodicity"].data_ptr(), _ptr(table), _stream(dev)))
+    n = sl.clamp(0, N) if sl is not None else torch.full((B,), N, dtype=torch.int32, device=dev)
+    out["frames"] = torch.div(n + (params.hop - 1), params.hop, rounding_mode="floor").to(torch.int32)
+    if want_table:
+        out["cmnd"] = table
+    return out
+
+
+def f0_compare(f0_a: torch.Tensor, f0_b: torch.Tensor, frames_a: Optional[torch.Tensor] = None,
+               frames_b: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """Two F0 contours [B, F] on the same frame grid (Hz, 0 = unvoiced, as ``pitch_track`` gives them), each row over the smaller of
+    its two frame counts (None: all F): gvx_f0_compare of include/genvox_amd.h.
+
+    Returns per row ``frames``, ``voiced_both``, ``voiced_one`` (voiced in exactly one contour), ``gross`` (voiced in both and more
+    than 20 % apart) as int32 [B], and fp32 [B]: ``vde`` = voiced_one / frames, ``gpe`` = gross / voiced_both, ``rmse_cents`` = the
+    root mean square of 1200 log2(a / b) over the frames voiced in both and not gross - NaN where a denominator is 0.  One launch."""
+    dev = _need_gpu(f0_a, "f0_a")
+    a, b = f0_a.to(dtype=torch.float32).contiguous(), f0_b.to(device=dev, dtype=torch.float32).contiguous()
+    if a.dim() != 2 or a.shape != b.shape:
+        raise ValueError(f"contours {tuple(a.shape)} and {tuple(b.shape)} must both be [B, F]")
+    B, F = a.shape
+    na, nb = _lengths(frames_a, B, dev), _lengths(frames_b, B, dev)
+    ints = torch.empty(B, len(F0_ROW_INT_NAMES), dtype=torch.int32, device=dev)
+    out = {k: torch.empty(B, dtype=torch.float32, device=dev) for k in ("vde", "gpe", "rmse_cents")}
+    _lib.check(_lib.load().gvx_f0_compare(a.data_ptr(), b.data_ptr(), _ptr(na), _ptr(nb), B, F, ints.data_ptr(), out["vde"].data_ptr(),
+                                          out["gpe"].data_ptr(), out["rmse_cents"].data_ptr(), _stream(dev)))
+    for i, name in enumerate(F0_ROW_INT_NAMES):
+        out[name] = ints[:, i]
+    return out
+
+
 def dct_rows(n_mels: int, n_cepstra: int) -> np.ndarray:
     """Rows 1 .. n_cepstra of the orthonormal DCT-II of size n_mels, float64 [n_cepstra, n_mels]:
     P[k][m] = sqrt(2 / M) cos(pi (k + 1) (2 m + 1) / (2 M)) - the mel cepstra without the energy term."""

@@ -8,7 +8,6 @@ from typing import Dict, List, Mapping, Optional, Sequence, Tuple, Union
 import numpy as np
 import torch
 
-from . import resample as rs
 from .audio import AudioProcessor
 from .text import TextProcessor
 
@@ -65,6 +64,27 @@ def token_times(start_frames: Sequence[int], hop_length: int, trim: int, n_sampl
     delivered.  A token ends where the next starts; the last ends at ``end_s``, the delivered waveform's own duration."""
     starts = [min(max(int(f) * hop_length - trim, 0), n_samples) / model_rate for f in start_frames]
     return starts, starts[1:] + [end_s]
+
+
+def token_pitch(start_frames: Sequence[int], n_frames: int, f0: Sequence[float]) -> List[Tuple[Optional[float], float]]:
+    """Pitch per token from a contour per frame (no GPU needed): ``start_frames`` are the first frames of the tokens (what the
+    timings are made of), token l owns the frames ``[start_frames[l], start_frames[l + 1])`` and the last one those up to
+    ``n_frames``, each bound clamped to ``[0, min(n_frames, len(f0))]``; ``f0`` is in Hz with 0 for an unvoiced frame.  Returns one
+    ``(mean_hz, voiced_fraction)`` per token: the mean of its voiced frames (None when it has none) and their share of its frames
+    (0.0 for a token without frames)."""
+    f0 = np.asarray(f0, dtype=np.float64)
+    if f0.ndim != 1:
+        raise ValueError(f"f0 must be one contour, got shape {f0.shape}")
+    if n_frames < 0:
+        raise ValueError(f"n_frames must be >= 0, not {n_frames}")
+    n = min(int(n_frames), len(f0))
+    bounds = [min(max(int(s), 0), n) for s in start_frames] + [n]
+    out: List[Tuple[Optional[float], float]] = []
+    for lo, hi in zip(bounds[:-1], bounds[1:]):
+        seg = f0[lo:hi]
+        voiced = seg[seg > 0]
+        out.append((float(voiced.mean()) if len(voiced) else None, len(voiced) / len(seg) if len(seg) else 0.0))
+    return out
 
 
 RATE_MIN, RATE_MAX = 0.125, 8.0   # GVX_RATE_MIN / GVX_RATE_MAX of include/genvox_amd.h: the range of speed and of speed * rate
@@ -185,25 +205,45 @@ class Synthesizer:
         rows' own lengths.  Without a vocoder model this is ``AudioProcessor.convert_mel2wav_batch`` (Griffin-Lim), call for call.
         With one, the rows go through it in one ragged call - float32 [B, T * hop], row b of ``frames[b] * hop`` samples - and are
         resampled like Griffin-Lim's, every row at its own sample count."""
+        wav, counts, _ = self._vocode_and_track(mel, frames, sampling_rate, False)
+        return wav, counts
+
+    def _vocode_and_track(self, mel: torch.Tensor, frames, sampling_rate: Optional[int], pitch: bool):
+        """``_vocode`` with the pitch contour of what it made: ``(waveforms, sample counts or None, f0 or None)``.  The waveform is
+        vocoded at the model's rate, tracked there when ``pitch`` asks (``metrics.pitch_track`` with the model's hop, every row at
+        its own sample count; frame 0 centred on sample ``-TRIM`` of a Griffin-Lim waveform, which lost ``TRIM`` samples at its
+        head, and on sample 0 of a neural vocoder's), and only then resampled by ``AudioProcessor.deliver_at`` - the launches of
+        ``convert_mel2wav_batch(..., out_rate=...)``, so tracking changes no bit of what is delivered.  f0 is float32 [B, T] on the
+        device, one value per frame of ``mel``: Hz, 0 for an unvoiced frame and behind a row's own frames."""
         ap = self.audio_processor
         if self.vocoder is None:
             if frames is None:
-                return ap.convert_mel2wav_batch(mel, out_rate=sampling_rate), None
-            return ap.convert_mel2wav_batch(mel, out_rate=sampling_rate, mel_lengths=frames)
-        hop, rate = self.vocoder.hop, int(ap.config.sampling_rate)
-        host = None if frames is None else [int(t) for t in (frames.tolist() if isinstance(frames, torch.Tensor) else frames)]
-        wav = self.vocoder.vocode(mel.contiguous(), host)
-        counts = None if host is None else [t * hop for t in host]
-        if sampling_rate is not None and int(sampling_rate) != rate:
-            up, down = rs.resample_ratio(rate, int(sampling_rate))
-            rs.check_ratio(up, down)
-            rows = counts if counts is not None else [wav.shape[1]] * wav.shape[0]
-            bounds = torch.tensor([[0, n] for n in rows], dtype=torch.int32, device=self.device)
-            out = torch.empty(wav.shape[0], rs.resampled_length(wav.shape[1], up, down), dtype=torch.float32, device=self.device)
-            ap._resample_into(wav, bounds, rate, int(sampling_rate), out)
-            wav = out
-            counts = None if counts is None else [rs.resampled_length(n, up, down) for n in counts]
-        return wav, counts
+                wav, counts = ap.convert_mel2wav_batch(mel), None
+            else:
+                wav, counts = ap.convert_mel2wav_batch(mel, mel_lengths=frames)
+            first_centre = -ap.TRIM
+        else:
+            host = None if frames is None else [int(t) for t in (frames.tolist() if isinstance(frames, torch.Tensor) else frames)]
+            wav = self.vocoder.vocode(mel.contiguous(), host)
+            counts = None if host is None else [t * self.vocoder.hop for t in host]
+            first_centre = 0
+        f0 = None
+        if pitch:
+            from . import metrics
+
+            lengths = None if counts is None else torch.tensor(counts, dtype=torch.int32, device=self.device)
+            tracked = metrics.pitch_track(wav, lengths, sampling_rate=int(ap.config.sampling_rate), hop_length=int(ap.config.hop_length),
+                                          first_centre=first_centre)["f0"]
+            T = mel.shape[2]
+            f0 = tracked[:, :T] if tracked.shape[1] >= T else torch.nn.functional.pad(tracked, (0, T - tracked.shape[1]))
+        wav, counts = ap.deliver_at(wav, counts, sampling_rate)
+        return wav, counts, f0
+
+    @staticmethod
+    def _pitch_keys(f0: np.ndarray) -> Dict:
+        """The two pitch keys of one sentence from its contour on the host."""
+        f0 = np.ascontiguousarray(f0, dtype=np.float32)
+        return {"f0": f0, "voiced_fraction": float((f0 > 0).mean()) if len(f0) else 0.0}
 
     @staticmethod
     def _sentence_rates(token_strs: Sequence[str], word_speed, token_speed) -> List[float]:
@@ -258,7 +298,7 @@ class Synthesizer:
 
     def tts(self, text: str, sampling_rate: Optional[int] = None, diagnostics: bool = False,
             attention_window: Optional[Tuple[int, int]] = None, timings: bool = False, speed: float = 1.0,
-            word_speed=None, token_speed=None) -> Dict[str, np.ndarray]:
+            word_speed=None, token_speed=None, pitch: bool = False) -> Dict[str, np.ndarray]:
         """``sampling_rate`` (Hz; default: the model's): the waveform is resampled on the device before it is copied to the host,
         and ``"sampling_rate"`` of the result is the rate delivered.  ``diagnostics``: the result gains ``"alignment_stats"``
         (focus, monotonic_fraction, max_jump, coverage, first_pos, last_pos of the sentence's alignment, as Python numbers) and
@@ -278,7 +318,12 @@ class Synthesizer:
         ``metrics.time_warp``) and the waveform is vocoded from the warped mel: the result gains ``"mel_outputs_warped"``
         [n_mels, T'] and ``"speed"``, every other mel, gate and alignment key is the decode as it was, and ``timings`` are read off
         the plan's own frame counts - exact for the delivered waveform.  A decode with fewer frames than tokens is warped as a whole
-        at ``speed``; a rate outside [0.125, 8] after multiplication, or a result above 32768 frames, raises ValueError."""
+        at ``speed``; a rate outside [0.125, 8] after multiplication, or a result above 32768 frames, raises ValueError.
+        ``pitch``: the result gains ``"f0"`` - float32 [frames], Hz, 0 for an unvoiced frame, one value per frame of the mel that was
+        vocoded (the warped one under rate control), tracked on the device on the model-rate waveform before any resampling
+        (``metrics.pitch_track``, YIN) - and ``"voiced_fraction"``; with ``timings`` and an ``"ok"`` status also ``"token_pitch"``: one
+        ``(token, mean_hz or None, voiced_fraction)`` per token over the token's frames (``token_pitch``).  Without ``pitch`` every
+        key and every bit is what it is today."""
         token_strs = self.text_processor.tokenize(text)
         paced = speed != 1.0 or word_speed is not None or token_speed is not None
         if paced:
@@ -299,7 +344,7 @@ class Synthesizer:
             aligned = ([plan[0][0]], [plan[0][1]]) if timings else None
         else:
             aligned = self._align(outputs, None, None) if timings else None
-        wav, _ = self._vocode(mel, None, sampling_rate)  # stays on the device until the end
+        wav, _, f0 = self._vocode_and_track(mel, None, sampling_rate, pitch)  # stays on the device until the end
         result = {key: val.squeeze(0).cpu().numpy() for key, val in outputs.items()}
         result["waveform"] = wav[0].cpu().numpy()
         result["sampling_rate"] = self._out_rate(sampling_rate)
@@ -311,11 +356,17 @@ class Synthesizer:
             result["speed"] = speed
         if aligned is not None:
             result.update(self._timings(token_strs, aligned[0][0], aligned[1][0], mel.shape[2], wav.shape[1], result["sampling_rate"]))
+        if f0 is not None:
+            result.update(self._pitch_keys(f0[0].cpu().numpy()))
+            if aligned is not None and result["timings_status"] == "ok":
+                per_token = token_pitch(aligned[0][0][:len(token_strs)], mel.shape[2], result["f0"])
+                result["token_pitch"] = [(tok, hz, share) for tok, (hz, share) in zip(token_strs, per_token)]
         return result
 
     def tts_batch(self, texts: Sequence[str], batch_size: int = 32, sampling_rate: Optional[int] = None,
                   diagnostics: bool = False, attention_window: Optional[Tuple[int, int]] = None,
-                  timings: bool = False, speed: float = 1.0, word_speed=None, token_speed=None) -> List[Dict[str, np.ndarray]]:
+                  timings: bool = False, speed: float = 1.0, word_speed=None, token_speed=None,
+                  pitch: bool = False) -> List[Dict[str, np.ndarray]]:
         """Many sentences per call: one dict per sentence, in input order, with the keys, dtypes and shapes ``tts(text)`` gives
         for that sentence (every row trimmed to its own frames, tokens and samples).  Sentences are decoded as padded batches of
         at most ``batch_size`` rows of similar token length (``plan_tts_batches``) and vocoded at their own lengths in one ragged
@@ -325,7 +376,8 @@ class Synthesizer:
         ``tts``: every sentence is decoded with it and carries its own ``"attention_centres"``.  ``timings`` as in ``tts``: every
         sentence aligned at its own frames and tokens, timed against its own waveform.  ``speed`` as in ``tts``, for every
         sentence; ``word_speed`` and ``token_speed`` are lists with one entry per sentence, each as in ``tts`` (None: no rates
-        for that sentence): every sentence is warped at its own frames, tokens and rates and vocoded at its own new length."""
+        for that sentence): every sentence is warped at its own frames, tokens and rates and vocoded at its own new length.
+        ``pitch`` as in ``tts``: every sentence's waveform is tracked at its own sample count, in one call per batch."""
         token_strs = [self.text_processor.tokenize(t) for t in texts]
         token_lists = [self.text_processor.tokens_to_indices(toks) for toks in token_strs]
         paced = speed != 1.0 or word_speed is not None or token_speed is not None
@@ -356,11 +408,14 @@ class Synthesizer:
                 aligned = self._align(outputs, outputs.get("mel_lengths"), inputs.get("token_lengths")) if timings else None
             if len(idx) > 1:
                 frames = outputs.pop("mel_lengths")
-                wav, samples = self._vocode(mel if warped is None else warped, frames if warped is None else new_frames, sampling_rate)
+                wav, samples, f0 = self._vocode_and_track(mel if warped is None else warped, frames if warped is None else new_frames,
+                                                          sampling_rate, pitch)
                 frames = frames.tolist()
             else:
-                wav, _ = self._vocode(mel if warped is None else warped, None, sampling_rate)
+                wav, _, f0 = self._vocode_and_track(mel if warped is None else warped, None, sampling_rate, pitch)
                 frames, samples = [mel.shape[2]], [wav.shape[1]]
+            if f0 is not None:
+                f0 = f0.cpu().numpy()
             host = {key: val.cpu().numpy() for key, val in outputs.items()}
             if warped is not None:
                 warped = warped.cpu().numpy()
@@ -387,4 +442,9 @@ class Synthesizer:
                     results[i]["speed"] = speed
                 if aligned is not None:
                     results[i].update(self._timings(token_strs[i], aligned[0][r], aligned[1][r], t, samples[r], self._out_rate(sampling_rate)))
+                if f0 is not None:
+                    results[i].update(self._pitch_keys(f0[r, :t]))
+                    if aligned is not None and results[i]["timings_status"] == "ok":
+                        per_token = token_pitch(aligned[0][r][:len(token_strs[i])], t, results[i]["f0"])
+                        results[i]["token_pitch"] = [(tok, hz, share) for tok, (hz, share) in zip(token_strs[i], per_token)]
         return results

@@ -778,6 +778,81 @@ int gvx_mel_time_warp(const float* mel, const int32_t* durations, const int32_t*
                       int M, int T, int L, int T_out, float* mel_out, int32_t* src_frame_out, float* src_frac_out,
                       int32_t* row_status_out, void* stream);
 
+/* ---- Pitch: YIN F0 contours of waveforms on the device (de Cheveigne and Kawahara 2002, steps 1 - 5, no smoothing: the contour is
+ * the raw decision of every frame), and the comparison of two contours - the F0 RMSE, gross pitch error and voicing decision error
+ * that accompany the mel-cepstral distance.  Both calls are asynchronous on `stream`, write caller-allocated outputs only, need no
+ * workspace and give the same bits every run (fixed summation orders, no atomics); no workgroup waits for another and every loop is
+ * bounded by the parameters.
+ *
+ * gvx_pitch_yin - the tracker.  wav is fp32 [B][N], row b of n_b = sample_lengths[b] samples (clamped to [0, N]; NULL: N); nothing at
+ * or behind n_b is read, whatever it holds.  Row b has F_b = gvx_pitch_frames(n_b, hop) = ceil(n_b / hop) frames, and
+ * F = gvx_pitch_frames(N, hop) is the stride of the outputs.  With W = window, x = the row with zeros outside [0, n_b), and for
+ * frame f
+ *
+ *     s        = first_centre + f * hop - (W + lag_max) / 2         (integer division; first_centre is the sample index of frame
+ *                                                                    0's centre and may be negative: -TRIM for a Griffin-Lim
+ *                                                                    waveform that lost TRIM samples at its head)
+ *     d(tau)   = sum over j = 0 .. W-1 of (x[s+j] - x[s+j+tau])^2    tau = 0 .. lag_max; fp32, j ascending, each term one
+ *                                                                    subtraction and one fused multiply-add
+ *     c(0)     = 1
+ *     c(tau)   = d(tau) * tau / sum over k = 1 .. tau of d(k)        tau >= 1; 1 where that sum is 0 (digital silence).  The sum's
+ *                                                                    order: lag_max lags in 64 runs of ceil(lag_max / 64), each run
+ *                                                                    ascending on top of the runs before it
+ *     lag      : scan tau from lag_min to lag_max - 1; at the first tau with c(tau) < threshold walk on while c(tau+1) < c(tau) and
+ *                tau + 1 <= lag_max - 1, and take that tau.  No such tau: the frame is unvoiced.
+ *     den      = c(lag-1) - 2 c(lag) + c(lag+1)
+ *     shift    = den > 0 ? clamp( (c(lag-1) - c(lag+1)) / (2 den), -1, 1 ) : 0
+ *     f0       = sampling_rate / (lag + shift)
+ *
+ * d is computed in this form and no other: energy minus autocorrelation, r(0) + r_tau(0) - 2 acf(tau), and every FFT route cancel
+ * catastrophically in fp32 on nearly periodic signals, which is where d is small and the decision is made; a sum of squared
+ * differences has no cancellation, so |c32 - c| <= (2 W + lag_max + 8) 2^-24 c in any summation order.  Outputs:
+ *     f0_out            fp32  [B][F]   Hz; 0 for an unvoiced frame and for f >= F_b
+ *     lag_out           int32 [B][F]   the lag; -1 for an unvoiced frame and for f >= F_b
+ *     aperiodicity_out  fp32  [B][F]   c(lag); for an unvoiced frame the minimum of c over [lag_min, lag_max); 1 for f >= F_b
+ *     cmnd_out          fp32  [B][F][lag_max + 1] or NULL: receives c(0 .. lag_max) of every frame f < F_b, the table the decision ran
+ *                                      on, and is not touched elsewhere; every other output has the same bits with and without it
+ * One launch.  A workgroup takes one row and gvx_pitch_tile_frames(params) consecutive frames (at most 16; fewer when W + lag_max +
+ * (frames - 1) hop samples and four tables of lag_max + 1 floats do not fit 64 KiB of LDS), stages their samples in LDS once, and
+ * gives every frame to one wave: lanes across lags, three consecutive lags and a sliding window of samples per lane.  Limits, all
+ * checked before anything is launched: a NULL wav, params, f0_out, lag_out or aperiodicity_out, B, N, sampling_rate, hop or window
+ * below 1, lag_min below 1 or not below lag_max, a threshold outside (0, 1] (NaN is): GVX_ERR_INVALID_ARG; window outside
+ * [GVX_PITCH_MIN_WINDOW, GVX_PITCH_MAX_WINDOW] = [32, 2048], lag_max above GVX_PITCH_MAX_LAG = 1024, B above GVX_PITCH_MAX_ROWS =
+ * 65535, F above GVX_PITCH_MAX_FRAMES = 32768: GVX_ERR_UNSUPPORTED (gvx_pitch_tile_frames then returns -1).
+ *
+ * gvx_f0_compare - two contours on the same frame grid.  f0_a and f0_b are fp32 [B][F] (0 or below: unvoiced, as is NaN); row b is
+ * compared over n = min(frames_a[b], frames_b[b]) frames (each clamped to [0, F]; NULL: F).  A frame voiced in both with ratio
+ * r = (double)a / (double)b is a gross error if |r - 1| > 0.2 (in double).  Outputs per row:
+ *     counts_out      int32 [B][GVX_F0_ROW_INTS]   [GVX_F0_FRAMES] n, [GVX_F0_VOICED_BOTH], [GVX_F0_VOICED_ONE] voiced in exactly one,
+ *                                                  [GVX_F0_GROSS]
+ *     vde_out         fp32  [B]   (float)voiced_one / (float)n                       NaN for n == 0
+ *     gpe_out         fp32  [B]   (float)gross / (float)voiced_both                  NaN for voiced_both == 0
+ *     rmse_cents_out  fp32  [B]   sqrt of the mean of (1200 log2 r)^2 over the frames voiced in both and not gross, formed in double
+ *                                 and rounded once; NaN when there is no such frame
+ * One launch, one workgroup per row: 256 partial results, number i over the frames i, i + 256, ... in ascending order, added
+ * pairwise at strides 128, 64, ..., 1.  Contours of different lengths along a warping path are out of scope (gvx_dtw_distance
+ * returns no path): the use is copy-synthesis, recording -> mel -> vocoder -> waveform against the recording, both tracked on the
+ * mel's frame grid.  A NULL f0_a, f0_b or output, B or F below 1: GVX_ERR_INVALID_ARG; F above
+ * GVX_PITCH_MAX_FRAMES: GVX_ERR_UNSUPPORTED. */
+typedef struct gvx_pitch_params {
+    int32_t sampling_rate;   /* Hz                                                           */
+    int32_t hop;             /* samples between frame centres                                */
+    int32_t window;          /* W: terms of the difference function                          */
+    int32_t lag_min;         /* shortest period searched, samples: floor(rate / fmax)        */
+    int32_t lag_max;         /* longest period, samples: ceil(rate / fmin)                   */
+    float threshold;         /* of the cumulative-mean-normalised difference; YIN uses 0.1 - 0.15 */
+    int32_t first_centre;    /* sample index of frame 0's centre; may be negative            */
+} gvx_pitch_params;
+enum { GVX_PITCH_MIN_WINDOW = 32, GVX_PITCH_MAX_WINDOW = 2048, GVX_PITCH_MAX_LAG = 1024, GVX_PITCH_MAX_ROWS = 65535,
+       GVX_PITCH_MAX_FRAMES = 32768 };
+enum { GVX_F0_FRAMES = 0, GVX_F0_VOICED_BOTH = 1, GVX_F0_VOICED_ONE = 2, GVX_F0_GROSS = 3, GVX_F0_ROW_INTS = 4 };
+int gvx_pitch_frames(long n, int hop);   /* host arithmetic: ceil(n / hop); 0 for n <= 0 or hop < 1 */
+int gvx_pitch_tile_frames(const gvx_pitch_params* params);
+int gvx_pitch_yin(const float* wav, const int32_t* sample_lengths, int B, long N, const gvx_pitch_params* params, float* f0_out,
+                  int32_t* lag_out, float* aperiodicity_out, float* cmnd_out, void* stream);
+int gvx_f0_compare(const float* f0_a, const float* f0_b, const int32_t* frames_a, const int32_t* frames_b, int B, int F,
+                   int32_t* counts_out, float* vde_out, float* gpe_out, float* rmse_cents_out, void* stream);
+
 /* ---- Neural vocoder: MelGAN generator inference, mel -> waveform.  The reference promises a vocoder model and ships only its config
  * (configs/models.py:89-121, MelGANConfig); the network below is this project's statement of the MelGAN generator.
  *
