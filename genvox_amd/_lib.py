@@ -38,6 +38,11 @@ class gvx_pitch_params(C.Structure):
                 ("threshold", C.c_float), ("first_centre", C.c_int32)]
 
 
+class gvx_psola_params(C.Structure):
+    _fields_ = [("hop", C.c_int32), ("first_centre", C.c_int32), ("lag_min", C.c_int32), ("lag_max", C.c_int32),
+                ("unvoiced_period", C.c_int32)]
+
+
 class gvx_tensor_ref(C.Structure):
     _fields_ = [("data", C.c_void_p), ("numel", C.c_int64)]
 
@@ -141,6 +146,10 @@ SIGNATURES = {
     "gvx_pitch_tile_frames": (_i, [C.POINTER(gvx_pitch_params)]),
     "gvx_pitch_yin": (_i, [_vp, _vp, _i, _l, C.POINTER(gvx_pitch_params), _vp, _vp, _vp, _vp, _vp]),
     "gvx_f0_compare": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "gvx_psola_max_marks": (_l, [_l, _i]),
+    "gvx_psola_max_grains": (_l, [_l, _i]),
+    "gvx_psola_plan": (_i, [_vp, _vp, _vp, _vp, _i, _l, C.POINTER(gvx_psola_params), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gvx_psola_synth": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _l, C.POINTER(gvx_psola_params), _vp, _vp]),
     "gvx_melgan_blob_floats":(_sz, [C.POINTER(gvx_melgan_dims)]),
     "gvx_melgan_workspace_bytes": (_sz, [C.POINTER(gvx_melgan_dims), _i, _i]),
     "gvx_melgan_pack_weights_device": (_i, [C.POINTER(gvx_melgan_dims), C.POINTER(gvx_weight_desc), _i, _vp, _vp]),

@@ -2,7 +2,9 @@
 free-running mel and its target, the monotonic alignment search that turns an alignment into frames per token, and the speaking
 rate control built on those frame counts - the plan and the token-wise time warp of a mel (C ABI: gvx_alignment_stats,
 gvx_mel_project, gvx_dtw_distance, gvx_monotonic_align, gvx_duration_scale, gvx_mel_time_warp; definitions in include/genvox_amd.h,
-restatements in tests/metrics_ref64.py, tests/mas_ref.py and tests/warp_ref.py).
+restatements in tests/metrics_ref64.py, tests/mas_ref.py and tests/warp_ref.py), the pitch tracker and the comparison of two contours
+(gvx_pitch_yin, gvx_f0_compare; tests/pitch_ref64.py) and the pitch control built on the tracker's contour - the plan and the
+overlap-add of a TD-PSOLA pitch shift (gvx_psola_plan, gvx_psola_synth; tests/psola_ref.py).
 
 Every function takes and returns device tensors and enqueues on the current stream; none of them synchronises with the host.
 """
@@ -278,6 +280,86 @@ def f0_compare(f0_a: torch.Tensor, f0_b: torch.Tensor, frames_a: Optional[torch.
     for i, name in enumerate(F0_ROW_INT_NAMES):
         out[name] = ints[:, i]
     return out
+
+
+PSOLA_STATUS_NAMES = ("ok", "empty", "bad_ratio")   # GVX_PSOLA_* of include/genvox_amd.h, in order
+PSOLA_RATIO_MIN, PSOLA_RATIO_MAX = 0.5, 2.0         # GVX_PSOLA_RATIO_MIN / GVX_PSOLA_RATIO_MAX
+
+
+def psola_params(sampling_rate: int, hop_length: int, first_centre: int = 0, unvoiced_period: Optional[int] = None, fmin: float = 60.0,
+                 fmax: float = 500.0) -> "_lib.gvx_psola_params":
+    """The parameter block of ``psola_plan`` and ``pitch_shift`` (host arithmetic, no GPU needed): the frame grid and the lag range
+    of ``pitch_params`` with the same arguments, and ``unvoiced_period`` - the spacing of marks where there is no pitch; None:
+    ``sampling_rate // 100``, 10 ms.  Whatever the calls would refuse raises ValueError here."""
+    p = pitch_params(sampling_rate, hop_length, fmin, fmax, first_centre=first_centre)
+    U = sampling_rate // 100 if unvoiced_period is None else unvoiced_period
+    if isinstance(U, bool) or not isinstance(U, (int, np.integer)) or not 1 <= U <= 1024:
+        raise ValueError(f"unvoiced_period = {U!r} is not an integer in [1, 1024]")
+    return _lib.gvx_psola_params(p.hop, p.first_centre, p.lag_min, p.lag_max, int(U))
+
+
+def _psola_inputs(wav, sample_lengths, what: str):
+    dev = _need_gpu(wav, what)
+    if wav.dim() != 2 or wav.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"{what} must be float32 or float64 [B, N], got {wav.dtype} {tuple(wav.shape)}")
+    x = wav.to(dtype=torch.float32).contiguous()
+    return dev, x, _lengths(sample_lengths, x.shape[0], dev)
+
+
+def psola_plan(wav: torch.Tensor, sample_lengths: Optional[torch.Tensor], lag: torch.Tensor, ratio: torch.Tensor, *, sampling_rate: int,
+               hop_length: int, first_centre: int = 0, unvoiced_period: Optional[int] = None, fmin: float = 60.0,
+               fmax: float = 500.0) -> Dict[str, torch.Tensor]:
+    """The plan of a pitch shift of waveforms [B, N], each row at its own ``sample_lengths[b]`` samples (None: all N): the pitch
+    marks of the input from its ``lag`` contour (int32 [B, F], what ``pitch_track`` returns for the same ``sampling_rate``,
+    ``hop_length``, ``first_centre``, ``fmin`` and ``fmax``) and the places of the output's grains for ``ratio`` fp32 [B, F], the
+    factor on the pitch per frame (gvx_psola_plan of include/genvox_amd.h; unvoiced frames are marked every ``unvoiced_period``
+    samples and never repitched).
+
+    Returns ``marks`` int32 [B, K], ``periods`` int32 [B, K] (negative: an unvoiced mark), ``syn_pos`` and ``syn_src`` int32 [B, J]
+    (where grain j goes and which mark it copies), ``n_marks`` and ``n_grains`` int32 [B] - nothing behind them is written - and
+    ``status`` int32 [B] (index into ``PSOLA_STATUS_NAMES``: "empty" for a row without samples, "bad_ratio" for a ratio inside the
+    row's frames that is NaN or outside [0.5, 2]: such a row has marks and no grains).  One launch, no workspace."""
+    params = psola_params(sampling_rate, hop_length, first_centre, unvoiced_period, fmin, fmax)
+    dev, x, sl = _psola_inputs(wav, sample_lengths, "wav")
+    B, N = x.shape
+    lib = _lib.load()
+    F = lib.gvx_pitch_frames(N, params.hop)
+    lg = lag.to(device=dev, dtype=torch.int32).contiguous()
+    rt = ratio.to(device=dev, dtype=torch.float32).contiguous()
+    if lg.shape != (B, F) or rt.shape != (B, F):
+        raise ValueError(f"lag {tuple(lg.shape)} and ratio {tuple(rt.shape)} must both be [{B}, {F}]: one value per frame of {hop_length} samples")
+    p_min = min(params.lag_min, params.unvoiced_period)
+    K, J = max(1, lib.gvx_psola_max_marks(N, p_min)), max(1, lib.gvx_psola_max_grains(N, p_min))
+    out = {"marks": torch.empty(B, K, dtype=torch.int32, device=dev), "periods": torch.empty(B, K, dtype=torch.int32, device=dev),
+           "syn_pos": torch.empty(B, J, dtype=torch.int32, device=dev), "syn_src": torch.empty(B, J, dtype=torch.int32, device=dev),
+           "status": torch.empty(B, dtype=torch.int32, device=dev)}
+    counts = torch.empty(B, 2, dtype=torch.int32, device=dev)
+    _lib.check(lib.gvx_psola_plan(x.data_ptr(), _ptr(sl), lg.data_ptr(), rt.data_ptr(), B, N, params, out["marks"].data_ptr(),
+                                  out["periods"].data_ptr(), out["syn_pos"].data_ptr(), out["syn_src"].data_ptr(), counts.data_ptr(),
+                                  out["status"].data_ptr(), _stream(dev)))
+    out["counts"], out["n_marks"], out["n_grains"] = counts, counts[:, 0], counts[:, 1]
+    return out
+
+
+def pitch_shift(wav: torch.Tensor, sample_lengths: Optional[torch.Tensor], lag: torch.Tensor, ratio: torch.Tensor, *, sampling_rate: int,
+                hop_length: int, first_centre: int = 0, unvoiced_period: Optional[int] = None, fmin: float = 60.0,
+                fmax: float = 500.0) -> Dict[str, torch.Tensor]:
+    """Waveforms [B, N] with their pitch multiplied by ``ratio`` fp32 [B, F], frame by frame, and their durations unchanged:
+    ``psola_plan`` with the same arguments and the overlap-add of gvx_psola_synth (grains of two periods under a polynomial
+    window, copied from the input's pitch marks to the output's; what lies before the first and behind the last mark is kept).
+
+    Returns ``wav`` fp32 [B, N] (zeros behind a row's samples; a "bad_ratio" row is the input), ``status``, ``n_marks`` and
+    ``n_grains`` int32 [B] as ``psola_plan`` gives them.  Two launches, no workspace, no synchronisation with the host."""
+    plan = psola_plan(wav, sample_lengths, lag, ratio, sampling_rate=sampling_rate, hop_length=hop_length, first_centre=first_centre,
+                      unvoiced_period=unvoiced_period, fmin=fmin, fmax=fmax)
+    params = psola_params(sampling_rate, hop_length, first_centre, unvoiced_period, fmin, fmax)
+    dev, x, sl = _psola_inputs(wav, sample_lengths, "wav")
+    B, N = x.shape
+    y = torch.empty_like(x)
+    _lib.check(_lib.load().gvx_psola_synth(x.data_ptr(), _ptr(sl), plan["marks"].data_ptr(), plan["periods"].data_ptr(), plan["syn_pos"].data_ptr(),
+                                           plan["syn_src"].data_ptr(), plan["counts"].data_ptr(), plan["status"].data_ptr(), B, N, params,
+                                           y.data_ptr(), _stream(dev)))
+    return {"wav": y, "status": plan["status"], "n_marks": plan["n_marks"], "n_grains": plan["n_grains"]}
 
 
 def dct_rows(n_mels: int, n_cepstra: int) -> np.ndarray:

@@ -127,6 +127,67 @@ def token_rates(token_strs: Sequence[str], word_speed: Union[Sequence[float], Ma
     return [1.0 if w < 0 else by_word[w] for w in word_of]
 
 
+PITCH_MAX_SEMITONES = 12.0   # a shift of an octave either way: the ratios 0.5 and 2 of GVX_PSOLA_RATIO_MIN / GVX_PSOLA_RATIO_MAX
+
+
+def _check_semitones(v, what: str) -> float:
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
+        raise ValueError(f"{what} must be a finite number of semitones, not {v!r}")
+    return float(v)
+
+
+def semitones_to_ratio(semitones: float) -> float:
+    """The factor on a frequency that ``semitones`` equal-tempered semitones are: 2 ** (semitones / 12) (no GPU needed)."""
+    return 2.0 ** (_check_semitones(semitones, "a pitch shift") / 12.0)
+
+
+def token_semitones(token_strs: Sequence[str], word_pitch: Union[Sequence[float], Mapping[int, float], None]) -> List[float]:
+    """Semitones per word -> semitones per token (no GPU needed): ``token_rates`` for pitch.  Words are ``group_words``' segmentation
+    of ``token_strs``, counted from 0; ``word_pitch`` is a sequence with one shift per word or a ``{word_index: semitones}`` dict
+    (None: no word is named); every token of a word gets the word's shift, spaces and unnamed words get 0.0.  A wrong count, an
+    index that is not the number of a word, or a shift that is not a finite number raises ValueError."""
+    word_of: List[int] = []   # per token: its word's number, -1 for a space
+    n_words, inside = 0, False
+    for tok in token_strs:
+        if tok.isspace():
+            word_of.append(-1)
+            inside = False
+        else:
+            if not inside:
+                n_words, inside = n_words + 1, True
+            word_of.append(n_words - 1)
+    by_word = [0.0] * n_words
+    if word_pitch is None:
+        pass
+    elif isinstance(word_pitch, Mapping):
+        for w, semis in word_pitch.items():
+            if isinstance(w, bool) or not isinstance(w, (int, np.integer)) or not 0 <= w < n_words:
+                raise ValueError(f"word index {w!r} is outside the sentence's {n_words} words")
+            by_word[int(w)] = _check_semitones(semis, f"the pitch of word {w}")
+    else:
+        shifts = list(word_pitch)
+        if len(shifts) != n_words:
+            raise ValueError(f"{len(shifts)} word pitches for a sentence of {n_words} words")
+        by_word = [_check_semitones(semis, f"the pitch of word {w}") for w, semis in enumerate(shifts)]
+    return [0.0 if w < 0 else by_word[w] for w in word_of]
+
+
+def frame_ratios(start_frames: Sequence[int], n_frames: int, per_token_semitones: Sequence[float], base_semitones: float = 0.0) -> np.ndarray:
+    """Pitch ratios per frame from semitones per token (no GPU needed): float32 [n_frames].  Token l owns the frames
+    ``[start_frames[l], start_frames[l + 1])`` and the last one those up to ``n_frames``, each bound clamped to ``[0, n_frames]``
+    (the frames of ``token_pitch``); its frames get ``semitones_to_ratio(base_semitones + per_token_semitones[l])``, frames of no
+    token ``semitones_to_ratio(base_semitones)``."""
+    if n_frames < 0:
+        raise ValueError(f"n_frames must be >= 0, not {n_frames}")
+    if len(start_frames) != len(per_token_semitones):
+        raise ValueError(f"{len(start_frames)} start frames for {len(per_token_semitones)} tokens")
+    out = np.full(int(n_frames), semitones_to_ratio(base_semitones), dtype=np.float32)
+    bounds = [min(max(int(s), 0), int(n_frames)) for s in start_frames] + [int(n_frames)]
+    for l, (lo, hi) in enumerate(zip(bounds[:-1], bounds[1:])):
+        out[lo:hi] = semitones_to_ratio(base_semitones + per_token_semitones[l])
+    return out
+
+
 class Synthesizer:
     def __init__(self, tts_model_class, tts_config_path: str, tts_checkpoint_path: str, use_cuda: bool = True, vocoder_model_class=None,
                  vocoder_config_path: Optional[str] = None, vocoder_checkpoint_path: Optional[str] = None) -> None:
@@ -205,16 +266,24 @@ class Synthesizer:
         rows' own lengths.  Without a vocoder model this is ``AudioProcessor.convert_mel2wav_batch`` (Griffin-Lim), call for call.
         With one, the rows go through it in one ragged call - float32 [B, T * hop], row b of ``frames[b] * hop`` samples - and are
         resampled like Griffin-Lim's, every row at its own sample count."""
-        wav, counts, _ = self._vocode_and_track(mel, frames, sampling_rate, False)
+        wav, counts, _, _ = self._vocode_and_track(mel, frames, sampling_rate, False)
         return wav, counts
 
-    def _vocode_and_track(self, mel: torch.Tensor, frames, sampling_rate: Optional[int], pitch: bool):
+    def _vocode_and_track(self, mel: torch.Tensor, frames, sampling_rate: Optional[int], pitch: bool, control: Optional[Dict] = None):
         """``_vocode`` with the pitch contour of what it made: ``(waveforms, sample counts or None, f0 or None)``.  The waveform is
         vocoded at the model's rate, tracked there when ``pitch`` asks (``metrics.pitch_track`` with the model's hop, every row at
         its own sample count; frame 0 centred on sample ``-TRIM`` of a Griffin-Lim waveform, which lost ``TRIM`` samples at its
         head, and on sample 0 of a neural vocoder's), and only then resampled by ``AudioProcessor.deliver_at`` - the launches of
         ``convert_mel2wav_batch(..., out_rate=...)``, so tracking changes no bit of what is delivered.  f0 is float32 [B, T] on the
-        device, one value per frame of ``mel``: Hz, 0 for an unvoiced frame and behind a row's own frames."""
+        device, one value per frame of ``mel``: Hz, 0 for an unvoiced frame and behind a row's own frames.
+
+        ``control`` (pitch control; None: nothing of it runs) is ``{"ratios": float32 [B, T] on the host, the factor on the pitch of
+        every frame that the shifts in semitones ask for (``frame_ratios``), "range": float}``.  The vocoded waveform is then
+        tracked, repitched at the model's rate by ``metrics.pitch_shift`` - ratio per frame = that table times, for a ``range``
+        other than 1, 2 ** ((range - 1) * (log2 f0 - the row's mean log2 f0 over its voiced frames)) on the voiced frames, clamped
+        to [0.5, 2], torch operations on the device - and tracked again when ``pitch`` asks, so that f0 is the contour of what is
+        delivered.  A fourth value is returned: the ratios applied, float32 [B, T] on the device (1 where the waveform has no
+        frame), or None."""
         ap = self.audio_processor
         if self.vocoder is None:
             if frames is None:
@@ -227,17 +296,74 @@ class Synthesizer:
             wav = self.vocoder.vocode(mel.contiguous(), host)
             counts = None if host is None else [t * self.vocoder.hop for t in host]
             first_centre = 0
-        f0 = None
-        if pitch:
+        f0 = ratios = None
+        if pitch or control is not None:
             from . import metrics
 
-            lengths = None if counts is None else torch.tensor(counts, dtype=torch.int32, device=self.device)
-            tracked = metrics.pitch_track(wav, lengths, sampling_rate=int(ap.config.sampling_rate), hop_length=int(ap.config.hop_length),
-                                          first_centre=first_centre)["f0"]
             T = mel.shape[2]
-            f0 = tracked[:, :T] if tracked.shape[1] >= T else torch.nn.functional.pad(tracked, (0, T - tracked.shape[1]))
+            fit = lambda t, fill=0.0: t[:, :T] if t.shape[1] >= T else torch.nn.functional.pad(t, (0, T - t.shape[1]), value=fill)
+            grid = dict(sampling_rate=int(ap.config.sampling_rate), hop_length=int(ap.config.hop_length), first_centre=first_centre)
+            lengths = None if counts is None else torch.tensor(counts, dtype=torch.int32, device=self.device)
+            tracked = metrics.pitch_track(wav, lengths, **grid)
+            if control is not None:
+                F = tracked["f0"].shape[1]
+                ratio = torch.from_numpy(np.ascontiguousarray(control["ratios"], dtype=np.float32)).to(self.device)   # [B, T]
+                ratio = ratio[:, :F] if F <= T else torch.nn.functional.pad(ratio, (0, F - T), value=1.0)
+                if control["range"] != 1.0:
+                    ratio = ratio * self._range_ratios(tracked["f0"], float(control["range"]))
+                ratio = ratio.clamp(metrics.PSOLA_RATIO_MIN, metrics.PSOLA_RATIO_MAX).contiguous()
+                wav = metrics.pitch_shift(wav, lengths, tracked["lag"], ratio, **grid)["wav"].to(wav.dtype)   # float32 inside; the vocoder's dtype is kept
+                ratios = fit(ratio, 1.0)
+                if pitch:
+                    tracked = metrics.pitch_track(wav, lengths, **grid)
+            if pitch:
+                f0 = fit(tracked["f0"])
         wav, counts = ap.deliver_at(wav, counts, sampling_rate)
-        return wav, counts, f0
+        return wav, counts, f0, ratios
+
+    @staticmethod
+    def _range_ratios(f0: torch.Tensor, pitch_range: float) -> torch.Tensor:
+        """The ratio per frame that scales every voiced frame's distance from its row's mean log-F0 by ``pitch_range``: f0 is float32
+        [B, F] on the device, Hz, 0 where unvoiced.  The mean is a sum of integers (log2 f0 in units of 2^-20 octave), so a row has
+        the same mean whatever batch it is in; unvoiced frames and rows without a voiced frame get 1."""
+        voiced = f0 > 0
+        logf = torch.where(voiced, torch.log2(torch.where(voiced, f0, torch.ones_like(f0))), torch.zeros_like(f0))
+        total = (logf.to(torch.float64) * 2.0 ** 20).round().to(torch.int64).sum(dim=1, keepdim=True)
+        count = voiced.sum(dim=1, keepdim=True)
+        mean = (total.to(torch.float64) / count.clamp(min=1).to(torch.float64) / 2.0 ** 20).to(torch.float32)
+        return torch.where(voiced, torch.exp2((pitch_range - 1.0) * (logf - mean)), torch.ones_like(f0))
+
+    @staticmethod
+    def _check_pitch_control(pitch_shift, pitch_range) -> Tuple[float, float]:
+        pitch_shift = _check_semitones(pitch_shift, "pitch_shift")
+        if abs(pitch_shift) > PITCH_MAX_SEMITONES:
+            raise ValueError(f"pitch_shift = {pitch_shift} is outside [-{PITCH_MAX_SEMITONES}, {PITCH_MAX_SEMITONES}] semitones")
+        if isinstance(pitch_range, bool) or not isinstance(pitch_range, (int, float, np.integer, np.floating)) or not math.isfinite(pitch_range) \
+                or pitch_range < 0:
+            raise ValueError(f"pitch_range must be a finite number >= 0, not {pitch_range!r}")
+        return pitch_shift, float(pitch_range)
+
+    @staticmethod
+    def _sentence_semitones(token_strs: Sequence[str], word_pitch, pitch_shift: float, name: str) -> List[float]:
+        """One shift per token of a sentence, on top of ``pitch_shift``: ``token_semitones`` of ``word_pitch``, each sum within an octave."""
+        per_token = token_semitones(token_strs, word_pitch)
+        for tok, semis in zip(token_strs, per_token):
+            if abs(pitch_shift + semis) > PITCH_MAX_SEMITONES:
+                raise ValueError(f"{name}: pitch_shift {pitch_shift} plus {semis} semitones on the word of {tok!r} is outside "
+                                 f"[-{PITCH_MAX_SEMITONES}, {PITCH_MAX_SEMITONES}]")
+        return per_token
+
+    @staticmethod
+    def _ratio_rows(starts, statuses, n_frames: int, per_token: Sequence[Sequence[float]], pitch_shift: float) -> np.ndarray:
+        """The factor on the pitch of every frame, float32 [rows, n_frames]: ``frame_ratios`` of every row's shifts per token on top
+        of ``pitch_shift`` (``starts``: first frames of the tokens per row, ``statuses``: of the search that found them; None, or a
+        row whose search was infeasible: ``pitch_shift`` alone)."""
+        table = np.full((len(per_token), n_frames), semitones_to_ratio(pitch_shift), dtype=np.float32)
+        if starts is not None:
+            for r, row in enumerate(per_token):
+                if statuses[r] == 0:
+                    table[r] = frame_ratios(starts[r][:len(row)], n_frames, row, pitch_shift)
+        return table
 
     @staticmethod
     def _pitch_keys(f0: np.ndarray) -> Dict:
@@ -298,7 +424,8 @@ class Synthesizer:
 
     def tts(self, text: str, sampling_rate: Optional[int] = None, diagnostics: bool = False,
             attention_window: Optional[Tuple[int, int]] = None, timings: bool = False, speed: float = 1.0,
-            word_speed=None, token_speed=None, pitch: bool = False) -> Dict[str, np.ndarray]:
+            word_speed=None, token_speed=None, pitch: bool = False, pitch_shift: float = 0.0, word_pitch=None,
+            pitch_range: float = 1.0) -> Dict[str, np.ndarray]:
         """``sampling_rate`` (Hz; default: the model's): the waveform is resampled on the device before it is copied to the host,
         and ``"sampling_rate"`` of the result is the rate delivered.  ``diagnostics``: the result gains ``"alignment_stats"``
         (focus, monotonic_fraction, max_jump, coverage, first_pos, last_pos of the sentence's alignment, as Python numbers) and
@@ -323,12 +450,25 @@ class Synthesizer:
         vocoded (the warped one under rate control), tracked on the device on the model-rate waveform before any resampling
         (``metrics.pitch_track``, YIN) - and ``"voiced_fraction"``; with ``timings`` and an ``"ok"`` status also ``"token_pitch"``: one
         ``(token, mean_hz or None, voiced_fraction)`` per token over the token's frames (``token_pitch``).  Without ``pitch`` every
-        key and every bit is what it is today."""
+        key and every bit is what it is today.  ``pitch_shift`` (semitones; 12 = an octave up), ``word_pitch`` (semitones per word, or
+        ``{word_index: semitones}``: see ``token_semitones``; on top of ``pitch_shift``, each sum within +-12) and ``pitch_range`` (>= 0:
+        every voiced frame's distance from the sentence's mean log-F0 is scaled by it - 0 is monotone, 2 twice as lively) set the
+        pitch.  With all three at their defaults nothing changes and no launch is added.  Otherwise the vocoded waveform is tracked
+        and repitched on the device at the model's rate, before any resampling (``metrics.pitch_shift``, TD-PSOLA: the duration and
+        every sample count stay, so ``timings`` are what they are without it; a word's frames are those of the search of
+        ``timings``, or of the rate plan): the result gains ``"pitch_shift"`` and ``"pitch_ratio"`` - float32 [frames], the factor on
+        the pitch applied to every frame of the vocoded mel, clamped to [0.5, 2] - and ``pitch`` reports the contour of the shifted
+        waveform."""
         token_strs = self.text_processor.tokenize(text)
         paced = speed != 1.0 or word_speed is not None or token_speed is not None
         if paced:
             speed = self._check_speed(speed)
             rates = [self._sentence_rates(token_strs, word_speed, token_speed)]
+        repitched = pitch_shift != 0.0 or word_pitch is not None or pitch_range != 1.0
+        if repitched:
+            pitch_shift, pitch_range = self._check_pitch_control(pitch_shift, pitch_range)
+            semis = [self._sentence_semitones(token_strs, word_pitch, pitch_shift, "sentence 0")]
+        by_word = repitched and word_pitch is not None
         tokens = self.text_processor.tokens_to_indices(token_strs)
         tokens = torch.IntTensor(tokens).unsqueeze(0).to(self.device)
         inputs = {"tokens": tokens}
@@ -341,10 +481,16 @@ class Synthesizer:
         mel = outputs["mel_outputs_postnet"]
         if paced:
             mel, _, plan = self._rate_control(outputs, None, None, speed, rates, ["sentence 0"])
-            aligned = ([plan[0][0]], [plan[0][1]]) if timings else None
+            aligned = ([plan[0][0]], [plan[0][1]]) if timings or by_word else None
         else:
-            aligned = self._align(outputs, None, None) if timings else None
-        wav, _, f0 = self._vocode_and_track(mel, None, sampling_rate, pitch)  # stays on the device until the end
+            aligned = self._align(outputs, None, None) if timings or by_word else None
+        control = None
+        if repitched:
+            control = {"ratios": self._ratio_rows(aligned[0] if by_word else None, aligned[1] if by_word else None, mel.shape[2], semis,
+                                                  pitch_shift), "range": pitch_range}
+        if not timings:
+            aligned = None
+        wav, _, f0, ratios = self._vocode_and_track(mel, None, sampling_rate, pitch, control)  # stays on the device until the end
         result = {key: val.squeeze(0).cpu().numpy() for key, val in outputs.items()}
         result["waveform"] = wav[0].cpu().numpy()
         result["sampling_rate"] = self._out_rate(sampling_rate)
@@ -361,12 +507,16 @@ class Synthesizer:
             if aligned is not None and result["timings_status"] == "ok":
                 per_token = token_pitch(aligned[0][0][:len(token_strs)], mel.shape[2], result["f0"])
                 result["token_pitch"] = [(tok, hz, share) for tok, (hz, share) in zip(token_strs, per_token)]
+        if ratios is not None:
+            result["pitch_shift"] = pitch_shift
+            result["pitch_ratio"] = ratios[0].cpu().numpy()
         return result
 
     def tts_batch(self, texts: Sequence[str], batch_size: int = 32, sampling_rate: Optional[int] = None,
                   diagnostics: bool = False, attention_window: Optional[Tuple[int, int]] = None,
                   timings: bool = False, speed: float = 1.0, word_speed=None, token_speed=None,
-                  pitch: bool = False) -> List[Dict[str, np.ndarray]]:
+                  pitch: bool = False, pitch_shift: float = 0.0, word_pitch=None,
+                  pitch_range: float = 1.0) -> List[Dict[str, np.ndarray]]:
         """Many sentences per call: one dict per sentence, in input order, with the keys, dtypes and shapes ``tts(text)`` gives
         for that sentence (every row trimmed to its own frames, tokens and samples).  Sentences are decoded as padded batches of
         at most ``batch_size`` rows of similar token length (``plan_tts_batches``) and vocoded at their own lengths in one ragged
@@ -377,7 +527,10 @@ class Synthesizer:
         sentence aligned at its own frames and tokens, timed against its own waveform.  ``speed`` as in ``tts``, for every
         sentence; ``word_speed`` and ``token_speed`` are lists with one entry per sentence, each as in ``tts`` (None: no rates
         for that sentence): every sentence is warped at its own frames, tokens and rates and vocoded at its own new length.
-        ``pitch`` as in ``tts``: every sentence's waveform is tracked at its own sample count, in one call per batch."""
+        ``pitch`` as in ``tts``: every sentence's waveform is tracked at its own sample count, in one call per batch.
+        ``pitch_shift`` and ``pitch_range`` as in ``tts``, for every sentence; ``word_pitch`` is a list with one entry per sentence,
+        each as in ``tts`` (None: no word of that sentence is named): every sentence is repitched at its own sample count, around its
+        own mean pitch, in one plan and one synthesis call per batch."""
         token_strs = [self.text_processor.tokenize(t) for t in texts]
         token_lists = [self.text_processor.tokens_to_indices(toks) for toks in token_strs]
         paced = speed != 1.0 or word_speed is not None or token_speed is not None
@@ -388,6 +541,14 @@ class Synthesizer:
                     raise ValueError(f"{what} has {len(per)} entries for {len(token_strs)} sentences")
             rates = [self._sentence_rates(toks, word_speed[i] if word_speed is not None else None,
                                           token_speed[i] if token_speed is not None else None) for i, toks in enumerate(token_strs)]
+        repitched = pitch_shift != 0.0 or word_pitch is not None or pitch_range != 1.0
+        if repitched:
+            pitch_shift, pitch_range = self._check_pitch_control(pitch_shift, pitch_range)
+            if word_pitch is not None and len(word_pitch) != len(token_strs):
+                raise ValueError(f"word_pitch has {len(word_pitch)} entries for {len(token_strs)} sentences")
+            semis = [self._sentence_semitones(toks, word_pitch[i] if word_pitch is not None else None, pitch_shift, f"sentence {i}")
+                     for i, toks in enumerate(token_strs)]
+        by_word = repitched and word_pitch is not None
         results: List[Dict[str, np.ndarray]] = [{} for _ in token_lists]
         for idx, tokens, lens in plan_tts_batches(token_lists, batch_size):
             inputs = {"tokens": tokens.to(self.device)}
@@ -402,20 +563,28 @@ class Synthesizer:
             if paced:
                 warped, new_frames, plan = self._rate_control(outputs, outputs.get("mel_lengths"), inputs.get("token_lengths"), speed,
                                                               [rates[i] for i in idx], [f"sentence {i}" for i in idx])
-                aligned = ([p[0] for p in plan], [p[1] for p in plan]) if timings else None
+                aligned = ([p[0] for p in plan], [p[1] for p in plan]) if timings or by_word else None
                 new_frames_host = [p[2] for p in plan]
             else:
-                aligned = self._align(outputs, outputs.get("mel_lengths"), inputs.get("token_lengths")) if timings else None
+                aligned = self._align(outputs, outputs.get("mel_lengths"), inputs.get("token_lengths")) if timings or by_word else None
+            vocoded = mel if warped is None else warped
+            control = None
+            if repitched:
+                control = {"ratios": self._ratio_rows(aligned[0] if by_word else None, aligned[1] if by_word else None, vocoded.shape[2],
+                                                      [semis[i] for i in idx], pitch_shift), "range": pitch_range}
+            if not timings:
+                aligned = None
             if len(idx) > 1:
                 frames = outputs.pop("mel_lengths")
-                wav, samples, f0 = self._vocode_and_track(mel if warped is None else warped, frames if warped is None else new_frames,
-                                                          sampling_rate, pitch)
+                wav, samples, f0, ratios = self._vocode_and_track(vocoded, frames if warped is None else new_frames, sampling_rate, pitch, control)
                 frames = frames.tolist()
             else:
-                wav, _, f0 = self._vocode_and_track(mel if warped is None else warped, None, sampling_rate, pitch)
+                wav, _, f0, ratios = self._vocode_and_track(vocoded, None, sampling_rate, pitch, control)
                 frames, samples = [mel.shape[2]], [wav.shape[1]]
             if f0 is not None:
                 f0 = f0.cpu().numpy()
+            if ratios is not None:
+                ratios = ratios.cpu().numpy()
             host = {key: val.cpu().numpy() for key, val in outputs.items()}
             if warped is not None:
                 warped = warped.cpu().numpy()
@@ -447,4 +616,7 @@ class Synthesizer:
                     if aligned is not None and results[i]["timings_status"] == "ok":
                         per_token = token_pitch(aligned[0][r][:len(token_strs[i])], t, results[i]["f0"])
                         results[i]["token_pitch"] = [(tok, hz, share) for tok, (hz, share) in zip(token_strs[i], per_token)]
+                if ratios is not None:
+                    results[i]["pitch_shift"] = pitch_shift
+                    results[i]["pitch_ratio"] = ratios[r, :t].copy()
         return results

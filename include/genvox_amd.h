@@ -853,6 +853,94 @@ int gvx_pitch_yin(const float* wav, const int32_t* sample_lengths, int B, long N
 int gvx_f0_compare(const float* f0_a, const float* f0_b, const int32_t* frames_a, const int32_t* frames_b, int B, int F,
                    int32_t* counts_out, float* vde_out, float* gpe_out, float* rmse_cents_out, void* stream);
 
+/* ---- Pitch control: time-domain pitch-synchronous overlap-add (TD-PSOLA) of waveforms on the device, in two calls - the plan
+ * (where the pitch marks of the input lie and where the grains of the output go) and the synthesis (the overlap-add).  The row
+ * keeps its length; its pitch is multiplied by a ratio per frame.  Both calls are asynchronous on `stream`, write caller-allocated
+ * outputs only, need no workspace and give the same bits every run (fixed summation orders, no atomics); no workgroup waits for
+ * another and every loop is bounded by the capacities below.
+ *
+ * All quantities are per row b.  The row has n = sample_lengths[b] samples, clamped to [0, N] (NULL: N); x is the row with zeros
+ * outside [0, n); nothing at or behind n is read, whatever it holds.  The frame grid is the tracker's: hop, first_centre,
+ * F_b = gvx_pitch_frames(n, hop), and F = gvx_pitch_frames(N, hop) is the stride of lag and ratio.
+ *
+ *     frame_of(t)  = clamp( floordiv(t - first_centre + hop / 2, hop), 0, F_b - 1 )        (hop / 2 by integer division)
+ *     lag          int32 [B][F], as gvx_pitch_yin writes it (-1: unvoiced)
+ *     voiced_at(t) = lag[frame_of(t)] >= 1
+ *     period_at(t) = clamp(lag[frame_of(t)], lag_min, lag_max) when voiced_at(t) (the clamp changes no lag of the tracker's),
+ *                    else U = unvoiced_period
+ *
+ * Analysis marks - integers and comparisons only, hence exact.  m_{-1} = -1.  The candidate is c = 0 for k = 0 and
+ * c = m_{k-1} + period_at(m_{k-1}) afterwards; the walk stops when c >= n.  If voiced_at(c):
+ *     r   = min(period_at(c), period_at(m_{k-1})) / 4     by integer division; for k = 0, r = period_at(0) / 4
+ *     m_k = the lowest index of the largest x over [max(c - r, m_{k-1} + 1), min(c + r, n - 1)]: the first index whose sample
+ *           compares greater than everything before it, from -inf (a window of nothing but NaN and -inf, which no waveform
+ *           holds, gives m_k = c)
+ * otherwise m_k = c.  Recorded: p_k = period_at(m_k) and v_k = voiced_at(m_k).  A step advances by at least ceil(3 p / 4), so a
+ * row has at most gvx_psola_max_marks(N, p_min) = N / ceil(3 p_min / 4) + 1 marks, p_min = min(lag_min, U): the loop bound and the
+ * capacity K of the mark outputs.
+ *
+ * Synthesis marks.  ratio is fp32 [B][F] on the same frame grid; ratio > 1 raises the pitch.  s_0 = m_0, a_0 = 0; grain j copies
+ * analysis grain a_j:
+ *     q_j     = v_{a_j} ? ratio[frame_of(s_j)] : 1                                  unvoiced sound is never repitched
+ *     step_j  = max(1, (int)floor((double)p_{a_j} / (double)q_j + 0.5))
+ *     s_{j+1} = s_j + step_j                                                        the walk stops when s_{j+1} >= n
+ *     a_{j+1} = the k >= a_j with the smallest |m_k - s_{j+1}|, lowest k on a tie    a pointer that only moves forward
+ * A row has at most gvx_psola_max_grains(N, p_min) = N / max(1, (p_min + 1) / 2) + 1 grains: the capacity J of the grain outputs.
+ * A ratio that is NaN or outside [GVX_PSOLA_RATIO_MIN, GVX_PSOLA_RATIO_MAX] = [0.5, 2] in a frame below F_b gives the row the
+ * status GVX_PSOLA_BAD_RATIO: its analysis marks are written, it has no grains, and the synthesis copies it through unchanged.
+ * A row with n = 0 (the only rows without marks) has the status GVX_PSOLA_EMPTY.
+ *
+ * Overlap-add, fp32, every operation rounded once, in this order.  Grain j reaches sample t when u = t - s_j has |u| < p_{a_j}:
+ *     v      = 1 - (float)|u| / (float)p_{a_j}
+ *     w      = (v * v) * (3 - 2 * v)                    S(v) = v^2 (3 - 2 v): a polynomial window, every bit defined without a device
+ *                                                       cosine; like Hann's, S(v) + S(1 - v) = 1: grains at a constant period sum to 1
+ *     Num(t) = fmaf(w, x[m_{a_j} + u], Num(t))          D(t) = D(t) + w        both from 0, j ascending
+ *     inside [s_0, s_last]:  y = Num / max(D, 0.5)
+ *     outside it:            y = D >= 1 ? Num / D : fmaf(1 - D, x[t], Num)     sound before the first and after the last mark is kept
+ *     y[t] = 0 for t >= n
+ *
+ * gvx_psola_plan - one launch, one workgroup (one wave) per row: both walks are sequential by nature.  The wave stages 4096 samples
+ * and the periods of their frames in LDS at a time, searches the window of a mark (at most 2 (lag_max / 4) + 1 samples) with all
+ * lanes and a lowest-index tie rule, and stores marks and grains 64 at a time.  Outputs:
+ *     marks_out       int32 [B][K]   m_k                                   K = gvx_psola_max_marks(N, min(lag_min, U))
+ *     periods_out     int32 [B][K]   v_k ? p_k : -p_k
+ *     syn_pos_out     int32 [B][J]   s_j                                   J = gvx_psola_max_grains(N, min(lag_min, U))
+ *     syn_src_out     int32 [B][J]   a_j
+ *     counts_out      int32 [B][GVX_PSOLA_ROW_INTS]   [GVX_PSOLA_MARKS], [GVX_PSOLA_GRAINS]
+ *     row_status_out  int32 [B]      GVX_PSOLA_OK / EMPTY / BAD_RATIO
+ * Nothing is written behind the counts.
+ *
+ * gvx_psola_synth - one launch, a workgroup per row and GVX_PSOLA_TILE output samples.  It finds the grains that can reach its tile
+ * (s within max(lag_max, U) of it) by bisection over s, keeps their (s, m, p) in LDS (at most GVX_PSOLA_TILE + 2 max(lag_max, U)),
+ * and every thread gathers its own sample in ascending j.  marks .. row_status are what the plan wrote (counts and indices that
+ * are out of range are clamped, samples outside [0, n) read as 0: no table can make the call read or write out of bounds).
+ * wav_out is fp32 [B][N] and may not overlap wav.
+ *
+ * Refused before anything is launched: a NULL wav, lag, ratio (plan), params, table or output, B, N, hop, lag_min or
+ * unvoiced_period below 1, lag_max below lag_min: GVX_ERR_INVALID_ARG; lag_max or unvoiced_period above GVX_PITCH_MAX_LAG, B above
+ * GVX_PITCH_MAX_ROWS, more than GVX_PITCH_MAX_FRAMES frames, or more than GVX_PITCH_MAX_FRAMES * GVX_PITCH_MAX_LAG samples at a hop beyond
+ * that lag (counts and indices are 32-bit): GVX_ERR_UNSUPPORTED. */
+typedef struct gvx_psola_params {
+    int32_t hop;               /* samples between frame centres: the tracker's                 */
+    int32_t first_centre;      /* sample index of frame 0's centre: the tracker's              */
+    int32_t lag_min;           /* shortest and                                                 */
+    int32_t lag_max;           /*   longest period the lag table can hold                      */
+    int32_t unvoiced_period;   /* U: the spacing of marks where there is no pitch              */
+} gvx_psola_params;
+enum { GVX_PSOLA_OK = 0, GVX_PSOLA_EMPTY = 1, GVX_PSOLA_BAD_RATIO = 2 };
+enum { GVX_PSOLA_MARKS = 0, GVX_PSOLA_GRAINS = 1, GVX_PSOLA_ROW_INTS = 2 };
+enum { GVX_PSOLA_TILE = 256 };
+#define GVX_PSOLA_RATIO_MIN 0.5f
+#define GVX_PSOLA_RATIO_MAX 2.0f
+long gvx_psola_max_marks(long N, int p_min);    /* host arithmetic; 0 for N < 1 or p_min < 1 */
+long gvx_psola_max_grains(long N, int p_min);   /* host arithmetic; 0 for N < 1 or p_min < 1 */
+int gvx_psola_plan(const float* wav, const int32_t* sample_lengths, const int32_t* lag, const float* ratio, int B, long N,
+                   const gvx_psola_params* params, int32_t* marks_out, int32_t* periods_out, int32_t* syn_pos_out,
+                   int32_t* syn_src_out, int32_t* counts_out, int32_t* row_status_out, void* stream);
+int gvx_psola_synth(const float* wav, const int32_t* sample_lengths, const int32_t* marks, const int32_t* periods,
+                    const int32_t* syn_pos, const int32_t* syn_src, const int32_t* counts, const int32_t* row_status, int B, long N,
+                    const gvx_psola_params* params, float* wav_out, void* stream);
+
 /* ---- Neural vocoder: MelGAN generator inference, mel -> waveform.  The reference promises a vocoder model and ships only its config
  * (configs/models.py:89-121, MelGANConfig); the network below is this project's statement of the MelGAN generator.
  *
