@@ -33,6 +33,10 @@ class gvx_melgan_dims(C.Structure):
                 ("n_residual_layers", C.c_int32), ("dilation_base", C.c_int32), ("slope", C.c_float)]
 
 
+class gvx_melgan_tape_entry(C.Structure):
+    _fields_ = [("byte_offset", C.c_uint64), ("positions_per_frame", C.c_int32), ("channels", C.c_int32)]
+
+
 class gvx_pitch_params(C.Structure):
     _fields_ = [("sampling_rate", C.c_int32), ("hop", C.c_int32), ("window", C.c_int32), ("lag_min", C.c_int32), ("lag_max", C.c_int32),
                 ("threshold", C.c_float), ("first_centre", C.c_int32)]
@@ -159,6 +163,11 @@ SIGNATURES = {
     "gvx_melgan_forward": (_i, [_vp, _vp, _vp, _i, _i, _vp, C.POINTER(_vp), _vp, _sz, _vp]),
     "gvx_melgan_timing_enable": (_i, [_vp, _i]),
     "gvx_melgan_stage_times_ms": (_i, [_vp, C.POINTER(_f), C.POINTER(_i)]),
+    "gvx_melgan_tape_bytes": (_sz, [C.POINTER(gvx_melgan_dims), _i, _i]),
+    "gvx_melgan_tape_layout": (_i, [C.POINTER(gvx_melgan_dims), _i, _i, C.POINTER(gvx_melgan_tape_entry), _i]),
+    "gvx_melgan_backward_workspace_bytes": (_sz, [C.POINTER(gvx_melgan_dims), _i, _i]),
+    "gvx_melgan_forward_train": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "gvx_melgan_backward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, C.POINTER(gvx_weight_desc), _i, _vp, _vp, _sz, _vp]),
     "gvx_kernel_timing_enable": (_i, [_vp, _i]),
     "gvx_model_set_persistent_attention": (_i, [_vp, _i]),
     "gvx_model_set_resident_kernels": (_i, [_vp, _i]),

@@ -20,57 +20,14 @@
 // A workgroup belongs to one batch row and computes nothing behind that row's length; tensors the caller sees are zero-filled there.
 //
 // Order of this file: layer description, the two kernels, the mel transpose, the weight packer, the C ABI.
-#include "gvx_internal.h"
+#include "melgan_internal.h"
 
 using gvx::fail;
-
-struct gvx_melgan {
-    gvx_melgan_dims d;
-    const float* blob = nullptr;
-    bool timing = false;
-    bool lds_ready = false;
-    hipEvent_t ev[GVX_MELGAN_MAX_STAGES + 3] = {};
-    int n_ev = 0;
-};
+using namespace gvx_mg;
 
 namespace {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
-
-struct MgLayer {
-    const float* src0; const float* src1;   // tap sources (src1: tap 1 of the residual tail)
-    const float* W; const float* bias; const float* bias2;
-    float* out;
-    const int32_t* lens;   // frames per row, or nullptr
-    int T, in_mul;         // row b has T_b * in_mul input positions; tensors are strided by T * in_mul positions per row
-    int Cin, Cout, K;      // K = taps * Cin
-    int taps, dil, phases;
-    int act_mask, two_src, zero_tail, tanh_out;
-    float slope;
-};
-
-__device__ __forceinline__ int mg_frames(const int32_t* lens, int b, int T) {
-    int v = lens ? lens[b] : T;
-    v = v > T ? T : v;
-    return v < GVX_MELGAN_MIN_FRAMES ? 0 : v;   // rows the host should have refused produce silence, never a bad address
-}
-
-// source position of tap tau for output group q (q < len); zero: the tap lies outside the row and contributes nothing
-__device__ __forceinline__ int mg_src_row(const MgLayer& p, int q, int tau, int phase, int len, bool& zero) {
-    int s;
-    if (p.phases == 1) {
-        s = q + (tau - ((p.taps - 1) >> 1)) * p.dil;
-        s = s < 0 ? -s : s;
-        s = s >= len ? 2 * (len - 1) - s : s;
-        zero = false;
-    } else {
-        s = tau == 0 ? q : (2 * phase < p.phases ? q - 1 : q + 1);
-        zero = s < 0 || s >= len;
-    }
-    return s < 0 ? 0 : (s >= len ? len - 1 : s);
-}
-
-__device__ __forceinline__ float mg_lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
 
 constexpr int MG_LD = 36;   // floats per LDS row of a 32-deep k-tile: the fragment reads of sixteen lanes fall on distinct 16-byte slots
 template <int BM, int BN>
@@ -276,64 +233,6 @@ __global__ void __launch_bounds__(256) mg_pack_tconv_kernel(float* dst, const fl
 }
 
 // ---- host side
-inline size_t mg_round64(size_t floats) { return (floats + 63) & ~(size_t)63; }
-inline size_t mg_round256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-inline int mg_cpad(const gvx_melgan_dims& d) { return (d.n_mels + 3) & ~3; }
-
-const char* mg_dims_problem(const gvx_melgan_dims* d) {
-    if (!d) return "null dims";
-    if (d->n_mels < 1 || d->base_channels < 1) return "n_mels and base_channels must be >= 1";
-    if (d->n_stages < 1 || d->n_stages > GVX_MELGAN_MAX_STAGES) return "n_stages must be in [1, GVX_MELGAN_MAX_STAGES]";
-    long hop = 1;
-    for (int i = 0; i < d->n_stages; ++i) {
-        if (d->ratios[i] < 2 || (d->ratios[i] & 1)) return "every upsampling ratio must be even and >= 2";
-        hop *= d->ratios[i];
-        if (hop > GVX_MELGAN_MAX_HOP) return "the product of the ratios is beyond GVX_MELGAN_MAX_HOP";
-    }
-    if (d->base_channels % (1 << d->n_stages) != 0) return "base_channels must be divisible by 2^n_stages";
-    if (d->n_residual_layers < 1 || d->n_residual_layers > 8) return "n_residual_layers must be in [1, 8]";
-    if (d->dilation_base < 1) return "dilation_base must be >= 1";
-    long dil = 1;
-    for (int j = 1; j < d->n_residual_layers; ++j) dil *= d->dilation_base;
-    if (dil >= (long)GVX_MELGAN_MIN_FRAMES * d->ratios[0]) return "the largest dilation must be below 4 * ratios[0], the shortest row of the first stage";
-    if (!(d->slope >= 0.f && d->slope <= 1.f)) return "slope must be in [0, 1]";
-    return nullptr;
-}
-
-struct MgBlob {   // offsets in floats
-    size_t pre_w, pre_b, post_w, post_b;
-    size_t up_w[GVX_MELGAN_MAX_STAGES], up_b[GVX_MELGAN_MAX_STAGES];
-    size_t conv_w[GVX_MELGAN_MAX_STAGES][8], conv_b[GVX_MELGAN_MAX_STAGES][8], tail_w[GVX_MELGAN_MAX_STAGES][8], sc_b[GVX_MELGAN_MAX_STAGES][8],
-        mix_b[GVX_MELGAN_MAX_STAGES][8];
-    size_t total;
-};
-
-MgBlob mg_blob_layout(const gvx_melgan_dims& d) {
-    MgBlob L{};
-    size_t at = 0;
-    auto take = [&](size_t floats) { const size_t o = at; at += mg_round64(floats); return o; };
-    size_t C = d.base_channels;
-    L.pre_w = take(C * 7 * mg_cpad(d));
-    L.pre_b = take(C);
-    for (int i = 0; i < d.n_stages; ++i) {
-        const size_t Cn = C / 2;
-        L.up_w[i] = take((size_t)d.ratios[i] * Cn * 2 * C);
-        L.up_b[i] = take(Cn);
-        for (int j = 0; j < d.n_residual_layers; ++j) {
-            L.conv_w[i][j] = take(Cn * 3 * Cn);
-            L.conv_b[i][j] = take(Cn);
-            L.tail_w[i][j] = take(Cn * 2 * Cn);
-            L.sc_b[i][j] = take(Cn);
-            L.mix_b[i][j] = take(Cn);
-        }
-        C = Cn;
-    }
-    L.post_w = take(7 * C);
-    L.post_b = take(1);
-    L.total = at;
-    return L;
-}
-
 struct MgWs {   // byte offsets; every region is B times a per-row size that is a multiple of 256
     size_t mel_t, buf[3], total;
 };
@@ -366,6 +265,10 @@ int mg_launch_mfma(const MgLayer& p, int B, hipStream_t s) {
     return GVX_OK;
 }
 
+}  // namespace
+
+namespace gvx_mg {
+
 int mg_launch(const MgLayer& p, int B, hipStream_t s) {
     if (p.Cout >= 32 && p.Cin % 4 == 0) {
         if (p.Cout >= 128) return mg_launch_mfma<2, 2, 2, 2>(p, B, s);
@@ -394,7 +297,23 @@ const gvx_weight_desc* mg_find(const gvx_weight_desc* table, int n, const std::s
     return nullptr;
 }
 
-}  // namespace
+int mg_mel_transpose(const float* mel, const int32_t* lens, int B, int M, int T, int Cp, float* out, hipStream_t s) {
+    const dim3 grid((unsigned)(((long)T * Cp + 255) / 256), (unsigned)B);
+    mg_mel_transpose_kernel<<<grid, 256, 0, s>>>(mel, lens, M, T, Cp, out);
+    HIP_TRY(hipGetLastError());
+    return GVX_OK;
+}
+
+int mg_prepare(gvx_melgan* h) {
+    if (!h->lds_ready) {
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(mg_mfma_kernel<2, 2, 2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)mg_lds_bytes<128, 128>()));
+        h->lds_ready = true;
+    }
+    return GVX_OK;
+}
+
+}  // namespace gvx_mg
 
 extern "C" {
 
@@ -513,11 +432,8 @@ int gvx_melgan_forward(gvx_melgan* h, const float* mel, const int32_t* frame_len
         for (int i = 0; i < d.n_stages; ++i)
             if (!stage_out[i] || (uintptr_t)stage_out[i] % 16) return fail(GVX_ERR_INVALID_ARG, "stage_out[%d] is null or not 16-byte aligned", i);
     hipStream_t s = (hipStream_t)stream;
-    if (!h->lds_ready) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(mg_mfma_kernel<2, 2, 2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)mg_lds_bytes<128, 128>()));
-        h->lds_ready = true;
-    }
+    int rc;
+    if ((rc = mg_prepare(h)) != GVX_OK) return rc;
     const MgBlob L = mg_blob_layout(d);
     const float* blob = h->blob;
     float* pool[3] = {gvx::ws_ptr<float>(workspace, wp.buf[0]), gvx::ws_ptr<float>(workspace, wp.buf[1]), gvx::ws_ptr<float>(workspace, wp.buf[2])};
@@ -531,16 +447,11 @@ int gvx_melgan_forward(gvx_melgan* h, const float* mel, const int32_t* frame_len
         if (h->timing) HIP_TRY(hipEventRecord(h->ev[ev++], s));
         return GVX_OK;
     };
-    int rc;
     if ((rc = stamp()) != GVX_OK) return rc;
 
     const int Cp = mg_cpad(d);
     float* mel_t = gvx::ws_ptr<float>(workspace, wp.mel_t);
-    {
-        const dim3 grid((unsigned)(((long)T * Cp + 255) / 256), (unsigned)B);
-        mg_mel_transpose_kernel<<<grid, 256, 0, s>>>(mel, frame_lengths, d.n_mels, T, Cp, mel_t);
-        HIP_TRY(hipGetLastError());
-    }
+    if ((rc = mg_mel_transpose(mel, frame_lengths, B, d.n_mels, T, Cp, mel_t, s)) != GVX_OK) return rc;
     MgLayer p{};
     p.lens = frame_lengths;
     p.T = T;

@@ -69,6 +69,50 @@ def fold_weight_norm(state_dict) -> Dict[str, torch.Tensor]:
     return out
 
 
+class _VocodeWithGrad(torch.autograd.Function):
+    """gvx_melgan_forward_train / gvx_melgan_backward as one autograd node.  The inputs after ``lens_dev`` are the model's parameters
+    in ``named_parameters()`` order; they go through ``save_for_backward``, so an in-place change between forward and backward raises
+    torch's own version error, and the tape is a tensor the node keeps."""
+
+    @staticmethod
+    def forward(ctx, model, mel, lens_dev, *params):
+        lib, dims = _lib.load(), model.dims()
+        h = model._ensure_packed()
+        B, _, T = mel.shape
+        dev = mel.device
+        wav = torch.empty(B, T * model.hop, dtype=torch.float32, device=dev)
+        tape = torch.empty(lib.gvx_melgan_tape_bytes(C.byref(dims), B, T), dtype=torch.uint8, device=dev)
+        _lib.check(lib.gvx_melgan_forward_train(h, mel.data_ptr(), lens_dev.data_ptr() if lens_dev is not None else None, B, T, wav.data_ptr(),
+                                                tape.data_ptr(), tape.numel(), None, 0, model._stream()))
+        ctx.model, ctx.lens_dev, ctx.shape, ctx.tape, ctx.packed_key = model, lens_dev, (B, T), tape, model._packed_key
+        ctx.save_for_backward(*params)
+        return wav
+
+    @staticmethod
+    def backward(ctx, d_wav):
+        params = ctx.saved_tensors   # raises if a parameter was changed in place since the forward
+        model, (B, T) = ctx.model, ctx.shape
+        lib, dims = _lib.load(), model.dims()
+        if model._packed_key != ctx.packed_key:
+            raise RuntimeError("the generator's weights were packed again between this forward and its backward")
+        dev = d_wav.device
+        d_wav = d_wav.to(torch.float32).contiguous()
+        names = [k for k, _ in model.named_parameters()]
+        grads = [torch.empty_like(p, dtype=torch.float32, memory_format=torch.contiguous_format) for p in params]
+        table = (_lib.gvx_weight_desc * len(grads))()
+        for i, (k, g) in enumerate(zip(names, grads)):
+            table[i] = _lib.gvx_weight_desc(k.encode(), g.data_ptr(), g.numel())
+        d_mel = torch.empty(B, model.audio_config.n_mels, T, dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
+        need = lib.gvx_melgan_backward_workspace_bytes(C.byref(dims), B, T)
+        if model._train_workspace is None or model._train_workspace.numel() < need or model._train_workspace.device != dev:
+            model._train_workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = model._train_workspace
+        _lib.check(lib.gvx_melgan_backward(model._handle, d_wav.data_ptr(), ctx.lens_dev.data_ptr() if ctx.lens_dev is not None else None, B, T,
+                                           ctx.tape.data_ptr(), ctx.tape.numel(), table, len(grads), d_mel.data_ptr() if d_mel is not None else None,
+                                           ws.data_ptr(), ws.numel(), model._stream()))
+        return (None, d_mel, None, *grads)
+
+
 class MelGANGenerator(nn.Module):
     model_name = "melgan"
     WORKSPACE_CAP_BYTES = 1 << 30   # a call whose workspace would pass this is split by rows (98,624 bytes per frame and row with the defaults)
@@ -89,6 +133,7 @@ class MelGANGenerator(nn.Module):
         self._blob: Optional[torch.Tensor] = None
         self._packed_key = None
         self._workspace: Optional[torch.Tensor] = None
+        self._train_workspace: Optional[torch.Tensor] = None   # the backward's scratch (vocode_with_grad)
         self._timing = False
 
     # ------------------------------------------------------------------ C-ABI plumbing
@@ -157,14 +202,8 @@ class MelGANGenerator(nn.Module):
         return [out[i] for i in range(n.value)]
 
     # ------------------------------------------------------------------ the call
-    def vocode(self, mel: torch.Tensor, mel_lengths=None, stage_outputs: bool = False, workspace: Optional[torch.Tensor] = None):
-        """mel float32 [B, n_mels, T] on the device (the model's own dB scale, as ``mel_outputs_postnet``) -> waveform float32
-        [B, T * hop].  ``mel_lengths`` ([B], host or device): every row at its own frames - bit for bit that row run alone - and
-        exact zeros behind ``T_b * hop`` samples; the padded frames of ``mel`` may hold anything.  A row below 4 frames raises
-        ValueError before anything is launched.  A batch whose workspace would pass ``WORKSPACE_CAP_BYTES`` is run in groups of rows;
-        rows do not depend on each other, so the split changes no bit.  ``stage_outputs``: also the list of x after every stage,
-        [B, len_i, C_i] channels-last (tests).  ``workspace``: a uint8 tensor to use as it is, of at least ``workspace_bytes(B, T)``
-        (tests of the workspace contract; no row split then)."""
+    def _check_call(self, mel: torch.Tensor, mel_lengths):
+        """The argument checks of ``vocode`` and ``vocode_with_grad`` -> (device, B, T, the lengths as int32 on the device or None)."""
         dev = self._require_gpu()
         if mel.dim() != 3 or mel.shape[1] != self.audio_config.n_mels:
             raise ValueError(f"mel must be [B, {self.audio_config.n_mels}, T], got {tuple(mel.shape)}")
@@ -182,6 +221,17 @@ class MelGANGenerator(nn.Module):
             lens_dev = (mel_lengths if isinstance(mel_lengths, torch.Tensor) else torch.tensor(host)).to(dev, torch.int32).contiguous()
         if B < 1 or T < MIN_FRAMES:
             raise ValueError(f"a mel of {B} rows and {T} frames: every row needs at least {MIN_FRAMES} frames (the first convolution reflects 3)")
+        return dev, B, T, lens_dev
+
+    def vocode(self, mel: torch.Tensor, mel_lengths=None, stage_outputs: bool = False, workspace: Optional[torch.Tensor] = None):
+        """mel float32 [B, n_mels, T] on the device (the model's own dB scale, as ``mel_outputs_postnet``) -> waveform float32
+        [B, T * hop].  ``mel_lengths`` ([B], host or device): every row at its own frames - bit for bit that row run alone - and
+        exact zeros behind ``T_b * hop`` samples; the padded frames of ``mel`` may hold anything.  A row below 4 frames raises
+        ValueError before anything is launched.  A batch whose workspace would pass ``WORKSPACE_CAP_BYTES`` is run in groups of rows;
+        rows do not depend on each other, so the split changes no bit.  ``stage_outputs``: also the list of x after every stage,
+        [B, len_i, C_i] channels-last (tests).  ``workspace``: a uint8 tensor to use as it is, of at least ``workspace_bytes(B, T)``
+        (tests of the workspace contract; no row split then)."""
+        dev, B, T, lens_dev = self._check_call(mel, mel_lengths)
         h = self._ensure_packed()
         lib = _lib.load()
         mel = mel.contiguous()
@@ -208,6 +258,26 @@ class MelGANGenerator(nn.Module):
             _lib.check(lib.gvx_melgan_forward(h, mel[lo:lo + n].data_ptr(), lens_dev[lo:lo + n].data_ptr() if lens_dev is not None else None, n, T,
                                               wav[lo:lo + n].data_ptr(), ptrs, workspace.data_ptr(), workspace.numel(), self._stream()))
         return (wav, stages) if stage_outputs else wav
+
+    def vocode_with_grad(self, mel: torch.Tensor, mel_lengths=None) -> torch.Tensor:
+        """``vocode`` attached to autograd: mel float32 [B, n_mels, T] on the device -> waveform float32 [B, T * hop] whose
+        ``backward()`` fills ``.grad`` of every parameter of the generator - and of ``mel`` if ``mel.requires_grad`` - on the device's
+        own kernels (gvx_melgan_forward_train / gvx_melgan_backward, csrc/melgan_train.hip), so a plain torch loop with any loss
+        written in torch and any torch optimizer trains or fine-tunes the vocoder.  The waveform has ``vocode``'s bits; under
+        ``torch.no_grad()`` (or when nothing requires a gradient) the call IS ``vocode``.  Rows are ragged as in ``vocode``; gradient
+        that arrives behind ``T_b * hop`` samples is never read, and ``mel.grad`` is 0 at and behind a row's frames.  The call keeps a
+        tape of every layer's pre-activations (747,840 bytes per frame and row with the defaults) until its backward has run; a
+        parameter changed in place between the two raises torch's version error.  Two backward calls give the same bits.
+
+        Training is on plain weights: a weight-normalised checkpoint is folded when it is loaded and stays folded, and the module
+        has no weight-norm parametrisation of its own."""
+        if not torch.is_grad_enabled() or not (mel.requires_grad or any(p.requires_grad for p in self.parameters())):
+            return self.vocode(mel, mel_lengths)
+        _, _, _, lens_dev = self._check_call(mel, mel_lengths)
+        for k, p in self.named_parameters():
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise ValueError(f"{k}: training needs contiguous float32 parameters")
+        return _VocodeWithGrad.apply(self, mel.contiguous(), lens_dev, *self.parameters())
 
     def inference(self, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         """{"mel": [B, n_mels, T], "mel_lengths": optional [B]} -> {"waveform": float32 [B, T * hop] on the device, "lengths": int32 [B]

@@ -237,7 +237,7 @@ def pitch_track(wav: torch.Tensor, sample_lengths: Optional[torch.Tensor] = None
     Returns ``f0`` fp32 [B, F] (Hz; 0 = unvoiced and behind a row's frames), ``lag`` int32 [B, F] (-1 there), ``aperiodicity`` fp32
     [B, F] (the normalised difference at the lag, or its minimum over the search range for an unvoiced frame; 1 behind the row) and
     ``frames`` int32 [B] (ceil(samples / hop_length) per row); with ``want_table`` also ``cmnd`` fp32 [B, F, lag_max + 1], the table
-    the decisions ran on.  One launch, no workspace."""
+    the decisions ran on (NaN behind a row's frames).  One launch, no workspace."""
     params = pitch_params(sampling_rate, hop_length, fmin, fmax, window, threshold, first_centre)
     dev = _need_gpu(wav, "wav")
     if wav.dim() != 2 or wav.dtype not in (torch.float32, torch.float64):
@@ -249,7 +249,8 @@ def pitch_track(wav: torch.Tensor, sample_lengths: Optional[torch.Tensor] = None
     F = lib.gvx_pitch_frames(N, params.hop)
     out = {"f0": torch.empty(B, F, dtype=torch.float32, device=dev), "lag": torch.empty(B, F, dtype=torch.int32, device=dev),
            "aperiodicity": torch.empty(B, F, dtype=torch.float32, device=dev)}
-    table = torch.empty(B, F, params.lag_max + 1, dtype=torch.float32, device=dev) if want_table else None
+    # the kernel writes the table of frames f < F_b only: what lies behind a row's frames is NaN, not whatever the allocator held
+    table = torch.full((B, F, params.lag_max + 1), float("nan"), dtype=torch.float32, device=dev) if want_table else None
     _lib.check(lib.gvx_pitch_yin(x.data_ptr(), _ptr(sl), B, N, params, out["f0"].data_ptr(), out["lag"].data_ptr(),
                                  out["aperiodicity"].data_ptr(), _ptr(table), _stream(dev)))
     n = sl.clamp(0, N) if sl is not None else torch.full((B,), N, dtype=torch.int32, device=dev)

@@ -941,7 +941,7 @@ int gvx_psola_synth(const float* wav, const int32_t* sample_lengths, const int32
                     const int32_t* syn_pos, const int32_t* syn_src, const int32_t* counts, const int32_t* row_status, int B, long N,
                     const gvx_psola_params* params, float* wav_out, void* stream);
 
-/* ---- Neural vocoder: MelGAN generator inference, mel -> waveform.  The reference promises a vocoder model and ships only its config
+/* ---- Neural vocoder: MelGAN generator, mel -> waveform: inference, and training (behind the inference calls).  The reference promises a vocoder model and ships only its config
  * (configs/models.py:89-121, MelGANConfig); the network below is this project's statement of the MelGAN generator.
  *
  * Input: mel fp32 [B][n_mels][T], as the Tacotron2 calls deliver mel_outputs_postnet (no conversion).  Output: wav fp32 [B][T * hop],
@@ -1014,6 +1014,58 @@ int gvx_melgan_forward(gvx_melgan* handle, const float* mel, const int32_t* fram
                        float* const* stage_out, void* workspace, size_t workspace_bytes, void* stream);
 int gvx_melgan_timing_enable(gvx_melgan* handle, int enable);
 int gvx_melgan_stage_times_ms(gvx_melgan* handle, float* ms_out, int* n_out);
+
+/* Training the generator: a forward that keeps a tape, and the backward.  Model, layouts, raggedness and error conventions are those of
+ * gvx_melgan_forward above; all arithmetic is fp32.  Training is on plain weights (a weight-normalised checkpoint is folded on load).
+ *
+ * Tape: the caller's memory, 256-byte aligned, gvx_melgan_tape_bytes (host arithmetic) long.  It holds every tensor the backward reads,
+ * in forward order, which gvx_melgan_tape_layout (host arithmetic) lists as (byte offset, positions per frame, channels):
+ *     the transposed mel [round4(n_mels) channels];  x after the first convolution;
+ *     per stage: the transposed convolution's output, then per residual layer h and the new x.
+ * Each is fp32, RAW pre-activation values, channels-last [B][T * positions per frame][channels] with rows strided by the padded T, and
+ * starts where the one before it ends: the tape is 4 * B * T * F bytes with F = round4(n_mels) + C_0 + the sum over the stages of
+ * (1 + 2 * n_residual_layers) * ratios[0] * .. * ratios[i] * C_{i+1} floats per frame and row.  With the defaults F = 80 + 512 +
+ * 7 * (2048 + 3 * 8192) = 186,960 floats, 747,840 bytes per frame and row.  Linear in B and in T.  Behind a row's own length the tape
+ * holds whatever it held before: the backward reads nothing there.  The layout call returns the number of entries
+ * (2 + n_stages * (1 + 2 * n_residual_layers)) and fills at most max_entries of them (entries may be NULL); both return 0 for refused
+ * dims, B outside [1, 65535] or T outside [GVX_MELGAN_MIN_FRAMES, GVX_MELGAN_MAX_FRAMES].
+ *
+ * gvx_melgan_forward_train is the forward with every layer writing into its own tape slot - the same kernels with the same arguments, so
+ * wav_out has the bits of gvx_melgan_forward.  It needs no scratch: workspace may be NULL and workspace_bytes 0.
+ *
+ * gvx_melgan_backward: d_wav fp32 [B][T * hop], never read at or behind sample T_b * hop.  grads is a HOST table that names DEVICE
+ * destinations under the packer's names; every parameter gradient is WRITTEN (not accumulated) in PyTorch's own layout: Conv1d
+ * [out][in][k] (the first convolution without padded channels), ConvTranspose1d [in][out][2 r], shortcut and mix as two tensors.
+ * d_mel_out is NULL (the first layer's data gradient is skipped; no parameter gradient changes a bit) or fp32 [B][n_mels][T], exactly 0
+ * at and behind a row's frames; row b of it has the bits of that row run alone.  Refused before anything is launched: a missing name
+ * (GVX_ERR_MISSING_WEIGHT), a wrong element count or NULL destination (GVX_ERR_SHAPE), a NULL, short or misaligned tape or workspace
+ * (GVX_ERR_WORKSPACE), T or B as the forward refuses them, B * T * hop above 65535 * 512 positions (GVX_ERR_UNSUPPORTED).
+ * gvx_melgan_backward_workspace_bytes is host arithmetic: any contents when the call starts, nothing is cleared; it holds the transposed
+ * weights (made from the bound blob at the start of every call, so never stale), the gradient of two activation tensors and of one
+ * residual tail, and the partial products of the widest weight gradient.
+ *
+ * The backward is a chain of ordinary launches.  Data gradients are implicit GEMMs that gather dY on the way into LDS (the reflections
+ * and the stride of the forward, transposed), on v_mfma_f32_32x32x2_f32 where the layer has 32 channels or more and fmaf dot products
+ * below; weight and bias gradients are reduced over all rows' positions in pieces of 512 positions, whose partial products are added in
+ * a fixed order.  No float atomics: two calls give the same bits. */
+typedef struct gvx_melgan_tape_entry {
+    uint64_t byte_offset;
+    int32_t positions_per_frame;
+    int32_t channels;
+} gvx_melgan_tape_entry;
+typedef struct gvx_grad_desc {
+    const char* name;   /* a parameter's name, as gvx_melgan_pack_weights_device reads it */
+    float* data;        /* DEVICE pointer that receives the gradient */
+    int64_t numel;
+} gvx_grad_desc;
+size_t gvx_melgan_tape_bytes(const gvx_melgan_dims* dims, int B, int T);
+int gvx_melgan_tape_layout(const gvx_melgan_dims* dims, int B, int T, gvx_melgan_tape_entry* entries, int max_entries);
+size_t gvx_melgan_backward_workspace_bytes(const gvx_melgan_dims* dims, int B, int T);
+int gvx_melgan_forward_train(gvx_melgan* handle, const float* mel, const int32_t* frame_lengths, int B, int T, float* wav_out, void* tape,
+                             size_t tape_bytes, void* workspace, size_t workspace_bytes, void* stream);
+int gvx_melgan_backward(gvx_melgan* handle, const float* d_wav, const int32_t* frame_lengths, int B, int T, const void* tape,
+                        size_t tape_bytes, const gvx_grad_desc* grads, int n_grads, float* d_mel_out, void* workspace,
+                        size_t workspace_bytes, void* stream);
 
 /* ---- Per-kernel timing of the decoder step (measurement only): when enabled, a teacher-forced call replays the
  * mid-sequence LSTM-step launch and the attention launches 64 times each, back to back, between HIP events on

@@ -1,0 +1,199 @@
+"""GPU: gvx_melgan_forward_train and gvx_melgan_backward (csrc/melgan_train.hip) through the C ABI against float64 autograd of the
+restatement in tests/melgan_grad_ref64.py: every tape tensor, every parameter gradient and d_mel, tensor by tensor.  The tape, the
+workspace and every output start as NaN; tape and workspace have exactly their stated sizes.
+
+Tolerance.  Per gradient tensor, e is the largest |float32 restatement - float64| (a number of the reference alone; e / max|g64| lies
+between 1e-7 and 2e-6 on the CPU for these cases); the device may differ from float64 by at most 8 x max(e, 2^-23 max|g64|), the
+second term being one ulp of the tensor's scale - a floor for one-element tensors such as post.bias.  Tape tensors follow the forward
+tests' 8 x rule.
+
+LeakyReLU ties.  Tie-free cases assert on the CPU that no float64 pre-activation lies within 8 x its tensor's float32 error of 0 (the
+mel seed is the first of 1..8 for which that holds; none: the case fails) and compare with plain autograd.  Pinned cases (the default
+sizes, and the long rows of the split-piece cases) read the LeakyReLU decisions from the device's own tape, assert that every decision
+that differs from float64's is a true near-tie, and compare with the restatement pinned to those decisions.
+
+Pieces.  The weight and bias gradients reduce over the positions of all rows laid end to end, B * T * mul of them for a layer at
+`mul` positions per frame, in pieces of MGB_PIECE = 512 positions.  test_split_pieces picks B * T = 512, 513 and 1030 for the layers
+at mul = 1 - exactly one piece, one piece plus one position, two pieces plus a tail of 6 - which are, per weight-gradient kernel:
+mgb_wgrad_valu_kernel NARROW's ups.0 (16 output channels), mgb_wgrad_mfma_kernel<1> NARROW's pre (32), mgb_wgrad_mfma_kernel<2>
+SHALLOW's pre and ups.0 (128 and 64), mgb_colsum_kernel every bias of those; the layers at mul = 4 and 8 run 4 to 17 pieces with and
+without a tail in the same calls."""
+import functools
+
+import pytest
+import torch
+
+from tests import melgan_grad_ref64 as GR
+from tests import melgan_ref64 as R
+from tests.melgan_train_helpers import DEV, NAN, TrainNet, compare_grads, compare_tape, poisoned
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _release_cached_blocks():
+    """The NaN-filled tapes and workspaces of this module go back to the driver, not into the allocator's cache for later modules."""
+    yield
+    torch.cuda.empty_cache()
+
+CFGS = dict(NARROW=R.NARROW, SHALLOW=R.SHALLOW, TWO_DEEP=R.TWO_DEEP, DEFAULT=R.DEFAULT,
+            WIDE=dict(R.SHALLOW, base_channels=512),      # channels 256 and 128: the 128-wide tile of the data gradients
+            DEFAULT_LINEAR=dict(R.DEFAULT, slope=1.0))    # no kinks: the same kernels against plain autograd at the default sizes
+
+
+@functools.lru_cache(maxsize=None)
+def _net(name):
+    cfg = CFGS[name]
+    sd = R.random_state(cfg, seed=11)
+    return cfg, sd, TrainNet(cfg, sd)
+
+
+def _cotangent(cfg, B, T):
+    g = torch.Generator().manual_seed(1000 * B + T)
+    return torch.randn(B, T * R.hop(cfg), generator=g, dtype=torch.float64)
+
+
+@functools.lru_cache(maxsize=None)
+def _tie_free(name, B, T, lens):
+    """(mel, G, reference) of a case without near-ties: computed once, shared by the tests, never changed."""
+    cfg, sd, _ = _net(name)
+    seed, mel, G, ref = GR.tie_free_case(sd, cfg, B, T, lens, G_seed=1000 * B + T)
+    assert GR.near_ties(ref, lens) == 0
+    print(f"{name} {B} x {T} {lens}: mel seed {seed} is tie-free")
+    return mel, G, ref
+
+
+def _device_run(name, mel, G, lens, want_mel=True):
+    cfg, _, net = _net(name)
+    B, _, T = mel.shape
+    mel_d, G_d = poisoned(mel, G, lens, R.hop(cfg))
+    lens_d = None if lens is None else torch.tensor(lens, dtype=torch.int32, device=DEV)
+    wav, tape = net.forward_train(mel_d, lens_d)
+    plain = net.forward(mel_d, lens_d)
+    grads = net.backward(G_d, lens_d, B, T, tape, want_mel)
+    assert torch.equal(wav, plain), "forward_train's waveform is not gvx_melgan_forward's, bit for bit"
+    return wav, tape, grads
+
+
+def _check_tie_free(name, B, T, lens=None):
+    _, _, net = _net(name)
+    mel, G, ref = _tie_free(name, B, T, lens)
+    wav, tape, grads = _device_run(name, mel, G, lens)
+    what = f"{name} {B} x {T}" + (f" lengths {lens}" if lens else "")
+    compare_tape(net.tape_views(tape, B, T), ref, lens, what)
+    compare_grads(grads, ref, what)
+    return mel, G, ref, tape, grads
+
+
+def _check_pinned(name, B, T, mel_seed=1):
+    """The reference is pinned to the device's own LeakyReLU decisions, after asserting that each one that differs from float64's
+    is a true near-tie."""
+    cfg, sd, net = _net(name)
+    mel, G = R.random_mel(cfg, B, T, mel_seed), _cotangent(cfg, B, T)
+    wav, tape, grads = _device_run(name, mel, G, None)
+    views = [v.cpu() for v in net.tape_views(tape, B, T)]
+    free = GR.reference(sd, mel, None, cfg, G)   # float64's own decisions
+    flips = 0
+    for i in range(1, len(views)):
+        differ = (views[i] > 0) != (free["tape"][i] > 0)
+        flips += int(differ.sum())
+        assert (free["tape"][i][differ].abs() <= GR.FACTOR * free["tape_err"][i]).all(), f"tape tensor {i}: a sign differs from float64 away from 0"
+    ref = GR.reference(sd, mel, None, cfg, G, GR.masks_from_tape(views, cfg["slope"]))
+    what = f"{name} {B} x {T} pinned ({GR.near_ties(free)} near-ties, {flips} decided the other way)"
+    compare_tape(views, ref, None, what)
+    compare_grads(grads, ref, what)
+
+
+@pytest.mark.parametrize("name,B,T", [("NARROW", 2, 4), ("NARROW", 2, 7), ("SHALLOW", 2, 5), ("TWO_DEEP", 1, 4), ("TWO_DEEP", 2, 17), ("WIDE", 2, 4)])
+def test_gradients_tie_free(name, B, T):
+    """NARROW: fmaf layers, K = 70 in the first convolution; at T = 4 both reflections of the dilation-9 layer fold onto the same
+    positions of a 16-position row.  TWO_DEEP 2 x 17: lengths 68 and 136 cross a 128-position tile.  WIDE: the 128-wide tile."""
+    _check_tie_free(name, B, T)
+
+
+@pytest.mark.parametrize("T", [4, 5])
+def test_gradients_default_sizes_pinned(T):
+    _check_pinned("DEFAULT", 1, T)
+
+
+def test_gradients_default_sizes_without_kinks():
+    """slope = 1: LeakyReLU is the identity, so plain float64 autograd is the reference at the default sizes, with no tape reading."""
+    name, B, T = "DEFAULT_LINEAR", 1, 4
+    cfg, sd, net = _net(name)
+    mel, G = R.random_mel(cfg, B, T, 1), _cotangent(cfg, B, T)
+    ref = GR.reference(sd, mel, None, cfg, G)
+    wav, tape, grads = _device_run(name, mel, G, None)
+    compare_tape(net.tape_views(tape, B, T), ref, None, name)
+    compare_grads(grads, ref, name)
+
+
+@pytest.mark.parametrize("name,T", [("NARROW", 512), ("NARROW", 513), ("NARROW", 1030), ("SHALLOW", 512), ("SHALLOW", 513), ("SHALLOW", 1030)])
+def test_split_pieces(name, T):
+    """Reduction lengths of one piece, one piece plus one position, two pieces plus a tail, for every weight-gradient kernel (the
+    module docstring names the layers)."""
+    _check_pinned(name, 1, T)
+
+
+@pytest.mark.parametrize("name,T,lens", [("NARROW", 9, (4, 9, 5)), ("TWO_DEEP", 17, (4, 17, 8))])
+def test_ragged_rows(name, T, lens):
+    """NaN in mel at and behind each length and in d_wav at and behind T_b * hop.  Parameter gradients equal the float64 sum of the
+    rows run alone (that is what the reference computes); d_mel of every row is bit-equal to that row run alone and exactly 0 behind
+    its length.  TWO_DEEP: the 4-frame row has 32 positions at the last stage and leaves the second 128-position tile empty."""
+    cfg, _, net = _net(name)
+    mel, G, ref, tape, grads = _check_tie_free(name, len(lens), T, lens)
+    hop = R.hop(cfg)
+    for b, t in enumerate(lens):
+        assert not grads["mel"][b, :, t:].any(), f"row {b}: d_mel is not 0 behind its {t} frames"
+        mel_d, G_d = poisoned(mel[b:b + 1, :, :t].contiguous(), G[b:b + 1, :t * hop].contiguous(), None, hop)
+        _, tape_b = net.forward_train(mel_d)
+        alone = net.backward(G_d, None, 1, t, tape_b)
+        assert torch.equal(alone["mel"][0], grads["mel"][b, :, :t]), f"row {b}: d_mel differs from that row run alone"
+
+
+def test_determinism_null_d_mel_and_dirty_workspace():
+    """Two backward calls give the same bits; d_mel_out = NULL changes no bit of a parameter gradient; the workspace is exactly
+    gvx_melgan_backward_workspace_bytes with a NaN guard behind it that stays NaN, and a reused (dirty) one gives the same bits."""
+    name, B, T, lens = "TWO_DEEP", 3, 17, (4, 17, 8)
+    cfg, _, net = _net(name)
+    mel, G, _ = _tie_free(name, B, T, lens)
+    mel_d, G_d = poisoned(mel, G, lens, R.hop(cfg))
+    lens_d = torch.tensor(lens, dtype=torch.int32, device=DEV)
+    _, tape = net.forward_train(mel_d, lens_d)
+    first = net.backward(G_d, lens_d, B, T, tape)
+    again = net.backward(G_d, lens_d, B, T, tape)
+    without = net.backward(G_d, lens_d, B, T, tape, want_mel=False)
+    for k in first:
+        assert torch.equal(first[k], again[k]), k
+        assert k == "mel" or torch.equal(first[k], without[k]), k
+    need = net.ws_bytes(B, T)
+    assert need % 256 == 0 and net.tape_bytes(B, T) == tape.numel() * 4
+    buf = torch.full(((need + 4096) // 4,), NAN, dtype=torch.float32, device=DEV)
+    for _ in range(2):   # the second call finds the first one's leftovers
+        grads = net.new_grads(True, B, T)
+        assert net.backward_rc(G_d, lens_d, B, T, tape, tape.numel() * 4, grads, buf, need) == 0
+        torch.cuda.synchronize()
+        assert torch.isnan(buf[need // 4:]).all(), "the call wrote behind the workspace"
+        assert all(torch.equal(first[k], grads[k]) for k in first)
+
+
+def test_refusals_happen_before_any_launch():
+    """A short tape, a short workspace, a missing name, a wrong element count: each returns its code and leaves every output NaN."""
+    name, B, T = "NARROW", 2, 7
+    cfg, _, net = _net(name)
+    mel, G, _ = _tie_free(name, B, T, None)
+    mel_d, G_d = poisoned(mel, G, None, R.hop(cfg))
+    _, tape = net.forward_train(mel_d)
+    tb, wb = tape.numel() * 4, net.ws_bytes(B, T)
+    ws = torch.full((wb // 4,), NAN, dtype=torch.float32, device=DEV)
+    wav = torch.full((B, T * R.hop(cfg)), NAN, dtype=torch.float32, device=DEV)
+    scratch = torch.full_like(tape, NAN)
+    assert net.forward_train_rc(mel_d, None, wav, scratch, tb - 1) == -5                      # GVX_ERR_WORKSPACE
+    torch.cuda.synchronize()
+    assert torch.isnan(wav).all() and torch.isnan(scratch).all()
+    for want, kw, tbytes, wbytes in ((-5, {}, tb - 1, wb), (-5, {}, tb, wb - 1), (-3, dict(skip=("res.1.2.mix.bias",)), tb, wb),
+                                     (-4, dict(numel={"ups.0.weight": 7}), tb, wb)):          # -3 GVX_ERR_MISSING_WEIGHT, -4 GVX_ERR_SHAPE
+        grads = net.new_grads(True, B, T)
+        assert net.backward_rc(G_d, None, B, T, tape, tbytes, grads, ws, wbytes, **kw) == want, (want, kw)
+        torch.cuda.synchronize()
+        assert all(torch.isnan(g).all() for g in grads.values()) and torch.isnan(ws).all()
+    assert net.backward_rc(G_d, None, B, T, tape.view(torch.uint8)[1:], tb - 1, net.new_grads(True, B, T), ws, wb) == -5   # misaligned

@@ -9,7 +9,9 @@ batch delivered at the model's rate;
 1000 x 1000 and 800 x 800 frames of 13 cepstra (and 1000 x 1000 of 80 features, the form without LDS tables), gvx_alignment_stats
 on 32 x 1000 x 128 - and the Python entry points around them by the host clock;
 `melgan` (on request): the MelGAN generator at 1 x 568 and 32 x 800 frames between device events, with the time per stage, against the
-same float32 network through torch's own ROCm convolutions and against Griffin-Lim (32 iterations) on the same mels."""
+same float32 network through torch's own ROCm convolutions and against Griffin-Lim (32 iterations) on the same mels;
+`melgan_train` (on request): `vocode_with_grad` + `backward()` (gvx_melgan_forward_train + gvx_melgan_backward) at 16 x 32 and 8 x 128
+frames between device events, against autograd through torch's own convolutions on the same parameters, with the tape's size."""
 import json
 import os
 import sys
@@ -261,11 +263,14 @@ def main():
         r["gb_per_s"] = round(a.numel() * 4 / 1e9 / (r["median_ms"] * 1e-3), 1)
         res[f"gvx_alignment_stats_b{B}_{T}x{L}"] = r
         res[f"alignment_stats_python_b{B}_{T}x{L}"] = host_runs(lambda: metrics.alignment_stats(a))
-    if "melgan" in which:
+    if which & {"melgan", "melgan_train"}:
         import statistics
 
         import torch.nn.functional as F
 
+        import ctypes as C
+
+        from genvox_amd import _lib
         from genvox_amd.configs import MelGANConfig
         from genvox_amd.melgan import MelGANGenerator
 
@@ -302,7 +307,7 @@ def main():
 
         ap = AudioProcessor(ac, device="cuda:0")
         gen = torch.Generator(device="cuda").manual_seed(0)
-        for B, T in ((1, 568), (32, 800)):
+        for B, T in ((1, 568), (32, 800)) if "melgan" in which else ():
             key = f"melgan_{B}x{T}"
             mel = (0.5 * torch.randn(B, 80, T, device="cuda", generator=gen) - 0.5).contiguous()
             res[key] = {"as_delivered": ev_runs(lambda: voc.vocode(mel)), "rows_per_call_as_delivered": None}
@@ -327,6 +332,32 @@ def main():
                 res[key]["torch_convolutions"] = ev_runs(lambda: torch_net(mel), warm=2, reps=5)
                 res[key]["max_abs_difference_from_torch"] = float((torch_net(mel) - wav).abs().max())
             print(json.dumps({key: res[key]["torch_convolutions"]}), flush=True)
+        for B, T in ((16, 32), (8, 128)) if "melgan_train" in which else ():   # a training segment; a longer one
+            key = f"melgan_train_{B}x{T}"
+            mel = (0.5 * torch.randn(B, 80, T, device="cuda", generator=gen) - 0.5).contiguous()
+            cot = torch.randn(B, T * voc.hop, device="cuda", generator=gen)
+            params = list(voc.parameters())
+
+            def ours():
+                for p in params:
+                    p.grad = None
+                (voc.vocode_with_grad(mel) * cot).sum().backward()
+
+            def torchs():   # autograd through torch's own convolutions, the same parameters
+                for p in params:
+                    p.grad = None
+                (torch_net(mel) * cot).sum().backward()
+
+            res[key] = {"forward_train_plus_backward": ev_runs(ours, warm=2, reps=7),
+                        "tape_mb": round(_lib.load().gvx_melgan_tape_bytes(C.byref(voc.dims()), B, T) / 1e6, 1),
+                        "backward_workspace_mb": round(_lib.load().gvx_melgan_backward_workspace_bytes(C.byref(voc.dims()), B, T) / 1e6, 1)}
+            got = {k: p.grad.clone() for k, p in voc.named_parameters()}
+            sd = dict(voc.named_parameters())   # torch_net reads sd: now the parameters themselves, so autograd reaches them
+            res[key]["torch_autograd"] = ev_runs(torchs, warm=2, reps=5)
+            res[key]["max_relative_gradient_difference_from_torch"] = max(
+                float((got[k] - p.grad).abs().max() / p.grad.abs().max().clamp_min(1e-30)) for k, p in voc.named_parameters())
+            sd = {k: v.detach() for k, v in voc.state_dict().items()}
+            print(json.dumps({key: res[key]}), flush=True)
     if "cpu" in which:
         # CPU baselines for configs 3 and 4 (the oracle = CPU restatement of the reference, on this box's host cores):
         # bounded samples, reported beside the GPU figures above; bench.py carries the one for config 2.
