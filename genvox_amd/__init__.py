@@ -3,6 +3,7 @@
     from genvox_amd import Tacotron2, Synthesizer, AudioProcessor, Tacotron2Config, AudioConfig, TextConfig
     from genvox_amd import MelGANGenerator, MelGANConfig   # neural vocoder: Synthesizer(..., vocoder_model_class=MelGANGenerator, ...)
     from genvox_amd import Tacotron2GuidedLoss    # training criterion: Tacotron2Loss + alpha x guided attention loss
+    from genvox_amd import MultiResolutionSTFTLoss, stft_distance   # vocoder training loss / waveform distance on the device
 """
 from .configs import AudioConfig, BaseConfig, MelGANConfig, Tacotron2Config, TextConfig  # noqa: F401
 
@@ -17,6 +18,12 @@ def __getattr__(name):  # torch-dependent classes are imported lazily
     if name == "MelGANGenerator":
         from .melgan import MelGANGenerator
         return MelGANGenerator
+    if name == "MultiResolutionSTFTLoss":
+        from .losses import MultiResolutionSTFTLoss
+        return MultiResolutionSTFTLoss
+    if name == "stft_distance":
+        from .metrics import stft_distance
+        return stft_distance
     if name == "Synthesizer":
         from .synthesizer import Synthesizer
         return Synthesizer

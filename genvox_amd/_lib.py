@@ -37,6 +37,14 @@ class gvx_melgan_tape_entry(C.Structure):
     _fields_ = [("byte_offset", C.c_uint64), ("positions_per_frame", C.c_int32), ("channels", C.c_int32)]
 
 
+class gvx_stft_resolution(C.Structure):
+    _fields_ = [("n_fft", C.c_int32), ("hop", C.c_int32), ("win_length", C.c_int32)]
+
+
+class gvx_stft_loss_debug(C.Structure):
+    _fields_ = [("mag_pred", C.c_void_p * 8), ("mag_target", C.c_void_p * 8)]
+
+
 class gvx_pitch_params(C.Structure):
     _fields_ = [("sampling_rate", C.c_int32), ("hop", C.c_int32), ("window", C.c_int32), ("lag_min", C.c_int32), ("lag_max", C.c_int32),
                 ("threshold", C.c_float), ("first_centre", C.c_int32)]
@@ -168,6 +176,10 @@ SIGNATURES = {
     "gvx_melgan_backward_workspace_bytes": (_sz, [C.POINTER(gvx_melgan_dims), _i, _i]),
     "gvx_melgan_forward_train": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _sz, _vp, _sz, _vp]),
     "gvx_melgan_backward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, C.POINTER(gvx_weight_desc), _i, _vp, _vp, _sz, _vp]),
+    "gvx_stft_loss_create": (_i, [C.POINTER(gvx_stft_resolution), _i, _f, _f, _f, C.POINTER(_vp)]),
+    "gvx_stft_loss_destroy": (None, [_vp]),
+    "gvx_stft_loss_workspace_bytes": (_sz, [_vp, _i, _l]),
+    "gvx_stft_loss": (_i, [_vp, _vp, _vp, _vp, _i, _l, _vp, _vp, _vp, C.POINTER(gvx_stft_loss_debug), _vp, _sz, _vp]),
     "gvx_kernel_timing_enable": (_i, [_vp, _i]),
     "gvx_model_set_persistent_attention": (_i, [_vp, _i]),
     "gvx_model_set_resident_kernels": (_i, [_vp, _i]),

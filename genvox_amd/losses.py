@@ -1,0 +1,156 @@
+"""Training losses for the neural vocoder, on the device.
+
+MultiResolutionSTFTLoss is the non-adversarial objective a waveform generator is trained on - spectral convergence plus log-magnitude
+L1 over several STFT resolutions - as one call of gvx_stft_loss (definition in include/genvox_amd.h, restatement in
+tests/stft_loss_ref64.py) that returns the value and, when pred asks for it, the gradient:
+
+    criterion = MultiResolutionSTFTLoss()
+    loss = criterion(vocoder.vocode_with_grad(mel, mel_lengths), recording, sample_lengths)
+    loss.backward()
+
+The norms and means are per row (a row's numbers never depend on the rows beside it), not over the batch as Parallel WaveGAN has them.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional, Sequence, Tuple
+
+import torch
+
+from . import _lib
+
+DEFAULT_RESOLUTIONS: Tuple[Tuple[int, int, int], ...] = ((1024, 120, 600), (2048, 240, 1200), (512, 50, 240))   # Parallel WaveGAN's
+SUPPORTED_N_FFT = (512, 1024, 2048)
+MAX_RESOLUTIONS = 8
+
+
+def check_resolutions(resolutions: Sequence[Sequence[int]]) -> Tuple[Tuple[int, int, int], ...]:
+    res = tuple(tuple(int(v) for v in r) for r in resolutions)
+    if not 1 <= len(res) <= MAX_RESOLUTIONS:
+        raise ValueError(f"{len(res)} resolutions: 1 .. {MAX_RESOLUTIONS} are supported")
+    for r in res:
+        if len(r) != 3:
+            raise ValueError(f"a resolution is (n_fft, hop, win_length), got {r}")
+        n_fft, hop, win_length = r
+        if n_fft not in SUPPORTED_N_FFT:
+            raise ValueError(f"n_fft = {n_fft}: supported are {SUPPORTED_N_FFT}")
+        if not 1 <= hop <= n_fft or not 2 <= win_length <= n_fft:
+            raise ValueError(f"resolution {r}: 1 <= hop <= n_fft and 2 <= win_length <= n_fft are required")
+    return res
+
+
+class _STFTLossFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target, lens_dev, module, want_grad):
+        loss, parts, d_pred = module._call(pred, target, lens_dev, want_grad)
+        module.last_parts = parts
+        ctx.d_pred = d_pred
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        if ctx.d_pred is None:
+            raise RuntimeError("MultiResolutionSTFTLoss: no gradient was kept for this call")
+        return grad_output * ctx.d_pred, None, None, None, None
+
+
+class MultiResolutionSTFTLoss(torch.nn.Module):
+    """loss = mean over rows and resolutions of (w_sc * spectral convergence + w_mag * log-magnitude L1).  No parameters.
+
+    forward(pred, target, sample_lengths=None): float32 [B, n_max] device tensors; returns a 0-d float32 device tensor.  `last_parts`
+    holds [B, R, 2] = (spectral convergence, log magnitude) of the last call.  target gets no gradient."""
+
+    def __init__(self, resolutions: Sequence[Sequence[int]] = DEFAULT_RESOLUTIONS, w_sc: float = 1.0, w_mag: float = 1.0, eps: float = 1e-7):
+        super().__init__()
+        self.resolutions = check_resolutions(resolutions)
+        if not (w_sc >= 0.0 and w_mag >= 0.0) or w_sc == float("inf") or w_mag == float("inf"):
+            raise ValueError("w_sc and w_mag must be finite and >= 0")
+        if not 0.0 < eps < float("inf"):
+            raise ValueError("eps must be finite and > 0")
+        self.w_sc, self.w_mag, self.eps = float(w_sc), float(w_mag), float(eps)
+        self.min_samples = max(r[0] for r in self.resolutions) // 2 + 1
+        self.last_parts: Optional[torch.Tensor] = None
+        self._handle = None
+        self._workspace: Optional[torch.Tensor] = None
+
+    def __del__(self):
+        try:
+            if self._handle is not None:
+                _lib.load().gvx_stft_loss_destroy(self._handle)
+        except Exception:
+            pass
+
+    def __getstate__(self):   # a copy makes its own plan: the handle is destroyed once, by its owner
+        state = dict(self.__dict__)
+        state.update(_handle=None, _workspace=None, last_parts=None)
+        return state
+
+    # ---- checks, all before anything is launched
+    def _require_gpu(self, pred: torch.Tensor) -> torch.device:
+        if pred.device.type != "cuda":
+            raise RuntimeError("genvox_amd.MultiResolutionSTFTLoss runs on an MI355X only: pass tensors on 'cuda:0'. There is no CPU fallback.")
+        return pred.device
+
+    def _check(self, pred, target, sample_lengths):
+        if not isinstance(pred, torch.Tensor) or not isinstance(target, torch.Tensor):
+            raise ValueError("pred and target must be tensors")
+        if pred.dim() != 2 or pred.shape != target.shape:
+            raise ValueError(f"pred and target must both be [B, n_max], got {tuple(pred.shape)} and {tuple(target.shape)}")
+        if pred.dtype != torch.float32 or target.dtype != torch.float32:
+            raise ValueError(f"pred and target must be float32, got {pred.dtype} and {target.dtype}")
+        B, n_max = pred.shape
+        if B < 1 or n_max < self.min_samples:
+            raise ValueError(f"a row needs at least n_fft / 2 + 1 = {self.min_samples} samples for the reflection, got [B, n_max] = [{B}, {n_max}]")
+        host = None
+        on_device = isinstance(sample_lengths, torch.Tensor) and sample_lengths.device.type == "cuda"
+        if sample_lengths is not None and not on_device:   # lengths the host has: refused here, with the row named
+            host = [int(v) for v in (sample_lengths.tolist() if isinstance(sample_lengths, torch.Tensor) else sample_lengths)]
+            if len(host) != B:
+                raise ValueError(f"{len(host)} sample lengths for a batch of {B} rows")
+            for b, n in enumerate(host):
+                if not self.min_samples <= n <= n_max:
+                    raise ValueError(f"row {b} has {n} samples: outside [{self.min_samples}, n_max = {n_max}]")
+        elif on_device and sample_lengths.shape != (B,):
+            raise ValueError(f"sample lengths of shape {tuple(sample_lengths.shape)} for a batch of {B} rows")
+        dev = self._require_gpu(pred)
+        if target.device != dev:
+            raise ValueError(f"pred is on {dev}, target on {target.device}")
+        if sample_lengths is None:
+            return dev, None
+        if host is not None:
+            return dev, torch.tensor(host, dtype=torch.int32, device=dev)
+        return dev, sample_lengths.to(device=dev, dtype=torch.int32).contiguous()   # checked by the call itself (GvxError naming the row)
+
+    # ---- the call
+    def _plan(self):
+        if self._handle is None:
+            table = (_lib.gvx_stft_resolution * len(self.resolutions))(*[_lib.gvx_stft_resolution(*r) for r in self.resolutions])
+            h = C.c_void_p()
+            _lib.check(_lib.load().gvx_stft_loss_create(table, len(self.resolutions), self.w_sc, self.w_mag, self.eps, C.byref(h)))
+            self._handle = h.value
+        return self._handle
+
+    def _call(self, pred, target, lens_dev, want_grad):
+        lib = _lib.load()
+        dev = pred.device
+        B, n_max = pred.shape
+        with torch.cuda.device(dev):
+            plan = self._plan()
+            need = lib.gvx_stft_loss_workspace_bytes(plan, B, n_max)
+            if need == 0:
+                _lib.check(-1)
+            if self._workspace is None or self._workspace.device != dev or self._workspace.numel() < need:
+                self._workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+            pred, target = pred.detach().contiguous(), target.detach().contiguous()
+            loss = torch.empty((), dtype=torch.float32, device=dev)
+            parts = torch.empty(B, len(self.resolutions), 2, dtype=torch.float32, device=dev)
+            d_pred = torch.empty_like(pred) if want_grad else None
+            _lib.check(lib.gvx_stft_loss(plan, pred.data_ptr(), target.data_ptr(), None if lens_dev is None else lens_dev.data_ptr(), B, n_max,
+                                         loss.data_ptr(), parts.data_ptr(), None if d_pred is None else d_pred.data_ptr(), None,
+                                         self._workspace.data_ptr(), self._workspace.numel(), torch.cuda.current_stream(dev).cuda_stream))
+        return loss, parts, d_pred
+
+    def forward(self, pred: torch.Tensor, target: torch.Tensor, sample_lengths=None) -> torch.Tensor:
+        _, lens_dev = self._check(pred, target, sample_lengths)
+        want_grad = pred.requires_grad and torch.is_grad_enabled()
+        return _STFTLossFunction.apply(pred, target, lens_dev, self, want_grad)

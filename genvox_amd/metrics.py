@@ -4,9 +4,11 @@ rate control built on those frame counts - the plan and the token-wise time warp
 gvx_mel_project, gvx_dtw_distance, gvx_monotonic_align, gvx_duration_scale, gvx_mel_time_warp; definitions in include/genvox_amd.h,
 restatements in tests/metrics_ref64.py, tests/mas_ref.py and tests/warp_ref.py), the pitch tracker and the comparison of two contours
 (gvx_pitch_yin, gvx_f0_compare; tests/pitch_ref64.py) and the pitch control built on the tracker's contour - the plan and the
-overlap-add of a TD-PSOLA pitch shift (gvx_psola_plan, gvx_psola_synth; tests/psola_ref.py).
+overlap-add of a TD-PSOLA pitch shift (gvx_psola_plan, gvx_psola_synth; tests/psola_ref.py), and the multi-resolution STFT distance
+between two waveforms (gvx_stft_loss, forward only; tests/stft_loss_ref64.py).
 
-Every function takes and returns device tensors and enqueues on the current stream; none of them synchronises with the host.
+Every function takes and returns device tensors and enqueues on the current stream; none of them synchronises with the host
+(stft_distance with device-side sample lengths does: the call reads them back to refuse a row that is too short).
 """
 from __future__ import annotations
 
@@ -434,3 +436,22 @@ def mcd_db(dist: torch.Tensor, audio_config) -> torch.Tensor:
     (AudioConfig.log_func "np.log10") and 1 for natural-log mels."""
     s = math.log(10.0) if audio_config.log_func == "np.log10" else 1.0
     return dist * (10.0 / math.log(10.0) * math.sqrt(2.0) * s)
+
+
+_stft_criteria: Dict[tuple, object] = {}
+
+
+def stft_distance(wav_a: torch.Tensor, wav_b: torch.Tensor, sample_lengths=None, resolutions=None) -> Dict[str, torch.Tensor]:
+    """Multi-resolution STFT distance of wav_a [B, n_max] from the reference wav_b, per row at its own length: {"spectral_convergence":
+    [B], "log_magnitude": [B]}, each the mean over the resolutions (default: losses.DEFAULT_RESOLUTIONS) of the parts of
+    losses.MultiResolutionSTFTLoss - ||M_b - M_a||_F / ||M_b||_F and mean |log M_b - log M_a|.  Forward only."""
+    from .losses import DEFAULT_RESOLUTIONS, MultiResolutionSTFTLoss, check_resolutions
+
+    res = check_resolutions(DEFAULT_RESOLUTIONS if resolutions is None else resolutions)
+    crit = _stft_criteria.get(res)
+    if crit is None:
+        crit = _stft_criteria[res] = MultiResolutionSTFTLoss(res)
+    with torch.no_grad():
+        crit(wav_a, wav_b, sample_lengths)
+    parts = crit.last_parts.mean(dim=1)
+    return {"spectral_convergence": parts[:, 0], "log_magnitude": parts[:, 1]}

@@ -1067,6 +1067,75 @@ int gvx_melgan_backward(gvx_melgan* handle, const float* d_wav, const int32_t* f
                         size_t tape_bytes, const gvx_grad_desc* grads, int n_grads, float* d_mel_out, void* workspace,
                         size_t workspace_bytes, void* stream);
 
+/* ---- Multi-resolution STFT loss: the distance between a predicted waveform and its target that a vocoder is trained on (spectral
+ * convergence plus log-magnitude L1 over several STFT resolutions; Yamamoto et al., Parallel WaveGAN), value and gradient in one call.
+ * The reference ships no vocoder loss; this is the standard non-adversarial one, on the in-LDS transforms of the vocoder kernels.
+ *
+ * Inputs.  pred, target: fp32 [B][n_max].  sample_lengths: int32 [B] on the device or NULL; row b has n_b = sample_lengths[b] samples
+ * (n_max without it).  Resolutions r = 0 .. R - 1, each (n_fft, hop, win_length) with 1 <= R <= 8, n_fft in {512, 1024, 2048},
+ * 1 <= hop <= n_fft, 2 <= win_length <= n_fft.  Weights w_sc and w_mag, and eps (1e-7 where Parallel WaveGAN's numbers are wanted).
+ *
+ * Per row b and resolution r - torch.stft with center=True and pad_mode="reflect" of the row cut at its own length:
+ *   - F = 1 + n_b / hop frames (integer division); frame t holds the padded samples p = t * hop + k, k in [0, n_fft);
+ *   - the source index of p is i = p - n_fft / 2; for i < 0 it is -i, for i >= n_b it is 2 (n_b - 1) - i.  So a row needs
+ *     n_b >= n_fft / 2 + 1 for the largest n_fft among the resolutions;
+ *   - the window is the periodic Hann 0.5 - 0.5 cos(2 pi k / win_length), centred in the frame at offset (n_fft - win_length) / 2 and
+ *     zero outside, computed in double on the host;
+ *   - bins 0 .. n_fft / 2; magnitude M = sqrt(max(re^2 + im^2, eps));
+ *   - sc[b][r] = ||M_t - M_p||_F / ||M_t||_F over the row's own F frames and all bins;
+ *   - mag[b][r] = the mean of |log M_t - log M_p| over the same frames and bins;
+ *   loss = (1 / (B R)) sum_b sum_r (w_sc sc[b][r] + w_mag mag[b][r]).
+ * The norms and the means are PER ROW, not over the batch as Parallel WaveGAN takes them: a batch-wide norm would make a row's numbers
+ * depend on its neighbours, and the ragged contract of this library is that a row's parts - and its gradient, up to the factor
+ * 1 / (B R) that the loss itself carries - are the bits of that row run alone, whatever the other rows and n_max are.
+ *
+ * Gradient with respect to pred (target gets none): the derivative of the above for d loss = 1.  d sqrt(max(P, eps)) is 0 where P < eps;
+ * d|u| at u == 0 is 0 (the sign is taken from M_t against M_p, the logarithm being monotone); the spectral-convergence term passes no
+ * gradient where ||M_t - M_p||_F == 0 (torch's subgradient of a norm at 0).  d_pred is exact zeros at and behind n_b, and whatever lies
+ * at and behind n_b in pred or target is never read.  So pred == target gives loss 0 and an all-zero gradient, and an all-zero pred a
+ * finite loss and an all-zero gradient.
+ *
+ * gvx_stft_loss_create makes the window and twiddle tables in double on the host: an n_fft outside the three sizes is
+ * GVX_ERR_UNSUPPORTED, any other value out of range GVX_ERR_INVALID_ARG.  gvx_stft_loss_workspace_bytes is host arithmetic (0 for a
+ * NULL plan, B outside [1, GVX_STFT_LOSS_MAX_ROWS] or n_max outside [1, GVX_STFT_LOSS_MAX_SAMPLES]); the workspace follows the
+ * conventions above: any contents, 256-byte aligned, nothing cleared.  It holds, per resolution, pred's spectrum, target's magnitudes,
+ * the frame gradients and the partial sums - linear in B and in the frames of a row of n_max samples.
+ *
+ * The call: loss_out [1]; parts_out [B][R][2] = (sc, mag), may be NULL; d_pred [B][n_max], or NULL for the value alone (same loss
+ * bits, no spectrum kept); dbg NULL, or for tests device pointers per resolution that receive M_p and M_t as
+ * [B][1 + n_max / hop][n_fft / 2 + 1], NaN behind a row's frames (either pointer of a resolution may be NULL).  Refused before
+ * anything is launched: NULL arguments and bad B or n_max (GVX_ERR_INVALID_ARG), n_max below n_fft_max / 2 + 1 (GVX_ERR_SHAPE), a
+ * NULL, short or misaligned workspace (GVX_ERR_WORKSPACE).  With sample_lengths the rows' lengths are only known on the device: a row
+ * with n_b outside [n_fft_max / 2 + 1, n_max] has no frames for the kernels - nothing of it is read, its parts and the loss are NaN -
+ * and the call reads the lengths back behind its launches (so with sample_lengths it waits for the stream, once, while the kernels
+ * run), zeroes all of d_pred and returns GVX_ERR_SHAPE naming the first such row.  Without sample_lengths the call enqueues and
+ * returns.
+ *
+ * Kernels (all fp32 but the last sums): per resolution one launch transforms both signals, a frame per wave and
+ * GVX_STFT_LOSS_FRAMES_PER_WORKGROUP frames per workgroup, as a complex transform of n_fft / 2 points in LDS plus the even/odd split,
+ * with the samples gathered through the reflection (no padded copy of the batch exists), and leaves the three sums of its workgroup;
+ * one small launch adds the partial sums of every (row, resolution) in a fixed order, in float64; per resolution one launch makes
+ * dL/dX = (dL/dM_p) X / M_p from the kept spectrum and applies the adjoint of the real transform (not 1 / n times the inverse: the
+ * interior bins count once) and the window; one launch gathers, a thread per sample and GVX_STFT_LOSS_GATHER_SAMPLES per workgroup,
+ * the frames that cover the sample and its two reflected images, in ascending frame order, the resolutions in their order.  No
+ * atomics: two calls give the same bits. */
+enum { GVX_STFT_LOSS_MAX_RESOLUTIONS = 8, GVX_STFT_LOSS_FRAMES_PER_WORKGROUP = 4, GVX_STFT_LOSS_GATHER_SAMPLES = 256,
+       GVX_STFT_LOSS_MAX_ROWS = 65535, GVX_STFT_LOSS_MAX_SAMPLES = 1 << 30 };
+typedef struct gvx_stft_resolution {
+    int32_t n_fft, hop, win_length;
+} gvx_stft_resolution;
+typedef struct gvx_stft_loss_debug {
+    float* mag_pred[GVX_STFT_LOSS_MAX_RESOLUTIONS];
+    float* mag_target[GVX_STFT_LOSS_MAX_RESOLUTIONS];
+} gvx_stft_loss_debug;
+typedef struct gvx_stft_loss_plan gvx_stft_loss_plan;   /* (the bare name is the call's) */
+int gvx_stft_loss_create(const gvx_stft_resolution* res, int R, float w_sc, float w_mag, float eps, gvx_stft_loss_plan** out);
+void gvx_stft_loss_destroy(gvx_stft_loss_plan* plan);
+size_t gvx_stft_loss_workspace_bytes(const gvx_stft_loss_plan* plan, int B, long n_max);
+int gvx_stft_loss(gvx_stft_loss_plan* plan, const float* pred, const float* target, const int32_t* sample_lengths, int B, long n_max,
+                  float* loss_out, float* parts_out, float* d_pred, const gvx_stft_loss_debug* dbg, void* workspace, size_t workspace_bytes,
+                  void* stream);
+
 /* ---- Per-kernel timing of the decoder step (measurement only): when enabled, a teacher-forced call replays the
  * mid-sequence LSTM-step launch and the attention launches 64 times each, back to back, between HIP events on
  * `stream` (after its loop; the call's outputs are not valid afterwards); gvx_kernel_times_ms synchronises and

@@ -11,7 +11,10 @@ on 32 x 1000 x 128 - and the Python entry points around them by the host clock;
 `melgan` (on request): the MelGAN generator at 1 x 568 and 32 x 800 frames between device events, with the time per stage, against the
 same float32 network through torch's own ROCm convolutions and against Griffin-Lim (32 iterations) on the same mels;
 `melgan_train` (on request): `vocode_with_grad` + `backward()` (gvx_melgan_forward_train + gvx_melgan_backward) at 16 x 32 and 8 x 128
-frames between device events, against autograd through torch's own convolutions on the same parameters, with the tape's size."""
+frames between device events, against autograd through torch's own convolutions on the same parameters, with the tape's size;
+`mrstft` (on request): the multi-resolution STFT loss, value + gradient (MultiResolutionSTFTLoss + `backward()`: one gvx_stft_loss call),
+at 16 x 8192 and 8 x 32768 samples with the default resolutions between device events, median of 7, against the same loss written
+with torch.stft + autograd on the same device, with the workspace's size."""
 import json
 import os
 import sys
@@ -357,6 +360,61 @@ def main():
             res[key]["max_relative_gradient_difference_from_torch"] = max(
                 float((got[k] - p.grad).abs().max() / p.grad.abs().max().clamp_min(1e-30)) for k, p in voc.named_parameters())
             sd = {k: v.detach() for k, v in voc.state_dict().items()}
+            print(json.dumps({key: res[key]}), flush=True)
+    if "mrstft" in which:
+        import statistics
+
+        from genvox_amd.losses import DEFAULT_RESOLUTIONS, MultiResolutionSTFTLoss
+
+        def ev_median(fn, warm=3, reps=7):
+            for _ in range(warm):
+                fn()
+            out = []
+            for _ in range(reps):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                e1.synchronize()
+                out.append(e0.elapsed_time(e1))
+            return {"median_ms": round(statistics.median(out), 3), "min_ms": round(min(out), 3), "max_ms": round(max(out), 3), "runs": reps}
+
+        windows = [torch.hann_window(w, periodic=True, device="cuda") for _, _, w in DEFAULT_RESOLUTIONS]
+
+        def torch_loss(p, t):   # the header's definition on rows of full length: norms and means per row
+            total = 0.0
+            for (n_fft, hop, wl), w in zip(DEFAULT_RESOLUTIONS, windows):
+                m = []
+                for x in (p, t):
+                    X = torch.stft(x, n_fft, hop, wl, w, center=True, pad_mode="reflect", return_complex=True)
+                    m.append(torch.sqrt(torch.clamp(X.real ** 2 + X.imag ** 2, min=1e-7)))
+                sc = torch.linalg.norm(m[1] - m[0], dim=(1, 2)) / torch.linalg.norm(m[1], dim=(1, 2))
+                total = total + (sc + (m[1].log() - m[0].log()).abs().mean(dim=(1, 2))).mean()
+            return total / len(DEFAULT_RESOLUTIONS)
+
+        crit = MultiResolutionSTFTLoss()
+        gen = torch.Generator(device="cuda").manual_seed(0)
+        for B, n in ((16, 8192), (8, 32768)):
+            key = f"mrstft_{B}x{n}"
+            pred = (0.3 * torch.randn(B, n, device="cuda", generator=gen)).requires_grad_(True)
+            target = 0.3 * torch.randn(B, n, device="cuda", generator=gen)
+
+            def ours():
+                pred.grad = None
+                crit(pred, target).backward()
+
+            def torchs():
+                pred.grad = None
+                torch_loss(pred, target).backward()
+
+            res[key] = {"value_plus_gradient": ev_median(ours)}
+            got, got_loss = pred.grad.clone(), float(crit(pred, target))
+            with torch.no_grad():
+                res[key]["value_alone"] = ev_median(lambda: crit(pred, target))
+            res[key]["torch_stft_autograd"] = ev_median(torchs)
+            res[key]["relative_loss_difference_from_torch"] = abs(got_loss - float(torch_loss(pred, target))) / got_loss
+            res[key]["max_relative_gradient_difference_from_torch"] = float((got - pred.grad).abs().max() / pred.grad.abs().max())
+            res[key]["workspace_mb"] = round(crit._workspace.numel() / 1e6, 1)
             print(json.dumps({key: res[key]}), flush=True)
     if "cpu" in which:
         # CPU baselines for configs 3 and 4 (the oracle = CPU restatement of the reference, on this box's host cores):
