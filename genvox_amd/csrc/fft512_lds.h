@@ -1,8 +1,9 @@
 // 512-point complex FFT of one frame by one wave, in LDS: the transform under every n_fft = 1024 / hop = 256 vocoder kernel
 // (griffinlim.hip: gl_inverse_ola_kernel, gl_iteration_kernel, gl_forward_update_kernel; wav_to_mel.hip: stft_magnitude_kernel).
 // A 1024-point real transform is a 512-point complex Stockham radix-8 (3 passes, 8 points per lane, exchange through LDS) plus
-// the even/odd split, which each kernel does for itself; the inverse is unnormalised like rocFFT's c2r.  fp32, table twiddles
-// computed in double on the host (gvx_gl_plan_create).
+// the even/odd split; the inverse is unnormalised like rocFFT's c2r.  fp32, table twiddles computed in double on the host
+// (gvx_gl_plan_create).  The split and its inverse-side pack are written once, here, for every size (rfft_split, irfft_pack: on
+// values, the callers keep their own LDS addressing); fft_lds.h builds the 256- and 1024-point transforms on the same pieces.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -41,6 +42,27 @@ __device__ __forceinline__ void dft8(float2 v[8]) {
     v[1] = cadd(e1, w1); v[5] = csub(e1, w1);
     v[2] = cadd(e2, w2); v[6] = csub(e2, w2);
     v[3] = cadd(e3, w3); v[7] = csub(e3, w3);
+}
+
+// Real transform of 2H samples from the complex transform Z of its H even/odd pairs: bin k from zk = Z[k mod H] and zc = Z[(H - k)
+// mod H], both as stored, and w = e^{-2 pi i k/2H}.  edge: k is 0 or H, the two bins that are exactly real for a real signal
+__device__ __forceinline__ float2 rfft_split(float2 zk, float2 zc, float2 w, bool edge) {
+    zc.y = -zc.y;
+    const float2 sm = cadd(zk, zc), df = csub(zk, zc);
+    const float2 wd = cmul(w, df);                       // W^k (Z[k] - conj Z[H-k])
+    float2 X = make_float2(0.5f * (sm.x + wd.y), 0.5f * (sm.y - wd.x));   // 0.5*sm - 0.5i*wd
+    if (edge) X.y = 0.f;
+    return X;
+}
+
+// The way back: point k of the H-point complex input of the unnormalised inverse real transform from a = S[k], c = S[H - k] as
+// stored and the same w.  dc: k is 0 (c is then the Nyquist bin); c2r ignores the imaginary parts of the DC and Nyquist bins
+__device__ __forceinline__ float2 irfft_pack(float2 a, float2 c, float2 w, bool dc) {
+    if (dc) { a.y = 0.f; c.y = 0.f; }
+    c.y = -c.y;                                          // conj(S[H - k])
+    const float2 d = csub(a, c);
+    const float2 id = make_float2(-d.y, d.x);            // i * d
+    return cadd(cadd(a, c), cmul(id, make_float2(w.x, -w.y)));   // w is e^{-...}; need e^{+...}
 }
 
 // 512-point complex FFT of one frame by one wave.  In: lane j holds x[j + 64 r] in v[r].  Out: lane j holds X[j + 64 r]
@@ -84,7 +106,5 @@ __device__ __forceinline__ void fft512_wave(float2 v[8], float2* buf, const floa
         }
     }
 }
-
-constexpr int GLF_FRAMES = 4;   // frames (waves) per workgroup of the forward kernels (gl_forward_update_kernel, stft_magnitude_kernel)
 
 }  // namespace

@@ -1,6 +1,7 @@
 // 256-, 512- and 1024-point complex FFT of one frame by one wave, in LDS: the transforms under the multi-resolution STFT loss
 // (stft_loss.hip), whose real transforms of 512, 1024 and 2048 samples are complex transforms of half the size plus the even/odd
-// split.  Stockham passes like fft512_lds.h's (whose butterflies, padding and wave fence this header reuses, and whose own 512-point
+// split (fft512_lds.h's rfft_split; the gradient kernel packs its inverse side for itself, two points from one pair of bins).
+// Stockham passes like fft512_lds.h's (whose butterflies, padding and wave fence this header reuses, and whose own 512-point
 // instantiations it leaves alone), but from LDS to LDS: the caller writes point i to buf[fpad(i)], the result is left there in
 // natural order, and every pass reads all of a lane's points into registers before it writes any - the exchange is in place.
 // Radices: 256 = 4.4.4.4, 512 = 8.8.8, 1024 = 8.8.4.4, so that every pass keeps all 64 lanes busy (a radix-8 pass over 256 points

@@ -1,15 +1,16 @@
 // Batched mel -> waveform vocoder on the GPU: dB->amplitude + pseudo-inverse mel projection, fast Griffin-Lim, overlap-add
-// inverse STFT, and the clip / trim / normalise / Butterworth tail.  Replaces the mel->wav half of the reference's NumPy audio
-// library, which is strictly per utterance with Python loops over frames (utils/audio/base.py:38-88, :143-169;
-// core/processors.py:81-96).  The wav -> mel half is wav_to_mel.hip; what the two share is vocoder_internal.h.
+// inverse STFT.  Replaces the mel->wav half of the reference's NumPy audio library, which is strictly per utterance with Python
+// loops over frames (utils/audio/base.py:38-88, :143-169; core/processors.py:81-96).  Its clip / trim / normalise / Butterworth
+// tail is wav_finalize.hip, the wav -> mel half is wav_to_mel.hip; what the three share is vocoder_internal.h.
 //
 // Layouts: the reference's spectrogram layout is [bins][frames]; internally everything is frame-major
 // ([B*T][bins] complex, [B*T][n_fft] real) because that is what a batched 1-D FFT wants (one contiguous transform
 // per frame).  The C ABI takes and returns the reference's layout and transposes once on the way in / out.
 //
 // A Griffin-Lim iteration takes one of four paths (gl_path picks one per call; all fp32 / complex64, all HBM-bound):
-//   one launch, two frames per wave  the default for n_fft 1024 / hop 256, the reference's vocoder setting: FFTs in LDS (fft512_lds.h),
-//                                    only the signal and the previous rebuilt spectrum cross iterations (gl_iteration_kernel<2>)
+//   one launch, two frames per wave  the default for n_fft 1024 / hop 256, the reference's vocoder setting: FFTs in LDS (fft512_lds.h:
+//                                    the transform, the even/odd split of the real transform and its inverse-side pack), only
+//                                    the signal and the previous rebuilt spectrum cross iterations (gl_iteration_kernel<2>)
 //   one launch, one frame per wave   the same kernel for sequences too short for the larger workgroup, or GVX_GL_ONE_FRAME=1
 //   two launches                     GVX_GL_TWO_KERNELS=1: gl_inverse_ola_kernel + gl_forward_update_kernel (A/B runs, cross-checks)
 //   rocFFT                           every other n_fft / hop, or GVX_GL_ROCFFT=1: C2R (rocFFT, batch B*T) -> overlap-add + window-sum
@@ -22,7 +23,6 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
-#include <cstring>
 #include <vector>
 
 using namespace gvx::voc;
@@ -90,20 +90,6 @@ __global__ void wss_kernel(const float* win, float* wss, int n_fft, int hop, int
         s += w * w;
     }
     wss[i] = s;
-}
-
-// ---- ragged batches: row b has T_b = frame_lengths[b] frames (clamped to [0, T], never trusted) and n_b = n_fft + (T_b-1)*hop
-// samples inside buffers that keep the strides of the padded T.  Kernels that know about lengths are the RAGGED = true
-// instantiation of the uniform kernel's body; RAGGED = false never touches `lens` and compiles to the uniform kernel.
-__device__ __forceinline__ int row_frames(const int32_t* __restrict__ lens, int b, int T) {
-    const int v = lens[b];
-    return v < 0 ? 0 : (v > T ? T : v);
-}
-__device__ __forceinline__ long row_samples(const int32_t* __restrict__ lens, int b, int n_fft, int hop, long n_cap) {
-    const long v = lens[b];
-    if (v < 1) return 0;
-    const long nb = (long)n_fft + (v - 1) * hop;
-    return nb < n_cap ? nb : n_cap;
 }
 
 // The window sum of squares of a row of T_b frames equals the padded table wss[i] for i < T_b*hop (there only the clip at frame
@@ -211,148 +197,6 @@ __global__ void copy_rows_ragged_kernel(const float* src, float* dst, long n, in
         dst[(long)b * n + i] = i < nb ? src[(long)b * n + i] : 0.f;
 }
 
-// clip spurious samples, trim, peak, normalise to float32, IIR low-pass in float64 (core/processors.py:91-95,
-// utils/audio/base.py:20-22, :164-169; scipy.signal.lfilter = direct form II transposed)
-// RAGGED: n is the row stride; row b holds n_b = n_fft + (T_b-1)*hop samples (row_samples) and everything - trim at both ends, peak,
-// filter, the chunks' warm-up positions - is counted within them, as in a call on that row alone; out is 0 past n_b - 2*trim
-template <bool RAGGED>
-__global__ void wav_peak_kernel(const float* y, long n, int trim, unsigned int* peak_bits, const int32_t* lens, int n_fft, int hop) {
-    const int b = blockIdx.y;
-    const long n_out = (RAGGED ? row_samples(lens, b, n_fft, hop, n) : n) - 2L * trim;
-    float m = 0.f;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n_out; i += (long)gridDim.x * blockDim.x) {
-        float v = y[(long)b * n + trim + i];
-        if (v > 1.f || v < -1.f) v = 0.f;
-        m = fmaxf(m, fabsf(v));
-    }
-    for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
-    if ((threadIdx.x & 63) == 0) atomicMax(peak_bits + b, __float_as_uint(m));  // non-negative floats order like their bit patterns
-}
-
-struct IirCoef { double b[8], a[8]; int order; };
-
-template <bool RAGGED>
-__global__ void wav_filter_kernel(const float* y, long n, int trim, const unsigned int* peak_bits, IirCoef c, double* out, int B,
-                                  const int32_t* lens, int n_fft, int hop) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    const long n_stride = n - 2L * trim;
-    long n_out = n_stride;
-    if (RAGGED) {
-        n_out = row_samples(lens, b, n_fft, hop, n) - 2L * trim;
-        if (n_out < 0) n_out = 0;
-        for (long i = n_out; i < n_stride; ++i) out[(long)b * n_stride + i] = 0.0;
-    }
-    const float peak = __uint_as_float(peak_bits[b]);
-    double z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const float* yb = y + (long)b * n + trim;
-    double* ob = out + (long)b * n_stride;
-    // the recurrence is strictly sequential per utterance; the loads are not: fetch the next 16 samples while the
-    // current 16 go through the filter (one thread = one utterance, a wave = 64 utterances in lock step)
-    constexpr int CH = 16;
-    float cur[CH], nxt[CH];
-#pragma unroll
-    for (int k = 0; k < CH; ++k) cur[k] = k < n_out ? yb[k] : 0.f;
-    for (long i0 = 0; i0 < n_out; i0 += CH) {
-#pragma unroll
-        for (int k = 0; k < CH; ++k) nxt[k] = (i0 + CH + k) < n_out ? yb[i0 + CH + k] : 0.f;
-#pragma unroll
-        for (int k = 0; k < CH; ++k) {
-            if (i0 + k < n_out) {
-                float v = cur[k];
-                if (v > 1.f || v < -1.f) v = 0.f;
-                const double x = (double)(v / peak);  // float32 division, then float64 filtering, like the reference
-                const double yo = c.b[0] * x + z[0];
-#pragma unroll
-                for (int q = 1; q < 8; ++q) {
-                    if (q <= c.order) z[q - 1] = c.b[q] * x + (q < c.order ? z[q] : 0.0) - c.a[q] * yo;
-                }
-                ob[i0 + k] = yo;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < CH; ++k) cur[k] = nxt[k];
-    }
-}
-
-// The same filter, parallel over chunks of every utterance.  The recurrence is linear and stable: a chunk started W samples
-// early from a zero state differs from the sequential filter by |M^W| (M = state transition matrix), and the host picks W
-// so that this is below 1e-18 - far under a float64 ulp of the output - so the warm-up samples are simply filtered and
-// discarded (overlap-discard).  One thread = one chunk; no cross-chunk exchange, no extra buffers; a row's result does
-// not depend on the batch it is in.  Reference: scipy.signal.lfilter in butter_lowpass_filter (utils/audio/base.py:164-166).
-template <bool RAGGED>
-__global__ void wav_filter_chunked_kernel(const float* y, long n, int trim, const unsigned int* peak_bits, IirCoef c, double* out,
-                                          int chunk, int warm, int nch, const int32_t* lens, int n_fft, int hop) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    const int b = blockIdx.y;
-    if (k >= nch) return;
-    const long n_stride = n - 2L * trim;
-    long n_out = n_stride;
-    const long i_begin = (long)k * chunk;
-    double* ob = out + (long)b * n_stride;
-    if (RAGGED) {
-        n_out = row_samples(lens, b, n_fft, hop, n) - 2L * trim;
-        if (n_out < 0) n_out = 0;
-        for (long i = max(i_begin, n_out); i < min(n_stride, i_begin + chunk); ++i) ob[i] = 0.0;   // the chunk's share of the padding
-        if (i_begin >= n_out) return;
-    }
-    const float peak = __uint_as_float(peak_bits[b]);
-    const long i_end = min(n_out, i_begin + chunk);
-    const long i_start = max(0L, i_begin - warm);
-    double z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const float* yb = y + (long)b * n + trim;
-    constexpr int CH = 16;
-    float cur[CH], nxt[CH];
-#pragma unroll
-    for (int q = 0; q < CH; ++q) cur[q] = (i_start + q) < i_end ? yb[i_start + q] : 0.f;
-    for (long i0 = i_start; i0 < i_end; i0 += CH) {
-#pragma unroll
-        for (int q = 0; q < CH; ++q) nxt[q] = (i0 + CH + q) < i_end ? yb[i0 + CH + q] : 0.f;
-#pragma unroll
-        for (int q = 0; q < CH; ++q) {
-            if (i0 + q < i_end) {
-                float v = cur[q];
-                if (v > 1.f || v < -1.f) v = 0.f;
-                const double x = (double)(v / peak);
-                const double yo = c.b[0] * x + z[0];
-#pragma unroll
-                for (int r = 1; r < 8; ++r) {
-                    if (r <= c.order) z[r - 1] = c.b[r] * x + (r < c.order ? z[r] : 0.0) - c.a[r] * yo;
-                }
-                if (i0 + q >= i_begin) ob[i0 + q] = yo;
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < CH; ++q) cur[q] = nxt[q];
-    }
-}
-
-// smallest W with max|M^W| < 1e-18 for the filter's state transition matrix (direct form II transposed), or -1 if the
-// filter decays too slowly (or not at all) for the overlap-discard scheme
-int iir_warmup_length(const IirCoef& c, int cap) {
-    const int n = c.order;
-    double P[8][8] = {}, M[8][8] = {}, R[8][8];
-    for (int q = 1; q <= n; ++q) {
-        M[q - 1][0] = -c.a[q];
-        if (q < n) M[q - 1][q] = 1.0;
-    }
-    for (int i = 0; i < n; ++i) P[i][i] = 1.0;
-    for (int w = 1; w <= cap; ++w) {
-        double mx = 0.0;
-        for (int i = 0; i < n; ++i)
-            for (int j = 0; j < n; ++j) {
-                double acc = 0.0;
-                for (int k = 0; k < n; ++k) acc += P[i][k] * M[k][j];
-                R[i][j] = acc;
-                mx = std::fmax(mx, std::fabs(acc));
-            }
-        std::memcpy(P, R, sizeof P);
-        if (!(mx < 1e300)) return -1;
-        if (mx < 1e-18) return w;
-    }
-    return -1;
-}
-
 // =====================================================================================================
 // Fused Griffin-Lim iteration for n_fft = 1024, hop = 256 (the reference's vocoder setting).
 // The rocFFT pipeline moves each frame through HBM seven times per iteration (c2r pre/post kernels, raw frames, overlap-add,
@@ -372,6 +216,59 @@ constexpr int GLI_FRAMES = 16;                 // frames (waves) per workgroup o
 constexpr int GLI_BLOCKS = GLI_FRAMES - 3;     // hop blocks it completes (n_fft / hop - 1 = 3 halo frames)
 constexpr int GLI_TAB_WIN = FN + 520;          // LDS tables of gl_iteration_kernel, in float2: twiddles [FN + 513], pad, window [512]
 constexpr int GLI_TAB = GLI_TAB_WIN + 512;
+
+// ---- the steps of a frame that the kernels below share.  Lane j of the frame's wave holds samples 2 (j + 64 r), 2 (j + 64 r) + 1
+// in v[r] (the complex points j + 64 r of fft512_wave) and owns bins j + 64 r and, on lane 0, bin 512.
+// (The prefetch of the update's operands is not among them: gl_forward_update_kernel loads its twiddles in the same loop, and with
+// the loop shared it needs 98 VGPRs instead of 96, a wave less per SIMD.)
+
+// v = win * frame at yb
+__device__ __forceinline__ void load_windowed_frame(float2 v[8], const float* __restrict__ yb, const float* __restrict__ win, int j) {
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        const int n2 = 2 * (j + 64 * r);
+        const float2 x = *reinterpret_cast<const float2*>(yb + n2);
+        const float2 w = *reinterpret_cast<const float2*>(win + n2);
+        v[r] = make_float2(w.x * x.x, w.y * x.y);
+    }
+}
+
+// the inverse transform's v, windowed, into the frame's LDS row of 1024 floats
+// (same operation order as gl_ola_kernel: win[k] * (fr[k] * (1/n_fft)))
+__device__ __forceinline__ void store_windowed_frame(float* frow, const float2 v[8], const float* __restrict__ win, int j) {
+    const float inv_n = 1.f / 1024.f;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        const int n2 = 2 * (j + 64 * r);
+        const float2 w = *reinterpret_cast<const float2*>(win + n2);
+        *reinterpret_cast<float2*>(frow + n2) = make_float2(w.x * (v[r].x * inv_n), w.y * (v[r].y * inv_n));
+    }
+}
+
+// Overlap-add of the workgroup's hop blocks h0 .. h0+NBL-1 from its NBL + 3 windowed frame rows in LDS (`rows`; frame h0-3 is row
+// 0), frames added in ascending order, divided by the window sum of squares (v_rcp_f32: 1 ulp).  Called by every thread, behind
+// the barrier that ends the rows' writes.  RAGGED: frames t >= Tb do not exist, the row ends at (Tb+3)*256, its last three hop
+// blocks are divided by the row's own wss_tail [B][768]
+template <int NBL, bool RAGGED>
+__device__ __forceinline__ void overlap_add_blocks(const float* rows, const float* __restrict__ wss, const float* __restrict__ wss_tail,
+                                                   float* __restrict__ y, int b, int h0, int T, int Tb, int tid) {
+    const long n = (long)(T + 3) * 256;
+    const long n_row = RAGGED ? (long)(Tb + 3) * 256 : n;
+    for (int idx = tid; idx < NBL * 256; idx += GLI_FRAMES * 64) {
+        const int hb = idx >> 8, q = idx & 255;
+        const int h = h0 + hb;
+        const long i = (long)h * 256 + q;
+        if (i >= n_row) break;
+        float sacc = 0.f;
+#pragma unroll
+        for (int d = 3; d >= 0; --d) {           // frames t = h-3 .. h  ->  rows hb .. hb+3
+            const int tt = h - d;
+            if (tt >= 0 && tt < Tb) sacc += rows[(long)(hb + 3 - d) * (FPAD * 2) + d * 256 + q];
+        }
+        const float w = (RAGGED && h >= Tb) ? wss_tail[(long)b * 768 + (h - Tb) * 256 + q] : wss[i];
+        y[(long)b * n + i] = w > 1.17549435e-38f ? sacc * __builtin_amdgcn_rcpf(w) : sacc;
+    }
+}
 
 // S [B*T][513] (frame-major) -> y [B][(T+3)*256]: y[i] = (sum_t win[k] * (irfft(S_t)[k] / 1024)) / wss[i], k = i - 256 t
 // RAGGED: only the frames t < T_b of row b exist; its samples i < (T_b+3)*256 are written (the last three hop blocks divided by the
@@ -400,50 +297,18 @@ __global__ __launch_bounds__(GLI_FRAMES * 64) void gl_inverse_ola_kernel(const f
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
             const int k = j + 64 * r;
-            float2 a = S[k], c = S[512 - k];
-            if (k == 0) { a.y = 0.f; c.y = 0.f; }          // c2r ignores the imaginary parts of the DC and Nyquist bins
-            c.y = -c.y;                                     // conj(S[512 - k])
-            const float2 w = tw2[k];                        // e^{-2 pi i k/1024}; need e^{+...}
-            const float2 d = csub(a, c);
-            const float2 id = make_float2(-d.y, d.x);       // i * d
-            v[r] = cadd(cadd(a, c), cmul(id, make_float2(w.x, -w.y)));
+            v[r] = irfft_pack(S[k], S[512 - k], tw2[k], k == 0);
         }
     } else {
 #pragma unroll
         for (int r = 0; r < 8; ++r) v[r] = make_float2(0.f, 0.f);
     }
     fft512_wave<true>(v, buf, tw, j, false);
-    // windowed frame (same operation order as gl_ola_kernel: win[k] * (fr[k] * (1/n_fft))) into this wave's LDS row
-    float* frow = reinterpret_cast<float*>(buf);   // 1024 floats inside the wave's FPAD*2 floats; all exchanges above are done
+    // the windowed frame goes into this wave's LDS row: 1024 floats inside the wave's FPAD*2 floats; all exchanges above are done
     __syncthreads();
-    if (valid) {
-        const float inv_n = 1.f / 1024.f;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            const int n2 = 2 * (j + 64 * r);
-            const float2 w = *reinterpret_cast<const float2*>(win + n2);
-            *reinterpret_cast<float2*>(frow + n2) = make_float2(w.x * (v[r].x * inv_n), w.y * (v[r].y * inv_n));
-        }
-    }
+    if (valid) store_windowed_frame(reinterpret_cast<float*>(buf), v, win, j);
     __syncthreads();
-    // overlap-add of hop blocks h0 .. h0+12 (ascending frame order), divide by the window sum of squares
-    const long n = (long)(T + 3) * 256;
-    const long n_row = RAGGED ? (long)(Tb + 3) * 256 : n;
-    const float* fall = reinterpret_cast<const float*>(fsm);
-    for (int idx = tid; idx < GLI_BLOCKS * 256; idx += GLI_FRAMES * 64) {
-        const int hb = idx >> 8, q = idx & 255;
-        const int h = h0 + hb;
-        const long i = (long)h * 256 + q;
-        if (i >= n_row) break;
-        float sacc = 0.f;
-#pragma unroll
-        for (int d = 3; d >= 0; --d) {           // frames t = h-3 .. h  ->  waves hb .. hb+3
-            const int tt = h - d;
-            if (tt >= 0 && tt < Tb) sacc += fall[(long)(hb + 3 - d) * (FPAD * 2) + d * 256 + q];
-        }
-        const float w = (RAGGED && h >= Tb) ? wss_tail[(long)b * 768 + (h - Tb) * 256 + q] : wss[i];
-        y[(long)b * n + i] = w > 1.17549435e-38f ? sacc * __builtin_amdgcn_rcpf(w) : sacc;   // v_rcp_f32: 1 ulp
-    }
+    overlap_add_blocks<GLI_BLOCKS, RAGGED>(reinterpret_cast<const float*>(fsm), wss, wss_tail, y, b, h0, T, Tb, tid);
 }
 
 // One whole Griffin-Lim iteration per launch (n_fft 1024 / hop 256):
@@ -479,7 +344,6 @@ __global__ __launch_bounds__(GLI_FRAMES * 64) void gl_iteration_kernel(const flo
     }
     const int tid = threadIdx.x, jj = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const long n = (long)(T + 3) * 256;
     // twiddle and window tables live in LDS behind the frame rows: a table read from global memory costs the wave a
     // round trip through L1 at every FFT pass (60 % of the wave cycles were s_waitcnt before this)
     float2* tab = fsm + NFR * FPAD;
@@ -503,14 +367,7 @@ __global__ __launch_bounds__(GLI_FRAMES * 64) void gl_iteration_kernel(const flo
         int j = jj;
         if (FPW > 1) asm volatile("" : "+v"(j));
         // ---- forward: frame of y_in, windowed
-        const float* yb = y_in + (long)b * n + (long)t * 256;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            const int n2 = 2 * (j + 64 * r);
-            const float2 x = *reinterpret_cast<const float2*>(yb + n2);
-            const float2 w = *reinterpret_cast<const float2*>(win + n2);
-            v[r] = make_float2(w.x * x.x, w.y * x.y);
-        }
+        load_windowed_frame(v, y_in + (long)b * ((long)(T + 3) * 256) + (long)t * 256, win, j);
         // the update's operands do not depend on the FFT: fetch them now so their latency hides under it.  (Measured the other
         // way round as well: loading them after the FFT and capping the kernel at 64 VGPRs puts two workgroups on a CU, but the
         // kernel is bound by instruction issue and LDS traffic, not by latency - 81 ms instead of 72 ms for 60 iterations.)
@@ -534,19 +391,17 @@ __global__ __launch_bounds__(GLI_FRAMES * 64) void gl_iteration_kernel(const flo
             const int k = r < 8 ? j + 64 * r : 512;
             const bool edge = r == 8 || (r == 0 && j == 0);       // DC / Nyquist
             const float2 zk = buf[r < 8 ? a_fwd + 72 * r : 0];
-            float2 zc = buf[r == 8 ? 0 : (r == 0 && j == 0 ? 0 : a_rev - 72 * r)];
-            zc.y = -zc.y;
-            const float2 sm = cadd(zk, zc), df = csub(zk, zc);
-            const float2 wd = cmul(tw2[k], df);                  // W^k (Z[k] - conj Z[512-k])
-            float2 reb = make_float2(0.5f * (sm.x + wd.y), 0.5f * (sm.y - wd.x));   // 0.5*sm - 0.5i*wd
-            if ((r == 0 || r == 8) && edge) reb.y = 0.f;         // exactly real for a real signal
+            const float2 zc = buf[r == 8 ? 0 : (r == 0 && j == 0 ? 0 : a_rev - 72 * r)];
+            const float2 reb = rfft_split(zk, zc, tw2[k], edge);
             float2 a = reb;
             if (!first) {
                 a.x = reb.x - c * pvk.x;
                 a.y = reb.y - c * pvk.y;
             }
             // a / (|a| + tiny) * mag with v_sqrt_f32 / v_rcp_f32; the operands are pre-scaled on the rare path where their
-            // squares would underflow (|a| < 1e-15), like the hypot behind the reference's abs()
+            // squares would underflow (|a| < 1e-15), like the hypot behind the reference's abs().  This is (a * rcp) * mag;
+            // gl_forward_update_kernel computes a * (rcp * mag), which rounds differently and can form 0 * inf for a == 0 under a
+            // large mag.  The two are kept apart on purpose: making one into the other changes what a path computes
             float dd = __builtin_amdgcn_sqrtf(a.x * a.x + a.y * a.y);
             if (fmaxf(fabsf(a.x), fabsf(a.y)) < 1e-15f) {
                 const float ax = a.x * 1.8446744e19f, ay = a.y * 1.8446744e19f;   // 2^64
@@ -572,49 +427,18 @@ __global__ __launch_bounds__(GLI_FRAMES * 64) void gl_iteration_kernel(const flo
         wave_lds_fence();
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
-            const int k = j + 64 * r;
             const bool dc = r == 0 && j == 0;
-            float2 a = S[r];
-            float2 cj = dc ? S[8] : buf[a_rev - 72 * r];       // lane 0 holds the Nyquist bin itself
-            if (dc) { a.y = 0.f; cj.y = 0.f; }                 // c2r ignores the imaginary parts of the DC and Nyquist bins
-            cj.y = -cj.y;                                      // conj(S[512 - k])
-            const float2 w = tw2[k];                           // e^{-2 pi i k/1024}; need e^{+...}
-            const float2 d = csub(a, cj);
-            const float2 id = make_float2(-d.y, d.x);          // i * d
-            v[r] = cadd(cadd(a, cj), cmul(id, make_float2(w.x, -w.y)));
+            v[r] = irfft_pack(S[r], dc ? S[8] : buf[a_rev - 72 * r], tw2[j + 64 * r], dc);   // lane 0 holds the Nyquist bin itself
         }
         wave_lds_fence();
         fft512_wave<true, true>(v, buf, tw, j, false);
-        // windowed frame (same operation order as gl_ola_kernel: win[k] * (fr[k] * (1/n_fft))) into this frame's LDS row, which
-        // only this wave touches until the barrier (the FFT's last exchange ended with a fence)
-        float* frow = reinterpret_cast<float*>(buf);
-        const float inv_n = 1.f / 1024.f;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            const int n2 = 2 * (j + 64 * r);
-            const float2 w = *reinterpret_cast<const float2*>(win + n2);
-            *reinterpret_cast<float2*>(frow + n2) = make_float2(w.x * (v[r].x * inv_n), w.y * (v[r].y * inv_n));
-        }
+        // the windowed frame goes into this frame's LDS row, which only this wave touches until the barrier (the FFT's last
+        // exchange ended with a fence)
+        store_windowed_frame(reinterpret_cast<float*>(buf), v, win, j);
     }
     if (!do_inverse) return;
     __syncthreads();
-    // overlap-add of hop blocks h0 .. h0+NBL-1 (ascending frame order), divide by the window sum of squares
-    const float* fall = reinterpret_cast<const float*>(fsm);
-    const long n_row = RAGGED ? (long)(Tb + 3) * 256 : n;
-    for (int idx = tid; idx < NBL * 256; idx += GLI_FRAMES * 64) {
-        const int hb = idx >> 8, q = idx & 255;
-        const int h = h0 + hb;
-        const long i = (long)h * 256 + q;
-        if (i >= n_row) break;
-        float sacc = 0.f;
-#pragma unroll
-        for (int d = 3; d >= 0; --d) {           // frames t = h-3 .. h  ->  rows hb .. hb+3
-            const int tt = h - d;
-            if (tt >= 0 && tt < Tb) sacc += fall[(long)(hb + 3 - d) * (FPAD * 2) + d * 256 + q];
-        }
-        const float w = (RAGGED && h >= Tb) ? wss_tail[(long)b * 768 + (h - Tb) * 256 + q] : wss[i];
-        y_out[(long)b * n + i] = w > 1.17549435e-38f ? sacc * __builtin_amdgcn_rcpf(w) : sacc;
-    }
+    overlap_add_blocks<NBL, RAGGED>(reinterpret_cast<const float*>(fsm), wss, wss_tail, y_out, b, h0, T, Tb, tid);
 }
 
 
@@ -633,14 +457,7 @@ __global__ __launch_bounds__(GLF_FRAMES * 64) void gl_forward_update_kernel(cons
     if (valid) {
         const unsigned fu = (unsigned)f;   // frames < 2^32 (checked on the host): 32-bit division, the 64-bit one is ~150 instructions
         const int b = (int)(fu / (unsigned)T), t = (int)(fu - (unsigned)b * (unsigned)T);
-        const float* yb = y + (long)b * (long)(T + 3) * 256 + (long)t * 256;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            const int n2 = 2 * (j + 64 * r);
-            const float2 x = *reinterpret_cast<const float2*>(yb + n2);
-            const float2 w = *reinterpret_cast<const float2*>(win + n2);
-            v[r] = make_float2(w.x * x.x, w.y * x.y);
-        }
+        load_windowed_frame(v, y + (long)b * (long)(T + 3) * 256 + (long)t * 256, win, j);
     } else {
 #pragma unroll
         for (int r = 0; r < 8; ++r) v[r] = make_float2(0.f, 0.f);
@@ -668,13 +485,7 @@ __global__ __launch_bounds__(GLF_FRAMES * 64) void gl_forward_update_kernel(cons
     for (int r = 0; r < 9; ++r) {
         const int k = r < 8 ? j + 64 * r : 512;
         if (r == 8 && j != 0) break;
-        const float2 zk = buf[fpad(k & (FN - 1))];
-        float2 zc = buf[fpad((512 - k) & (FN - 1))];
-        zc.y = -zc.y;
-        const float2 sm = cadd(zk, zc), df = csub(zk, zc);
-        const float2 wd = cmul(wk[r], df);                   // W^k (Z[k] - conj Z[512-k])
-        float2 reb = make_float2(0.5f * (sm.x + wd.y), 0.5f * (sm.y - wd.x));   // 0.5*sm - 0.5i*wd
-        if (k == 0 || k == 512) reb.y = 0.f;                 // exactly real for a real signal
+        const float2 reb = rfft_split(buf[fpad(k & (FN - 1))], buf[fpad((512 - k) & (FN - 1))], wk[r], k == 0 || k == 512);
         float2 a = reb;
         if (!first) {
             a.x = reb.x - c * pv[r].x;
@@ -683,6 +494,8 @@ __global__ __launch_bounds__(GLF_FRAMES * 64) void gl_forward_update_kernel(cons
         // a / (|a| + tiny) * mag with v_sqrt_f32 / v_rcp_f32 (1 ulp each) instead of libm hypotf and two IEEE divisions,
         // which together were half of this kernel's vector instructions.  Operands are pre-scaled by a power of two when
         // they are so small that their squares would underflow (hypotf's only advantage here), so tiny bins keep their phase.
+        // This is a * (rcp * mag); gl_iteration_kernel computes (a * rcp) * mag, the unit vector first, which rounds differently
+        // and never forms 0 * inf.  The two are kept apart on purpose: making one into the other changes what a path computes
         const float big = fmaxf(fabsf(a.x), fabsf(a.y));
         const float sc = big < 1e-15f ? 1.8446744e19f : 1.f;         // 2^64 (exact)
         const float isc = big < 1e-15f ? 5.4210109e-20f : 1.f;       // 2^-64
@@ -960,39 +773,6 @@ int griffin_lim_impl(gvx_gl_plan* p, const float* mag, const float* window, int 
     return GVX_OK;
 }
 
-// gvx_wav_finalize (lens == nullptr, n_fft = hop = 0) and gvx_wav_finalize_ragged
-int wav_finalize_impl(const float* wav, int B, long n_samples, const int32_t* lens, int n_fft, int hop, int trim, const double* b_coef,
-                      const double* a_coef, int order, double* out, unsigned int* scratch_B, void* stream) {
-    if (!wav || !b_coef || !a_coef || !out || !scratch_B) return gl_fail(GVX_ERR_INVALID_ARG, "null argument");
-    if (order < 1 || order > 7) return gl_fail(GVX_ERR_UNSUPPORTED, "filter order %d not in [1, 7]", order);
-    if (n_samples <= 2L * trim) return gl_fail(GVX_ERR_INVALID_ARG, "signal shorter than the trim");
-    hipStream_t s = (hipStream_t)stream;
-    IirCoef c{};
-    c.order = order;
-    for (int k = 0; k <= order; ++k) { c.b[k] = b_coef[k] / a_coef[0]; c.a[k] = a_coef[k] / a_coef[0]; }
-    GL_HIP(hipMemsetAsync(scratch_B, 0, (size_t)B * sizeof(unsigned int), s));
-    ragged_dispatch(lens != nullptr, [&](auto R) {
-        wav_peak_kernel<decltype(R)::value><<<dim3(64, B), 256, 0, s>>>(wav, n_samples, trim, scratch_B, lens, n_fft, hop);
-    });
-    GL_HIP(hipGetLastError());
-    const int warm = iir_warmup_length(c, 4096);
-    ragged_dispatch(lens != nullptr, [&](auto R) {
-        constexpr bool ragged = decltype(R)::value;
-        if (warm > 0) {
-            int chunk = 1024;
-            while (chunk < 8 * warm) chunk *= 2;   // warm-up work <= 1/8 of the total
-            const long n_out = n_samples - 2L * trim;
-            const int nch = (int)((n_out + chunk - 1) / chunk);
-            wav_filter_chunked_kernel<ragged><<<dim3((nch + 63) / 64, B), 64, 0, s>>>(wav, n_samples, trim, scratch_B, c, out, chunk, warm, nch,
-                                                                                     lens, n_fft, hop);
-        } else {                                    // slowly decaying filter: sequential
-            wav_filter_kernel<ragged><<<(B + 63) / 64, 64, 0, s>>>(wav, n_samples, trim, scratch_B, c, out, B, lens, n_fft, hop);
-        }
-    });
-    GL_HIP(hipGetLastError());
-    return GVX_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -1129,18 +909,6 @@ int gvx_griffin_lim_ragged(gvx_gl_plan* p, const float* mag, const float* window
                            float momentum, float* phase_out, float* wav_out, void* ws, size_t ws_bytes, void* stream) {
     if (!frame_lengths) return gl_fail(GVX_ERR_INVALID_ARG, "null frame_lengths (gvx_griffin_lim is the call for rows of one length)");
     return griffin_lim_impl(p, mag, window, B, T, frame_lengths, n_iter, momentum, phase_out, wav_out, ws, ws_bytes, stream);
-}
-
-int gvx_wav_finalize(const float* wav, int B, long n_samples, int trim, const double* b_coef, const double* a_coef, int order,
-                     double* out, unsigned int* scratch_B, void* stream) {
-    return wav_finalize_impl(wav, B, n_samples, nullptr, 0, 0, trim, b_coef, a_coef, order, out, scratch_B, stream);
-}
-
-int gvx_wav_finalize_ragged(const float* wav, int B, long n_samples, const int32_t* frame_lengths, int n_fft, int hop, int trim,
-                            const double* b_coef, const double* a_coef, int order, double* out, unsigned int* scratch_B, void* stream) {
-    if (!frame_lengths) return gl_fail(GVX_ERR_INVALID_ARG, "null frame_lengths (gvx_wav_finalize is the call for rows of one length)");
-    if (B < 1 || n_fft < 1 || hop < 1 || trim < 0) return gl_fail(GVX_ERR_INVALID_ARG, "B, n_fft, hop must be >= 1 and trim >= 0");
-    return wav_finalize_impl(wav, B, n_samples, frame_lengths, n_fft, hop, trim, b_coef, a_coef, order, out, scratch_B, stream);
 }
 
 }  // C ABI

@@ -84,13 +84,7 @@ __global__ __launch_bounds__(SL_FRAMES * 64) void sl_forward_kernel(const float*
             for (int q = 0; q <= Q; ++q) {
                 const int k = j + 64 * q;
                 if (k <= H) {
-                    const float2 zk = buf[fpad(k & (H - 1))];
-                    float2 zc = buf[fpad((H - k) & (H - 1))];
-                    zc.y = -zc.y;
-                    const float2 sm = cadd(zk, zc), df = csub(zk, zc);
-                    const float2 wd = cmul(p.tw2[k], df);
-                    float2 X = make_float2(0.5f * (sm.x + wd.y), 0.5f * (sm.y - wd.x));
-                    if (k == 0 || k == H) X.y = 0.f;
+                    const float2 X = rfft_split(buf[fpad(k & (H - 1))], buf[fpad((H - k) & (H - 1))], p.tw2[k], k == 0 || k == H);
                     const float P = X.x * X.x + X.y * X.y;
                     const float M = sqrtf(fmaxf(P, eps));
                     if (sig == 0) {

@@ -1,5 +1,6 @@
-// Internal to the vocoder sources (griffinlim.hip: mel -> wav, wav_to_mel.hip: wav -> mel); not installed.  The plan handle, the
-// workspace layout, the opening every call shares, the choice of the Griffin-Lim path, and the device code both sources launch.
+// Internal to the vocoder sources (griffinlim.hip: mel -> wav, wav_finalize.hip: its clip / trim / normalise / Butterworth tail,
+// wav_to_mel.hip: wav -> mel); not installed.  The plan handle, the workspace layout, the opening every call shares, the choice of
+// the Griffin-Lim path, and the device code more than one source uses.
 #pragma once
 #include "../../include/genvox_amd.h"
 #include "gvx_kernels.h"
@@ -90,8 +91,24 @@ void ragged_dispatch(bool ragged, F&& f) {
 
 }}  // namespace gvx::voc
 
-// ---- device code of both sources (file-local in each) ----------------------------------------------------------------------------
+// ---- device code of more than one source (file-local in each) --------------------------------------------------------------------
 namespace {
+
+constexpr int GLF_FRAMES = 4;   // frames (waves) per workgroup of the forward kernels (gl_forward_update_kernel, stft_magnitude_kernel)
+
+// ---- ragged batches: row b has T_b = frame_lengths[b] frames (clamped to [0, T], never trusted) and n_b = n_fft + (T_b-1)*hop
+// samples inside buffers that keep the strides of the padded T.  Kernels that know about lengths are the RAGGED = true
+// instantiation of the uniform kernel's body; RAGGED = false never touches `lens` and compiles to the uniform kernel.
+__device__ __forceinline__ int row_frames(const int32_t* __restrict__ lens, int b, int T) {
+    const int v = lens[b];
+    return v < 0 ? 0 : (v > T ? T : v);
+}
+__device__ __forceinline__ long row_samples(const int32_t* __restrict__ lens, int b, int n_fft, int hop, long n_cap) {
+    const long v = lens[b];
+    if (v < 1) return 0;
+    const long nb = (long)n_fft + (v - 1) * hop;
+    return nb < n_cap ? nb : n_cap;
+}
 
 // ---- rows of the ragged wav -> mel front-end (gvx_wav_to_mel_ragged) ------------------------------------------------------
 // A PCM row is int16 or float32.  wav_row_plan_kernel turns each row's bounds into rows[b] = {first sample, frames T_b} and its

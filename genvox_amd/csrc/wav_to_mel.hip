@@ -3,7 +3,7 @@
 // of silence and peak-normalised per row on the way (gvx_wav_trim_bounds, gvx_wav_to_mel_ragged).  Both calls run one chain,
 // wav_to_mel_chain; n_fft 1024 / hop 256 frames, windows, transforms and takes magnitudes in one kernel (fft512_lds.h), every other
 // size - and GVX_GL_ROCFFT=1 - goes through rocFFT.  The plan, the workspace and the path choice are those of the mel -> wav half
-// (griffinlim.hip, vocoder_internal.h).
+// (griffinlim.hip, vocoder_internal.h); the even/odd split of the real transform is fft512_lds.h's rfft_split.
 //
 // Order of this file: kernels, the host side of the calls, the C ABI.
 #include "fft512_lds.h"
@@ -78,10 +78,12 @@ __global__ __launch_bounds__(GLF_FRAMES * 64) void stft_magnitude_kernel(const P
     __shared__ __attribute__((aligned(16))) float2 fsm[GLF_FRAMES * FPAD];
     const int tid = threadIdx.x, j = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    long f;
-    bool valid;
     float2* buf = fsm + wave * FPAD;
-    float2 v[8];
+    // the frame f of this wave, whether it is transformed, and where its samples start
+    long f;
+    bool valid = true, norm = false;
+    const PCM* xb = x;
+    double peak = 1.0;
     if constexpr (RAGGED) {
         const int b = blockIdx.y, t = (int)blockIdx.x * GLF_FRAMES + wave;
         if (t >= T) return;
@@ -91,33 +93,28 @@ __global__ __launch_bounds__(GLF_FRAMES * 64) void stft_magnitude_kernel(const P
             for (int k = j; k < kp; k += 64) row[k] = 0.f;
             return;
         }
-        valid = true;
-        const PCM* xb = x + (long)b * n_samples + wr.rows[2 * b] + (long)t * 256;
-        const double peak = wr.peak[b];
-        const bool norm = wr.normalize != 0;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            const int n2 = 2 * (j + 64 * r);
-            const float2 w = *reinterpret_cast<const float2*>(win + n2);
-            v[r] = make_float2(w.x * pcm_sample(xb[n2], peak, norm), w.y * pcm_sample(xb[n2 + 1], peak, norm));
-        }
+        xb = x + (long)b * n_samples + wr.rows[2 * b] + (long)t * 256;
+        peak = wr.peak[b];
+        norm = wr.normalize != 0;
     } else {
-    f = (long)blockIdx.x * GLF_FRAMES + wave;
-    valid = f < frames;
-    if (valid) {
-        const unsigned fu = (unsigned)f;
-        const int b = (int)(fu / (unsigned)T), t = (int)(fu - (unsigned)b * (unsigned)T);
-        const float* xb = x + (long)b * n_samples + (long)t * 256;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            const int n2 = 2 * (j + 64 * r);
-            const float2 w = *reinterpret_cast<const float2*>(win + n2);
-            v[r] = make_float2(w.x * xb[n2], w.y * xb[n2 + 1]);   // rows need not be 8-byte aligned (n_samples is arbitrary)
+        f = (long)blockIdx.x * GLF_FRAMES + wave;
+        valid = f < frames;   // a wave behind the last frame still takes part in the transform, on zeros
+        if (valid) {
+            const unsigned fu = (unsigned)f;
+            const int b = (int)(fu / (unsigned)T), t = (int)(fu - (unsigned)b * (unsigned)T);
+            xb = x + (long)b * n_samples + (long)t * 256;
         }
-    } else {
-#pragma unroll
-        for (int r = 0; r < 8; ++r) v[r] = make_float2(0.f, 0.f);
     }
+    // scalar loads: a PCM row, and a float row as well, need not be 8-byte aligned (n_samples is arbitrary)
+    auto sample = [&](int i) -> float { if constexpr (RAGGED) return pcm_sample(xb[i], peak, norm); else return xb[i]; };
+    float2 v[8] = {};
+    if (valid) {
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const int n2 = 2 * (j + 64 * r);
+            const float2 w = *reinterpret_cast<const float2*>(win + n2);
+            v[r] = make_float2(w.x * sample(n2), w.y * sample(n2 + 1));
+        }
     }
     fft512_wave<false>(v, buf, tw, j, true);
     wave_lds_fence();
@@ -127,13 +124,7 @@ __global__ __launch_bounds__(GLF_FRAMES * 64) void stft_magnitude_kernel(const P
     for (int k = j; k < kp; k += 64) {
         float out = 0.f;
         if (k <= 512) {
-            const float2 zk = buf[fpad(k & (FN - 1))];
-            float2 zc = buf[fpad((512 - k) & (FN - 1))];
-            zc.y = -zc.y;
-            const float2 sm = cadd(zk, zc), df = csub(zk, zc);
-            const float2 wd = cmul(tw2[k], df);
-            float2 X = make_float2(0.5f * (sm.x + wd.y), 0.5f * (sm.y - wd.x));
-            if (k == 0 || k == 512) X.y = 0.f;
+            const float2 X = rfft_split(buf[fpad(k & (FN - 1))], buf[fpad((512 - k) & (FN - 1))], tw2[k], k == 0 || k == 512);
             out = hypotf(X.x, X.y);
         }
         row[k] = out;

@@ -2,8 +2,8 @@
 intermediate kept, and the element-wise metrics that hold the HIP kernels to it: what tests/test_vocoder_kernels_gpu.py asserts
 and what tests/test_vocoder_metric_cpu.py shows to bite.
 
-Written from the formulas in oracle/audio_ref.py and the comments of genvox_amd/csrc/griffinlim.hip and wav_to_mel.hip, not from
-their code:
+Written from the formulas in oracle/audio_ref.py and the comments of genvox_amd/csrc/griffinlim.hip, wav_to_mel.hip and
+fft512_lds.h, not from their code:
 NumPy, float64 / complex128 throughout.  Every input (signal, window, mel basis, magnitudes) is an fp32 number converted to
 float64 once; nothing is rounded on the way.  oracle/audio_ref.py - the reference's own float32 arithmetic - stays the parity
 oracle; this file is the yardstick that says how far a float32 computation may be from the exact one.

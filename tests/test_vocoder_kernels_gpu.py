@@ -1,5 +1,6 @@
-"""The vocoder's HIP kernels (genvox_amd/csrc/griffinlim.hip, wav_to_mel.hip) against the float64 restatement
-tests/audio_ref64.py, element by element, at the edges of their workgroups.
+"""The vocoder's HIP kernels (genvox_amd/csrc/griffinlim.hip, wav_to_mel.hip; the real-transform pieces they share are
+csrc/fft512_lds.h, the waveform tail is wav_finalize.hip) against the float64 restatement tests/audio_ref64.py, element by
+element, at the edges of their workgroups.
 
 tests/test_audio_gpu.py holds the same calls to the reference's fixture with aggregates (one number per call); here every bin,
 sample and mel element is checked on its own with the metrics of tests/audio_ref64.py, and the assertion message names the worst
