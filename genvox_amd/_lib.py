@@ -37,6 +37,15 @@ class gvx_melgan_tape_entry(C.Structure):
     _fields_ = [("byte_offset", C.c_uint64), ("positions_per_frame", C.c_int32), ("channels", C.c_int32)]
 
 
+class gvx_melgan_disc_dims(C.Structure):
+    _fields_ = [("n_scales", C.c_int32), ("base_channels", C.c_int32), ("n_layers", C.c_int32), ("downsampling_factor", C.c_int32),
+                ("max_channels", C.c_int32), ("slope", C.c_float)]
+
+
+class gvx_melgan_disc_entry(C.Structure):
+    _fields_ = [("byte_offset", C.c_uint64), ("channels", C.c_int32), ("positions", C.c_int32)]
+
+
 class gvx_stft_resolution(C.Structure):
     _fields_ = [("n_fft", C.c_int32), ("hop", C.c_int32), ("win_length", C.c_int32)]
 
@@ -176,6 +185,16 @@ SIGNATURES = {
     "gvx_melgan_backward_workspace_bytes": (_sz, [C.POINTER(gvx_melgan_dims), _i, _i]),
     "gvx_melgan_forward_train": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _sz, _vp, _sz, _vp]),
     "gvx_melgan_backward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, C.POINTER(gvx_weight_desc), _i, _vp, _vp, _sz, _vp]),
+    "gvx_melgan_disc_blob_floats": (_sz, [C.POINTER(gvx_melgan_disc_dims)]),
+    "gvx_melgan_disc_pack_weights_device": (_i, [C.POINTER(gvx_melgan_disc_dims), C.POINTER(gvx_weight_desc), _i, _vp, _vp]),
+    "gvx_melgan_disc_create": (_i, [C.POINTER(gvx_melgan_disc_dims), C.POINTER(_vp)]),
+    "gvx_melgan_disc_destroy": (None, [_vp]),
+    "gvx_melgan_disc_bind": (_i, [_vp, _vp]),
+    "gvx_melgan_disc_layout": (_i, [C.POINTER(gvx_melgan_disc_dims), _i, _i, C.POINTER(gvx_melgan_disc_entry), _i]),
+    "gvx_melgan_disc_features_bytes": (_sz, [C.POINTER(gvx_melgan_disc_dims), _i, _i]),
+    "gvx_melgan_disc_workspace_bytes": (_sz, [C.POINTER(gvx_melgan_disc_dims), _i, _i, _i]),
+    "gvx_melgan_disc_forward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _sz, _vp]),
+    "gvx_melgan_disc_backward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, C.POINTER(gvx_weight_desc), _i, _vp, _vp, _sz, _vp]),
     "gvx_stft_loss_create": (_i, [C.POINTER(gvx_stft_resolution), _i, _f, _f, _f, C.POINTER(_vp)]),
     "gvx_stft_loss_destroy": (None, [_vp]),
     "gvx_stft_loss_workspace_bytes": (_sz, [_vp, _i, _l]),

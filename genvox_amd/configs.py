@@ -214,3 +214,58 @@ class MelGANConfig(BaseConfig):
     def check_hop(self, hop_length: int) -> None:
         if self.hop != int(hop_length):
             raise ValueError(f"upsample_ratios {tuple(self.upsample_ratios)} multiply to {self.hop}, the audio config's hop_length is {hop_length}")
+
+
+class MelGANDiscriminatorConfig(BaseConfig):
+    """The multi-scale discriminator a MelGAN generator is trained against (include/genvox_amd.h, "MelGAN discriminators").  The
+    reference ships no such model or config; the defaults are the published architecture's (Kumar et al. 2019)."""
+
+    _FIELDS = {
+        "n_scales": (3, None),
+        "base_channels": (16, None),
+        "n_layers": (4, None),
+        "downsampling_factor": (4, None),
+        "max_channels": (1024, None),
+        "leaky_slope": (0.2, None),
+    }
+
+    def _normalise(self) -> None:
+        for name in ("n_scales", "base_channels", "n_layers", "downsampling_factor", "max_channels"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise ValueError(f"{name} must be an integer, not {v!r}")
+        if not 1 <= self.n_scales <= 4:
+            raise ValueError(f"n_scales = {self.n_scales} is outside [1, 4]")
+        if self.base_channels < 4 or self.base_channels % 4:
+            raise ValueError(f"base_channels = {self.base_channels} must be a positive multiple of 4 (grouped layers take 4 input channels per group)")
+        if not 1 <= self.n_layers <= 6:
+            raise ValueError(f"n_layers = {self.n_layers} is outside [1, 6]")
+        if not 1 <= self.downsampling_factor <= 8:
+            raise ValueError(f"downsampling_factor = {self.downsampling_factor} is outside [1, 8]")
+        if not 4 <= self.max_channels <= 65536:
+            raise ValueError(f"max_channels = {self.max_channels} is outside [4, 65536]")
+        if not 0.0 <= float(self.leaky_slope) <= 1.0:
+            raise ValueError(f"leaky_slope = {self.leaky_slope} is outside [0, 1]")
+        for i, (cin, cout, _k, _stride, _pad, groups) in enumerate(self.layer_shapes()):
+            if cin % groups or cout % groups or (groups > 1 and cin != 4 * groups):
+                raise ValueError(f"layer {i}: {cin} -> {cout} channels cannot be split into {groups} groups of 4 input channels")
+
+    def layer_shapes(self):
+        """The n_layers + 3 convolutions of one scale as (c_in, c_out, taps, stride, padding, groups)."""
+        s, c = self.downsampling_factor, self.base_channels
+        shapes = [(1, c, 15, 1, 7, 1)]
+        for _ in range(self.n_layers):
+            cn = min(c * s, self.max_channels)
+            shapes.append((c, cn, 10 * s + 1, s, 5 * s, max(c // 4, 1)))
+            c = cn
+        c2 = min(2 * c, self.max_channels)
+        shapes += [(c, c2, 5, 1, 2, 1), (c2, 1, 3, 1, 1, 1)]
+        return shapes
+
+    @property
+    def min_samples(self) -> int:
+        """The shortest row: the last scale still reflects 7 samples."""
+        return 8 << (self.n_scales - 1)
+
+    def parameter_count(self) -> int:
+        return self.n_scales * sum(cout * (cin // g) * k + cout for cin, cout, k, _s, _p, g in self.layer_shapes())

@@ -154,3 +154,55 @@ class MultiResolutionSTFTLoss(torch.nn.Module):
         _, lens_dev = self._check(pred, target, sample_lengths)
         want_grad = pred.requires_grad and torch.is_grad_enabled()
         return _STFTLossFunction.apply(pred, target, lens_dev, self, want_grad)
+
+
+# ---- the adversarial losses of the MelGAN step: small elementwise reductions over the discriminator's maps, in plain torch
+def _row_mean(values: torch.Tensor, lengths) -> torch.Tensor:
+    """values [B, C, L] -> the mean over rows of each row's mean over its own C x L_b elements (``lengths`` None: all L)."""
+    B, Cn, L = values.shape
+    if lengths is None:
+        return values.mean(dim=(1, 2)).mean()
+    lens = torch.as_tensor(lengths, device=values.device).to(torch.int64).reshape(B)
+    inside = (torch.arange(L, device=values.device)[None, :] < lens[:, None])[:, None, :]
+    return (torch.where(inside, values, torch.zeros((), dtype=values.dtype, device=values.device)).sum(dim=(1, 2)) / (Cn * lens).to(values.dtype)).mean()
+
+
+def _lengths_of(map_lengths, k: int, i: int):
+    return None if map_lengths is None else map_lengths[k][i]
+
+
+class MelGANDiscriminatorLoss(torch.nn.Module):
+    """Hinge loss of the discriminator: the sum over the scales of mean(relu(1 - D(real))) + mean(relu(1 + D(fake))) on the scores (the
+    last map of every scale).  ``map_lengths[k][i]`` ([B] per map, ``MelGANDiscriminator.map_lengths``) makes every mean a mean per row
+    over the row's own positions, then over rows - the rule of MultiResolutionSTFTLoss - so ragged rows never see each other's padding."""
+
+    def forward(self, real, fake, map_lengths=None) -> torch.Tensor:
+        loss = 0.0
+        for k, (r, f) in enumerate(zip(real, fake)):
+            lens = _lengths_of(map_lengths, k, len(r) - 1)
+            loss = loss + _row_mean(torch.relu(1.0 - r[-1]), lens) + _row_mean(torch.relu(1.0 + f[-1]), lens)
+        return loss
+
+
+class MelGANGeneratorLoss(torch.nn.Module):
+    """The generator's side: adversarial = the sum over the scales of -mean(D(fake)) on the scores; feature matching = ``feat_match``
+    times the L1 distance between the fake and the (detached) real features over every non-score map, each map weighted
+    4 / (n_layers + 1) / n_scales as in the published implementation (n_layers + 1 = the maps of a scale without its last feature map
+    and its score).  Means as in MelGANDiscriminatorLoss.  ``last_terms`` holds (adversarial, feature matching) of the last call."""
+
+    def __init__(self, feat_match: float = 10.0) -> None:
+        super().__init__()
+        self.feat_match = float(feat_match)
+        self.last_terms = None
+
+    def forward(self, real, fake, map_lengths=None) -> torch.Tensor:
+        n_scales = len(fake)
+        adv, fm = 0.0, 0.0
+        for k, (r, f) in enumerate(zip(real, fake)):
+            adv = adv - _row_mean(f[-1], _lengths_of(map_lengths, k, len(f) - 1))
+            weight = 4.0 / (len(f) - 2) / n_scales   # len(f) = n_layers + 3 maps
+            for i in range(len(f) - 1):
+                fm = fm + weight * _row_mean((f[i] - r[i].detach()).abs(), _lengths_of(map_lengths, k, i))
+        fm = self.feat_match * fm
+        self.last_terms = (adv, fm)
+        return adv + fm

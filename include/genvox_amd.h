@@ -1067,6 +1067,90 @@ int gvx_melgan_backward(gvx_melgan* handle, const float* d_wav, const int32_t* f
                         size_t tape_bytes, const gvx_grad_desc* grads, int n_grads, float* d_mel_out, void* workspace,
                         size_t workspace_bytes, void* stream);
 
+/* ---- MelGAN discriminators: the multi-scale discriminator a MelGAN generator is trained against (Kumar et al. 2019), forward and
+ * backward.  The reference ships the training fields of MelGANConfig and no model; this is a statement of the published architecture.
+ * All arithmetic is fp32.  lrelu and "reflect" as for the generator above; s = downsampling_factor.
+ *
+ * One scale, on a row of n samples:
+ *     layer 0:                Conv1d(1 -> c_0 = base_channels, k = 15)(reflect 7 (x)), lrelu                             length n
+ *     layers i = 1..n_layers: c_i = min(c_{i-1} s, max_channels);
+ *                             Conv1d(c_{i-1} -> c_i, k = 10 s + 1, stride s, zero padding 5 s, groups = c_{i-1} / 4), lrelu
+ *                                                                                             length L_i = (L_{i-1} - 1) / s + 1
+ *     layer n_layers + 1:     c' = min(2 c_last, max_channels);  Conv1d(c_last -> c', k = 5, zero padding 2), lrelu
+ *     layer n_layers + 2:     the score, Conv1d(c' -> 1, k = 3, zero padding 1), no activation
+ * and all n_layers + 3 maps are returned (post-activation; the last is the score).  Scale k + 1 sees the waveform of scale k through
+ * AvgPool1d(4, stride 2, padding 1, count_include_pad = False): y[j] = the mean of x[2j-1 .. 2j+2] inside [0, n), j < n / 2.
+ *
+ * Ragged batches: sample_lengths is int32 [B] on the device, or NULL for all n_max.  Row b is computed as if alone at n_b =
+ * min(sample_lengths[b], n_max): the reflection, the zero padding, every pooled length n_b >> k and every L_i are its own; nothing of wav
+ * at or behind n_b is read; every map is exact zeros behind the row's own length; a ragged row has the bits of its one-row run.  A row
+ * needs n_b >= 8 * 2^(n_scales - 1) (the last scale's reflection); the host cannot see device lengths, so the CALLER checks them - a
+ * shorter row comes out as all-zero maps.
+ *
+ * Dims are refused (GVX_ERR_INVALID_ARG from create and pack, 0 from the size functions) unless: n_scales in [1, 4]; base_channels a
+ * positive multiple of 4; n_layers in [1, 6]; downsampling_factor in [1, 8]; max_channels in [4, 65536]; slope in [0, 1]; and every
+ * grouped layer's input channels are a multiple of 4 and its output channels divisible by its group count.
+ *
+ * Weights.  gvx_melgan_disc_pack_weights_device reads PyTorch-layout tensors from DEVICE pointers, by name:
+ *     scales.<k>.layers.<i>.weight [c_out][c_in / groups][taps], scales.<k>.layers.<i>.bias [c_out],   i = 0 .. n_layers + 2
+ * and writes the blob, which keeps those layouts, every tensor starting at a multiple of 64 floats (gvx_melgan_disc_blob_floats).  A
+ * missing name is GVX_ERR_MISSING_WEIGHT, a wrong element count GVX_ERR_SHAPE, both before anything is launched.  The blob must be
+ * 256-byte aligned; the handle keeps the pointer.
+ *
+ * Features buffer: the caller's, 256-byte aligned, gvx_melgan_disc_features_bytes long.  gvx_melgan_disc_layout (host arithmetic) lists,
+ * scale by scale and layer by layer, (byte offset, channels, positions): map (k, i) is fp32 [B][channels][positions] with positions =
+ * L_i of a row of n_max >> k samples, every map starting at a multiple of 256 bytes.  It returns the number of entries,
+ * n_scales * (n_layers + 3), and fills at most max_entries of them (entries may be NULL); 0 for refused dims, B or n_max.
+ *
+ * Workspace: gvx_melgan_disc_workspace_bytes(dims, B, n_max, backward) is host arithmetic; any contents when a call starts, nothing is
+ * cleared, 256-byte aligned.  The forward's (backward = 0) holds the pooled waveforms of the scales behind the first.  The backward's
+ * holds those again (it recomputes them from wav), their gradients, two activation gradients of the largest map, and the partial
+ * weight gradients of the layer that needs most.
+ *
+ * gvx_melgan_disc_forward: a chain of ordinary launches on `stream`, one per layer and one per pooling; a workgroup computes
+ * GVX_MELGAN_DISC_TILE positions of one row.  Refused before anything is launched: a NULL handle, wav or features, B outside [1, 65535],
+ * n_max below 8 * 2^(n_scales - 1) (GVX_ERR_INVALID_ARG); n_max above GVX_MELGAN_DISC_MAX_SAMPLES (GVX_ERR_UNSUPPORTED); no blob
+ * bound (GVX_ERR_STATE); a misaligned or short features buffer, a NULL, misaligned or short workspace (GVX_ERR_WORKSPACE).
+ *
+ * gvx_melgan_disc_backward: features is what the forward wrote for the same wav, lengths and weights - it is the tape: a LeakyReLU
+ * output is positive exactly where its pre-activation is, so the masks are read off the maps.  d_features has the layout of features
+ * and holds the cotangent of EVERY map (a feature-matching loss feeds all of them); nothing of it is read behind a row's own
+ * lengths.  grads is a HOST table of n_grads DEVICE destinations under the packer's names, each WRITTEN in PyTorch's layout; n_grads = 0
+ * skips every parameter gradient (the generator's step).  d_wav is fp32 [B][n_max], the sum over the scales through the adjoint of the
+ * pooling, exactly 0 at and behind n_b, or NULL to skip it (the discriminator's step).  What a call does compute has the bits the full
+ * call gives it.  Refused as the forward refuses, and: a missing name (GVX_ERR_MISSING_WEIGHT), a wrong element count or NULL
+ * destination (GVX_ERR_SHAPE), a NULL d_features, or neither gradient asked for (GVX_ERR_INVALID_ARG).  Weight gradients are summed
+ * over rows and positions in pieces that are added in a fixed order; no float atomics: two calls give the same bits. */
+enum { GVX_MELGAN_DISC_MAX_SCALES = 4, GVX_MELGAN_DISC_TILE = 64, GVX_MELGAN_DISC_MAX_SAMPLES = 1 << 24 };
+typedef struct gvx_melgan_disc_dims {
+    int32_t n_scales;
+    int32_t base_channels;
+    int32_t n_layers;
+    int32_t downsampling_factor;
+    int32_t max_channels;
+    float slope;
+} gvx_melgan_disc_dims;
+typedef struct gvx_melgan_disc_entry {
+    uint64_t byte_offset;
+    int32_t channels;
+    int32_t positions;
+} gvx_melgan_disc_entry;
+typedef struct gvx_melgan_disc gvx_melgan_disc;
+size_t gvx_melgan_disc_blob_floats(const gvx_melgan_disc_dims* dims);
+int gvx_melgan_disc_pack_weights_device(const gvx_melgan_disc_dims* dims, const gvx_weight_desc* table, int n, float* device_blob,
+                                        void* stream);
+int gvx_melgan_disc_create(const gvx_melgan_disc_dims* dims, gvx_melgan_disc** out);
+void gvx_melgan_disc_destroy(gvx_melgan_disc* handle);
+int gvx_melgan_disc_bind(gvx_melgan_disc* handle, const float* device_blob);
+int gvx_melgan_disc_layout(const gvx_melgan_disc_dims* dims, int B, int n_max, gvx_melgan_disc_entry* entries, int max_entries);
+size_t gvx_melgan_disc_features_bytes(const gvx_melgan_disc_dims* dims, int B, int n_max);
+size_t gvx_melgan_disc_workspace_bytes(const gvx_melgan_disc_dims* dims, int B, int n_max, int backward);
+int gvx_melgan_disc_forward(gvx_melgan_disc* handle, const float* wav, const int32_t* sample_lengths, int B, int n_max, void* features,
+                            size_t features_bytes, void* workspace, size_t workspace_bytes, void* stream);
+int gvx_melgan_disc_backward(gvx_melgan_disc* handle, const float* wav, const int32_t* sample_lengths, int B, int n_max,
+                             const void* features, const void* d_features, const gvx_grad_desc* grads, int n_grads, float* d_wav,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Multi-resolution STFT loss: the distance between a predicted waveform and its target that a vocoder is trained on (spectral
  * convergence plus log-magnitude L1 over several STFT resolutions; Yamamoto et al., Parallel WaveGAN), value and gradient in one call.
  * The reference ships no vocoder loss; this is the standard non-adversarial one, on the in-LDS transforms of the vocoder kernels.

@@ -14,7 +14,12 @@ same float32 network through torch's own ROCm convolutions and against Griffin-L
 frames between device events, against autograd through torch's own convolutions on the same parameters, with the tape's size;
 `mrstft` (on request): the multi-resolution STFT loss, value + gradient (MultiResolutionSTFTLoss + `backward()`: one gvx_stft_loss call),
 at 16 x 8192 and 8 x 32768 samples with the default resolutions between device events, median of 7, against the same loss written
-with torch.stft + autograd on the same device, with the workspace's size."""
+with torch.stft + autograd on the same device, with the workspace's size;
+`melgan_disc` (on request): the MelGAN discriminator at 16 x 8192 and 8 x 32768 samples (the `mrstft` shapes) between device events,
+median of 7 with the spread: forward, forward + full backward (cotangents on every map), and the whole `MelGANTrainer.train_step` with
+the default generator, against the same discriminator built from torch.nn modules that hold the same (seeded) parameters, through
+torch's own convolutions and autograd; with the count of LeakyReLU decisions on which the two forwards differ and the gradient
+difference again with torch differentiating through the device's own decisions."""
 import json
 import os
 import sys
@@ -416,6 +421,111 @@ def main():
             res[key]["max_relative_gradient_difference_from_torch"] = float((got - pred.grad).abs().max() / pred.grad.abs().max())
             res[key]["workspace_mb"] = round(crit._workspace.numel() / 1e6, 1)
             print(json.dumps({key: res[key]}), flush=True)
+    if "melgan_disc" in which:
+        import statistics
+
+
+        from genvox_amd.configs import MelGANConfig, MelGANDiscriminatorConfig
+        from genvox_amd.melgan import MelGANGenerator
+        from genvox_amd.melgan_disc import MelGANDiscriminator
+        from genvox_amd.melgan_training import MelGANTrainer
+
+        def ev_spread(fn, warm=2, reps=7):
+            for _ in range(warm):
+                fn()
+            out = []
+            for _ in range(reps):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                e1.synchronize()
+                out.append(e0.elapsed_time(e1))
+            return {"median_ms": round(statistics.median(out), 3), "min_ms": round(min(out), 3), "max_ms": round(max(out), 3), "runs": reps}
+
+        torch.manual_seed(0)   # the same weights every run: the differences from torch below are comparable between runs
+        dc = MelGANDiscriminatorConfig()
+        disc = MelGANDiscriminator(dc).to("cuda:0")
+        with torch.no_grad():
+            for name, p in disc.named_parameters():
+                if name.endswith("bias"):
+                    p.copy_(0.1 * torch.randn_like(p))
+        dparams = dict(disc.named_parameters())
+        shapes = dc.layer_shapes()
+
+        class TorchDisc(torch.nn.Module):
+            """The same float32 network from torch.nn modules; its convolutions hold the discriminator's own parameters.  ``pin``:
+            [scale][map] masks in {1, slope} that replace every LeakyReLU by a product (the device's own decisions)."""
+
+            def __init__(self):
+                super().__init__()
+                self.pad, self.act = torch.nn.ReflectionPad1d(7), torch.nn.LeakyReLU(dc.leaky_slope)
+                self.pool = torch.nn.AvgPool1d(4, stride=2, padding=1, count_include_pad=False)
+                self.scales = torch.nn.ModuleList()
+                for k in range(dc.n_scales):
+                    convs = torch.nn.ModuleList()
+                    for i, (ci, co, kk, stride, pad, groups) in enumerate(shapes):
+                        conv = torch.nn.Conv1d(ci, co, kk, stride=stride, padding=0 if i == 0 else pad, groups=groups)
+                        conv.weight, conv.bias = dparams[f"scales.{k}.layers.{i}.weight"], dparams[f"scales.{k}.layers.{i}.bias"]
+                        convs.append(conv)
+                    self.scales.append(convs)
+
+            def forward(self, wav, pin=None):
+                out, x = [], wav[:, None, :]
+                for k, convs in enumerate(self.scales):
+                    maps, h = [], x
+                    for i, conv in enumerate(convs):
+                        h = conv(self.pad(h) if i == 0 else h)
+                        if i < len(convs) - 1:
+                            h = self.act(h) if pin is None else h * pin[k][i]
+                        maps.append(h)
+                    out.append(maps)
+                    x = self.pool(x)
+                return out
+
+        torch_disc = TorchDisc().to("cuda:0")
+
+        voc = MelGANGenerator(MelGANConfig(), ac).to("cuda:0")
+        gen = torch.Generator(device="cuda").manual_seed(0)
+        for B, n in ((16, 8192), (8, 32768)):
+            key = f"melgan_disc_{B}x{n}"
+            wav = (0.3 * torch.randn(B, n, device="cuda", generator=gen)).requires_grad_(True)
+            with torch.no_grad():
+                ours_maps, torch_maps = disc(wav), torch_disc(wav)
+                res[key] = {"forward": ev_spread(lambda: disc(wav)), "torch_forward": ev_spread(lambda: torch_disc(wav))}
+            res[key]["max_relative_map_difference_from_torch"] = max(float((a - b).abs().max() / b.abs().max()) for x, y in zip(ours_maps, torch_maps) for a, b in zip(x, y))
+            cots = [[torch.randn(m.shape, device="cuda", generator=gen) / m.numel() for m in ms] for ms in ours_maps]
+
+            def step(net):
+                wav.grad = None
+                for p in dparams.values():
+                    p.grad = None
+                sum((m * c).sum() for ms, cs in zip(net(wav), cots) for m, c in zip(ms, cs)).backward()
+
+            res[key]["forward_plus_backward"] = ev_spread(lambda: step(disc))
+            got = {k: p.grad.clone() for k, p in dparams.items()}
+            got["wav"] = wav.grad.clone()
+            res[key]["torch_forward_plus_backward"] = ev_spread(lambda: step(torch_disc))
+
+            def grad_difference():
+                return max([float((got[k] - p.grad).abs().max() / p.grad.abs().max().clamp_min(1e-30)) for k, p in dparams.items()]
+                           + [float((got["wav"] - wav.grad).abs().max() / wav.grad.abs().max())])
+
+            res[key]["max_relative_gradient_difference_from_torch"] = grad_difference()
+            # where the two forwards put a LeakyReLU on different sides (pre-activations within rounding of 0), and the same comparison
+            # with torch differentiating through the device's own decisions
+            res[key]["leaky_relu_decisions_that_differ"] = sum(int(((a > 0) != (b > 0)).sum()) for x, y in zip(ours_maps, torch_maps) for a, b in zip(x[:-1], y[:-1]))
+            one, low = torch.ones((), device="cuda"), torch.full((), dc.leaky_slope, device="cuda")
+            pin = [[torch.where(m > 0, one, low) for m in ms] for ms in ours_maps]
+            step(lambda w: torch_disc(w, pin))
+            res[key]["max_relative_gradient_difference_from_torch_pinned"] = grad_difference()
+            res[key]["backward_workspace_mb"] = round(disc._train_workspace.numel() / 1e6, 1)
+            print(json.dumps({key: res[key]}), flush=True)
+            trainer = MelGANTrainer(voc, disc)
+            mel = (0.5 * torch.randn(B, 80, n // voc.hop, device="cuda", generator=gen) - 0.5).contiguous()
+            real = wav.detach()
+            res[key]["train_step"] = ev_spread(lambda: trainer.train_step(mel, real), warm=2, reps=5)
+            print(json.dumps({key: {"train_step": res[key]["train_step"]}}), flush=True)
     if "cpu" in which:
         # CPU baselines for configs 3 and 4 (the oracle = CPU restatement of the reference, on this box's host cores):
         # bounded samples, reported beside the GPU figures above; bench.py carries the one for config 2.
