@@ -2,11 +2,12 @@
 
     from genvox_amd import Tacotron2, Synthesizer, AudioProcessor, Tacotron2Config, AudioConfig, TextConfig
     from genvox_amd import MelGANGenerator, MelGANConfig   # neural vocoder: Synthesizer(..., vocoder_model_class=MelGANGenerator, ...)
+    from genvox_amd import HiFiGANGenerator, HiFiGANConfig   # HiFi-GAN V1 / V2 / V3 generators, the same place in Synthesizer
     from genvox_amd import Tacotron2GuidedLoss    # training criterion: Tacotron2Loss + alpha x guided attention loss
     from genvox_amd import MelGANDiscriminator, MelGANDiscriminatorConfig, MelGANTrainer   # the other side of the vocoder's GAN step
     from genvox_amd import MultiResolutionSTFTLoss, stft_distance   # vocoder training loss / waveform distance on the device
 """
-from .configs import AudioConfig, BaseConfig, MelGANConfig, MelGANDiscriminatorConfig, Tacotron2Config, TextConfig  # noqa: F401
+from .configs import AudioConfig, BaseConfig, HiFiGANConfig, MelGANConfig, MelGANDiscriminatorConfig, Tacotron2Config, TextConfig  # noqa: F401
 
 
 def __getattr__(name):  # torch-dependent classes are imported lazily
@@ -19,6 +20,9 @@ def __getattr__(name):  # torch-dependent classes are imported lazily
     if name == "MelGANGenerator":
         from .melgan import MelGANGenerator
         return MelGANGenerator
+    if name == "HiFiGANGenerator":
+        from .hifigan import HiFiGANGenerator
+        return HiFiGANGenerator
     if name == "MelGANDiscriminator":
         from .melgan_disc import MelGANDiscriminator
         return MelGANDiscriminator

@@ -33,6 +33,13 @@ class gvx_melgan_dims(C.Structure):
                 ("n_residual_layers", C.c_int32), ("dilation_base", C.c_int32), ("slope", C.c_float)]
 
 
+class gvx_hifigan_dims(C.Structure):
+    _fields_ = [("n_mels", C.c_int32), ("upsample_initial_channel", C.c_int32), ("n_stages", C.c_int32), ("upsample_rates", C.c_int32 * 8),
+                ("upsample_kernel_sizes", C.c_int32 * 8), ("resblock", C.c_int32), ("n_resblocks", C.c_int32), ("n_dilations", C.c_int32),
+                ("resblock_kernel_sizes", C.c_int32 * 4), ("resblock_dilation_sizes", (C.c_int32 * 3) * 4), ("slope", C.c_float),
+                ("post_slope", C.c_float)]
+
+
 class gvx_melgan_tape_entry(C.Structure):
     _fields_ = [("byte_offset", C.c_uint64), ("positions_per_frame", C.c_int32), ("channels", C.c_int32)]
 
@@ -185,6 +192,15 @@ SIGNATURES = {
     "gvx_melgan_backward_workspace_bytes": (_sz, [C.POINTER(gvx_melgan_dims), _i, _i]),
     "gvx_melgan_forward_train": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _sz, _vp, _sz, _vp]),
     "gvx_melgan_backward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, C.POINTER(gvx_weight_desc), _i, _vp, _vp, _sz, _vp]),
+    "gvx_hifigan_blob_floats": (_sz, [C.POINTER(gvx_hifigan_dims)]),
+    "gvx_hifigan_workspace_bytes": (_sz, [C.POINTER(gvx_hifigan_dims), _i, _i]),
+    "gvx_hifigan_pack_weights_device": (_i, [C.POINTER(gvx_hifigan_dims), C.POINTER(gvx_weight_desc), _i, _vp, _vp]),
+    "gvx_hifigan_create": (_i, [C.POINTER(gvx_hifigan_dims), C.POINTER(_vp)]),
+    "gvx_hifigan_destroy": (None, [_vp]),
+    "gvx_hifigan_bind": (_i, [_vp, _vp]),
+    "gvx_hifigan_forward": (_i, [_vp, _vp, _vp, _i, _i, _vp, C.POINTER(_vp), _vp, _sz, _vp]),
+    "gvx_hifigan_timing_enable": (_i, [_vp, _i]),
+    "gvx_hifigan_stage_times_ms": (_i, [_vp, C.POINTER(_f), C.POINTER(_i)]),
     "gvx_melgan_disc_blob_floats": (_sz, [C.POINTER(gvx_melgan_disc_dims)]),
     "gvx_melgan_disc_pack_weights_device": (_i, [C.POINTER(gvx_melgan_disc_dims), C.POINTER(gvx_weight_desc), _i, _vp, _vp]),
     "gvx_melgan_disc_create": (_i, [C.POINTER(gvx_melgan_disc_dims), C.POINTER(_vp)]),

@@ -269,3 +269,89 @@ class MelGANDiscriminatorConfig(BaseConfig):
 
     def parameter_count(self) -> int:
         return self.n_scales * sum(cout * (cin // g) * k + cout for cin, cout, k, _s, _p, g in self.layer_shapes())
+
+
+class HiFiGANConfig(BaseConfig):
+    """The HiFi-GAN generator (Kong et al. 2020; include/genvox_amd.h, "HiFi-GAN generator").  The reference ships no such model; the
+    fields carry the names of the published implementation's ``config.json`` and the defaults of its V1 generator, followed by the
+    two LeakyReLU slopes, which that implementation keeps in its code.  ``upsample_rates`` must multiply to the audio config's
+    ``hop_length`` (``check_hop``: the config alone does not know it)."""
+
+    MAX_WINDOW = 72   # GVX_HIFIGAN_MAX_WINDOW: the largest (kernel size - 1) * dilation, V3's k = 7 at d = 12
+
+    _FIELDS = {
+        "upsample_initial_channel": (512, None),
+        "upsample_rates": ((8, 8, 2, 2), None),
+        "upsample_kernel_sizes": ((16, 16, 4, 4), None),
+        "resblock": ("1", None),
+        "resblock_kernel_sizes": ((3, 7, 11), None),
+        "resblock_dilation_sizes": (((1, 3, 5), (1, 3, 5), (1, 3, 5)), None),
+        "leaky_slope": (0.1, None),
+        "post_leaky_slope": (0.01, None),
+    }
+
+    def _normalise(self) -> None:
+        try:   # lists: what a yaml or json file holds
+            self.upsample_rates = [int(r) for r in self.upsample_rates]
+            self.upsample_kernel_sizes = [int(k) for k in self.upsample_kernel_sizes]
+            self.resblock_kernel_sizes = [int(k) for k in self.resblock_kernel_sizes]
+            self.resblock_dilation_sizes = [[int(d) for d in ds] for ds in self.resblock_dilation_sizes]
+        except (TypeError, ValueError):
+            raise ValueError("upsample_rates, upsample_kernel_sizes and resblock_kernel_sizes must be sequences of integers and "
+                             "resblock_dilation_sizes a sequence of such sequences") from None
+        self.resblock = str(self.resblock)
+        c0 = self.upsample_initial_channel
+        if isinstance(c0, bool) or not isinstance(c0, int) or c0 < 1:
+            raise ValueError(f"upsample_initial_channel must be an integer >= 1, not {c0!r}")
+        if self.resblock not in ("1", "2"):
+            raise ValueError(f"resblock must be '1' or '2', not {self.resblock!r}")
+        n = len(self.upsample_rates)
+        if not 1 <= n <= 8:
+            raise ValueError(f"upsample_rates must name 1 to 8 stages, not {n}")
+        if len(self.upsample_kernel_sizes) != n:
+            raise ValueError(f"{len(self.upsample_kernel_sizes)} upsample_kernel_sizes for {n} upsample_rates")
+        for r, k in zip(self.upsample_rates, self.upsample_kernel_sizes):
+            if r < 2 or r % 2:
+                raise ValueError(f"every upsampling rate must be even and >= 2, not {r}")
+            if k != 2 * r:
+                raise ValueError(f"upsample_kernel_sizes[i] must be 2 * upsample_rates[i] (kernel 2r, stride r, padding r/2: the only form "
+                                 f"supported, which covers the published V1, V2 and V3), not kernel {k} at rate {r}")
+        if self.hop > 4096:
+            raise ValueError(f"upsample_rates multiply to {self.hop}, above 4096")
+        if c0 % (1 << n) or (c0 >> n) < 4 or (c0 >> n) % 4:
+            raise ValueError(f"upsample_initial_channel = {c0}: every stage halves the channels, and every stage's channel count must be a "
+                             f"multiple of 4 and at least 4")
+        if not 1 <= len(self.resblock_kernel_sizes) <= 4:
+            raise ValueError(f"there must be 1 to 4 resblock_kernel_sizes, not {len(self.resblock_kernel_sizes)}")
+        if len(self.resblock_dilation_sizes) != len(self.resblock_kernel_sizes):
+            raise ValueError(f"{len(self.resblock_dilation_sizes)} resblock_dilation_sizes for {len(self.resblock_kernel_sizes)} resblock_kernel_sizes")
+        n_dil = 3 if self.resblock == "1" else 2
+        for k, ds in zip(self.resblock_kernel_sizes, self.resblock_dilation_sizes):
+            if k < 3 or k > 11 or k % 2 == 0:
+                raise ValueError(f"every resblock kernel size must be odd and in [3, 11], not {k}")
+            if len(ds) != n_dil:
+                raise ValueError(f"resblock '{self.resblock}' has {n_dil} dilations per block, not {len(ds)}")
+            for d in ds:
+                if d < 1:
+                    raise ValueError(f"every dilation must be >= 1, not {d}")
+                if (k - 1) * d > self.MAX_WINDOW:
+                    raise ValueError(f"(kernel size - 1) * dilation = {(k - 1) * d} (k = {k}, d = {d}) is above the window cap of {self.MAX_WINDOW}")
+        for name in ("leaky_slope", "post_leaky_slope"):
+            if not 0.0 <= float(getattr(self, name)) <= 1.0:
+                raise ValueError(f"{name} = {getattr(self, name)} is outside [0, 1]")
+
+    @property
+    def hop(self) -> int:
+        hop = 1
+        for r in self.upsample_rates:
+            hop *= r
+        return hop
+
+    def check_hop(self, hop_length: int) -> None:
+        if self.hop != int(hop_length):
+            raise ValueError(f"upsample_rates {tuple(self.upsample_rates)} multiply to {self.hop}, the audio config's hop_length is {hop_length}")
+
+    @classmethod
+    def from_published(cls, config: Mapping[str, Any]) -> "HiFiGANConfig":
+        """The generator's part of a published ``config.json`` (as a dict); that file's training and audio keys are ignored."""
+        return cls(**{k: config[k] for k in cls._FIELDS if k in config})

@@ -1067,6 +1067,91 @@ int gvx_melgan_backward(gvx_melgan* handle, const float* d_wav, const int32_t* f
                         size_t tape_bytes, const gvx_grad_desc* grads, int n_grads, float* d_mel_out, void* workspace,
                         size_t workspace_bytes, void* stream);
 
+/* ---- HiFi-GAN generator, mel -> waveform, inference (Kong et al. 2020; its V1, V2 and V3 generators).  The reference ships no such
+ * model; the network below is the published implementation's, under its names.  Kernels: csrc/hifigan.hip; all arithmetic is fp32.
+ *
+ * Input: mel fp32 [B][n_mels][T].  Output: wav fp32 [B][T * hop], hop = the product of upsample_rates, every sample in (-1, 1).
+ * lrelu(v, s) = v > 0 ? v : s * v.  Every convolution pads with ZEROS.  C_0 = upsample_initial_channel, C_{i+1} = C_i / 2, n_k =
+ * n_resblocks.
+ *
+ *     x = Conv1d(n_mels -> C_0, k = 7, padding 3)(mel)                                                       conv_pre
+ *     for stage i, r = upsample_rates[i]:
+ *         x = ConvTranspose1d(C_i -> C_{i+1}, kernel 2 r, stride r, padding r / 2)(lrelu(x, slope))          ups.<i>, length times r
+ *         y_j = resblocks.<i * n_k + j>(x) for j = 0 .. n_k - 1;   x = (y_0 + y_1 + ..) / n_k                 added in that order, then divided
+ *     wav = tanh(Conv1d(C_last -> 1, k = 7, padding 3)(lrelu(x, post_slope)))                                conv_post
+ *
+ *     resblock 1, kernel k = resblock_kernel_sizes[j], dilations d_m = resblock_dilation_sizes[j][m], m = 0 .. 2:
+ *         x = x + convs2.<m>(lrelu(convs1.<m>(lrelu(x, slope)), slope))      convs1: dilation d_m, padding (k - 1) d_m / 2; convs2: dilation 1
+ *     resblock 2, m = 0 .. 1:
+ *         x = x + convs.<m>(lrelu(x, slope))                                 dilation d_m, padding (k - 1) d_m / 2
+ *
+ * Ragged batches: frame_lengths is int32 [B] on the device, or NULL for all T.  Row b is computed at T_b = min(frame_lengths[b], T)
+ * frames as that row run alone: at every layer zeros lie beyond the row's own T_b * (rates so far) positions.  Nothing of mel at or
+ * behind frame T_b is read, and wav is exactly 0 from sample T_b * hop on.  The shortest row is 1 frame; the host cannot see device
+ * lengths, so the CALLER checks them - a row below 1 frame comes out as silence of length 0.
+ *
+ * Dims are refused (GVX_ERR_INVALID_ARG from create and pack, 0 from the size functions) unless: n_mels >= 1; n_stages in [1,
+ * GVX_HIFIGAN_MAX_STAGES]; every rate even and >= 2 with upsample_kernel_sizes[i] == 2 * upsample_rates[i] (the two-tap phase split;
+ * it covers the three published configurations), their product <= GVX_HIFIGAN_MAX_HOP; upsample_initial_channel divisible by
+ * 2^n_stages and every stage's channel count C_{i+1} a multiple of 4 and >= 4; resblock 1 with n_dilations 3 or resblock 2 with
+ * n_dilations 2; n_resblocks in [1, GVX_HIFIGAN_MAX_RESBLOCKS]; every resblock kernel size odd and in [3, 11]; every dilation >= 1 with
+ * (k - 1) * d <= GVX_HIFIGAN_MAX_WINDOW (72: V3's k = 7, d = 12); slope and post_slope in [0, 1].
+ *
+ * Weights.  gvx_hifigan_pack_weights_device reads PyTorch-layout tensors from DEVICE pointers, by the published names:
+ *     conv_pre.weight [C_0][n_mels][7];  ups.<i>.weight [C_i][C_{i+1}][2 r] (ConvTranspose1d: in, out, k);
+ *     resblocks.<n>.convs1.<m>.weight / .convs2.<m>.weight [C][C][k] (resblock 2: .convs.<m>.weight);  conv_post.weight [1][C_last][7];
+ *     and every layer's .bias
+ * (plain weights: a weight-normalised checkpoint is folded by the caller) and writes the blob the kernels read: K-contiguous rows
+ * [C_out][taps * C_in] (conv_pre's channels padded with zeros to a multiple of 4), the transposed convolutions split into their r
+ * phases [r][C_out][2 C_in].  Every tensor of the blob starts at a multiple of 64 floats, so gvx_hifigan_blob_floats = the parameter
+ * count + 7 * C_0 * (round4(n_mels) - n_mels) + what rounds each weight and each bias up to a multiple of 64 floats.  A missing name is
+ * GVX_ERR_MISSING_WEIGHT, a wrong element count GVX_ERR_SHAPE, both before anything is launched.  The blob must be 256-byte aligned.
+ *
+ * Workspace: gvx_hifigan_workspace_bytes is host arithmetic (no device, no handle):
+ *     B * ( round256(4 * T * round4(n_mels)) + 4 * round256(4 * T * W) ),   W = max(C_0, max_i rates[0] * .. * rates[i] * C_{i+1})
+ * - the transposed mel and four activation tensors of the widest stage: a stage's x, a residual block's running value and its inner
+ * tensor, and the sum of the blocks.  V1, V2, V3: W = 8192, 2048, 8192 floats.  Linear in B, monotone in T; any contents when the call
+ * starts, nothing is cleared; 256-byte aligned; a NULL, misaligned or short one is GVX_ERR_WORKSPACE before anything is launched.
+ *
+ * gvx_hifigan_forward is a feed-forward chain of ordinary launches on `stream`, one per layer.  A convolution with C_out >= 32 is an
+ * implicit GEMM over channels-last activations on v_mfma_f32_32x32x2_f32 whose workgroup holds its input window in LDS once per block
+ * of 32 input channels and runs every tap off it; narrower layers and the output layer are fmaf dot products.  The last convolution of
+ * resblock j writes (j = 0) or adds (j > 0) y_j into the stage's sum, and the last of them divides: no atomics, no workgroup waits for
+ * another, two calls give the same bits.  stage_out is NULL or a HOST array of n_stages device pointers (16-byte aligned):
+ * stage_out[i] receives x after stage i's average, fp32 [B][T * rates[0] * .. * rates[i]][C_{i+1}], exact zeros behind a row's own
+ * length; it changes no bit of wav.  T below 1, B outside [1, 65535] or a NULL mel / wav_out: GVX_ERR_INVALID_ARG; T above
+ * GVX_HIFIGAN_MAX_FRAMES: GVX_ERR_UNSUPPORTED; no blob bound: GVX_ERR_STATE.
+ *
+ * Timing (measurement only): as gvx_melgan_timing_enable / gvx_melgan_stage_times_ms: n_stages + 2 durations, conv_pre (with the mel
+ * transpose), every stage, conv_post. */
+enum { GVX_HIFIGAN_MAX_STAGES = 8, GVX_HIFIGAN_MAX_RESBLOCKS = 4, GVX_HIFIGAN_MAX_DILATIONS = 3, GVX_HIFIGAN_MAX_WINDOW = 72,
+       GVX_HIFIGAN_MAX_FRAMES = 32768, GVX_HIFIGAN_MAX_HOP = 4096 };
+typedef struct gvx_hifigan_dims {
+    int32_t n_mels;
+    int32_t upsample_initial_channel;
+    int32_t n_stages;
+    int32_t upsample_rates[GVX_HIFIGAN_MAX_STAGES];
+    int32_t upsample_kernel_sizes[GVX_HIFIGAN_MAX_STAGES];
+    int32_t resblock;      /* 1 or 2 */
+    int32_t n_resblocks;   /* n_k: residual blocks per stage */
+    int32_t n_dilations;   /* 3 for resblock 1, 2 for resblock 2 */
+    int32_t resblock_kernel_sizes[GVX_HIFIGAN_MAX_RESBLOCKS];
+    int32_t resblock_dilation_sizes[GVX_HIFIGAN_MAX_RESBLOCKS][GVX_HIFIGAN_MAX_DILATIONS];
+    float slope;
+    float post_slope;
+} gvx_hifigan_dims;
+typedef struct gvx_hifigan gvx_hifigan;
+size_t gvx_hifigan_blob_floats(const gvx_hifigan_dims* dims);
+size_t gvx_hifigan_workspace_bytes(const gvx_hifigan_dims* dims, int B, int T);
+int gvx_hifigan_pack_weights_device(const gvx_hifigan_dims* dims, const gvx_weight_desc* table, int n, float* device_blob, void* stream);
+int gvx_hifigan_create(const gvx_hifigan_dims* dims, gvx_hifigan** out);
+void gvx_hifigan_destroy(gvx_hifigan* handle);
+int gvx_hifigan_bind(gvx_hifigan* handle, const float* device_blob);
+int gvx_hifigan_forward(gvx_hifigan* handle, const float* mel, const int32_t* frame_lengths, int B, int T, float* wav_out,
+                        float* const* stage_out, void* workspace, size_t workspace_bytes, void* stream);
+int gvx_hifigan_timing_enable(gvx_hifigan* handle, int enable);
+int gvx_hifigan_stage_times_ms(gvx_hifigan* handle, float* ms_out, int* n_out);
+
 /* ---- MelGAN discriminators: the multi-scale discriminator a MelGAN generator is trained against (Kumar et al. 2019), forward and
  * backward.  The reference ships the training fields of MelGANConfig and no model; this is a statement of the published architecture.
  * All arithmetic is fp32.  lrelu and "reflect" as for the generator above; s = downsampling_factor.
