@@ -44,6 +44,9 @@ class gvx_melgan_tape_entry(C.Structure):
     _fields_ = [("byte_offset", C.c_uint64), ("positions_per_frame", C.c_int32), ("channels", C.c_int32)]
 
 
+gvx_hifigan_tape_entry = gvx_melgan_tape_entry   # the header's typedef
+
+
 class gvx_melgan_disc_dims(C.Structure):
     _fields_ = [("n_scales", C.c_int32), ("base_channels", C.c_int32), ("n_layers", C.c_int32), ("downsampling_factor", C.c_int32),
                 ("max_channels", C.c_int32), ("slope", C.c_float)]
@@ -201,6 +204,12 @@ SIGNATURES = {
     "gvx_hifigan_forward": (_i, [_vp, _vp, _vp, _i, _i, _vp, C.POINTER(_vp), _vp, _sz, _vp]),
     "gvx_hifigan_timing_enable": (_i, [_vp, _i]),
     "gvx_hifigan_stage_times_ms": (_i, [_vp, C.POINTER(_f), C.POINTER(_i)]),
+    "gvx_hifigan_backward_stage_times_ms": (_i, [_vp, C.POINTER(_f), C.POINTER(_i)]),
+    "gvx_hifigan_tape_bytes": (_sz, [C.POINTER(gvx_hifigan_dims), _i, _i]),
+    "gvx_hifigan_tape_layout": (_i, [C.POINTER(gvx_hifigan_dims), _i, _i, C.POINTER(gvx_melgan_tape_entry), _i]),
+    "gvx_hifigan_backward_workspace_bytes": (_sz, [C.POINTER(gvx_hifigan_dims), _i, _i]),
+    "gvx_hifigan_forward_train": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "gvx_hifigan_backward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, C.POINTER(gvx_weight_desc), _i, _vp, _vp, _sz, _vp]),
     "gvx_melgan_disc_blob_floats": (_sz, [C.POINTER(gvx_melgan_disc_dims)]),
     "gvx_melgan_disc_pack_weights_device": (_i, [C.POINTER(gvx_melgan_disc_dims), C.POINTER(gvx_weight_desc), _i, _vp, _vp]),
     "gvx_melgan_disc_create": (_i, [C.POINTER(gvx_melgan_disc_dims), C.POINTER(_vp)]),

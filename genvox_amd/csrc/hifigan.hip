@@ -14,225 +14,14 @@
 //   hg_valu_kernel   Cout < 32 and the 1-channel output layer (with tanh): fmaf dot products, G lanes per output element
 // A workgroup belongs to one batch row and computes nothing behind that row's length; tensors the caller sees are zero-filled there.
 //
-// Order of this file: the two kernels, the mel transpose, the weight packer, the host walk, the C ABI.
-#include "hifigan_internal.h"
+// The two kernels are in hifigan_kernels.h (the training path, hifigan_train.hip, runs its data gradients on them).
+// Order of this file: the mel transpose, the weight packer, the launches, the C ABI.
+#include "hifigan_kernels.h"
 
 using gvx::fail;
 using namespace gvx_hg;
 
 namespace {
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
-constexpr int HG_LD = 36;    // floats per LDS row of a 32-deep k-tile: the fragment reads of sixteen lanes fall on distinct 16-byte slots
-constexpr int HG_BM = 128;   // positions per workgroup
-constexpr int HG_A_PASS = (HG_BM + GVX_HIFIGAN_MAX_WINDOW + 31) / 32;   // 32 window rows per pass of the 256 threads
-inline size_t hg_lds_bytes(int halo, int BN) { return (size_t)2 * (HG_BM + halo + BN) * HG_LD * sizeof(float); }
-
-__device__ __forceinline__ float hg_finish(const HgLayer& p, float v, const float* res, float* o) {
-    if (res) v += *res;
-    if (p.accumulate) v = *o + v;
-    if (p.divide > 0.f) v = v / p.divide;
-    return v;
-}
-
-template <int WR, int WC, int TM, int TN>
-__global__ void __launch_bounds__(256) hg_mfma_kernel(const HgLayer p) {
-    constexpr int BM = WR * TM * 32, BN = WC * TN * 32, B_V4 = BN / 32;
-    static_assert(WR * WC == 4 && BM == HG_BM, "four waves, 128 positions");
-    extern __shared__ __attribute__((aligned(16))) float hg_smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave / WC, wc = wave % WC, r = lane & 31, h = lane >> 5;
-    const int b = blockIdx.z;
-    const int n_tiles = (p.Cout + BN - 1) / BN;
-    const int nt = (int)blockIdx.y % n_tiles, phase = (int)blockIdx.y / n_tiles;
-    const int q0 = (int)blockIdx.x * BM, n0 = nt * BN;
-    const int Lmax = p.T * p.in_mul;
-    const int len = hg_frames(p.lens, b, p.T) * p.in_mul;
-    float* out_b = p.out + (size_t)b * Lmax * p.phases * p.Cout;
-    if (q0 >= len) {   // nothing of this row here
-        if (p.zero_tail) {
-            const int rows = min(BM, Lmax - q0), cols = min(BN, p.Cout - n0);
-            for (int i = tid; i < rows * cols; i += 256) {
-                const int q = q0 + i / cols, n = n0 + i % cols;
-                out_b[((size_t)q * p.phases + phase) * p.Cout + n] = 0.f;
-            }
-        }
-        return;
-    }
-    const HgTaps tp = hg_taps(p.taps, p.dil, p.phases, phase);
-    const int win = BM + tp.halo;              // window rows: source positions q0 - left .. q0 - left + win - 1
-    float* As = hg_smem;                       // [2][win][HG_LD]
-    float* Bs = hg_smem + 2 * win * HG_LD;     // [2][BN][HG_LD]
-    const float* src_b = p.src + (size_t)b * Lmax * p.Cin;
-
-    const int ld_row = tid >> 3, ld_c4 = tid & 7;
-    const float* w_row[B_V4];
-#pragma unroll
-    for (int i = 0; i < B_V4; ++i) {
-        const int n = n0 + ld_row + 32 * i;
-        w_row[i] = p.W + ((size_t)phase * p.Cout + (n < p.Cout ? n : 0)) * p.K;   // columns past Cout read row 0 and are never stored
-    }
-    float4 a_reg[HG_A_PASS], b_reg[B_V4];
-    int a_keep = 0;               // bit i: a_reg[i] lies inside the row and inside the channels
-    bool a_c_ok = false, b_c_ok = false;
-
-    // global -> registers; what is zeroed is decided here and applied, with the activation, at the LDS stores, so that nothing waits
-    // for the loads while the products of the current tile run
-#define HG_LOAD_A(CB)                                                                                                \
-    {                                                                                                                \
-        const int c_ = 32 * (CB) + 4 * ld_c4;                                                                        \
-        a_c_ok = c_ < p.Cin;                                                                                         \
-        const float* s_ = src_b + (a_c_ok ? c_ : 0);                                                                 \
-        a_keep = 0;                                                                                                  \
-        _Pragma("unroll") for (int i = 0; i < HG_A_PASS; ++i) {                                                      \
-            const int w_ = ld_row + 32 * i;                                                                          \
-            if (w_ < win) {                                                                                          \
-                const int pos_ = q0 - tp.left + w_;                                                                  \
-                const bool in_ = pos_ >= 0 && pos_ < len;                                                            \
-                a_keep |= (int)(in_ && a_c_ok) << i;                                                                 \
-                a_reg[i] = *reinterpret_cast<const float4*>(s_ + (size_t)(in_ ? pos_ : 0) * p.Cin);                  \
-            }                                                                                                        \
-        }                                                                                                            \
-    }
-#define HG_STORE_A(BUF)                                                                                              \
-    {                                                                                                                \
-        _Pragma("unroll") for (int i = 0; i < HG_A_PASS; ++i) {                                                      \
-            const int w_ = ld_row + 32 * i;                                                                          \
-            if (w_ < win) {                                                                                          \
-                const bool keep_ = (a_keep >> i) & 1;                                                                \
-                float4 v_ = a_reg[i];                                                                                \
-                if (p.act) v_ = make_float4(hg_lrelu(v_.x, p.slope), hg_lrelu(v_.y, p.slope), hg_lrelu(v_.z, p.slope), hg_lrelu(v_.w, p.slope)); \
-                *reinterpret_cast<float4*>(&As[((BUF) * win + w_) * HG_LD + 4 * ld_c4]) =                            \
-                    make_float4(keep_ ? v_.x : 0.f, keep_ ? v_.y : 0.f, keep_ ? v_.z : 0.f, keep_ ? v_.w : 0.f);     \
-            }                                                                                                        \
-        }                                                                                                            \
-    }
-#define HG_LOAD_B(TAU, CB)                                                                                           \
-    {                                                                                                                \
-        const int c_ = 32 * (CB) + 4 * ld_c4;                                                                        \
-        b_c_ok = c_ < p.Cin;                                                                                         \
-        const int k_ = b_c_ok ? (TAU) * p.Cin + c_ : 0;                                                              \
-        _Pragma("unroll") for (int i = 0; i < B_V4; ++i) b_reg[i] = *reinterpret_cast<const float4*>(w_row[i] + k_); \
-    }
-#define HG_STORE_B(BUF)                                                                                              \
-    {                                                                                                                \
-        _Pragma("unroll") for (int i = 0; i < B_V4; ++i)                                                             \
-            *reinterpret_cast<float4*>(&Bs[((BUF) * BN + ld_row + 32 * i) * HG_LD + 4 * ld_c4]) =                    \
-                make_float4(b_c_ok ? b_reg[i].x : 0.f, b_c_ok ? b_reg[i].y : 0.f, b_c_ok ? b_reg[i].z : 0.f, b_c_ok ? b_reg[i].w : 0.f); \
-    }
-
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-    const int n_it = ((p.Cin + 31) / 32) * p.taps;   // (channel block, tap) pairs, the tap fastest
-    HG_LOAD_A(0)
-    HG_LOAD_B(0, 0)
-    HG_STORE_A(0)
-    HG_STORE_B(0)
-    __syncthreads();
-    int tau = 0, cb = 0;
-    for (int it = 0; it < n_it; ++it) {
-        int ntau = tau + 1, ncb = cb;
-        if (ntau == p.taps) { ntau = 0; ++ncb; }
-        const bool more = it + 1 < n_it, new_a = more && ntau == 0;
-        if (more) HG_LOAD_B(ntau, ncb)
-        if (new_a) HG_LOAD_A(ncb)
-        const float* a_base = &As[((cb & 1) * win + tp.off0 + tau * tp.step + wr * TM * 32 + r) * HG_LD + 4 * h];
-        const float* b_base = &Bs[((it & 1) * BN + wc * TN * 32 + r) * HG_LD + 4 * h];
-#pragma unroll
-        for (int kg = 0; kg < 4; ++kg) {
-            float4 af[TM], bf[TN];
-#pragma unroll
-            for (int i = 0; i < TM; ++i) af[i] = *reinterpret_cast<const float4*>(a_base + i * 32 * HG_LD + 8 * kg);
-#pragma unroll
-            for (int j = 0; j < TN; ++j) bf[j] = *reinterpret_cast<const float4*>(b_base + j * 32 * HG_LD + 8 * kg);
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i].x, bf[j].x, acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i].y, bf[j].y, acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i].z, bf[j].z, acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i].w, bf[j].w, acc[i][j], 0, 0, 0);
-                }
-        }
-        if (more) HG_STORE_B((it + 1) & 1)
-        if (new_a) HG_STORE_A(ncb & 1)
-        __syncthreads();
-        tau = ntau;
-        cb = ncb;
-    }
-#undef HG_LOAD_A
-#undef HG_STORE_A
-#undef HG_LOAD_B
-#undef HG_STORE_B
-
-    // epilogue: lane (r, h) holds column r of rows (e & 3) + 8 (e >> 2) + 4 h of every 32 x 32 tile
-    const float* res_b = p.res ? p.res + (size_t)b * Lmax * p.Cout : nullptr;   // a residual comes with phases = 1 only
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int col = n0 + (wc * TN + j) * 32 + r;
-        if (col >= p.Cout) continue;
-        const float bias = p.bias[col];
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int q = q0 + (wr * TM + i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-                float* o = out_b + ((size_t)q * p.phases + phase) * p.Cout + col;
-                if (q < len) *o = hg_finish(p, acc[i][j][e] + bias, res_b ? res_b + (size_t)q * p.Cout + col : nullptr, o);
-                else if (p.zero_tail && q < Lmax) *o = 0.f;
-            }
-    }
-}
-
-// G lanes per output element (position, channel), channel fastest; the G partial sums are added by shuffles.
-template <int G>
-__global__ void __launch_bounds__(256) hg_valu_kernel(const HgLayer p) {
-    const int b = blockIdx.z, phase = blockIdx.y;
-    const int Lmax = p.T * p.in_mul;
-    const int len = hg_frames(p.lens, b, p.T) * p.in_mul;
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    const int g = (int)(idx % G);
-    const long e = idx / G;
-    const int n = (int)(e % p.Cout);
-    const long ql = e / p.Cout;
-    const bool inside = ql < Lmax, live = ql < len;
-    const int q = (int)ql;
-    float sum = 0.f;
-    if (live) {
-        const HgTaps tp = hg_taps(p.taps, p.dil, p.phases, phase);
-        const float* w = p.W + ((size_t)phase * p.Cout + n) * p.K;
-        for (int tau = 0; tau < p.taps; ++tau) {
-            const int pos = q - tp.left + tp.off0 + tau * tp.step;
-            if (pos < 0 || pos >= len) continue;
-            const float* x = p.src + ((size_t)b * Lmax + pos) * p.Cin;
-            const float* wt = w + tau * p.Cin;
-            for (int c = g; c < p.Cin; c += G) {
-                float v = x[c];
-                if (p.act) v = hg_lrelu(v, p.slope);
-                sum = fmaf(v, wt[c], sum);
-            }
-        }
-    }
-#pragma unroll
-    for (int off = G >> 1; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
-    if (g == 0 && inside) {
-        float* o = p.out + (((size_t)b * Lmax + q) * p.phases + phase) * p.Cout + n;
-        if (live) {
-            float v = hg_finish(p, sum + p.bias[n], p.res ? p.res + ((size_t)b * Lmax + q) * p.Cout + n : nullptr, o);
-            if (p.tanh_out) v = tanhf(v);
-            *o = v;
-        } else if (p.zero_tail) {
-            *o = 0.f;
-        }
-    }
-}
 
 // mel [B][M][T] -> channels-last [B][T][Cp] with the channels padded by zeros to a multiple of four; nothing behind a row's frames is read
 __global__ void __launch_bounds__(256) hg_mel_transpose_kernel(const float* mel, const int32_t* lens, int M, int T, int Cp, float* out) {
@@ -295,7 +84,9 @@ int hg_launch_mfma(const HgLayer& p, int B, hipStream_t s) {
     return GVX_OK;
 }
 
-int hg_launch(const HgLayer& p, int B, hipStream_t s) {
+}  // namespace
+
+int gvx_hg::hg_launch(const HgLayer& p, int B, hipStream_t s) {
     if (p.Cout >= 32 && p.Cin % 4 == 0) {
         if (p.Cout >= 128) return hg_launch_mfma<2, 2, 2, 2>(p, B, s);
         if (p.Cout > 32) return hg_launch_mfma<4, 1, 1, 2>(p, B, s);
@@ -311,7 +102,7 @@ int hg_launch(const HgLayer& p, int B, hipStream_t s) {
 }
 
 // once per handle: the dynamic LDS of the largest window any layer of any supported configuration asks for
-int hg_prepare(gvx_hifigan* h) {
+int gvx_hg::hg_prepare(gvx_hifigan* h) {
     if (!h->lds_ready) {
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(hg_mfma_kernel<2, 2, 2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)hg_lds_bytes(GVX_HIFIGAN_MAX_WINDOW, 128)));
@@ -324,6 +115,15 @@ int hg_prepare(gvx_hifigan* h) {
     return GVX_OK;
 }
 
+int gvx_hg::hg_mel_transpose(const float* mel, const int32_t* lens, int B, int M, int T, int Cp, float* out, hipStream_t s) {
+    const dim3 grid((unsigned)(((long)T * Cp + 255) / 256), (unsigned)B);
+    hg_mel_transpose_kernel<<<grid, 256, 0, s>>>(mel, lens, M, T, Cp, out);
+    HIP_TRY(hipGetLastError());
+    return GVX_OK;
+}
+
+namespace {
+
 const gvx_weight_desc* hg_find(const gvx_weight_desc* table, int n, const std::string& name, size_t numel, int& rc) {
     for (int i = 0; i < n; ++i)
         if (table[i].name && name == table[i].name) {
@@ -335,13 +135,6 @@ const gvx_weight_desc* hg_find(const gvx_weight_desc* table, int n, const std::s
         }
     rc = fail(GVX_ERR_MISSING_WEIGHT, "%s is missing", name.c_str());
     return nullptr;
-}
-
-// the names of a residual block's convolutions: [m][0 / 1]
-std::string hg_conv_name(const gvx_hifigan_dims& d, int block, int m, int v) {
-    const std::string base = "resblocks." + std::to_string(block);
-    if (d.resblock == 2) return base + ".convs." + std::to_string(m);
-    return base + (v == 0 ? ".convs1." : ".convs2.") + std::to_string(m);
 }
 
 }  // namespace
@@ -416,6 +209,7 @@ int gvx_hifigan_create(const gvx_hifigan_dims* dims, gvx_hifigan** out) {
 void gvx_hifigan_destroy(gvx_hifigan* h) {
     if (!h) return;
     for (int i = 0; i < h->n_ev; ++i) (void)hipEventDestroy(h->ev[i]);
+    for (int i = 0; i < h->n_ev_bwd; ++i) (void)hipEventDestroy(h->ev_bwd[i]);
     delete h;
 }
 
@@ -430,6 +224,7 @@ int gvx_hifigan_timing_enable(gvx_hifigan* h, int enable) {
     if (!h) return fail(GVX_ERR_INVALID_ARG, "null argument");
     const int need = h->d.n_stages + 3;
     while (enable && h->n_ev < need) HIP_TRY(hipEventCreate(&h->ev[h->n_ev++]));
+    while (enable && h->n_ev_bwd < need + 1) HIP_TRY(hipEventCreate(&h->ev_bwd[h->n_ev_bwd++]));
     h->timing = enable != 0;
     return GVX_OK;
 }
@@ -474,11 +269,7 @@ int gvx_hifigan_forward(gvx_hifigan* h, const float* mel, const int32_t* frame_l
 
     const int Cp = hg_cpad(d);
     float* mel_t = gvx::ws_ptr<float>(workspace, wp.mel_t);
-    {
-        const dim3 grid((unsigned)(((long)T * Cp + 255) / 256), (unsigned)B);
-        hg_mel_transpose_kernel<<<grid, 256, 0, s>>>(mel, frame_lengths, d.n_mels, T, Cp, mel_t);
-        HIP_TRY(hipGetLastError());
-    }
+    if ((rc = hg_mel_transpose(mel, frame_lengths, B, d.n_mels, T, Cp, mel_t, s)) != GVX_OK) return rc;
     auto layer = [&](const float* src, size_t w, size_t bias, float* out, int in_mul, int Cin, int Cout, int taps, int dil, int phases, int act) {
         HgLayer p{};
         p.lens = frame_lengths; p.T = T; p.slope = d.slope;

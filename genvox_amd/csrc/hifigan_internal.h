@@ -10,6 +10,8 @@ struct gvx_hifigan {
     bool lds_ready = false;
     hipEvent_t ev[GVX_HIFIGAN_MAX_STAGES + 3] = {};
     int n_ev = 0;
+    hipEvent_t ev_bwd[GVX_HIFIGAN_MAX_STAGES + 4] = {};   // gvx_hifigan_backward's parts (hifigan_train.hip)
+    int n_ev_bwd = 0;
 };
 
 namespace gvx_hg {
@@ -33,6 +35,9 @@ struct HgLayer {
     float divide;          // > 0: the value is divided by it last (the stage's average)
     int zero_tail, tanh_out;
     float slope;
+    // data gradients only (hifigan_kernels.h, BWD): the raw tape tensor whose LeakyReLU the gradient passes through, and a second tensor
+    // added element by element after `res`; both [B][len][Cout] or nullptr
+    const float* mask; const float* add2;
 };
 
 struct HgTaps { int halo, left, off0, step; };
@@ -118,5 +123,17 @@ inline HgBlob hg_blob_layout(const gvx_hifigan_dims& d) {
     L.total = at;
     return L;
 }
+
+// the names of a residual block's convolutions: [m][0 / 1]
+inline std::string hg_conv_name(const gvx_hifigan_dims& d, int block, int m, int v) {
+    const std::string base = "resblocks." + std::to_string(block);
+    if (d.resblock == 2) return base + ".convs." + std::to_string(m);
+    return base + (v == 0 ? ".convs1." : ".convs2.") + std::to_string(m);
+}
+
+// hifigan.hip, for the training path: one layer's launch, the handle's dynamic-LDS sizes, the mel transpose
+int hg_launch(const HgLayer& p, int B, hipStream_t s);
+int hg_prepare(gvx_hifigan* h);
+int hg_mel_transpose(const float* mel, const int32_t* lens, int B, int M, int T, int Cp, float* out, hipStream_t s);
 
 }  // namespace gvx_hg

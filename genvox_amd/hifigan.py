@@ -3,7 +3,8 @@
 The module holds the parameters in PyTorch's own layouts - ``Conv1d`` as [out, in, k], ``ConvTranspose1d`` as [in, out, k] - under the
 published implementation's names (``conv_pre``, ``ups.<i>``, ``resblocks.<n>.convs1.<m>`` / ``.convs2.<m>`` or ``.convs.<m>``,
 ``conv_post``), so a published V1, V2 or V3 generator checkpoint loads as it is; weight normalisation is folded on load.  The kernels
-read a packed blob that is rebuilt on the device whenever the parameters change.  Inference only; there is no CPU or eager path.
+read a packed blob that is rebuilt on the device whenever the parameters change.  ``vocode`` is inference; ``vocode_with_grad`` is the
+same call attached to autograd, for training or fine-tuning the generator.  There is no CPU or eager path.
 
 The model vocodes whatever mel scale its checkpoint was trained on.  A checkpoint trained on the published recipe's natural-log mels
 is NOT matched to this package's Tacotron2 mels (log10, dB-scaled: ``AudioProcessor``), and no conversion is part of this module: pair
@@ -18,7 +19,7 @@ from torch import nn
 
 from . import _lib
 from .configs import AudioConfig, BaseConfig, HiFiGANConfig
-from .melgan import _Layer, fold_weight_norm
+from .melgan import _Layer, _VocodeWithGrad, fold_weight_norm
 
 
 def dims_from_config(mc: HiFiGANConfig, ac: AudioConfig) -> _lib.gvx_hifigan_dims:
@@ -71,6 +72,7 @@ class HiFiGANGenerator(nn.Module):
         self._blob: Optional[torch.Tensor] = None
         self._packed_key = None
         self._workspace: Optional[torch.Tensor] = None
+        self._train_workspace: Optional[torch.Tensor] = None
 
     # ------------------------------------------------------------------ C-ABI plumbing
     def __del__(self):
@@ -137,6 +139,13 @@ class HiFiGANGenerator(nn.Module):
         _lib.check(_lib.load().gvx_hifigan_stage_times_ms(self._ensure_packed(), out, C.byref(n)))
         return [out[i] for i in range(n.value)]
 
+    def backward_stage_times_ms(self) -> List[float]:
+        """Durations of the last ``vocode_with_grad`` backward's parts, in the order they ran: the weight transposes, conv_post,
+        every stage from the last to the first, conv_pre (synchronises)."""
+        out, n = (C.c_float * 12)(), C.c_int()
+        _lib.check(_lib.load().gvx_hifigan_backward_stage_times_ms(self._ensure_packed(), out, C.byref(n)))
+        return [out[i] for i in range(n.value)]
+
     # ------------------------------------------------------------------ the call
     def _check_call(self, mel: torch.Tensor, mel_lengths):
         """The argument checks of ``vocode`` -> (device, B, T, the lengths as int32 on the device or None)."""
@@ -195,6 +204,27 @@ class HiFiGANGenerator(nn.Module):
             _lib.check(lib.gvx_hifigan_forward(h, mel[lo:lo + n].data_ptr(), lens_dev[lo:lo + n].data_ptr() if lens_dev is not None else None, n, T,
                                                wav[lo:lo + n].data_ptr(), ptrs, workspace.data_ptr(), workspace.numel(), self._stream()))
         return (wav, stages) if stage_outputs else wav
+
+    def vocode_with_grad(self, mel: torch.Tensor, mel_lengths=None) -> torch.Tensor:
+        """``vocode`` attached to autograd: mel float32 [B, n_mels, T] on the device -> waveform float32 [B, T * hop] whose
+        ``backward()`` fills ``.grad`` of every parameter of the generator - and of ``mel`` if ``mel.requires_grad`` - on the device's
+        own kernels (gvx_hifigan_forward_train / gvx_hifigan_backward, csrc/hifigan_train.hip), so a plain torch loop with any loss
+        written in torch (``MultiResolutionSTFTLoss``, a discriminator) and any torch optimizer trains or fine-tunes the vocoder.  The
+        waveform has ``vocode``'s bits; under ``torch.no_grad()`` (or when nothing requires a gradient) the call IS ``vocode``.  Rows
+        are ragged as in ``vocode``; gradient that arrives behind ``T_b * hop`` samples is never read, and ``mel.grad`` is 0 at and
+        behind a row's frames.  The call keeps a tape of every layer's pre-activations (1,812,800 bytes per frame and row for V1,
+        453,440 for V2, 267,584 for V3) until its backward has run; a parameter changed in place between the two raises torch's version
+        error, and packing the weights again between the two raises RuntimeError.  Two backward calls give the same bits.
+
+        Training is on plain weights: a weight-normalised checkpoint is folded when it is loaded and stays folded, and the module
+        has no weight-norm parametrisation of its own.  Parameters must be contiguous float32."""
+        if not torch.is_grad_enabled() or not (mel.requires_grad or any(p.requires_grad for p in self.parameters())):
+            return self.vocode(mel, mel_lengths)
+        _, _, _, lens_dev = self._check_call(mel, mel_lengths)
+        for k, p in self.named_parameters():
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise ValueError(f"{k}: training needs contiguous float32 parameters")
+        return _VocodeWithGrad.apply(self, mel.contiguous(), lens_dev, *self.parameters())
 
     def inference(self, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         """{"mel": [B, n_mels, T], "mel_lengths": optional [B]} -> {"waveform": float32 [B, T * hop] on the device, "lengths": int32 [B]

@@ -70,9 +70,10 @@ def fold_weight_norm(state_dict) -> Dict[str, torch.Tensor]:
 
 
 class _VocodeWithGrad(torch.autograd.Function):
-    """gvx_melgan_forward_train / gvx_melgan_backward as one autograd node.  The inputs after ``lens_dev`` are the model's parameters
-    in ``named_parameters()`` order; they go through ``save_for_backward``, so an in-place change between forward and backward raises
-    torch's own version error, and the tape is a tensor the node keeps."""
+    """gvx_<model_name>_forward_train / gvx_<model_name>_backward as one autograd node, for the generators whose C ABI has that pair
+    (MelGAN, HiFi-GAN).  The inputs after ``lens_dev`` are the model's parameters in ``named_parameters()`` order; they go through
+    ``save_for_backward``, so an in-place change between forward and backward raises torch's own version error, and the tape is a
+    tensor the node keeps."""
 
     @staticmethod
     def forward(ctx, model, mel, lens_dev, *params):
@@ -81,8 +82,9 @@ class _VocodeWithGrad(torch.autograd.Function):
         B, _, T = mel.shape
         dev = mel.device
         wav = torch.empty(B, T * model.hop, dtype=torch.float32, device=dev)
-        tape = torch.empty(lib.gvx_melgan_tape_bytes(C.byref(dims), B, T), dtype=torch.uint8, device=dev)
-        _lib.check(lib.gvx_melgan_forward_train(h, mel.data_ptr(), lens_dev.data_ptr() if lens_dev is not None else None, B, T, wav.data_ptr(),
+        abi = "gvx_" + model.model_name
+        tape = torch.empty(getattr(lib, abi + "_tape_bytes")(C.byref(dims), B, T), dtype=torch.uint8, device=dev)
+        _lib.check(getattr(lib, abi + "_forward_train")(h, mel.data_ptr(), lens_dev.data_ptr() if lens_dev is not None else None, B, T, wav.data_ptr(),
                                                 tape.data_ptr(), tape.numel(), None, 0, model._stream()))
         ctx.model, ctx.lens_dev, ctx.shape, ctx.tape, ctx.packed_key = model, lens_dev, (B, T), tape, model._packed_key
         ctx.save_for_backward(*params)
@@ -103,11 +105,12 @@ class _VocodeWithGrad(torch.autograd.Function):
         for i, (k, g) in enumerate(zip(names, grads)):
             table[i] = _lib.gvx_weight_desc(k.encode(), g.data_ptr(), g.numel())
         d_mel = torch.empty(B, model.audio_config.n_mels, T, dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
-        need = lib.gvx_melgan_backward_workspace_bytes(C.byref(dims), B, T)
+        abi = "gvx_" + model.model_name
+        need = getattr(lib, abi + "_backward_workspace_bytes")(C.byref(dims), B, T)
         if model._train_workspace is None or model._train_workspace.numel() < need or model._train_workspace.device != dev:
             model._train_workspace = torch.empty(need, dtype=torch.uint8, device=dev)
         ws = model._train_workspace
-        _lib.check(lib.gvx_melgan_backward(model._handle, d_wav.data_ptr(), ctx.lens_dev.data_ptr() if ctx.lens_dev is not None else None, B, T,
+        _lib.check(getattr(lib, abi + "_backward")(model._handle, d_wav.data_ptr(), ctx.lens_dev.data_ptr() if ctx.lens_dev is not None else None, B, T,
                                            ctx.tape.data_ptr(), ctx.tape.numel(), table, len(grads), d_mel.data_ptr() if d_mel is not None else None,
                                            ws.data_ptr(), ws.numel(), model._stream()))
         return (None, d_mel, None, *grads)

@@ -1067,7 +1067,7 @@ int gvx_melgan_backward(gvx_melgan* handle, const float* d_wav, const int32_t* f
                         size_t tape_bytes, const gvx_grad_desc* grads, int n_grads, float* d_mel_out, void* workspace,
                         size_t workspace_bytes, void* stream);
 
-/* ---- HiFi-GAN generator, mel -> waveform, inference (Kong et al. 2020; its V1, V2 and V3 generators).  The reference ships no such
+/* ---- HiFi-GAN generator, mel -> waveform (Kong et al. 2020; its V1, V2 and V3 generators).  The reference ships no such
  * model; the network below is the published implementation's, under its names.  Kernels: csrc/hifigan.hip; all arithmetic is fp32.
  *
  * Input: mel fp32 [B][n_mels][T].  Output: wav fp32 [B][T * hop], hop = the product of upsample_rates, every sample in (-1, 1).
@@ -1151,6 +1151,61 @@ int gvx_hifigan_forward(gvx_hifigan* handle, const float* mel, const int32_t* fr
                         float* const* stage_out, void* workspace, size_t workspace_bytes, void* stream);
 int gvx_hifigan_timing_enable(gvx_hifigan* handle, int enable);
 int gvx_hifigan_stage_times_ms(gvx_hifigan* handle, float* ms_out, int* n_out);
+
+/* HiFi-GAN generator: training.  A forward that keeps a tape, and the backward: the calls of "Training the generator" above (MelGAN),
+ * with their contracts, argument order and error codes, for the network of gvx_hifigan_forward.  Kernels: csrc/hifigan_train.hip and
+ * csrc/hifigan_kernels.h; all arithmetic is fp32; training is on plain weights.
+ *
+ * Tape: the caller's memory, 256-byte aligned, gvx_hifigan_tape_bytes (host arithmetic) long.  It holds every tensor the backward
+ * reads, in forward order, which gvx_hifigan_tape_layout (host arithmetic) lists as (byte offset, positions per frame, channels):
+ *     the transposed mel [round4(n_mels) channels];  conv_pre's output;
+ *     per stage: ups.<i>'s output;  per residual block, per dilation m: the inner tensor (convs1.<m>'s output, resblock 1 only), then the
+ *     block's running value after dilation m, for every m but the last;  the stage's average.
+ * The last dilation's y_j is not kept: the forward adds it straight into the stage's sum, which is the average's slot, and its gradient
+ * is d(sum) / n_k whatever its value.  That is 2 + n_k * (n_dilations * convs per dilation - 1) tensors per stage: 17 for resblock 1 with
+ * three kernels, 5 for resblock 2.  Each is fp32, RAW pre-activation values, channels-last [B][T * positions per frame][channels] with
+ * rows strided by the padded T, and starts where the one before it ends: the tape is 4 * B * T * F bytes, F = round4(n_mels) + C_0 + the
+ * sum over the stages of that count * rates[0] * .. * rates[i] * C_{i+1}.  V1: F = 80 + 512 + 17 * (2048 + 3 * 8192) = 453,200 floats,
+ * 1,812,800 bytes per frame and row.  Linear in B and in T.  Behind a row's own length the tape holds whatever it held before: the
+ * backward reads nothing there.  The layout call returns the number of entries and fills at most max_entries of them (entries may be
+ * NULL); both return 0 for refused dims, B outside [1, 65535] or T outside [1, GVX_HIFIGAN_MAX_FRAMES].
+ *
+ * gvx_hifigan_forward_train is the forward with every layer writing into its own tape slot - the same kernels with the same arguments
+ * (the in-place write of convs2's output becomes a write beside its residual input, which the kernel reads element by element), so
+ * wav_out has the bits of gvx_hifigan_forward.  It needs no scratch: workspace may be NULL and workspace_bytes 0.
+ *
+ * gvx_hifigan_backward: d_wav fp32 [B][T * hop], never read at or behind sample T_b * hop.  grads is a HOST table that names DEVICE
+ * destinations under the packer's names; every parameter gradient is WRITTEN (not accumulated) in PyTorch's own layout: Conv1d
+ * [out][in][k] (conv_pre without padded channels), ConvTranspose1d [in][out][2 r].  d_mel_out is NULL (the first layer's data gradient is
+ * skipped; no parameter gradient changes a bit) or fp32 [B][n_mels][T], exactly 0 at and behind a row's frames; row b of it has the bits
+ * of that row run alone.  A LeakyReLU's derivative is decided by `v > 0` on the tape value, as the forward decides it.  Refused before
+ * anything is launched: a missing name (GVX_ERR_MISSING_WEIGHT), a wrong element count or NULL destination (GVX_ERR_SHAPE), a NULL,
+ * short or misaligned tape or workspace (GVX_ERR_WORKSPACE), T or B as the forward refuses them, B * ceil(T * hop / 512) above
+ * GVX_HIFIGAN_MAX_TRAIN_PIECES (GVX_ERR_UNSUPPORTED).  gvx_hifigan_backward_workspace_bytes is host arithmetic and exact: any contents
+ * when the call starts, nothing is cleared; it holds the transposed weights (made from the bound blob at the start of every call, so
+ * never stale), the waveform and its pre-tanh gradient, five activation-gradient tensors of the widest stage, and the partial products
+ * of the widest weight gradient and of the widest bias gradient.
+ *
+ * The backward is a chain of ordinary launches.  A data gradient is the forward's own windowed kernel with dY as the operand and the
+ * transposed, tap-reversed weights (a transposed convolution as a 3-tap convolution over its output read as [len][r C]); the epilogue
+ * applies lrelu', the residual path's gradient and the 1 / n_k of a stage's average.  Weight and bias gradients are reduced per row in
+ * pieces of 512 positions - a row of T * m positions has ceil(T * m / 512) of them - on v_mfma_f32_32x32x2_f32 where the layer has 32
+ * output channels or more, every tap off one activated source window in LDS, and the partial products are added in a fixed order.  No
+ * float atomics: two calls give the same bits.
+ *
+ * Timing (measurement only): with gvx_hifigan_timing_enable on, gvx_hifigan_backward_stage_times_ms gives the last backward call's
+ * n_stages + 3 durations in the order they ran: the weight transposes, conv_post, every stage from the last to the first, conv_pre. */
+enum { GVX_HIFIGAN_MAX_TRAIN_PIECES = 1 << 24 };
+typedef gvx_melgan_tape_entry gvx_hifigan_tape_entry;
+size_t gvx_hifigan_tape_bytes(const gvx_hifigan_dims* dims, int B, int T);
+int gvx_hifigan_tape_layout(const gvx_hifigan_dims* dims, int B, int T, gvx_hifigan_tape_entry* entries, int max_entries);
+size_t gvx_hifigan_backward_workspace_bytes(const gvx_hifigan_dims* dims, int B, int T);
+int gvx_hifigan_forward_train(gvx_hifigan* handle, const float* mel, const int32_t* frame_lengths, int B, int T, float* wav_out, void* tape,
+                              size_t tape_bytes, void* workspace, size_t workspace_bytes, void* stream);
+int gvx_hifigan_backward(gvx_hifigan* handle, const float* d_wav, const int32_t* frame_lengths, int B, int T, const void* tape,
+                         size_t tape_bytes, const gvx_grad_desc* grads, int n_grads, float* d_mel_out, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int gvx_hifigan_backward_stage_times_ms(gvx_hifigan* handle, float* ms_out, int* n_out);
 
 /* ---- MelGAN discriminators: the multi-scale discriminator a MelGAN generator is trained against (Kumar et al. 2019), forward and
  * backward.  The reference ships the training fields of MelGANConfig and no model; this is a statement of the published architecture.

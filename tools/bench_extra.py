@@ -22,7 +22,10 @@ torch's own convolutions and autograd; with the count of LeakyReLU decisions on 
 difference again with torch differentiating through the device's own decisions;
 `hifigan` (on request): the HiFi-GAN generator - V1 at 1 x 568 and 32 x 800 frames, V2 at 32 x 800 - between device events, median of 7
 with the spread and the time per stage, against the same float32 network built from torch.nn modules that hold the same (seeded)
-parameters, through torch's own ROCm convolutions, and against `MelGANGenerator` and Griffin-Lim (32 iterations) on the same mels."""
+parameters, through torch's own ROCm convolutions, and against `MelGANGenerator` and Griffin-Lim (32 iterations) on the same mels;
+`hifigan_train` (on request): HiFi-GAN V1 `vocode_with_grad` + `backward()` (gvx_hifigan_forward_train + gvx_hifigan_backward) at 16 x 32
+and 8 x 128 frames between device events, median of 7 with the spread, against autograd through the same torch.nn network, with the
+forward's and the backward's time per stage from the same run and the tape's and the workspace's size."""
 import json
 import os
 import sys
@@ -529,12 +532,14 @@ def main():
             real = wav.detach()
             res[key]["train_step"] = ev_spread(lambda: trainer.train_step(mel, real), warm=2, reps=5)
             print(json.dumps({key: {"train_step": res[key]["train_step"]}}), flush=True)
-    if "hifigan" in which:
+    if which & {"hifigan", "hifigan_train"}:
+        import ctypes as C
         import statistics
 
         from torch import nn
 
         from genvox_amd.configs import HiFiGANConfig, MelGANConfig
+        from genvox_amd import _lib
         from genvox_amd.hifigan import HiFiGANGenerator
         from genvox_amd.melgan import MelGANGenerator
 
@@ -593,7 +598,8 @@ def main():
         ap = AudioProcessor(ac, device="cuda:0")
         gen = torch.Generator(device="cuda").manual_seed(0)
         melgan = MelGANGenerator(MelGANConfig(), ac).to("cuda:0")
-        for name, hc, shapes in (("v1", HiFiGANConfig(), ((1, 568), (32, 800))), ("v2", HiFiGANConfig(upsample_initial_channel=128), ((32, 800),))):
+        configs = (("v1", HiFiGANConfig(), ((1, 568), (32, 800))), ("v2", HiFiGANConfig(upsample_initial_channel=128), ((32, 800),)))
+        for name, hc, shapes in configs if "hifigan" in which else ():
             torch.manual_seed(0)
             voc = HiFiGANGenerator(hc, ac).to("cuda:0")
             with torch.no_grad():
@@ -623,6 +629,59 @@ def main():
                     res[key]["max_abs_difference_from_torch"] = float((ref(mel) - wav).abs().max())
                 res[key]["melgan"] = ev_spread(lambda: melgan.vocode(mel))
                 res[key]["griffin_lim_32it"] = ev_spread(lambda: ap.convert_mel2wav_batch(mel), warm=1, reps=5)
+                print(json.dumps({key: res[key]}), flush=True)
+            del voc, ref
+        if "hifigan_train" in which:
+            hc = HiFiGANConfig()
+            torch.manual_seed(0)
+            voc = HiFiGANGenerator(hc, ac).to("cuda:0")
+            with torch.no_grad():
+                for pname, p in voc.named_parameters():
+                    if pname.endswith("bias"):
+                        p.copy_(0.1 * torch.randn_like(p))
+            ref = TorchHiFiGAN(hc, ac.n_mels).to("cuda:0")
+            ref.load_state_dict(voc.state_dict())
+            params, ref_params = list(voc.parameters()), dict(ref.named_parameters())
+            for B, T in ((16, 32), (8, 128)):   # a training segment; a longer one
+                key = f"hifigan_train_v1_{B}x{T}"
+                mel = (0.5 * torch.randn(B, 80, T, device="cuda", generator=gen) - 0.5).contiguous()
+                cot = torch.randn(B, T * voc.hop, device="cuda", generator=gen)
+
+                def ours():
+                    for p in params:
+                        p.grad = None
+                    (voc.vocode_with_grad(mel) * cot).sum().backward()
+
+                def torchs():   # autograd through torch's own convolutions, the same parameter values
+                    for p in ref_params.values():
+                        p.grad = None
+                    (ref(mel) * cot).sum().backward()
+
+                lib, dims = _lib.load(), voc.dims()
+                res[key] = {"forward_train_plus_backward": ev_spread(ours, warm=2, reps=7),
+                            "inference_forward": ev_spread(lambda: voc.vocode(mel), warm=2, reps=7),
+                            "tape_mb": round(lib.gvx_hifigan_tape_bytes(C.byref(dims), B, T) / 1e6, 1),
+                            "backward_workspace_mb": round(lib.gvx_hifigan_backward_workspace_bytes(C.byref(dims), B, T) / 1e6, 1)}
+                voc.enable_stage_timing(True)
+                fwd, bwd = [], []
+                for _ in range(5):
+                    voc.vocode(mel)
+                    fwd.append(voc.stage_times_ms())
+                    ours()
+                    bwd.append(voc.backward_stage_times_ms())
+                voc.enable_stage_timing(False)
+                fwd = [statistics.median(col) for col in zip(*fwd)]                 # conv_pre, every stage, conv_post
+                bwd = [statistics.median(col) for col in zip(*bwd)]                 # transposes, conv_post, stages from the last, conv_pre
+                bwd_fwd_order = [bwd[-1]] + bwd[2:-1][::-1] + [bwd[1]]
+                res[key]["forward_stage_ms"] = [round(v, 3) for v in fwd]
+                res[key]["backward_stage_ms"] = [round(v, 3) for v in bwd_fwd_order]
+                res[key]["backward_over_forward_per_stage"] = [round(b / f, 2) for b, f in zip(bwd_fwd_order, fwd)]
+                res[key]["backward_weight_transposes_ms"] = round(bwd[0], 3)
+                ours()
+                got = {k: p.grad.clone() for k, p in voc.named_parameters()}
+                res[key]["torch_autograd"] = ev_spread(torchs, warm=2, reps=7)
+                res[key]["max_relative_gradient_difference_from_torch"] = max(
+                    float((got[k] - p.grad).abs().max() / p.grad.abs().max().clamp_min(1e-30)) for k, p in ref_params.items())
                 print(json.dumps({key: res[key]}), flush=True)
             del voc, ref
     if "cpu" in which:
