@@ -29,6 +29,7 @@ from genvox_amd.melgan_disc import MelGANDiscriminator
 from genvox_amd.melgan_training import MelGANTrainer
 from tests import melgan_disc_ref64 as DR
 from tests import melgan_ref64 as R
+from tests import stft_loss_ref64 as SR
 
 pytestmark = pytest.mark.gpu
 
@@ -45,15 +46,17 @@ def _row_mean(rows):
     return sum(r.mean() for r in rows) / len(rows)
 
 
-def restated_step(sd_g, sd_d, mel, wav, dtype):
-    """The step of MelGANTrainer.train_step in ``dtype`` -> (post-step parameters of G and of D after every discriminator step, terms, G's clipped gradients)."""
+def restated_step(sd_g, sd_d, mel, wav, dtype, mel_lengths=MEL_LENGTHS, stft=None):
+    """The step of MelGANTrainer.train_step in ``dtype`` -> (post-step parameters of G and of D after every discriminator step, terms, G's clipped gradients).
+    ``stft`` = (resolutions, stft_weight) adds the spectral-convergence term of tests/stft_loss_ref64.py (w_mag = 0) to the generator's
+    loss: the mean over rows and resolutions, every row at its own length."""
     pg = {k: v.to(dtype).clone().requires_grad_(True) for k, v in sd_g.items()}
     pd = {k: v.to(dtype).clone().requires_grad_(True) for k, v in sd_d.items()}
     adam = dict(lr=HP["learning_rate"], betas=(HP["beta1"], HP["beta2"]), weight_decay=HP["weight_decay"])
     opt_g, opt_d = torch.optim.Adam(list(pg.values()), **adam), torch.optim.Adam(list(pd.values()), **adam)
     hop = R.hop(G_CFG)
-    fake = [R.generator(pg, mel[b:b + 1, :, :t].to(dtype), G_CFG)[0] for b, t in enumerate(MEL_LENGTHS)]
-    real = [wav[b:b + 1, :t * hop].to(dtype) for b, t in enumerate(MEL_LENGTHS)]
+    fake = [R.generator(pg, mel[b:b + 1, :, :t].to(dtype), G_CFG)[0] for b, t in enumerate(mel_lengths)]
+    real = [wav[b:b + 1, :t * hop].to(dtype) for b, t in enumerate(mel_lengths)]
     n_scales, n_maps = D_CFG["n_scales"], D_CFG["n_layers"] + 3
     d_states = []
     for _ in range(HP["train_repeat_discriminator"]):
@@ -74,11 +77,17 @@ def restated_step(sd_g, sd_d, mel, wav, dtype):
     weight = 4.0 / (D_CFG["n_layers"] + 1) / n_scales
     fm = HP["feat_match"] * sum(weight * _row_mean([(f[k][i] - r[k][i]).abs() for f, r in zip(d_fake, d_real)]) for k in range(n_scales) for i in range(n_maps - 1))
     g_loss = adv + fm
+    terms = dict(d_loss=d_loss.item(), g_adv=adv.item(), g_feat_match=fm.item())
+    if stft is not None:
+        res, weight = stft
+        g_stft = sum(SR.row_terms(f[0], r[0], rs)[0] for f, r in zip(fake, real) for rs in res) / (len(fake) * len(res))
+        g_loss = g_loss + weight * g_stft
+        terms["g_stft"] = g_stft.item()
     g_loss.backward()
     torch.nn.utils.clip_grad_norm_(list(pg.values()), HP["grad_clip_thresh"])
     g_grads = {k: v.grad.detach().clone() for k, v in pg.items()}   # as the optimizer sees them: clipped
     opt_g.step()
-    terms = dict(d_loss=d_loss.item(), g_adv=adv.item(), g_feat_match=fm.item(), g_loss=g_loss.item())
+    terms["g_loss"] = g_loss.item()
     return {k: v.detach() for k, v in pg.items()}, d_states, terms, g_grads
 
 
@@ -114,8 +123,9 @@ def _case():
     raise AssertionError("no well-conditioned step among seeds 1 .. 32")
 
 
-def _models():
-    sd_g, sd_d = _case()[:2]
+def _models(sd_g=None, sd_d=None):
+    if sd_g is None:
+        sd_g, sd_d = _case()[:2]
     ac = AudioConfig(n_mels=12)
     ac.n_mels, ac.hop_length = G_CFG["n_mels"], R.hop(G_CFG)   # below a preprocessing config's ranges: a test's size
     gen = MelGANGenerator(MelGANConfig(base_channels=G_CFG["base_channels"], upsample_ratios=G_CFG["ratios"], n_residual_layers=G_CFG["n_res"],
