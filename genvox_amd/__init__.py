@@ -5,8 +5,10 @@
     from genvox_amd import HiFiGANGenerator, HiFiGANConfig   # HiFi-GAN V1 / V2 / V3 generators, the same place in Synthesizer
     from genvox_amd import Tacotron2GuidedLoss    # training criterion: Tacotron2Loss + alpha x guided attention loss
     from genvox_amd import MelGANDiscriminator, MelGANDiscriminatorConfig, MelGANTrainer   # the other side of the vocoder's GAN step
+    from genvox_amd import HiFiGANPeriodDiscriminator, HiFiGANPeriodDiscriminatorConfig, HiFiGANTrainer, HiFiGANTrainingConfig   # HiFi-GAN's GAN step
     from genvox_amd import MultiResolutionSTFTLoss, stft_distance   # vocoder training loss / waveform distance on the device
 """
+from .configs import HiFiGANPeriodDiscriminatorConfig, HiFiGANTrainingConfig  # noqa: F401
 from .configs import AudioConfig, BaseConfig, HiFiGANConfig, MelGANConfig, MelGANDiscriminatorConfig, Tacotron2Config, TextConfig  # noqa: F401
 
 
@@ -29,7 +31,13 @@ def __getattr__(name):  # torch-dependent classes are imported lazily
     if name == "MelGANTrainer":
         from .melgan_training import MelGANTrainer
         return MelGANTrainer
-    if name in ("MelGANDiscriminatorLoss", "MelGANGeneratorLoss"):
+    if name == "HiFiGANPeriodDiscriminator":
+        from .hifigan_disc import HiFiGANPeriodDiscriminator
+        return HiFiGANPeriodDiscriminator
+    if name == "HiFiGANTrainer":
+        from .hifigan_training import HiFiGANTrainer
+        return HiFiGANTrainer
+    if name in ("MelGANDiscriminatorLoss", "MelGANGeneratorLoss", "HiFiGANDiscriminatorLoss", "HiFiGANGeneratorLoss"):
         from . import losses
         return getattr(losses, name)
     if name == "MultiResolutionSTFTLoss":

@@ -56,6 +56,16 @@ class gvx_melgan_disc_entry(C.Structure):
     _fields_ = [("byte_offset", C.c_uint64), ("channels", C.c_int32), ("positions", C.c_int32)]
 
 
+class gvx_hifigan_mpd_dims(C.Structure):
+    _fields_ = [("n_periods", C.c_int32), ("periods", C.c_int32 * 8), ("n_layers", C.c_int32), ("channels", C.c_int32 * 8),
+                ("kernel_size", C.c_int32), ("stride", C.c_int32), ("slope", C.c_float)]
+
+
+class gvx_hifigan_mpd_entry(C.Structure):
+    _fields_ = [("byte_offset", C.c_uint64), ("channels", C.c_int32), ("height", C.c_int32), ("period", C.c_int32), ("reserved", C.c_int32),
+                ("stride_b", C.c_int64), ("stride_c", C.c_int64), ("stride_h", C.c_int64), ("stride_p", C.c_int64)]
+
+
 class gvx_stft_resolution(C.Structure):
     _fields_ = [("n_fft", C.c_int32), ("hop", C.c_int32), ("win_length", C.c_int32)]
 
@@ -220,6 +230,18 @@ SIGNATURES = {
     "gvx_melgan_disc_workspace_bytes": (_sz, [C.POINTER(gvx_melgan_disc_dims), _i, _i, _i]),
     "gvx_melgan_disc_forward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _sz, _vp]),
     "gvx_melgan_disc_backward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, C.POINTER(gvx_weight_desc), _i, _vp, _vp, _sz, _vp]),
+    "gvx_hifigan_mpd_blob_floats": (_sz, [C.POINTER(gvx_hifigan_mpd_dims)]),
+    "gvx_hifigan_mpd_pack_weights_device": (_i, [C.POINTER(gvx_hifigan_mpd_dims), C.POINTER(gvx_weight_desc), _i, _vp, _vp]),
+    "gvx_hifigan_mpd_create": (_i, [C.POINTER(gvx_hifigan_mpd_dims), C.POINTER(_vp)]),
+    "gvx_hifigan_mpd_destroy": (None, [_vp]),
+    "gvx_hifigan_mpd_bind": (_i, [_vp, _vp]),
+    "gvx_hifigan_mpd_layout": (_i, [C.POINTER(gvx_hifigan_mpd_dims), _i, _i, C.POINTER(gvx_hifigan_mpd_entry), _i]),
+    "gvx_hifigan_mpd_features_bytes": (_sz, [C.POINTER(gvx_hifigan_mpd_dims), _i, _i]),
+    "gvx_hifigan_mpd_workspace_bytes": (_sz, [C.POINTER(gvx_hifigan_mpd_dims), _i, _i, _i]),
+    "gvx_hifigan_mpd_forward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _sz, _vp]),
+    "gvx_hifigan_mpd_backward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, C.POINTER(gvx_weight_desc), _i, _vp, _vp, _sz, _vp]),
+    "gvx_hifigan_mpd_timing_enable": (_i, [_vp, _i]),
+    "gvx_hifigan_mpd_layer_times_ms": (_i, [_vp, C.POINTER(_f), C.POINTER(_f), C.POINTER(_i)]),
     "gvx_stft_loss_create": (_i, [C.POINTER(gvx_stft_resolution), _i, _f, _f, _f, C.POINTER(_vp)]),
     "gvx_stft_loss_destroy": (None, [_vp]),
     "gvx_stft_loss_workspace_bytes": (_sz, [_vp, _i, _l]),

@@ -355,3 +355,88 @@ class HiFiGANConfig(BaseConfig):
     def from_published(cls, config: Mapping[str, Any]) -> "HiFiGANConfig":
         """The generator's part of a published ``config.json`` (as a dict); that file's training and audio keys are ignored."""
         return cls(**{k: config[k] for k in cls._FIELDS if k in config})
+
+
+class HiFiGANPeriodDiscriminatorConfig(BaseConfig):
+    """HiFi-GAN's multi-period discriminator (Kong et al. 2020; include/genvox_amd.h, "HiFi-GAN period discriminators").  The defaults
+    are the published ``MultiPeriodDiscriminator``; the ranges are what the kernels take."""
+
+    MAX_PERIODS = 8      # GVX_HIFIGAN_MPD_MAX_PERIODS
+    MAX_LAYERS = 8       # GVX_HIFIGAN_MPD_MAX_LAYERS
+    MAX_PERIOD = 64      # GVX_HIFIGAN_MPD_MAX_PERIOD
+    MFMA_MULT = 32       # GVX_HIFIGAN_MPD_MFMA_MULT
+
+    _FIELDS = {
+        "periods": ((2, 3, 5, 7, 11), None),
+        "channels": ((32, 128, 512, 1024, 1024), None),
+        "kernel_size": (5, None),
+        "stride": (3, None),
+        "leaky_slope": (0.1, None),
+    }
+
+    def _normalise(self) -> None:
+        try:
+            self.periods = [int(p) for p in self.periods]
+            self.channels = [int(c) for c in self.channels]
+        except (TypeError, ValueError):
+            raise ValueError("periods and channels must be sequences of integers") from None
+        for name in ("kernel_size", "stride"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise ValueError(f"{name} must be an integer, not {v!r}")
+        if not 1 <= len(self.periods) <= self.MAX_PERIODS:
+            raise ValueError(f"periods must name 1 to {self.MAX_PERIODS} periods, not {len(self.periods)}")
+        for p in self.periods:
+            if not 1 <= p <= self.MAX_PERIOD:
+                raise ValueError(f"periods: {p} is outside [1, {self.MAX_PERIOD}]")
+        if not 2 <= len(self.channels) <= self.MAX_LAYERS:
+            raise ValueError(f"channels must name 2 to {self.MAX_LAYERS} layers, not {len(self.channels)}")
+        for c in self.channels:
+            if not 1 <= c <= 4096:
+                raise ValueError(f"channels: {c} is outside [1, 4096]")
+            if c > 64 and c % self.MFMA_MULT:
+                raise ValueError(f"channels: {c} is above 64 and no multiple of {self.MFMA_MULT}, the matrix kernels' k-tile")
+        if not 1 <= self.kernel_size <= 15 or self.kernel_size % 2 == 0:
+            raise ValueError(f"kernel_size = {self.kernel_size} must be odd and in [1, 15]")
+        if not 1 <= self.stride <= 8:
+            raise ValueError(f"stride = {self.stride} is outside [1, 8]")
+        if not 0.0 <= float(self.leaky_slope) <= 1.0:
+            raise ValueError(f"leaky_slope = {self.leaky_slope} is outside [0, 1]")
+
+    def layer_shapes(self):
+        """The convolutions of one period, the score last, as (c_in, c_out, taps, stride, padding) along the height."""
+        shapes, cin = [], 1
+        for i, c in enumerate(self.channels):
+            shapes.append((cin, c, self.kernel_size, 1 if i == len(self.channels) - 1 else self.stride, self.kernel_size // 2))
+            cin = c
+        shapes.append((cin, 1, 3, 1, 1))
+        return shapes
+
+    @property
+    def min_samples(self) -> int:
+        """The shortest row: the reflection of the largest period p needs at most p - 1 samples behind the first."""
+        return max(self.periods)
+
+    def parameter_count(self) -> int:
+        return len(self.periods) * sum(cout * cin * k + cout for cin, cout, k, _s, _p in self.layer_shapes())
+
+
+class HiFiGANTrainingConfig(BaseConfig):
+    """The training keys of a published HiFi-GAN ``config.json`` under their names and with their defaults; ``feat_match`` and
+    ``aux_weight`` are the weights that implementation keeps in its training script (2 on the feature-matching term, 45 on the
+    spectral term).  ``grad_clip_thresh`` <= 0 switches clipping off, as published."""
+
+    _FIELDS = {
+        "learning_rate": (2e-4, (0.0, None)),
+        "adam_b1": (0.8, (0.0, 1.0)),
+        "adam_b2": (0.99, (0.0, 1.0)),
+        "lr_decay": (0.999, (0.0, 1.0)),
+        "weight_decay": (0.01, (0.0, None)),
+        "feat_match": (2.0, (0.0, None)),
+        "aux_weight": (45.0, (0.0, None)),
+        "grad_clip_thresh": (0.0, None),
+    }
+
+    @classmethod
+    def from_published(cls, config: Mapping[str, Any]) -> "HiFiGANTrainingConfig":
+        return cls(**{k: config[k] for k in cls._FIELDS if k in config})

@@ -206,3 +206,70 @@ class MelGANGeneratorLoss(torch.nn.Module):
         fm = self.feat_match * fm
         self.last_terms = (adv, fm)
         return adv + fm
+
+
+# ---- the least-squares losses of the HiFi-GAN step (Kong et al. 2020), over any number of discriminators
+def _row_mean_any(values: torch.Tensor, lengths) -> torch.Tensor:
+    """values [B, C, L] or [B, C, H, p] -> the mean over rows of each row's mean over its own elements: C x L_b, or C x H_b x p
+    (``lengths`` [B]: L_b or H_b; None: the whole map, the published mean)."""
+    if values.dim() == 3:
+        return _row_mean(values, lengths)
+    if values.dim() != 4:
+        raise ValueError(f"a discriminator map is [B, C, L] or [B, C, H, p], got {tuple(values.shape)}")
+    B, Cn, H, P = values.shape
+    if lengths is None:
+        return values.mean(dim=(1, 2, 3)).mean()
+    lens = torch.as_tensor(lengths, device=values.device).to(torch.int64).reshape(B)
+    inside = (torch.arange(H, device=values.device)[None, :] < lens[:, None])[:, None, :, None]
+    kept = torch.where(inside, values, torch.zeros((), dtype=values.dtype, device=values.device))
+    return (kept.sum(dim=(1, 2, 3)) / (Cn * P * lens).to(values.dtype)).mean()
+
+
+def _as_outputs(maps, map_lengths):
+    """One discriminator's output ([sub-discriminator][map] tensors) or a list of such -> the list form, with its lengths."""
+    if len(maps) and len(maps[0]) and isinstance(maps[0][0], torch.Tensor):
+        return [maps], [map_lengths]
+    return list(maps), ([None] * len(maps) if map_lengths is None else list(map_lengths))
+
+
+class HiFiGANDiscriminatorLoss(torch.nn.Module):
+    """The published least-squares discriminator loss: the sum over all sub-discriminators (periods, scales) of
+    mean((1 - D(real))^2) + mean(D(fake)^2) on the scores (the last map of each).  ``real`` / ``fake``: the output of one discriminator
+    ([sub-discriminator][map]) or a list of such outputs - ``HiFiGANPeriodDiscriminator``'s 4-D maps and ``MelGANDiscriminator``'s 3-D
+    maps alike; ``map_lengths`` the matching ``map_lengths(sample_lengths)`` (or list of them): every mean is then a mean per row over
+    the row's own elements, then over rows; for rows of equal length that is the published mean."""
+
+    def forward(self, real, fake, map_lengths=None) -> torch.Tensor:
+        real, lens = _as_outputs(real, map_lengths)
+        fake, _ = _as_outputs(fake, map_lengths)
+        loss = 0.0
+        for d, (rs, fs) in enumerate(zip(real, fake)):
+            for k, (r, f) in enumerate(zip(rs, fs)):
+                ln = _lengths_of(lens[d], k, len(r) - 1)
+                loss = loss + _row_mean_any((1.0 - r[-1]) ** 2, ln) + _row_mean_any(f[-1] ** 2, ln)
+        return loss
+
+
+class HiFiGANGeneratorLoss(torch.nn.Module):
+    """The generator's side as published: adversarial = the sum over all sub-discriminators of mean((1 - D(fake))^2) on the scores;
+    feature matching = ``feat_match`` times the sum over ALL maps - the score's included, as published - of mean|real - fake|, the real
+    maps detached.  Inputs and means as in HiFiGANDiscriminatorLoss.  ``last_terms`` holds (adversarial, feature matching) of the
+    last call."""
+
+    def __init__(self, feat_match: float = 2.0) -> None:
+        super().__init__()
+        self.feat_match = float(feat_match)
+        self.last_terms = None
+
+    def forward(self, real, fake, map_lengths=None) -> torch.Tensor:
+        real, lens = _as_outputs(real, map_lengths)
+        fake, _ = _as_outputs(fake, map_lengths)
+        adv, fm = 0.0, 0.0
+        for d, (rs, fs) in enumerate(zip(real, fake)):
+            for k, (r, f) in enumerate(zip(rs, fs)):
+                adv = adv + _row_mean_any((1.0 - f[-1]) ** 2, _lengths_of(lens[d], k, len(f) - 1))
+                for i in range(len(f)):
+                    fm = fm + _row_mean_any((f[i] - r[i].detach()).abs(), _lengths_of(lens[d], k, i))
+        fm = self.feat_match * fm
+        self.last_terms = (adv, fm)
+        return adv + fm

@@ -1291,6 +1291,105 @@ int gvx_melgan_disc_backward(gvx_melgan_disc* handle, const float* wav, const in
                              const void* features, const void* d_features, const gvx_grad_desc* grads, int n_grads, float* d_wav,
                              void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- HiFi-GAN period discriminators (Kong et al. 2020, the published DiscriminatorP / MultiPeriodDiscriminator): forward, and the
+ * backward that reads the forward's own maps as its tape.  The surface mirrors the MelGAN discriminators' above.
+ *
+ * The model.  For each period p = periods[j] and each row of n_b samples: the row is extended by reflection (sample n_b + i is sample
+ * n_b - 2 - i) to H_0 p samples, H_0 = ceil(n_b / p), and read as a grid of H_0 heights and p columns, sample i at (i / p, i % p).
+ * Layers i = 0 .. n_layers - 1 convolve along the height only: Conv2d(c_{i-1} -> channels[i], (kernel_size, 1), zero padding
+ * (kernel_size / 2, 0), stride (stride, 1) for all but the last, (1, 1) for the last), each followed by LeakyReLU(slope); heights
+ * H' = (H - 1) / stride + 1 for the strided layers.  The score is Conv2d(c_last -> 1, (3, 1), padding (1, 0)) without activation.  All
+ * n_layers + 1 maps are returned (post-activation; the last is the score).  The p columns of a grid never mix.
+ *
+ * Ragged batches: sample_lengths is int32 [B] on the device, or NULL for all n_max.  Row b is computed as if alone at n_b =
+ * min(sample_lengths[b], n_max): the reflection, the zero padding and every height are its own; nothing of wav at or behind n_b is
+ * read; every map is exact zeros behind the row's own height; a ragged row has the bits of its one-row run.  A row needs n_b >= the
+ * largest period (its reflection); the host cannot see device lengths, so the CALLER checks them - a shorter row comes out as all-zero
+ * maps, never a bad address.
+ *
+ * Dims are refused (GVX_ERR_INVALID_ARG from create and pack, 0 from the size functions) unless: n_periods in [1, 8]; every period in
+ * [1, 64]; n_layers in [2, 8]; every channel count in [1, 4096] and, above 64, a multiple of 32; kernel_size odd and in [1, 15];
+ * stride in [1, 8]; slope in [0, 1].
+ *
+ * Weights.  gvx_hifigan_mpd_pack_weights_device reads PyTorch-layout tensors from DEVICE pointers, by name:
+ *     discriminators.<j>.convs.<i>.weight [c_out][c_in][kernel_size] (Conv2d's trailing 1 dropped), .bias [c_out],
+ *     discriminators.<j>.conv_post.weight [1][c_last][3], .bias [1]
+ * and writes the blob (gvx_hifigan_mpd_blob_floats): every weight twice, as [c_out][tap][c_in] for the forward and as
+ * [c_in][tap][c_out] for the data gradient, so that both products read their k index contiguously.  A missing name is
+ * GVX_ERR_MISSING_WEIGHT, a wrong element count GVX_ERR_SHAPE, both before anything is launched.  The blob must be 256-byte aligned.
+ *
+ * Features buffer: the caller's, 256-byte aligned, gvx_hifigan_mpd_features_bytes long.  Maps are CHANNELS-LAST: map (j, i) is fp32
+ * [B][height][period][channels], every map starting at a multiple of 256 bytes.  gvx_hifigan_mpd_layout (host arithmetic) lists, period
+ * by period and map by map, the byte offset, channels, height (of a row of n_max samples), period, and the strides in floats of the
+ * [B, C, H, p] view.  It returns the number of entries, n_periods * (n_layers + 1), and fills at most max_entries of them (entries
+ * may be NULL); 0 for refused dims, B or n_max.
+ *
+ * Workspace: gvx_hifigan_mpd_workspace_bytes(dims, B, n_max, backward) is host arithmetic; any contents when a call starts, nothing is
+ * cleared, 256-byte aligned.  The forward needs none beyond the minimum of 256 bytes; the backward's holds two activation gradients of
+ * the largest map and the partial weight and bias gradients of the layer that needs most.
+ *
+ * Kernels.  A workgroup computes GVX_HIFIGAN_MPD_TILE positions (height, column) of one row, in every kernel family; a data gradient's
+ * workgroup takes its positions from ONE stride phase (input heights h with the same h mod stride), so that only the taps
+ * t = (h + pad) mod stride, + stride, ... are multiplied.  A layer whose two channel counts are multiples of GVX_HIFIGAN_MPD_MFMA_MULT
+ * runs - forward, data gradient and weight gradient - as an implicit GEMM on v_mfma_f32_32x32x2_f32, GVX_HIFIGAN_MPD_TILE_N_WIDE
+ * output channels per workgroup of the forward and the data gradient where that many are produced, GVX_HIFIGAN_MPD_TILE_N below; the others (the first layer, which absorbs the reflection and the reshape; the score, whose input channels
+ * are dealt over the lanes of a wave and added by a fixed butterfly; narrow test layers) are fp32 VALU code.  LeakyReLU and its mask
+ * are applied in the epilogues.  Nothing is computed for a tile that lies behind its row.
+ *
+ * gvx_hifigan_mpd_forward: refused before anything is launched: a NULL handle, wav or features, B outside [1, 65535], n_max below the
+ * largest period (GVX_ERR_INVALID_ARG); n_max above GVX_HIFIGAN_MPD_MAX_SAMPLES (GVX_ERR_UNSUPPORTED); no blob bound (GVX_ERR_STATE);
+ * a misaligned or short features buffer, a NULL, misaligned or short workspace (GVX_ERR_WORKSPACE).
+ *
+ * gvx_hifigan_mpd_backward: features is what the forward wrote for the same wav, lengths and weights - it is the tape: a LeakyReLU
+ * output is positive exactly where its pre-activation is, so the masks are read off the maps.  d_features has the layout of features
+ * and holds the cotangent of EVERY map; nothing of it is read behind a row's own heights.  grads is a HOST table of n_grads DEVICE
+ * destinations under the packer's names, each WRITTEN in PyTorch's layout; n_grads = 0 skips every parameter gradient.  d_wav is fp32
+ * [B][n_max], the sum over the periods in their order through the adjoint of the reshape and the reflection (a gather: a sample
+ * collects its own cell and the reflected cell that copies it), exactly 0 at and behind n_b, or NULL to skip it.  What a call does
+ * compute has the bits the full call gives it.  Refused as the forward refuses, and: a missing name (GVX_ERR_MISSING_WEIGHT), a wrong
+ * element count or NULL destination (GVX_ERR_SHAPE), a NULL d_features, or neither gradient asked for (GVX_ERR_INVALID_ARG).  Weight
+ * and bias gradients are summed over rows and positions in pieces that are added in a fixed order; no atomics: two calls give the
+ * same bits. */
+enum { GVX_HIFIGAN_MPD_MAX_PERIODS = 8, GVX_HIFIGAN_MPD_MAX_LAYERS = 8, GVX_HIFIGAN_MPD_MAX_PERIOD = 64, GVX_HIFIGAN_MPD_TILE = 64,
+       GVX_HIFIGAN_MPD_TILE_N = 64, GVX_HIFIGAN_MPD_TILE_N_WIDE = 128, GVX_HIFIGAN_MPD_MFMA_MULT = 32, GVX_HIFIGAN_MPD_MAX_SAMPLES = 1 << 24 };
+typedef struct gvx_hifigan_mpd_dims {
+    int32_t n_periods;
+    int32_t periods[8];
+    int32_t n_layers;
+    int32_t channels[8];
+    int32_t kernel_size;
+    int32_t stride;
+    float slope;
+} gvx_hifigan_mpd_dims;
+typedef struct gvx_hifigan_mpd_entry {
+    uint64_t byte_offset;
+    int32_t channels;
+    int32_t height;
+    int32_t period;
+    int32_t reserved;
+    int64_t stride_b, stride_c, stride_h, stride_p;   /* floats, of the [B, C, H, p] view */
+} gvx_hifigan_mpd_entry;
+typedef struct gvx_hifigan_mpd gvx_hifigan_mpd;
+size_t gvx_hifigan_mpd_blob_floats(const gvx_hifigan_mpd_dims* dims);
+int gvx_hifigan_mpd_pack_weights_device(const gvx_hifigan_mpd_dims* dims, const gvx_weight_desc* table, int n, float* device_blob,
+                                        void* stream);
+int gvx_hifigan_mpd_create(const gvx_hifigan_mpd_dims* dims, gvx_hifigan_mpd** out);
+void gvx_hifigan_mpd_destroy(gvx_hifigan_mpd* handle);
+int gvx_hifigan_mpd_bind(gvx_hifigan_mpd* handle, const float* device_blob);
+int gvx_hifigan_mpd_layout(const gvx_hifigan_mpd_dims* dims, int B, int n_max, gvx_hifigan_mpd_entry* entries, int max_entries);
+size_t gvx_hifigan_mpd_features_bytes(const gvx_hifigan_mpd_dims* dims, int B, int n_max);
+size_t gvx_hifigan_mpd_workspace_bytes(const gvx_hifigan_mpd_dims* dims, int B, int n_max, int backward);
+int gvx_hifigan_mpd_forward(gvx_hifigan_mpd* handle, const float* wav, const int32_t* sample_lengths, int B, int n_max, void* features,
+                            size_t features_bytes, void* workspace, size_t workspace_bytes, void* stream);
+int gvx_hifigan_mpd_backward(gvx_hifigan_mpd* handle, const float* wav, const int32_t* sample_lengths, int B, int n_max,
+                             const void* features, const void* d_features, const gvx_grad_desc* grads, int n_grads, float* d_wav,
+                             void* workspace, size_t workspace_bytes, void* stream);
+/* Measurement only (tools/bench_extra.py hifigan_mpd): when enabled, the calls record events around every layer;
+ * gvx_hifigan_mpd_layer_times_ms synchronises and returns, per layer (the score last; n_layers + 1 of them) and summed over the periods,
+ * the time of the last forward and of the last backward (a layer's weight, bias and data gradient together; 0 for a call not made). */
+int gvx_hifigan_mpd_timing_enable(gvx_hifigan_mpd* handle, int enable);
+int gvx_hifigan_mpd_layer_times_ms(gvx_hifigan_mpd* handle, float* forward_ms, float* backward_ms, int* n_layers_out);
+
 /* ---- Multi-resolution STFT loss: the distance between a predicted waveform and its target that a vocoder is trained on (spectral
  * convergence plus log-magnitude L1 over several STFT resolutions; Yamamoto et al., Parallel WaveGAN), value and gradient in one call.
  * The reference ships no vocoder loss; this is the standard non-adversarial one, on the in-LDS transforms of the vocoder kernels.

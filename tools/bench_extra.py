@@ -25,7 +25,11 @@ with the spread and the time per stage, against the same float32 network built f
 parameters, through torch's own ROCm convolutions, and against `MelGANGenerator` and Griffin-Lim (32 iterations) on the same mels;
 `hifigan_train` (on request): HiFi-GAN V1 `vocode_with_grad` + `backward()` (gvx_hifigan_forward_train + gvx_hifigan_backward) at 16 x 32
 and 8 x 128 frames between device events, median of 7 with the spread, against autograd through the same torch.nn network, with the
-forward's and the backward's time per stage from the same run and the tape's and the workspace's size."""
+forward's and the backward's time per stage from the same run and the tape's and the workspace's size;
+`hifigan_mpd` (on request): HiFi-GAN's multi-period discriminator, default shape, at 16 x 8192 and 8 x 32768 samples between device events,
+median of 7 with the spread: forward, forward + full backward (cotangents on every map), against torch's own Conv2d + autograd on the
+same parameters; per layer the counted multiply-adds, the time (events around every layer, summed over the periods) and the share of
+the fp32 matrix rate; and one `HiFiGANTrainer.train_step` of the V1 generator against the period discriminators."""
 import json
 import os
 import sys
@@ -532,6 +536,112 @@ def main():
             real = wav.detach()
             res[key]["train_step"] = ev_spread(lambda: trainer.train_step(mel, real), warm=2, reps=5)
             print(json.dumps({key: {"train_step": res[key]["train_step"]}}), flush=True)
+    if "hifigan_mpd" in which:
+        import ctypes as C
+        import statistics
+
+        import torch.nn.functional as F
+
+        from genvox_amd import _lib
+        from genvox_amd.configs import HiFiGANConfig, HiFiGANPeriodDiscriminatorConfig
+        from genvox_amd.hifigan import HiFiGANGenerator
+        from genvox_amd.hifigan_disc import HiFiGANPeriodDiscriminator
+        from genvox_amd.hifigan_training import HiFiGANTrainer
+
+        FP32_MATRIX_TFLOPS = 157.3   # the MI355X's fp32 matrix (= vector) peak
+
+        def ev_spread(fn, warm=2, reps=7):
+            for _ in range(warm):
+                fn()
+            out = []
+            for _ in range(reps):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                e1.synchronize()
+                out.append(e0.elapsed_time(e1))
+            return {"median_ms": round(statistics.median(out), 3), "min_ms": round(min(out), 3), "max_ms": round(max(out), 3), "runs": reps}
+
+        torch.manual_seed(0)
+        pc = HiFiGANPeriodDiscriminatorConfig()
+        mpd = HiFiGANPeriodDiscriminator(pc).to("cuda:0")
+        with torch.no_grad():
+            for name, p in mpd.named_parameters():
+                if name.endswith("bias"):
+                    p.copy_(0.1 * torch.randn_like(p))
+        pparams = dict(mpd.named_parameters())
+        pshapes = pc.layer_shapes()
+
+        def torch_mpd(wav):
+            """The published composition on the module's own parameters, through torch's Conv2d kernels."""
+            out = []
+            for j, p in enumerate(pc.periods):
+                x, n = wav[:, None, :], wav.shape[1]
+                if n % p:
+                    x = F.pad(x, (0, p - n % p), "reflect")
+                h, maps = x.view(wav.shape[0], 1, -1, p), []
+                for i, (_ci, _co, _k, stride, pad) in enumerate(pshapes):
+                    name = f"discriminators.{j}.conv_post" if i == len(pshapes) - 1 else f"discriminators.{j}.convs.{i}"
+                    h = F.conv2d(h, pparams[name + ".weight"], pparams[name + ".bias"], stride=(stride, 1), padding=(pad, 0))
+                    if i < len(pshapes) - 1:
+                        h = F.leaky_relu(h, pc.leaky_slope)
+                    maps.append(h)
+                out.append(maps)
+            return out
+
+        def layer_macs(n):
+            """Multiply-adds of one row of n samples per layer, summed over the periods (every tap counted, padding included)."""
+            heights = mpd.feature_heights(n)
+            return [sum(heights[j][i] * p * co * ci * k for j, p in enumerate(pc.periods)) for i, (ci, co, k, _s, _p) in enumerate(pshapes)]
+
+        gen = torch.Generator(device="cuda").manual_seed(0)
+        hvoc = HiFiGANGenerator(HiFiGANConfig(), ac).to("cuda:0")
+        for B, n in ((16, 8192), (8, 32768)):
+            key = f"hifigan_mpd_{B}x{n}"
+            wav = (0.3 * torch.randn(B, n, device="cuda", generator=gen)).requires_grad_(True)
+            with torch.no_grad():
+                ours_maps, torch_maps = mpd(wav), torch_mpd(wav)
+                res[key] = {"forward": ev_spread(lambda: mpd(wav)), "torch_forward": ev_spread(lambda: torch_mpd(wav))}
+            res[key]["max_relative_map_difference_from_torch"] = max(float((a - b).abs().max() / b.abs().max()) for x, y in zip(ours_maps, torch_maps) for a, b in zip(x, y))
+            cots = [[torch.randn(m.shape, device="cuda", generator=gen) / m.numel() for m in ms] for ms in ours_maps]
+
+            def step(net):
+                wav.grad = None
+                for p in pparams.values():
+                    p.grad = None
+                sum((m * c).sum() for ms, cs in zip(net(wav), cots) for m, c in zip(ms, cs)).backward()
+
+            res[key]["forward_plus_backward"] = ev_spread(lambda: step(mpd))
+            got = {k: p.grad.clone() for k, p in pparams.items()}
+            got["wav"] = wav.grad.clone()
+            res[key]["torch_forward_plus_backward"] = ev_spread(lambda: step(torch_mpd))
+            res[key]["max_relative_gradient_difference_from_torch"] = max(
+                [float((got[k] - p.grad).abs().max() / p.grad.abs().max().clamp_min(1e-30)) for k, p in pparams.items()]
+                + [float((got["wav"] - wav.grad).abs().max() / wav.grad.abs().max())])
+            res[key]["backward_workspace_mb"] = round(mpd._train_workspace.numel() / 1e6, 1)
+            # per layer: counted multiply-adds and the share of the fp32 matrix rate, from events around every layer of one more call
+            lib = _lib.load()
+            _lib.check(lib.gvx_hifigan_mpd_timing_enable(mpd._handle, 1))
+            step(mpd)
+            fwd_ms, bwd_ms, n_l = (C.c_float * 9)(), (C.c_float * 9)(), C.c_int()
+            _lib.check(lib.gvx_hifigan_mpd_layer_times_ms(mpd._handle, fwd_ms, bwd_ms, C.byref(n_l)))
+            _lib.check(lib.gvx_hifigan_mpd_timing_enable(mpd._handle, 0))
+            macs = [B * m for m in layer_macs(n)]
+            res[key]["multiply_adds_per_row_forward"] = sum(layer_macs(n))
+            res[key]["layers"] = [
+                {"layer": f"{ci}->{co}", "forward_gmacs": round(m / 1e9, 3), "forward_ms": round(fwd_ms[i], 3),
+                 "forward_share_of_fp32_matrix_rate": round(2 * m / (fwd_ms[i] * 1e-3) / (FP32_MATRIX_TFLOPS * 1e12), 4) if fwd_ms[i] > 0 else None,
+                 "backward_ms": round(bwd_ms[i], 3),
+                 "backward_share_of_fp32_matrix_rate": round(2 * (2 if i else 1) * m / (bwd_ms[i] * 1e-3) / (FP32_MATRIX_TFLOPS * 1e12), 4) if bwd_ms[i] > 0 else None}
+                for i, ((ci, co, _k, _s, _p), m) in enumerate(zip(pshapes, macs))]
+            print(json.dumps({key: res[key]}), flush=True)
+            trainer = HiFiGANTrainer(hvoc, [mpd])
+            mel = (0.5 * torch.randn(B, 80, n // hvoc.hop, device="cuda", generator=gen) - 0.5).contiguous()
+            real = wav.detach()
+            res[key]["train_step_v1"] = ev_spread(lambda: trainer.train_step(mel, real), warm=2, reps=5)
+            print(json.dumps({key: {"train_step_v1": res[key]["train_step_v1"]}}), flush=True)
+            del trainer
     if which & {"hifigan", "hifigan_train"}:
         import ctypes as C
         import statistics
