@@ -249,6 +249,8 @@ SIGNATURES = {
     "gvx_kernel_timing_enable": (_i, [_vp, _i]),
     "gvx_model_set_persistent_attention": (_i, [_vp, _i]),
     "gvx_model_set_resident_kernels": (_i, [_vp, _i]),
+    "gvx_model_set_winograd": (_i, [_vp, _i]),
+    "gvx_debug_conv_plan": (_i, [_vp, _i, _i, _i]),
     "gvx_teacher_forced_rows_per_call": (_i, [_vp, _i]),
     "gvx_teacher_forced_resident": (_i, [_vp, _i, _i]),
     "gvx_teacher_forced_loop_kind": (_i, [_vp, _i, _i]),

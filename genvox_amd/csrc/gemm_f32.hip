@@ -1,10 +1,15 @@
 // Dense fp32 GEMM on the gfx950 f32 matrix instruction (v_mfma_f32_32x32x2_f32): exact fp32,
-// bit-for-bit a k-ordered fmaf chain per output, which is what the 1e-3 parity budget needs
+// every output of a PRODUCT bit-for-bit a k-ordered fmaf chain, which is what the 1e-3 parity budget needs
 // (bf16/f16 MFMA inputs would not fit it; there is no xf32 on gfx950).
 //
 // Used for every "dense over all positions" contraction on the path:
 //   encoder convs, encoder LSTM input projection, memory projection, Prenet, mel/gate projection
 //   (teacher-forced: hoisted out of the step loop), Postnet convs.
+// Not every CONVOLUTION is such a chain any more: the Postnet's square 5-tap layers run as Winograd F(4,5) (winograd_conv.hip) -
+// eight of these products per layer in one launch (GemmParams::slices, grid.y = the slice), each still a k-ordered chain over
+// the channels, summed by the output transform.  That rounds differently from the direct form (3-4 times its error per layer,
+// three orders below the budget) and was given up on purpose for 20 -> 8 multiplies per 4 frames; the first and last Postnet
+// layer and the encoder's convolutions are direct implicit GEMMs as described next.
 // conv1d(k, pad (k-1)/2) is an implicit GEMM: activations are kept channels-last with a zero halo,
 // [B][T+2p][C], so the im2col row of (b,t) is simply the 5*C contiguous floats starting at row t
 // of the padded buffer - no gather, no materialised im2col.  The conv weight is repacked at load
@@ -72,7 +77,11 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int blo
     // split-K: this workgroup's k range and partial output (the whole K and C itself when splitk == 1)
     const int k_begin = p.splitk > 1 ? (int)blockIdx.y * p.kchunk : 0;
     const int k_end = p.splitk > 1 ? min(p.K, k_begin + p.kchunk) : p.K;
-    float* const Cout = p.C + (p.splitk > 1 ? (long)blockIdx.y * p.c_split : 0);
+    // a batch of slices (splitk == 1 then): grid.y is the slice, each with its own A, W and C
+    const long slice = p.splitk > 1 ? 0 : (long)blockIdx.y;
+    const float* const Ab = p.A + slice * p.a_slice;
+    const float* const Wb = p.W + slice * p.w_slice;
+    float* const Cout = p.C + (p.splitk > 1 ? (long)blockIdx.y * p.c_split : slice * p.c_slice);
 
     // global -> register staging assignments
     const int ld_row = tid / TPR, ld_c4 = tid % TPR;
@@ -102,13 +111,13 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int blo
         for (int i = 0; i < A_V4; ++i) {
             int m = m0 + ld_row + RPP * i;
             a_ok[i] = m < p.M;
-            a_ptr[i] = p.A + (a_ok[i] ? row_off(p.amap, m) : 0);
+            a_ptr[i] = Ab + (a_ok[i] ? row_off(p.amap, m) : 0);
         }
 #pragma unroll
         for (int i = 0; i < B_V4; ++i) {
             int n = n0 + ld_row + RPP * i;
             b_ok[i] = n < p.N;
-            b_ptr[i] = p.W + (b_ok[i] ? (long)n * p.ldw : 0);
+            b_ptr[i] = Wb + (b_ok[i] ? (long)n * p.ldw : 0);
         }
     }
     float4 a_reg[A_V4], b_reg[B_V4];
@@ -135,8 +144,8 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int blo
 #define GEMM_LOAD_TILE(K0)                                                                                  \
     if (KMAJ) {                                                                                             \
         const int K0_ = (K0);                                                                               \
-        GEMM_KMAJ_LOAD(A_P, (256 / A_MQ), akq, ak_g, ak_i, p.amap, a_safe, p.A, a_col, ka_reg)              \
-        GEMM_KMAJ_LOAD(B_P, (256 / B_NQ), bkq, bk_g, bk_i, p.wmap, b_safe, p.W, b_col, kb_reg)              \
+        GEMM_KMAJ_LOAD(A_P, (256 / A_MQ), akq, ak_g, ak_i, p.amap, a_safe, Ab, a_col, ka_reg)              \
+        GEMM_KMAJ_LOAD(B_P, (256 / B_NQ), bkq, bk_g, bk_i, p.wmap, b_safe, Wb, b_col, kb_reg)              \
     } else                                                                                                  \
     {                                                                                                       \
         const int k_ = (K0) + 4 * ld_c4;                                                                    \
@@ -309,7 +318,7 @@ template <int WR, int WC, int TM, int TN, bool KMAJ = false, int BK = BK32>
 static hipError_t launch_cfg(const GemmParams& p, hipStream_t s) {
     constexpr int BM = WR * TM * 32, BN = WC * TN * 32;
     const int grid = ((p.M - p.m_begin + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-    gemm_f32_kernel<WR, WC, TM, TN, KMAJ, BK><<<dim3(grid, p.splitk > 1 ? p.splitk : 1), dim3(WR * WC * 64), lds_bytes_cfg<WR, WC, TM, TN, BK>(), s>>>(p);
+    gemm_f32_kernel<WR, WC, TM, TN, KMAJ, BK><<<dim3(grid, p.splitk > 1 ? p.splitk : p.slices > 1 ? p.slices : 1), dim3(WR * WC * 64), lds_bytes_cfg<WR, WC, TM, TN, BK>(), s>>>(p);
     return hipGetLastError();
 }
 
@@ -324,6 +333,7 @@ static bool four_waves() {
 GemmPlan plan_gemm(const GemmParams& p) {
     GemmPlan pl{hipSuccess, 0, 0};
     if (p.M <= 0 || p.N <= 0) return pl;
+    if (p.slices > 1 && (p.splitk > 1 || p.kmajor || p.keep || p.slices > 65535)) { pl.err = hipErrorInvalidValue; return pl; }
     if (p.kmajor) {   // K-major operands (weight gradients): the two square-ish tile shapes only, any K; 16-byte pieces along m / n
         if ((p.M & 3) || (p.N & 3) || p.M < 4 || p.N < 4 || ((p.amap.s0 | p.amap.s1 | p.wmap.s0 | p.wmap.s1) & 3)) { pl.err = hipErrorInvalidValue; return pl; }
         const long t128 = (long)((p.M + 127) / 128) * ((p.N + 127) / 128);
@@ -341,7 +351,8 @@ GemmPlan plan_gemm(const GemmParams& p) {
     }
     // fewer than ~1.5 workgroups per CU with 128 x 128 tiles (encoder convolutions: 4096 x 512): halve the tile height so
     // that all 256 CUs get work
-    const long n_tiles = (p.N + 127) / 128, tiles128 = (long)((p.M + 127) / 128) * n_tiles;
+    // (a batch of slices: the launch holds the tiles of all of them - `n_tiles` counts a row tile's columns over the slices)
+    const long n_tiles = (long)((p.N + 127) / 128) * (p.slices > 1 ? p.slices : 1), tiles128 = (long)((p.M + 127) / 128) * n_tiles;
     // and below ~0.75 per CU (the encoder convolutions themselves: 128 tiles) 64 x 64 tiles, two workgroups per CU: one
     // 64 x 128 workgroup of four waves per CU left the matrix pipe waiting on its own loads (155 -> 115 us per convolution)
     if (tiles128 < 192) { pl.tile = 2211; return pl; }

@@ -57,6 +57,23 @@ int fail(int code, const char* fmt, ...) {
 
 std::mutex& capture_mutex() { return g_capture_mutex; }
 
+bool conv_uses_winograd(const gvx_model* m, int cin, int cout, int k) {
+    if (m->winograd <= 0 || !winograd_shape_ok(cin, cout, k)) return false;
+    return m->winograd >= 2 || cin >= WINOGRAD_MIN_CHANNELS;
+}
+
+// Scratch of the Postnet's Winograd layers: V and M of one group of tiles, 2 x 8 x C floats per tile.  The whole batch where that
+// stays inside WINOGRAD_GROUP_BYTES, else that budget in whole tiles (a layer then runs group after group; a group is any range
+// of the batch's tiles, and where it is cut changes no value).  From the shape alone: a workspace amount must not depend on a knob.
+size_t winograd_scratch_floats(const gvx_model* m, int B, int T) {
+    bool any = false;
+    for (int i = 0; i < m->d.postnet_n_conv; ++i) any = any || postnet_layer_winograd_shape(m->d, i);
+    if (!any) return 0;
+    const size_t tile = (size_t)2 * WINO_PTS * m->d.postnet_dim, all = (size_t)B * ((T + WINO_OUT - 1) / WINO_OUT) * tile;
+    const size_t budget = WINOGRAD_GROUP_BYTES / sizeof(float) / tile * tile;
+    return all <= budget ? all : budget > tile ? budget : tile;
+}
+
 WsPlan make_ws_plan(const gvx_model* m, int B, int L, int T, int mode) {
     const gvx_dims& d = m->d;
     const int E = d.embed_dim, H = E / 2, M = d.n_mels, P = d.prenet_dim, A = d.att_rnn_dim, D = d.dec_rnn_dim;
@@ -101,6 +118,8 @@ WsPlan make_ws_plan(const gvx_model* m, int B, int L, int T, int mode) {
     const int cmax = d.postnet_dim > M ? d.postnet_dim : M;
     w.ya = take((size_t)B * (T + 2 * pp) * cmax);
     w.yb = take((size_t)B * (T + 2 * pp) * cmax);
+    // (the Postnet's Winograd scratch inside the fused forward is [xa, ya): every buffer of the encoder and the decoder is dead
+    // once the projection has been split into mel_out and gate_out - the status and hand-off words sit in front of xa)
     w.total = off;
     return w;
 }
@@ -194,6 +213,8 @@ void read_knobs(gvx_model* m) {
     m->debug_skip_resident = flag("GVX_DEBUG_SKIP_RESIDENT", false);
     m->debug_enc_skip_block = number("GVX_DEBUG_ENC_SKIP_BLOCK", -1);
     m->debug_plan = std::getenv("GVX_DEBUG_PLAN") != nullptr;
+    m->winograd = number("GVX_CONV_WINOGRAD", 1);
+    if (m->winograd < 0 || m->winograd > 2) m->winograd = 1;
 }
 
 }  // namespace
@@ -391,8 +412,10 @@ int encoder_impl(gvx_model* m, const int64_t* tokens, const int32_t* lengths, in
 // Postnet + residual on channels-last halo buffers ya / yb (each B * (T + 2p) * max(postnet_dim, n_mels) floats).
 // mel_lengths (optional): row b is treated as a sequence of mel_lengths[b] frames - the input and every layer's output
 // are zero from that frame on, exactly what the convolutions of a batch-1 run see as padding at the sequence end.
+// wino: wino_floats floats of scratch (V and M of one group of tiles) for the layers that run as Winograd F(4,5); at least one
+// tile's worth, more than WINOGRAD_GROUP_BYTES is not used.
 int postnet_impl(gvx_model* m, const float* mel_in, const int32_t* mel_lengths, int B, int T, float* mel_post_out, float* ya,
-                 float* yb, hipStream_t s) {
+                 float* yb, float* wino, size_t wino_floats, hipStream_t s) {
     const gvx_dims& d = m->d;
     const int M = d.n_mels, pp = (d.postnet_kernel - 1) / 2, n = d.postnet_n_conv;
     // every conv input needs zero halo rows in ITS channel layout: the producer of a buffer writes them (the transpose for
@@ -403,6 +426,34 @@ int postnet_impl(gvx_model* m, const float* mel_in, const int32_t* mel_lengths, 
     for (int i = 0; i < n; ++i) {
         const int cin = i == 0 ? M : d.postnet_dim, cout = i == n - 1 ? M : d.postnet_dim;
         const bool last = i == n - 1;
+        if (postnet_layer_winograd_shape(d, i) && conv_uses_winograd(m, cin, cout, d.postnet_kernel)) {
+            // input transform, eight products in one batched launch, output transform (bias, tanh, row_len, the halo rows of nxt);
+            // V and M are written whole before they are read, group by group
+            const int C = cin;
+            const long total = (long)B * ((T + WINO_OUT - 1) / WINO_OUT);
+            const size_t tile = (size_t)2 * WINO_PTS * C, budget = WINOGRAD_GROUP_BYTES / sizeof(float);
+            long fit = (long)((wino_floats < budget ? wino_floats : budget) / tile);
+            if (fit < 1) return fail(GVX_ERR_WORKSPACE, "Postnet: %zu floats of scratch do not hold one Winograd tile (%zu)", wino_floats, tile);
+            if (m->wino_group > 0 && m->wino_group < fit) fit = m->wino_group;
+            if (fit > total) fit = total;
+            const long groups = (total + fit - 1) / fit, per_group = (total + groups - 1) / groups;   // as equal as they come
+            for (long mt0 = 0; mt0 < total; mt0 += per_group) {
+                const long Mt = total - mt0 < per_group ? total - mt0 : per_group;
+                float* V = wino;
+                float* Mm = wino + (size_t)WINO_PTS * Mt * C;
+                HIP_TRY(launch_winograd_input(cur, V, B, mt0, Mt, T, C, s));
+                GemmParams g{};
+                g.A = V; g.amap = RowMap{(int)Mt, 0, (long)C};
+                g.W = m->dev_blob + m->blob.post_u[i]; g.ldw = C;
+                g.C = Mm; g.cmap = RowMap{(int)Mt, 0, (long)C};
+                g.bias = nullptr; g.M = (int)Mt; g.N = C; g.K = C; g.act = ACT_NONE;
+                g.slices = WINO_PTS; g.a_slice = Mt * C; g.w_slice = (long)C * C; g.c_slice = Mt * C;
+                HIP_TRY(launch_gemm(g, s));
+                HIP_TRY(launch_winograd_output(Mm, m->dev_blob + m->blob.post_b[i], mel_lengths, nxt, B, mt0, Mt, T, C, s));
+            }
+            float* t = cur; cur = nxt; nxt = t;
+            continue;
+        }
         const int out_halo = last ? 0 : pp;
         const bool fused_halo = out_halo > 0 && T >= out_halo;
         if (out_halo > 0 && !fused_halo) HIP_TRY(launch_zero_halo(nxt, B, T, pp, cout, s));
@@ -421,7 +472,7 @@ int postnet_impl(gvx_model* m, const float* mel_in, const int32_t* mel_lengths, 
     return GVX_OK;
 }
 
-struct PostnetPlan { size_t ya, yb, total; };
+struct PostnetPlan { size_t ya, yb, wino, wino_floats, total; };
 PostnetPlan make_postnet_plan(const gvx_model* m, int B, int T) {
     const gvx_dims& d = m->d;
     const int pp = (d.postnet_kernel - 1) / 2, cmax = d.postnet_dim > d.n_mels ? d.postnet_dim : d.n_mels;
@@ -429,7 +480,14 @@ PostnetPlan make_postnet_plan(const gvx_model* m, int B, int T) {
     PostnetPlan p;
     p.ya = align_up((128 + HANDOFF_WORDS) * sizeof(float), 256);   // behind the status and hand-off words of the full plan
     p.yb = p.ya + buf;
-    p.total = p.yb + buf;
+    p.wino = p.yb + buf;
+    // the Winograd scratch, but never more than the model workspaces have in front of their own ya for the shortest row (those
+    // promise to hold a Postnet call: gvx_workspace_bytes_autoregressive and gvx_workspace_bytes are not to grow for it)
+    const WsPlan w = make_ws_plan(m, B, 1, T, WS_AUTOREGRESSIVE);
+    const size_t tile = (size_t)2 * WINO_PTS * d.postnet_dim, room = (w.ya - w.xa) / sizeof(float) / tile * tile;
+    p.wino_floats = winograd_scratch_floats(m, B, T);
+    if (p.wino_floats > room) p.wino_floats = room > tile ? room : tile;
+    p.total = p.wino + align_up(p.wino_floats * sizeof(float), 256);
     return p;
 }
 
@@ -502,6 +560,40 @@ int gvx_debug_encoder_resident(const gvx_model* m, int B) {
 int gvx_model_set_persistent_attention(gvx_model* m, int enable) {
     if (!m) return fail(GVX_ERR_INVALID_ARG, "null argument");
     m->attn_persistent = enable != 0;
+    return GVX_OK;
+}
+
+int gvx_model_set_winograd(gvx_model* m, int mode) {
+    if (!m) return fail(GVX_ERR_INVALID_ARG, "null argument");
+    if (mode < 0 || mode > 2) return fail(GVX_ERR_INVALID_ARG, "winograd mode must be 0, 1 or 2 (got %d)", mode);
+    m->winograd = mode;
+    return GVX_OK;
+}
+
+// 1: a Postnet convolution layer of this shape runs as Winograd F(4,5) on this handle, 0: as the direct implicit GEMM
+// (conv_uses_winograd, the function postnet_impl asks); host arithmetic only
+int gvx_debug_conv_plan(const gvx_model* m, int cin, int cout, int k) {
+    if (!m || cin < 1 || cout < 1 || k < 1) return -1;
+    return conv_uses_winograd(m, cin, cout, k) ? 1 : 0;
+}
+
+// Host-only, for the tests (not in the public header).  Tiles of four frames per Winograd group: 0 = as the scratch allows,
+// n > 0 = at most n (where a group ends must not change a bit)
+int gvx_debug_set_winograd_group(gvx_model* m, int tiles) {
+    if (!m || tiles < 0) return fail(GVX_ERR_INVALID_ARG, "bad argument");
+    m->wino_group = tiles;
+    return GVX_OK;
+}
+
+// The transform matrices of winograd_f45.h as doubles: at[4][8], g[8][5], bt[8][8]
+int gvx_debug_winograd_constants(double* at, double* g, double* bt) {
+    if (!at || !g || !bt) return fail(GVX_ERR_INVALID_ARG, "null argument");
+    for (int i = 0; i < WINO_OUT; ++i)
+        for (int s = 0; s < WINO_PTS; ++s) at[i * WINO_PTS + s] = wino_AT(i, s);
+    for (int s = 0; s < WINO_PTS; ++s) {
+        for (int k = 0; k < WINO_TAPS; ++k) g[s * WINO_TAPS + k] = wino_G(s, k);
+        for (int i = 0; i < WINO_PTS; ++i) bt[s * WINO_PTS + i] = wino_BT(s, i);
+    }
     return GVX_OK;
 }
 
@@ -634,7 +726,8 @@ int gvx_postnet_forward(gvx_model* m, const float* mel_in, const int32_t* mel_le
     const PostnetPlan pp = make_postnet_plan(m, B, T);
     if (ws_bytes < pp.total) return fail(GVX_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", ws_bytes, pp.total);
     if (!mel_in || !mel_post_out) return fail(GVX_ERR_INVALID_ARG, "null argument");
-    return postnet_impl(m, mel_in, mel_lengths, B, T, mel_post_out, ws_ptr<float>(ws, pp.ya), ws_ptr<float>(ws, pp.yb), (hipStream_t)stream);
+    return postnet_impl(m, mel_in, mel_lengths, B, T, mel_post_out, ws_ptr<float>(ws, pp.ya), ws_ptr<float>(ws, pp.yb), ws_ptr<float>(ws, pp.wino), pp.wino_floats,
+                        (hipStream_t)stream);
 }
 
 int gvx_mask_padding(float* mel, float* mel_post, float* gate, const int32_t* mel_lengths, int B, int n_mels, int T, void* stream) {
@@ -692,7 +785,8 @@ int gvx_tacotron2_forward(gvx_model* m, const int64_t* tokens, const int32_t* to
     // (mel_post_out == nullptr: the caller runs the Postnet and the padding mask itself - over all chunks of a larger batch in
     // one call, whose GEMMs fill the chip better than a chunk's; a timed-out call's NaN in mel_out reaches them through the Postnet)
     if (mel_post_out) {
-        rc = postnet_impl(m, mel_out, nullptr, B, T, mel_post_out, ws_ptr<float>(ws, wp.ya), ws_ptr<float>(ws, wp.yb), s);
+        rc = postnet_impl(m, mel_out, nullptr, B, T, mel_post_out, ws_ptr<float>(ws, wp.ya), ws_ptr<float>(ws, wp.yb), ws_ptr<float>(ws, wp.xa),
+                          (wp.ya - wp.xa) / sizeof(float), s);
         if (rc != GVX_OK) return rc;
         if (mel_lengths) HIP_TRY(launch_mask_padding(mel_out, mel_post_out, gate_out, mel_lengths, B, m->d.n_mels, T, s));
     }

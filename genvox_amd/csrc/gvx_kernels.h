@@ -64,6 +64,10 @@ struct GemmParams {
     int c_halo = 0;                    // > 0: C has c_halo halo rows before and after each group's cmap.R rows (C points at
                                        // the first interior row); the tile that owns an edge row also zeroes "its" halo row
                                        // (requires cmap.R >= c_halo)
+    // batch of `slices` independent products of one shape in one launch (the eight Winograd products of a convolution):
+    // slice z reads A + z * a_slice and W + z * w_slice and writes C + z * c_slice; bias, row_len and the row maps are shared.
+    // grid.y carries the slice, so splitk must be 1 then (row-major operands, no keep mask)
+    int slices = 1; long a_slice = 0, w_slice = 0, c_slice = 0;
 };
 hipError_t launch_gemm(const GemmParams& p, hipStream_t s);
 // What launch_gemm does with p, as host arithmetic (no device is touched).  tile: the <WR,WC,TM,TN> shape as the four digits
@@ -406,6 +410,12 @@ hipError_t launch_residual_to_channels_first(const float* mel, const float* y, f
                                              const int32_t* lens, hipStream_t s);
 // zero the 2*halo halo rows of every sequence of a channels-last buffer [B][T+2*halo][C]
 hipError_t launch_zero_halo(float* buf, int B, int T, int halo, int C, hipStream_t s);
+// k = 5 convolution as Winograd F(4,5) (winograd_conv.hip): the transforms on either side of the batched GEMM, for the tiles
+// [mt0, mt0 + nmt) of the batch (tile b * ceil(T / 4) + j = frames 4 j .. 4 j + 3 of sequence b).  x / y: the batch's halo
+// buffers [B][T + 4][C], V / M: [8][nmt][C]; C % 4 == 0.  The output transform adds the bias, applies tanh, zeroes frames at or
+// behind row_len[b] (may be nullptr) and writes y's halo rows.
+hipError_t launch_winograd_input(const float* x, float* V, int B, long mt0, long nmt, int T, int C, hipStream_t s);
+hipError_t launch_winograd_output(const float* M, const float* bias, const int32_t* row_len, float* y, int B, long mt0, long nmt, int T, int C, hipStream_t s);
 hipError_t launch_mask_padding(float* mel, float* mel_post, float* gate, const int32_t* mel_lengths, int B, int M, int T,
                                hipStream_t s);
 // if *tmo != 0 (a bounded in-launch wait of this call gave up): NaN over the n_arrays (<= 4) output arrays and *sticky = *tmo

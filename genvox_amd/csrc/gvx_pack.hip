@@ -38,6 +38,9 @@ Blob make_blob_layout(const gvx_dims& d) {
         b.post_w[i] = take((size_t)cout * d.postnet_kernel * cin);
         b.post_b[i] = take(cout);
     }
+    // behind everything else (every older offset stays where it was): the Winograd transforms of the layers whose shape admits them
+    for (int i = 0; i < d.postnet_n_conv; ++i)
+        if (postnet_layer_winograd_shape(d, i)) b.post_u[i] = take((size_t)WINO_PTS * d.postnet_dim * d.postnet_dim);
     b.total = off;
     return b;
 }
@@ -72,7 +75,8 @@ struct WeightTable {
 };
 
 // conv (+ eval BatchNorm) -> [Cout][k][Cin] with the BN scale folded in, bias' = (b - mean) * scale + beta
-int pack_conv(const WeightTable& wt, const std::string& prefix, int cout, int cin, int k, float* w_out, float* b_out) {
+// u_out (optional, k = 5): the Winograd transform of the same folded weights, U[8][Cout][Cin] = G w (winograd_f45.h)
+int pack_conv(const WeightTable& wt, const std::string& prefix, int cout, int cin, int k, float* w_out, float* b_out, float* u_out = nullptr) {
     int rc = GVX_OK;
     const float* w = wt.get(prefix + ".0.conv.weight", (int64_t)cout * cin * k, &rc); if (!w) return rc;
     const float* b = wt.get(prefix + ".0.conv.bias", cout, &rc); if (!b) return rc;
@@ -85,6 +89,10 @@ int pack_conv(const WeightTable& wt, const std::string& prefix, int cout, int ci
         for (int kk = 0; kk < k; ++kk)
             for (int ci = 0; ci < cin; ++ci)
                 w_out[((size_t)co * k + kk) * cin + ci] = (float)((double)w[((size_t)co * cin + ci) * k + kk] * scale);
+        if (u_out)
+            for (int ci = 0; ci < cin; ++ci)
+                for (int s = 0; s < WINO_PTS; ++s)
+                    u_out[((size_t)s * cout + co) * cin + ci] = wino_weight(w + ((size_t)co * cin + ci) * k, 1, scale, s);
         b_out[co] = (float)(((double)b[co] - (double)mu[co]) * scale + (double)beta[co]);
     }
     return GVX_OK;
@@ -225,7 +233,8 @@ int gvx_model_pack_weights(gvx_model* m, const gvx_weight_desc* table, int n, vo
     }
     for (int i = 0; i < d.postnet_n_conv; ++i) {
         const int cin = i == 0 ? M : d.postnet_dim, cout = i == d.postnet_n_conv - 1 ? M : d.postnet_dim;
-        rc = pack_conv(wt, "postnet.convolutions." + std::to_string(i), cout, cin, d.postnet_kernel, out + bl.post_w[i], out + bl.post_b[i]);
+        rc = pack_conv(wt, "postnet.convolutions." + std::to_string(i), cout, cin, d.postnet_kernel, out + bl.post_w[i], out + bl.post_b[i],
+                       postnet_layer_winograd_shape(d, i) ? out + bl.post_u[i] : nullptr);
         if (rc != GVX_OK) return rc;
     }
     return GVX_OK;
@@ -245,14 +254,17 @@ __global__ void pack_gather_kernel(PackSources src, const int32_t* off, const ui
         blob[i] = t ? src.p[t - 1][off[i]] : 0.f;
     }
 }
-// pack_conv on the device: [Cout][Cin][k] -> [Cout][k][Cin] with the eval-mode BatchNorm scale folded in (double, like the host)
+// pack_conv on the device: [Cout][Cin][k] -> [Cout][k][Cin] with the eval-mode BatchNorm scale folded in (double, like the host);
+// u_out (nullptr: none): the Winograd transform U[8][Cout][Cin] of the same weights, the host's expression (wino_weight)
 __global__ void pack_conv_fold_kernel(const float* w, const float* b, const float* g, const float* beta, const float* mu, const float* var,
-                                      int cout, int cin, int k, float* w_out, float* b_out) {
+                                      int cout, int cin, int k, float* w_out, float* b_out, float* u_out) {
     const long n = (long)cout * cin * k;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
         const int ci = (int)(i % cin), kk = (int)((i / cin) % k), co = (int)(i / ((long)cin * k));
         const double scale = (double)g[co] / sqrt((double)var[co] + BN_EPS);
         w_out[i] = (float)((double)w[((long)co * cin + ci) * k + kk] * scale);
+        if (u_out && kk == 0)
+            for (int s = 0; s < WINO_PTS; ++s) u_out[((long)s * cout + co) * cin + ci] = wino_weight(w + ((long)co * cin + ci) * k, 1, scale, s);
         if (ci == 0 && kk == 0) b_out[co] = (float)(((double)b[co] - (double)mu[co]) * scale + (double)beta[co]);
     }
 }
@@ -314,6 +326,7 @@ int ensure_gather_map(gvx_model* m, const gvx_weight_desc* table, int n) {
     for (int i = 0; i < d.postnet_n_conv; ++i) {
         const int cin = i == 0 ? M : d.postnet_dim, cout = i == d.postnet_n_conv - 1 ? M : d.postnet_dim;
         mark(b.post_w[i], (size_t)cout * d.postnet_kernel * cin); mark(b.post_b[i], cout);
+        if (postnet_layer_winograd_shape(d, i)) mark(b.post_u[i], (size_t)WINO_PTS * cout * cin);
     }
     mark(b.enc_bih, (size_t)8 * H); mark(b.att_bias, (size_t)4 * d.att_rnn_dim); mark(b.dec_bias, (size_t)4 * d.dec_rnn_dim);
     // sanity: every gathered float points inside its tensor
@@ -351,7 +364,7 @@ int gvx_model_pack_weights_device(gvx_model* m, const gvx_weight_desc* table, in
     const gvx_dims& d = m->d;
     const Blob& bl = m->blob;
     const int E = d.embed_dim, H = E / 2, M = d.n_mels;
-    auto conv = [&](const std::string& prefix, int cout, int cin, int k, size_t w_off, size_t b_off) -> int {
+    auto conv = [&](const std::string& prefix, int cout, int cin, int k, size_t w_off, size_t b_off, const size_t* u_off = nullptr) -> int {
         int r = GVX_OK;
         const float* w = dt.get(prefix + ".0.conv.weight", (int64_t)cout * cin * k, &r); if (!w) return r;
         const float* b = dt.get(prefix + ".0.conv.bias", cout, &r); if (!b) return r;
@@ -360,14 +373,16 @@ int gvx_model_pack_weights_device(gvx_model* m, const gvx_weight_desc* table, in
         const float* mu = dt.get(prefix + ".1.running_mean", cout, &r); if (!mu) return r;
         const float* var = dt.get(prefix + ".1.running_var", cout, &r); if (!var) return r;
         const long cnt = (long)cout * cin * k;
-        hipLaunchKernelGGL(pack_conv_fold_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, w, b, g, beta, mu, var, cout, cin, k, out + w_off, out + b_off);
+        hipLaunchKernelGGL(pack_conv_fold_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, w, b, g, beta, mu, var, cout, cin, k, out + w_off, out + b_off,
+                           u_off ? out + *u_off : (float*)nullptr);
         return GVX_OK;
     };
     for (int i = 0; i < d.enc_n_conv; ++i)
         if ((rc = conv("encoder.convolutions." + std::to_string(i), E, E, d.enc_kernel, bl.enc_w[i], bl.enc_b[i])) != GVX_OK) return rc;
     for (int i = 0; i < d.postnet_n_conv; ++i) {
         const int cin = i == 0 ? M : d.postnet_dim, cout = i == d.postnet_n_conv - 1 ? M : d.postnet_dim;
-        if ((rc = conv("postnet.convolutions." + std::to_string(i), cout, cin, d.postnet_kernel, bl.post_w[i], bl.post_b[i])) != GVX_OK) return rc;
+        if ((rc = conv("postnet.convolutions." + std::to_string(i), cout, cin, d.postnet_kernel, bl.post_w[i], bl.post_b[i],
+                       postnet_layer_winograd_shape(d, i) ? &bl.post_u[i] : nullptr)) != GVX_OK) return rc;
     }
     auto bias = [&](const std::string& bih_n, const std::string& bhh_n, int Hd, size_t o) -> int {
         int r = GVX_OK;

@@ -221,6 +221,19 @@ int gvx_debug_gemm_plan(int M, int N, int K, int kmajor, int have_scratch, size_
     return pl.err == hipSuccess ? GVX_OK : GVX_ERR_INVALID_ARG;
 }
 
+// ... and of a batch of `slices` row-major products of that shape in one launch (GemmParams::slices: the Winograd layers of the
+// Postnet); slices = 1 is the plain product.  Host arithmetic only, not in the public header.
+int gvx_debug_gemm_plan_batched(int M, int N, int K, int slices, int* tile_out, int* rows_big_out) {
+    if (!tile_out || !rows_big_out || M < 1 || N < 1 || K < 1 || slices < 1) return GVX_ERR_INVALID_ARG;
+    GemmParams g{};
+    g.amap = RowMap{M, 0, (long)K};
+    g.M = M; g.N = N; g.K = K;
+    g.slices = slices; g.a_slice = (long)M * K; g.w_slice = (long)N * K; g.c_slice = (long)M * N;
+    const GemmPlan pl = plan_gemm(g);
+    *tile_out = pl.tile; *rows_big_out = pl.rows_big;
+    return pl.err == hipSuccess ? GVX_OK : GVX_ERR_INVALID_ARG;
+}
+
 // C[m][n] = sum_k A[m*lda + k] * W[n*ldw + k] (+ bias[n]);  K % 4 == 0
 int gvx_train_gemm_nt(const float* A, long lda, const float* W, long ldw, float* C, long ldc, int M, int N, int K, const float* bias,
                       float* scratch, size_t scratch_bytes, void* stream) {

@@ -1,7 +1,7 @@
 """Multi-GPU plumbing for batched inference: one process per GPU, utterances sharded across ranks.
 
 The forward has no exchange step: utterances never interact (BatchNorm runs on running statistics), so the batch
-dimension partitions freely and the only collective is ONE broadcast of the packed weight blob (~113 MB fp32) from
+dimension partitions freely and the only collective is ONE broadcast of the packed weight blob (~144 MB fp32) from
 the rank that loaded the checkpoint, over RCCL/xGMI (``torch.distributed`` backend "nccl"; "gloo" works for CPU
 rehearsal of the sharding logic).  The reference is single-device.
 """

@@ -98,6 +98,7 @@ class Tacotron2(nn.Module):
         self._workspace: Optional[torch.Tensor] = None
         self._lane_ws = [None, None]     # workspaces of the two concurrent chunk lanes
         self._lane_streams = None
+        self._winograd_mode: Optional[int] = None   # set_winograd: None = the library's default (GVX_CONV_WINOGRAD)
         self._lane_handles = [None, None]   # autoregressive lanes run on host threads: one C-ABI handle each (same blob)
         self._timing = False
         self._sticky_bad = False        # host-side copies of the device status words (a replaced workspace takes its words with it)
@@ -321,6 +322,8 @@ class Tacotron2(nn.Module):
                 _lib.check(lib.gvx_model_set_persistent_attention(h.value, 0))
                 if self._resident_off:
                     _lib.check(lib.gvx_model_set_resident_kernels(h.value, 0))
+                if self._winograd_mode is not None:
+                    _lib.check(lib.gvx_model_set_winograd(h.value, self._winograd_mode))
                 _lib.check(lib.gvx_model_bind_blob(h.value, self._blob.data_ptr()))
                 if self._timing:
                     _lib.check(lib.gvx_stage_timing_enable(h.value, 1))
@@ -354,6 +357,20 @@ class Tacotron2(nn.Module):
     def enable_kernel_timing(self, enable: bool = True) -> None:
         self._ensure_packed()
         _lib.check(_lib.load().gvx_kernel_timing_enable(self._handle, int(enable)))
+
+    def set_winograd(self, mode: int) -> None:
+        """How the Postnet's square 5-tap convolutions run (gvx_model_set_winograd): 0 = direct implicit GEMM, 1 = Winograd F(4,5)
+        where the layer's shape was measured faster (default), 2 = wherever the form supports the shape.  Applies to every
+        handle of this model, the chunk lanes' included."""
+        self._ensure_handle()
+        for h in [self._handle] + self._lane_handles:
+            if h is not None:
+                _lib.check(_lib.load().gvx_model_set_winograd(h, int(mode)))
+        self._winograd_mode = int(mode)
+
+    def conv_plan(self, cin: int, cout: int, k: int) -> int:
+        """1 if a Postnet convolution of this shape runs as Winograd F(4,5) on this model, 0 if direct (gvx_debug_conv_plan)."""
+        return int(_lib.load().gvx_debug_conv_plan(self._ensure_handle(), cin, cout, k))
 
     def loop_kind(self, B: int, L: int) -> int:
         """How a teacher-forced inference call of this shape runs its decoder loop (gvx_teacher_forced_loop_kind): 2 = one resident

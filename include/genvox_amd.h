@@ -157,6 +157,18 @@ int gvx_model_set_persistent_attention(gvx_model* model, int enable);
  * enable = 1 restores the defaults (environment knobs are not re-read). */
 int gvx_model_set_resident_kernels(gvx_model* model, int enable);
 
+/* Postnet convolutions with as many input as output channels and 5 taps (layers 2-4 of the default model) may run as
+ * Winograd F(4,5) along time: 8 instead of 20 fp32 products per 4 output frames, against weights transformed when they are
+ * packed.  mode 0 = never (every layer the direct implicit GEMM), 1 = by the layer's shape (default: 256 channels and more),
+ * 2 = every layer whose shape the form supports (channels a multiple of 32).  The choice depends on (cin, cout, k) alone, never
+ * on B, T or the lengths, so a row's result does not depend on the batch it runs in.  Results differ from the direct form by
+ * fp32 rounding only (a few 1e-6 at the Postnet's output scale).  The environment variable GVX_CONV_WINOGRAD sets the mode a
+ * handle starts with.  Workspace sizes do not depend on the mode. */
+int gvx_model_set_winograd(gvx_model* model, int mode);
+/* 1 if a Postnet convolution of this shape runs as Winograd F(4,5) on this handle, 0 if as the direct implicit GEMM, -1 for
+ * a null handle or a non-positive size.  Host arithmetic: the question the Postnet itself asks. */
+int gvx_debug_conv_plan(const gvx_model* model, int cin, int cout, int k);
+
 /* Batch rows gvx_tacotron2_forward / gvx_decoder_teacher_forced serve best per call for rows of L tokens: 64 where the 64-row
  * loop beside the resident attention kernel applies (default layer sizes, L <= 128, resident attention enabled: one pass over
  * the recurrent weights per step for all 64 rows), else 32 (callers with more rows run 32-row chunks - in turn where gvx_teacher_forced_resident says 1, else on two streams with a
