@@ -5,11 +5,11 @@
 // Used for every "dense over all positions" contraction on the path:
 //   encoder convs, encoder LSTM input projection, memory projection, Prenet, mel/gate projection
 //   (teacher-forced: hoisted out of the step loop), Postnet convs.
-// Not every CONVOLUTION is such a chain any more: the Postnet's square 5-tap layers run as Winograd F(4,5) (winograd_conv.hip) -
+// Not every CONVOLUTION is such a chain any more: the Postnet's and the encoder's square 5-tap layers run as Winograd F(4,5) (winograd_conv.hip) -
 // eight of these products per layer in one launch (GemmParams::slices, grid.y = the slice), each still a k-ordered chain over
 // the channels, summed by the output transform.  That rounds differently from the direct form (3-4 times its error per layer,
 // three orders below the budget) and was given up on purpose for 20 -> 8 multiplies per 4 frames; the first and last Postnet
-// layer and the encoder's convolutions are direct implicit GEMMs as described next.
+// layer, every layer in Winograd mode 0 and the training forward's convolutions are direct implicit GEMMs as described next.
 // conv1d(k, pad (k-1)/2) is an implicit GEMM: activations are kept channels-last with a zero halo,
 // [B][T+2p][C], so the im2col row of (b,t) is simply the 5*C contiguous floats starting at row t
 // of the padded buffer - no gather, no materialised im2col.  The conv weight is repacked at load
@@ -370,6 +370,18 @@ GemmPlan plan_gemm(const GemmParams& p) {
         if (rows_big > 0 && rows_big < p.M) pl.rows_big = (int)rows_big;
     }
     return pl;
+}
+
+// The fewest rows M (a multiple of the 128-row tile) whose 128 x 128 tiles are a whole number of plan_gemm's rounds of 256 for this
+// N and slice count: a caller that cuts its rows into several products (the Winograd groups) cuts there, and only its last
+// product has a remainder.  0: the plan of `p` is not the big-tile one (few tiles: no rounds to speak of).
+long gemm_round_rows(const GemmParams& p) {
+    const GemmPlan pl = plan_gemm(p);
+    if (pl.err != hipSuccess || (pl.tile != 4212 && pl.tile != 2222)) return 0;
+    const long n_tiles = (long)((p.N + 127) / 128) * (p.slices > 1 ? p.slices : 1);
+    long a = 256, b = n_tiles;
+    while (b) { const long t = a % b; a = b; b = t; }   // a = gcd(256, n_tiles)
+    return 128 * (256 / a);
 }
 
 static hipError_t launch_tile(int tile, const GemmParams& p, hipStream_t s) {

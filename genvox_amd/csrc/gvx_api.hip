@@ -74,6 +74,25 @@ size_t winograd_scratch_floats(const gvx_model* m, int B, int T) {
     return all <= budget ? all : budget > tile ? budget : tile;
 }
 
+// Tiles per group of a Winograd layer of `total` tiles whose scratch holds `fit` of them (C channels): as few groups as fit, as
+// equal as they come - but every group except the last a whole number of rounds of the batched products' 128 x 128 tiles
+// (gemm_round_rows), so that only the last group's products end in a remainder launch on a part of the chip.  Where a group ends
+// changes no value.  One group where everything fits; where not even one round fits, the equal cut.
+long winograd_group_tiles(long total, long fit, int C) {
+    if (fit >= total) return total;
+    const long groups = (total + fit - 1) / fit, per = (total + groups - 1) / groups;
+    GemmParams g{};
+    g.M = (int)per; g.N = C; g.K = C; g.slices = WINO_PTS;
+    const long unit = gemm_round_rows(g);
+    if (unit <= 0) return per;
+    // a candidate: whole rounds, and still enough rows for the plan whose rounds they are
+    auto whole = [&](long rows) { g.M = (int)rows; return rows > 0 && rows <= fit && rows % unit == 0 && gemm_round_rows(g) == unit; };
+    const long down = per / unit * unit, up = (per + unit - 1) / unit * unit, most = fit / unit * unit;
+    if (whole(down) && total - (groups - 1) * down <= fit) return down;   // the same number of groups, the last one the largest
+    if (whole(up)) return up;                                             // ... the last one the smallest
+    return whole(most) ? most : per;                                      // one or two groups more; or no round fits the scratch
+}
+
 WsPlan make_ws_plan(const gvx_model* m, int B, int L, int T, int mode) {
     const gvx_dims& d = m->d;
     const int E = d.embed_dim, H = E / 2, M = d.n_mels, P = d.prenet_dim, A = d.att_rnn_dim, D = d.dec_rnn_dim;
@@ -198,7 +217,7 @@ void read_knobs(gvx_model* m) {
     m->ar_resident = flag("GVX_AR_RESIDENT", false);
     m->ar_split_h = flag("GVX_AR_SPLIT_H", true);
     m->enc_persistent = flag("GVX_ENC_PERSISTENT", true);
-    m->enc_fork_after = number("GVX_ENC_FORK_AFTER", 1);
+    m->enc_fork_after = number("GVX_ENC_FORK_AFTER", 2);
     m->train_resident = flag("GVX_TRAIN_RESIDENT", true);
     m->train_resident_loop = flag("GVX_TRAIN_RESIDENT_LOOP", true);
     m->tf_rows64 = flag("GVX_TF_ROWS64", false);
@@ -304,12 +323,55 @@ int conv_layer(const gvx_model* m, const float* in, float* out, int B, int T, in
     return GVX_OK;
 }
 
+// One k = 5, C -> C convolution layer as Winograd F(4,5) on the halo buffers cur -> nxt ([B][T + 4][C]): input transform, eight
+// products in one batched launch, output transform (bias, act, row_len, the halo rows of nxt).  wino: wino_floats floats of
+// scratch; V and M are written whole before they are read, group by group (winograd_group_tiles).
+int winograd_layer(const gvx_model* m, const char* who, const float* cur, float* nxt, int B, int T, int C, size_t u_off, size_t b_off,
+                   const int32_t* row_len, int act, float* wino, size_t wino_floats, hipStream_t s) {
+    const long total = (long)B * ((T + WINO_OUT - 1) / WINO_OUT);
+    const size_t tile = (size_t)2 * WINO_PTS * C, budget = WINOGRAD_GROUP_BYTES / sizeof(float);
+    long fit = (long)((wino_floats < budget ? wino_floats : budget) / tile);
+    if (fit < 1) return fail(GVX_ERR_WORKSPACE, "%s: %zu floats of scratch do not hold one Winograd tile (%zu)", who, wino_floats, tile);
+    if (m->wino_group > 0 && m->wino_group < fit) fit = m->wino_group;
+    const long per_group = winograd_group_tiles(total, fit, C);
+    for (long mt0 = 0, Mt; mt0 < total; mt0 += Mt) {
+        Mt = total - mt0 <= fit ? total - mt0 : per_group;   // (the last group takes what is left: at most `fit`, not at most per_group)
+        float* V = wino;
+        float* Mm = wino + (size_t)WINO_PTS * Mt * C;
+        HIP_TRY(launch_winograd_input(cur, V, B, mt0, Mt, T, C, s));
+        GemmParams g{};
+        g.A = V; g.amap = RowMap{(int)Mt, 0, (long)C};
+        g.W = m->dev_blob + u_off; g.ldw = C;
+        g.C = Mm; g.cmap = RowMap{(int)Mt, 0, (long)C};
+        g.bias = nullptr; g.M = (int)Mt; g.N = C; g.K = C; g.act = ACT_NONE;
+        g.slices = WINO_PTS; g.a_slice = Mt * C; g.w_slice = (long)C * C; g.c_slice = Mt * C;
+        HIP_TRY(launch_gemm(g, s));
+        HIP_TRY(launch_winograd_output(Mm, m->dev_blob + b_off, row_len, nxt, B, mt0, Mt, T, C, act, s));
+    }
+    return GVX_OK;
+}
+
+// Scratch of the encoder's layers that run as Winograd F(4,5) (V and M of a group of tiles): workspace regions that are dead while the
+// convolutions run, so that no workspace grows for them.
+//   alone == true  (gvx_encoder_forward: nothing else runs on the workspace): everything from xg to the end of the plan the call
+//                  checked the workspace against - xg .. pm are written behind the convolutions, the rest belongs to a decoder call.
+//   alone == false (the fused forward, whose Prenet products write frames, pre1, prenet and pre_gate on the caller's stream at
+//                  the same time - decoder_prenet_part): the larger of [xg, frames) - xg, enc_h, enc_c, memory, len_copy, pm, all
+//                  written on the encoder's stream behind the convolutions - and [h_a, pre_gate) - the decoder's states and
+//                  step buffers, first touched by decoder_init_states on the encoder's stream behind the encoder.
+struct WinoScratch { size_t off, floats; };
+WinoScratch encoder_wino_scratch(const WsPlan& wp, bool alone) {
+    if (alone) return {wp.xg, (wp.total - wp.xg) / sizeof(float)};
+    const size_t front = wp.frames - wp.xg, back = wp.pre_gate - wp.h_a;
+    return front >= back ? WinoScratch{wp.xg, front / sizeof(float)} : WinoScratch{wp.h_a, back / sizeof(float)};
+}
+
 // conv_out (training mode only): the output of the convolution stack, [B, E, L] in the reference's layout, computed by the
 // caller with batch statistics and dropout (gvx_conv_bn_act_train_forward); the embedding and the folded-BatchNorm
 // convolutions are then skipped and only the BiLSTM part runs
 int encoder_impl(gvx_model* m, const int64_t* tokens, const int32_t* lengths, int B, int L, float* memory_out, void* ws,
-                 const WsPlan& wp, hipStream_t s, const float* conv_out = nullptr, float* c_seq_out = nullptr, float* xg_out = nullptr,
-                 hipEvent_t dense_done = nullptr) {   // dense_done: recorded on s behind the convolutions (see below)
+                 const WsPlan& wp, const WinoScratch& wsc, hipStream_t s, const float* conv_out = nullptr, float* c_seq_out = nullptr,
+                 float* xg_out = nullptr, hipEvent_t dense_done = nullptr) {   // dense_done: recorded on s behind the convolutions (see below)
     const gvx_dims& d = m->d;
     const int E = d.embed_dim, H = E / 2, pe = (d.enc_kernel - 1) / 2;
     float* xa = ws_ptr<float>(ws, wp.xa);
@@ -328,7 +390,11 @@ int encoder_impl(gvx_model* m, const int64_t* tokens, const int32_t* lengths, in
         HIP_TRY(launch_embed(tokens, m->dev_blob + m->blob.emb, d.n_tokens, xa, xb, B, L, E, pe, flags + FLAG_TOKEN, s));   // (+ the halo rows of xa and xb)
         for (int i = 0; i < d.enc_n_conv; ++i) {
             if (dense_done && i == m->enc_fork_after) { HIP_TRY(hipEventRecord(dense_done, s)); dense_done = nullptr; }
-            int rc = conv_layer(m, cur, nxt, B, L, E, E, d.enc_kernel, m->blob.enc_w[i], m->blob.enc_b[i], ACT_RELU, pe, s);
+            // (the choice looks at the layer's shape and the handle's mode alone: a row's bits must not depend on B or L)
+            const bool wino = encoder_layer_winograd_shape(d, i) && conv_uses_winograd(m, E, E, d.enc_kernel);
+            int rc = wino ? winograd_layer(m, "encoder", cur, nxt, B, L, E, m->blob.enc_u[i], m->blob.enc_b[i], nullptr, ACT_RELU,
+                                           ws_ptr<float>(ws, wsc.off), wsc.floats, s)
+                          : conv_layer(m, cur, nxt, B, L, E, E, d.enc_kernel, m->blob.enc_w[i], m->blob.enc_b[i], ACT_RELU, pe, s);
             if (rc != GVX_OK) return rc;
             float* t = cur; cur = nxt; nxt = t;
         }
@@ -427,30 +493,8 @@ int postnet_impl(gvx_model* m, const float* mel_in, const int32_t* mel_lengths, 
         const int cin = i == 0 ? M : d.postnet_dim, cout = i == n - 1 ? M : d.postnet_dim;
         const bool last = i == n - 1;
         if (postnet_layer_winograd_shape(d, i) && conv_uses_winograd(m, cin, cout, d.postnet_kernel)) {
-            // input transform, eight products in one batched launch, output transform (bias, tanh, row_len, the halo rows of nxt);
-            // V and M are written whole before they are read, group by group
-            const int C = cin;
-            const long total = (long)B * ((T + WINO_OUT - 1) / WINO_OUT);
-            const size_t tile = (size_t)2 * WINO_PTS * C, budget = WINOGRAD_GROUP_BYTES / sizeof(float);
-            long fit = (long)((wino_floats < budget ? wino_floats : budget) / tile);
-            if (fit < 1) return fail(GVX_ERR_WORKSPACE, "Postnet: %zu floats of scratch do not hold one Winograd tile (%zu)", wino_floats, tile);
-            if (m->wino_group > 0 && m->wino_group < fit) fit = m->wino_group;
-            if (fit > total) fit = total;
-            const long groups = (total + fit - 1) / fit, per_group = (total + groups - 1) / groups;   // as equal as they come
-            for (long mt0 = 0; mt0 < total; mt0 += per_group) {
-                const long Mt = total - mt0 < per_group ? total - mt0 : per_group;
-                float* V = wino;
-                float* Mm = wino + (size_t)WINO_PTS * Mt * C;
-                HIP_TRY(launch_winograd_input(cur, V, B, mt0, Mt, T, C, s));
-                GemmParams g{};
-                g.A = V; g.amap = RowMap{(int)Mt, 0, (long)C};
-                g.W = m->dev_blob + m->blob.post_u[i]; g.ldw = C;
-                g.C = Mm; g.cmap = RowMap{(int)Mt, 0, (long)C};
-                g.bias = nullptr; g.M = (int)Mt; g.N = C; g.K = C; g.act = ACT_NONE;
-                g.slices = WINO_PTS; g.a_slice = Mt * C; g.w_slice = (long)C * C; g.c_slice = Mt * C;
-                HIP_TRY(launch_gemm(g, s));
-                HIP_TRY(launch_winograd_output(Mm, m->dev_blob + m->blob.post_b[i], mel_lengths, nxt, B, mt0, Mt, T, C, s));
-            }
+            const int rc = winograd_layer(m, "Postnet", cur, nxt, B, T, cin, m->blob.post_u[i], m->blob.post_b[i], mel_lengths, ACT_TANH, wino, wino_floats, s);
+            if (rc != GVX_OK) return rc;
             float* t = cur; cur = nxt; nxt = t;
             continue;
         }
@@ -570,8 +614,8 @@ int gvx_model_set_winograd(gvx_model* m, int mode) {
     return GVX_OK;
 }
 
-// 1: a Postnet convolution layer of this shape runs as Winograd F(4,5) on this handle, 0: as the direct implicit GEMM
-// (conv_uses_winograd, the function postnet_impl asks); host arithmetic only
+// 1: a Postnet or encoder convolution layer of this shape runs as Winograd F(4,5) on this handle, 0: as the direct implicit GEMM
+// (conv_uses_winograd, the function postnet_impl and encoder_impl ask); host arithmetic only
 int gvx_debug_conv_plan(const gvx_model* m, int cin, int cout, int k) {
     if (!m || cin < 1 || cout < 1 || k < 1) return -1;
     return conv_uses_winograd(m, cin, cout, k) ? 1 : 0;
@@ -583,6 +627,13 @@ int gvx_debug_set_winograd_group(gvx_model* m, int tiles) {
     if (!m || tiles < 0) return fail(GVX_ERR_INVALID_ARG, "bad argument");
     m->wino_group = tiles;
     return GVX_OK;
+}
+
+// Host-only, for the tests (not in the public header): tiles per group of a C-channel Winograd layer of `total` tiles whose scratch
+// holds `fit` of them (winograd_group_tiles, the function the layers ask); -1 on a bad argument
+long gvx_debug_winograd_group_tiles(long total, long fit, int channels) {
+    if (total < 1 || fit < 1 || channels < 4 || total > INT_MAX) return -1;
+    return winograd_group_tiles(total, fit, channels);
 }
 
 // The transform matrices of winograd_f45.h as doubles: at[4][8], g[8][5], bt[8][8]
@@ -631,7 +682,8 @@ int gvx_encoder_forward(gvx_model* m, const int64_t* tokens, const int32_t* leng
     int rc = check_common(m, B, L, 1, ws, ws_bytes, WS_AUTOREGRESSIVE);   // (the encoder's buffers precede every mode-dependent one)
     if (rc != GVX_OK) return rc;
     if (!tokens || !memory_out) return fail(GVX_ERR_INVALID_ARG, "null argument");
-    return encoder_impl(m, tokens, lengths, B, L, memory_out, ws, make_ws_plan(m, B, L, 1, WS_AUTOREGRESSIVE), (hipStream_t)stream);
+    const WsPlan wp = make_ws_plan(m, B, L, 1, WS_AUTOREGRESSIVE);
+    return encoder_impl(m, tokens, lengths, B, L, memory_out, ws, wp, encoder_wino_scratch(wp, true), (hipStream_t)stream);
 }
 
 int gvx_decoder_teacher_forced(gvx_model* m, const float* memory, const int32_t* lengths, int B, int L, const float* mel_in, int T,
@@ -654,8 +706,9 @@ int gvx_encoder_lstm_forward(gvx_model* m, const float* conv_out, const int32_t*
     if (rc != GVX_OK) return rc;
     if (!conv_out || !memory_out) return fail(GVX_ERR_INVALID_ARG, "null argument");
     if (cell_states_out) HIP_TRY(zero_async(cell_states_out, (size_t)B * L * m->d.embed_dim * sizeof(float), (hipStream_t)stream));
-    return encoder_impl(m, nullptr, lengths, B, L, memory_out, ws, make_ws_plan(m, B, L, 1, WS_AUTOREGRESSIVE), (hipStream_t)stream, conv_out,
-                        cell_states_out, input_preact_out);
+    const WsPlan wp = make_ws_plan(m, B, L, 1, WS_AUTOREGRESSIVE);   // (conv_out: the folded convolutions do not run, no scratch is touched)
+    return encoder_impl(m, nullptr, lengths, B, L, memory_out, ws, wp, encoder_wino_scratch(wp, true), (hipStream_t)stream, conv_out, cell_states_out,
+                        input_preact_out);
 }
 
 int gvx_decoder_teacher_forced_train(gvx_model* m, const float* memory, const int32_t* lengths, int B, int L, const float* mel_in, int T,
@@ -705,6 +758,7 @@ int gvx_train_export(const gvx_model* m, const void* ws_c, size_t ws_bytes, int 
         case 1: HIP_TRY(hipMemcpyAsync(dst, ws_ptr<float>(ws, wp.pre1), rows * d.prenet_dim * sizeof(float), hipMemcpyDeviceToDevice, s)); break;
         case 2: return gvx_train_unblock(ws_ptr<float>(ws, wp.prenet), dst, T + 1, B, d.prenet_dim, stream);
         case 3: HIP_TRY(hipMemcpyAsync(dst, ws_ptr<float>(ws, wp.pm), (size_t)B * L * d.att_dim * sizeof(float), hipMemcpyDeviceToDevice, s)); break;
+        case 4: HIP_TRY(hipMemcpyAsync(dst, ws_ptr<float>(ws, wp.memory), (size_t)B * L * d.embed_dim * sizeof(float), hipMemcpyDeviceToDevice, s)); break;
         default: return fail(GVX_ERR_INVALID_ARG, "gvx_train_export: unknown buffer %d", what);
     }
     return GVX_OK;
@@ -758,12 +812,12 @@ int gvx_tacotron2_forward(gvx_model* m, const int64_t* tokens, const int32_t* to
         if (rc != GVX_OK) return rc;
         HIP_TRY(hipEventRecord(m->pa_fork, s));
         HIP_TRY(hipStreamWaitEvent(m->pa_stream, m->pa_fork, 0));
-        // The Prenet products start behind the FIRST encoder convolution (enc_fork_after): side by side from the start the two sets
+        // The Prenet products start behind the SECOND encoder convolution (enc_fork_after): side by side from the start the two sets
         // of GEMMs slow each other and leave the second half of the recurrence - a quarter of the chip, latency bound - alone on
-        // an idle GPU; behind all three convolutions the `pre_gate` GEMM outlasts the recurrence (encoder stage 1.335 / 1.31 / 1.28 /
-        // 1.335 ms for the fork behind 3 / 2 / 1 / 0 convolutions with four-wave GEMM tiles; 1.14 / 1.13 / 1.15 / 1.22 with eight-wave ones:
-        // tools/r4_enc2.sh)
-        rc = encoder_impl(m, tokens, token_lengths, B, L, memory, ws, wp, m->pa_stream, nullptr, nullptr, nullptr, m->enc_mid);
+        // an idle GPU; behind all three convolutions the `pre_gate` GEMM outlasts the recurrence.  Encoder stage for the fork behind
+        // 3 / 2 / 1 / 0 convolutions, 32 x 800 frames: 1.016 / 1.007 / 1.033 / 1.114 ms with the convolutions as Winograd F(4,5)
+        // (medians of three runs, EXPERIMENTS.md; with direct convolutions it was 1.14 / 1.13 / 1.15 / 1.22, and 1 the default)
+        rc = encoder_impl(m, tokens, token_lengths, B, L, memory, ws, wp, encoder_wino_scratch(wp, false), m->pa_stream, nullptr, nullptr, nullptr, m->enc_mid);
         if (rc != GVX_OK) return rc;
         // the decoder's zero states and the memory projection (needs the encoder output) right behind the encoder on its stream:
         // they end under the tail of the Prenet products instead of between the join and the first step (~60 us)
@@ -775,7 +829,7 @@ int gvx_tacotron2_forward(gvx_model* m, const int64_t* tokens, const int32_t* to
         if (rc != GVX_OK) return rc;
         HIP_TRY(hipStreamWaitEvent(s, m->pa_join, 0));
     } else {
-        rc = encoder_impl(m, tokens, token_lengths, B, L, memory, ws, wp, s);
+        rc = encoder_impl(m, tokens, token_lengths, B, L, memory, ws, wp, encoder_wino_scratch(wp, false), s);
         if (rc != GVX_OK) return rc;
     }
     if (timed) HIP_TRY(hipEventRecord(m->ev[1], s));

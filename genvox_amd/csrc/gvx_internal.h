@@ -38,6 +38,7 @@ struct Blob {  // offsets in floats into the packed weight blob
     size_t proj_w, proj_b, proj_frag, proj_hd_t, proj_ctx_frag, proj_ctx_t;   // last three: autoregressive split of the projection (see gvx_decoder_autoregressive)
     size_t post_w[MAX_CONV], post_b[MAX_CONV];
     size_t post_u[MAX_CONV];   // Winograd transform U[8][Cout][Cin] = G w of the layers winograd_shape_ok admits (others: unused)
+    size_t enc_u[MAX_CONV];    // the same of the encoder's layers (encoder_layer_winograd_shape)
     size_t total;
 };
 // A convolution layer whose SHAPE admits the Winograd F(4,5) form (winograd_conv.hip): these have U in the blob.
@@ -45,6 +46,10 @@ inline bool winograd_shape_ok(int cin, int cout, int k) { return k == WINO_TAPS 
 // Postnet layer i is such a layer (the first and the last one, n_mels wide on one side, never are)
 inline bool postnet_layer_winograd_shape(const gvx_dims& d, int i) {
     return i > 0 && i < d.postnet_n_conv - 1 && winograd_shape_ok(d.postnet_dim, d.postnet_dim, d.postnet_kernel);
+}
+// Encoder layer i is such a layer (every one of them is embed_dim -> embed_dim: all or none)
+inline bool encoder_layer_winograd_shape(const gvx_dims& d, int i) {
+    return i >= 0 && i < d.enc_n_conv && winograd_shape_ok(d.embed_dim, d.embed_dim, d.enc_kernel);
 }
 Blob make_blob_layout(const gvx_dims& d);   // gvx_pack.hip
 
@@ -97,13 +102,13 @@ struct gvx_model {
     // launch into its XCD's L2 (both grids are dealt round-robin over the XCDs) - loop 20.27 -> 20.06 ms at 32 x 800
     // (GVX_ATTN_PREFETCH=0: off); the rotated K walk (GVX_SK_ROT, an A/B knob) is not followed
     bool attn_prefetch = true;
-    // Postnet convolutions with cin = cout, k = 5 as Winograd F(4,5): 0 never, 1 by the layer's shape (the shapes where it was
+    // Postnet and encoder convolutions with cin = cout, k = 5 as Winograd F(4,5): 0 never, 1 by the layer's shape (the shapes where it was
     // measured faster: at least WINOGRAD_MIN_CHANNELS channels), 2 every shape winograd_shape_ok admits (tests at small sizes).
     // GVX_CONV_WINOGRAD=<mode>, gvx_model_set_winograd.  The choice never looks at B, T or the lengths: a row's bits must not
     // depend on the batch it runs in.
     int winograd = 1;
     int wino_group = 0;                // debug (gvx_debug_set_winograd_group): tiles per Winograd group at most, 0 = as the scratch allows
-    int enc_fork_after = 1;            // GVX_ENC_FORK_AFTER=<n>: the caller's Prenet products start behind n encoder convolutions
+    int enc_fork_after = 2;            // GVX_ENC_FORK_AFTER=<n>: the caller's Prenet products start behind n encoder convolutions
     int pa_depth = 4;                  // GVX_PA_DEPTH=6: prefetch depth of the launch beside the resident kernel (tests, A/B runs)
     unsigned side_pool = 1;            // GVX_SIDE_POOL=2: this handle's resident kernels are dealt two side streams round-robin (ensure_side_stream)
     unsigned spin_limit = 0;           // GVX_HANDOFF_SPIN_LIMIT: polls before an in-launch wait gives up (0 = the built-in limit)
@@ -214,10 +219,11 @@ ArLoopPlan plan_autoregressive(const gvx_model* m, int B, int L, bool windowed =
 
 enum WsMode : int { WS_TEACHER_FORCED = 0, WS_AUTOREGRESSIVE = 1 };
 
-// ---- Winograd path of the Postnet (gvx_api.hip)
+// ---- Winograd path of the Postnet and the encoder (gvx_api.hip)
 constexpr int WINOGRAD_MIN_CHANNELS = 256;
 constexpr size_t WINOGRAD_GROUP_BYTES = (size_t)128 << 20;   // V + M of one group of tiles: half the 256 MiB Infinity Cache
 bool conv_uses_winograd(const gvx_model* m, int cin, int cout, int k);
+long winograd_group_tiles(long total, long fit, int C);   // tiles per group: where a layer of `total` tiles is cut when `fit` fit the scratch
 size_t winograd_scratch_floats(const gvx_model* m, int B, int T); // V + M of one group of tiles; 0: no layer of the model has the shape
 
 // status words at the front of every workspace (int32 indices into `flags`)

@@ -75,6 +75,7 @@ hipError_t launch_gemm(const GemmParams& p, hipStream_t s);
 // second launch.  err != hipSuccess: the shape is refused.
 struct GemmPlan { hipError_t err; int tile; int rows_big; };
 GemmPlan plan_gemm(const GemmParams& p);
+long gemm_round_rows(const GemmParams& p);   // rows of the fewest whole rounds of the plan's 128 x 128 tiles; 0: another plan
 void set_splitk(GemmParams& p, int splitk);   // launch_gemm_splitk's cut of K: fills p.kchunk and p.splitk (pieces <= splitk)
 // plain row-major C [M][N] (ldc) = A W^T (+ bias) with K split over `splitk` workgroups per tile; partials [splitk][M][N] in scratch
 hipError_t launch_gemm_splitk(const GemmParams& p, int splitk, float* scratch, hipStream_t s);
@@ -412,10 +413,11 @@ hipError_t launch_residual_to_channels_first(const float* mel, const float* y, f
 hipError_t launch_zero_halo(float* buf, int B, int T, int halo, int C, hipStream_t s);
 // k = 5 convolution as Winograd F(4,5) (winograd_conv.hip): the transforms on either side of the batched GEMM, for the tiles
 // [mt0, mt0 + nmt) of the batch (tile b * ceil(T / 4) + j = frames 4 j .. 4 j + 3 of sequence b).  x / y: the batch's halo
-// buffers [B][T + 4][C], V / M: [8][nmt][C]; C % 4 == 0.  The output transform adds the bias, applies tanh, zeroes frames at or
-// behind row_len[b] (may be nullptr) and writes y's halo rows.
+// buffers [B][T + 4][C], V / M: [8][nmt][C]; C % 4 == 0.  The output transform adds the bias, applies `act` and writes y's halo
+// rows.  act = ACT_TANH (Postnet): frames at or behind row_len[b] (may be nullptr) are zeros; act = ACT_RELU (encoder): row_len
+// must be nullptr, every frame is computed.
 hipError_t launch_winograd_input(const float* x, float* V, int B, long mt0, long nmt, int T, int C, hipStream_t s);
-hipError_t launch_winograd_output(const float* M, const float* bias, const int32_t* row_len, float* y, int B, long mt0, long nmt, int T, int C, hipStream_t s);
+hipError_t launch_winograd_output(const float* M, const float* bias, const int32_t* row_len, float* y, int B, long mt0, long nmt, int T, int C, int act, hipStream_t s);
 hipError_t launch_mask_padding(float* mel, float* mel_post, float* gate, const int32_t* mel_lengths, int B, int M, int T,
                                hipStream_t s);
 // if *tmo != 0 (a bounded in-launch wait of this call gave up): NaN over the n_arrays (<= 4) output arrays and *sticky = *tmo

@@ -41,6 +41,8 @@ Blob make_blob_layout(const gvx_dims& d) {
     // behind everything else (every older offset stays where it was): the Winograd transforms of the layers whose shape admits them
     for (int i = 0; i < d.postnet_n_conv; ++i)
         if (postnet_layer_winograd_shape(d, i)) b.post_u[i] = take((size_t)WINO_PTS * d.postnet_dim * d.postnet_dim);
+    for (int i = 0; i < d.enc_n_conv; ++i)
+        if (encoder_layer_winograd_shape(d, i)) b.enc_u[i] = take((size_t)WINO_PTS * E * E);
     b.total = off;
     return b;
 }
@@ -138,7 +140,8 @@ int gvx_model_pack_weights(gvx_model* m, const gvx_weight_desc* table, int n, vo
     std::memcpy(out + bl.emb, src, sizeof(float) * d.n_tokens * E);
 
     for (int i = 0; i < d.enc_n_conv; ++i) {
-        rc = pack_conv(wt, "encoder.convolutions." + std::to_string(i), E, E, d.enc_kernel, out + bl.enc_w[i], out + bl.enc_b[i]);
+        rc = pack_conv(wt, "encoder.convolutions." + std::to_string(i), E, E, d.enc_kernel, out + bl.enc_w[i], out + bl.enc_b[i],
+                       encoder_layer_winograd_shape(d, i) ? out + bl.enc_u[i] : nullptr);
         if (rc != GVX_OK) return rc;
     }
     {   // encoder BiLSTM: input projection rows [dir][4*j+gate], recurrent part in fragment order
@@ -322,7 +325,10 @@ int ensure_gather_map(gvx_model* m, const gvx_weight_desc* table, int n) {
     const Blob& b = m->blob;
     auto mark = [&](size_t o, size_t cnt) { std::fill(tid.begin() + o, tid.begin() + o + cnt, (uint8_t)255); };
     const int E = d.embed_dim, H = E / 2, M = d.n_mels;
-    for (int i = 0; i < d.enc_n_conv; ++i) { mark(b.enc_w[i], (size_t)E * d.enc_kernel * E); mark(b.enc_b[i], E); }
+    for (int i = 0; i < d.enc_n_conv; ++i) {
+        mark(b.enc_w[i], (size_t)E * d.enc_kernel * E); mark(b.enc_b[i], E);
+        if (encoder_layer_winograd_shape(d, i)) mark(b.enc_u[i], (size_t)WINO_PTS * E * E);
+    }
     for (int i = 0; i < d.postnet_n_conv; ++i) {
         const int cin = i == 0 ? M : d.postnet_dim, cout = i == d.postnet_n_conv - 1 ? M : d.postnet_dim;
         mark(b.post_w[i], (size_t)cout * d.postnet_kernel * cin); mark(b.post_b[i], cout);
@@ -378,7 +384,8 @@ int gvx_model_pack_weights_device(gvx_model* m, const gvx_weight_desc* table, in
         return GVX_OK;
     };
     for (int i = 0; i < d.enc_n_conv; ++i)
-        if ((rc = conv("encoder.convolutions." + std::to_string(i), E, E, d.enc_kernel, bl.enc_w[i], bl.enc_b[i])) != GVX_OK) return rc;
+        if ((rc = conv("encoder.convolutions." + std::to_string(i), E, E, d.enc_kernel, bl.enc_w[i], bl.enc_b[i],
+                       encoder_layer_winograd_shape(d, i) ? &bl.enc_u[i] : nullptr)) != GVX_OK) return rc;
     for (int i = 0; i < d.postnet_n_conv; ++i) {
         const int cin = i == 0 ? M : d.postnet_dim, cout = i == d.postnet_n_conv - 1 ? M : d.postnet_dim;
         if ((rc = conv("postnet.convolutions." + std::to_string(i), cout, cin, d.postnet_kernel, bl.post_w[i], bl.post_b[i],

@@ -5,7 +5,8 @@
 //   input   x[B][T + 4][C]  channels-last, two zero halo rows on either side of each sequence (what the direct form reads too)
 //   V[s][b * tiles + j][c] = sum_i BT[s][i] x[b][4 j + i][c]          tiles = ceil(T / 4), tile j = frames 4 j .. 4 j + 3
 //   M[s][m][n]             = sum_c V[s][m][c] U[s][n][c]              (the GEMM, K = C)
-//   y[b][4 j + i][n]       = tanh(bias[n] + sum_s AT[i][s] M[s][b * tiles + j][n]), zero at or behind row_len[b]
+//   y[b][4 j + i][n]       = act(bias[n] + sum_s AT[i][s] M[s][b * tiles + j][n])     Postnet: tanh, zero at or behind row_len[b];
+//                                                                                      encoder: ReLU, every position of the sequence
 //
 // Tiles start at frame 0 of each sequence, so a row's values do not depend on the batch it runs in, on T, or on how the batch's
 // tiles are cut into groups (a group is any range of tiles: the caller sizes it to the scratch it has); rows of x past the
@@ -53,7 +54,10 @@ __global__ void __launch_bounds__(256) winograd_input_kernel(const float* __rest
 }
 
 // y: the batch's next halo buffer (front halo of sequence 0), row_len: the batch's; the thread of a sequence's first / last tile
-// also writes the two front / back halo rows (zeros), so the buffer may hold anything before
+// also writes the two front / back halo rows (zeros), so the buffer may hold anything before.
+// ACT: the layer's activation.  ACT_TANH is the Postnet's form: frames at or behind row_len[b] are zeros.  ACT_RELU is the encoder's:
+// no row_len (its convolutions see the padding tokens' embeddings, as the reference's do), every frame of the sequence is computed.
+template <int ACT>
 __global__ void __launch_bounds__(256) winograd_output_kernel(const float* __restrict__ Mm, const float* __restrict__ bias, const int32_t* __restrict__ row_len,
                                                               float* __restrict__ y, long mt0, long nmt, int T, int C) {
     const int tiles = (T + WINO_OUT - 1) / WINO_OUT, c4n = C >> 2;
@@ -69,7 +73,7 @@ __global__ void __launch_bounds__(256) winograd_output_kernel(const float* __res
 #pragma unroll
     for (int s = 0; s < WINO_PTS; ++s) m[s] = *reinterpret_cast<const float4*>(src + s * slice);
     const float4 bv = *reinterpret_cast<const float4*>(bias + c);
-    const int len = row_len ? row_len[b] : T;
+    [[maybe_unused]] const int len = row_len ? row_len[b] : T;
     constexpr int HALO = (WINO_TAPS - 1) / 2;
     const int rows = T + 2 * HALO;
     float* dst = y + ((long)b * rows + HALO) * C + c;   // frame 0 of the sequence
@@ -81,8 +85,12 @@ __global__ void __launch_bounds__(256) winograd_output_kernel(const float* __res
 #pragma unroll
         for (int s = 0; s < WINO_PTS; ++s)
             if (wino_AT(i, s) != 0.f) v = f4_fma(wino_AT(i, s), m[s], v);
-        const bool live = t < len;   // (selected per component: a float4 select makes LLVM build a lookup table in scratch)
-        v = make_float4(live ? tanhf(v.x + bv.x) : 0.f, live ? tanhf(v.y + bv.y) : 0.f, live ? tanhf(v.z + bv.z) : 0.f, live ? tanhf(v.w + bv.w) : 0.f);
+        if constexpr (ACT == ACT_TANH) {
+            const bool live = t < len;   // (selected per component: a float4 select makes LLVM build a lookup table in scratch)
+            v = make_float4(live ? tanhf(v.x + bv.x) : 0.f, live ? tanhf(v.y + bv.y) : 0.f, live ? tanhf(v.z + bv.z) : 0.f, live ? tanhf(v.w + bv.w) : 0.f);
+        } else {
+            v = make_float4(fmaxf(v.x + bv.x, 0.f), fmaxf(v.y + bv.y, 0.f), fmaxf(v.z + bv.z, 0.f), fmaxf(v.w + bv.w, 0.f));
+        }
         if (t < T) *reinterpret_cast<float4*>(dst + (long)t * C) = v;
     }
     if (j == 0) {
@@ -110,9 +118,10 @@ hipError_t launch_winograd_input(const float* x, float* V, int B, long mt0, long
     return hipGetLastError();
 }
 
-hipError_t launch_winograd_output(const float* Mm, const float* bias, const int32_t* row_len, float* y, int B, long mt0, long nmt, int T, int C, hipStream_t s) {
-    if (bad_shape(B, mt0, nmt, T, C)) return hipErrorInvalidValue;
-    winograd_output_kernel<<<dim3(blocks_of(nmt, C)), dim3(256), 0, s>>>(Mm, bias, row_len, y, mt0, nmt, T, C);
+hipError_t launch_winograd_output(const float* Mm, const float* bias, const int32_t* row_len, float* y, int B, long mt0, long nmt, int T, int C, int act, hipStream_t s) {
+    if (bad_shape(B, mt0, nmt, T, C) || (act != ACT_TANH && (act != ACT_RELU || row_len))) return hipErrorInvalidValue;
+    if (act == ACT_TANH) winograd_output_kernel<ACT_TANH><<<dim3(blocks_of(nmt, C)), dim3(256), 0, s>>>(Mm, bias, row_len, y, mt0, nmt, T, C);
+    else winograd_output_kernel<ACT_RELU><<<dim3(blocks_of(nmt, C)), dim3(256), 0, s>>>(Mm, bias, nullptr, y, mt0, nmt, T, C);
     return hipGetLastError();
 }
 

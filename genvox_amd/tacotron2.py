@@ -359,7 +359,7 @@ class Tacotron2(nn.Module):
         _lib.check(_lib.load().gvx_kernel_timing_enable(self._handle, int(enable)))
 
     def set_winograd(self, mode: int) -> None:
-        """How the Postnet's square 5-tap convolutions run (gvx_model_set_winograd): 0 = direct implicit GEMM, 1 = Winograd F(4,5)
+        """How the Postnet's and the encoder's square 5-tap convolutions run (gvx_model_set_winograd): 0 = direct implicit GEMM, 1 = Winograd F(4,5)
         where the layer's shape was measured faster (default), 2 = wherever the form supports the shape.  Applies to every
         handle of this model, the chunk lanes' included."""
         self._ensure_handle()
@@ -369,7 +369,7 @@ class Tacotron2(nn.Module):
         self._winograd_mode = int(mode)
 
     def conv_plan(self, cin: int, cout: int, k: int) -> int:
-        """1 if a Postnet convolution of this shape runs as Winograd F(4,5) on this model, 0 if direct (gvx_debug_conv_plan)."""
+        """1 if a Postnet or encoder convolution of this shape runs as Winograd F(4,5) on this model, 0 if direct (gvx_debug_conv_plan)."""
         return int(_lib.load().gvx_debug_conv_plan(self._ensure_handle(), cin, cout, k))
 
     def loop_kind(self, B: int, L: int) -> int:

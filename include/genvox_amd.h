@@ -157,16 +157,17 @@ int gvx_model_set_persistent_attention(gvx_model* model, int enable);
  * enable = 1 restores the defaults (environment knobs are not re-read). */
 int gvx_model_set_resident_kernels(gvx_model* model, int enable);
 
-/* Postnet convolutions with as many input as output channels and 5 taps (layers 2-4 of the default model) may run as
- * Winograd F(4,5) along time: 8 instead of 20 fp32 products per 4 output frames, against weights transformed when they are
- * packed.  mode 0 = never (every layer the direct implicit GEMM), 1 = by the layer's shape (default: 256 channels and more),
- * 2 = every layer whose shape the form supports (channels a multiple of 32).  The choice depends on (cin, cout, k) alone, never
- * on B, T or the lengths, so a row's result does not depend on the batch it runs in.  Results differ from the direct form by
- * fp32 rounding only (a few 1e-6 at the Postnet's output scale).  The environment variable GVX_CONV_WINOGRAD sets the mode a
- * handle starts with.  Workspace sizes do not depend on the mode. */
+/* Postnet and encoder convolutions with as many input as output channels and 5 taps (Postnet layers 2-4 and the three encoder
+ * layers of the default model) may run as Winograd F(4,5) along time: 8 instead of 20 fp32 products per 4 output frames, against
+ * weights transformed when they are packed.  mode 0 = never (every layer the direct implicit GEMM), 1 = by the layer's shape
+ * (default: 256 channels and more), 2 = every layer whose shape the form supports (channels a multiple of 32).  The choice
+ * depends on (cin, cout, k) alone, never on B, L, T or the lengths, so a row's result does not depend on the batch it runs in.
+ * Results differ from the direct form by fp32 rounding only (a few 1e-6 at the layers' output scale).  The environment variable
+ * GVX_CONV_WINOGRAD sets the mode a handle starts with.  Workspace sizes do not depend on the mode.  The training forward's
+ * convolutions (batch statistics) are not affected. */
 int gvx_model_set_winograd(gvx_model* model, int mode);
-/* 1 if a Postnet convolution of this shape runs as Winograd F(4,5) on this handle, 0 if as the direct implicit GEMM, -1 for
- * a null handle or a non-positive size.  Host arithmetic: the question the Postnet itself asks. */
+/* 1 if a Postnet or encoder convolution of this shape runs as Winograd F(4,5) on this handle, 0 if as the direct implicit GEMM,
+ * -1 for a null handle or a non-positive size.  Host arithmetic: the question the Postnet and the encoder themselves ask. */
 int gvx_debug_conv_plan(const gvx_model* model, int cin, int cout, int k);
 
 /* Batch rows gvx_tacotron2_forward / gvx_decoder_teacher_forced serve best per call for rows of L tokens: 64 where the 64-row
@@ -327,7 +328,9 @@ int gvx_decoder_teacher_forced_train(gvx_model* model, const float* memory, cons
                                      float* dec_preact_all, void* workspace, size_t workspace_bytes, void* stream);
 /* Copy one of the decoder's per-call buffers out of the workspace of the last gvx_decoder_teacher_forced(_train) call with the
  * same (B, L, T), row-major: what 0 = decoder input frames [(T+1) B, n_mels] (row t B + b; frame 0 = zeros), 1 = Prenet layer-1
- * output [(T+1) B, prenet_dim], 2 = Prenet output [(T+1) B, prenet_dim], 3 = processed memory [B, L, att_dim]. */
+ * output [(T+1) B, prenet_dim], 2 = Prenet output [(T+1) B, prenet_dim], 3 = processed memory [B, L, att_dim];
+ * 4 = the encoder output [B, L, embed_dim] of the last gvx_tacotron2_forward of that shape (a Postnet of many frames takes the
+ * region as scratch: read it behind a call with mel_post_out = NULL). */
 int gvx_train_export(const gvx_model* model, const void* workspace, size_t workspace_bytes, int B, int L, int T, int what, float* dst, void* stream);
 /* `saved` and the workspace of the two calls below: no clearing, any contents (Conventions, "Workspaces and scratch"); the backward
  * reads of `saved` only what the forward of the same shape wrote there. */
