@@ -7,6 +7,7 @@
     from genvox_amd import MelGANDiscriminator, MelGANDiscriminatorConfig, MelGANTrainer   # the other side of the vocoder's GAN step
     from genvox_amd import HiFiGANPeriodDiscriminator, HiFiGANPeriodDiscriminatorConfig, HiFiGANTrainer, HiFiGANTrainingConfig   # HiFi-GAN's GAN step
     from genvox_amd import MultiResolutionSTFTLoss, stft_distance   # vocoder training loss / waveform distance on the device
+    from genvox_amd import MelSpectrogramLoss, mel_distance         # HiFi-GAN's mel-spectrogram L1 term / log-mel distance
 """
 from .configs import HiFiGANPeriodDiscriminatorConfig, HiFiGANTrainingConfig  # noqa: F401
 from .configs import AudioConfig, BaseConfig, HiFiGANConfig, MelGANConfig, MelGANDiscriminatorConfig, Tacotron2Config, TextConfig  # noqa: F401
@@ -43,6 +44,12 @@ def __getattr__(name):  # torch-dependent classes are imported lazily
     if name == "MultiResolutionSTFTLoss":
         from .losses import MultiResolutionSTFTLoss
         return MultiResolutionSTFTLoss
+    if name == "MelSpectrogramLoss":
+        from .losses import MelSpectrogramLoss
+        return MelSpectrogramLoss
+    if name == "mel_distance":
+        from .metrics import mel_distance
+        return mel_distance
     if name == "stft_distance":
         from .metrics import stft_distance
         return stft_distance

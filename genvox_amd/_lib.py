@@ -74,6 +74,10 @@ class gvx_stft_loss_debug(C.Structure):
     _fields_ = [("mag_pred", C.c_void_p * 8), ("mag_target", C.c_void_p * 8)]
 
 
+class gvx_mel_loss_debug(C.Structure):
+    _fields_ = [("log_mel_pred", C.c_void_p), ("log_mel_target", C.c_void_p)]
+
+
 class gvx_pitch_params(C.Structure):
     _fields_ = [("sampling_rate", C.c_int32), ("hop", C.c_int32), ("window", C.c_int32), ("lag_min", C.c_int32), ("lag_max", C.c_int32),
                 ("threshold", C.c_float), ("first_centre", C.c_int32)]
@@ -246,6 +250,11 @@ SIGNATURES = {
     "gvx_stft_loss_destroy": (None, [_vp]),
     "gvx_stft_loss_workspace_bytes": (_sz, [_vp, _i, _l]),
     "gvx_stft_loss": (_i, [_vp, _vp, _vp, _vp, _i, _l, _vp, _vp, _vp, C.POINTER(gvx_stft_loss_debug), _vp, _sz, _vp]),
+    "gvx_mel_loss_create": (_i, [_i, _i, _i, _i, _vp, _f, _f, C.POINTER(_vp)]),
+    "gvx_mel_loss_destroy": (None, [_vp]),
+    "gvx_mel_loss_bands": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "gvx_mel_loss_workspace_bytes": (_sz, [_vp, _i, _l]),
+    "gvx_mel_loss": (_i, [_vp, _vp, _vp, _vp, _i, _l, _vp, _vp, _vp, C.POINTER(gvx_mel_loss_debug), _vp, _sz, _vp]),
     "gvx_kernel_timing_enable": (_i, [_vp, _i]),
     "gvx_model_set_persistent_attention": (_i, [_vp, _i]),
     "gvx_model_set_resident_kernels": (_i, [_vp, _i]),

@@ -1,14 +1,15 @@
 """One GAN step of HiFi-GAN: the generator against the multi-period discriminator - and, optionally, further discriminators - all on
 the device's own kernels.
 
-    trainer = HiFiGANTrainer(generator, [HiFiGANPeriodDiscriminator(), MelGANDiscriminator()], aux_loss=MultiResolutionSTFTLoss())
+    trainer = HiFiGANTrainer(generator, [HiFiGANPeriodDiscriminator(), MelGANDiscriminator()], aux_loss=MelSpectrogramLoss())
     terms = trainer.train_step(mel, wav, mel_lengths)     # {"d_loss": ..., "g_adv": ..., "g_feat_match": ..., "g_aux": ..., "g_loss": ...}
     trainer.end_epoch()                                   # both learning rates times lr_decay
 
 It is a step, not a loop: data loading, checkpoint rotation and logging belong to the caller.  A discriminator is any module that
-offers ``forward(wav, sample_lengths)`` -> [sub-discriminator][map] and ``map_lengths(sample_lengths)``.  HiFi-GAN's own scale
-discriminator and its mel-spectrogram L1 term are not built; ``MelGANDiscriminator`` serves as the scale-side adversary and
-``MultiResolutionSTFTLoss`` as the spectral term (``aux_loss(fake, wav, sample_lengths)``, weighted ``aux_weight``) until they are."""
+offers ``forward(wav, sample_lengths)`` -> [sub-discriminator][map] and ``map_lengths(sample_lengths)``.  The spectral term is
+``aux_loss(fake, wav, sample_lengths)``, weighted ``aux_weight``: with ``losses.MelSpectrogramLoss()`` - HiFi-GAN's mel-spectrogram L1
+term - the default ``aux_weight`` of 45 carries its published meaning (``MultiResolutionSTFTLoss`` fits the same slot, on another scale).
+HiFi-GAN's own scale discriminator is not built; ``MelGANDiscriminator`` serves as the scale-side adversary until it is."""
 from __future__ import annotations
 
 from typing import Dict, Optional, Sequence

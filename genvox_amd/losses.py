@@ -9,12 +9,18 @@ tests/stft_loss_ref64.py) that returns the value and, when pred asks for it, the
     loss.backward()
 
 The norms and means are per row (a row's numbers never depend on the rows beside it), not over the batch as Parallel WaveGAN has them.
+
+MelSpectrogramLoss is HiFi-GAN's spectral term - the L1 distance between the log-mel spectrograms of the two waveforms, the published
+mel_spectrogram + F.l1_loss - as one call of gvx_mel_loss (restatement in tests/mel_loss_ref64.py), with the same per-row mean:
+
+    trainer = HiFiGANTrainer(generator, discriminators, aux_loss=MelSpectrogramLoss())   # aux_weight = 45 is this term's published weight
 """
 from __future__ import annotations
 
 import ctypes as C
 from typing import Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -44,31 +50,26 @@ class _STFTLossFunction(torch.autograd.Function):
     def forward(ctx, pred, target, lens_dev, module, want_grad):
         loss, parts, d_pred = module._call(pred, target, lens_dev, want_grad)
         module.last_parts = parts
-        ctx.d_pred = d_pred
+        ctx.d_pred, ctx.name = d_pred, type(module).__name__
         return loss
 
     @staticmethod
     def backward(ctx, grad_output):
         if ctx.d_pred is None:
-            raise RuntimeError("MultiResolutionSTFTLoss: no gradient was kept for this call")
+            raise RuntimeError(f"{ctx.name}: no gradient was kept for this call")
         return grad_output * ctx.d_pred, None, None, None, None
 
 
-class MultiResolutionSTFTLoss(torch.nn.Module):
-    """loss = mean over rows and resolutions of (w_sc * spectral convergence + w_mag * log-magnitude L1).  No parameters.
+class _WaveformLoss(torch.nn.Module):
+    """What the two waveform losses share: the plan's ownership, the checks before anything is launched, and forward through
+    _STFTLossFunction.  A subclass sets ``min_samples`` and ``_min_rule`` (how that number comes about, for the message), names the
+    C ABI's destroy function in ``_destroy`` and gives ``_call(pred, target, lens_dev, want_grad) -> (loss, parts, d_pred)``."""
 
-    forward(pred, target, sample_lengths=None): float32 [B, n_max] device tensors; returns a 0-d float32 device tensor.  `last_parts`
-    holds [B, R, 2] = (spectral convergence, log magnitude) of the last call.  target gets no gradient."""
+    _destroy = ""
+    _min_rule = ""
 
-    def __init__(self, resolutions: Sequence[Sequence[int]] = DEFAULT_RESOLUTIONS, w_sc: float = 1.0, w_mag: float = 1.0, eps: float = 1e-7):
+    def __init__(self):
         super().__init__()
-        self.resolutions = check_resolutions(resolutions)
-        if not (w_sc >= 0.0 and w_mag >= 0.0) or w_sc == float("inf") or w_mag == float("inf"):
-            raise ValueError("w_sc and w_mag must be finite and >= 0")
-        if not 0.0 < eps < float("inf"):
-            raise ValueError("eps must be finite and > 0")
-        self.w_sc, self.w_mag, self.eps = float(w_sc), float(w_mag), float(eps)
-        self.min_samples = max(r[0] for r in self.resolutions) // 2 + 1
         self.last_parts: Optional[torch.Tensor] = None
         self._handle = None
         self._workspace: Optional[torch.Tensor] = None
@@ -76,7 +77,7 @@ class MultiResolutionSTFTLoss(torch.nn.Module):
     def __del__(self):
         try:
             if self._handle is not None:
-                _lib.load().gvx_stft_loss_destroy(self._handle)
+                getattr(_lib.load(), self._destroy)(self._handle)
         except Exception:
             pass
 
@@ -88,7 +89,7 @@ class MultiResolutionSTFTLoss(torch.nn.Module):
     # ---- checks, all before anything is launched
     def _require_gpu(self, pred: torch.Tensor) -> torch.device:
         if pred.device.type != "cuda":
-            raise RuntimeError("genvox_amd.MultiResolutionSTFTLoss runs on an MI355X only: pass tensors on 'cuda:0'. There is no CPU fallback.")
+            raise RuntimeError(f"genvox_amd.{type(self).__name__} runs on an MI355X only: pass tensors on 'cuda:0'. There is no CPU fallback.")
         return pred.device
 
     def _check(self, pred, target, sample_lengths):
@@ -100,7 +101,7 @@ class MultiResolutionSTFTLoss(torch.nn.Module):
             raise ValueError(f"pred and target must be float32, got {pred.dtype} and {target.dtype}")
         B, n_max = pred.shape
         if B < 1 or n_max < self.min_samples:
-            raise ValueError(f"a row needs at least n_fft / 2 + 1 = {self.min_samples} samples for the reflection, got [B, n_max] = [{B}, {n_max}]")
+            raise ValueError(f"a row needs at least {self._min_rule.format(self.min_samples)}, got [B, n_max] = [{B}, {n_max}]")
         host = None
         on_device = isinstance(sample_lengths, torch.Tensor) and sample_lengths.device.type == "cuda"
         if sample_lengths is not None and not on_device:   # lengths the host has: refused here, with the row named
@@ -120,6 +121,31 @@ class MultiResolutionSTFTLoss(torch.nn.Module):
         if host is not None:
             return dev, torch.tensor(host, dtype=torch.int32, device=dev)
         return dev, sample_lengths.to(device=dev, dtype=torch.int32).contiguous()   # checked by the call itself (GvxError naming the row)
+
+    def forward(self, pred: torch.Tensor, target: torch.Tensor, sample_lengths=None) -> torch.Tensor:
+        _, lens_dev = self._check(pred, target, sample_lengths)
+        want_grad = pred.requires_grad and torch.is_grad_enabled()
+        return _STFTLossFunction.apply(pred, target, lens_dev, self, want_grad)
+
+
+class MultiResolutionSTFTLoss(_WaveformLoss):
+    """loss = mean over rows and resolutions of (w_sc * spectral convergence + w_mag * log-magnitude L1).  No parameters.
+
+    forward(pred, target, sample_lengths=None): float32 [B, n_max] device tensors; returns a 0-d float32 device tensor.  `last_parts`
+    holds [B, R, 2] = (spectral convergence, log magnitude) of the last call.  target gets no gradient."""
+
+    _destroy = "gvx_stft_loss_destroy"
+    _min_rule = "n_fft / 2 + 1 = {} samples for the reflection"
+
+    def __init__(self, resolutions: Sequence[Sequence[int]] = DEFAULT_RESOLUTIONS, w_sc: float = 1.0, w_mag: float = 1.0, eps: float = 1e-7):
+        super().__init__()
+        self.resolutions = check_resolutions(resolutions)
+        if not (w_sc >= 0.0 and w_mag >= 0.0) or w_sc == float("inf") or w_mag == float("inf"):
+            raise ValueError("w_sc and w_mag must be finite and >= 0")
+        if not 0.0 < eps < float("inf"):
+            raise ValueError("eps must be finite and > 0")
+        self.w_sc, self.w_mag, self.eps = float(w_sc), float(w_mag), float(eps)
+        self.min_samples = max(r[0] for r in self.resolutions) // 2 + 1
 
     # ---- the call
     def _plan(self):
@@ -150,10 +176,80 @@ class MultiResolutionSTFTLoss(torch.nn.Module):
                                          self._workspace.data_ptr(), self._workspace.numel(), torch.cuda.current_stream(dev).cuda_stream))
         return loss, parts, d_pred
 
-    def forward(self, pred: torch.Tensor, target: torch.Tensor, sample_lengths=None) -> torch.Tensor:
-        _, lens_dev = self._check(pred, target, sample_lengths)
-        want_grad = pred.requires_grad and torch.is_grad_enabled()
-        return _STFTLossFunction.apply(pred, target, lens_dev, self, want_grad)
+
+MAX_MELS = 128   # GVX_MEL_LOSS_MAX_MELS
+
+
+class MelSpectrogramLoss(_WaveformLoss):
+    """loss = mean over rows of the row's mean |log mel(target) - log mel(pred)| over its own n_b // hop_length frames and n_mels bands:
+    HiFi-GAN's mel_spectrogram (reflect padding by (n_fft - hop_length) / 2, center=False, sqrt(re^2 + im^2 + mag_eps), the mel basis,
+    log(max(., clamp))) and F.l1_loss, per row.  No parameters.  Without ``mel_basis`` ([n_mels, n_fft / 2 + 1]) the basis is
+    audio.get_mel_filter's Slaney filterbank from ``fmin`` to ``fmax`` (None: Nyquist, the published ``fmax_for_loss: null``).
+
+    forward(pred, target, sample_lengths=None): float32 [B, n_max] device tensors; returns a 0-d float32 device tensor.  `last_parts`
+    holds [B], the rows' means of the last call.  target gets no gradient."""
+
+    _destroy = "gvx_mel_loss_destroy"
+    _min_rule = "max(hop_length, (n_fft - hop_length) / 2 + 1) = {} samples"
+
+    def __init__(self, sampling_rate: int = 22050, n_fft: int = 1024, hop_length: int = 256, win_length: int = 1024, n_mels: int = 80,
+                 fmin: float = 0.0, fmax: Optional[float] = None, clamp: float = 1e-5, mag_eps: float = 1e-9, mel_basis=None):
+        super().__init__()
+        n_fft, hop_length, win_length, n_mels = int(n_fft), int(hop_length), int(win_length), int(n_mels)
+        if n_fft not in SUPPORTED_N_FFT:
+            raise ValueError(f"n_fft = {n_fft}: supported are {SUPPORTED_N_FFT}")
+        if not 1 <= hop_length <= n_fft or (n_fft - hop_length) % 2:
+            raise ValueError(f"hop_length = {hop_length}: 1 <= hop_length <= n_fft = {n_fft} with n_fft - hop_length even is required")
+        if not 2 <= win_length <= n_fft:
+            raise ValueError(f"win_length = {win_length}: 2 <= win_length <= n_fft = {n_fft} is required")
+        if not 1 <= n_mels <= MAX_MELS:
+            raise ValueError(f"n_mels = {n_mels}: 1 .. {MAX_MELS} are supported")
+        if not 0.0 < clamp < float("inf") or not 0.0 < mag_eps < float("inf"):
+            raise ValueError("clamp and mag_eps must be finite and > 0")
+        if mel_basis is None:
+            from .audio import get_mel_filter
+            top = sampling_rate / 2.0 if fmax is None else float(fmax)
+            if not 0.0 <= fmin < top <= sampling_rate / 2.0:
+                raise ValueError(f"0 <= fmin < fmax <= sampling_rate / 2 is required, got fmin = {fmin}, fmax = {top}")
+            basis = get_mel_filter(int(sampling_rate), n_fft, n_mels, float(fmin), top)
+        else:
+            basis = mel_basis.detach().cpu().numpy() if isinstance(mel_basis, torch.Tensor) else np.asarray(mel_basis)
+        basis = np.ascontiguousarray(basis, dtype=np.float32)
+        if basis.shape != (n_mels, n_fft // 2 + 1) or not np.isfinite(basis).all():
+            raise ValueError(f"mel_basis must be a finite [n_mels, n_fft / 2 + 1] = [{n_mels}, {n_fft // 2 + 1}] matrix, got {basis.shape}")
+        self.sampling_rate, self.n_fft, self.hop_length, self.win_length, self.n_mels = int(sampling_rate), n_fft, hop_length, win_length, n_mels
+        self.clamp, self.mag_eps = float(clamp), float(mag_eps)
+        self.mel_basis = basis
+        self.pad = (n_fft - hop_length) // 2
+        self.min_samples = max(hop_length, self.pad + 1)
+
+    def _plan(self):
+        if self._handle is None:
+            h = C.c_void_p()
+            _lib.check(_lib.load().gvx_mel_loss_create(self.n_fft, self.hop_length, self.win_length, self.n_mels, self.mel_basis.ctypes.data,
+                                                       self.clamp, self.mag_eps, C.byref(h)))
+            self._handle = h.value
+        return self._handle
+
+    def _call(self, pred, target, lens_dev, want_grad):
+        lib = _lib.load()
+        dev = pred.device
+        B, n_max = pred.shape
+        with torch.cuda.device(dev):
+            plan = self._plan()
+            need = lib.gvx_mel_loss_workspace_bytes(plan, B, n_max)
+            if need == 0:
+                _lib.check(-1)
+            if self._workspace is None or self._workspace.device != dev or self._workspace.numel() < need:
+                self._workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+            pred, target = pred.detach().contiguous(), target.detach().contiguous()
+            loss = torch.empty((), dtype=torch.float32, device=dev)
+            parts = torch.empty(B, dtype=torch.float32, device=dev)
+            d_pred = torch.empty_like(pred) if want_grad else None
+            _lib.check(lib.gvx_mel_loss(plan, pred.data_ptr(), target.data_ptr(), None if lens_dev is None else lens_dev.data_ptr(), B, n_max,
+                                        loss.data_ptr(), parts.data_ptr(), None if d_pred is None else d_pred.data_ptr(), None,
+                                        self._workspace.data_ptr(), self._workspace.numel(), torch.cuda.current_stream(dev).cuda_stream))
+        return loss, parts, d_pred
 
 
 # ---- the adversarial losses of the MelGAN step: small elementwise reductions over the discriminator's maps, in plain torch

@@ -455,3 +455,23 @@ def stft_distance(wav_a: torch.Tensor, wav_b: torch.Tensor, sample_lengths=None,
         crit(wav_a, wav_b, sample_lengths)
     parts = crit.last_parts.mean(dim=1)
     return {"spectral_convergence": parts[:, 0], "log_magnitude": parts[:, 1]}
+
+
+_mel_criteria: Dict[tuple, "torch.nn.Module"] = {}
+
+
+def mel_distance(wav_a: torch.Tensor, wav_b: torch.Tensor, sample_lengths=None, **mel_args) -> torch.Tensor:
+    """Log-mel L1 distance of wav_a [B, n_max] from the reference wav_b, per row at its own length: [B], the parts of
+    losses.MelSpectrogramLoss(**mel_args) (default: HiFi-GAN's 22.05 kHz, 1024 / 256 / 1024, 80 mels up to Nyquist).  Forward only."""
+    from .losses import MelSpectrogramLoss
+
+    basis = mel_args.get("mel_basis")
+    key = None if basis is not None else tuple(sorted(mel_args.items()))
+    crit = _mel_criteria.get(key) if key is not None else None
+    if crit is None:
+        crit = MelSpectrogramLoss(**mel_args)
+        if key is not None:
+            _mel_criteria[key] = crit
+    with torch.no_grad():
+        crit(wav_a, wav_b, sample_lengths)
+    return crit.last_parts

@@ -1474,6 +1474,77 @@ int gvx_stft_loss(gvx_stft_loss_plan* plan, const float* pred, const float* targ
                   float* loss_out, float* parts_out, float* d_pred, const gvx_stft_loss_debug* dbg, void* workspace, size_t workspace_bytes,
                   void* stream);
 
+/* ---- Mel-spectrogram L1 loss: the spectral term of HiFi-GAN's generator objective (Kong et al. 2020) - the L1 distance between the
+ * log-mel spectrograms of the generated waveform and of the recording, the published mel_spectrogram + F.l1_loss - made ragged the
+ * way gvx_stft_loss is, value and gradient in one call.
+ *
+ * Inputs.  pred, target: fp32 [B][n_max].  sample_lengths: int32 [B] on the device or NULL; row b has n_b = sample_lengths[b] samples
+ * (n_max without it).  Plan: n_fft in {512, 1024, 2048}; 1 <= hop <= n_fft with n_fft - hop even; 2 <= win_length <= n_fft;
+ * 1 <= n_mels <= GVX_MEL_LOSS_MAX_MELS; mel_basis, a host float matrix [n_mels][n_fft / 2 + 1] - any finite matrix, zero rows and zero
+ * columns included; clamp (1e-5 as published) and mag_eps (1e-9 as published), both finite and > 0.
+ *
+ * Per row b - torch.stft with center=False on the row cut at its own length and reflect-padded by pad = (n_fft - hop) / 2 on both sides:
+ *   - F = n_b / hop frames (integer division); frame t holds the padded positions p = t * hop + k, k in [0, n_fft);
+ *   - the source index of p is i = p - pad; for i < 0 it is -i, for i >= n_b it is 2 (n_b - 1) - i.  So a row needs
+ *     n_b >= max(hop, pad + 1);
+ *   - the window is the periodic Hann 0.5 - 0.5 cos(2 pi k / win_length), centred in the frame at offset (n_fft - win_length) / 2 and
+ *     zero outside, computed in double on the host (the window of gvx_stft_loss);
+ *   - bins k = 0 .. n_fft / 2; S_k = sqrt(re^2 + im^2 + mag_eps): an added epsilon, not a clamp;
+ *   - m_j = sum_k mel_basis[j][k] S_k;  l_j = log(max(m_j, clamp)), the natural logarithm;
+ *   - part[b] = the mean of |l_t - l_p| over the row's own F n_mels cells;
+ *   loss = (1 / B) sum_b part[b].
+ * The mean is PER ROW, not over the batch, for the reason given under gvx_stft_loss: a row's part is the bits of that row run alone,
+ * and its gradient the bits of that row in any batch of the same B, whatever the other rows and n_max are.
+ *
+ * Gradient with respect to pred (target gets none), for d loss = 1.  d|u| at u == 0 is 0; the clamp passes gradient where
+ * m >= clamp and none below it (torch.clamp); dS_k = sum_j mel_basis[j][k] dm_j; dX_k = dS_k X_k / S_k (S > 0 always); then the
+ * adjoint of the real transform and the window.  d_pred is exact zeros at and behind n_b and on samples no frame reaches (with
+ * hop > pad the tail behind F hop + pad is never read), and whatever lies at and behind n_b in pred or target is never read.  So
+ * pred == target gives loss 0 and an all-zero gradient, and an all-zero pred - every mel of such a row lies under the clamp - a finite
+ * loss and an all-zero gradient.
+ *
+ * gvx_mel_loss_create is host work alone (the first call of a plan moves its tables to the device; calls on one plan are not
+ * concurrent): it makes the window and twiddle tables in double and derives the bands of the matrix: per mel the first
+ * and last bin with a non-zero entry, per bin the first and last mel (a row with scattered non-zeros has the band min .. max; an
+ * all-zero row or column has none).  The kernels run both products off the bands.  gvx_mel_loss_bands is that derivation by
+ * itself, host arithmetic that needs no device: from a matrix [n_mels][bins] it fills mel_lo / mel_hi [n_mels] and bin_lo / bin_hi
+ * [bins] on the host; hi is inclusive and an empty band has lo = 0, hi = -1.  An n_fft outside the three sizes is GVX_ERR_UNSUPPORTED, any other value out of range
+ * GVX_ERR_INVALID_ARG.  gvx_mel_loss_workspace_bytes is host arithmetic (0 for a NULL plan, B outside [1, GVX_MEL_LOSS_MAX_ROWS] or
+ * n_max outside [1, GVX_MEL_LOSS_MAX_SAMPLES]); the workspace follows the conventions above: any contents, 256-byte aligned, exactly
+ * that size, nothing cleared.  It holds the frame gradients and the partial sums - linear in B and in the frames of a row of n_max.
+ *
+ * The call: loss_out [1]; parts_out [B], may be NULL; d_pred [B][n_max], or NULL for the value alone (same loss bits); dbg NULL, or
+ * for tests two device pointers that receive l_p and l_t as [B][n_max / hop][n_mels], NaN behind a row's frames (either may be
+ * NULL).  Refusals are those of gvx_stft_loss: NULL arguments and bad B or n_max (GVX_ERR_INVALID_ARG), n_max below
+ * max(hop, pad + 1) (GVX_ERR_SHAPE), a NULL, short or misaligned workspace (GVX_ERR_WORKSPACE), all before anything is launched; with
+ * sample_lengths a row with n_b outside [max(hop, pad + 1), n_max] has no frames for the kernels - its part and the loss are NaN - and
+ * the call reads the lengths back behind its launches, zeroes all of d_pred and returns GVX_ERR_SHAPE naming the first such row.
+ *
+ * Kernels (fp32 but the last sums).  One launch does everything of a frame, a frame per wave and GVX_MEL_LOSS_FRAMES_PER_WORKGROUP
+ * frames per workgroup: target's transform (samples gathered through the reflection, a complex transform of n_fft / 2 points in LDS,
+ * the even/odd split), its magnitudes staged in LDS, the banded mel product and the logarithm; the same for pred with its spectrum
+ * kept in registers; the cell's |l_t - l_p|; and, with d_pred, dm from the lengths alone (the coefficient 1 / (B F n_mels) needs no
+ * batch sum), the banded transposed product, dX, the adjoint transform and the window - no spectrum goes through the workspace.
+ * One launch gathers, a thread per sample and GVX_MEL_LOSS_GATHER_SAMPLES per workgroup, the frames that cover the sample and its
+ * two reflected images (p = i + pad; pad - i for 1 <= i <= pad; 2 (n_b - 1) - i + pad for n_b - 1 - pad <= i <= n_b - 2) in
+ * ascending frame order.  One small launch adds the workgroups' partial sums per row and the rows, in a fixed order in float64.
+ * No atomics: two calls give the same bits. */
+enum { GVX_MEL_LOSS_FRAMES_PER_WORKGROUP = 4, GVX_MEL_LOSS_GATHER_SAMPLES = 256, GVX_MEL_LOSS_MAX_MELS = 128,
+       GVX_MEL_LOSS_MAX_ROWS = 65535, GVX_MEL_LOSS_MAX_SAMPLES = 1 << 30 };
+typedef struct gvx_mel_loss_debug {
+    float* log_mel_pred;
+    float* log_mel_target;
+} gvx_mel_loss_debug;
+typedef struct gvx_mel_loss_plan gvx_mel_loss_plan;   /* (the bare name is the call's) */
+int gvx_mel_loss_create(int n_fft, int hop, int win_length, int n_mels, const float* mel_basis, float clamp, float mag_eps,
+                        gvx_mel_loss_plan** out);
+void gvx_mel_loss_destroy(gvx_mel_loss_plan* plan);
+int gvx_mel_loss_bands(const float* mel_basis, int n_mels, int bins, int32_t* mel_lo, int32_t* mel_hi, int32_t* bin_lo, int32_t* bin_hi);
+size_t gvx_mel_loss_workspace_bytes(const gvx_mel_loss_plan* plan, int B, long n_max);
+int gvx_mel_loss(gvx_mel_loss_plan* plan, const float* pred, const float* target, const int32_t* sample_lengths, int B, long n_max,
+                 float* loss_out, float* parts_out, float* d_pred, const gvx_mel_loss_debug* dbg, void* workspace, size_t workspace_bytes,
+                 void* stream);
+
 /* ---- Per-kernel timing of the decoder step (measurement only): when enabled, a teacher-forced call replays the
  * mid-sequence LSTM-step launch and the attention launches 64 times each, back to back, between HIP events on
  * `stream` (after its loop; the call's outputs are not valid afterwards); gvx_kernel_times_ms synchronises and
