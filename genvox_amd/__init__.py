@@ -6,10 +6,11 @@
     from genvox_amd import Tacotron2GuidedLoss    # training criterion: Tacotron2Loss + alpha x guided attention loss
     from genvox_amd import MelGANDiscriminator, MelGANDiscriminatorConfig, MelGANTrainer   # the other side of the vocoder's GAN step
     from genvox_amd import HiFiGANPeriodDiscriminator, HiFiGANPeriodDiscriminatorConfig, HiFiGANTrainer, HiFiGANTrainingConfig   # HiFi-GAN's GAN step
+    from genvox_amd import HiFiGANScaleDiscriminator, HiFiGANScaleDiscriminatorConfig   # ... and its multi-scale discriminator
     from genvox_amd import MultiResolutionSTFTLoss, stft_distance   # vocoder training loss / waveform distance on the device
     from genvox_amd import MelSpectrogramLoss, mel_distance         # HiFi-GAN's mel-spectrogram L1 term / log-mel distance
 """
-from .configs import HiFiGANPeriodDiscriminatorConfig, HiFiGANTrainingConfig  # noqa: F401
+from .configs import HiFiGANPeriodDiscriminatorConfig, HiFiGANScaleDiscriminatorConfig, HiFiGANTrainingConfig  # noqa: F401
 from .configs import AudioConfig, BaseConfig, HiFiGANConfig, MelGANConfig, MelGANDiscriminatorConfig, Tacotron2Config, TextConfig  # noqa: F401
 
 
@@ -35,6 +36,9 @@ def __getattr__(name):  # torch-dependent classes are imported lazily
     if name == "HiFiGANPeriodDiscriminator":
         from .hifigan_disc import HiFiGANPeriodDiscriminator
         return HiFiGANPeriodDiscriminator
+    if name == "HiFiGANScaleDiscriminator":
+        from .hifigan_msd import HiFiGANScaleDiscriminator
+        return HiFiGANScaleDiscriminator
     if name == "HiFiGANTrainer":
         from .hifigan_training import HiFiGANTrainer
         return HiFiGANTrainer

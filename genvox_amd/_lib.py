@@ -61,6 +61,16 @@ class gvx_hifigan_mpd_dims(C.Structure):
                 ("kernel_size", C.c_int32), ("stride", C.c_int32), ("slope", C.c_float)]
 
 
+class gvx_hifigan_msd_dims(C.Structure):
+    _fields_ = [("n_scales", C.c_int32), ("n_layers", C.c_int32), ("channels", C.c_int32 * 8), ("kernel_sizes", C.c_int32 * 8),
+                ("strides", C.c_int32 * 8), ("groups", C.c_int32 * 8), ("slope", C.c_float)]
+
+
+class gvx_hifigan_msd_entry(C.Structure):
+    _fields_ = [("byte_offset", C.c_uint64), ("channels", C.c_int32), ("length", C.c_int32),
+                ("stride_b", C.c_int64), ("stride_c", C.c_int64), ("stride_l", C.c_int64)]
+
+
 class gvx_hifigan_mpd_entry(C.Structure):
     _fields_ = [("byte_offset", C.c_uint64), ("channels", C.c_int32), ("height", C.c_int32), ("period", C.c_int32), ("reserved", C.c_int32),
                 ("stride_b", C.c_int64), ("stride_c", C.c_int64), ("stride_h", C.c_int64), ("stride_p", C.c_int64)]
@@ -246,6 +256,18 @@ SIGNATURES = {
     "gvx_hifigan_mpd_backward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, C.POINTER(gvx_weight_desc), _i, _vp, _vp, _sz, _vp]),
     "gvx_hifigan_mpd_timing_enable": (_i, [_vp, _i]),
     "gvx_hifigan_mpd_layer_times_ms": (_i, [_vp, C.POINTER(_f), C.POINTER(_f), C.POINTER(_i)]),
+    "gvx_hifigan_msd_blob_floats": (_sz, [C.POINTER(gvx_hifigan_msd_dims)]),
+    "gvx_hifigan_msd_pack_weights_device": (_i, [C.POINTER(gvx_hifigan_msd_dims), C.POINTER(gvx_weight_desc), _i, _vp, _vp]),
+    "gvx_hifigan_msd_create": (_i, [C.POINTER(gvx_hifigan_msd_dims), C.POINTER(_vp)]),
+    "gvx_hifigan_msd_destroy": (None, [_vp]),
+    "gvx_hifigan_msd_bind": (_i, [_vp, _vp]),
+    "gvx_hifigan_msd_layout": (_i, [C.POINTER(gvx_hifigan_msd_dims), _i, _i, C.POINTER(gvx_hifigan_msd_entry), _i]),
+    "gvx_hifigan_msd_features_bytes": (_sz, [C.POINTER(gvx_hifigan_msd_dims), _i, _i]),
+    "gvx_hifigan_msd_workspace_bytes": (_sz, [C.POINTER(gvx_hifigan_msd_dims), _i, _i, _i]),
+    "gvx_hifigan_msd_forward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _sz, _vp]),
+    "gvx_hifigan_msd_backward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, C.POINTER(gvx_weight_desc), _i, _vp, _vp, _sz, _vp]),
+    "gvx_hifigan_msd_timing_enable": (_i, [_vp, _i]),
+    "gvx_hifigan_msd_layer_times_ms": (_i, [_vp, C.POINTER(_f), C.POINTER(_f), C.POINTER(_i)]),
     "gvx_stft_loss_create": (_i, [C.POINTER(gvx_stft_resolution), _i, _f, _f, _f, C.POINTER(_vp)]),
     "gvx_stft_loss_destroy": (None, [_vp]),
     "gvx_stft_loss_workspace_bytes": (_sz, [_vp, _i, _l]),

@@ -421,6 +421,77 @@ class HiFiGANPeriodDiscriminatorConfig(BaseConfig):
         return len(self.periods) * sum(cout * cin * k + cout for cin, cout, k, _s, _p in self.layer_shapes())
 
 
+class HiFiGANScaleDiscriminatorConfig(BaseConfig):
+    """HiFi-GAN's multi-scale discriminator (Kong et al. 2020; include/genvox_amd.h, "HiFi-GAN scale discriminators").  The defaults
+    are the published ``MultiScaleDiscriminator``: three scales, the first under spectral norm (``spectral_norm_scales``), the others
+    under weight norm, which is folded on load; the ranges are what the kernels take."""
+
+    MAX_SCALES = 4       # GVX_HIFIGAN_MSD_MAX_SCALES
+    MAX_LAYERS = 8       # GVX_HIFIGAN_MSD_MAX_LAYERS
+    MAX_KERNEL = 41      # GVX_HIFIGAN_MSD_MAX_KERNEL
+
+    _FIELDS = {
+        "n_scales": (3, None),
+        "channels": ((128, 128, 256, 512, 1024, 1024, 1024), None),
+        "kernel_sizes": ((15, 41, 41, 41, 41, 41, 5), None),
+        "strides": ((1, 2, 2, 4, 4, 1, 1), None),
+        "groups": ((1, 4, 16, 16, 16, 16, 1), None),
+        "spectral_norm_scales": ((0,), None),
+        "leaky_slope": (0.1, None),
+    }
+
+    def _normalise(self) -> None:
+        try:
+            for name in ("channels", "kernel_sizes", "strides", "groups", "spectral_norm_scales"):
+                setattr(self, name, [int(v) for v in getattr(self, name)])
+        except (TypeError, ValueError):
+            raise ValueError("channels, kernel_sizes, strides, groups and spectral_norm_scales must be sequences of integers") from None
+        if isinstance(self.n_scales, bool) or not isinstance(self.n_scales, int):
+            raise ValueError(f"n_scales must be an integer, not {self.n_scales!r}")
+        if not 1 <= self.n_scales <= self.MAX_SCALES:
+            raise ValueError(f"n_scales = {self.n_scales} is outside [1, {self.MAX_SCALES}]")
+        if not 2 <= len(self.channels) <= self.MAX_LAYERS:
+            raise ValueError(f"channels must name 2 to {self.MAX_LAYERS} layers, not {len(self.channels)}")
+        for name in ("kernel_sizes", "strides", "groups"):
+            if len(getattr(self, name)) != len(self.channels):
+                raise ValueError(f"{name} names {len(getattr(self, name))} layers, channels {len(self.channels)}")
+        cin = 1
+        for c, k, s, g in zip(self.channels, self.kernel_sizes, self.strides, self.groups):
+            if not 1 <= c <= 4096:
+                raise ValueError(f"channels: {c} is outside [1, 4096]")
+            if not 1 <= k <= self.MAX_KERNEL or k % 2 == 0:
+                raise ValueError(f"kernel_sizes: {k} must be odd and in [1, {self.MAX_KERNEL}]")
+            if not 1 <= s <= 8:
+                raise ValueError(f"strides: {s} is outside [1, 8]")
+            if g < 1 or cin % g or c % g:
+                raise ValueError(f"groups: {g} must be at least 1 and divide both channel counts of its layer ({cin} -> {c})")
+            cin = c
+        for s in self.spectral_norm_scales:
+            if not 0 <= s < self.n_scales:
+                raise ValueError(f"spectral_norm_scales: {s} names no scale of {self.n_scales}")
+        if len(set(self.spectral_norm_scales)) != len(self.spectral_norm_scales):
+            raise ValueError("spectral_norm_scales names a scale twice")
+        if not 0.0 <= float(self.leaky_slope) <= 1.0:
+            raise ValueError(f"leaky_slope = {self.leaky_slope} is outside [0, 1]")
+
+    def layer_shapes(self):
+        """The convolutions of one scale, the score last, as (c_in, c_out, taps, stride, padding, groups)."""
+        shapes, cin = [], 1
+        for c, k, s, g in zip(self.channels, self.kernel_sizes, self.strides, self.groups):
+            shapes.append((cin, c, k, s, k // 2, g))
+            cin = c
+        shapes.append((cin, 1, 3, 1, 1, 1))
+        return shapes
+
+    @property
+    def min_samples(self) -> int:
+        """The shortest row: there is no reflection, 1 sample is enough."""
+        return 1
+
+    def parameter_count(self) -> int:
+        return self.n_scales * sum(cout * (cin // g) * k + cout for cin, cout, k, _s, _p, g in self.layer_shapes())
+
+
 class HiFiGANTrainingConfig(BaseConfig):
     """The training keys of a published HiFi-GAN ``config.json`` under their names and with their defaults; ``feat_match`` and
     ``aux_weight`` are the weights that implementation keeps in its training script (2 on the feature-matching term, 45 on the

@@ -1,7 +1,7 @@
-"""One GAN step of HiFi-GAN: the generator against the multi-period discriminator - and, optionally, further discriminators - all on
-the device's own kernels.
+"""One GAN step of HiFi-GAN: the generator against the multi-period and the multi-scale discriminator - or any other list of
+discriminators - all on the device's own kernels.  The published step:
 
-    trainer = HiFiGANTrainer(generator, [HiFiGANPeriodDiscriminator(), MelGANDiscriminator()], aux_loss=MelSpectrogramLoss())
+    trainer = HiFiGANTrainer(generator, [HiFiGANPeriodDiscriminator(), HiFiGANScaleDiscriminator()], aux_loss=MelSpectrogramLoss())
     terms = trainer.train_step(mel, wav, mel_lengths)     # {"d_loss": ..., "g_adv": ..., "g_feat_match": ..., "g_aux": ..., "g_loss": ...}
     trainer.end_epoch()                                   # both learning rates times lr_decay
 
@@ -9,7 +9,8 @@ It is a step, not a loop: data loading, checkpoint rotation and logging belong t
 offers ``forward(wav, sample_lengths)`` -> [sub-discriminator][map] and ``map_lengths(sample_lengths)``.  The spectral term is
 ``aux_loss(fake, wav, sample_lengths)``, weighted ``aux_weight``: with ``losses.MelSpectrogramLoss()`` - HiFi-GAN's mel-spectrogram L1
 term - the default ``aux_weight`` of 45 carries its published meaning (``MultiResolutionSTFTLoss`` fits the same slot, on another scale).
-HiFi-GAN's own scale discriminator is not built; ``MelGANDiscriminator`` serves as the scale-side adversary until it is."""
+``HiFiGANScaleDiscriminator`` in training mode does one power iteration of its spectral scale per forward, four per step, as the
+published recipe does; ``MelGANDiscriminator`` fits the same list."""
 from __future__ import annotations
 
 from typing import Dict, Optional, Sequence

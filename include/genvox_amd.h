@@ -1405,6 +1405,109 @@ int gvx_hifigan_mpd_backward(gvx_hifigan_mpd* handle, const float* wav, const in
 int gvx_hifigan_mpd_timing_enable(gvx_hifigan_mpd* handle, int enable);
 int gvx_hifigan_mpd_layer_times_ms(gvx_hifigan_mpd* handle, float* forward_ms, float* backward_ms, int* n_layers_out);
 
+/* ---- HiFi-GAN scale discriminators (Kong et al. 2020, the published DiscriminatorS / MultiScaleDiscriminator): forward, and the
+ * backward that reads the forward's own maps as its tape.  The surface mirrors the period discriminators' above.  All arithmetic fp32.
+ *
+ * The model.  Scale 0 sees the waveform; scale s + 1 sees the waveform of scale s through AvgPool1d(4, stride 2, padding 2) with
+ * count_include_pad: y[j] = (the sum of x[2j - 2 .. 2j + 1] inside [0, n)) / 4 for j = 0 .. n / 2, so n' = n / 2 + 1.  On a row of n
+ * samples of its scale, layers i = 0 .. n_layers - 1 are Conv1d(c_{i-1} -> channels[i], kernel_sizes[i], stride strides[i], zero
+ * padding kernel_sizes[i] / 2, groups[i]) with c_{-1} = 1, each followed by LeakyReLU(slope); lengths L' = (L - 1) / stride + 1.  The
+ * score is Conv1d(c_last -> 1, 3, padding 1) without activation.  All n_layers + 1 maps of a scale are returned (post-activation; the
+ * last is the score).  The published shape is channels 128, 128, 256, 512, 1024, 1024, 1024; kernel sizes 15, 41, 41, 41, 41, 41, 5;
+ * strides 1, 2, 2, 4, 4, 1, 1; groups 1, 4, 16, 16, 16, 16, 1; three scales; slope 0.1 - 9,870,209 parameters per scale.  Spectral and
+ * weight norm are the caller's: the kernels see effective weights.
+ *
+ * Ragged batches: sample_lengths is int32 [B] on the device, or NULL for all n_max.  Row b is computed as if alone at n_b =
+ * min(sample_lengths[b], n_max): the zero padding, every pooled length and every L_i are its own; nothing of wav at or behind n_b is
+ * read; every map is exact zeros behind the row's own length; a ragged row has the bits of its one-row run.  There is no reflection:
+ * the shortest legal row is 1 sample; a row of fewer comes out as all-zero maps, never a bad address.
+ *
+ * Dims are refused (GVX_ERR_INVALID_ARG from create and pack, 0 from the size functions) unless: n_scales in [1, 4]; n_layers in
+ * [2, 8]; every channel count in [1, 4096]; every kernel size odd and in [1, 41]; every stride in [1, 8]; every group count at least 1
+ * and a divisor of both channel counts of its layer; slope in [0, 1].
+ *
+ * Weights.  gvx_hifigan_msd_pack_weights_device reads PyTorch-layout tensors from DEVICE pointers, by name:
+ *     discriminators.<s>.convs.<i>.weight [c_out][c_in / groups][k], .bias [c_out],
+ *     discriminators.<s>.conv_post.weight [1][c_last][3], .bias [1]
+ * and writes the blob (gvx_hifigan_msd_blob_floats): every weight twice, once for the forward and once for the data gradient, in the
+ * order the layer's kernels read them.  A missing name is GVX_ERR_MISSING_WEIGHT, a wrong element count GVX_ERR_SHAPE, both before
+ * anything is launched.  The blob must be 256-byte aligned.
+ *
+ * Features buffer: the caller's, 256-byte aligned, gvx_hifigan_msd_features_bytes long.  Maps are CHANNELS-LAST: map (s, i) is fp32
+ * [B][length][channels], every map starting at a multiple of 256 bytes.  gvx_hifigan_msd_layout (host arithmetic) lists, scale by scale
+ * and map by map, the byte offset, channels, length (of a row of n_max samples) and the strides in floats of the [B, C, L] view.  It
+ * returns the number of entries, n_scales * (n_layers + 1), and fills at most max_entries of them (entries may be NULL); 0 for refused
+ * dims, B or n_max.
+ *
+ * Workspace: gvx_hifigan_msd_workspace_bytes(dims, B, n_max, backward) is host arithmetic; any contents when a call starts, nothing is
+ * cleared, 256-byte aligned.  The forward's holds the pooled waveforms; the backward's holds them again, the waveform gradient of every
+ * pooled scale, two activation gradients of the largest map and the partial weight and bias gradients of the layer that needs most.
+ *
+ * Kernels.  A workgroup computes GVX_HIFIGAN_MSD_TILE positions of one row, in every convolution kernel; a data gradient's workgroup
+ * takes its positions from ONE stride phase (input positions l with the same l mod stride), so that only the taps
+ * t = (l + pad) mod stride, + stride, ... are multiplied.  A layer whose per-group input channels are a multiple of
+ * GVX_HIFIGAN_MSD_MFMA_IN_MULT and whose per-group output channels are a multiple of GVX_HIFIGAN_MSD_MFMA_OUT_MULT runs - forward,
+ * data gradient and weight gradient - as an implicit GEMM on the fp32 matrix instruction: positions on M, the group's output channels
+ * on N, taps x group channels on K; v_mfma_f32_32x32x2_f32 where both per-group counts are multiples of 32, v_mfma_f32_16x16x4_f32
+ * otherwise.  The forward and the data gradient stage a tile's input window - (GVX_HIFIGAN_MSD_TILE - 1) * stride + k positions of a
+ * block of the group's channels, zeros outside the row - into LDS once and run every tap off row offsets in it.  The weight gradient
+ * is a per-group GEMM with positions on K, one piece per row or per run of GVX_HIFIGAN_MSD_WG_RUN positions of a row.  The other
+ * layers (the first, the score, narrow test layers), the pooling and its adjoint are fp32 VALU code.  LeakyReLU and its mask are
+ * applied in the epilogues.  Every kernel is an ordinary launch.  Nothing is computed for a tile that lies behind its row.
+ *
+ * gvx_hifigan_msd_forward: refused before anything is launched: a NULL handle, wav or features, B outside [1, 65535], n_max below 1
+ * (GVX_ERR_INVALID_ARG); n_max above GVX_HIFIGAN_MSD_MAX_SAMPLES (GVX_ERR_UNSUPPORTED); no blob bound (GVX_ERR_STATE); a misaligned
+ * or short features buffer, a NULL, misaligned or short workspace (GVX_ERR_WORKSPACE).
+ *
+ * gvx_hifigan_msd_backward: features is what the forward wrote for the same wav, lengths and weights - it is the tape: a LeakyReLU
+ * output is positive exactly where its pre-activation is, so the masks are read off the maps.  d_features has the layout of features
+ * and holds the cotangent of EVERY map; nothing of it is read behind a row's own lengths.  grads is a HOST table of n_grads DEVICE
+ * destinations under the packer's names, each WRITTEN in PyTorch's layout; n_grads = 0 skips every parameter gradient.  d_wav is fp32
+ * [B][n_max], the sum over the scales through the adjoint of the pooling written as a gather (sample i collects pooled positions i / 2
+ * and i / 2 + 1): the last scale's waveform gradient is pooled back into the one before it, and so on down to scale 0 - one fixed
+ * order; exactly 0 at and behind n_b, or NULL to skip it.  What a call does compute has the bits the full call gives it.  Refused as
+ * the forward refuses, and: a missing name (GVX_ERR_MISSING_WEIGHT), a wrong element count or NULL destination (GVX_ERR_SHAPE), a NULL
+ * d_features, or neither gradient asked for (GVX_ERR_INVALID_ARG).  Weight and bias gradients are summed over rows and positions in
+ * pieces that are added in a fixed order; no atomics: two calls give the same bits. */
+enum { GVX_HIFIGAN_MSD_MAX_SCALES = 4, GVX_HIFIGAN_MSD_MAX_LAYERS = 8, GVX_HIFIGAN_MSD_MAX_KERNEL = 41, GVX_HIFIGAN_MSD_TILE = 64,
+       GVX_HIFIGAN_MSD_MFMA_IN_MULT = 8, GVX_HIFIGAN_MSD_MFMA_OUT_MULT = 16, GVX_HIFIGAN_MSD_WG_RUN = 256,
+       GVX_HIFIGAN_MSD_MAX_SAMPLES = 1 << 24 };
+typedef struct gvx_hifigan_msd_dims {
+    int32_t n_scales;
+    int32_t n_layers;
+    int32_t channels[8];
+    int32_t kernel_sizes[8];
+    int32_t strides[8];
+    int32_t groups[8];
+    float slope;
+} gvx_hifigan_msd_dims;
+typedef struct gvx_hifigan_msd_entry {
+    uint64_t byte_offset;
+    int32_t channels;
+    int32_t length;
+    int64_t stride_b, stride_c, stride_l;   /* floats, of the [B, C, L] view */
+} gvx_hifigan_msd_entry;
+typedef struct gvx_hifigan_msd gvx_hifigan_msd;
+size_t gvx_hifigan_msd_blob_floats(const gvx_hifigan_msd_dims* dims);
+int gvx_hifigan_msd_pack_weights_device(const gvx_hifigan_msd_dims* dims, const gvx_weight_desc* table, int n, float* device_blob,
+                                        void* stream);
+int gvx_hifigan_msd_create(const gvx_hifigan_msd_dims* dims, gvx_hifigan_msd** out);
+void gvx_hifigan_msd_destroy(gvx_hifigan_msd* handle);
+int gvx_hifigan_msd_bind(gvx_hifigan_msd* handle, const float* device_blob);
+int gvx_hifigan_msd_layout(const gvx_hifigan_msd_dims* dims, int B, int n_max, gvx_hifigan_msd_entry* entries, int max_entries);
+size_t gvx_hifigan_msd_features_bytes(const gvx_hifigan_msd_dims* dims, int B, int n_max);
+size_t gvx_hifigan_msd_workspace_bytes(const gvx_hifigan_msd_dims* dims, int B, int n_max, int backward);
+int gvx_hifigan_msd_forward(gvx_hifigan_msd* handle, const float* wav, const int32_t* sample_lengths, int B, int n_max, void* features,
+                            size_t features_bytes, void* workspace, size_t workspace_bytes, void* stream);
+int gvx_hifigan_msd_backward(gvx_hifigan_msd* handle, const float* wav, const int32_t* sample_lengths, int B, int n_max,
+                             const void* features, const void* d_features, const gvx_grad_desc* grads, int n_grads, float* d_wav,
+                             void* workspace, size_t workspace_bytes, void* stream);
+/* Measurement only (tools/bench_extra.py hifigan_msd): when enabled, the calls record events around every layer;
+ * gvx_hifigan_msd_layer_times_ms synchronises and returns, per layer (the score last; n_layers + 1 of them) and summed over the scales,
+ * the time of the last forward and of the last backward (a layer's weight, bias and data gradient together; 0 for a call not made). */
+int gvx_hifigan_msd_timing_enable(gvx_hifigan_msd* handle, int enable);
+int gvx_hifigan_msd_layer_times_ms(gvx_hifigan_msd* handle, float* forward_ms, float* backward_ms, int* n_layers_out);
+
 /* ---- Multi-resolution STFT loss: the distance between a predicted waveform and its target that a vocoder is trained on (spectral
  * convergence plus log-magnitude L1 over several STFT resolutions; Yamamoto et al., Parallel WaveGAN), value and gradient in one call.
  * The reference ships no vocoder loss; this is the standard non-adversarial one, on the in-LDS transforms of the vocoder kernels.

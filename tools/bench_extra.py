@@ -32,7 +32,11 @@ forward's and the backward's time per stage from the same run and the tape's and
 `hifigan_mpd` (on request): HiFi-GAN's multi-period discriminator, default shape, at 16 x 8192 and 8 x 32768 samples between device events,
 median of 7 with the spread: forward, forward + full backward (cotangents on every map), against torch's own Conv2d + autograd on the
 same parameters; per layer the counted multiply-adds, the time (events around every layer, summed over the periods) and the share of
-the fp32 matrix rate; and one `HiFiGANTrainer.train_step` of the V1 generator against the period discriminators."""
+the fp32 matrix rate; and one `HiFiGANTrainer.train_step` of the V1 generator against the period discriminators;
+`hifigan_msd` (on request): HiFi-GAN's multi-scale discriminator, published shape, the same measurement at the same two sizes against
+torch's own grouped Conv1d + avg_pool1d + autograd on the same effective weights (eval mode: no power iteration), the per-layer times
+summed over the scales; and one `HiFiGANTrainer.train_step` of the V1 generator against the period and the scale discriminators with
+`MelSpectrogramLoss` - the published step."""
 import json
 import os
 import sys
@@ -699,6 +703,116 @@ def main():
             res[key]["train_step_v1"] = ev_spread(lambda: trainer.train_step(mel, real), warm=2, reps=5)
             print(json.dumps({key: {"train_step_v1": res[key]["train_step_v1"]}}), flush=True)
             del trainer
+    if "hifigan_msd" in which:
+        import ctypes as C
+        import statistics
+
+        import torch.nn.functional as F
+
+        from genvox_amd import _lib
+        from genvox_amd.configs import HiFiGANConfig, HiFiGANScaleDiscriminatorConfig
+        from genvox_amd.hifigan import HiFiGANGenerator
+        from genvox_amd.hifigan_disc import HiFiGANPeriodDiscriminator
+        from genvox_amd.hifigan_msd import HiFiGANScaleDiscriminator
+        from genvox_amd.hifigan_training import HiFiGANTrainer
+        from genvox_amd.losses import MelSpectrogramLoss
+
+        FP32_MATRIX_TFLOPS = 157.3   # the MI355X's fp32 matrix (= vector) peak
+
+        def ev_spread(fn, warm=2, reps=7):
+            for _ in range(warm):
+                fn()
+            out = []
+            for _ in range(reps):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                e1.synchronize()
+                out.append(e0.elapsed_time(e1))
+            return {"median_ms": round(statistics.median(out), 3), "min_ms": round(min(out), 3), "max_ms": round(max(out), 3), "runs": reps}
+
+        torch.manual_seed(0)
+        sc = HiFiGANScaleDiscriminatorConfig()
+        msd = HiFiGANScaleDiscriminator(sc).to("cuda:0").eval()   # eval: the weights of both sides stay the same from call to call
+        with torch.no_grad():
+            for name, p in msd.named_parameters():
+                if name.endswith("bias"):
+                    p.copy_(0.1 * torch.randn_like(p))
+        sparams = dict(msd.named_parameters())
+        sshapes = sc.layer_shapes()
+
+        def torch_msd(wav):
+            """The published composition on the module's own parameters (spectral norm through the same sigma), through torch's grouped
+            Conv1d and avg_pool1d kernels."""
+            out, x = [], wav[:, None, :]
+            eff = dict(zip(msd.weight_names(), msd.effective_weights()))
+            for s in range(sc.n_scales):
+                h, maps = x, []
+                for i, (_ci, _co, _k, stride, pad, groups) in enumerate(sshapes):
+                    name = f"discriminators.{s}.conv_post" if i == len(sshapes) - 1 else f"discriminators.{s}.convs.{i}"
+                    h = F.conv1d(h, eff[name + ".weight"], eff[name + ".bias"], stride=stride, padding=pad, groups=groups)
+                    if i < len(sshapes) - 1:
+                        h = F.leaky_relu(h, sc.leaky_slope)
+                    maps.append(h)
+                out.append(maps)
+                x = F.avg_pool1d(x, 4, 2, 2)
+            return out
+
+        def layer_macs(n):
+            """Multiply-adds of one row of n samples per layer, summed over the scales (every tap counted, padding included)."""
+            lengths = msd.feature_lengths(n)
+            return [sum(lengths[s][i] * co * (ci // g) * k for s in range(sc.n_scales)) for i, (ci, co, k, _s, _p, g) in enumerate(sshapes)]
+
+        gen = torch.Generator(device="cuda").manual_seed(0)
+        hvoc = HiFiGANGenerator(HiFiGANConfig(), ac).to("cuda:0")
+        for B, n in ((16, 8192), (8, 32768)):
+            key = f"hifigan_msd_{B}x{n}"
+            wav = (0.3 * torch.randn(B, n, device="cuda", generator=gen)).requires_grad_(True)
+            with torch.no_grad():
+                ours_maps, torch_maps = msd(wav), torch_msd(wav)
+                res[key] = {"forward": ev_spread(lambda: msd(wav)), "torch_forward": ev_spread(lambda: torch_msd(wav))}
+            res[key]["max_relative_map_difference_from_torch"] = max(float((a - b).abs().max() / b.abs().max()) for x, y in zip(ours_maps, torch_maps) for a, b in zip(x, y))
+            cots = [[torch.randn(m.shape, device="cuda", generator=gen) / m.numel() for m in ms] for ms in ours_maps]
+
+            def step(net):
+                wav.grad = None
+                for p in sparams.values():
+                    p.grad = None
+                sum((m * c).sum() for ms, cs in zip(net(wav), cots) for m, c in zip(ms, cs)).backward()
+
+            res[key]["forward_plus_backward"] = ev_spread(lambda: step(msd))
+            got = {k: p.grad.clone() for k, p in sparams.items()}
+            got["wav"] = wav.grad.clone()
+            res[key]["torch_forward_plus_backward"] = ev_spread(lambda: step(torch_msd))
+            res[key]["max_relative_gradient_difference_from_torch"] = max(
+                [float((got[k] - p.grad).abs().max() / p.grad.abs().max().clamp_min(1e-30)) for k, p in sparams.items()]
+                + [float((got["wav"] - wav.grad).abs().max() / wav.grad.abs().max())])
+            res[key]["backward_workspace_mb"] = round(msd._train_workspace.numel() / 1e6, 1)
+            # per layer: counted multiply-adds and the share of the fp32 matrix rate, from events around every layer of one more call
+            lib = _lib.load()
+            _lib.check(lib.gvx_hifigan_msd_timing_enable(msd._handle, 1))
+            step(msd)
+            fwd_ms, bwd_ms, n_l = (C.c_float * 9)(), (C.c_float * 9)(), C.c_int()
+            _lib.check(lib.gvx_hifigan_msd_layer_times_ms(msd._handle, fwd_ms, bwd_ms, C.byref(n_l)))
+            _lib.check(lib.gvx_hifigan_msd_timing_enable(msd._handle, 0))
+            macs = [B * m for m in layer_macs(n)]
+            res[key]["multiply_adds_per_row_forward"] = sum(layer_macs(n))
+            res[key]["layers"] = [
+                {"layer": f"{ci}->{co} k{k} g{g}", "forward_gmacs": round(m / 1e9, 3), "forward_ms": round(fwd_ms[i], 3),
+                 "forward_share_of_fp32_matrix_rate": round(2 * m / (fwd_ms[i] * 1e-3) / (FP32_MATRIX_TFLOPS * 1e12), 4) if fwd_ms[i] > 0 else None,
+                 "backward_ms": round(bwd_ms[i], 3),
+                 "backward_share_of_fp32_matrix_rate": round(2 * (2 if i else 1) * m / (bwd_ms[i] * 1e-3) / (FP32_MATRIX_TFLOPS * 1e12), 4) if bwd_ms[i] > 0 else None}
+                for i, ((ci, co, k, _s, _p, g), m) in enumerate(zip(sshapes, macs))]
+            print(json.dumps({key: res[key]}), flush=True)
+            msd.train()
+            trainer = HiFiGANTrainer(hvoc, [HiFiGANPeriodDiscriminator().to("cuda:0"), msd], aux_loss=MelSpectrogramLoss())
+            mel = (0.5 * torch.randn(B, 80, n // hvoc.hop, device="cuda", generator=gen) - 0.5).contiguous()
+            real = wav.detach()
+            res[key]["train_step_v1_mpd_msd_mel"] = ev_spread(lambda: trainer.train_step(mel, real), warm=2, reps=5)
+            print(json.dumps({key: {"train_step_v1_mpd_msd_mel": res[key]["train_step_v1_mpd_msd_mel"]}}), flush=True)
+            del trainer
+            msd.eval()
     if which & {"hifigan", "hifigan_train"}:
         import ctypes as C
         import statistics
