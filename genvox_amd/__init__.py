@@ -9,6 +9,7 @@
     from genvox_amd import HiFiGANScaleDiscriminator, HiFiGANScaleDiscriminatorConfig   # ... and its multi-scale discriminator
     from genvox_amd import MultiResolutionSTFTLoss, stft_distance   # vocoder training loss / waveform distance on the device
     from genvox_amd import MelSpectrogramLoss, mel_distance         # HiFi-GAN's mel-spectrogram L1 term / log-mel distance
+    from genvox_amd import Denoiser   # vocoder denoiser: Denoiser.from_vocoder(vocoder)(wav), or Synthesizer.tts(text, denoise=0.01)
 """
 from .configs import HiFiGANPeriodDiscriminatorConfig, HiFiGANScaleDiscriminatorConfig, HiFiGANTrainingConfig  # noqa: F401
 from .configs import AudioConfig, BaseConfig, HiFiGANConfig, MelGANConfig, MelGANDiscriminatorConfig, Tacotron2Config, TextConfig  # noqa: F401
@@ -51,6 +52,9 @@ def __getattr__(name):  # torch-dependent classes are imported lazily
     if name == "MelSpectrogramLoss":
         from .losses import MelSpectrogramLoss
         return MelSpectrogramLoss
+    if name == "Denoiser":
+        from .denoiser import Denoiser
+        return Denoiser
     if name == "mel_distance":
         from .metrics import mel_distance
         return mel_distance

@@ -277,6 +277,10 @@ SIGNATURES = {
     "gvx_mel_loss_bands": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     "gvx_mel_loss_workspace_bytes": (_sz, [_vp, _i, _l]),
     "gvx_mel_loss": (_i, [_vp, _vp, _vp, _vp, _i, _l, _vp, _vp, _vp, C.POINTER(gvx_mel_loss_debug), _vp, _sz, _vp]),
+    "gvx_denoise_create": (_i, [_i, _i, C.POINTER(_vp)]),
+    "gvx_denoise_destroy": (None, [_vp]),
+    "gvx_denoise_workspace_bytes": (_sz, [_vp, _i, _l]),
+    "gvx_denoise": (_i, [_vp, _vp, _vp, _i, _l, _vp, _f, _vp, _vp, _vp, _sz, _vp]),
     "gvx_kernel_timing_enable": (_i, [_vp, _i]),
     "gvx_model_set_persistent_attention": (_i, [_vp, _i]),
     "gvx_model_set_resident_kernels": (_i, [_vp, _i]),

@@ -127,6 +127,15 @@ def token_rates(token_strs: Sequence[str], word_speed: Union[Sequence[float], Ma
     return [1.0 if w < 0 else by_word[w] for w in word_of]
 
 
+def _check_denoise(denoise, has_vocoder: bool) -> float:
+    """The ``denoise`` of ``tts`` / ``tts_batch`` (no GPU needed): a finite number >= 0, not a bool; above 0 it needs a vocoder model."""
+    if isinstance(denoise, bool) or not isinstance(denoise, (int, float, np.integer, np.floating)) or not math.isfinite(denoise) or denoise < 0:
+        raise ValueError(f"denoise must be a finite number >= 0, not {denoise!r}")
+    if denoise > 0 and not has_vocoder:
+        raise ValueError(f"denoise = {denoise} needs a vocoder model: Griffin-Lim has no bias to subtract")
+    return float(denoise)
+
+
 PITCH_MAX_SEMITONES = 12.0   # a shift of an octave either way: the ratios 0.5 and 2 of GVX_PSOLA_RATIO_MIN / GVX_PSOLA_RATIO_MAX
 
 
@@ -208,6 +217,7 @@ class Synthesizer:
         self.audio_processor = AudioProcessor(config=self.tts_model.audio_config, device=self.device)
         given = [vocoder_model_class, vocoder_config_path, vocoder_checkpoint_path]
         self.vocoder = None
+        self._denoiser = None   # made on the first denoise > 0: the vocoder's bias spectrum is taken once
         if any(g is not None for g in given):
             if any(g is None for g in given):
                 raise ValueError("a vocoder needs vocoder_model_class, vocoder_config_path and vocoder_checkpoint_path, all three")
@@ -269,7 +279,30 @@ class Synthesizer:
         wav, counts, _, _ = self._vocode_and_track(mel, frames, sampling_rate, False)
         return wav, counts
 
-    def _vocode_and_track(self, mel: torch.Tensor, frames, sampling_rate: Optional[int], pitch: bool, control: Optional[Dict] = None):
+    def _denoise(self, wav: torch.Tensor, counts, strength: float) -> torch.Tensor:
+        """The vocoder's waveforms with ``strength`` times its bias spectrum taken off (``Denoiser.from_vocoder`` at its defaults, made
+        on first use and kept): the ragged batch in one call, every row at its own sample count.  Rows below the denoiser's
+        ``min_samples`` (513: fewer than 3 frames at a hop of 256) pass through unchanged."""
+        if self._denoiser is None:
+            from .denoiser import Denoiser
+
+            self._denoiser = Denoiser.from_vocoder(self.vocoder)
+        dn = self._denoiser
+        if wav.shape[1] < dn.min_samples:
+            return wav
+        if counts is None:
+            return dn(wav, None, strength)
+        keep = [b for b, n in enumerate(counts) if n >= dn.min_samples]
+        if len(keep) == len(counts):
+            return dn(wav, counts, strength)
+        if not keep:
+            return wav
+        out = wav.clone()
+        out[keep] = dn(wav[keep], [counts[b] for b in keep], strength)
+        return out
+
+    def _vocode_and_track(self, mel: torch.Tensor, frames, sampling_rate: Optional[int], pitch: bool, control: Optional[Dict] = None,
+                          denoise: float = 0.0):
         """``_vocode`` with the pitch contour of what it made: ``(waveforms, sample counts or None, f0 or None)``.  The waveform is
         vocoded at the model's rate, tracked there when ``pitch`` asks (``metrics.pitch_track`` with the model's hop, every row at
         its own sample count; frame 0 centred on sample ``-TRIM`` of a Griffin-Lim waveform, which lost ``TRIM`` samples at its
@@ -283,7 +316,10 @@ class Synthesizer:
         other than 1, 2 ** ((range - 1) * (log2 f0 - the row's mean log2 f0 over its voiced frames)) on the voiced frames, clamped
         to [0.5, 2], torch operations on the device - and tracked again when ``pitch`` asks, so that f0 is the contour of what is
         delivered.  A fourth value is returned: the ratios applied, float32 [B, T] on the device (1 where the waveform has no
-        frame), or None."""
+        frame), or None.
+
+        ``denoise`` > 0 (a vocoder model only): the vocoded waveform goes through ``_denoise`` directly behind ``vocode``, before
+        tracking, pitch control and resampling, so that f0 and the pitch control see what is delivered."""
         ap = self.audio_processor
         if self.vocoder is None:
             if frames is None:
@@ -295,6 +331,8 @@ class Synthesizer:
             host = None if frames is None else [int(t) for t in (frames.tolist() if isinstance(frames, torch.Tensor) else frames)]
             wav = self.vocoder.vocode(mel.contiguous(), host)
             counts = None if host is None else [t * self.vocoder.hop for t in host]
+            if denoise > 0.0:
+                wav = self._denoise(wav, counts, denoise)
             first_centre = 0
         f0 = ratios = None
         if pitch or control is not None:
@@ -425,7 +463,7 @@ class Synthesizer:
     def tts(self, text: str, sampling_rate: Optional[int] = None, diagnostics: bool = False,
             attention_window: Optional[Tuple[int, int]] = None, timings: bool = False, speed: float = 1.0,
             word_speed=None, token_speed=None, pitch: bool = False, pitch_shift: float = 0.0, word_pitch=None,
-            pitch_range: float = 1.0) -> Dict[str, np.ndarray]:
+            pitch_range: float = 1.0, denoise: float = 0.0) -> Dict[str, np.ndarray]:
         """``sampling_rate`` (Hz; default: the model's): the waveform is resampled on the device before it is copied to the host,
         and ``"sampling_rate"`` of the result is the rate delivered.  ``diagnostics``: the result gains ``"alignment_stats"``
         (focus, monotonic_fraction, max_jump, coverage, first_pos, last_pos of the sentence's alignment, as Python numbers) and
@@ -458,7 +496,11 @@ class Synthesizer:
         every sample count stay, so ``timings`` are what they are without it; a word's frames are those of the search of
         ``timings``, or of the rate plan): the result gains ``"pitch_shift"`` and ``"pitch_ratio"`` - float32 [frames], the factor on
         the pitch applied to every frame of the vocoded mel, clamped to [0.5, 2] - and ``pitch`` reports the contour of the shifted
-        waveform."""
+        waveform.  ``denoise`` (>= 0; needs a vocoder model, Griffin-Lim has no bias to subtract): above 0 the vocoded waveform
+        goes through the vocoder's ``Denoiser`` at that strength - ``Denoiser.from_vocoder`` at its defaults, made on first use and
+        kept - at the model's rate, before pitch tracking, pitch control and resampling, and the result gains ``"denoise"``: the
+        strength.  A waveform of fewer than 513 samples passes through unchanged.  At 0 nothing changes and no launch is added."""
+        denoise = _check_denoise(denoise, self.vocoder is not None)
         token_strs = self.text_processor.tokenize(text)
         paced = speed != 1.0 or word_speed is not None or token_speed is not None
         if paced:
@@ -490,7 +532,7 @@ class Synthesizer:
                                                   pitch_shift), "range": pitch_range}
         if not timings:
             aligned = None
-        wav, _, f0, ratios = self._vocode_and_track(mel, None, sampling_rate, pitch, control)  # stays on the device until the end
+        wav, _, f0, ratios = self._vocode_and_track(mel, None, sampling_rate, pitch, control, denoise)  # stays on the device until the end
         result = {key: val.squeeze(0).cpu().numpy() for key, val in outputs.items()}
         result["waveform"] = wav[0].cpu().numpy()
         result["sampling_rate"] = self._out_rate(sampling_rate)
@@ -510,13 +552,15 @@ class Synthesizer:
         if ratios is not None:
             result["pitch_shift"] = pitch_shift
             result["pitch_ratio"] = ratios[0].cpu().numpy()
+        if denoise > 0.0:
+            result["denoise"] = denoise
         return result
 
     def tts_batch(self, texts: Sequence[str], batch_size: int = 32, sampling_rate: Optional[int] = None,
                   diagnostics: bool = False, attention_window: Optional[Tuple[int, int]] = None,
                   timings: bool = False, speed: float = 1.0, word_speed=None, token_speed=None,
                   pitch: bool = False, pitch_shift: float = 0.0, word_pitch=None,
-                  pitch_range: float = 1.0) -> List[Dict[str, np.ndarray]]:
+                  pitch_range: float = 1.0, denoise: float = 0.0) -> List[Dict[str, np.ndarray]]:
         """Many sentences per call: one dict per sentence, in input order, with the keys, dtypes and shapes ``tts(text)`` gives
         for that sentence (every row trimmed to its own frames, tokens and samples).  Sentences are decoded as padded batches of
         at most ``batch_size`` rows of similar token length (``plan_tts_batches``) and vocoded at their own lengths in one ragged
@@ -530,7 +574,9 @@ class Synthesizer:
         ``pitch`` as in ``tts``: every sentence's waveform is tracked at its own sample count, in one call per batch.
         ``pitch_shift`` and ``pitch_range`` as in ``tts``, for every sentence; ``word_pitch`` is a list with one entry per sentence,
         each as in ``tts`` (None: no word of that sentence is named): every sentence is repitched at its own sample count, around its
-        own mean pitch, in one plan and one synthesis call per batch."""
+        own mean pitch, in one plan and one synthesis call per batch.  ``denoise`` as in ``tts``, for every sentence: one ragged call
+        per batch, every sentence at its own sample count."""
+        denoise = _check_denoise(denoise, self.vocoder is not None)
         token_strs = [self.text_processor.tokenize(t) for t in texts]
         token_lists = [self.text_processor.tokens_to_indices(toks) for toks in token_strs]
         paced = speed != 1.0 or word_speed is not None or token_speed is not None
@@ -576,10 +622,11 @@ class Synthesizer:
                 aligned = None
             if len(idx) > 1:
                 frames = outputs.pop("mel_lengths")
-                wav, samples, f0, ratios = self._vocode_and_track(vocoded, frames if warped is None else new_frames, sampling_rate, pitch, control)
+                wav, samples, f0, ratios = self._vocode_and_track(vocoded, frames if warped is None else new_frames, sampling_rate, pitch, control,
+                                                                          denoise)
                 frames = frames.tolist()
             else:
-                wav, _, f0, ratios = self._vocode_and_track(vocoded, None, sampling_rate, pitch, control)
+                wav, _, f0, ratios = self._vocode_and_track(vocoded, None, sampling_rate, pitch, control, denoise)
                 frames, samples = [mel.shape[2]], [wav.shape[1]]
             if f0 is not None:
                 f0 = f0.cpu().numpy()
@@ -619,4 +666,6 @@ class Synthesizer:
                 if ratios is not None:
                     results[i]["pitch_shift"] = pitch_shift
                     results[i]["pitch_ratio"] = ratios[r, :t].copy()
+                if denoise > 0.0:
+                    results[i]["denoise"] = denoise
         return results

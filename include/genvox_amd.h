@@ -1648,6 +1648,59 @@ int gvx_mel_loss(gvx_mel_loss_plan* plan, const float* pred, const float* target
                  float* loss_out, float* parts_out, float* d_pred, const gvx_mel_loss_debug* dbg, void* workspace, size_t workspace_bytes,
                  void* stream);
 
+/* ---- Vocoder denoiser: the post-filter that the usual neural-vocoder inference scripts apply - take strength times the vocoder's bias
+ * spectrum (the magnitudes of what it makes of a constant mel) off the STFT magnitudes of a vocoded waveform, clamp at 0, and transform
+ * back with the phase kept.  The reference ships no vocoder and no such filter; the definition is this library's own, on the in-LDS
+ * transforms of the two waveform losses.
+ *
+ * Inputs.  wav: fp32 [B][n_max].  sample_lengths: int32 [B] on the device or NULL; row b has n_b = sample_lengths[b] samples (n_max
+ * without it).  Plan: n_fft in {512, 1024, 2048}, 1 <= hop <= n_fft / 2.  bias: fp32 [n_fft / 2 + 1] on the device, or NULL;
+ * strength finite and >= 0, and a strength > 0 needs a bias.  With pad = n_fft / 2, per row b:
+ *   - frames: F_b = 1 + n_b / hop (integer division); frame t holds the padded positions p = t * hop + j, j in [0, n_fft), through the
+ *     single reflection of gvx_stft_loss: the source index of p is i = p - pad; for i < 0 it is -i, for i >= n_b it is 2 (n_b - 1) - i.
+ *     So a row needs n_b >= pad + 1.  The window is the periodic Hann 0.5 - 0.5 cos(2 pi j / n_fft); it and the twiddles are made in
+ *     double on the host.  This is torch.stft with center=True and pad_mode="reflect" on the row cut at its own length;
+ *   - gain, per bin k = 0 .. n_fft / 2 of the frame's spectrum X: M = sqrt(re^2 + im^2) and a = strength * bias[k] (a = 0 without a
+ *     bias).  Y = X max(0, M - a) / M where M > 0 and Y = 0 where M == 0; with a == 0, Y is X unchanged;
+ *   - inverse: z_t = the inverse real transform of Y_t, the 1 / n_fft included, times the same window;
+ *   - out[b][i] = (sum_t z_t[p - t hop]) / (sum_t w^2[p - t hop]) with p = i + pad, both sums in ascending order over the row's own
+ *     frames t that cover p: torch.istft with center=True and length=n_b.  The denominator comes from the row's own frames, so the
+ *     row's ends are right without a table per length, and it is positive at every sample of the row: the periodic Hann is zero only
+ *     at index 0, and with hop <= n_fft / 2 every p in [pad, pad + n_b) lies in two consecutive frames of the row at least - where
+ *     one of them has p at its index 0, the frame before it (there is one: p >= pad >= hop) has it at index hop, where w > 0;
+ *   - out is exact zeros at and behind n_b; mag_out[b][t][k] = M, exact zeros behind the row's frames.
+ * Whatever lies at and behind n_b in wav is never read.  out == wav (in place) is allowed: the first launch only reads wav and the
+ * second only writes out.
+ *
+ * gvx_denoise_create is host work alone (the first call of a plan moves its tables to the device; calls on one plan are not
+ * concurrent): an n_fft outside the three sizes is GVX_ERR_UNSUPPORTED, a hop outside [1, n_fft / 2] GVX_ERR_INVALID_ARG.
+ * gvx_denoise_workspace_bytes is host arithmetic (0 for a NULL plan, B outside [1, GVX_DENOISE_MAX_ROWS] or n_max outside
+ * [1, GVX_DENOISE_MAX_SAMPLES]); the workspace follows the conventions of gvx_mel_loss: any contents, 256-byte aligned, exactly that
+ * size, nothing cleared.  It holds the windowed inverse frames [B][1 + n_max / hop][n_fft] - linear in B and in the frames of a row
+ * of n_max samples - and is asked for whatever the outputs are.
+ *
+ * The call: out [B][n_max] or NULL, mag_out [B][1 + n_max / hop][n_fft / 2 + 1] or NULL, one of them at least; without out the
+ * inverse half and the second launch are skipped, and either output has the same bits whether or not the other is asked for.  Refused
+ * before anything is launched, as gvx_mel_loss has it: NULL arguments, bad B or n_max, a strength that is negative or not finite, a
+ * strength > 0 without a bias (GVX_ERR_INVALID_ARG), n_max below pad + 1 (GVX_ERR_SHAPE), a NULL, short or misaligned workspace
+ * (GVX_ERR_WORKSPACE).  With sample_lengths a row with n_b outside [pad + 1, n_max] has no frames for the kernels - nothing of it is
+ * read, its row of out and its magnitudes are zeros - and the call reads the lengths back behind its launches (so with sample_lengths
+ * it waits for the stream, once) and returns GVX_ERR_SHAPE naming the first such row; the other rows are what they are without it.
+ *
+ * Kernels (fp32).  One launch does everything of a frame, a frame per wave and GVX_DENOISE_FRAMES_PER_WORKGROUP frames per workgroup:
+ * the samples gathered through the reflection and windowed, a complex transform of n_fft / 2 points in LDS and the even/odd split,
+ * magnitude and gain in registers, the inverse side packed through the wave's LDS row, the inverse transform and the window; the frame
+ * goes to the workspace, nothing of the spectrum does.  One launch gathers, a thread per sample and GVX_DENOISE_GATHER_SAMPLES per
+ * workgroup, the at most ceil(n_fft / hop) frames that cover the sample, in ascending frame order for both sums, and writes the zeros
+ * behind n_b.  No atomics: two calls give the same bits, and a ragged row is the bits of its own one-row run. */
+enum { GVX_DENOISE_FRAMES_PER_WORKGROUP = 4, GVX_DENOISE_GATHER_SAMPLES = 256, GVX_DENOISE_MAX_ROWS = 65535, GVX_DENOISE_MAX_SAMPLES = 1 << 30 };
+typedef struct gvx_denoise_plan gvx_denoise_plan;
+int gvx_denoise_create(int n_fft, int hop, gvx_denoise_plan** out);
+void gvx_denoise_destroy(gvx_denoise_plan* plan);
+size_t gvx_denoise_workspace_bytes(const gvx_denoise_plan* plan, int B, long n_max);
+int gvx_denoise(gvx_denoise_plan* plan, const float* wav, const int32_t* sample_lengths, int B, long n_max, const float* bias, float strength,
+                float* out, float* mag_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Per-kernel timing of the decoder step (measurement only): when enabled, a teacher-forced call replays the
  * mid-sequence LSTM-step launch and the attention launches 64 times each, back to back, between HIP events on
  * `stream` (after its loop; the call's outputs are not valid afterwards); gvx_kernel_times_ms synchronises and

@@ -18,6 +18,9 @@ with torch.stft + autograd on the same device, with the workspace's size;
 `melloss` (on request): the mel-spectrogram L1 loss, value + gradient (MelSpectrogramLoss + `backward()`: one gvx_mel_loss call), with the
 published parameters (1024 / 256 / 1024, 80 mels to Nyquist) at the `mrstft` shapes between device events, median of 7, against the same
 per-row loss written with torch.stft, a matmul and autograd on the same device, with the workspace's size;
+`denoise` (on request): the vocoder denoiser (Denoiser.forward: one gvx_denoise call, two launches) at 1024 / 256 at the `mrstft` shapes,
+200 calls per window between device events, the windows of the two sides alternating, median and range of 7, against the same
+definition through torch.stft / torch.istft on the same device, with the largest difference between the two and the workspace's size;
 `melgan_disc` (on request): the MelGAN discriminator at 16 x 8192 and 8 x 32768 samples (the `mrstft` shapes) between device events,
 median of 7 with the spread: forward, forward + full backward (cotangents on every map), and the whole `MelGANTrainer.train_step` with
 the default generator, against the same discriminator built from torch.nn modules that hold the same (seeded) parameters, through
@@ -491,6 +494,52 @@ def main():
             res[key]["relative_loss_difference_from_torch"] = abs(got_loss - float(torch_loss(pred, target))) / got_loss
             res[key]["max_relative_gradient_difference_from_torch"] = float((got - pred.grad).abs().max() / pred.grad.abs().max())
             res[key]["workspace_mb"] = round(crit._workspace.numel() / 1e6, 1)
+            print(json.dumps({key: res[key]}), flush=True)
+    if "denoise" in which:
+        import statistics
+
+        from genvox_amd.denoiser import Denoiser
+
+        n_fft, hop, strength, inner = 1024, 256, 0.5, 200
+        gen = torch.Generator(device="cuda").manual_seed(0)
+        bias = torch.rand(n_fft // 2 + 1, device="cuda", generator=gen) * 20.0   # around the magnitudes of 0.3-sigma noise: part of the bins clamp
+        dn = Denoiser(bias, n_fft, hop, strength).to("cuda")
+        window = torch.hann_window(n_fft, periodic=True, device="cuda")
+
+        def torch_denoise(x):   # the header's definition on rows of full length
+            X = torch.stft(x, n_fft, hop, n_fft, window, center=True, pad_mode="reflect", return_complex=True)
+            M = torch.sqrt(X.real ** 2 + X.imag ** 2)
+            live = M > 0
+            g = torch.where(live, torch.clamp(M - strength * bias[None, :, None], min=0.0) / torch.where(live, M, torch.ones_like(M)), torch.zeros_like(M))
+            return torch.istft(X * g, n_fft, hop, n_fft, window, center=True, length=x.shape[1])
+
+        def window_ms(fn):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(inner):
+                fn()
+            e1.record()
+            e1.synchronize()
+            return e0.elapsed_time(e1) / inner
+
+        def stats(out):
+            return {"median_ms": round(statistics.median(out), 4), "min_ms": round(min(out), 4), "max_ms": round(max(out), 4), "runs": len(out),
+                    "calls_per_run": inner}
+
+        for B, n in ((16, 8192), (8, 32768)):
+            key = f"denoise_{B}x{n}"
+            wav = 0.3 * torch.randn(B, n, device="cuda", generator=gen)
+            with torch.no_grad():
+                for _ in range(3):   # warm both sides at this shape
+                    got, want = dn(wav), torch_denoise(wav)
+                ours, theirs = [], []
+                for _ in range(7):   # the two sides alternate, so that what else runs on the machine meets both
+                    ours.append(window_ms(lambda: dn(wav)))
+                    theirs.append(window_ms(lambda: torch_denoise(wav)))
+                clamped = float(((torch.stft(wav, n_fft, hop, n_fft, window, return_complex=True).abs() <= strength * bias[None, :, None])).float().mean())
+            res[key] = {"gvx_denoise": stats(ours), "torch_stft_istft": stats(theirs),
+                        "max_abs_difference_from_torch": float((got - want).abs().max()), "max_abs_output": float(want.abs().max()),
+                        "clamped_fraction": round(clamped, 3), "workspace_mb": round(dn._workspace.numel() / 1e6, 1)}
             print(json.dumps({key: res[key]}), flush=True)
     if "melgan_disc" in which:
         import statistics
