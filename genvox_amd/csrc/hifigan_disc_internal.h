@@ -1,19 +1,13 @@
-// What the host side of csrc/hifigan_disc.hip is built from: the layer table of one period discriminator, the dims check, the height
-// arithmetic that host and kernels share, and the layouts of the blob, the features buffer and the backward's workspace.  Host
-// arithmetic only, so that a stand-alone program can check it without a device.
+// What the host side of csrc/hifigan_disc.hip is built from: the layer table of one period discriminator, the dims check, and the
+// layouts of the blob, the features buffer and the backward's workspace; the height arithmetic that host and kernels share is
+// disc_conv.h's.  Host arithmetic only, so that a stand-alone program can check it without a device.
 #pragma once
 #include "../../include/genvox_amd.h"
-
-#include <cstddef>
-#include <cstdint>
-
-#if defined(__HIPCC__)
-#define PD_HD __host__ __device__
-#else
-#define PD_HD
-#endif
+#include "disc_conv.h"
 
 namespace gvx_pd {
+
+using namespace gvx_dc;
 
 // Tile constants (the public header repeats them as GVX_HIFIGAN_MPD_*): every convolution kernel - matrix or VALU, forward or data
 // gradient - gives a workgroup PD_TILE positions (h, column) of one row; the data gradient's positions are those of ONE stride phase.
@@ -22,27 +16,15 @@ constexpr int PD_TILE_N = 64;      // output channels per workgroup: the VALU ke
 constexpr int PD_TILE_N_WIDE = 128;   // output channels per workgroup of the matrix kernels from 128 output channels on
 constexpr int PD_MFMA_MULT = 32;   // a layer runs on the matrix instruction when both channel counts are multiples of this
 constexpr int PD_WG_CHUNK = 32;    // positions per k-step of the matrix weight-gradient kernel
-constexpr int PD_DB_SLICES = 64;   // slices of the bias-gradient sum, added in their order
 constexpr int PD_MAX_MAPS = GVX_HIFIGAN_MPD_MAX_LAYERS + 1;
-constexpr int PD_PART_FLOATS = 1 << 24;   // the weight-gradient partials of one layer stay below this many floats where the rows allow it
+static_assert(PD_TILE == DC_TILE && PD_TILE_N == DC_TILE_N && PD_MAX_MAPS == DC_MAX_MAPS, "the shared kernels' constants");
 
 struct PdLayer {
     int cin, cout, k, stride, pad;
-    int down_in, down_out;   // how many strided layers lie in front of the input / the output
     int act, mfma;
     size_t wf_off, wb_off, b_off;   // floats, inside one period's part of the blob: W as [cout][k][cin], as [cin][k][cout], the bias
+    size_t wn() const { return (size_t)cout * cin * k; }
 };
-
-// height of a row of n samples on the period-p grid after `down` strided layers (0 stays 0: a refused row is silent)
-PD_HD inline int pd_height(int n, int period, int s, int down) {
-    if (n <= 0) return 0;
-    int h = (n + period - 1) / period;
-    for (int i = 0; i < down; ++i) h = (h - 1) / s + 1;
-    return h;
-}
-
-inline size_t pd_round64(size_t floats) { return (floats + 63) & ~(size_t)63; }
-inline size_t pd_round256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
 inline int pd_min_samples(const gvx_hifigan_mpd_dims& d) {
     int m = 1;
@@ -71,23 +53,27 @@ inline const char* pd_dims_problem(const gvx_hifigan_mpd_dims* d) {
 inline int pd_layers(const gvx_hifigan_mpd_dims& d, PdLayer* L, size_t* floats_out = nullptr, size_t* params_out = nullptr) {
     size_t at = 0, params = 0;
     int n = 0, cin = 1;
-    auto add = [&](int ci, int co, int k, int stride, int down_in, int down_out, int act) {
+    auto add = [&](int ci, int co, int k, int stride, int act) {
         PdLayer& l = L[n++];
-        l = PdLayer{ci, co, k, stride, k / 2, down_in, down_out, act, (ci % PD_MFMA_MULT == 0 && co % PD_MFMA_MULT == 0) ? 1 : 0, 0, 0, 0};
-        l.wf_off = at; at += pd_round64((size_t)co * ci * k);
-        l.wb_off = at; at += pd_round64((size_t)co * ci * k);
-        l.b_off = at; at += pd_round64((size_t)co);
-        params += (size_t)co * ci * k + co;
+        l = PdLayer{ci, co, k, stride, k / 2, act, (ci % PD_MFMA_MULT == 0 && co % PD_MFMA_MULT == 0) ? 1 : 0, 0, 0, 0};
+        l.wf_off = at; at += dc_round64(l.wn());
+        l.wb_off = at; at += dc_round64(l.wn());
+        l.b_off = at; at += dc_round64((size_t)co);
+        params += l.wn() + co;
     };
     for (int i = 0; i < d.n_layers; ++i) {
-        const bool last = i == d.n_layers - 1;
-        add(cin, d.channels[i], d.kernel_size, last ? 1 : d.stride, i, last ? i : i + 1, 1);
+        add(cin, d.channels[i], d.kernel_size, i == d.n_layers - 1 ? 1 : d.stride, 1);   // the last convolution keeps the height
         cin = d.channels[i];
     }
-    add(cin, 1, 3, 1, d.n_layers - 1, d.n_layers - 1, 0);
+    add(cin, 1, 3, 1, 0);
     if (floats_out) *floats_out = at;
     if (params_out) *params_out = params;
     return n;
+}
+
+// the strides in front of map i's height: those of layers 0 .. i
+inline void pd_strides(const gvx_hifigan_mpd_dims& d, int* str) {
+    for (int i = 0; i < PD_MAX_MAPS; ++i) str[i] = i < d.n_layers - 1 ? d.stride : 1;
 }
 
 struct PdFeat {   // the features buffer: map (period j, layer i) is [B][height][period][channels] at byte `off`
@@ -101,30 +87,30 @@ struct PdFeat {   // the features buffer: map (period j, layer i) is [B][height]
 inline PdFeat pd_feat_layout(const gvx_hifigan_mpd_dims& d, int B, int n_max) {
     PdFeat F{};
     PdLayer L[PD_MAX_MAPS];
+    int str[PD_MAX_MAPS];
     F.n_maps = pd_layers(d, L);
+    pd_strides(d, str);
     size_t at = 0;
     for (int j = 0; j < d.n_periods; ++j)
         for (int i = 0; i < F.n_maps; ++i) {
             F.channels[i] = L[i].cout;
-            F.height[j][i] = pd_height(n_max, d.periods[j], d.stride, L[i].down_out);
+            F.height[j][i] = dc_length(n_max, d.periods[j], str, i + 1);
             F.off[j][i] = at;
-            at += pd_round256((size_t)B * F.height[j][i] * d.periods[j] * L[i].cout * sizeof(float));
+            at += dc_round256((size_t)B * F.height[j][i] * d.periods[j] * L[i].cout * sizeof(float));
         }
     F.total = at;
     return F;
 }
 
-// pieces of one layer's weight gradient: rows are dealt `rows_per_piece` to a piece, or a row is cut into `chunks` runs of positions
-struct PdPieces { int chunks, rows_per_piece, n, run; size_t numel; };
-
-inline PdPieces pd_pieces(const PdLayer& l, int B, int positions) {
-    PdPieces P{};
-    P.numel = (size_t)l.cout * l.cin * l.k;
+// the pieces of one layer's weight gradient
+inline DcPieces pd_pieces(const PdLayer& l, int B, int positions) {
+    DcPieces P{};
+    P.numel = l.wn();
     const size_t out_blocks = l.mfma ? (size_t)((l.cout + 63) / 64) * ((l.cin + 63) / 64) * l.k : (P.numel + 255) / 256;
     // about 1024 workgroups per launch; the VALU kernel walks its run one position at a time, so it gets four times as many, shorter runs
     const size_t target = l.mfma ? 1024 : 4096, shortest = l.mfma ? 4 * PD_WG_CHUNK : PD_WG_CHUNK;
     size_t want = (target + out_blocks - 1) / out_blocks;
-    const size_t cap = PD_PART_FLOATS / P.numel ? PD_PART_FLOATS / P.numel : 1;
+    const size_t cap = DC_PART_FLOATS / P.numel ? DC_PART_FLOATS / P.numel : 1;
     if (want > cap) want = cap;
     if (want >= (size_t)B) {
         size_t chunks = (want + B - 1) / B, most = ((size_t)positions + shortest - 1) / shortest;
@@ -139,34 +125,23 @@ inline PdPieces pd_pieces(const PdLayer& l, int B, int positions) {
     return P;
 }
 
-struct PdWs {   // byte offsets (backward only; the forward needs no scratch)
-    size_t grad[2];    // two activation gradients of the largest map, the layers alternate
-    size_t parts;      // partial weight gradients
-    size_t db_parts;   // partial bias gradients, float64
-    size_t total;
-};
+struct PdWs : DcWs { size_t total; };   // byte offsets (backward only; the forward needs no scratch)
 
 inline PdWs pd_ws_plan(const gvx_hifigan_mpd_dims& d, int B, int n_max, bool backward) {
     PdWs W{};
     size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += pd_round256(bytes); return o; };
+    auto take = [&](size_t bytes) { const size_t o = at; at += dc_round256(bytes); return o; };
     if (backward) {
         PdLayer L[PD_MAX_MAPS];
         const int nl = pd_layers(d, L);
-        size_t act = 0, parts = 0, cmax = 1;
+        const PdFeat F = pd_feat_layout(d, B, n_max);
+        DcWsNeed need;
         for (int j = 0; j < d.n_periods; ++j)
             for (int i = 0; i < nl; ++i) {
-                const int pos = pd_height(n_max, d.periods[j], d.stride, L[i].down_out) * d.periods[j];
-                const size_t a = (size_t)B * L[i].cout * pos;
-                if (i < nl - 1 && a > act) act = a;
-                const PdPieces P = pd_pieces(L[i], B, pos);
-                if (P.n * P.numel > parts) parts = P.n * P.numel;
-                if ((size_t)L[i].cout > cmax) cmax = L[i].cout;
+                const int pos = F.height[j][i] * d.periods[j];
+                need.layer(B, L[i].cout, pos, i == nl - 1, pd_pieces(L[i], B, pos));
             }
-        W.grad[0] = take(act * sizeof(float));
-        W.grad[1] = take(act * sizeof(float));
-        W.parts = take(parts * sizeof(float));
-        W.db_parts = take(PD_DB_SLICES * cmax * sizeof(double));
+        static_cast<DcWs&>(W) = need.place(take);
     }
     W.total = at < 256 ? 256 : at;
     return W;

@@ -1,55 +1,31 @@
-// What the host side of csrc/hifigan_msd.hip is built from: the layer table of one scale discriminator, the dims check, the length
-// arithmetic that host and kernels share, and the layouts of the blob, the features buffer and the workspaces.  Host arithmetic only,
-// so that a stand-alone program can check it without a device.
+// What the host side of csrc/hifigan_msd.hip is built from: the layer table of one scale discriminator, the dims check, and the
+// layouts of the blob, the features buffer and the workspaces; the length arithmetic that host and kernels share is disc_conv.h's.
+// Host arithmetic only, so that a stand-alone program can check it without a device.
 #pragma once
 #include "../../include/genvox_amd.h"
-
-#include <cstddef>
-#include <cstdint>
-
-#if defined(__HIPCC__)
-#define SD_HD __host__ __device__
-#else
-#define SD_HD
-#endif
+#include "disc_conv.h"
 
 namespace gvx_sd {
 
+using namespace gvx_dc;
+
 // Tile constants (the public header repeats them as GVX_HIFIGAN_MSD_*)
 constexpr int SD_TILE = 64;          // positions per workgroup, every convolution kernel; a data gradient's are those of ONE stride phase
-constexpr int SD_TILE_N = 64;        // output channels per workgroup of the VALU kernels
 constexpr int SD_MFMA_IN = 8;        // a layer runs on the matrix instruction when its per-group input channels are a multiple of this
 constexpr int SD_MFMA_OUT = 16;      // ... and its per-group output channels a multiple of this
 constexpr int SD_WG_RUN = 256;       // positions per piece of a weight gradient where a row is cut into runs
 constexpr int SD_WG_ALIGN = 32;      // a longer run (the partials' cap) is a multiple of this
-constexpr int SD_DB_SLICES = 64;     // slices of the bias-gradient sum, added in their order
 constexpr int SD_MAX_MAPS = GVX_HIFIGAN_MSD_MAX_LAYERS + 1;
-constexpr int SD_PART_FLOATS = 1 << 24;   // the weight-gradient partials of one layer stay below this many floats where the rows allow it
 constexpr int SD_MAX_PIECES = 32768;
 constexpr int SD_WIN_BYTES = 48 * 1024;   // the LDS window of the matrix kernels stays below this
+static_assert(SD_TILE == DC_TILE && SD_MAX_MAPS == DC_MAX_MAPS, "the shared kernels' constants");
 
 struct SdLayer {
     int cin, cout, k, stride, pad, groups;
     int act, mfma;           // mfma: 0 VALU, 32 the 32x32x2 instruction, 16 the 16x16x4 instruction
     size_t wf_off, wb_off, b_off;   // floats, inside one scale's part of the blob
+    size_t wn() const { return (size_t)cout * (cin / groups) * k; }
 };
-
-// samples of a row at scale s (0 stays 0: a refused row is silent)
-SD_HD inline int sd_scale_n(int n, int s) {
-    if (n <= 0) return 0;
-    for (int i = 0; i < s; ++i) n = n / 2 + 1;
-    return n;
-}
-
-// length of a row of n samples (of its scale) after the layers whose strides are str[0 .. count)
-SD_HD inline int sd_length(int n, const int* str, int count) {
-    if (n <= 0) return 0;
-    for (int i = 0; i < count; ++i) n = (n - 1) / str[i] + 1;
-    return n;
-}
-
-inline size_t sd_round64(size_t floats) { return (floats + 63) & ~(size_t)63; }
-inline size_t sd_round256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
 inline const char* sd_dims_problem(const gvx_hifigan_msd_dims* d) {
     if (!d) return "null dims";
@@ -80,11 +56,10 @@ inline int sd_layers(const gvx_hifigan_msd_dims& d, SdLayer* L, size_t* floats_o
     auto add = [&](int ci, int co, int k, int stride, int groups, int act) {
         SdLayer& l = L[n++];
         l = SdLayer{ci, co, k, stride, k / 2, groups, act, sd_mfma_kind(ci / groups, co / groups), 0, 0, 0};
-        const size_t wn = (size_t)co * (ci / groups) * k;
-        l.wf_off = at; at += sd_round64(wn);
-        l.wb_off = at; at += sd_round64(wn);
-        l.b_off = at; at += sd_round64((size_t)co);
-        params += wn + co;
+        l.wf_off = at; at += dc_round64(l.wn());
+        l.wb_off = at; at += dc_round64(l.wn());
+        l.b_off = at; at += dc_round64((size_t)co);
+        params += l.wn() + co;
     };
     for (int i = 0; i < d.n_layers; ++i) {
         add(cin, d.channels[i], d.kernel_sizes[i], d.strides[i], d.groups[i], 1);
@@ -118,25 +93,23 @@ inline SdFeat sd_feat_layout(const gvx_hifigan_msd_dims& d, int B, int n_max) {
     sd_strides(d, str);
     size_t at = 0;
     for (int s = 0; s < d.n_scales; ++s) {
-        F.n_scale[s] = sd_scale_n(n_max, s);
+        F.n_scale[s] = dc_samples(n_max, 1, s);
         for (int i = 0; i < F.n_maps; ++i) {
             F.channels[i] = L[i].cout;
-            F.length[s][i] = sd_length(F.n_scale[s], str, i + 1);
+            F.length[s][i] = dc_length(F.n_scale[s], 1, str, i + 1);
             F.off[s][i] = at;
-            at += sd_round256((size_t)B * F.length[s][i] * L[i].cout * sizeof(float));
+            at += dc_round256((size_t)B * F.length[s][i] * L[i].cout * sizeof(float));
         }
     }
     F.total = at;
     return F;
 }
 
-// pieces of one layer's weight gradient: rows are dealt `rows_per_piece` to a piece, or a row is cut into `chunks` runs of positions
-struct SdPieces { int chunks, rows_per_piece, n, run; size_t numel; };
-
-inline SdPieces sd_pieces(const SdLayer& l, int B, int positions) {
-    SdPieces P{};
-    P.numel = (size_t)l.cout * (l.cin / l.groups) * l.k;
-    size_t cap = SD_PART_FLOATS / P.numel ? SD_PART_FLOATS / P.numel : 1;
+// the pieces of one layer's weight gradient
+inline DcPieces sd_pieces(const SdLayer& l, int B, int positions) {
+    DcPieces P{};
+    P.numel = l.wn();
+    size_t cap = DC_PART_FLOATS / P.numel ? DC_PART_FLOATS / P.numel : 1;
     if (cap > (size_t)SD_MAX_PIECES) cap = SD_MAX_PIECES;
     if (cap >= (size_t)B) {
         const size_t most = cap / B, want = ((size_t)positions + SD_WG_RUN - 1) / SD_WG_RUN;
@@ -175,38 +148,26 @@ inline SdWin sd_window(int kg, int k, int stride, bool backward) {
     return w;
 }
 
-struct SdWs {   // byte offsets
+struct SdWs : DcWs {   // byte offsets
     size_t pooled[GVX_HIFIGAN_MSD_MAX_SCALES];   // the waveform of scales 1 .., [B][n_scale]
     size_t dpool[GVX_HIFIGAN_MSD_MAX_SCALES];    // backward: the waveform gradient of scales 1 ..
-    size_t grad[2];    // backward: two activation gradients of the largest map, the layers alternate
-    size_t parts;      // partial weight gradients
-    size_t db_parts;   // partial bias gradients, float64
     size_t total;
 };
 
 inline SdWs sd_ws_plan(const gvx_hifigan_msd_dims& d, int B, int n_max, bool backward) {
     SdWs W{};
     size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += sd_round256(bytes); return o; };
+    auto take = [&](size_t bytes) { const size_t o = at; at += dc_round256(bytes); return o; };
     const SdFeat F = sd_feat_layout(d, B, n_max);
     for (int s = 1; s < d.n_scales; ++s) W.pooled[s] = take((size_t)B * F.n_scale[s] * sizeof(float));
     if (backward) {
         for (int s = 1; s < d.n_scales; ++s) W.dpool[s] = take((size_t)B * F.n_scale[s] * sizeof(float));
         SdLayer L[SD_MAX_MAPS];
         const int nl = sd_layers(d, L);
-        size_t act = 0, parts = 0, cmax = 1;
+        DcWsNeed need;
         for (int s = 0; s < d.n_scales; ++s)
-            for (int i = 0; i < nl; ++i) {
-                const size_t a = (size_t)B * L[i].cout * F.length[s][i];
-                if (i < nl - 1 && a > act) act = a;
-                const SdPieces P = sd_pieces(L[i], B, F.length[s][i]);
-                if (P.n * P.numel > parts) parts = P.n * P.numel;
-                if ((size_t)L[i].cout > cmax) cmax = L[i].cout;
-            }
-        W.grad[0] = take(act * sizeof(float));
-        W.grad[1] = take(act * sizeof(float));
-        W.parts = take(parts * sizeof(float));
-        W.db_parts = take(SD_DB_SLICES * cmax * sizeof(double));
+            for (int i = 0; i < nl; ++i) need.layer(B, L[i].cout, F.length[s][i], i == nl - 1, sd_pieces(L[i], B, F.length[s][i]));
+        static_cast<DcWs&>(W) = need.place(take);
     }
     W.total = at < 256 ? 256 : at;
     return W;

@@ -111,7 +111,6 @@ inline MgBlob mg_blob_layout(const gvx_melgan_dims& d) {
 // defined in melgan.hip
 int mg_launch(const MgLayer& p, int B, hipStream_t s);   // one layer of the forward
 int mg_mel_transpose(const float* mel, const int32_t* lens, int B, int M, int T, int Cp, float* out, hipStream_t s);
-int mg_prepare(gvx_melgan* h);   // once per handle: the dynamic LDS size of the widest tile
-const gvx_weight_desc* mg_find(const gvx_weight_desc* table, int n, const std::string& name, size_t numel, int& rc);
+int mg_prepare(gvx_melgan* h);   // once per handle: the dynamic LDS size of the widest tile (mg_find: gvx_internal.h)
 
 }  // namespace gvx_mg
