@@ -50,9 +50,19 @@ __device__ __forceinline__ long row_off(const RowMap& m, int row) {
     return (long)(row / m.R) * m.s1 + (long)(row % m.R) * m.s0;
 }
 
+// What follows the products is chosen on the host (epilogue_kind) and compiled in: a path that a launch does not take does not
+// exist in the kernel it runs.
+//   EPI_PLAIN    C = acc                          (the Winograd products, pre_gate, the memory projection, split-K partials)
+//   EPI_BIAS     C = acc + bias[n]                (the LSTM input GEMM, the mel / gate projection, the last Postnet layer)
+//   EPI_GENERAL  bias, activation, keep mask, row_len zeros and halo rows, each decided at run time (everything else)
+//   EPI_PARENT   the epilogue all launches had before the kinds, kept word for word (a division pair per row, every load
+//                behind its own wait): gvx_debug_gemm_parent_epilogue / GVX_GEMM_EPILOGUE=parent select it for tests and A/B runs
+// All four store the same values to the same addresses.
+enum Epi : int { EPI_PARENT = 0, EPI_GENERAL = 1, EPI_PLAIN = 2, EPI_BIAS = 3 };
+
 // KMAJ: both operands are K-major - element (m, k) of A at A + amap(k) + m, element (n, k) of W at W + wmap(k) + n - the
 // form of a weight gradient (sum over the rows of two activation matrices) without transposed copies.
-template <int WR, int WC, int TM, int TN, bool KMAJ = false, int BK = BK32>
+template <int WR, int WC, int TM, int TN, bool KMAJ = false, int BK = BK32, int EPI = EPI_GENERAL>
 __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int block_x, const int tid, float* smem) {
     constexpr int LDS_LD = BK + 4;   // 36 / 68 floats: see the header
     static_assert(BK == 32 || (BK == 64 && !KMAJ), "k-tiles of 32, or 64 for the row-major form");
@@ -239,6 +249,34 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int blo
         GEMM_STORE_TILE(cur ^ 1, k_begin + (kt + 1) * BK)
         __syncthreads();
     }
+    // What the epilogue needs besides the accumulators is fetched here, in front of the last tile's products, so that the MFMAs
+    // cover the latency of the loads and the one division per M tile: bias[n] (the lane's TN columns; n does not depend on the
+    // row), the place of the lane's first row of each M tile under cmap, and row_len of the groups the wave's 32 rows of an M tile
+    // touch - at most 32 consecutive groups (R >= 1), lane l holds the one of group grp_w + (l & 31), and a row reads its own with
+    // a cross-lane move.
+    constexpr bool EPI_GEN = EPI == EPI_GENERAL;
+    float bias_v[TN];
+    RowWalk walk0[TM];
+    int len_v[TM], grp_w[TM];
+    if constexpr (EPI != EPI_PARENT) {
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const int n = n0 + (wc * TN + j) * 32 + r;
+            bias_v[j] = 0.f;
+            if constexpr (EPI == EPI_BIAS) { if (n < p.N) bias_v[j] = p.bias[n]; }
+            if constexpr (EPI_GEN) { if (p.bias && n < p.N) bias_v[j] = p.bias[n]; }
+        }
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            walk0[i] = row_walk_begin(p.cmap, m0 + (wr * TM + i) * 32 + 4 * h);
+            len_v[i] = 0; grp_w[i] = 0;
+            if constexpr (EPI_GEN) {
+                grp_w[i] = __builtin_amdgcn_readfirstlane(walk0[i].grp);   // lane 0: h = 0, the M tile's first row
+                const int g = grp_w[i] + r;
+                if (p.row_len && (long)g * p.cmap.R < p.M) len_v[i] = p.row_len[g];
+            }
+        }
+    }
     GEMM_COMPUTE_TILE(kt & 1)               // last tile
 #undef GEMM_LOAD_TILE
 #undef GEMM_KMAJ_LOAD
@@ -248,6 +286,67 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int blo
 #undef GEMM_COMPUTE_KGS
 
     // epilogue: D[row][col] with col = lane&31, row = (q&3) + 8*(q>>2) + 4*(lane>>5)
+    if constexpr (EPI != EPI_PARENT) {
+        // the lane's columns: where they lie in a row of C, once
+        float* c_col[TN]; bool n_ok[TN];
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const int n = n0 + (wc * TN + j) * 32 + r;
+            n_ok[j] = n < p.N;
+            c_col[j] = Cout + (long)(n >> 3) * p.c_nblk + (n & 7);
+        }
+        const bool has_bias = EPI_GEN && p.bias, has_len = EPI_GEN && p.row_len, has_halo = EPI_GEN && p.c_halo > 0;
+        const long halo_step = EPI_GEN ? (long)p.c_halo * p.cmap.s0 : 0;
+        // The hoisted loads are waited for ONCE, here, in straight-line code and by hand.  Left to the compiler, their first use
+        // lies inside one of the row loop's predicated blocks (it sinks the bias additions below into them), the load still
+        // counts as pending on the path around the block, and so EVERY such block got an s_waitcnt vmcnt(0) - which there waits
+        // for all the stores before it.
+        if constexpr (EPI != EPI_PLAIN) __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0) alone: the expcnt and lgkmcnt fields at their maxima
+        if (EPI == EPI_BIAS || has_bias) {
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+#pragma unroll
+                    for (int q = 0; q < 16; ++q) acc[i][j][q] += bias_v[j];
+        }
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            RowWalk w = walk0[i];
+            const int m_first = m0 + (wr * TM + i) * 32 + 4 * h;
+            const uint8_t* keep_row = EPI_GEN && p.keep ? p.keep + (long)m_first * p.keep_ld + n0 + wc * TN * 32 + r : nullptr;
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                if (q > 0) {
+                    row_walk_advance(w, p.cmap, mfma32_row_step(q));
+                    if (EPI_GEN && p.keep) keep_row += mfma32_row_step(q) * p.keep_ld;
+                }
+                const bool m_ok = m_first + (q & 3) + 8 * (q >> 2) < p.M;
+                bool live = true, halo_front = false, halo_back = false;
+                if constexpr (EPI_GEN) {
+                    // (every lane takes part in the cross-lane move: no row has left the loop, rows past M only skip their stores)
+                    if (has_len) live = w.idx < __shfl(len_v[i], w.grp - grp_w[i]);
+                    // conv output with halo rows: the first / last c_halo interior rows of a sequence also zero one halo row each
+                    halo_front = has_halo && w.idx < p.c_halo;
+                    halo_back = has_halo && w.idx >= p.cmap.R - p.c_halo;
+                }
+#pragma unroll
+                for (int j = 0; j < TN; ++j) {
+                    if (!(m_ok && n_ok[j])) continue;
+                    float v = acc[i][j][q];   // (+ bias: above)
+                    if constexpr (EPI_GEN) {
+                        if (p.act == ACT_RELU) v = fmaxf(v, 0.f);
+                        else if (p.act == ACT_TANH) v = tanhf(v);
+                        if (p.keep) v = keep_row[j * 32] ? 2.f * v : 0.f;
+                    }
+                    c_col[j][w.off] = live ? v : 0.f;
+                    if (halo_front) c_col[j][w.off - halo_step] = 0.f;
+                    if (halo_back) c_col[j][w.off + halo_step] = 0.f;
+                }
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
 #pragma unroll
@@ -279,47 +378,87 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int blo
     }
 }
 
-template <int WR, int WC, int TM, int TN, bool KMAJ = false, int BK = BK32>
+template <int WR, int WC, int TM, int TN, bool KMAJ = false, int BK = BK32, int EPI = EPI_GENERAL>
 __global__ __launch_bounds__(WR * WC * 64) void gemm_f32_kernel(GemmParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    gemm_f32_body<WR, WC, TM, TN, KMAJ, BK>(p, (int)blockIdx.x, (int)threadIdx.x, smem);
+    gemm_f32_body<WR, WC, TM, TN, KMAJ, BK, EPI>(p, (int)blockIdx.x, (int)threadIdx.x, smem);
 }
 
 template <int WR, int WC, int TM, int TN, int BK = BK32>
 static size_t lds_bytes_cfg() { return (size_t)2 * (WR * TM * 32 + WC * TN * 32) * (BK + 4) * sizeof(float); }
 
-template <int WR, int WC, int TM, int TN, bool KMAJ = false, int BK = BK32>
+template <int WR, int WC, int TM, int TN, bool KMAJ, int EPI>
 static hipError_t init_cfg() {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f32_kernel<WR, WC, TM, TN, KMAJ, BK>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes_cfg<WR, WC, TM, TN, BK>());
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f32_kernel<WR, WC, TM, TN, KMAJ, BK32, EPI>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes_cfg<WR, WC, TM, TN>());
 }
 
-hipError_t gemm_init() {
-    hipError_t e = init_cfg<2, 2, 2, 2>();
-    if (e != hipSuccess) return e;
-    e = init_cfg<2, 2, 1, 2>();
-    if (e != hipSuccess) return e;
-    e = init_cfg<4, 1, 1, 3>();
-    if (e != hipSuccess) return e;
-    e = init_cfg<2, 3, 1, 1>();
-    if (e != hipSuccess) return e;
-    e = init_cfg<4, 2, 1, 2>();
-    if (e != hipSuccess) return e;
-    e = init_cfg<2, 2, 1, 1>();
-    if (e != hipSuccess) return e;
-    e = init_cfg<2, 2, 2, 2, true>();
-    if (e != hipSuccess) return e;
-    e = init_cfg<2, 2, 1, 2, true>();
-    if (e != hipSuccess) return e;
-    return init_cfg<4, 1, 1, 1>();
-}
-
-template <int WR, int WC, int TM, int TN, bool KMAJ = false, int BK = BK32>
+template <int WR, int WC, int TM, int TN, bool KMAJ, int EPI>
 static hipError_t launch_cfg(const GemmParams& p, hipStream_t s) {
     constexpr int BM = WR * TM * 32, BN = WC * TN * 32;
     const int grid = ((p.M - p.m_begin + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-    gemm_f32_kernel<WR, WC, TM, TN, KMAJ, BK><<<dim3(grid, p.splitk > 1 ? p.splitk : p.slices > 1 ? p.slices : 1), dim3(WR * WC * 64), lds_bytes_cfg<WR, WC, TM, TN, BK>(), s>>>(p);
+    gemm_f32_kernel<WR, WC, TM, TN, KMAJ, BK32, EPI><<<dim3(grid, p.splitk > 1 ? p.splitk : p.slices > 1 ? p.slices : 1), dim3(WR * WC * 64), lds_bytes_cfg<WR, WC, TM, TN>(), s>>>(p);
     return hipGetLastError();
+}
+
+// Every instantiation there is: X(tile digits, WR, WC, TM, TN, KMAJ, special kinds).  EPI_GENERAL and EPI_PARENT exist for each
+// shape; EPI_PLAIN and EPI_BIAS only where the forward launches them (a bit per kind) - the Winograd products on the three
+// square-ish row-major tiles, bias-only products on those and on the two N <= 96 tiles (the mel / gate projection).  A launch of
+// a special kind on a shape without it takes EPI_GENERAL: the same stores, with the run-time checks.
+constexpr int KIND_PLAIN = 1 << EPI_PLAIN, KIND_BIAS = 1 << EPI_BIAS;
+#define GVX_GEMM_SHAPES(X)                            \
+    X(4111, 4, 1, 1, 1, false, 0)                     \
+    X(2311, 2, 3, 1, 1, false, KIND_BIAS)             \
+    X(4113, 4, 1, 1, 3, false, KIND_BIAS)             \
+    X(2211, 2, 2, 1, 1, false, KIND_PLAIN | KIND_BIAS) \
+    X(2212, 2, 2, 1, 2, false, KIND_PLAIN | KIND_BIAS) \
+    X(2222, 2, 2, 2, 2, false, 0)                     \
+    X(4212, 4, 2, 1, 2, false, KIND_PLAIN | KIND_BIAS) \
+    X(2212, 2, 2, 1, 2, true, 0)                      \
+    X(2222, 2, 2, 2, 2, true, 0)
+
+template <int WR, int WC, int TM, int TN, bool KMAJ, int KINDS>
+static hipError_t init_shape() {
+    hipError_t e = init_cfg<WR, WC, TM, TN, KMAJ, EPI_GENERAL>();
+    if (e == hipSuccess) e = init_cfg<WR, WC, TM, TN, KMAJ, EPI_PARENT>();
+    if constexpr ((KINDS & KIND_PLAIN) != 0) { if (e == hipSuccess) e = init_cfg<WR, WC, TM, TN, KMAJ, EPI_PLAIN>(); }
+    if constexpr ((KINDS & KIND_BIAS) != 0) { if (e == hipSuccess) e = init_cfg<WR, WC, TM, TN, KMAJ, EPI_BIAS>(); }
+    return e;
+}
+
+template <int WR, int WC, int TM, int TN, bool KMAJ, int KINDS>
+static hipError_t launch_shape(int epi, const GemmParams& p, hipStream_t s) {
+    if constexpr ((KINDS & KIND_PLAIN) != 0) { if (epi == EPI_PLAIN) return launch_cfg<WR, WC, TM, TN, KMAJ, EPI_PLAIN>(p, s); }
+    if constexpr ((KINDS & KIND_BIAS) != 0) { if (epi == EPI_BIAS) return launch_cfg<WR, WC, TM, TN, KMAJ, EPI_BIAS>(p, s); }
+    if (epi == EPI_PARENT) return launch_cfg<WR, WC, TM, TN, KMAJ, EPI_PARENT>(p, s);
+    return launch_cfg<WR, WC, TM, TN, KMAJ, EPI_GENERAL>(p, s);
+}
+
+hipError_t gemm_init() {
+#define GVX_GEMM_INIT(TILE, WR, WC, TM, TN, KMAJ, KINDS) \
+    if (const hipError_t e = init_shape<WR, WC, TM, TN, KMAJ, KINDS>(); e != hipSuccess) return e;
+    GVX_GEMM_SHAPES(GVX_GEMM_INIT)
+#undef GVX_GEMM_INIT
+    return hipSuccess;
+}
+
+// Every launch takes the parent's epilogue (EPI_PARENT) while this is set: GVX_GEMM_EPILOGUE=parent in the environment, or
+// gvx_debug_gemm_parent_epilogue at run time (tests and A/B runs compare the kinds inside one build)
+static bool& parent_epilogue() {
+    static bool on = [] { const char* e = std::getenv("GVX_GEMM_EPILOGUE"); return e && e[0] == 'p'; }();
+    return on;
+}
+int gemm_set_parent_epilogue(int on) {
+    const int was = parent_epilogue() ? 1 : 0;
+    if (on >= 0) parent_epilogue() = on != 0;
+    return was;
+}
+
+// The epilogue kind of a launch, from what its parameters ask for
+static int epilogue_kind(const GemmParams& p) {
+    if (parent_epilogue()) return EPI_PARENT;
+    if (p.act == ACT_RELU || p.act == ACT_TANH || p.keep || p.row_len || p.c_halo > 0) return EPI_GENERAL;
+    return p.bias ? EPI_BIAS : EPI_PLAIN;
 }
 
 // GVX_GEMM_8W=0 (A/B): the 128 x 128 tile on four waves of 64 x 64 instead of eight of 32 x 64
@@ -384,16 +523,24 @@ long gemm_round_rows(const GemmParams& p) {
     return 128 * (256 / a);
 }
 
+// ... and the kind that runs on tile shape `tile`: the one asked for where the shape has it, EPI_GENERAL otherwise (launch_tile
+// launches exactly this; gvx_debug_gemm_epilogue reports it)
+int gemm_epilogue_of(int tile, const GemmParams& p) {
+    const int want = epilogue_kind(p);
+    if (want != EPI_PLAIN && want != EPI_BIAS) return want;
+#define GVX_GEMM_HAS(TILE, WR, WC, TM, TN, KMAJ, KINDS) \
+    if (tile == TILE && p.kmajor == KMAJ) return ((KINDS) >> want) & 1 ? want : (int)EPI_GENERAL;
+    GVX_GEMM_SHAPES(GVX_GEMM_HAS)
+#undef GVX_GEMM_HAS
+    return EPI_GENERAL;
+}
+
 static hipError_t launch_tile(int tile, const GemmParams& p, hipStream_t s) {
-    switch (tile) {
-        case 4111: return launch_cfg<4, 1, 1, 1>(p, s);
-        case 2311: return launch_cfg<2, 3, 1, 1>(p, s);
-        case 4113: return launch_cfg<4, 1, 1, 3>(p, s);
-        case 2211: return launch_cfg<2, 2, 1, 1>(p, s);
-        case 2212: return p.kmajor ? launch_cfg<2, 2, 1, 2, true>(p, s) : launch_cfg<2, 2, 1, 2>(p, s);
-        case 2222: return p.kmajor ? launch_cfg<2, 2, 2, 2, true>(p, s) : launch_cfg<2, 2, 2, 2>(p, s);
-        case 4212: return launch_cfg<4, 2, 1, 2>(p, s);
-    }
+    const int epi = gemm_epilogue_of(tile, p);
+#define GVX_GEMM_LAUNCH(TILE, WR, WC, TM, TN, KMAJ, KINDS) \
+    if (tile == TILE && p.kmajor == KMAJ) return launch_shape<WR, WC, TM, TN, KMAJ, KINDS>(epi, p, s);
+    GVX_GEMM_SHAPES(GVX_GEMM_LAUNCH)
+#undef GVX_GEMM_LAUNCH
     return hipErrorInvalidValue;
 }
 

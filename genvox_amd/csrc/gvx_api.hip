@@ -32,6 +32,8 @@ hipError_t read_row_stamps_persist(unsigned long long* host512);
 #endif
 hipError_t skinny_init();
 hipError_t gemm_init();
+int gemm_set_parent_epilogue(int on);   // gemm_f32.hip: > 0 every launch takes EPI_PARENT, 0 the kinds, < 0 only asks; returns what it was
+int gemm_epilogue_of(int tile, const GemmParams& p);   // the epilogue kind (gemm_f32.hip's Epi) a launch of p on tile shape `tile` takes
 hipError_t attention_init();
 hipError_t attention_persistent_init();
 }  // namespace gvx
@@ -634,6 +636,38 @@ int gvx_debug_set_winograd_group(gvx_model* m, int tiles) {
 long gvx_debug_winograd_group_tiles(long total, long fit, int channels) {
     if (total < 1 || fit < 1 || channels < 4 || total > INT_MAX) return -1;
     return winograd_group_tiles(total, fit, channels);
+}
+
+// Host-only, for the tests and A/B runs (not in the public header; process-wide, like GVX_GEMM_8W): on > 0 makes every fp32
+// GEMM launch take the epilogue the kernels had before the compile-time kinds (EPI_PARENT), 0 switches back, < 0 only asks.
+// Returns the setting as it was.  Starts out as GVX_GEMM_EPILOGUE=parent in the environment says (unset: the kinds).
+int gvx_debug_gemm_parent_epilogue(int on) { return gemm_set_parent_epilogue(on); }
+
+// Host-only, for the tests (not in the public header; no device touched): the epilogue kind a launch on tile shape `tile` (four
+// digits, as gvx_debug_gemm_plan reports it) takes when its parameters ask for these extras - 0 the parent's epilogue (the
+// switch above), 1 general, 2 plain, 3 bias only; the function launch_gemm asks.  -1: a bad argument.
+int gvx_debug_gemm_epilogue(int tile, int kmajor, int has_bias, int act, int has_keep, int has_row_len, int c_halo) {
+    if (tile < 1111 || tile > 9999 || c_halo < 0) return -1;
+    static const float some_bias = 0.f; static const uint8_t some_keep = 0; static const int32_t some_len = 0;
+    GemmParams g{};
+    g.kmajor = kmajor != 0;
+    g.bias = has_bias ? &some_bias : nullptr; g.act = act;
+    g.keep = has_keep ? &some_keep : nullptr; g.row_len = has_row_len ? &some_len : nullptr; g.c_halo = c_halo;
+    return gemm_epilogue_of(tile, g);
+}
+
+// Host-only, for the tests (not in the public header; no device touched): the GEMM epilogue's row walk for one lane and M tile.
+// out row q (0..15) is the tile row first_row + (q & 3) + 8 * (q >> 2), reached as the kernel reaches it - row_walk_begin at
+// first_row, row_walk_advance by mfma32_row_step(q) from there: off[q], grp[q], idx[q] under the map (R, s1, s0).
+int gvx_debug_gemm_row_walk(int R, long s1, long s0, int first_row, long* off, int* grp, int* idx) {
+    if (R < 1 || first_row < 0 || !off || !grp || !idx) return GVX_ERR_INVALID_ARG;
+    const RowMap map{R, s1, s0};
+    RowWalk w = row_walk_begin(map, first_row);
+    for (int q = 0; q < 16; ++q) {
+        if (q > 0) row_walk_advance(w, map, mfma32_row_step(q));
+        off[q] = w.off; grp[q] = w.grp; idx[q] = w.idx;
+    }
+    return GVX_OK;
 }
 
 // The transform matrices of winograd_f45.h as doubles: at[4][8], g[8][5], bt[8][8]

@@ -41,6 +41,24 @@ struct RowMap {
     long s1, s0;   // offset(m) = (m / R) * s1 + (m % R) * s0   (in floats)
 };
 
+// A row's place under a RowMap - (grp, idx) = (m / R, m % R) and its offset - for code that visits rows in ascending order: one
+// division at the first row, additions and a wrap from there on (the GEMM epilogue: 16 rows per lane and M tile; a division per
+// row was most of its instructions).  The wrap takes step / R turns at most, none while the rows stay inside a group.
+struct RowWalk { int grp, idx; long off; };
+__host__ __device__ inline RowWalk row_walk_begin(const RowMap& m, int row) {
+    RowWalk w;
+    w.grp = row / m.R; w.idx = row - w.grp * m.R;
+    w.off = (long)w.grp * m.s1 + (long)w.idx * m.s0;
+    return w;
+}
+__host__ __device__ inline void row_walk_advance(RowWalk& w, const RowMap& m, int step) {   // step >= 0 rows further
+    w.idx += step; w.off += (long)step * m.s0;
+    while (w.idx >= m.R) { w.idx -= m.R; ++w.grp; w.off += m.s1 - (long)m.R * m.s0; }
+}
+// Accumulator element q (0..15) of a lane of the 32 x 32 MFMA tile lies in row (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5): the rows
+// from one q to the next
+__host__ __device__ inline int mfma32_row_step(int q) { return (q & 3) ? 1 : 5; }
+
 // Recurrent vectors (LSTM inputs/outputs, context, Prenet output) live in a k-group-blocked layout
 //   v[b][k]  at  base + (k >> 3) * B * 8 + b * 8 + (k & 7)
 // so that one wave-wide 16-byte-per-lane load of an MFMA x-fragment (32 rows x 8 k) is 1 KiB contiguous.
