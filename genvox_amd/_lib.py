@@ -40,6 +40,10 @@ class gvx_hifigan_dims(C.Structure):
                 ("post_slope", C.c_float)]
 
 
+class gvx_bigvgan_dims(C.Structure):
+    _fields_ = [("net", gvx_hifigan_dims), ("snakebeta", C.c_int32), ("tanh_at_final", C.c_int32), ("bias_at_final", C.c_int32)]
+
+
 class gvx_melgan_tape_entry(C.Structure):
     _fields_ = [("byte_offset", C.c_uint64), ("positions_per_frame", C.c_int32), ("channels", C.c_int32)]
 
@@ -244,6 +248,16 @@ SIGNATURES = {
     "gvx_melgan_disc_workspace_bytes": (_sz, [C.POINTER(gvx_melgan_disc_dims), _i, _i, _i]),
     "gvx_melgan_disc_forward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _sz, _vp]),
     "gvx_melgan_disc_backward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, C.POINTER(gvx_weight_desc), _i, _vp, _vp, _sz, _vp]),
+    "gvx_snake_antialiased": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "gvx_bigvgan_blob_floats": (_sz, [C.POINTER(gvx_bigvgan_dims)]),
+    "gvx_bigvgan_workspace_bytes": (_sz, [C.POINTER(gvx_bigvgan_dims), _i, _i]),
+    "gvx_bigvgan_pack_weights_device": (_i, [C.POINTER(gvx_bigvgan_dims), C.POINTER(gvx_weight_desc), _i, _vp, _vp]),
+    "gvx_bigvgan_create": (_i, [C.POINTER(gvx_bigvgan_dims), C.POINTER(_vp)]),
+    "gvx_bigvgan_destroy": (None, [_vp]),
+    "gvx_bigvgan_bind": (_i, [_vp, _vp]),
+    "gvx_bigvgan_forward": (_i, [_vp, _vp, _vp, _i, _i, _vp, C.POINTER(_vp), _vp, _sz, _vp]),
+    "gvx_bigvgan_timing_enable": (_i, [_vp, _i]),
+    "gvx_bigvgan_stage_times_ms": (_i, [_vp, C.POINTER(_f), C.POINTER(_i)]),
     "gvx_hifigan_mpd_blob_floats": (_sz, [C.POINTER(gvx_hifigan_mpd_dims)]),
     "gvx_hifigan_mpd_pack_weights_device": (_i, [C.POINTER(gvx_hifigan_mpd_dims), C.POINTER(gvx_weight_desc), _i, _vp, _vp]),
     "gvx_hifigan_mpd_create": (_i, [C.POINTER(gvx_hifigan_mpd_dims), C.POINTER(_vp)]),

@@ -357,6 +357,33 @@ class HiFiGANConfig(BaseConfig):
         return cls(**{k: config[k] for k in cls._FIELDS if k in config})
 
 
+class BigVGANConfig(HiFiGANConfig):
+    """The BigVGAN generator (Lee et al. 2023; include/genvox_amd.h, "BigVGAN generator").  The reference ships no such model; the
+    fields carry the names of the published implementation's ``config.json`` and the defaults of ``bigvgan_base_22khz_80band``.  The
+    structure is HiFi-GAN's generator's and is held to ``HiFiGANConfig``'s ranges by that class's own checks; ``upsample_rates`` must
+    multiply to the audio config's ``hop_length`` (``check_hop``)."""
+
+    _STRUCTURE = ("upsample_initial_channel", "upsample_rates", "upsample_kernel_sizes", "resblock", "resblock_kernel_sizes",
+                  "resblock_dilation_sizes")
+    _FIELDS = {
+        **{k: HiFiGANConfig._FIELDS[k] for k in _STRUCTURE},
+        "activation": ("snakebeta", None),
+        "snake_logscale": (True, None),
+        "use_tanh_at_final": (True, None),
+        "use_bias_at_final": (True, None),
+    }
+
+    def _normalise(self) -> None:
+        net = HiFiGANConfig(**{k: getattr(self, k) for k in self._STRUCTURE})   # its checks, its normal forms
+        for k in self._STRUCTURE:
+            setattr(self, k, getattr(net, k))
+        if self.activation not in ("snake", "snakebeta"):
+            raise ValueError(f"activation must be 'snake' or 'snakebeta', not {self.activation!r}")
+        for name in ("snake_logscale", "use_tanh_at_final", "use_bias_at_final"):
+            if not isinstance(getattr(self, name), bool):
+                raise ValueError(f"{name} must be true or false, not {getattr(self, name)!r}")
+
+
 class HiFiGANPeriodDiscriminatorConfig(BaseConfig):
     """HiFi-GAN's multi-period discriminator (Kong et al. 2020; include/genvox_amd.h, "HiFi-GAN period discriminators").  The defaults
     are the published ``MultiPeriodDiscriminator``; the ranges are what the kernels take."""

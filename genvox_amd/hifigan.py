@@ -21,7 +21,8 @@ from ._device_module import DeviceGenerator, _Layer
 from .configs import AudioConfig, HiFiGANConfig
 
 
-def dims_from_config(mc: HiFiGANConfig, ac: AudioConfig) -> _lib.gvx_hifigan_dims:
+def structure_dims(mc: HiFiGANConfig, ac: AudioConfig) -> _lib.gvx_hifigan_dims:
+    """The network's structure, which BigVGAN shares; the slopes stay 0."""
     d = _lib.gvx_hifigan_dims()
     d.n_mels, d.upsample_initial_channel, d.n_stages = ac.n_mels, mc.upsample_initial_channel, len(mc.upsample_rates)
     for i, (r, k) in enumerate(zip(mc.upsample_rates, mc.upsample_kernel_sizes)):
@@ -32,6 +33,11 @@ def dims_from_config(mc: HiFiGANConfig, ac: AudioConfig) -> _lib.gvx_hifigan_dim
         d.resblock_kernel_sizes[j] = k
         for m, dil in enumerate(ds):
             d.resblock_dilation_sizes[j][m] = dil
+    return d
+
+
+def dims_from_config(mc: HiFiGANConfig, ac: AudioConfig) -> _lib.gvx_hifigan_dims:
+    d = structure_dims(mc, ac)
     d.slope, d.post_slope = float(mc.leaky_slope), float(mc.post_leaky_slope)
     return d
 

@@ -200,7 +200,7 @@ def frame_ratios(start_frames: Sequence[int], n_frames: int, per_token_semitones
 class Synthesizer:
     def __init__(self, tts_model_class, tts_config_path: str, tts_checkpoint_path: str, use_cuda: bool = True, vocoder_model_class=None,
                  vocoder_config_path: Optional[str] = None, vocoder_checkpoint_path: Optional[str] = None) -> None:
-        """``vocoder_model_class`` (``MelGANGenerator`` or ``HiFiGANGenerator``) with its config and checkpoint paths: ``tts`` and ``tts_batch`` vocode the mel
+        """``vocoder_model_class`` (``MelGANGenerator``, ``HiFiGANGenerator`` or ``BigVGANGenerator``) with its config and checkpoint paths: ``tts`` and ``tts_batch`` vocode the mel
         through that model instead of Griffin-Lim.  The waveform is then float32 of exactly ``frames * hop_length`` samples (no trim,
         no low-pass), and every result carries ``"vocoder"``: the model's name.  All three or none: with none nothing changes."""
         if not (use_cuda and torch.cuda.is_available()):

@@ -1222,6 +1222,76 @@ int gvx_hifigan_backward(gvx_hifigan* handle, const float* d_wav, const int32_t*
                          size_t workspace_bytes, void* stream);
 int gvx_hifigan_backward_stage_times_ms(gvx_hifigan* handle, float* ms_out, int* n_out);
 
+/* ---- BigVGAN generator, mel -> waveform (Lee et al. 2023; bigvgan_base_22khz_80band, bigvgan_22khz_80band and their kin): inference.
+ * The reference ships no such model; the network below is the published implementation's, under its names.  It is HiFi-GAN's
+ * generator (above) with every LeakyReLU replaced by an anti-aliased periodic activation A, and no activation in front of the
+ * transposed convolutions.  Kernels: csrc/bigvgan.hip (the activation, the C ABI) on csrc/hifigan_kernels.h (every convolution, with
+ * its operand taken as it is); all arithmetic is fp32.  `net` holds the structure with gvx_hifigan_dims's meaning and ranges; its two
+ * slopes are not read.
+ *
+ *     x = Conv1d(n_mels -> C_0, k = 7, padding 3)(mel)                                                       conv_pre
+ *     for stage i, r = upsample_rates[i]:
+ *         x = ConvTranspose1d(C_i -> C_{i+1}, kernel 2 r, stride r, padding r / 2)(x)                        ups.<i>.0, length times r
+ *         y_j = resblocks.<i * n_k + j>(x) for j = 0 .. n_k - 1;   x = (y_0 + y_1 + ..) / n_k                 added in that order, then divided
+ *     x = Conv1d(C_last -> 1, k = 7, padding 3)(A_post(x))                                                   activation_post, conv_post
+ *     wav = tanh_at_final ? tanh(x) : min(max(x, -1), 1)                 conv_post has no bias when bias_at_final is 0
+ *
+ *     resblock 1 (AMPBlock1), m = 0 .. 2:  x = x + convs2.<m>(A_{2m+1}(convs1.<m>(A_{2m}(x))))    convs1: dilation d_m; convs2: dilation 1
+ *     resblock 2 (AMPBlock2), m = 0 .. 1:  x = x + convs.<m>(A_m(x))                              dilation d_m
+ *
+ * The activation A, per channel c over a row of n >= 1 positions, with the fixed 12-tap filter f (a Kaiser-windowed sinc of cutoff
+ * 0.25 and half-width 0.3, window beta = 0.1102 * (2.285 * 5 * pi * 1.2 + 7.95 - 8.7), normalised to sum 1; the CALLER computes it in
+ * float64 and hands it over as fp32):
+ *     u[m] = 2 * sum_i xp[i] * f[m + 13 - 2 i],   xp[i] = x[clamp(i - 4, 0, n - 1)],   0 <= m < 2 n         2x upsample, replicate padding
+ *     z[m] = u[m] + g_c * sin(a_c * u[m])^2                                                                  Snake
+ *     y[t] = sum_{j = 0 .. 11} f[j] * z[clamp(2 t + j - 5, 0, 2 n - 1)],   0 <= t < n                        2x low-pass downsample
+ * z is REPEATED beyond the row's ends, not recomputed from padded x.  y[t] depends on x[t - 5 .. t + 5].  a_c and g_c are per-channel
+ * constants the caller derives from the checkpoint's alpha and beta: a = exp(alpha) (snake_logscale) or alpha; g = 1 / (a + 1e-9)
+ * ("snake") or 1 / (b + 1e-9) with b = exp(beta) or beta ("snakebeta").
+ *
+ * gvx_snake_antialiased is A on its own: x and out fp32 [B][n_max][C] channels-last (out must not be x), lens int32 [B] on the device
+ * or NULL for all n_max, f fp32 [12], a and g fp32 [C], all on the device.  One launch: a workgroup of 256 threads owns
+ * GVX_BIGVGAN_ACT_TILE positions of one row by a block of up to 64 channels, lanes along the channels; it stages x[t0 - 6 .. t0 + P + 5]
+ * in LDS with both ends clamped to the row, forms the z pairs (2 q, 2 q + 1) of q = t0 - 3 .. t0 + P + 2 ONCE (u polyphase: six taps of f
+ * for even m, six for odd m, over seven shared values of x) into LDS, then every y.  No atomics; a row's result depends on that row alone, so a ragged row has the bits of its one-row
+ * run, and two calls give the same bits.  out is written as exact ZEROS at and behind a row's length, up to n_max; x is never read there.
+ * lens[b] is clamped to [0, n_max].  B outside [1, 65535], n_max < 1, C < 1, n_max above GVX_BIGVGAN_ACT_MAX_POSITIONS or a NULL
+ * pointer: GVX_ERR_INVALID_ARG.
+ *
+ * Weights.  gvx_bigvgan_pack_weights_device reads DEVICE pointers by name: every convolution as gvx_hifigan_pack_weights_device reads
+ * it (ups.<i>.weight / .bias: the caller strips the published ".0"; conv_post.bias is zeros when the model has none), and
+ *     filter [12];   resblocks.<n>.activations.<p>.a / .g [C];   activation_post.a / .g [C_last]
+ * The blob is gvx_hifigan_blob_floats(net) floats in that call's layout - written by that call - followed by the filter and every a and
+ * g in network order, each starting at a multiple of 64 floats.  Errors as there.
+ *
+ * Workspace: gvx_bigvgan_workspace_bytes is host arithmetic:  B * ( round256(4 * T * round4(n_mels)) + 5 * round256(4 * T * W) ), W as
+ * for HiFi-GAN: its four tensors and the activation's output.  The same contract: any contents when the call starts, nothing is cleared.
+ *
+ * gvx_bigvgan_forward: gvx_hifigan_forward's arguments, contracts and error codes; one launch per convolution and one per activation
+ * (the clamp of tanh_at_final = 0 is one more).  Ragged rows as there: row b has the bits of that row run alone, wav is exactly 0 from
+ * sample T_b * hop on.  Timing as gvx_hifigan_timing_enable / gvx_hifigan_stage_times_ms: n_stages + 2 durations, the last one
+ * activation_post with conv_post.  There is no backward. */
+enum { GVX_BIGVGAN_FILTER_TAPS = 12, GVX_BIGVGAN_ACT_TILE = 32, GVX_BIGVGAN_ACT_MAX_POSITIONS = 1 << 28 };
+typedef struct gvx_bigvgan_dims {
+    gvx_hifigan_dims net;
+    int32_t snakebeta;       /* 1: "snakebeta", 0: "snake" (names the tensors the caller derives g from; the kernels see a and g) */
+    int32_t tanh_at_final;   /* 1: tanh, 0: clamp to [-1, 1] */
+    int32_t bias_at_final;   /* 0: conv_post has no bias (the caller hands zeros) */
+} gvx_bigvgan_dims;
+typedef struct gvx_bigvgan gvx_bigvgan;
+int gvx_snake_antialiased(const float* x, const int32_t* lens, int B, int n_max, int C, const float* f, const float* a, const float* g,
+                          float* out, void* stream);
+size_t gvx_bigvgan_blob_floats(const gvx_bigvgan_dims* dims);
+size_t gvx_bigvgan_workspace_bytes(const gvx_bigvgan_dims* dims, int B, int T);
+int gvx_bigvgan_pack_weights_device(const gvx_bigvgan_dims* dims, const gvx_weight_desc* table, int n, float* device_blob, void* stream);
+int gvx_bigvgan_create(const gvx_bigvgan_dims* dims, gvx_bigvgan** out);
+void gvx_bigvgan_destroy(gvx_bigvgan* handle);
+int gvx_bigvgan_bind(gvx_bigvgan* handle, const float* device_blob);
+int gvx_bigvgan_forward(gvx_bigvgan* handle, const float* mel, const int32_t* frame_lengths, int B, int T, float* wav_out,
+                        float* const* stage_out, void* workspace, size_t workspace_bytes, void* stream);
+int gvx_bigvgan_timing_enable(gvx_bigvgan* handle, int enable);
+int gvx_bigvgan_stage_times_ms(gvx_bigvgan* handle, float* ms_out, int* n_out);
+
 /* ---- MelGAN discriminators: the multi-scale discriminator a MelGAN generator is trained against (Kumar et al. 2019), forward and
  * backward.  The reference ships the training fields of MelGANConfig and no model; this is a statement of the published architecture.
  * All arithmetic is fp32.  lrelu and "reflect" as for the generator above; s = downsampling_factor.

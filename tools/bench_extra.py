@@ -39,7 +39,12 @@ the fp32 matrix rate; and one `HiFiGANTrainer.train_step` of the V1 generator ag
 `hifigan_msd` (on request): HiFi-GAN's multi-scale discriminator, published shape, the same measurement at the same two sizes against
 torch's own grouped Conv1d + avg_pool1d + autograd on the same effective weights (eval mode: no power iteration), the per-layer times
 summed over the scales; and one `HiFiGANTrainer.train_step` of the V1 generator against the period and the scale discriminators with
-`MelSpectrogramLoss` - the published step."""
+`MelSpectrogramLoss` - the published step;
+`bigvgan` (on request): the BigVGAN generator - the base model at 32 x 800 and 1 x 568 frames, the large one at 8 x 200 - between device
+events, median of 7 with the spread and the time per stage, against the float32 restatement of tests/bigvgan_ref64.py (torch's own ROCm
+convolutions, the activation as replicate padding + grouped conv_transpose1d / conv1d) on the same device and the same parameters; and
+the anti-aliased activation's launches on their own: gvx_snake_antialiased timed at every stage's shape, times the launches of that
+stage, summed, as a share of one call."""
 import json
 import os
 import sys
@@ -1012,6 +1017,77 @@ def main():
                 res[key]["torch_autograd"] = ev_spread(torchs, warm=2, reps=7)
                 res[key]["max_relative_gradient_difference_from_torch"] = max(
                     float((got[k] - p.grad).abs().max() / p.grad.abs().max().clamp_min(1e-30)) for k, p in ref_params.items())
+                print(json.dumps({key: res[key]}), flush=True)
+            del voc, ref
+    if "bigvgan" in which:
+        import ctypes as C
+        import statistics
+
+        from genvox_amd import _lib
+        from genvox_amd.bigvgan import BigVGANGenerator, kaiser_sinc_filter, snake_constants
+        from genvox_amd.configs import BigVGANConfig
+        from tests import bigvgan_ref64 as R
+
+        def ev_spread(fn, warm=2, reps=7):
+            for _ in range(warm):
+                fn()
+            out = []
+            for _ in range(reps):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                e1.synchronize()
+                out.append(e0.elapsed_time(e1))
+            return {"median_ms": round(statistics.median(out), 3), "min_ms": round(min(out), 3), "max_ms": round(max(out), 3), "runs": reps}
+
+        lib = _lib.load()
+        gen = torch.Generator(device="cuda").manual_seed(0)
+        large = dict(upsample_initial_channel=1536, upsample_rates=(4, 4, 2, 2, 2, 2), upsample_kernel_sizes=(8, 8, 4, 4, 4, 4))
+        for name, bc, cfg, shapes in (("base", BigVGANConfig(), R.BASE, ((32, 800), (1, 568))), ("large", BigVGANConfig(**large), R.LARGE, ((8, 200),))):
+            ref = R.Generator(cfg, seed=0).float().to("cuda:0")   # random weights, a_c and b_c spread over 0.3 .. 5
+            voc = BigVGANGenerator(bc, ac)
+            voc.load_state_dict(ref.state_dict())
+            voc.to("cuda:0")
+            f_dev = kaiser_sinc_filter().to("cuda:0", torch.float32)
+            for B, T in shapes:
+                key = f"bigvgan_{name}_{B}x{T}"
+                mel = (0.5 * torch.randn(B, 80, T, device="cuda", generator=gen) - 0.5).contiguous()
+                rows = B
+                while rows > 1 and voc.workspace_bytes(rows, T) > voc.WORKSPACE_CAP_BYTES:
+                    rows = (rows + 1) // 2
+                res[key] = {"as_delivered": ev_spread(lambda: voc.vocode(mel)), "rows_per_call_as_delivered": rows}
+                voc.enable_stage_timing(True)   # the stage times are of one call: the rows of one group
+                per = []
+                for _ in range(5):
+                    voc.vocode(mel[:rows])
+                    per.append(voc.stage_times_ms())
+                voc.enable_stage_timing(False)
+                res[key]["stage_ms_median_of_one_call"] = [round(statistics.median(col), 3) for col in zip(*per)]   # conv_pre, every stage, activation_post + conv_post
+                # the activation's launches alone, at every stage's shape of one call
+                n_act = len(bc.resblock_kernel_sizes) * len(bc.resblock_dilation_sizes[0]) * (2 if bc.resblock == "1" else 1)
+                c, mul, act_ms = bc.upsample_initial_channel, 1, []
+                stream = torch.cuda.current_stream().cuda_stream
+                for i, r in enumerate(bc.upsample_rates):
+                    c, mul = c // 2, mul * r
+                    x = torch.randn(rows, T * mul, c, device="cuda", generator=gen)
+                    out = torch.empty_like(x)
+                    a, g = snake_constants(R.random_snake(c, None, True).cuda(), R.random_snake(c, None, True).cuda(), "snakebeta", True)
+                    one = lambda: _lib.check(lib.gvx_snake_antialiased(x.data_ptr(), None, rows, T * mul, c, f_dev.data_ptr(), a.data_ptr(), g.data_ptr(),
+                                                                       out.data_ptr(), stream))
+                    launches = n_act + (1 if i == len(bc.upsample_rates) - 1 else 0)   # activation_post runs at the last stage's shape
+                    t = ev_spread(one, warm=2, reps=7)["median_ms"]
+                    act_ms.append({"channels": c, "positions": T * mul, "one_launch_ms": t, "launches": launches, "ms": round(t * launches, 3),
+                                   "GBs_read_plus_write": round(8.0 * x.numel() / t / 1e6, 1)})
+                    del x, out
+                res[key]["activation_launches_of_one_call"] = act_ms
+                res[key]["activation_ms_of_one_call"] = round(sum(e["ms"] for e in act_ms), 3)
+                res[key]["activation_share_of_one_call"] = round(sum(e["ms"] for e in act_ms) / sum(res[key]["stage_ms_median_of_one_call"]), 3)
+                wav = voc.vocode(mel)
+                print(json.dumps({key: res[key]}), flush=True)
+                with torch.no_grad():
+                    res[key]["torch_float32_restatement"] = ev_spread(lambda: ref(mel), warm=1, reps=5)
+                    res[key]["max_abs_difference_from_torch"] = float((ref(mel)[0] - wav).abs().max())
                 print(json.dumps({key: res[key]}), flush=True)
             del voc, ref
     if "cpu" in which:
