@@ -8,11 +8,13 @@
     from genvox_amd import MelGANDiscriminator, MelGANDiscriminatorConfig, MelGANTrainer   # the other side of the vocoder's GAN step
     from genvox_amd import HiFiGANPeriodDiscriminator, HiFiGANPeriodDiscriminatorConfig, HiFiGANTrainer, HiFiGANTrainingConfig   # HiFi-GAN's GAN step
     from genvox_amd import HiFiGANScaleDiscriminator, HiFiGANScaleDiscriminatorConfig   # ... and its multi-scale discriminator
+    from genvox_amd import MultiResolutionDiscriminator, MultiResolutionDiscriminatorConfig   # UnivNet's / BigVGAN's spectrogram discriminator
     from genvox_amd import MultiResolutionSTFTLoss, stft_distance   # vocoder training loss / waveform distance on the device
     from genvox_amd import MelSpectrogramLoss, mel_distance         # HiFi-GAN's mel-spectrogram L1 term / log-mel distance
     from genvox_amd import Denoiser   # vocoder denoiser: Denoiser.from_vocoder(vocoder)(wav), or Synthesizer.tts(text, denoise=0.01)
 """
 from .configs import HiFiGANPeriodDiscriminatorConfig, HiFiGANScaleDiscriminatorConfig, HiFiGANTrainingConfig  # noqa: F401
+from .configs import MultiResolutionDiscriminatorConfig  # noqa: F401
 from .configs import AudioConfig, BaseConfig, BigVGANConfig, HiFiGANConfig, MelGANConfig, MelGANDiscriminatorConfig, Tacotron2Config, TextConfig  # noqa: F401
 
 
@@ -44,6 +46,9 @@ def __getattr__(name):  # torch-dependent classes are imported lazily
     if name == "HiFiGANScaleDiscriminator":
         from .hifigan_msd import HiFiGANScaleDiscriminator
         return HiFiGANScaleDiscriminator
+    if name == "MultiResolutionDiscriminator":
+        from .mrd import MultiResolutionDiscriminator
+        return MultiResolutionDiscriminator
     if name == "HiFiGANTrainer":
         from .hifigan_training import HiFiGANTrainer
         return HiFiGANTrainer

@@ -80,6 +80,16 @@ class gvx_hifigan_mpd_entry(C.Structure):
                 ("stride_b", C.c_int64), ("stride_c", C.c_int64), ("stride_h", C.c_int64), ("stride_p", C.c_int64)]
 
 
+class gvx_mrd_dims(C.Structure):
+    _fields_ = [("n_resolutions", C.c_int32), ("n_fft", C.c_int32 * 8), ("hop", C.c_int32 * 8), ("win", C.c_int32 * 8),
+                ("channels", C.c_int32), ("window", C.c_int32), ("slope", C.c_float)]
+
+
+class gvx_mrd_entry(C.Structure):
+    _fields_ = [("byte_offset", C.c_uint64), ("channels", C.c_int32), ("frames", C.c_int32), ("bins", C.c_int32), ("reserved", C.c_int32),
+                ("stride_b", C.c_int64), ("stride_c", C.c_int64), ("stride_w", C.c_int64), ("stride_f", C.c_int64)]
+
+
 class gvx_stft_resolution(C.Structure):
     _fields_ = [("n_fft", C.c_int32), ("hop", C.c_int32), ("win_length", C.c_int32)]
 
@@ -270,6 +280,18 @@ SIGNATURES = {
     "gvx_hifigan_mpd_backward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, C.POINTER(gvx_weight_desc), _i, _vp, _vp, _sz, _vp]),
     "gvx_hifigan_mpd_timing_enable": (_i, [_vp, _i]),
     "gvx_hifigan_mpd_layer_times_ms": (_i, [_vp, C.POINTER(_f), C.POINTER(_f), C.POINTER(_i)]),
+    "gvx_mrd_blob_floats": (_sz, [C.POINTER(gvx_mrd_dims)]),
+    "gvx_mrd_pack_weights_device": (_i, [C.POINTER(gvx_mrd_dims), C.POINTER(gvx_weight_desc), _i, _vp, _vp]),
+    "gvx_mrd_create": (_i, [C.POINTER(gvx_mrd_dims), C.POINTER(_vp)]),
+    "gvx_mrd_destroy": (None, [_vp]),
+    "gvx_mrd_bind": (_i, [_vp, _vp]),
+    "gvx_mrd_layout": (_i, [C.POINTER(gvx_mrd_dims), _i, _i, C.POINTER(gvx_mrd_entry), _i]),
+    "gvx_mrd_features_bytes": (_sz, [C.POINTER(gvx_mrd_dims), _i, _i]),
+    "gvx_mrd_workspace_bytes": (_sz, [C.POINTER(gvx_mrd_dims), _i, _i, _i]),
+    "gvx_mrd_forward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _sz, _vp]),
+    "gvx_mrd_backward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, C.POINTER(gvx_weight_desc), _i, _vp, _vp, _sz, _vp]),
+    "gvx_mrd_timing_enable": (_i, [_vp, _i]),
+    "gvx_mrd_layer_times_ms": (_i, [_vp, C.POINTER(_f), C.POINTER(_f), C.POINTER(_i)]),
     "gvx_hifigan_msd_blob_floats": (_sz, [C.POINTER(gvx_hifigan_msd_dims)]),
     "gvx_hifigan_msd_pack_weights_device": (_i, [C.POINTER(gvx_hifigan_msd_dims), C.POINTER(gvx_weight_desc), _i, _vp, _vp]),
     "gvx_hifigan_msd_create": (_i, [C.POINTER(gvx_hifigan_msd_dims), C.POINTER(_vp)]),

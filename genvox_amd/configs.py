@@ -519,6 +519,62 @@ class HiFiGANScaleDiscriminatorConfig(BaseConfig):
         return self.n_scales * sum(cout * (cin // g) * k + cout for cin, cout, k, _s, _p, g in self.layer_shapes())
 
 
+class MultiResolutionDiscriminatorConfig(BaseConfig):
+    """UnivNet's multi-resolution spectrogram discriminator (Jang et al. 2021; include/genvox_amd.h, "Multi-resolution spectrogram
+    discriminator").  The defaults are the ones the published BigVGAN recipe trains with; the ranges are what the kernels take.
+    ``window`` is ``"rectangular"`` - what ``torch.stft`` uses when it is given no window, as the published code does - or ``"hann"``
+    (periodic); either has ``win`` samples and is zero-padded to ``n_fft``, centred."""
+
+    MAX_RESOLUTIONS = 8     # GVX_MRD_MAX_RESOLUTIONS
+    N_FFTS = (512, 1024, 2048)
+    WINDOWS = ("rectangular", "hann")   # GVX_MRD_WINDOW_*
+    MAPS = 6                # GVX_MRD_MAPS
+
+    _FIELDS = {
+        "resolutions": (((1024, 120, 600), (2048, 240, 1200), (512, 50, 240)), None),
+        "channels": (32, None),
+        "leaky_slope": (0.1, None),
+        "window": ("rectangular", None),
+    }
+
+    def _normalise(self) -> None:
+        try:
+            self.resolutions = [tuple(int(v) for v in r) for r in self.resolutions]
+        except (TypeError, ValueError):
+            raise ValueError("resolutions must be a sequence of (n_fft, hop, win) integer triples") from None
+        if not 1 <= len(self.resolutions) <= self.MAX_RESOLUTIONS:
+            raise ValueError(f"resolutions must name 1 to {self.MAX_RESOLUTIONS} resolutions, not {len(self.resolutions)}")
+        for r in self.resolutions:
+            if len(r) != 3:
+                raise ValueError(f"resolutions: {r} is no (n_fft, hop, win) triple")
+            n_fft, hop, win = r
+            if n_fft not in self.N_FFTS:
+                raise ValueError(f"resolutions: n_fft = {n_fft} is none of {self.N_FFTS}")
+            if not 1 <= hop <= win <= n_fft:
+                raise ValueError(f"resolutions: {r} does not satisfy 1 <= hop <= win <= n_fft")
+        if isinstance(self.channels, bool) or not isinstance(self.channels, int):
+            raise ValueError(f"channels must be an integer, not {self.channels!r}")
+        if not 32 <= self.channels <= 128 or self.channels % 32:
+            raise ValueError(f"channels = {self.channels} must be a multiple of 32 in [32, 128]")
+        if not 0.0 <= float(self.leaky_slope) <= 1.0:
+            raise ValueError(f"leaky_slope = {self.leaky_slope} is outside [0, 1]")
+        if self.window not in self.WINDOWS:
+            raise ValueError(f"window = {self.window!r} is none of {self.WINDOWS}")
+
+    def layer_shapes(self):
+        """The convolutions of one resolution, the score last, as (c_in, c_out, (taps in frequency, taps in time), stride in time)."""
+        C = self.channels
+        return [(1, C, (3, 9), 1), (C, C, (3, 9), 2), (C, C, (3, 9), 2), (C, C, (3, 9), 2), (C, C, (3, 3), 1), (C, 1, (3, 3), 1)]
+
+    @property
+    def min_samples(self) -> int:
+        """The shortest row: a reflection by (n_fft - hop) // 2 samples needs one sample more."""
+        return max((n_fft - hop) // 2 + 1 for n_fft, hop, _win in self.resolutions)
+
+    def parameter_count(self) -> int:
+        return len(self.resolutions) * sum(cout * cin * kf * kt + cout for cin, cout, (kf, kt), _s in self.layer_shapes())
+
+
 class HiFiGANTrainingConfig(BaseConfig):
     """The training keys of a published HiFi-GAN ``config.json`` under their names and with their defaults; ``feat_match`` and
     ``aux_weight`` are the weights that implementation keeps in its training script (2 on the feature-matching term, 45 on the

@@ -10,7 +10,9 @@ offers ``forward(wav, sample_lengths)`` -> [sub-discriminator][map] and ``map_le
 ``aux_loss(fake, wav, sample_lengths)``, weighted ``aux_weight``: with ``losses.MelSpectrogramLoss()`` - HiFi-GAN's mel-spectrogram L1
 term - the default ``aux_weight`` of 45 carries its published meaning (``MultiResolutionSTFTLoss`` fits the same slot, on another scale).
 ``HiFiGANScaleDiscriminator`` in training mode does one power iteration of its spectral scale per forward, four per step, as the
-published recipe does; ``MelGANDiscriminator`` fits the same list."""
+published recipe does; ``MelGANDiscriminator`` fits the same list, and so does ``MultiResolutionDiscriminator`` (UnivNet's spectrogram
+discriminator, which the published BigVGAN recipe trains with in place of the multi-scale one): its maps are [B, C, W, F] with the
+frames, the ragged axis, on dim 2, where the period discriminators have their heights."""
 from __future__ import annotations
 
 from typing import Dict, Optional, Sequence

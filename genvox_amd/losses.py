@@ -307,7 +307,9 @@ class MelGANGeneratorLoss(torch.nn.Module):
 # ---- the least-squares losses of the HiFi-GAN step (Kong et al. 2020), over any number of discriminators
 def _row_mean_any(values: torch.Tensor, lengths) -> torch.Tensor:
     """values [B, C, L] or [B, C, H, p] -> the mean over rows of each row's mean over its own elements: C x L_b, or C x H_b x p
-    (``lengths`` [B]: L_b or H_b; None: the whole map, the published mean)."""
+    (``lengths`` [B]: L_b or H_b; None: the whole map, the published mean).  A 4-D map is masked along dim 2 and its dim 3 taken whole:
+    ``HiFiGANPeriodDiscriminator``'s [B, C, H, p] with the row's heights, ``MultiResolutionDiscriminator``'s [B, C, W, F] with its
+    frames."""
     if values.dim() == 3:
         return _row_mean(values, lengths)
     if values.dim() != 4:

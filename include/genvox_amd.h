@@ -1475,6 +1475,105 @@ int gvx_hifigan_mpd_backward(gvx_hifigan_mpd* handle, const float* wav, const in
 int gvx_hifigan_mpd_timing_enable(gvx_hifigan_mpd* handle, int enable);
 int gvx_hifigan_mpd_layer_times_ms(gvx_hifigan_mpd* handle, float* forward_ms, float* backward_ms, int* n_layers_out);
 
+/* ---- Multi-resolution spectrogram discriminator (UnivNet's MRD, Jang et al. 2021; the published BigVGAN recipe trains with it):
+ * forward, and the backward that reads the forward's own maps as its tape.  The surface, the contracts and the error codes are the
+ * period discriminators' above.  All arithmetic fp32.
+ *
+ * The model.  One sub-discriminator per resolution (n_fft, hop, win).  A row of n samples is reflect-padded by p = (n_fft - hop) / 2
+ * samples at both ends (padded sample -1 - i is sample 1 + i, padded sample n + i is sample n - 2 - i; needs n > p) and framed without
+ * centring: frame w starts at padded position w * hop, W_0 = 1 + (n + 2p - n_fft) / hop frames (none if that is negative).  A frame
+ * is multiplied by the window - rectangular or periodic Hann of `win` samples, zero-padded to n_fft with left offset (n_fft - win) / 2
+ * - and transformed: F = n_fft / 2 + 1 bins, mag[w][f] = sqrt(re^2 + im^2), whose gradient is d_mag (re, im) / mag and exactly 0 where
+ * mag == 0.  On the one-channel image mag, with the axes in Conv2d's order (frequency, time): Conv2d(1 -> C, (3, 9), padding (1, 4)),
+ * three times Conv2d(C -> C, (3, 9), stride (1, 2), padding (1, 4)), Conv2d(C -> C, (3, 3), padding (1, 1)), each followed by
+ * LeakyReLU(slope); the score is Conv2d(C -> 1, (3, 3), padding (1, 1)) without activation.  A strided layer takes W frames to
+ * (W - 1) / 2 + 1; F never changes.  All six maps are returned (post-activation; the last is the score).
+ *
+ * Ragged batches: sample_lengths is int32 [B] on the device, or NULL for all n_max.  Row b is computed as if alone at n_b =
+ * min(sample_lengths[b], n_max): the reflection, the frame count and the zero padding in time are its own; nothing of wav at or behind
+ * n_b is read; every map is exact zeros behind the row's own frames; a ragged row has the bits of its one-row run.  A row needs
+ * n_b >= min_samples = the largest p + 1; the host cannot see device lengths, so the CALLER checks them - a shorter row comes out as
+ * all-zero maps, never a bad address.
+ *
+ * Dims are refused (GVX_ERR_INVALID_ARG from create and pack, 0 from the size functions) unless: n_resolutions in [1, 8]; every n_fft
+ * one of 512, 1024, 2048; 1 <= hop <= win <= n_fft; channels a multiple of 32 in [32, 128]; window one of GVX_MRD_WINDOW_*; slope in
+ * [0, 1].
+ *
+ * Weights.  gvx_mrd_pack_weights_device reads PyTorch-layout tensors from DEVICE pointers, by name:
+ *     discriminators.<j>.convs.<i>.weight [c_out][c_in][3][9] (i = 4: [c_out][c_in][3][3]), .bias [c_out],
+ *     discriminators.<j>.conv_post.weight [1][C][3][3], .bias [1]
+ * and writes the blob (gvx_mrd_blob_floats): every weight twice, as [c_out][time tap][frequency tap][c_in] for the forward and as
+ * [c_in][time tap][frequency tap, reversed][c_out] for the data gradient - in channels-last storage the three frequency taps of one
+ * time tap are one contiguous run of 3 C floats of the operand, and both products read it against a contiguous run of weights - and,
+ * behind the weights, every resolution's padded window and twiddle factors (computed in double on the device).  Errors as the period
+ * discriminators'.
+ *
+ * Features buffer: the caller's, 256-byte aligned, gvx_mrd_features_bytes long.  Maps are CHANNELS-LAST: map (j, i) is fp32
+ * [B][frames][bins][channels], every map starting at a multiple of 256 bytes, a row's valid part one contiguous run.  gvx_mrd_layout
+ * (host arithmetic) lists, resolution by resolution and map by map, the byte offset, channels, frames (of a row of n_max samples),
+ * bins, and the strides in floats of the [B, C, W, F] view - frames in front of bins: the transpose of the published [B, C, F, W].
+ * It returns the number of entries, 6 n_resolutions, and fills at most max_entries of them; 0 for refused dims, B or n_max.
+ *
+ * Workspace: gvx_mrd_workspace_bytes(dims, B, n_max, backward) is host arithmetic; any contents when a call starts, nothing is
+ * cleared, 256-byte aligned.  The forward's holds the spectrogram of one resolution; the backward's also that spectrogram's gradient,
+ * the frame gradients [B][W_0][n_fft], two activation gradients of the largest map and the partial weight and bias gradients.
+ *
+ * Kernels.  The spectrogram is a wave per frame (GVX_MRD_FRAMES_PER_WORKGROUP frames per workgroup): gather through the reflection,
+ * window, real transform in LDS (fft_lds.h), magnitude.  A position is a cell (frame, bin) of a map, numbered frame * F + bin.  The
+ * first layer (K = 27) and the score (N = 1) are fp32 VALU code, GVX_MRD_TILE positions per workgroup.  The C -> C layers run -
+ * forward, data gradient and weight gradient - as implicit GEMMs on v_mfma_f32_32x32x2_f32 with K = 3 C per time tap: GVX_MRD_TILE
+ * positions x 64 channels per workgroup where c_out is a multiple of 64, GVX_MRD_TILE_NARROW positions x 32 channels otherwise;
+ * LeakyReLU and its mask are applied in the epilogues, the zero padding is by index at both ends of both axes, and a tile that lies
+ * behind its row computes nothing and writes zeros.  A data gradient's workgroup takes its positions from ONE stride phase in time.
+ *
+ * gvx_mrd_forward / gvx_mrd_backward: the arguments, the refusals before any launch and the results are those of
+ * gvx_hifigan_mpd_forward / _backward, with min_samples for the largest period, GVX_MRD_MAX_SAMPLES for the limit of n_max, and
+ * GVX_ERR_UNSUPPORTED as well where a map of n_max samples would have more than GVX_MRD_MAX_POSITIONS positions in a row.  The
+ * backward recomputes the spectrogram from wav; d_mag goes through (re, im) / mag, the adjoint of the real transform and the window
+ * to frame gradients, which are overlap-added as a gather: a sample collects its own padded cell and the reflected cells that copy
+ * it, over the frames that cover each.  d_wav is the sum over the resolutions in their order, exactly 0 at and behind n_b.  A weight
+ * gradient is summed in pieces of GVX_MRD_PIECE_FRAMES output frames of a row, added in a fixed order; bias gradients in float64
+ * slices; no atomics: two calls give the same bits.  n_grads = 0 or d_wav = NULL skips that part; what is still computed keeps its
+ * bits. */
+enum { GVX_MRD_MAX_RESOLUTIONS = 8, GVX_MRD_MAPS = 6, GVX_MRD_TILE = 64, GVX_MRD_TILE_NARROW = 128, GVX_MRD_PIECE_FRAMES = 16,
+       GVX_MRD_FRAMES_PER_WORKGROUP = 4, GVX_MRD_MAX_SAMPLES = 1 << 24, GVX_MRD_MAX_POSITIONS = 1 << 28 };
+enum { GVX_MRD_WINDOW_RECTANGULAR = 0, GVX_MRD_WINDOW_HANN = 1 };
+typedef struct gvx_mrd_dims {
+    int32_t n_resolutions;
+    int32_t n_fft[8];
+    int32_t hop[8];
+    int32_t win[8];
+    int32_t channels;
+    int32_t window;
+    float slope;
+} gvx_mrd_dims;
+typedef struct gvx_mrd_entry {
+    uint64_t byte_offset;
+    int32_t channels;
+    int32_t frames;
+    int32_t bins;
+    int32_t reserved;
+    int64_t stride_b, stride_c, stride_w, stride_f;   /* floats, of the [B, C, W, F] view */
+} gvx_mrd_entry;
+typedef struct gvx_mrd gvx_mrd;
+size_t gvx_mrd_blob_floats(const gvx_mrd_dims* dims);
+int gvx_mrd_pack_weights_device(const gvx_mrd_dims* dims, const gvx_weight_desc* table, int n, float* device_blob, void* stream);
+int gvx_mrd_create(const gvx_mrd_dims* dims, gvx_mrd** out);
+void gvx_mrd_destroy(gvx_mrd* handle);
+int gvx_mrd_bind(gvx_mrd* handle, const float* device_blob);
+int gvx_mrd_layout(const gvx_mrd_dims* dims, int B, int n_max, gvx_mrd_entry* entries, int max_entries);
+size_t gvx_mrd_features_bytes(const gvx_mrd_dims* dims, int B, int n_max);
+size_t gvx_mrd_workspace_bytes(const gvx_mrd_dims* dims, int B, int n_max, int backward);
+int gvx_mrd_forward(gvx_mrd* handle, const float* wav, const int32_t* sample_lengths, int B, int n_max, void* features,
+                    size_t features_bytes, void* workspace, size_t workspace_bytes, void* stream);
+int gvx_mrd_backward(gvx_mrd* handle, const float* wav, const int32_t* sample_lengths, int B, int n_max, const void* features,
+                     const void* d_features, const gvx_grad_desc* grads, int n_grads, float* d_wav, void* workspace,
+                     size_t workspace_bytes, void* stream);
+/* Measurement only (tools/bench_extra.py mrd): as gvx_hifigan_mpd_timing_enable / _layer_times_ms; six layers, the score last, summed
+ * over the resolutions; the spectrogram and its adjoint count towards layer 0. */
+int gvx_mrd_timing_enable(gvx_mrd* handle, int enable);
+int gvx_mrd_layer_times_ms(gvx_mrd* handle, float* forward_ms, float* backward_ms, int* n_layers_out);
+
 /* ---- HiFi-GAN scale discriminators (Kong et al. 2020, the published DiscriminatorS / MultiScaleDiscriminator): forward, and the
  * backward that reads the forward's own maps as its tape.  The surface mirrors the period discriminators' above.  All arithmetic fp32.
  *

@@ -40,6 +40,10 @@ the fp32 matrix rate; and one `HiFiGANTrainer.train_step` of the V1 generator ag
 torch's own grouped Conv1d + avg_pool1d + autograd on the same effective weights (eval mode: no power iteration), the per-layer times
 summed over the scales; and one `HiFiGANTrainer.train_step` of the V1 generator against the period and the scale discriminators with
 `MelSpectrogramLoss` - the published step;
+`mrd` (on request): the multi-resolution spectrogram discriminator, published shape, at 16 x 8192 and 32 x 8192 samples between device
+events, median of 7 with the spread: forward, forward + full backward (cotangents on every map), against torch's own stft + Conv2d +
+autograd on the same device and parameters; the per-layer times summed over the resolutions (the spectrogram and its adjoint count
+towards layer 0) and the backward's workspace;
 `bigvgan` (on request): the BigVGAN generator - the base model at 32 x 800 and 1 x 568 frames, the large one at 8 x 200 - between device
 events, median of 7 with the spread and the time per stage, against the float32 restatement of tests/bigvgan_ref64.py (torch's own ROCm
 convolutions, the activation as replicate padding + grouped conv_transpose1d / conv1d) on the same device and the same parameters; and
@@ -867,6 +871,96 @@ def main():
             print(json.dumps({key: {"train_step_v1_mpd_msd_mel": res[key]["train_step_v1_mpd_msd_mel"]}}), flush=True)
             del trainer
             msd.eval()
+    if "mrd" in which:
+        import ctypes as C
+        import statistics
+
+        import torch.nn.functional as F
+
+        from genvox_amd import _lib
+        from genvox_amd.configs import MultiResolutionDiscriminatorConfig
+        from genvox_amd.mrd import MultiResolutionDiscriminator
+
+        def ev_spread(fn, warm=2, reps=7):
+            for _ in range(warm):
+                fn()
+            out = []
+            for _ in range(reps):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                e1.synchronize()
+                out.append(e0.elapsed_time(e1))
+            return {"median_ms": round(statistics.median(out), 3), "min_ms": round(min(out), 3), "max_ms": round(max(out), 3), "runs": reps}
+
+        torch.manual_seed(0)
+        rc = MultiResolutionDiscriminatorConfig()
+        mrd = MultiResolutionDiscriminator(rc).to("cuda:0")
+        with torch.no_grad():
+            for name, p in mrd.named_parameters():
+                if name.endswith("bias"):
+                    p.copy_(0.1 * torch.randn_like(p))
+        rparams = dict(mrd.named_parameters())
+        rshapes = rc.layer_shapes()
+
+        def torch_mrd(wav):
+            """The published composition on the module's own parameters, through torch's stft and Conv2d kernels; the maps transposed to
+            the module's [B, C, W, F]."""
+            out = []
+            for j, (n_fft, hop, win) in enumerate(rc.resolutions):
+                pad = (n_fft - hop) // 2
+                x = F.pad(wav[:, None, :], (pad, pad), mode="reflect")[:, 0, :]
+                spec = torch.stft(x, n_fft, hop_length=hop, win_length=win, window=torch.ones(win, device=wav.device), center=False, return_complex=True)
+                h, maps = torch.linalg.vector_norm(torch.view_as_real(spec), dim=-1)[:, None], []
+                for i, (_ci, _co, (kf, kt), stride) in enumerate(rshapes):
+                    name = f"discriminators.{j}.conv_post" if i == len(rshapes) - 1 else f"discriminators.{j}.convs.{i}"
+                    h = F.conv2d(h, rparams[name + ".weight"], rparams[name + ".bias"], stride=(1, stride), padding=(kf // 2, kt // 2))
+                    if i < len(rshapes) - 1:
+                        h = F.leaky_relu(h, rc.leaky_slope)
+                    maps.append(h.transpose(2, 3))
+                out.append(maps)
+            return out
+
+        gen = torch.Generator(device="cuda").manual_seed(0)
+        for B, n in ((16, 8192), (32, 8192)):
+            key = f"mrd_{B}x{n}"
+            wav = (0.3 * torch.randn(B, n, device="cuda", generator=gen)).requires_grad_(True)
+            with torch.no_grad():
+                ours_maps, torch_maps = mrd(wav), torch_mrd(wav)
+                res[key] = {"forward": ev_spread(lambda: mrd(wav)), "torch_forward": ev_spread(lambda: torch_mrd(wav))}
+            res[key]["max_relative_map_difference_from_torch"] = max(float((a - b).abs().max() / b.abs().max()) for x, y in zip(ours_maps, torch_maps) for a, b in zip(x, y))
+            cots = [[torch.randn(m.shape, device="cuda", generator=gen) / m.numel() for m in ms] for ms in ours_maps]
+
+            def step(net):
+                wav.grad = None
+                for p in rparams.values():
+                    p.grad = None
+                sum((m * c).sum() for ms, cs in zip(net(wav), cots) for m, c in zip(ms, cs)).backward()
+
+            res[key]["forward_plus_backward"] = ev_spread(lambda: step(mrd))
+            got = {k: p.grad.clone() for k, p in rparams.items()}
+            got["wav"] = wav.grad.clone()
+            res[key]["torch_forward_plus_backward"] = ev_spread(lambda: step(torch_mrd))
+            res[key]["max_relative_gradient_difference_from_torch"] = max(
+                [float((got[k] - p.grad).abs().max() / p.grad.abs().max().clamp_min(1e-30)) for k, p in rparams.items()]
+                + [float((got["wav"] - wav.grad).abs().max() / wav.grad.abs().max())])
+            res[key]["leaky_relu_decisions_that_differ"] = sum(int(((a > 0) != (b > 0)).sum()) for x, y in zip(ours_maps, torch_maps) for a, b in zip(x[:-1], y[:-1]))
+            res[key]["forward_workspace_mb"] = round(mrd._workspace.numel() / 1e6, 1)
+            res[key]["backward_workspace_mb"] = round(mrd._train_workspace.numel() / 1e6, 1)
+            res[key]["features_mb"] = round(_lib.load().gvx_mrd_features_bytes(C.byref(mrd.dims()), B, n) / 1e6, 1)
+            lib = _lib.load()
+            _lib.check(lib.gvx_mrd_timing_enable(mrd._handle, 1))
+            step(mrd)
+            fwd_ms, bwd_ms, n_l = (C.c_float * 9)(), (C.c_float * 9)(), C.c_int()
+            _lib.check(lib.gvx_mrd_layer_times_ms(mrd._handle, fwd_ms, bwd_ms, C.byref(n_l)))
+            _lib.check(lib.gvx_mrd_timing_enable(mrd._handle, 0))
+            widths = mrd.map_widths(n)
+            macs = [B * sum(widths[j][i] * (nf // 2 + 1) * co * ci * kf * kt for j, (nf, _h, _w) in enumerate(rc.resolutions))
+                    for i, (ci, co, (kf, kt), _s) in enumerate(rshapes)]
+            res[key]["layers"] = [{"layer": f"{ci}->{co} {kf}x{kt}", "forward_gmacs": round(m / 1e9, 3), "forward_ms": round(fwd_ms[i], 3), "backward_ms": round(bwd_ms[i], 3)}
+                                  for i, ((ci, co, (kf, kt), _s), m) in enumerate(zip(rshapes, macs))]
+            print(json.dumps({key: res[key]}), flush=True)
     if which & {"hifigan", "hifigan_train"}:
         import ctypes as C
         import statistics
