@@ -245,9 +245,29 @@ class DeviceGenerator(DeviceModule):
         """-> (the channels in front of the first upsampling stage, every stage's rate); a stage halves the channels."""
         raise NotImplementedError
 
+    def _stage_tensor_shapes(self, T: int):
+        """-> the (positions, channels) of every ``stage_outputs`` tensor of a call on ``T`` frames, in the C ABI's order.  The default
+        is the upsampling generators' arithmetic on ``_stage_shapes()``: a stage multiplies the positions by its rate and halves the
+        channels."""
+        c, rates = self._stage_shapes()
+        shapes, mul = [], 1
+        for r in rates:
+            mul, c = mul * r, c // 2
+            shapes.append((T * mul, c))
+        return shapes
+
     @property
     def hop(self) -> int:
         return self.model_config.hop
+
+    def sample_counts(self, frame_lengths):
+        """Frame counts (an int, a list or a tensor) -> the samples a row of that many frames delivers: ``t * hop`` unless the model
+        says otherwise."""
+        if isinstance(frame_lengths, torch.Tensor):
+            return frame_lengths * self.hop
+        if isinstance(frame_lengths, int):
+            return frame_lengths * self.hop
+        return [int(t) * self.hop for t in frame_lengths]
 
     def blob_numel(self) -> int:
         return self._c("blob_floats")(C.byref(self.dims()))
@@ -296,11 +316,7 @@ class DeviceGenerator(DeviceModule):
         wav = torch.empty(B, T * self.hop, dtype=torch.float32, device=dev)
         stages = None
         if stage_outputs:
-            c, rates = self._stage_shapes()
-            stages, mul = [], 1
-            for r in rates:
-                mul, c = mul * r, c // 2
-                stages.append(torch.empty(B, T * mul, c, dtype=torch.float32, device=dev))
+            stages = [torch.empty(B, n, c, dtype=torch.float32, device=dev) for n, c in self._stage_tensor_shapes(T)]
         rows = B
         if workspace is None:
             while rows > 1 and self.workspace_bytes(rows, T) > self.WORKSPACE_CAP_BYTES:
@@ -339,9 +355,9 @@ class DeviceGenerator(DeviceModule):
         mel, lens = inputs["mel"], inputs.get("mel_lengths")
         wav = self.vocode(mel, lens)
         if lens is None:
-            lengths = torch.full((mel.shape[0],), mel.shape[2] * self.hop, dtype=torch.int32, device=wav.device)
+            lengths = torch.full((mel.shape[0],), self.sample_counts(int(mel.shape[2])), dtype=torch.int32, device=wav.device)
         else:
-            lengths = torch.as_tensor(lens).to(wav.device, torch.int32) * self.hop
+            lengths = self.sample_counts(torch.as_tensor(lens).to(wav.device, torch.int32))
         return {"waveform": wav, "lengths": lengths}
 
     def forward(self, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:

@@ -44,6 +44,10 @@ class gvx_bigvgan_dims(C.Structure):
     _fields_ = [("net", gvx_hifigan_dims), ("snakebeta", C.c_int32), ("tanh_at_final", C.c_int32), ("bias_at_final", C.c_int32)]
 
 
+class gvx_vocos_dims(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("n_mels", "dim", "intermediate_dim", "num_layers", "n_fft", "hop_length", "center")]
+
+
 class gvx_melgan_tape_entry(C.Structure):
     _fields_ = [("byte_offset", C.c_uint64), ("positions_per_frame", C.c_int32), ("channels", C.c_int32)]
 
@@ -268,6 +272,18 @@ SIGNATURES = {
     "gvx_bigvgan_forward": (_i, [_vp, _vp, _vp, _i, _i, _vp, C.POINTER(_vp), _vp, _sz, _vp]),
     "gvx_bigvgan_timing_enable": (_i, [_vp, _i]),
     "gvx_bigvgan_stage_times_ms": (_i, [_vp, C.POINTER(_f), C.POINTER(_i)]),
+    "gvx_dwconv_layernorm": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp]),
+    "gvx_istft_head_workspace_bytes": (_sz, [_i, _i, _i]),
+    "gvx_istft_head": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "gvx_vocos_blob_floats": (_sz, [C.POINTER(gvx_vocos_dims)]),
+    "gvx_vocos_workspace_bytes": (_sz, [C.POINTER(gvx_vocos_dims), _i, _i]),
+    "gvx_vocos_pack_weights_device": (_i, [C.POINTER(gvx_vocos_dims), C.POINTER(gvx_weight_desc), _i, _vp, _vp]),
+    "gvx_vocos_create": (_i, [C.POINTER(gvx_vocos_dims), C.POINTER(_vp)]),
+    "gvx_vocos_destroy": (None, [_vp]),
+    "gvx_vocos_bind": (_i, [_vp, _vp]),
+    "gvx_vocos_forward": (_i, [_vp, _vp, _vp, _i, _i, _vp, C.POINTER(_vp), _vp, _sz, _vp]),
+    "gvx_vocos_timing_enable": (_i, [_vp, _i]),
+    "gvx_vocos_stage_times_ms": (_i, [_vp, C.POINTER(_f), C.POINTER(_i)]),
     "gvx_hifigan_mpd_blob_floats": (_sz, [C.POINTER(gvx_hifigan_mpd_dims)]),
     "gvx_hifigan_mpd_pack_weights_device": (_i, [C.POINTER(gvx_hifigan_mpd_dims), C.POINTER(gvx_weight_desc), _i, _vp, _vp]),
     "gvx_hifigan_mpd_create": (_i, [C.POINTER(gvx_hifigan_mpd_dims), C.POINTER(_vp)]),

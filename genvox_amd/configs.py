@@ -384,6 +384,62 @@ class BigVGANConfig(HiFiGANConfig):
                 raise ValueError(f"{name} must be true or false, not {getattr(self, name)!r}")
 
 
+class VocosConfig(BaseConfig):
+    """The Vocos generator, mel variant (Siuzdak 2023; include/genvox_amd.h, "Vocos generator").  The reference ships no such model; the
+    fields carry the names of the published ``config.yaml`` and the defaults of ``charactr/vocos-mel-24khz``.  ``input_channels`` is the
+    audio config's ``n_mels``; the window is the periodic Hann of ``n_fft`` points; ``hop_length`` must be the audio config's
+    (``check_hop``).  The ranges are what the kernels take."""
+
+    N_FFTS = (512, 1024, 2048)   # the sizes the in-LDS FFT has
+    MAX_DIM = 512                # GVX_VOCOS_MAX_DIM
+    MAX_INTERMEDIATE = 8192      # GVX_VOCOS_MAX_INTERMEDIATE
+    MAX_LAYERS = 64              # GVX_VOCOS_MAX_LAYERS
+
+    _FIELDS = {
+        "dim": (512, None),
+        "intermediate_dim": (1536, None),
+        "num_layers": (8, None),
+        "n_fft": (1024, None),
+        "hop_length": (256, None),
+        "padding": ("center", None),
+        "layer_scale_init_value": (None, None),
+    }
+
+    def _normalise(self) -> None:
+        for name in ("dim", "intermediate_dim", "num_layers", "n_fft", "hop_length"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise ValueError(f"{name} must be an integer, not {v!r}")
+        if self.n_fft not in self.N_FFTS:
+            raise ValueError(f"n_fft = {self.n_fft} is not one of {self.N_FFTS}, the sizes the FFT kernels have")
+        if not self.n_fft // 8 <= self.hop_length <= self.n_fft // 2:
+            raise ValueError(f"hop_length = {self.hop_length} is outside [n_fft / 8, n_fft / 2] = [{self.n_fft // 8}, {self.n_fft // 2}]")
+        if (self.n_fft - self.hop_length) % 2:
+            raise ValueError(f"hop_length = {self.hop_length}: n_fft - hop_length must be even, the trim of either end is half of it")
+        for name, most in (("dim", self.MAX_DIM), ("intermediate_dim", self.MAX_INTERMEDIATE)):
+            v = getattr(self, name)
+            if v % 32 or not 32 <= v <= most:
+                raise ValueError(f"{name} = {v} must be a multiple of 32 in [32, {most}]")
+        if not 1 <= self.num_layers <= self.MAX_LAYERS:
+            raise ValueError(f"num_layers = {self.num_layers} is outside [1, {self.MAX_LAYERS}]")
+        if self.padding not in ("center", "same"):
+            raise ValueError(f"padding must be 'center' or 'same', not {self.padding!r}")
+        if self.layer_scale_init_value is not None:
+            self.layer_scale_init_value = float(self.layer_scale_init_value)
+
+    @property
+    def hop(self) -> int:
+        return self.hop_length
+
+    @property
+    def layer_scale(self) -> float:
+        return 1.0 / self.num_layers if self.layer_scale_init_value is None else self.layer_scale_init_value
+
+    def check_hop(self, hop_length: int) -> None:
+        if self.hop_length != int(hop_length):
+            raise ValueError(f"hop_length = {self.hop_length}, the audio config's hop_length is {hop_length}")
+
+
 class HiFiGANPeriodDiscriminatorConfig(BaseConfig):
     """HiFi-GAN's multi-period discriminator (Kong et al. 2020; include/genvox_amd.h, "HiFi-GAN period discriminators").  The defaults
     are the published ``MultiPeriodDiscriminator``; the ranges are what the kernels take."""

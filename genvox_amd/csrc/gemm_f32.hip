@@ -58,7 +58,15 @@ __device__ __forceinline__ long row_off(const RowMap& m, int row) {
 //   EPI_PARENT   the epilogue all launches had before the kinds, kept word for word (a division pair per row, every load
 //                behind its own wait): gvx_debug_gemm_parent_epilogue / GVX_GEMM_EPILOGUE=parent select it for tests and A/B runs
 // All four store the same values to the same addresses.
-enum Epi : int { EPI_PARENT = 0, EPI_GENERAL = 1, EPI_PLAIN = 2, EPI_BIAS = 3 };
+// Two more kinds carry what no launch had before them (the Vocos MLP, vocos.hip); they share EPI_BIAS's hoisted bias and EPI_GENERAL's
+// row_len zeros, and nothing else is in them:
+//   EPI_GELU     C = gelu(acc + bias[n]), the erf form             (act = ACT_GELU with a bias; pwconv1)
+//   EPI_RES      C = acc + bias[n] + res(m, n)                     (res set, with a bias; pwconv2 and the block's residual)
+enum Epi : int { EPI_PARENT = 0, EPI_GENERAL = 1, EPI_PLAIN = 2, EPI_BIAS = 3, EPI_GELU = 4, EPI_RES = 5 };
+
+// nn.GELU(): x Phi(x) with the library's erff (1 ulp; the 1 + erf cancellation for x < 0 costs an absolute 6e-8 |x|, below an ulp of
+// the tensor's scale)
+__device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752f)); }
 
 // KMAJ: both operands are K-major - element (m, k) of A at A + amap(k) + m, element (n, k) of W at W + wmap(k) + n - the
 // form of a weight gradient (sum over the rows of two activation matrices) without transposed copies.
@@ -255,6 +263,8 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int blo
     // touch - at most 32 consecutive groups (R >= 1), lane l holds the one of group grp_w + (l & 31), and a row reads its own with
     // a cross-lane move.
     constexpr bool EPI_GEN = EPI == EPI_GENERAL;
+    constexpr bool EPI_VOC = EPI == EPI_GELU || EPI == EPI_RES;   // a bias always, row_len where the launch has one
+    constexpr bool EPI_LEN = EPI_GEN || EPI_VOC;
     float bias_v[TN];
     RowWalk walk0[TM];
     int len_v[TM], grp_w[TM];
@@ -263,14 +273,14 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int blo
         for (int j = 0; j < TN; ++j) {
             const int n = n0 + (wc * TN + j) * 32 + r;
             bias_v[j] = 0.f;
-            if constexpr (EPI == EPI_BIAS) { if (n < p.N) bias_v[j] = p.bias[n]; }
+            if constexpr (EPI == EPI_BIAS || EPI_VOC) { if (n < p.N) bias_v[j] = p.bias[n]; }
             if constexpr (EPI_GEN) { if (p.bias && n < p.N) bias_v[j] = p.bias[n]; }
         }
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
             walk0[i] = row_walk_begin(p.cmap, m0 + (wr * TM + i) * 32 + 4 * h);
             len_v[i] = 0; grp_w[i] = 0;
-            if constexpr (EPI_GEN) {
+            if constexpr (EPI_LEN) {
                 grp_w[i] = __builtin_amdgcn_readfirstlane(walk0[i].grp);   // lane 0: h = 0, the M tile's first row
                 const int g = grp_w[i] + r;
                 if (p.row_len && (long)g * p.cmap.R < p.M) len_v[i] = p.row_len[g];
@@ -289,20 +299,22 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int blo
     if constexpr (EPI != EPI_PARENT) {
         // the lane's columns: where they lie in a row of C, once
         float* c_col[TN]; bool n_ok[TN];
+        [[maybe_unused]] const float* r_col[TN];
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             const int n = n0 + (wc * TN + j) * 32 + r;
             n_ok[j] = n < p.N;
             c_col[j] = Cout + (long)(n >> 3) * p.c_nblk + (n & 7);
+            if constexpr (EPI == EPI_RES) r_col[j] = p.res + slice * p.c_slice + (long)(n >> 3) * p.c_nblk + (n & 7);
         }
-        const bool has_bias = EPI_GEN && p.bias, has_len = EPI_GEN && p.row_len, has_halo = EPI_GEN && p.c_halo > 0;
+        const bool has_bias = EPI_GEN && p.bias, has_len = EPI_LEN && p.row_len, has_halo = EPI_GEN && p.c_halo > 0;
         const long halo_step = EPI_GEN ? (long)p.c_halo * p.cmap.s0 : 0;
         // The hoisted loads are waited for ONCE, here, in straight-line code and by hand.  Left to the compiler, their first use
         // lies inside one of the row loop's predicated blocks (it sinks the bias additions below into them), the load still
         // counts as pending on the path around the block, and so EVERY such block got an s_waitcnt vmcnt(0) - which there waits
         // for all the stores before it.
         if constexpr (EPI != EPI_PLAIN) __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0) alone: the expcnt and lgkmcnt fields at their maxima
-        if (EPI == EPI_BIAS || has_bias) {
+        if (EPI == EPI_BIAS || EPI_VOC || has_bias) {
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -323,9 +335,11 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int blo
                 }
                 const bool m_ok = m_first + (q & 3) + 8 * (q >> 2) < p.M;
                 bool live = true, halo_front = false, halo_back = false;
-                if constexpr (EPI_GEN) {
+                if constexpr (EPI_LEN) {
                     // (every lane takes part in the cross-lane move: no row has left the loop, rows past M only skip their stores)
                     if (has_len) live = w.idx < __shfl(len_v[i], w.grp - grp_w[i]);
+                }
+                if constexpr (EPI_GEN) {
                     // conv output with halo rows: the first / last c_halo interior rows of a sequence also zero one halo row each
                     halo_front = has_halo && w.idx < p.c_halo;
                     halo_back = has_halo && w.idx >= p.cmap.R - p.c_halo;
@@ -339,6 +353,8 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int blo
                         else if (p.act == ACT_TANH) v = tanhf(v);
                         if (p.keep) v = keep_row[j * 32] ? 2.f * v : 0.f;
                     }
+                    if constexpr (EPI == EPI_GELU) v = gelu_erf(v);
+                    if constexpr (EPI == EPI_RES) v += r_col[j][w.off];
                     c_col[j][w.off] = live ? v : 0.f;
                     if (halo_front) c_col[j][w.off - halo_step] = 0.f;
                     if (halo_back) c_col[j][w.off + halo_step] = 0.f;
@@ -405,15 +421,18 @@ static hipError_t launch_cfg(const GemmParams& p, hipStream_t s) {
 // shape; EPI_PLAIN and EPI_BIAS only where the forward launches them (a bit per kind) - the Winograd products on the three
 // square-ish row-major tiles, bias-only products on those and on the two N <= 96 tiles (the mel / gate projection).  A launch of
 // a special kind on a shape without it takes EPI_GENERAL: the same stores, with the run-time checks.
-constexpr int KIND_PLAIN = 1 << EPI_PLAIN, KIND_BIAS = 1 << EPI_BIAS;
+// EPI_GELU and EPI_RES (KIND_VOC: both) exist on every row-major shape: the Vocos MLP's two products have N = intermediate_dim and
+// N = dim, any multiples of 32, so plan_gemm sends them to each of these by N and by the row count.  They have no EPI_GENERAL to
+// fall back to: a launch of one on a shape without it (the K-major forms) is refused.
+constexpr int KIND_PLAIN = 1 << EPI_PLAIN, KIND_BIAS = 1 << EPI_BIAS, KIND_GELU = 1 << EPI_GELU, KIND_RES = 1 << EPI_RES, KIND_VOC = KIND_GELU | KIND_RES;
 #define GVX_GEMM_SHAPES(X)                            \
-    X(4111, 4, 1, 1, 1, false, 0)                     \
-    X(2311, 2, 3, 1, 1, false, KIND_BIAS)             \
-    X(4113, 4, 1, 1, 3, false, KIND_BIAS)             \
-    X(2211, 2, 2, 1, 1, false, KIND_PLAIN | KIND_BIAS) \
-    X(2212, 2, 2, 1, 2, false, KIND_PLAIN | KIND_BIAS) \
-    X(2222, 2, 2, 2, 2, false, 0)                     \
-    X(4212, 4, 2, 1, 2, false, KIND_PLAIN | KIND_BIAS) \
+    X(4111, 4, 1, 1, 1, false, KIND_VOC)              \
+    X(2311, 2, 3, 1, 1, false, KIND_BIAS | KIND_VOC)  \
+    X(4113, 4, 1, 1, 3, false, KIND_BIAS | KIND_VOC)  \
+    X(2211, 2, 2, 1, 1, false, KIND_PLAIN | KIND_BIAS | KIND_VOC) \
+    X(2212, 2, 2, 1, 2, false, KIND_PLAIN | KIND_BIAS | KIND_VOC) \
+    X(2222, 2, 2, 2, 2, false, KIND_VOC)              \
+    X(4212, 4, 2, 1, 2, false, KIND_PLAIN | KIND_BIAS | KIND_VOC) \
     X(2212, 2, 2, 1, 2, true, 0)                      \
     X(2222, 2, 2, 2, 2, true, 0)
 
@@ -423,6 +442,8 @@ static hipError_t init_shape() {
     if (e == hipSuccess) e = init_cfg<WR, WC, TM, TN, KMAJ, EPI_PARENT>();
     if constexpr ((KINDS & KIND_PLAIN) != 0) { if (e == hipSuccess) e = init_cfg<WR, WC, TM, TN, KMAJ, EPI_PLAIN>(); }
     if constexpr ((KINDS & KIND_BIAS) != 0) { if (e == hipSuccess) e = init_cfg<WR, WC, TM, TN, KMAJ, EPI_BIAS>(); }
+    if constexpr ((KINDS & KIND_GELU) != 0) { if (e == hipSuccess) e = init_cfg<WR, WC, TM, TN, KMAJ, EPI_GELU>(); }
+    if constexpr ((KINDS & KIND_RES) != 0) { if (e == hipSuccess) e = init_cfg<WR, WC, TM, TN, KMAJ, EPI_RES>(); }
     return e;
 }
 
@@ -430,6 +451,9 @@ template <int WR, int WC, int TM, int TN, bool KMAJ, int KINDS>
 static hipError_t launch_shape(int epi, const GemmParams& p, hipStream_t s) {
     if constexpr ((KINDS & KIND_PLAIN) != 0) { if (epi == EPI_PLAIN) return launch_cfg<WR, WC, TM, TN, KMAJ, EPI_PLAIN>(p, s); }
     if constexpr ((KINDS & KIND_BIAS) != 0) { if (epi == EPI_BIAS) return launch_cfg<WR, WC, TM, TN, KMAJ, EPI_BIAS>(p, s); }
+    if constexpr ((KINDS & KIND_GELU) != 0) { if (epi == EPI_GELU) return launch_cfg<WR, WC, TM, TN, KMAJ, EPI_GELU>(p, s); }
+    if constexpr ((KINDS & KIND_RES) != 0) { if (epi == EPI_RES) return launch_cfg<WR, WC, TM, TN, KMAJ, EPI_RES>(p, s); }
+    if (epi == EPI_GELU || epi == EPI_RES || epi < 0) return hipErrorInvalidValue;   // no general form of these
     if (epi == EPI_PARENT) return launch_cfg<WR, WC, TM, TN, KMAJ, EPI_PARENT>(p, s);
     return launch_cfg<WR, WC, TM, TN, KMAJ, EPI_GENERAL>(p, s);
 }
@@ -456,6 +480,12 @@ int gemm_set_parent_epilogue(int on) {
 
 // The epilogue kind of a launch, from what its parameters ask for
 static int epilogue_kind(const GemmParams& p) {
+    // the two kinds the parent's epilogue never had (no launch could ask for them before they existed); anything beside their bias
+    // and row_len is refused (-1)
+    if (p.act == ACT_GELU || p.res) {
+        if (!p.bias || p.keep || p.c_halo > 0 || p.splitk > 1 || (p.res && p.act != ACT_NONE)) return -1;
+        return p.res ? EPI_RES : EPI_GELU;
+    }
     if (parent_epilogue()) return EPI_PARENT;
     if (p.act == ACT_RELU || p.act == ACT_TANH || p.keep || p.row_len || p.c_halo > 0) return EPI_GENERAL;
     return p.bias ? EPI_BIAS : EPI_PLAIN;
@@ -527,12 +557,13 @@ long gemm_round_rows(const GemmParams& p) {
 // launches exactly this; gvx_debug_gemm_epilogue reports it)
 int gemm_epilogue_of(int tile, const GemmParams& p) {
     const int want = epilogue_kind(p);
-    if (want != EPI_PLAIN && want != EPI_BIAS) return want;
+    if (want < 0 || want == EPI_PARENT || want == EPI_GENERAL) return want;
+    const int without = want == EPI_GELU || want == EPI_RES ? -1 : (int)EPI_GENERAL;
 #define GVX_GEMM_HAS(TILE, WR, WC, TM, TN, KMAJ, KINDS) \
-    if (tile == TILE && p.kmajor == KMAJ) return ((KINDS) >> want) & 1 ? want : (int)EPI_GENERAL;
+    if (tile == TILE && p.kmajor == KMAJ) return ((KINDS) >> want) & 1 ? want : without;
     GVX_GEMM_SHAPES(GVX_GEMM_HAS)
 #undef GVX_GEMM_HAS
-    return EPI_GENERAL;
+    return without;
 }
 
 static hipError_t launch_tile(int tile, const GemmParams& p, hipStream_t s) {

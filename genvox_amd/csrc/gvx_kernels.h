@@ -26,7 +26,7 @@ int set_error(int code, const char* msg);
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2 };
+enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2, ACT_GELU = 3 };   // ACT_GELU: the erf form, with a bias, as a compile-time kind of its own
 
 // ---------------------------------------------------------------------------------------------
 // Dense GEMM  C[m][n] = epi(sum_k A(m,k) * W[n][k])  on v_mfma_f32_32x32x2_f32 (exact fp32).
@@ -86,6 +86,9 @@ struct GemmParams {
     // slice z reads A + z * a_slice and W + z * w_slice and writes C + z * c_slice; bias, row_len and the row maps are shared.
     // grid.y carries the slice, so splitk must be 1 then (row-major operands, no keep mask)
     int slices = 1; long a_slice = 0, w_slice = 0, c_slice = 0;
+    // residual: element (m, n) of `res`, addressed as C's is (cmap, c_nblk, c_slice), is added behind the bias.  res may be C itself.
+    // Needs a bias and no activation, keep mask or halo (a compile-time kind of its own, as ACT_GELU with a bias is)
+    const float* res = nullptr;
 };
 hipError_t launch_gemm(const GemmParams& p, hipStream_t s);
 // What launch_gemm does with p, as host arithmetic (no device is touched).  tile: the <WR,WC,TM,TN> shape as the four digits

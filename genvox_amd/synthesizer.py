@@ -200,8 +200,8 @@ def frame_ratios(start_frames: Sequence[int], n_frames: int, per_token_semitones
 class Synthesizer:
     def __init__(self, tts_model_class, tts_config_path: str, tts_checkpoint_path: str, use_cuda: bool = True, vocoder_model_class=None,
                  vocoder_config_path: Optional[str] = None, vocoder_checkpoint_path: Optional[str] = None) -> None:
-        """``vocoder_model_class`` (``MelGANGenerator``, ``HiFiGANGenerator`` or ``BigVGANGenerator``) with its config and checkpoint paths: ``tts`` and ``tts_batch`` vocode the mel
-        through that model instead of Griffin-Lim.  The waveform is then float32 of exactly ``frames * hop_length`` samples (no trim,
+        """``vocoder_model_class`` (``MelGANGenerator``, ``HiFiGANGenerator``, ``BigVGANGenerator`` or ``VocosGenerator``) with its config and checkpoint paths: ``tts`` and ``tts_batch`` vocode the mel
+        through that model instead of Griffin-Lim.  The waveform is then float32 of exactly ``frames * hop_length`` samples (``(frames - 1) * hop_length`` from a Vocos model with padding "center"; no trim,
         no low-pass), and every result carries ``"vocoder"``: the model's name.  All three or none: with none nothing changes."""
         if not (use_cuda and torch.cuda.is_available()):
             raise RuntimeError("genvox_amd.Synthesizer needs an MI355X (use_cuda=True and a visible GPU); it has no CPU path")
@@ -266,7 +266,7 @@ class Synthesizer:
             return {"token_timings": [], "word_timings": [], "timings_status": "infeasible"}
         ap = self.audio_processor
         # a neural vocoder delivers frames * hop samples untrimmed: frame f starts at sample f * hop
-        trim, n_samples = (ap.TRIM, ap.row_samples([n_frames])[0]) if self.vocoder is None else (0, n_frames * ap.config.hop_length)
+        trim, n_samples = (ap.TRIM, ap.row_samples([n_frames])[0]) if self.vocoder is None else (0, self.vocoder.sample_counts(int(n_frames)))
         starts, ends = token_times(start_frames[:len(token_strs)], ap.config.hop_length, trim, n_samples, ap.config.sampling_rate, n_delivered / out_rate)
         return {"token_timings": list(zip(token_strs, starts, ends)), "word_timings": group_words(token_strs, starts, ends),
                 "timings_status": "ok"}
@@ -274,7 +274,7 @@ class Synthesizer:
     def _vocode(self, mel: torch.Tensor, frames, sampling_rate: Optional[int]):
         """mel [B, M, T] on the device -> ``(waveforms on the device, sample counts per row or None)``; ``frames`` (None: all T) are the
         rows' own lengths.  Without a vocoder model this is ``AudioProcessor.convert_mel2wav_batch`` (Griffin-Lim), call for call.
-        With one, the rows go through it in one ragged call - float32 [B, T * hop], row b of ``frames[b] * hop`` samples - and are
+        With one, the rows go through it in one ragged call - float32 [B, T * hop], row b of ``vocoder.sample_counts(frames[b])`` samples, ``frames[b] * hop`` unless the model says otherwise - and are
         resampled like Griffin-Lim's, every row at its own sample count."""
         wav, counts, _, _ = self._vocode_and_track(mel, frames, sampling_rate, False)
         return wav, counts
@@ -330,7 +330,9 @@ class Synthesizer:
         else:
             host = None if frames is None else [int(t) for t in (frames.tolist() if isinstance(frames, torch.Tensor) else frames)]
             wav = self.vocoder.vocode(mel.contiguous(), host)
-            counts = None if host is None else [t * self.vocoder.hop for t in host]
+            counts = None if host is None else self.vocoder.sample_counts(host)
+            if host is None and self.vocoder.sample_counts(int(mel.shape[2])) != wav.shape[1]:   # a model that delivers fewer than T * hop samples
+                wav = wav[:, :self.vocoder.sample_counts(int(mel.shape[2]))].contiguous()
             if denoise > 0.0:
                 wav = self._denoise(wav, counts, denoise)
             first_centre = 0

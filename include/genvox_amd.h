@@ -1292,6 +1292,91 @@ int gvx_bigvgan_forward(gvx_bigvgan* handle, const float* mel, const int32_t* fr
 int gvx_bigvgan_timing_enable(gvx_bigvgan* handle, int enable);
 int gvx_bigvgan_stage_times_ms(gvx_bigvgan* handle, float* ms_out, int* n_out);
 
+/* ---- Vocos generator, mel -> waveform (Siuzdak 2023; charactr/vocos-mel-24khz): inference.  The reference ships no such model; the
+ * network below is the published implementation's mel variant, under its names.  A ConvNeXt backbone at the FRAME rate and an inverse
+ * STFT: nothing runs at the sample rate but the transform.  Kernels: csrc/vocos.hip (filter + LayerNorm, the ISTFT frame, the
+ * overlap-add, the C ABI) on the dense fp32 GEMM (csrc/gemm_f32.hip: every product) and the in-LDS FFT (csrc/fft_lds.h).  All arithmetic
+ * is fp32; every tensor is channels-last [B][T][C].  N = n_fft, H = N / 2, LN = LayerNorm over the channels of a frame with eps 1e-6.
+ *
+ *     x = LN_norm(Conv1d(n_mels -> dim, k = 7, padding 3)(mel))                                              backbone.embed, backbone.norm
+ *     for i < num_layers:   x = x + gamma_i * pwconv2_i(GELU(pwconv1_i(LN_i(dwconv_i(x)))))                  backbone.convnext.<i>
+ *             dwconv: Conv1d(dim, dim, 7, padding 3, groups = dim);  pwconv1: Linear(dim, intermediate_dim);  GELU: the erf form
+ *     y = Linear(dim -> N + 2)(LN_final(x));   m = y[0 .. H],  p = y[H + 1 .. N + 1]                         backbone.final_layer_norm, head.out
+ *     S = min(exp(m), 100) * (cos p + i sin p);   frame = window * irfft(S, N)       (the 1 / N of the backward norm; periodic Hann of N)
+ *     wav = overlap-add of the frames at stride hop / overlap-add of window^2, trimmed by `pad` samples at either end:
+ *         center = 0 ("same"):   pad = (N - hop) / 2,  a row of T_b frames gives T_b * hop samples
+ *         center = 1 ("center"): pad = N / 2,          a row of T_b frames gives (T_b - 1) * hop samples, T_b >= 2   (torch.istft, center = True)
+ *
+ * Contracts, as for the other generators: every row runs at its own length frame_lengths[b] (NULL: all T); wav [B][T * hop] holds a
+ * row's samples in front and exact ZEROS behind them; the padded frames of mel may hold anything, NaN included, and are never read;
+ * every stage tensor is zeros at and behind a row's frames; no atomics, and every product sums its k in an order that does not depend
+ * on the tile shape or on M, so a row of a ragged batch has, bit for bit, the result of that row run alone.
+ *
+ * gvx_dwconv_layernorm is "k = 7 channel-wise filter, then LayerNorm" on its own: x and out fp32 [B][T][C] (out must not be x), lens
+ * int32 [B] on the device or NULL, taps 7 or 0 (0: the LayerNorm alone; w and b are not read), w fp32 [7][C] TAP-major
+ * (w[j][c] multiplies x[t + j - 3][c]), b, ln_w, ln_b fp32 [C].  A workgroup of four waves owns GVX_VOCOS_TILE frames of a row; the
+ * tile's P + 6 input frames go into LDS once, with zeros for frames outside [0, T_b); a wave owns one frame at a time, lanes along the
+ * channels (lane l holds channels l, l + 64, ..), and forms mean and variance as two passes over its registers (the mean first, then
+ * the squared deviations), each a butterfly over the wave.  out is zeros at and behind T_b; x is never read there.  C must be a
+ * multiple of 4 in [4, GVX_VOCOS_MAX_DIM], B in [1, 65535], T in [1, GVX_VOCOS_MAX_FRAMES]: GVX_ERR_INVALID_ARG otherwise.
+ *
+ * gvx_istft_head is the head behind its Linear: coeffs fp32 [B][T][N + 2] -> wav_out fp32 [B][T * hop].  N in {512, 1024, 2048}, hop in
+ * [N / 8, N / 2] with N - hop even, center 0 or 1, window fp32 [N] on the device.  vc_istft_kernel takes a frame per wave: exp, the
+ * clamp, sincosf and the product in registers, the pack into the H-point complex transform, the inverse transform in LDS, 1 / N and the
+ * window; the frame goes to the workspace.  vc_ola_kernel gathers each sample's frames in ascending frame order, divides by the envelope
+ * of the row's own T_b frames summed in the same order, applies the trim and writes zeros behind the row's samples.  The workspace holds
+ * the frames and the call's twiddle tables (computed in float64 on the device at every call): gvx_istft_head_workspace_bytes =
+ * round256(4 * B * T * N) + round256(8 * (N + 1)); 256-byte aligned, any contents.
+ *
+ * Weights.  gvx_vocos_pack_weights_device copies DEVICE tensors by name into the blob, every tensor starting at a multiple of 64 floats,
+ * in this order (Cp = n_mels rounded up to a multiple of 4, L = num_layers, I = intermediate_dim):
+ *     embed.weight [dim][7][Cp] (tap-major rows, zero channel padding)   embed.bias [dim]   norm.weight, norm.bias [dim]
+ *     per layer i: convnext.<i>.dwconv.weight [7][dim]  .dwconv.bias [dim]  .norm.weight, .norm.bias [dim]  .pwconv1.weight [I][dim]
+ *                  .pwconv1.bias [I]  .pwconv2.weight [dim][I]  .pwconv2.bias [dim]    (pwconv2 with gamma_i folded in by the caller)
+ *     final_layer_norm.weight, .bias [dim]   head.weight [N + 2][dim]   head.bias [N + 2]
+ * followed by the window [N] and the twiddles w_H^m [H] and w_N^k [H + 1] as float2, which the call computes itself in float64:
+ *     blob_floats = r(7 dim Cp) + 3 r(dim) + L (r(7 dim) + 4 r(dim) + 2 r(I dim) + r(I)) + 2 r(dim) + r((N + 2) dim) + r(N + 2)
+ *                   + r(N) + r(2 H) + r(2 (H + 1)),   r = round up to 64.
+ * A missing name: GVX_ERR_MISSING_WEIGHT; a wrong element count: GVX_ERR_SHAPE.
+ *
+ * Workspace: gvx_vocos_workspace_bytes is host arithmetic:
+ *     B * ( round256(4 (T + 6) Cp) + 2 round256(4 T dim) + round256(4 T I) + round256(4 T (N + 2)) + round256(4 T N) )
+ * the mel with its 3-frame zero halo, x and the A operand, the MLP's hidden tensor, the head product and the frames: 18,840 bytes per
+ * frame and row for the default model with 100 mels (and 2,400 per row for the halo).  Any contents when the call starts, nothing is cleared.
+ *
+ * gvx_vocos_forward: mel fp32 [B][n_mels][T] -> wav_out [B][T * hop_length].  stage_out, if not NULL: num_layers + 3 device tensors,
+ * x after embed + norm, after every block and after the final norm ([B][T][dim] each), then the head product [B][T][N + 2].  T below
+ * 1 + center: GVX_ERR_INVALID_ARG; the workspace missing, misaligned or short: GVX_ERR_WORKSPACE.  Launches: one transpose, the embed
+ * product, per LayerNorm or filter + LayerNorm one, per product one (two where the GEMM's plan covers the rows with two tile shapes),
+ * the frame kernel and the gather.  gvx_vocos_stage_times_ms: four durations - embed + norm, the blocks, final norm + head product,
+ * the ISTFT.  Every dims field is checked: a bad one gives blob_floats == 0 and create == GVX_ERR_INVALID_ARG.  There is no backward. */
+enum { GVX_VOCOS_TILE = 16, GVX_VOCOS_MAX_DIM = 512, GVX_VOCOS_MAX_INTERMEDIATE = 8192, GVX_VOCOS_MAX_LAYERS = 64, GVX_VOCOS_MAX_FRAMES = 1 << 20 };
+typedef struct gvx_vocos_dims {
+    int32_t n_mels;             /* >= 1 */
+    int32_t dim;                /* a multiple of 32 in [32, GVX_VOCOS_MAX_DIM]: the filter + LayerNorm tile's LDS */
+    int32_t intermediate_dim;   /* a multiple of 32 in [32, GVX_VOCOS_MAX_INTERMEDIATE] */
+    int32_t num_layers;         /* in [1, GVX_VOCOS_MAX_LAYERS] */
+    int32_t n_fft;              /* 512, 1024 or 2048 */
+    int32_t hop_length;         /* in [n_fft / 8, n_fft / 2], n_fft - hop_length even */
+    int32_t center;             /* 1: padding "center", 0: padding "same" */
+} gvx_vocos_dims;
+typedef struct gvx_vocos gvx_vocos;
+int gvx_dwconv_layernorm(const float* x, const int32_t* lens, int B, int T, int C, int taps, const float* w, const float* b,
+                         const float* ln_w, const float* ln_b, float eps, float* out, void* stream);
+size_t gvx_istft_head_workspace_bytes(int B, int T, int n_fft);
+int gvx_istft_head(const float* coeffs, const int32_t* lens, int B, int T, int n_fft, int hop, int center, const float* window,
+                   void* workspace, float* wav_out, void* stream);
+size_t gvx_vocos_blob_floats(const gvx_vocos_dims* dims);
+size_t gvx_vocos_workspace_bytes(const gvx_vocos_dims* dims, int B, int T);
+int gvx_vocos_pack_weights_device(const gvx_vocos_dims* dims, const gvx_weight_desc* table, int n, float* device_blob, void* stream);
+int gvx_vocos_create(const gvx_vocos_dims* dims, gvx_vocos** out);
+void gvx_vocos_destroy(gvx_vocos* handle);
+int gvx_vocos_bind(gvx_vocos* handle, const float* device_blob);
+int gvx_vocos_forward(gvx_vocos* handle, const float* mel, const int32_t* frame_lengths, int B, int T, float* wav_out,
+                      float* const* stage_out, void* workspace, size_t workspace_bytes, void* stream);
+int gvx_vocos_timing_enable(gvx_vocos* handle, int enable);
+int gvx_vocos_stage_times_ms(gvx_vocos* handle, float* ms_out, int* n_out);
+
 /* ---- MelGAN discriminators: the multi-scale discriminator a MelGAN generator is trained against (Kumar et al. 2019), forward and
  * backward.  The reference ships the training fields of MelGANConfig and no model; this is a statement of the published architecture.
  * All arithmetic is fp32.  lrelu and "reflect" as for the generator above; s = downsampling_factor.

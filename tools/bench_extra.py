@@ -48,7 +48,11 @@ towards layer 0) and the backward's workspace;
 events, median of 7 with the spread and the time per stage, against the float32 restatement of tests/bigvgan_ref64.py (torch's own ROCm
 convolutions, the activation as replicate padding + grouped conv_transpose1d / conv1d) on the same device and the same parameters; and
 the anti-aliased activation's launches on their own: gvx_snake_antialiased timed at every stage's shape, times the launches of that
-stage, summed, as a share of one call."""
+stage, summed, as a share of one call;
+`vocos` (on request): the Vocos generator, default configuration with 100 mels, at 32 x 800, 1 x 568 and 8 x 200 frames between device
+events, median of 7 with the spread: ours, the float32 restatement of tests/vocos_ref64.py on the same device and parameters ("torch"),
+the four stage times (embed + norm, the blocks, final norm + head product, ISTFT), and the share of the fp32 matrix rate (157.3 TFLOP/s)
+that the blocks' time amounts to for their MLP products."""
 import json
 import os
 import sys
@@ -1184,6 +1188,59 @@ def main():
                     res[key]["max_abs_difference_from_torch"] = float((ref(mel)[0] - wav).abs().max())
                 print(json.dumps({key: res[key]}), flush=True)
             del voc, ref
+    if "vocos" in which:
+        import statistics
+
+        from genvox_amd.configs import VocosConfig
+        from genvox_amd.vocos import VocosGenerator
+        from tests import vocos_ref64 as R
+
+        def ev_spread(fn, warm=2, reps=7):
+            for _ in range(warm):
+                fn()
+            out = []
+            for _ in range(reps):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                e1.synchronize()
+                out.append(e0.elapsed_time(e1))
+            return {"median_ms": round(statistics.median(out), 3), "min_ms": round(min(out), 3), "max_ms": round(max(out), 3), "runs": reps}
+
+        cfg = R.DEFAULT
+        vac = AudioConfig(filter_length=1024, hop_length=256, log_func="np.log")
+        vac.n_mels = cfg["n_mels"]
+        ref = R.Generator(cfg, seed=0).float().to("cuda:0")
+        voc = VocosGenerator(VocosConfig(), vac)
+        voc.load_state_dict(ref.state_dict())
+        voc.to("cuda:0")
+        gen = torch.Generator(device="cuda").manual_seed(0)
+        mlp_flops_per_frame = 2.0 * cfg["num_layers"] * 2 * cfg["dim"] * cfg["intermediate_dim"]
+        for B, T in ((32, 800), (1, 568), (8, 200)):
+            key = f"vocos_{B}x{T}"
+            mel = (1.5 * torch.randn(B, cfg["n_mels"], T, device="cuda", generator=gen) - 3.0).contiguous()
+            res[key] = {"ours": ev_spread(lambda: voc.vocode(mel)), "workspace_bytes": voc.workspace_bytes(B, T)}
+            voc.enable_stage_timing(True)
+            per = []
+            for _ in range(7):
+                voc.vocode(mel)
+                per.append(voc.stage_times_ms())
+            voc.enable_stage_timing(False)
+            stage = [statistics.median(col) for col in zip(*per)]
+            res[key]["stage_ms_median"] = [round(v, 3) for v in stage]   # embed + norm, the blocks, final norm + head product, ISTFT
+            res[key]["stage_ms_range"] = [[round(min(col), 3), round(max(col), 3)] for col in zip(*per)]
+            tflops = mlp_flops_per_frame * B * T / (stage[1] * 1e-3) / 1e12
+            res[key]["blocks_mlp_tflops"] = round(tflops, 1)   # the filter + LayerNorm launches count towards the time
+            res[key]["blocks_mlp_fraction_of_157TF_fp32_mfma"] = round(tflops / 157.3, 3)
+            wav = voc.vocode(mel)
+            with torch.no_grad():
+                res[key]["torch_float32_restatement"] = ev_spread(lambda: ref(mel), warm=1, reps=7)
+                want = ref(mel)[0]
+            res[key]["max_abs_difference_from_torch"] = float((want - wav[:, :want.shape[1]]).abs().max())
+            res[key]["verdict"] = "faster" if res[key]["ours"]["median_ms"] < res[key]["torch_float32_restatement"]["median_ms"] else "SLOWER"
+            print(json.dumps({key: res[key]}), flush=True)
+        del voc, ref
     if "cpu" in which:
         # CPU baselines for configs 3 and 4 (the oracle = CPU restatement of the reference, on this box's host cores):
         # bounded samples, reported beside the GPU figures above; bench.py carries the one for config 2.
