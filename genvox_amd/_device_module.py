@@ -301,15 +301,25 @@ class DeviceGenerator(DeviceModule):
             raise ValueError(f"a mel of {B} rows and {T} frames: every row needs at least {self._short_tail}")
         return dev, B, T, lens_dev
 
-    def vocode(self, mel: torch.Tensor, mel_lengths=None, stage_outputs: bool = False, workspace: Optional[torch.Tensor] = None):
+    def _check_extra(self, extra, dev: torch.device, B: int, T: int):
+        """``vocode``'s ``_extra``, checked behind the mel and the lengths -> what ``_forward_extra`` is handed.  The default takes none."""
+        return extra
+
+    def _forward_extra(self, extra, lo: int, n: int):
+        """The arguments of ``<_abi>_forward`` between ``mel`` and the frame lengths for rows [lo, lo + n) of ``vocode``'s ``_extra``:
+        none, unless the model takes a second per-row input (UnivNet's noise)."""
+        return ()
+
+    def vocode(self, mel: torch.Tensor, mel_lengths=None, stage_outputs: bool = False, workspace: Optional[torch.Tensor] = None, _extra=None):
         """mel float32 [B, n_mels, T] on the device, on the mel scale the weights were trained on -> waveform float32 [B, T * hop].
         ``mel_lengths`` ([B], host or device): every row at its own frames - bit for bit that row run alone - and exact zeros behind
         ``T_b * hop`` samples; the padded frames of ``mel`` may hold anything.  A row outside [the least frame count, T] raises
         ValueError before anything is launched.  A batch whose workspace would pass ``WORKSPACE_CAP_BYTES`` is run in groups of rows;
         rows do not depend on each other, so the split changes no bit.  ``stage_outputs``: also the list of x after every stage,
         [B, len_i, C_i] channels-last (tests).  ``workspace``: a uint8 tensor to use as it is, of at least ``workspace_bytes(B, T)``
-        (tests of the workspace contract; no row split then)."""
+        (tests of the workspace contract; no row split then).  ``_extra``: what a subclass hands its own ``_check_extra`` and ``_forward_extra``."""
         dev, B, T, lens_dev = self._check_call(mel, mel_lengths)
+        _extra = self._check_extra(_extra, dev, B, T)
         h = self._ensure_packed()
         forward = self._c("forward")
         mel = mel.contiguous()
@@ -327,7 +337,8 @@ class DeviceGenerator(DeviceModule):
             ptrs = None
             if stages is not None:
                 ptrs = (C.c_void_p * len(stages))(*[s[lo:lo + n].data_ptr() for s in stages])
-            _lib.check(forward(h, mel[lo:lo + n].data_ptr(), lens_dev[lo:lo + n].data_ptr() if lens_dev is not None else None, n, T,
+            _lib.check(forward(h, mel[lo:lo + n].data_ptr(), *self._forward_extra(_extra, lo, n),
+                               lens_dev[lo:lo + n].data_ptr() if lens_dev is not None else None, n, T,
                                wav[lo:lo + n].data_ptr(), ptrs, workspace.data_ptr(), workspace.numel(), self._stream(dev)))
         return (wav, stages) if stage_outputs else wav
 
@@ -349,11 +360,16 @@ class DeviceGenerator(DeviceModule):
         self._check_trainable()
         return _VocodeWithGrad.apply(self, mel.contiguous(), lens_dev, *self.parameters())
 
+    def vocode_utterances(self, mel: torch.Tensor, mel_lengths=None) -> torch.Tensor:
+        """What ``inference`` and ``Synthesizer`` call on whole utterances: ``vocode``, unless the model's published inference does more
+        (UnivNet pads every utterance's end and drops the padding's samples)."""
+        return self.vocode(mel, mel_lengths)
+
     def inference(self, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         """{"mel": [B, n_mels, T], "mel_lengths": optional [B]} -> {"waveform": float32 [B, T * hop] on the device, "lengths": int32 [B]
         sample counts}."""
         mel, lens = inputs["mel"], inputs.get("mel_lengths")
-        wav = self.vocode(mel, lens)
+        wav = self.vocode_utterances(mel, lens)
         if lens is None:
             lengths = torch.full((mel.shape[0],), self.sample_counts(int(mel.shape[2])), dtype=torch.int32, device=wav.device)
         else:

@@ -48,6 +48,12 @@ class gvx_vocos_dims(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("n_mels", "dim", "intermediate_dim", "num_layers", "n_fft", "hop_length", "center")]
 
 
+class gvx_univnet_dims(C.Structure):
+    _fields_ = [("n_mels", C.c_int32), ("noise_dim", C.c_int32), ("channel_size", C.c_int32), ("n_dilations", C.c_int32),
+                ("dilations", C.c_int32 * 8), ("n_blocks", C.c_int32), ("strides", C.c_int32 * 4), ("kpnet_hidden_channels", C.c_int32),
+                ("kpnet_conv_size", C.c_int32), ("slope", C.c_float)]
+
+
 class gvx_melgan_tape_entry(C.Structure):
     _fields_ = [("byte_offset", C.c_uint64), ("positions_per_frame", C.c_int32), ("channels", C.c_int32)]
 
@@ -284,6 +290,16 @@ SIGNATURES = {
     "gvx_vocos_forward": (_i, [_vp, _vp, _vp, _i, _i, _vp, C.POINTER(_vp), _vp, _sz, _vp]),
     "gvx_vocos_timing_enable": (_i, [_vp, _i]),
     "gvx_vocos_stage_times_ms": (_i, [_vp, C.POINTER(_f), C.POINTER(_i)]),
+    "gvx_lvc_gated": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
+    "gvx_univnet_blob_floats": (_sz, [C.POINTER(gvx_univnet_dims)]),
+    "gvx_univnet_workspace_bytes": (_sz, [C.POINTER(gvx_univnet_dims), _i, _i]),
+    "gvx_univnet_pack_weights_device": (_i, [C.POINTER(gvx_univnet_dims), C.POINTER(gvx_weight_desc), _i, _vp, _vp]),
+    "gvx_univnet_create": (_i, [C.POINTER(gvx_univnet_dims), C.POINTER(_vp)]),
+    "gvx_univnet_destroy": (None, [_vp]),
+    "gvx_univnet_bind": (_i, [_vp, _vp]),
+    "gvx_univnet_forward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, C.POINTER(_vp), _vp, _sz, _vp]),
+    "gvx_univnet_timing_enable": (_i, [_vp, _i]),
+    "gvx_univnet_stage_times_ms": (_i, [_vp, C.POINTER(_f), C.POINTER(_i)]),
     "gvx_hifigan_mpd_blob_floats": (_sz, [C.POINTER(gvx_hifigan_mpd_dims)]),
     "gvx_hifigan_mpd_pack_weights_device": (_i, [C.POINTER(gvx_hifigan_mpd_dims), C.POINTER(gvx_weight_desc), _i, _vp, _vp]),
     "gvx_hifigan_mpd_create": (_i, [C.POINTER(gvx_hifigan_mpd_dims), C.POINTER(_vp)]),

@@ -440,6 +440,83 @@ class VocosConfig(BaseConfig):
             raise ValueError(f"hop_length = {self.hop_length}, the audio config's hop_length is {hop_length}")
 
 
+class UnivNetConfig(BaseConfig):
+    """The UnivNet generator (Jang et al. 2021; include/genvox_amd.h, "UnivNet generator").  The reference ships no such model; the
+    fields carry the names of the ``gen:`` block of the published ``config.yaml`` and the defaults of the c32 model (``channel_size``
+    16 is the published c16).  The LVC kernel size is 3.  ``strides`` must multiply to the audio config's ``hop_length``
+    (``check_hop``).  ``tail_pad_frames`` frames of ``tail_pad_value`` (log 1e-5) are what the published inference appends behind an
+    utterance and cuts off again.  The ranges are what the kernels take."""
+
+    MAX_BLOCKS = 4         # GVX_UNIVNET_MAX_BLOCKS
+    MAX_DILATIONS = 8      # GVX_UNIVNET_MAX_DILATIONS
+    MAX_DILATION = 36      # GVX_UNIVNET_MAX_DILATION: HiFi-GAN's window cap of 72 at kernel size 3
+    MAX_HIDDEN = 256       # GVX_UNIVNET_MAX_HIDDEN
+    MIN_FRAMES = 4         # GVX_UNIVNET_MIN_FRAMES: the reflection by 3
+
+    _FIELDS = {
+        "noise_dim": (64, None),
+        "channel_size": (32, None),
+        "dilations": ((1, 3, 9, 27), None),
+        "strides": ((8, 8, 4), None),
+        "lReLU_slope": (0.2, None),
+        "kpnet_conv_size": (3, None),
+        "kpnet_hidden_channels": (64, None),
+        "tail_pad_frames": (10, None),
+        "tail_pad_value": (-11.5129, None),
+    }
+
+    def _normalise(self) -> None:
+        try:
+            self.dilations = [int(d) for d in self.dilations]
+            self.strides = [int(s) for s in self.strides]
+        except (TypeError, ValueError):
+            raise ValueError("dilations and strides must be sequences of integers") from None
+        for name in ("noise_dim", "channel_size", "kpnet_conv_size", "kpnet_hidden_channels", "tail_pad_frames"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise ValueError(f"{name} must be an integer, not {v!r}")
+        if not 1 <= self.noise_dim <= 1024:
+            raise ValueError(f"noise_dim = {self.noise_dim} is outside [1, 1024]")
+        if self.channel_size % 4 or not 4 <= self.channel_size <= 32:
+            raise ValueError(f"channel_size = {self.channel_size} must be a multiple of 4 in [4, 32]")
+        if not 1 <= len(self.dilations) <= self.MAX_DILATIONS:
+            raise ValueError(f"there must be 1 to {self.MAX_DILATIONS} dilations, not {len(self.dilations)}")
+        for d in self.dilations:
+            if not 1 <= d <= self.MAX_DILATION:
+                raise ValueError(f"every dilation must be in [1, {self.MAX_DILATION}], not {d}")
+        if not 1 <= len(self.strides) <= self.MAX_BLOCKS:
+            raise ValueError(f"strides must name 1 to {self.MAX_BLOCKS} blocks, not {len(self.strides)}")
+        for s in self.strides:
+            if s % 2:
+                raise ValueError(f"every stride must be even, not {s}: the transposed convolution runs as kernel 2 s, stride s, padding s / 2 "
+                                 f"in two-tap phases, and an odd stride's output_padding form is not built")
+            if not 2 <= s <= 64:
+                raise ValueError(f"every stride must be in [2, 64], not {s}")
+        if self.hop > 4096:
+            raise ValueError(f"strides multiply to {self.hop}, above 4096")
+        if self.kpnet_hidden_channels % 32 or not 32 <= self.kpnet_hidden_channels <= self.MAX_HIDDEN:
+            raise ValueError(f"kpnet_hidden_channels = {self.kpnet_hidden_channels} must be a multiple of 32 in [32, {self.MAX_HIDDEN}]")
+        if self.kpnet_conv_size != 3:
+            raise ValueError(f"kpnet_conv_size must be 3, not {self.kpnet_conv_size}")
+        self.lReLU_slope = float(self.lReLU_slope)
+        if not 0.0 <= self.lReLU_slope <= 1.0:
+            raise ValueError(f"lReLU_slope = {self.lReLU_slope} is outside [0, 1]")
+        if not 0 <= self.tail_pad_frames <= 1024:
+            raise ValueError(f"tail_pad_frames = {self.tail_pad_frames} is outside [0, 1024]")
+        self.tail_pad_value = float(self.tail_pad_value)
+
+    @property
+    def hop(self) -> int:
+        hop = 1
+        for s in self.strides:
+            hop *= s
+        return hop
+
+    def check_hop(self, hop_length: int) -> None:
+        if self.hop != int(hop_length):
+            raise ValueError(f"strides {tuple(self.strides)} multiply to {self.hop}, the audio config's hop_length is {hop_length}")
+
+
 class HiFiGANPeriodDiscriminatorConfig(BaseConfig):
     """HiFi-GAN's multi-period discriminator (Kong et al. 2020; include/genvox_amd.h, "HiFi-GAN period discriminators").  The defaults
     are the published ``MultiPeriodDiscriminator``; the ranges are what the kernels take."""

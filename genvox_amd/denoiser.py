@@ -134,7 +134,7 @@ class Denoiser(torch.nn.Module):
     @classmethod
     def from_vocoder(cls, vocoder, n_fft: int = 1024, hop_length: Optional[int] = None, frames: int = 88, mel_value: float = 0.0,
                      reduce: str = "first", strength: float = 0.01) -> "Denoiser":
-        """The denoiser of ``vocoder`` (``MelGANGenerator``, ``HiFiGANGenerator``, ``BigVGANGenerator``, ``VocosGenerator``: anything with ``vocode`` and ``n_mels``, its own or
+        """The denoiser of ``vocoder`` (``MelGANGenerator``, ``HiFiGANGenerator``, ``BigVGANGenerator``, ``VocosGenerator``, ``UnivNetGenerator``: anything with ``vocode`` and ``n_mels``, its own or
         its ``audio_config``'s): one constant mel [1, n_mels, frames] of ``mel_value`` is vocoded under ``no_grad``, and the bias is
         frame 0 of that waveform's magnitudes (``reduce="first"``, the usual recipe) or their mean over the frames (``"mean"``).
         ``hop_length`` None: ``n_fft // 4``."""

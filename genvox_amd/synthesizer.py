@@ -200,7 +200,7 @@ def frame_ratios(start_frames: Sequence[int], n_frames: int, per_token_semitones
 class Synthesizer:
     def __init__(self, tts_model_class, tts_config_path: str, tts_checkpoint_path: str, use_cuda: bool = True, vocoder_model_class=None,
                  vocoder_config_path: Optional[str] = None, vocoder_checkpoint_path: Optional[str] = None) -> None:
-        """``vocoder_model_class`` (``MelGANGenerator``, ``HiFiGANGenerator``, ``BigVGANGenerator`` or ``VocosGenerator``) with its config and checkpoint paths: ``tts`` and ``tts_batch`` vocode the mel
+        """``vocoder_model_class`` (``MelGANGenerator``, ``HiFiGANGenerator``, ``BigVGANGenerator``, ``VocosGenerator`` or ``UnivNetGenerator``) with its config and checkpoint paths: ``tts`` and ``tts_batch`` vocode the mel
         through that model instead of Griffin-Lim.  The waveform is then float32 of exactly ``frames * hop_length`` samples (``(frames - 1) * hop_length`` from a Vocos model with padding "center"; no trim,
         no low-pass), and every result carries ``"vocoder"``: the model's name.  All three or none: with none nothing changes."""
         if not (use_cuda and torch.cuda.is_available()):
@@ -329,7 +329,7 @@ class Synthesizer:
             first_centre = -ap.TRIM
         else:
             host = None if frames is None else [int(t) for t in (frames.tolist() if isinstance(frames, torch.Tensor) else frames)]
-            wav = self.vocoder.vocode(mel.contiguous(), host)
+            wav = self.vocoder.vocode_utterances(mel.contiguous(), host)
             counts = None if host is None else self.vocoder.sample_counts(host)
             if host is None and self.vocoder.sample_counts(int(mel.shape[2])) != wav.shape[1]:   # a model that delivers fewer than T * hop samples
                 wav = wav[:, :self.vocoder.sample_counts(int(mel.shape[2]))].contiguous()

@@ -1377,6 +1377,105 @@ int gvx_vocos_forward(gvx_vocos* handle, const float* mel, const int32_t* frame_
 int gvx_vocos_timing_enable(gvx_vocos* handle, int enable);
 int gvx_vocos_stage_times_ms(gvx_vocos* handle, float* ms_out, int* n_out);
 
+/* ---- UnivNet generator, (mel, noise) -> waveform (Jang et al. 2021; the maum-ai/univnet implementation, c32 and c16): inference.  The
+ * reference ships no such model; the network below is a statement of the published implementation, under its names, and the float64
+ * restatement tests/univnet_ref64.py is the definition the device is held to.  A time-domain generator that upsamples NOISE at the frame
+ * rate and conditions it on the mel through location-variable convolutions (LVC): a small network at the frame rate predicts, for every
+ * frame, the weights of the convolutions that run on that frame's positions.  Kernels: csrc/univnet.hip (the LVC layer, the reflecting
+ * output layer, the C ABI) on the dense fp32 GEMM (csrc/gemm_f32.hip: conv_pre, kernel_conv + bias_conv) and HiFi-GAN's layer kernels
+ * (csrc/hifigan_kernels.h: the transposed and the dilated convolutions, the predictor's small convolutions).  All arithmetic is fp32;
+ * every tensor is channels-last [B][len][C].  C = channel_size, H = kpnet_hidden_channels, D = n_dilations, lrelu = LeakyReLU(slope),
+ * cum_i = strides[0] * .. * strides[i] positions per frame in block i, hop = cum_last.
+ *
+ *     x = Conv1d(noise_dim -> C, k = 7)(reflect 3 (z))                                                       conv_pre, at the frame rate
+ *     for block i, s = strides[i]:                                                                           res_stack.<i>
+ *         x = ConvTranspose1d(C -> C, kernel 2 s, stride s, padding s / 2)(lrelu(x))                         convt_pre.1, length times s
+ *         c = lrelu(Conv1d(n_mels -> H, k = 5, padding 2)(mel))                                              kernel_predictor.input_conv.0
+ *         for j < 3:  c = c + lrelu(Conv1d(H -> H, 3, padding 1)(lrelu(Conv1d(H -> H, 3, padding 1)(c))))    .residual_convs.<j>.1, .3
+ *         kernels = Conv1d(H -> 6 C^2 D, 3, padding 1)(c) viewed as [D][C in][2 C out][3 taps] per frame     .kernel_conv
+ *         bias    = Conv1d(H -> 2 C D, 3, padding 1)(c)   viewed as [D][2 C] per frame                       .bias_conv
+ *         for m < D, d = dilations[m]:
+ *             y = lrelu(Conv1d(C -> C, 3, dilation d, padding d)(lrelu(x)))                                  conv_blocks.<m>.1
+ *             o[j][t cum + p] = bias[m][j][t] + sum_{i, k} kernels[m][i][j][k][t] * y[i][t cum + p + k - 1],   0 <= p < cum       the LVC
+ *             x = x + sigmoid(o[0 .. C)) * tanh(o[C .. 2 C))
+ *     wav = tanh(Conv1d(C -> 1, k = 7)(reflect 3 (lrelu(x))))                                                conv_post.1
+ * Zero paddings and the LVC's zero outside [0, T_b cum) fall at a row's own end, and so do both reflections.  A row needs 4 frames:
+ * frame_lengths lives on the device, so a value below 4 is the CALLER's to refuse (UnivNetGenerator does, before anything is launched);
+ * handed to gvx_univnet_forward it reads or writes nothing out of bounds, that row's wav is silence, and its stage tensors are unspecified.
+ *
+ * Contracts, as for the other generators: every row runs at its own length frame_lengths[b] (NULL: all T); wav [B][T * hop] holds a
+ * row's samples in front and exact ZEROS behind T_b * hop; the padded frames of mel AND noise may hold anything, NaN included, and are
+ * never read; every stage tensor is zeros behind a row's positions; no atomics; a row of a ragged batch has, bit for bit, the result of
+ * that row run alone, and two calls give the same bits.
+ *
+ * The device order of a block's prediction, per frame `ld = D (6 C^2 + 2 C)` floats: kernels [D][2 C][3][C] - layer m's operand is a
+ * row-major [2 C][3 C] matrix, k = tap * C + i - and then bias [D][2 C].  kernel_conv and bias_conv are ONE product whose output
+ * channels the caller permutes into this order when it packs (kernel_predictor.kb.weight [ld][3][H] tap-major, .kb.bias [ld]): the
+ * [B][T][ld] result is the LVC kernel's operand as it stands, and nothing is permuted per call.
+ *
+ * gvx_lvc_gated is one layer on its own: x fp32 [B][T * cum][C] -> out, kern fp32 [B][T][n_layers (6 C^2 + 2 C)] in the device
+ * order, of which layer `layer` is used; conv_w fp32 [C][3][C] (tap-major rows) and conv_b [C] of the dilated convolution, or both NULL:
+ * then y = lrelu(x).  With a convolution, scratch fp32 [B][T * cum][C] (a tensor of its own) takes its output, and out may be x: an
+ * element of x is then read and written by one lane.  Without one the layer reads x at its neighbours' positions, so out == x is refused
+ * (GVX_ERR_INVALID_ARG).  lens counts frames, each in [0, T]; a row's positions behind T_b * cum are copied from x to out unread by the layer.  Two LVC kernels, one source
+ * (un_lvc_kernel<MFMA>): a workgroup owns up to 128 positions of ONE frame, brings that frame's [2 C][3 C] weights and its window of y
+ * (one position either side, lrelu applied, zeros outside the row) into LDS once, and
+ *     C == 32 and cum a multiple of 32 (of 128 above 128):  v_mfma_f32_32x32x2_f32, a wave per 32 positions, the 2 C output channels as
+ *         two 32-wide tiles whose column r is lane r: o[j] and o[j + C] meet in one lane, and bias, sigmoid * tanh and the residual
+ *         add are that lane's epilogue;
+ *     otherwise (C == 16; the first block, whose frames have 8 positions):  fmaf code, a thread per (position, gate pair).
+ * T in [1, GVX_UNIVNET_MAX_FRAMES], cum in [1, 4096], C a multiple of 4 in [4, 32], dilation in [1, 36], B in [1, 65535]:
+ * GVX_ERR_INVALID_ARG otherwise, before anything is launched.
+ *
+ * Weights.  gvx_univnet_pack_weights_device copies DEVICE tensors by name into the blob, every tensor starting at a multiple of 64
+ * floats, in this order (Np = noise_dim and Mp = n_mels rounded up to a multiple of 4; the CALLER brings every tensor into the layout):
+ *     conv_pre.weight [C][7][Np]   conv_pre.bias [C]
+ *     per block i, res_stack.<i>. in front: convt_pre.weight [s][C][2][C] (phase, out, tap, in: hifigan.hip's two-tap phase split)
+ *         convt_pre.bias [C]   kernel_predictor.input_conv.weight [H][5][Mp]  .bias [H]   kernel_predictor.residual_convs.<j>.<1 | 3>.weight
+ *         [H][3][H]  .bias [H] for j < 3   kernel_predictor.kb.weight [ld][3][H]  .kb.bias [ld]   conv_blocks.<m>.weight [C][3][C]  .bias [C]
+ *     conv_post.weight [7][C]   conv_post.bias [1]
+ * A missing name: GVX_ERR_MISSING_WEIGHT; a wrong element count: GVX_ERR_SHAPE.
+ *
+ * Workspace: gvx_univnet_workspace_bytes is host arithmetic:
+ *     B * ( round256(4 T Mp) + round256(4 (T + 6) Np) + 3 round256(4 T H) + round256(4 (T + 2) H) + round256(4 T ld) + 3 round256(4 T hop C) )
+ * the transposed mel, the reflected noise, the predictor's three tensors and its zero-haloed output, ONE slot for a block's predicted
+ * kernels (reused by every block), and x, its successor and y at the sample rate: 199,312 bytes per frame and row for c32 with 100
+ * mels, of which 99,328 are the predicted kernels.  Any contents when the call starts, nothing is cleared; every launch writes all it
+ * later reads.
+ *
+ * gvx_univnet_forward: mel fp32 [B][n_mels][T], noise fp32 [B][noise_dim][T] -> wav_out [B][T * hop].  stage_out, if not NULL:
+ * n_blocks + 2 device tensors - x after conv_pre [B][T][C], after every block [B][T cum_i][C], and the output layer before its tanh
+ * [B][T hop].  T < 4: GVX_ERR_INVALID_ARG; the workspace missing, misaligned or short: GVX_ERR_WORKSPACE.  gvx_univnet_stage_times_ms:
+ * 2 n_blocks + 2 durations - conv_pre, per block its predictor and then its layers, conv_post.  Every dims field is checked: a bad one
+ * gives blob_floats == 0 and create == GVX_ERR_INVALID_ARG.  There is no backward yet. */
+enum { GVX_UNIVNET_MAX_BLOCKS = 4, GVX_UNIVNET_MAX_DILATIONS = 8, GVX_UNIVNET_MAX_FRAMES = 1 << 16, GVX_UNIVNET_MIN_FRAMES = 4,
+       GVX_UNIVNET_MAX_DILATION = 36, GVX_UNIVNET_MAX_HIDDEN = 256 };
+typedef struct gvx_univnet_dims {
+    int32_t n_mels;                                  /* in [1, 4096] */
+    int32_t noise_dim;                               /* in [1, 1024] */
+    int32_t channel_size;                            /* a multiple of 4 in [4, 32]; 32 runs the LVC on the matrix pipe */
+    int32_t n_dilations;                             /* in [1, GVX_UNIVNET_MAX_DILATIONS] */
+    int32_t dilations[GVX_UNIVNET_MAX_DILATIONS];    /* each in [1, GVX_UNIVNET_MAX_DILATION]: HiFi-GAN's window cap of 72 */
+    int32_t n_blocks;                                /* in [1, GVX_UNIVNET_MAX_BLOCKS] */
+    int32_t strides[GVX_UNIVNET_MAX_BLOCKS];         /* each even and in [2, 64]; their product at most 4096 */
+    int32_t kpnet_hidden_channels;                   /* a multiple of 32 in [32, GVX_UNIVNET_MAX_HIDDEN] */
+    int32_t kpnet_conv_size;                         /* 3 */
+    float slope;                                     /* in [0, 1] */
+} gvx_univnet_dims;
+typedef struct gvx_univnet gvx_univnet;
+int gvx_lvc_gated(const float* x, const float* kern, int n_layers, int layer, const float* conv_w, const float* conv_b, int dilation,
+                  const int32_t* lens, int B, int T, int cum, int C, float slope, float* scratch, float* out, void* stream);
+size_t gvx_univnet_blob_floats(const gvx_univnet_dims* dims);
+size_t gvx_univnet_workspace_bytes(const gvx_univnet_dims* dims, int B, int T);
+int gvx_univnet_pack_weights_device(const gvx_univnet_dims* dims, const gvx_weight_desc* table, int n, float* device_blob, void* stream);
+int gvx_univnet_create(const gvx_univnet_dims* dims, gvx_univnet** out);
+void gvx_univnet_destroy(gvx_univnet* handle);
+int gvx_univnet_bind(gvx_univnet* handle, const float* device_blob);
+int gvx_univnet_forward(gvx_univnet* handle, const float* mel, const float* noise, const int32_t* frame_lengths, int B, int T,
+                        float* wav_out, float* const* stage_out, void* workspace, size_t workspace_bytes, void* stream);
+int gvx_univnet_timing_enable(gvx_univnet* handle, int enable);
+int gvx_univnet_stage_times_ms(gvx_univnet* handle, float* ms_out, int* n_out);
+
 /* ---- MelGAN discriminators: the multi-scale discriminator a MelGAN generator is trained against (Kumar et al. 2019), forward and
  * backward.  The reference ships the training fields of MelGANConfig and no model; this is a statement of the published architecture.
  * All arithmetic is fp32.  lrelu and "reflect" as for the generator above; s = downsampling_factor.

@@ -52,7 +52,12 @@ stage, summed, as a share of one call;
 `vocos` (on request): the Vocos generator, default configuration with 100 mels, at 32 x 800, 1 x 568 and 8 x 200 frames between device
 events, median of 7 with the spread: ours, the float32 restatement of tests/vocos_ref64.py on the same device and parameters ("torch"),
 the four stage times (embed + norm, the blocks, final norm + head product, ISTFT), and the share of the fp32 matrix rate (157.3 TFLOP/s)
-that the blocks' time amounts to for their MLP products."""
+that the blocks' time amounts to for their MLP products;
+`univnet` (on request): the UnivNet generator - c32 with 100 mels at 32 x 800, 1 x 568 and 8 x 200 frames, c16 at 32 x 800 - between device
+events, median of 7 with the spread: ours as delivered (the row split under the workspace cap included), the float32 restatement of
+tests/univnet_ref64.py on the same device with the same weights and noise ("torch", 8 rows at a time), the stage times of one call
+(conv_pre, per block the predictor and the layers, conv_post), the fp32 matrix rate of kernel_conv + bias_conv timed on its own (the same product through gvx_train_gemm_nt) and
+against each predictor's whole time, and gvx_lvc_gated timed on its own at every block's shape: its rate against 157.3 TFLOP/s and the rate at which it reads weights."""
 import json
 import os
 import sys
@@ -1241,6 +1246,101 @@ def main():
             res[key]["verdict"] = "faster" if res[key]["ours"]["median_ms"] < res[key]["torch_float32_restatement"]["median_ms"] else "SLOWER"
             print(json.dumps({key: res[key]}), flush=True)
         del voc, ref
+    if "univnet" in which:
+        import statistics
+
+        from genvox_amd import _lib
+        from genvox_amd.configs import UnivNetConfig
+        from genvox_amd.univnet import UnivNetGenerator
+        from tests import univnet_ref64 as R
+
+        def ev_spread(fn, warm=2, reps=7):
+            for _ in range(warm):
+                fn()
+            out = []
+            for _ in range(reps):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                e1.synchronize()
+                out.append(e0.elapsed_time(e1))
+            return {"median_ms": round(statistics.median(out), 3), "min_ms": round(min(out), 3), "max_ms": round(max(out), 3), "runs": reps}
+
+        lib = _lib.load()
+        gen = torch.Generator(device="cuda").manual_seed(0)
+        for name, cfg, shapes in (("c32", R.DEFAULT, ((32, 800), (1, 568), (8, 200))), ("c16", R.C16, ((32, 800),))):
+            vac = AudioConfig(filter_length=1024, hop_length=256, log_func="np.log")
+            vac.n_mels = cfg["n_mels"]
+            ref = R.Generator(cfg, seed=0).float().to("cuda:0")
+            voc = UnivNetGenerator(UnivNetConfig(**R.model_kwargs(cfg)), vac)
+            voc.load_state_dict(ref.state_dict())
+            voc.to("cuda:0")
+            c, h, D = cfg["channel_size"], cfg["kpnet_hidden_channels"], len(cfg["dilations"])
+            ld = D * (6 * c * c + 2 * c)
+            for B, T in shapes:
+                key = f"univnet_{name}_{B}x{T}"
+                mel = (1.5 * torch.randn(B, cfg["n_mels"], T, device="cuda", generator=gen) - 3.0).contiguous()
+                noise = torch.randn(B, cfg["noise_dim"], T, device="cuda", generator=gen)
+                rows = B
+                while rows > 1 and voc.workspace_bytes(rows, T) > voc.WORKSPACE_CAP_BYTES:
+                    rows = (rows + 1) // 2
+                res[key] = {"ours": ev_spread(lambda: voc.vocode(mel, noise=noise)), "rows_per_call": rows, "workspace_bytes": voc.workspace_bytes(rows, T)}
+                voc.enable_stage_timing(True)   # the stage times are of one call: the rows of one group
+                per = []
+                for _ in range(7):
+                    voc.vocode(mel[:rows], noise=noise[:rows])
+                    per.append(voc.stage_times_ms())
+                voc.enable_stage_timing(False)
+                stage = [statistics.median(col) for col in zip(*per)]
+                res[key]["stage_ms_median_of_one_call"] = [round(v, 3) for v in stage]   # conv_pre, per block predictor then layers, conv_post
+                res[key]["stage_ms_range_of_one_call"] = [[round(min(col), 3), round(max(col), 3)] for col in zip(*per)]
+                # kernel_conv + bias_conv on its own: the product of one call - M = rows x T, N = ld, K = 3 H, bias - through gvx_train_gemm_nt, whose
+                # A rows start H floats apart and are 3 H long, as the implicit k = 3 convolution's are (same launch_gemm and plan; the forward's
+                # launch also takes row_len).  Beside it, the same multiply-adds against each predictor's whole time, small convolutions included
+                stream = torch.cuda.current_stream().cuda_stream
+                kb_flops = 2.0 * rows * T * (3 * h) * ld
+                M = rows * T
+                ga = torch.randn((M + 2) * h, device="cuda", generator=gen)
+                gw = torch.randn(ld, 3 * h, device="cuda", generator=gen) * (3 * h) ** -0.5
+                gb = torch.randn(ld, device="cuda", generator=gen)
+                gc = torch.empty(M, ld, device="cuda")
+                gemm = lambda: _lib.check(lib.gvx_train_gemm_nt(ga.data_ptr(), h, gw.data_ptr(), 3 * h, gc.data_ptr(), ld, M, ld, 3 * h, gb.data_ptr(),
+                                                                None, 0, stream))
+                t = ev_spread(gemm)
+                res[key]["kernel_conv_alone"] = {**t, "M": M, "N": ld, "K": 3 * h, "tflops": round(kb_flops / (t["median_ms"] * 1e-3) / 1e12, 1),
+                                                 "fraction_of_157TF_fp32_mfma": round(kb_flops / (t["median_ms"] * 1e-3) / 1e12 / 157.3, 3),
+                                                 "GBs_written": round(4.0 * M * ld / t["median_ms"] / 1e6, 1)}
+                del ga, gw, gb, gc
+                res[key]["kernel_conv_tflops_in_its_predictors_time"] = [round(kb_flops / (stage[1 + 2 * i] * 1e-3) / 1e12, 1) for i in range(len(cfg["strides"]))]
+                # the LVC launches on their own, at every block's shape of one call, without a convolution in front (out is a tensor of its own)
+                cum, lvc = 1, []
+                for s in cfg["strides"]:
+                    cum *= s
+                    x = torch.randn(rows, T * cum, c, device="cuda", generator=gen)
+                    kern = torch.randn(rows, T, ld, device="cuda", generator=gen) * (3 * c) ** -0.5
+                    out = torch.empty_like(x)
+                    one = lambda: _lib.check(lib.gvx_lvc_gated(x.data_ptr(), kern.data_ptr(), D, 1, None, None, 1, None, rows, T, cum, c, 0.2,
+                                                               None, out.data_ptr(), stream))
+                    t = ev_spread(one)["median_ms"]
+                    flops = 2.0 * rows * T * cum * (3 * c) * (2 * c)
+                    lvc.append({"positions_per_frame": cum, "one_launch_ms": t, "launches": D, "ms": round(t * D, 3), "tflops": round(flops / (t * 1e-3) / 1e12, 1),
+                                "fraction_of_157TF_fp32_mfma": round(flops / (t * 1e-3) / 1e12 / 157.3, 3),
+                                "GBs_weights_read": round(4.0 * rows * T * 6 * c * c / t / 1e6, 1)})
+                    del x, kern, out
+                res[key]["lvc_launches_of_one_call"] = lvc
+                wav = voc.vocode(mel, noise=noise)
+                print(json.dumps({key: res[key]}), flush=True)
+                with torch.no_grad():
+                    torch_rows = min(B, 8)   # the restatement holds a block's kernels AND their unfolded windows: 8 rows at a time
+                    run = lambda: [ref(mel[lo:lo + torch_rows], noise[lo:lo + torch_rows])[0] for lo in range(0, B, torch_rows)]
+                    res[key]["torch_float32_restatement"] = ev_spread(run, warm=1, reps=7)
+                    res[key]["torch_rows_per_call"] = torch_rows
+                    want = torch.cat(run())
+                res[key]["max_abs_difference_from_torch"] = float((want - wav).abs().max())
+                res[key]["verdict"] = "faster" if res[key]["ours"]["median_ms"] < res[key]["torch_float32_restatement"]["median_ms"] else "SLOWER"
+                print(json.dumps({key: res[key]}), flush=True)
+            del voc, ref
     if "cpu" in which:
         # CPU baselines for configs 3 and 4 (the oracle = CPU restatement of the reference, on this box's host cores):
         # bounded samples, reported beside the GPU figures above; bench.py carries the one for config 2.
