@@ -6,6 +6,7 @@
     from genvox_amd import BigVGANGenerator, BigVGANConfig   # BigVGAN (anti-aliased Snake activations), inference, the same place
     from genvox_amd import VocosGenerator, VocosConfig   # Vocos (ConvNeXt backbone at the frame rate + inverse STFT), inference, the same place
     from genvox_amd import UnivNetGenerator, UnivNetConfig   # UnivNet (noise through location-variable convolutions), inference, the same place
+    from genvox_amd import FastPitch, FastPitchConfig   # non-autoregressive text->mel: Synthesizer(tts_model_class=FastPitch, ...)
     from genvox_amd import Tacotron2GuidedLoss    # training criterion: Tacotron2Loss + alpha x guided attention loss
     from genvox_amd import MelGANDiscriminator, MelGANDiscriminatorConfig, MelGANTrainer   # the other side of the vocoder's GAN step
     from genvox_amd import HiFiGANPeriodDiscriminator, HiFiGANPeriodDiscriminatorConfig, HiFiGANTrainer, HiFiGANTrainingConfig   # HiFi-GAN's GAN step
@@ -16,7 +17,7 @@
     from genvox_amd import Denoiser   # vocoder denoiser: Denoiser.from_vocoder(vocoder)(wav), or Synthesizer.tts(text, denoise=0.01)
 """
 from .configs import HiFiGANPeriodDiscriminatorConfig, HiFiGANScaleDiscriminatorConfig, HiFiGANTrainingConfig  # noqa: F401
-from .configs import MultiResolutionDiscriminatorConfig, UnivNetConfig, VocosConfig  # noqa: F401
+from .configs import FastPitchConfig, MultiResolutionDiscriminatorConfig, UnivNetConfig, VocosConfig  # noqa: F401
 from .configs import AudioConfig, BaseConfig, BigVGANConfig, HiFiGANConfig, MelGANConfig, MelGANDiscriminatorConfig, Tacotron2Config, TextConfig  # noqa: F401
 
 
@@ -27,6 +28,9 @@ def __getattr__(name):  # torch-dependent classes are imported lazily
     if name == "Tacotron2GuidedLoss":
         from .tacotron2 import Tacotron2GuidedLoss
         return Tacotron2GuidedLoss
+    if name == "FastPitch":
+        from .fastpitch import FastPitch
+        return FastPitch
     if name == "MelGANGenerator":
         from .melgan import MelGANGenerator
         return MelGANGenerator

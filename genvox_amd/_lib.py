@@ -48,6 +48,15 @@ class gvx_vocos_dims(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("n_mels", "dim", "intermediate_dim", "num_layers", "n_fft", "hop_length", "center")]
 
 
+class gvx_fft_stack_dims(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("n_layers", "n_head", "d_head", "d_inner", "kernel_size")]
+
+
+class gvx_fastpitch_dims(C.Structure):
+    _fields_ = [("n_tokens", C.c_int32), ("n_mels", C.c_int32), ("d_model", C.c_int32), ("enc", gvx_fft_stack_dims), ("dec", gvx_fft_stack_dims)] + [
+        (k, C.c_int32) for k in ("pred_filter", "pred_layers", "energy", "max_tokens", "max_decoder_steps", "max_duration", "min_token_frames")]
+
+
 class gvx_univnet_dims(C.Structure):
     _fields_ = [("n_mels", C.c_int32), ("noise_dim", C.c_int32), ("channel_size", C.c_int32), ("n_dilations", C.c_int32),
                 ("dilations", C.c_int32 * 8), ("n_blocks", C.c_int32), ("strides", C.c_int32 * 4), ("kpnet_hidden_channels", C.c_int32),
@@ -290,6 +299,17 @@ SIGNATURES = {
     "gvx_vocos_forward": (_i, [_vp, _vp, _vp, _i, _i, _vp, C.POINTER(_vp), _vp, _sz, _vp]),
     "gvx_vocos_timing_enable": (_i, [_vp, _i]),
     "gvx_vocos_stage_times_ms": (_i, [_vp, C.POINTER(_f), C.POINTER(_i)]),
+    "gvx_self_attention": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "gvx_fastpitch_blob_floats": (_sz, [C.POINTER(gvx_fastpitch_dims)]),
+    "gvx_fastpitch_workspace_bytes": (_sz, [C.POINTER(gvx_fastpitch_dims), _i, _i]),
+    "gvx_fastpitch_pack_weights_device": (_i, [C.POINTER(gvx_fastpitch_dims), C.POINTER(gvx_weight_desc), _i, _vp, _vp]),
+    "gvx_fastpitch_create": (_i, [C.POINTER(gvx_fastpitch_dims), C.POINTER(_vp)]),
+    "gvx_fastpitch_destroy": (None, [_vp]),
+    "gvx_fastpitch_bind": (_i, [_vp, _vp]),
+    "gvx_fastpitch_encode": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), _vp, _sz, _vp]),
+    "gvx_fastpitch_decode": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, C.POINTER(_vp), _vp, _sz, _vp]),
+    "gvx_fastpitch_timing_enable": (_i, [_vp, _i]),
+    "gvx_fastpitch_stage_times_ms": (_i, [_vp, C.POINTER(_f), C.POINTER(_i)]),
     "gvx_lvc_gated": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
     "gvx_univnet_blob_floats": (_sz, [C.POINTER(gvx_univnet_dims)]),
     "gvx_univnet_workspace_bytes": (_sz, [C.POINTER(gvx_univnet_dims), _i, _i]),

@@ -158,6 +158,69 @@ class Tacotron2Config(BaseConfig):
     }
 
 
+class FastPitchConfig(BaseConfig):
+    """The FastPitch acoustic model (Lancucki 2021; include/genvox_amd.h, "FastPitch acoustic model").  The reference ships no such
+    model; the defaults are the published NVIDIA model's (``enc_*`` its ``in_fft_*`` arguments, ``dec_*`` its ``out_fft_*``, one
+    ``d_model`` for both stacks - the published ``symbols_embedding_dim``; ``predictor_*`` serve the duration, pitch and energy
+    predictors alike, each a stack of k = 3 convolutions).  ``min_token_frames`` (0 as published) is the least frame count the length
+    regulator gives a token; ``max_decoder_steps`` cuts a row's frames; ``max_tokens`` bounds a row's tokens (with ``max_decoder_steps``
+    it sizes the position table).  The ranges are what the kernels take: anything else is refused here, by name."""
+
+    MAX_DIM = 512          # GVX_FASTPITCH_MAX_DIM: the LayerNorm kernel's limit
+    MAX_INNER = 8192       # GVX_FASTPITCH_MAX_INNER
+    MAX_LAYERS = 32        # GVX_FASTPITCH_MAX_LAYERS
+    MAX_HEADS = 16         # GVX_FASTPITCH_MAX_HEADS
+    MAX_TOKENS = 4096      # GVX_FASTPITCH_MAX_TOKENS
+    MAX_POSITIONS = 1 << 16   # GVX_FASTPITCH_MAX_POSITIONS
+
+    _FIELDS = {
+        "d_model": (384, None),
+        "enc_n_layers": (6, None), "enc_n_head": (1, None), "enc_d_head": (64, None), "enc_d_inner": (1536, None), "enc_kernel_size": (3, None),
+        "dec_n_layers": (6, None), "dec_n_head": (1, None), "dec_d_head": (64, None), "dec_d_inner": (1536, None), "dec_kernel_size": (3, None),
+        "predictor_filter_size": (256, None),
+        "predictor_n_layers": (2, None),
+        "energy_conditioning": (True, None),
+        "max_duration": (75, None),
+        "min_token_frames": (0, None),
+        "max_decoder_steps": (2000, None),
+        "max_tokens": (512, None),
+        "pre_lnorm": (False, None),
+        "n_speakers": (1, None),
+    }
+
+    def _normalise(self) -> None:
+        ints = [k for k in self._FIELDS if k not in ("energy_conditioning", "pre_lnorm")]
+        for name in ints:
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise ValueError(f"{name} must be an integer, not {v!r}")
+        if self.pre_lnorm:
+            raise ValueError("pre_lnorm = True is not supported: the kernels run the published default, LayerNorm behind the residual")
+        if self.n_speakers != 1:
+            raise ValueError(f"n_speakers = {self.n_speakers}: only the single-speaker model is supported")
+        self.energy_conditioning = bool(self.energy_conditioning)
+        for name in ("d_model", "predictor_filter_size"):
+            v = getattr(self, name)
+            if v % 32 or not 32 <= v <= self.MAX_DIM:
+                raise ValueError(f"{name} = {v} must be a multiple of 32 in [32, {self.MAX_DIM}], the LayerNorm kernel's limit")
+        for s in ("enc", "dec"):
+            v = getattr(self, f"{s}_d_inner")
+            if v % 32 or not 32 <= v <= self.MAX_INNER:
+                raise ValueError(f"{s}_d_inner = {v} must be a multiple of 32 in [32, {self.MAX_INNER}]")
+            if getattr(self, f"{s}_d_head") not in (32, 64):
+                raise ValueError(f"{s}_d_head = {getattr(self, f'{s}_d_head')} must be 32 or 64, the head sizes the attention kernel has")
+            if getattr(self, f"{s}_kernel_size") not in (1, 3):
+                raise ValueError(f"{s}_kernel_size = {getattr(self, f'{s}_kernel_size')} must be 1 or 3")
+            if not 1 <= getattr(self, f"{s}_n_layers") <= self.MAX_LAYERS:
+                raise ValueError(f"{s}_n_layers = {getattr(self, f'{s}_n_layers')} is outside [1, {self.MAX_LAYERS}]")
+            if not 1 <= getattr(self, f"{s}_n_head") <= self.MAX_HEADS:
+                raise ValueError(f"{s}_n_head = {getattr(self, f'{s}_n_head')} is outside [1, {self.MAX_HEADS}]")
+        for name, lo, hi in (("predictor_n_layers", 1, 8), ("max_duration", 1, self.MAX_POSITIONS), ("min_token_frames", 0, self.max_duration),
+                             ("max_decoder_steps", 1, self.MAX_POSITIONS), ("max_tokens", 1, self.MAX_TOKENS)):
+            if not lo <= getattr(self, name) <= hi:
+                raise ValueError(f"{name} = {getattr(self, name)} is outside [{lo}, {hi}]")
+
+
 class MelGANConfig(BaseConfig):
     """reference: configs/models.py:89-121 (the eight training fields: same names, defaults and ranges), followed by the generator's
     own shape, which the reference's config does not carry (it ships no vocoder model): a yaml written from the reference's

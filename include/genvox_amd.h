@@ -2054,6 +2054,99 @@ size_t gvx_denoise_workspace_bytes(const gvx_denoise_plan* plan, int B, long n_m
 int gvx_denoise(gvx_denoise_plan* plan, const float* wav, const int32_t* sample_lengths, int B, long n_max, const float* bias, float strength,
                 float* out, float* mag_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- FastPitch acoustic model, tokens -> mel (Lancucki 2021; the published NVIDIA implementation, single speaker): inference.  The
+ * reference ships no such model; the network below is a statement of the published implementation, under its state-dict names, and the
+ * float64 restatement tests/fastpitch_ref64.py is the definition the device is held to.  Kernels: csrc/fastpitch.hip (self-attention,
+ * residual + LayerNorm, embedding, the duration plan, the regulator, the C ABI) on the dense fp32 GEMM (csrc/gemm_f32.hip: every
+ * product).  All arithmetic is fp32; every tensor is channels-last.  C = d_model, H = n_head, D = d_head, I = d_inner, k = kernel_size,
+ * F = pred_filter, LN = LayerNorm over the channels of a position with eps 1e-5, pos[p] = cat(sin(p f), cos(p f)),
+ * f_i = 10000^(-2 i / C), i < C / 2.
+ *
+ *     FFT stack (encoder, decoder), per layer:                                                         <stack>.layers.<i>
+ *         qkv = Linear(C -> 3 H D)(x), columns [q | k | v], each [H][D]                                   .dec_attn.qkv_net
+ *         a   = softmax(q k^T / sqrt(D)) v over the row's own keys, per head
+ *         x   = LN(x + Linear(H D -> C, no bias)(a))                                                      .dec_attn.o_net, .dec_attn.layer_norm
+ *         x   = LN(x + Conv1d(I -> C, k)(relu(Conv1d(C -> I, k, padding k / 2)(x))))                      .pos_ff.CoreNet.0, .2, .pos_ff.layer_norm
+ *     x = word_emb[tokens] + pos;  x = encoder(x)                                                      encoder.word_emb
+ *     predictor(x) = Linear(F -> 1)(n_layers of LN(relu(Conv1d(., F, 3, padding 1)(.))))               <p>.layers.<i>.conv, .norm, <p>.fc
+ *     log_dur = duration_predictor(x);  dur = clamp(exp(log_dur) - 1, 0, max_duration)
+ *     pitch = pitch_predictor(x);   x = x + Conv1d(1 -> C, 3, padding 1)(pitch)                         pitch_emb
+ *     energy = energy_predictor(x); x = x + Conv1d(1 -> C, 3, padding 1)(energy)                        energy_emb   (energy_conditioning)
+ *     reps_l = max(floor(dur_l / pace + 0.5), min_token_frames); start = exclusive scan; a row is cut at max_decoder_steps frames, and a
+ *         row of 0 frames gets one frame of its last token
+ *     y[t] = x[l] + pos[t] for start_l <= t < start_l + reps_l;  y = decoder(y);  mel = Linear(C -> n_mels)(y) as [B][n_mels][T]       proj
+ * Every row is the row alone: every convolution sees zeros outside [0, T_b), keys at or behind T_b get weight exactly 0, every tensor is
+ * zeros at and behind a row's length, and a row of a ragged batch has, bit for bit, the result of that row run alone.  This is the
+ * published single-utterance inference, not its padded batch (which lets a padded row's last positions see non-zero values behind its end).
+ *
+ * gvx_self_attention is the attention on its own: qkv fp32 [B][T][3 H D] -> out fp32 [B][T][H D], lens int32 [B] on the device or NULL.
+ * A workgroup of four waves owns GVX_ATTN_Q_TILE = 128 queries of one (row, head), a wave 32 of them; key / value tiles of
+ * GVX_ATTN_K_TILE = 64 positions go through LDS (zeros at and behind T_b: qkv is never read there), the wave forms S^T = K Q^T and
+ * O^T = V^T P^T on v_mfma_f32_32x32x2_f32 - so a query is a lane's column in both, and the running maximum, the running sum and the
+ * rescale of the online softmax are the lane's own - and a tile wholly behind T_b is not visited.  Queries at or behind T_b are written
+ * as zeros.  The order of the sum over keys is the tile walk's: the same row gives the same bits whatever B and T are.  No atomics.
+ * D must be 32 or 64, H in [1, GVX_FASTPITCH_MAX_HEADS], B in [1, 65535], T in [1, GVX_FASTPITCH_MAX_POSITIONS]; qkv and out 16-byte aligned.
+ *
+ * Weights.  gvx_fastpitch_pack_weights_device copies DEVICE tensors by name into the blob, every tensor starting at a multiple of 64
+ * floats: encoder.word_emb.weight [n_tokens][C]; per stack and layer dec_attn.qkv_net.weight [3 H D][C], .bias, dec_attn.o_net.weight
+ * [C][H D], dec_attn.layer_norm.weight, .bias, pos_ff.CoreNet.0.weight [I][k][C] and pos_ff.CoreNet.2.weight [C][k][I] (TAP-major rows:
+ * the caller permutes Conv1d's [out][in][k]), their biases, pos_ff.layer_norm.weight, .bias; per predictor and layer layers.<i>.conv.weight
+ * [F][3][C_in], .bias, layers.<i>.norm.weight, .bias, then fc.weight [F], fc.bias [1]; pitch_emb.weight [C][3], .bias, energy_emb likewise
+ * (energy = 1); proj.weight [n_mels][C], proj.bias.  The position table [max(max_tokens, max_decoder_steps)][C] follows; the call computes
+ * it itself in float64.  A missing name: GVX_ERR_MISSING_WEIGHT; a wrong element count: GVX_ERR_SHAPE.
+ *
+ * A call runs in two phases, because the decoder's length is not known before the durations exist.  gvx_fastpitch_encode: tokens int32
+ * [B][L] (a token outside [0, n_tokens) reads row 0), token_lengths int32 [B] or NULL, pace in [0.125, 8], durations_in int32 [B][L] or
+ * NULL (used instead of the predicted ones), pitch_in fp32 [B][L] or NULL (used instead of the predicted pitch) -> enc_out fp32
+ * [B][L + 2][C] (the conditioned encoder output between two zero halo rows), log_dur, pitch_pred, energy_pred fp32 [B][L], reps and starts
+ * int32 [B][L], frame_counts int32 [B].  stage_out, if not NULL: enc_layers + 1 tensors [B][L][C], x after the embedding and after every
+ * layer.  gvx_fastpitch_decode: what encode wrote and T >= every frame count -> mel fp32 [B][n_mels][T], gate fp32 [B][T] (-1e3 on a row's
+ * frames but its last, +1e3 on the last and behind), alignments fp32 [B][T][L] (exact 0 / 1).  stage_out, if not NULL: dec_layers + 1
+ * tensors [B][T][C], the regulated sequence and x after every layer.  The caller reads frame_counts between the two: the one
+ * synchronisation of a call.  gvx_fastpitch_workspace_bytes(dims, B, N) is host arithmetic and serves either phase at N positions (L or
+ * T); any contents when a call starts, nothing is cleared.  gvx_fastpitch_stage_times_ms: four durations - embedding + encoder,
+ * predictors + plan + regulator, decoder, projection.  Every dims field is checked: a bad one gives blob_floats == 0 and
+ * create == GVX_ERR_INVALID_ARG with the reason.  There is no backward. */
+enum { GVX_ATTN_Q_TILE = 128, GVX_ATTN_K_TILE = 64, GVX_FASTPITCH_MAX_DIM = 512, GVX_FASTPITCH_MAX_INNER = 8192, GVX_FASTPITCH_MAX_LAYERS = 32,
+       GVX_FASTPITCH_MAX_HEADS = 16, GVX_FASTPITCH_MAX_TOKENS = 4096, GVX_FASTPITCH_MAX_POSITIONS = 1 << 16 };
+typedef struct gvx_fft_stack_dims {
+    int32_t n_layers;      /* in [1, GVX_FASTPITCH_MAX_LAYERS] */
+    int32_t n_head;        /* in [1, GVX_FASTPITCH_MAX_HEADS] */
+    int32_t d_head;        /* 32 or 64 */
+    int32_t d_inner;       /* a multiple of 32 in [32, GVX_FASTPITCH_MAX_INNER] */
+    int32_t kernel_size;   /* 1 or 3 */
+} gvx_fft_stack_dims;
+typedef struct gvx_fastpitch_dims {
+    int32_t n_tokens;            /* rows of the embedding table, >= 1 */
+    int32_t n_mels;              /* in [1, 4096] */
+    int32_t d_model;             /* a multiple of 32 in [32, GVX_FASTPITCH_MAX_DIM]: the LayerNorm kernel's limit */
+    gvx_fft_stack_dims enc, dec;
+    int32_t pred_filter;         /* a multiple of 32 in [32, GVX_FASTPITCH_MAX_DIM] */
+    int32_t pred_layers;         /* in [1, 8] */
+    int32_t energy;              /* 1: energy_predictor and energy_emb exist */
+    int32_t max_tokens;          /* in [1, GVX_FASTPITCH_MAX_TOKENS] */
+    int32_t max_decoder_steps;   /* in [1, GVX_FASTPITCH_MAX_POSITIONS] */
+    int32_t max_duration;        /* >= 1 */
+    int32_t min_token_frames;    /* >= 0 */
+} gvx_fastpitch_dims;
+typedef struct gvx_fastpitch gvx_fastpitch;
+int gvx_self_attention(const float* qkv, const int32_t* lens, int B, int T, int n_head, int d_head, float* out, void* stream);
+size_t gvx_fastpitch_blob_floats(const gvx_fastpitch_dims* dims);
+size_t gvx_fastpitch_workspace_bytes(const gvx_fastpitch_dims* dims, int B, int N);
+int gvx_fastpitch_pack_weights_device(const gvx_fastpitch_dims* dims, const gvx_weight_desc* table, int n, float* device_blob, void* stream);
+int gvx_fastpitch_create(const gvx_fastpitch_dims* dims, gvx_fastpitch** out);
+void gvx_fastpitch_destroy(gvx_fastpitch* handle);
+int gvx_fastpitch_bind(gvx_fastpitch* handle, const float* device_blob);
+int gvx_fastpitch_encode(gvx_fastpitch* handle, const int32_t* tokens, const int32_t* token_lengths, int B, int L, float pace,
+                         const int32_t* durations_in, const float* pitch_in, float* enc_out, float* log_dur, float* pitch_pred,
+                         float* energy_pred, int32_t* reps, int32_t* starts, int32_t* frame_counts, float* const* stage_out, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int gvx_fastpitch_decode(gvx_fastpitch* handle, const float* enc_out, const int32_t* reps, const int32_t* starts, const int32_t* frame_counts,
+                         const int32_t* token_lengths, int B, int L, int T, float* mel_out, float* gate_out, float* align_out,
+                         float* const* stage_out, void* workspace, size_t workspace_bytes, void* stream);
+int gvx_fastpitch_timing_enable(gvx_fastpitch* handle, int enable);
+int gvx_fastpitch_stage_times_ms(gvx_fastpitch* handle, float* ms_out, int* n_out);
+
 /* ---- Per-kernel timing of the decoder step (measurement only): when enabled, a teacher-forced call replays the
  * mid-sequence LSTM-step launch and the attention launches 64 times each, back to back, between HIP events on
  * `stream` (after its loop; the call's outputs are not valid afterwards); gvx_kernel_times_ms synchronises and

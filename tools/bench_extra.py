@@ -53,6 +53,11 @@ stage, summed, as a share of one call;
 events, median of 7 with the spread: ours, the float32 restatement of tests/vocos_ref64.py on the same device and parameters ("torch"),
 the four stage times (embed + norm, the blocks, final norm + head product, ISTFT), and the share of the fp32 matrix rate (157.3 TFLOP/s)
 that the blocks' time amounts to for their MLP products;
+`fastpitch` (on request): the FastPitch acoustic model, published sizes, on given durations - 32 x 128 tokens -> 800 frames, 1 x 100 tokens
+-> 568 frames, 8 x 40 tokens -> 200 frames - between device events, median of 7 with the spread: ours (both phases and the read-back of
+the frame counts), the float32 restatement of tests/fastpitch_ref64.py run as a batch on the same device with the same weights ("torch":
+F.scaled_dot_product_attention, Conv1d, LayerNorm), the four stage times (embedding + encoder, predictors + plan + regulator, decoder,
+projection), the decoder's share of the fp32 matrix rate, and gvx_self_attention on its own at 32 x 800 and 1 x 568 against torch's;
 `univnet` (on request): the UnivNet generator - c32 with 100 mels at 32 x 800, 1 x 568 and 8 x 200 frames, c16 at 32 x 800 - between device
 events, median of 7 with the spread: ours as delivered (the row split under the workspace cap included), the float32 restatement of
 tests/univnet_ref64.py on the same device with the same weights and noise ("torch", 8 rows at a time), the stage times of one call
@@ -1246,6 +1251,102 @@ def main():
             res[key]["verdict"] = "faster" if res[key]["ours"]["median_ms"] < res[key]["torch_float32_restatement"]["median_ms"] else "SLOWER"
             print(json.dumps({key: res[key]}), flush=True)
         del voc, ref
+    if "fastpitch" in which:
+        import statistics
+
+        import torch.nn.functional as F
+
+        from genvox_amd.configs import FastPitchConfig
+        from genvox_amd.fastpitch import FastPitch, self_attention
+        from tests import fastpitch_ref64 as R
+
+        def ev_spread(fn, warm=2, reps=7):
+            for _ in range(warm):
+                fn()
+            out = []
+            for _ in range(reps):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                e1.synchronize()
+                out.append(e0.elapsed_time(e1))
+            return {"median_ms": round(statistics.median(out), 3), "min_ms": round(min(out), 3), "max_ms": round(max(out), 3), "runs": reps}
+
+        cfg = R.full(R.DEFAULT)
+        ref = R.Model(R.DEFAULT, seed=0).float().to("cuda:0")
+        fp = FastPitch(FastPitchConfig(), AudioConfig(filter_length=1024, hop_length=256, log_func="np.log"), TextConfig(n_tokens=cfg["n_tokens"]))
+        fp.load_state_dict(ref.state_dict())
+        fp.to("cuda:0")
+        pos = R.position_table(2000, cfg["d_model"], torch.float32).to("cuda:0")
+
+        def stack(st, x):   # the restatement's layers on a batch of full-length rows: [B, N, C]
+            for layer in st.layers:
+                a = layer.dec_attn
+                B_, N_, _ = x.shape
+                q, k, v = (t.reshape(B_, N_, a.n_head, a.d_head).transpose(1, 2) for t in a.qkv_net(x).chunk(3, dim=2))
+                o = F.scaled_dot_product_attention(q, k, v).transpose(1, 2).reshape(B_, N_, -1)
+                x = a.layer_norm(x + a.o_net(o))
+                x = layer.pos_ff.layer_norm(x + layer.pos_ff.CoreNet(x.transpose(1, 2)).transpose(1, 2))
+            return x
+
+        def pred(p, x):
+            for layer in p.layers:
+                x = layer.norm(F.relu(layer.conv(x.transpose(1, 2)).transpose(1, 2)))
+            return p.fc(x)[..., 0]
+
+        def torch_forward(tokens, reps):   # every row has the same durations: the regulated batch is rectangular
+            x = stack(ref.encoder, ref.encoder.word_emb(tokens) + pos[:tokens.shape[1]])
+            log_dur = pred(ref.duration_predictor, x)
+            x = x + ref.pitch_emb(pred(ref.pitch_predictor, x)[:, None]).transpose(1, 2)
+            x = x + ref.energy_emb(pred(ref.energy_predictor, x)[:, None]).transpose(1, 2)
+            y = torch.repeat_interleave(x, reps, dim=1)
+            y = stack(ref.decoder, y + pos[:y.shape[1]])
+            return ref.proj(y).transpose(1, 2), log_dur
+
+        gen = torch.Generator(device="cuda").manual_seed(0)
+        C_, I_ = cfg["d_model"], cfg["enc_d_inner"]
+        # multiply-adds of a position of one FFT layer: qkv, o_net, the two k = 3 convolutions (the attention's own products come on top: 2 N D)
+        layer_macs = C_ * 3 * 64 + 64 * C_ + 2 * 3 * C_ * I_
+        for B, L, T in ((32, 128, 800), (1, 100, 568), (8, 40, 200)):
+            key = f"fastpitch_{B}x{L}tokens_{T}frames"
+            tokens = torch.randint(0, cfg["n_tokens"], (B, L), device="cuda", generator=gen)
+            row = torch.full((L,), T // L, dtype=torch.int64, device="cuda")
+            row[:T - L * (T // L)] += 1
+            durations = row[None].repeat(B, 1)
+            inputs = {"tokens": tokens, "durations": durations}
+            res[key] = {"ours": ev_spread(lambda: fp.inference(inputs)), "workspace_bytes": max(fp.workspace_bytes(B, L), fp.workspace_bytes(B, T))}
+            fp.enable_stage_timing(True)
+            per = []
+            for _ in range(7):
+                fp.inference(inputs)
+                per.append(fp.stage_times_ms())
+            fp.enable_stage_timing(False)
+            stage = [statistics.median(col) for col in zip(*per)]
+            res[key]["stage_ms_median"] = [round(v, 3) for v in stage]   # embedding + encoder, predictors + plan + regulator, decoder, projection
+            res[key]["stage_ms_range"] = [[round(min(col), 3), round(max(col), 3)] for col in zip(*per)]
+            dec_flops = 2.0 * cfg["dec_n_layers"] * B * T * (layer_macs + 2 * T * 64)
+            res[key]["decoder_tflops"] = round(dec_flops / (stage[2] * 1e-3) / 1e12, 1)   # LayerNorm and attention launches count towards the time
+            res[key]["decoder_fraction_of_157TF_fp32_mfma"] = round(dec_flops / (stage[2] * 1e-3) / 157.3e12, 3)
+            out = fp.inference(inputs)
+            with torch.no_grad():
+                res[key]["torch_float32_restatement"] = ev_spread(lambda: torch_forward(tokens, row), warm=1, reps=7)
+                want, _ = torch_forward(tokens, row)
+            res[key]["max_abs_difference_from_torch"] = float((want - out["mel_outputs"]).abs().max())
+            res[key]["verdict"] = "faster" if res[key]["ours"]["median_ms"] < res[key]["torch_float32_restatement"]["median_ms"] else "SLOWER"
+            print(json.dumps({key: res[key]}), flush=True)
+        for B, T in ((32, 800), (1, 568)):   # the attention launch on its own
+            key = f"self_attention_{B}x{T}"
+            qkv = torch.randn(B, T, 192, device="cuda", generator=gen)
+            q, k, v = (t.reshape(B, T, 1, 64).transpose(1, 2) for t in qkv.chunk(3, dim=2))
+            res[key] = {"ours": ev_spread(lambda: self_attention(qkv, None, 1, 64)), "torch_sdpa_float32": ev_spread(lambda: F.scaled_dot_product_attention(q, k, v))}
+            flops = 4.0 * B * T * T * 64
+            res[key]["tflops"] = round(flops / (res[key]["ours"]["median_ms"] * 1e-3) / 1e12, 1)
+            res[key]["fraction_of_157TF_fp32_mfma"] = round(flops / (res[key]["ours"]["median_ms"] * 1e-3) / 157.3e12, 3)
+            res[key]["max_abs_difference_from_torch"] = float((F.scaled_dot_product_attention(q, k, v).transpose(1, 2).reshape(B, T, 64) - self_attention(qkv, None, 1, 64)).abs().max())
+            res[key]["verdict"] = "faster" if res[key]["ours"]["median_ms"] < res[key]["torch_sdpa_float32"]["median_ms"] else "SLOWER"
+            print(json.dumps({key: res[key]}), flush=True)
+        del fp, ref
     if "univnet" in which:
         import statistics
 
