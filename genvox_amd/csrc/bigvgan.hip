@@ -19,10 +19,9 @@
 using gvx::fail;
 using namespace gvx_hg;
 
-struct gvx_bigvgan {
+struct gvx_bigvgan : gvx_gen::GenHandle {
     gvx_bigvgan_dims d;
-    const float* blob = nullptr;
-    gvx_hifigan core;   // what hg_prepare and the timing keep per handle: the dynamic-LDS flag and the events
+    bool lds_ready = false;   // hg_prepare
 };
 
 namespace {
@@ -73,7 +72,7 @@ __global__ void __launch_bounds__(256) bv_snake_kernel(const BvAct p) {
     const int b = blockIdx.z, c = (int)blockIdx.y * CB + cl, t0 = (int)blockIdx.x * BV_P;
     const bool c_ok = c < p.C;
     const int Lmax = p.T * p.mul;
-    const int len = hg_frames(p.lens, b, p.T) * p.mul;
+    const int len = gen_frames(p.lens, b, p.T) * p.mul;
     const size_t row = (size_t)b * Lmax;
     const int t_end = min(t0 + BV_P, Lmax);
     if (t0 >= len) {   // nothing of this row here
@@ -175,7 +174,7 @@ inline int bv_acts_per_block(const gvx_hifigan_dims& d) { return d.n_dilations *
 BvBlob bv_blob_layout(const gvx_hifigan_dims& d) {
     BvBlob L{};
     size_t at = hg_blob_layout(d).total;
-    auto take = [&](size_t floats) { const size_t o = at; at += hg_round64(floats); return o; };
+    auto take = [&](size_t floats) { const size_t o = at; at += gen_round64(floats); return o; };
     L.filter = take(BV_TAPS);
     size_t C = d.upsample_initial_channel;
     for (int i = 0; i < d.n_stages; ++i) {
@@ -197,31 +196,7 @@ const char* bv_dims_problem(const gvx_bigvgan_dims* d) {
     return nullptr;
 }
 
-size_t bv_widest(const gvx_hifigan_dims& d) {   // floats per frame of the widest activation tensor
-    size_t widest = d.upsample_initial_channel, mul = 1, C = d.upsample_initial_channel;
-    for (int i = 0; i < d.n_stages; ++i) {
-        mul *= d.upsample_rates[i];
-        C /= 2;
-        widest = std::max(widest, mul * C);
-    }
-    return widest;
-}
-
 constexpr int BV_BUFS = 5;   // HiFi-GAN's four tensors of a stage and the activation's output
-struct BvWs { size_t mel_t, buf[BV_BUFS], total; };
-
-BvWs bv_ws_plan(const gvx_hifigan_dims& d, int B, int T) {
-    BvWs w{};
-    size_t at = 0;
-    w.mel_t = at;
-    at += (size_t)B * hg_round256((size_t)T * hg_cpad(d) * sizeof(float));
-    for (int i = 0; i < BV_BUFS; ++i) {
-        w.buf[i] = at;
-        at += (size_t)B * hg_round256((size_t)T * bv_widest(d) * sizeof(float));
-    }
-    w.total = at;
-    return w;
-}
 
 }  // namespace
 
@@ -246,7 +221,7 @@ size_t gvx_bigvgan_blob_floats(const gvx_bigvgan_dims* dims) {
 
 size_t gvx_bigvgan_workspace_bytes(const gvx_bigvgan_dims* dims, int B, int T) {
     if (bv_dims_problem(dims) || B < 1 || T < 1 || T > GVX_HIFIGAN_MAX_FRAMES) return 0;
-    return bv_ws_plan(dims->net, B, T).total;
+    return hg_ws_plan(dims->net, B, T, BV_BUFS).total;
 }
 
 int gvx_bigvgan_pack_weights_device(const gvx_bigvgan_dims* dims, const gvx_weight_desc* table, int n, float* device_blob, void* stream) {
@@ -254,40 +229,22 @@ int gvx_bigvgan_pack_weights_device(const gvx_bigvgan_dims* dims, const gvx_weig
     if (!table || n < 1 || !device_blob) return fail(GVX_ERR_INVALID_ARG, "null argument");
     const gvx_hifigan_dims& d = dims->net;
     const BvBlob L = bv_blob_layout(d);
-    hipStream_t s = (hipStream_t)stream;
-    struct Job { size_t dst; const float* src; size_t numel; };
-    std::vector<Job> jobs;
-    auto take = [&](const std::string& name, size_t dst, size_t numel) -> int {
-        for (int i = 0; i < n; ++i)
-            if (table[i].name && name == table[i].name) {
-                if (!table[i].data || table[i].numel != (int64_t)numel)
-                    return fail(GVX_ERR_SHAPE, "%s has %lld elements, the dims ask for %zu", name.c_str(), (long long)table[i].numel, numel);
-                jobs.push_back({dst, table[i].data, numel});
-                return GVX_OK;
-            }
-        return fail(GVX_ERR_MISSING_WEIGHT, "%s is missing", name.c_str());
-    };
-    int rc;
-    if ((rc = take("filter", L.filter, BV_TAPS)) != GVX_OK) return rc;
+    GenPacker P{{table, n}};
+    P.take("filter", L.filter, BV_TAPS);
     size_t C = d.upsample_initial_channel;
     static const char* const part[2] = {".a", ".g"};
     for (int i = 0; i < d.n_stages; ++i) {
         C /= 2;
         for (int j = 0; j < d.n_resblocks; ++j)
             for (int q = 0; q < bv_acts_per_block(d); ++q)
-                for (int v = 0; v < 2; ++v) {
-                    const std::string name = "resblocks." + std::to_string(i * d.n_resblocks + j) + ".activations." + std::to_string(q) + part[v];
-                    if ((rc = take(name, L.act[i][j][q][v], C)) != GVX_OK) return rc;
-                }
+                for (int v = 0; v < 2; ++v)
+                    P.take("resblocks." + std::to_string(i * d.n_resblocks + j) + ".activations." + std::to_string(q) + part[v], L.act[i][j][q][v], C);
     }
-    for (int v = 0; v < 2; ++v)
-        if ((rc = take(std::string("activation_post") + part[v], L.post[v], C)) != GVX_OK) return rc;
+    for (int v = 0; v < 2; ++v) P.take(std::string("activation_post") + part[v], L.post[v], C);
+    if (P.rc != GVX_OK) return P.rc;
     // the convolutions: HiFi-GAN's packer, which refuses before it launches and clears its own part of the blob
-    if ((rc = gvx_hifigan_pack_weights_device(&d, table, n, device_blob, stream)) != GVX_OK) return rc;
-    const size_t base = hg_blob_layout(d).total;
-    HIP_TRY(hipMemsetAsync(device_blob + base, 0, (L.total - base) * sizeof(float), s));   // the padding between the tensors
-    for (const Job& j : jobs) HIP_TRY(hipMemcpyAsync(device_blob + j.dst, j.src, j.numel * sizeof(float), hipMemcpyDeviceToDevice, s));
-    return GVX_OK;
+    if (const int rc = gvx_hifigan_pack_weights_device(&d, table, n, device_blob, stream)) return rc;
+    return P.run(device_blob, hg_blob_layout(d).total, L.total, (hipStream_t)stream);
 }
 
 int gvx_bigvgan_create(const gvx_bigvgan_dims* dims, gvx_bigvgan** out) {
@@ -295,152 +252,45 @@ int gvx_bigvgan_create(const gvx_bigvgan_dims* dims, gvx_bigvgan** out) {
     if (const char* why = bv_dims_problem(dims)) return fail(GVX_ERR_INVALID_ARG, "%s", why);
     gvx_bigvgan* h = new gvx_bigvgan();
     h->d = *dims;
-    h->core.d = dims->net;
     *out = h;
     return GVX_OK;
 }
 
-void gvx_bigvgan_destroy(gvx_bigvgan* h) {
-    if (!h) return;
-    for (int i = 0; i < h->core.n_ev; ++i) (void)hipEventDestroy(h->core.ev[i]);
-    delete h;
-}
+void gvx_bigvgan_destroy(gvx_bigvgan* h) { delete h; }
 
-int gvx_bigvgan_bind(gvx_bigvgan* h, const float* device_blob) {
-    if (!h || !device_blob) return fail(GVX_ERR_INVALID_ARG, "null argument");
-    if ((uintptr_t)device_blob % 256) return fail(GVX_ERR_INVALID_ARG, "the blob must be 256-byte aligned");
-    h->blob = device_blob;
-    return GVX_OK;
-}
+int gvx_bigvgan_bind(gvx_bigvgan* h, const float* device_blob) { return gen_bind(h, device_blob); }
 
-int gvx_bigvgan_timing_enable(gvx_bigvgan* h, int enable) {
-    if (!h) return fail(GVX_ERR_INVALID_ARG, "null argument");
-    const int need = h->d.net.n_stages + 3;
-    while (enable && h->core.n_ev < need) HIP_TRY(hipEventCreate(&h->core.ev[h->core.n_ev++]));
-    h->core.timing = enable != 0;
-    return GVX_OK;
-}
+int gvx_bigvgan_timing_enable(gvx_bigvgan* h, int enable) { return gen_timing_enable(h, enable, h ? h->d.net.n_stages + 3 : 0); }
 
-int gvx_bigvgan_stage_times_ms(gvx_bigvgan* h, float* ms_out, int* n_out) {
-    if (!h || !ms_out || !n_out) return fail(GVX_ERR_INVALID_ARG, "null argument");
-    if (!h->core.timing) return fail(GVX_ERR_STATE, "timing is not enabled");
-    const int n = h->d.net.n_stages + 2;
-    HIP_TRY(hipEventSynchronize(h->core.ev[n]));
-    for (int i = 0; i < n; ++i) HIP_TRY(hipEventElapsedTime(&ms_out[i], h->core.ev[i], h->core.ev[i + 1]));
-    *n_out = n;
-    return GVX_OK;
-}
+int gvx_bigvgan_stage_times_ms(gvx_bigvgan* h, float* ms_out, int* n_out) { return gen_stage_times_ms(h, h ? h->d.net.n_stages + 2 : 0, ms_out, n_out); }
 
 int gvx_bigvgan_forward(gvx_bigvgan* h, const float* mel, const int32_t* frame_lengths, int B, int T, float* wav_out, float* const* stage_out,
                         void* workspace, size_t workspace_bytes, void* stream) {
-    if (!h || !mel || !wav_out) return fail(GVX_ERR_INVALID_ARG, "null argument");
-    if (!h->blob) return fail(GVX_ERR_STATE, "no weight blob is bound");
+    if (!h) return fail(GVX_ERR_INVALID_ARG, "null argument");
     const gvx_hifigan_dims& d = h->d.net;
-    if (B < 1 || B > 65535) return fail(GVX_ERR_INVALID_ARG, "B must be in [1, 65535]");
-    if (T < 1) return fail(GVX_ERR_INVALID_ARG, "T = %d: a row needs at least 1 frame", T);
-    if (T > GVX_HIFIGAN_MAX_FRAMES) return fail(GVX_ERR_UNSUPPORTED, "T = %d is beyond the limit of %d frames", T, GVX_HIFIGAN_MAX_FRAMES);
-    const BvWs wp = bv_ws_plan(d, B, T);
-    if (!workspace || (uintptr_t)workspace % 256 || workspace_bytes < wp.total)
-        return fail(GVX_ERR_WORKSPACE, "the workspace is missing, misaligned or smaller than %zu bytes", wp.total);
-    if (stage_out)
-        for (int i = 0; i < d.n_stages; ++i)
-            if (!stage_out[i] || (uintptr_t)stage_out[i] % 16) return fail(GVX_ERR_INVALID_ARG, "stage_out[%d] is null or not 16-byte aligned", i);
     hipStream_t s = (hipStream_t)stream;
-    int rc;
-    if ((rc = hg_prepare(&h->core)) != GVX_OK) return rc;
-    const HgBlob L = hg_blob_layout(d);
+    const HgWs wp = hg_ws_plan(d, B, T, BV_BUFS);
     const BvBlob A = bv_blob_layout(d);
-    const float* blob = h->blob;
-    float* pool[4];
-    for (int i = 0; i < 4; ++i) pool[i] = gvx::ws_ptr<float>(workspace, wp.buf[i]);
-    float* act = gvx::ws_ptr<float>(workspace, wp.buf[4]);   // A's output: written by one launch, read by the next
-    int ev = 0;
-    auto stamp = [&]() -> int {
-        if (h->core.timing) HIP_TRY(hipEventRecord(h->core.ev[ev++], s));
-        return GVX_OK;
+    // A in front of every convolution but conv_pre and ups: one launch into the fifth tensor, which the convolution then reads as it is
+    const HgFront front = [&](const HgAt& at, HgLayer& p) -> int {
+        if (at.site == HG_PRE || at.site == HG_UPS) return GVX_OK;
+        if (at.site == HG_POST) p.tanh_out = h->d.tanh_at_final;
+        const size_t* ag = at.site == HG_POST ? A.post : A.act[at.stage][at.block][at.act];
+        BvAct a{};
+        a.x = p.src; a.out = gvx::ws_ptr<float>(workspace, wp.buf[4]); a.lens = frame_lengths; a.T = T; a.mul = p.in_mul; a.C = p.Cin;
+        a.f = h->blob + A.filter; a.a = h->blob + ag[0]; a.g = h->blob + ag[1];
+        p.src = a.out;
+        return bv_snake(a, B, s);
     };
-    if ((rc = stamp()) != GVX_OK) return rc;
-
-    const int Cp = hg_cpad(d);
-    float* mel_t = gvx::ws_ptr<float>(workspace, wp.mel_t);
-    if ((rc = hg_mel_transpose(mel, frame_lengths, B, d.n_mels, T, Cp, mel_t, s)) != GVX_OK) return rc;
-    auto layer = [&](const float* src, size_t w, size_t bias, float* out, int in_mul, int Cin, int Cout, int taps, int dil, int phases) {
-        HgLayer p{};
-        p.lens = frame_lengths; p.T = T;
-        p.src = src; p.W = blob + w; p.bias = blob + bias; p.out = out;
-        p.in_mul = in_mul; p.Cin = Cin; p.Cout = Cout; p.taps = taps; p.K = taps * Cin; p.dil = dil; p.phases = phases;
-        return p;   // act = 0: the operand as it is
-    };
-    auto snake = [&](const float* src, const size_t* ag, int mul, int C) {   // act = A(src)
-        BvAct p{};
-        p.x = src; p.out = act; p.lens = frame_lengths; p.T = T; p.mul = mul; p.C = C;
-        p.f = blob + A.filter; p.a = blob + ag[0]; p.g = blob + ag[1];
-        return bv_snake(p, B, s);
-    };
-    int C = d.upsample_initial_channel, mul = 1;
-    float* cur = pool[0];
-    HgLayer p = layer(mel_t, L.pre_w, L.pre_b, cur, 1, Cp, C, 7, 1, 1);
-    if ((rc = hg_launch(p, B, s)) != GVX_OK) return rc;
-    if ((rc = stamp()) != GVX_OK) return rc;
-
-    for (int i = 0; i < d.n_stages; ++i) {
-        const int Cn = C / 2, r = d.upsample_rates[i];
-        // the stage's tensors, as gvx_hifigan_forward assigns them: x, its sum, and a block's two
-        float* rest[4];
-        int n_rest = 0;
-        for (float* c : pool)
-            if (c != cur) rest[n_rest++] = c;
-        float* x = rest[0];
-        float* sum = stage_out ? stage_out[i] : rest[1];
-        float* t0 = rest[2];
-        float* t1 = n_rest == 3 ? cur : rest[1];
-        p = layer(cur, L.up_w[i], L.up_b[i], x, mul, C, Cn, 2, 0, r);   // no activation in front of ups
-        if ((rc = hg_launch(p, B, s)) != GVX_OK) return rc;
-        mul *= r;
-        for (int j = 0; j < d.n_resblocks; ++j) {
-            const int k = d.resblock_kernel_sizes[j];
-            const float* in = x;   // the block's running value
-            for (int m = 0; m < d.n_dilations; ++m) {
-                const bool last = m == d.n_dilations - 1;
-                const int dil = d.resblock_dilation_sizes[j][m];
-                int conv_dil = dil, v = 0;
-                float* next;
-                if (d.resblock == 1) {   // t1 = convs1(A(in)); next = in + convs2(A(t1)): next may be `in` itself once that is t0
-                    if ((rc = snake(in, A.act[i][j][2 * m], mul, Cn)) != GVX_OK) return rc;
-                    p = layer(act, L.conv_w[i][j][m][0], L.conv_b[i][j][m][0], t1, mul, Cn, Cn, k, dil, 1);
-                    if ((rc = hg_launch(p, B, s)) != GVX_OK) return rc;
-                    if ((rc = snake(t1, A.act[i][j][2 * m + 1], mul, Cn)) != GVX_OK) return rc;
-                    conv_dil = 1; v = 1;
-                    next = t0;
-                } else {                 // next = in + convs(A(in))
-                    if ((rc = snake(in, A.act[i][j][m], mul, Cn)) != GVX_OK) return rc;
-                    next = in == t0 ? t1 : t0;
-                }
-                p = layer(act, L.conv_w[i][j][m][v], L.conv_b[i][j][m][v], last ? sum : next, mul, Cn, Cn, k, conv_dil, 1);
-                p.res = in;
-                if (last) {   // y_j goes into the stage's sum: written by the first block, added by the later ones, the last divides
-                    p.accumulate = j > 0;
-                    p.divide = j == d.n_resblocks - 1 ? (float)d.n_resblocks : 0.f;
-                    p.zero_tail = (stage_out && j == 0) ? 1 : 0;
-                }
-                if ((rc = hg_launch(p, B, s)) != GVX_OK) return rc;
-                in = next;
-            }
-        }
-        cur = sum;
-        C = Cn;
-        if ((rc = stamp()) != GVX_OK) return rc;
-    }
-    if ((rc = snake(cur, A.post, mul, C)) != GVX_OK) return rc;
-    p = layer(act, L.post_w, L.post_b, wav_out, mul, C, 1, 7, 1, 1);
-    p.tanh_out = h->d.tanh_at_final; p.zero_tail = 1;
-    if ((rc = hg_launch(p, B, s)) != GVX_OK) return rc;
+    int rc;
+    if ((rc = hg_forward(h, &h->lds_ready, d, wp, front, mel, frame_lengths, B, T, wav_out, stage_out, workspace, workspace_bytes, s)) != GVX_OK) return rc;
     if (!h->d.tanh_at_final) {
-        const long count = (long)B * T * mul;
+        long count = (long)B * T;
+        for (int i = 0; i < d.n_stages; ++i) count *= d.upsample_rates[i];
         bv_clamp_kernel<<<(unsigned)((count + 255) / 256), 256, 0, s>>>(wav_out, count);
         HIP_TRY(hipGetLastError());
     }
-    return stamp();
+    return gen_mark(h, d.n_stages + 2, s);
 }
 
 }  // C ABI

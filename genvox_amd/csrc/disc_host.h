@@ -3,7 +3,7 @@
 // the pack loop, and the per-layer blocks of the backward walk.  A "stack" is one period or one scale: nl layers, the score last.
 #pragma once
 #include "disc_conv.h"
-#include "gvx_internal.h"
+#include "gen_host.h"
 
 #include <string>
 #include <vector>
@@ -88,9 +88,9 @@ int dc_find_params(const gvx_weight_desc* table, int n, int n_stacks, const Laye
     for (int j = 0; j < n_stacks; ++j)
         for (int i = 0; i < nl; ++i) {
             const std::string name = dc_name(j, i, nl);
-            const gvx_weight_desc* w = gvx_mg::mg_find(table, n, name + ".weight", L[i].wn(), rc);
+            const gvx_weight_desc* w = gvx_gen::gen_find(table, n, name + ".weight", L[i].wn(), rc);
             if (!w) return rc;
-            const gvx_weight_desc* b = gvx_mg::mg_find(table, n, name + ".bias", (size_t)L[i].cout, rc);
+            const gvx_weight_desc* b = gvx_gen::gen_find(table, n, name + ".bias", (size_t)L[i].cout, rc);
             if (!b) return rc;
             out[j * nl + i] = DcParam{const_cast<float*>(w->data), const_cast<float*>(b->data)};
         }

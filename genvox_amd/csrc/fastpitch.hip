@@ -19,23 +19,19 @@
 // No atomics anywhere.  Positions at and behind a row's length are written as zeros by every launch and never read by one.
 //
 // Order of this file: kernels, dims / blob / workspace layouts, the C ABI.
-#include "gvx_internal.h"
+#include "gen_host.h"
 
 #include <algorithm>
 
-using gvx::fail;
+using namespace gvx_gen;
 using gvx::GemmParams;
 using gvx::RowMap;
 
 namespace gvx { hipError_t gemm_init(); }
 
-struct gvx_fastpitch {
+struct gvx_fastpitch : GenHandle {
     gvx_fastpitch_dims d;
-    const float* blob = nullptr;
-    bool timing = false;
-    hipEvent_t ev[7] = {};
-    int n_ev = 0;
-    bool encoded = false, decoded = false;   // which events of the last call exist
+    bool encoded = false, decoded = false;   // which marks have been recorded since timing was enabled
 };
 
 namespace {
@@ -428,9 +424,6 @@ __global__ void fp_zero_kernel(float* p, long n) {
 }
 
 // ---- dims, blob, workspace
-inline size_t fp_round64(size_t floats) { return (floats + 63) & ~(size_t)63; }
-inline size_t fp_round256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-
 const char* fp_stack_problem(const gvx_fft_stack_dims& s) {
     if (s.n_layers < 1 || s.n_layers > GVX_FASTPITCH_MAX_LAYERS) return "n_layers must be in [1, GVX_FASTPITCH_MAX_LAYERS]";
     if (s.n_head < 1 || s.n_head > GVX_FASTPITCH_MAX_HEADS) return "n_head must be in [1, GVX_FASTPITCH_MAX_HEADS]";
@@ -478,7 +471,7 @@ template <typename F>
 FpBlob fp_blob_layout(const gvx_fastpitch_dims& d, F&& visit) {
     FpBlob L{};
     size_t at = 0;
-    auto take = [&](const std::string& name, size_t floats) { const size_t o = at; at += fp_round64(floats); if (!name.empty()) visit(name, o, floats); return o; };
+    auto take = [&](const std::string& name, size_t floats) { const size_t o = at; at += gen_round64(floats); if (!name.empty()) visit(name, o, floats); return o; };
     const size_t C = d.d_model, F_ = d.pred_filter;
     L.emb = take("encoder.word_emb.weight", (size_t)d.n_tokens * C);
     for (int s = 0; s < 2; ++s) {
@@ -520,16 +513,15 @@ struct FpWs { size_t xa, xb, qkv, att, o, hid, pa, pb, pt, proj, total; };
 // either phase at N positions: the stack's tensors at the larger of the two stacks' widths, the predictors' and the projection's
 FpWs fp_ws_plan(const gvx_fastpitch_dims& d, int B, int N) {
     FpWs w{};
-    size_t at = 0;
-    auto take = [&](size_t floats_per_row) { const size_t o = at; at += (size_t)B * fp_round256(floats_per_row * sizeof(float)); return o; };
+    GenRows ws{B};
     const size_t C = d.d_model, HD = std::max(d.enc.n_head * d.enc.d_head, d.dec.n_head * d.dec.d_head), I = std::max(d.enc.d_inner, d.dec.d_inner);
     const size_t F_ = d.pred_filter, n = N;
-    w.xa = take((n + 2) * C); w.xb = take((n + 2) * C);
-    w.qkv = take(n * 3 * HD); w.att = take(n * HD); w.o = take(n * C);
-    w.hid = take((n + 2) * I);
-    w.pa = take((n + 2) * F_); w.pb = take((n + 2) * F_); w.pt = take(n * F_);
-    w.proj = take(n * d.n_mels);
-    w.total = at;
+    w.xa = ws.rows((n + 2) * C); w.xb = ws.rows((n + 2) * C);
+    w.qkv = ws.rows(n * 3 * HD); w.att = ws.rows(n * HD); w.o = ws.rows(n * C);
+    w.hid = ws.rows((n + 2) * I);
+    w.pa = ws.rows((n + 2) * F_); w.pb = ws.rows((n + 2) * F_); w.pt = ws.rows(n * F_);
+    w.proj = ws.rows(n * d.n_mels);
+    w.total = ws.total;
     return w;
 }
 
@@ -637,19 +629,9 @@ int gvx_fastpitch_pack_weights_device(const gvx_fastpitch_dims* dims, const gvx_
     if (!table || n < 1 || !device_blob) return fail(GVX_ERR_INVALID_ARG, "null argument");
     const gvx_fastpitch_dims& d = *dims;
     hipStream_t s = (hipStream_t)stream;
-    struct Job { size_t dst; const float* src; size_t numel; };
-    std::vector<Job> jobs;
-    int rc = GVX_OK;
-    const FpBlob L = fp_blob_layout(d, [&](const std::string& name, size_t dst, size_t numel) {   // every name is looked up before anything is launched
-        if (rc != GVX_OK) return;
-        int found = GVX_OK;
-        const gvx_weight_desc* e = gvx_mg::mg_find(table, n, name, numel, found);
-        if (!e) { rc = found; return; }
-        jobs.push_back({dst, e->data, numel});
-    });
-    if (rc != GVX_OK) return rc;
-    HIP_TRY(hipMemsetAsync(device_blob, 0, L.total * sizeof(float), s));   // the padding between the tensors
-    for (const Job& j : jobs) HIP_TRY(hipMemcpyAsync(device_blob + j.dst, j.src, j.numel * sizeof(float), hipMemcpyDeviceToDevice, s));
+    GenPacker P{{table, n}};
+    const FpBlob L = fp_blob_layout(d, [&](const std::string& name, size_t dst, size_t numel) { P.take(name, dst, numel); });
+    if (const int rc = P.run(device_blob, 0, L.total, s)) return rc;
     const long n_pos = (long)fp_positions(d) * d.d_model;
     fp_pos_table_kernel<<<(unsigned)((n_pos + 255) / 256), 256, 0, s>>>(device_blob + L.pos, fp_positions(d), d.d_model);
     HIP_TRY(hipGetLastError());
@@ -665,41 +647,34 @@ int gvx_fastpitch_create(const gvx_fastpitch_dims* dims, gvx_fastpitch** out) {
     return GVX_OK;
 }
 
-void gvx_fastpitch_destroy(gvx_fastpitch* h) {
-    if (!h) return;
-    for (int i = 0; i < h->n_ev; ++i) (void)hipEventDestroy(h->ev[i]);
-    delete h;
-}
+void gvx_fastpitch_destroy(gvx_fastpitch* h) { delete h; }
 
 int gvx_fastpitch_bind(gvx_fastpitch* h, const float* device_blob) {
-    if (!h || !device_blob) return fail(GVX_ERR_INVALID_ARG, "null argument");
-    if ((uintptr_t)device_blob % 256) return fail(GVX_ERR_INVALID_ARG, "the blob must be 256-byte aligned");
-    h->blob = device_blob;
+    if (const int rc = gen_bind(h, device_blob)) return rc;
     HIP_TRY(gvx::gemm_init());   // the big tiles' dynamic LDS
     return GVX_OK;
 }
 
 int gvx_fastpitch_timing_enable(gvx_fastpitch* h, int enable) {
-    if (!h) return fail(GVX_ERR_INVALID_ARG, "null argument");
-    while (enable && h->n_ev < 7) HIP_TRY(hipEventCreate(&h->ev[h->n_ev++]));
-    h->timing = enable != 0;
+    if (const int rc = gen_timing_enable(h, enable, 7)) return rc;
     h->encoded = h->decoded = false;
     return GVX_OK;
 }
 
-// ev[0 .. 2]: encode's start, behind the encoder, its end; ev[3 .. 6]: decode's start, behind the regulator, the decoder, the projection
+// marks 0 .. 2: encode's start, behind the encoder, its end; marks 3 .. 6: decode's start, behind the regulator, the decoder, the projection
 int gvx_fastpitch_stage_times_ms(gvx_fastpitch* h, float* ms_out, int* n_out) {
     if (!h || !ms_out || !n_out) return fail(GVX_ERR_INVALID_ARG, "null argument");
     if (!h->timing) return fail(GVX_ERR_STATE, "timing is not enabled");
     if (!h->encoded || !h->decoded) return fail(GVX_ERR_STATE, "no encode and decode since timing was enabled");
-    HIP_TRY(hipEventSynchronize(h->ev[6]));
+    const std::vector<hipEvent_t>& ev = h->marks.ev;
+    HIP_TRY(hipEventSynchronize(ev[6]));
     float reg = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms_out[0], h->ev[0], h->ev[1]));
-    HIP_TRY(hipEventElapsedTime(&ms_out[1], h->ev[1], h->ev[2]));
-    HIP_TRY(hipEventElapsedTime(&reg, h->ev[3], h->ev[4]));
+    HIP_TRY(hipEventElapsedTime(&ms_out[0], ev[0], ev[1]));
+    HIP_TRY(hipEventElapsedTime(&ms_out[1], ev[1], ev[2]));
+    HIP_TRY(hipEventElapsedTime(&reg, ev[3], ev[4]));
     ms_out[1] += reg;
-    HIP_TRY(hipEventElapsedTime(&ms_out[2], h->ev[4], h->ev[5]));
-    HIP_TRY(hipEventElapsedTime(&ms_out[3], h->ev[5], h->ev[6]));
+    HIP_TRY(hipEventElapsedTime(&ms_out[2], ev[4], ev[5]));
+    HIP_TRY(hipEventElapsedTime(&ms_out[3], ev[5], ev[6]));
     *n_out = 4;
     return GVX_OK;
 }
@@ -714,21 +689,15 @@ int gvx_fastpitch_encode(gvx_fastpitch* h, const int32_t* tokens, const int32_t*
     if (L > d.max_tokens) return fail(GVX_ERR_INVALID_ARG, "L = %d is beyond max_tokens = %d", L, d.max_tokens);
     if (!(pace >= 0.125f && pace <= 8.f)) return fail(GVX_ERR_INVALID_ARG, "pace must be in [0.125, 8]");
     const FpWs wp = fp_ws_plan(d, B, L);
-    if (!workspace || (uintptr_t)workspace % 256 || workspace_bytes < wp.total)
-        return fail(GVX_ERR_WORKSPACE, "the workspace is missing, misaligned or smaller than %zu bytes", wp.total);
+    int ev = 0, rc;
+    if ((rc = gen_check_workspace(workspace, workspace_bytes, wp.total)) != GVX_OK) return rc;
     if ((uintptr_t)enc_out % 16) return fail(GVX_ERR_INVALID_ARG, "enc_out must be 16-byte aligned");
-    if (stage_out)
-        for (int i = 0; i <= d.enc.n_layers; ++i)
-            if (!stage_out[i] || (uintptr_t)stage_out[i] % 16) return fail(GVX_ERR_INVALID_ARG, "stage_out[%d] is null or not 16-byte aligned", i);
+    if ((rc = gen_check_stage_out(stage_out, d.enc.n_layers + 1)) != GVX_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     const FpBlob BL = fp_blob_layout(d);
     const float* blob = h->blob;
     const int C = d.d_model;
-    int ev = 0, rc;
-    auto stamp = [&]() -> int {
-        if (h->timing) HIP_TRY(hipEventRecord(h->ev[ev++], s));
-        return GVX_OK;
-    };
+    auto stamp = [&] { return gen_mark(h, ev++, s); };
     if ((rc = stamp()) != GVX_OK) return rc;
     // the stack's last LayerNorm writes the buffer it started from: an even walk that ends in enc_out starts there
     float* xb = gvx::ws_ptr<float>(workspace, wp.xb);
@@ -769,20 +738,14 @@ int gvx_fastpitch_decode(gvx_fastpitch* h, const float* enc_out, const int32_t* 
     if (const char* why = fp_shape_problem(B, T)) return fail(GVX_ERR_INVALID_ARG, "%s", why);
     if (T > d.max_decoder_steps) return fail(GVX_ERR_INVALID_ARG, "T = %d is beyond max_decoder_steps = %d", T, d.max_decoder_steps);
     const FpWs wp = fp_ws_plan(d, B, T);
-    if (!workspace || (uintptr_t)workspace % 256 || workspace_bytes < wp.total)
-        return fail(GVX_ERR_WORKSPACE, "the workspace is missing, misaligned or smaller than %zu bytes", wp.total);
-    if (stage_out)
-        for (int i = 0; i <= d.dec.n_layers; ++i)
-            if (!stage_out[i] || (uintptr_t)stage_out[i] % 16) return fail(GVX_ERR_INVALID_ARG, "stage_out[%d] is null or not 16-byte aligned", i);
+    int ev = 3, rc;
+    if ((rc = gen_check_workspace(workspace, workspace_bytes, wp.total)) != GVX_OK) return rc;
+    if ((rc = gen_check_stage_out(stage_out, d.dec.n_layers + 1)) != GVX_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     const FpBlob BL = fp_blob_layout(d);
     const float* blob = h->blob;
     const int C = d.d_model, M = d.n_mels;
-    int ev = 3, rc;
-    auto stamp = [&]() -> int {
-        if (h->timing) HIP_TRY(hipEventRecord(h->ev[ev++], s));
-        return GVX_OK;
-    };
+    auto stamp = [&] { return gen_mark(h, ev++, s); };
     if ((rc = stamp()) != GVX_OK) return rc;
     float* xa = gvx::ws_ptr<float>(workspace, wp.xa);
     float* xb = gvx::ws_ptr<float>(workspace, wp.xb);

@@ -302,9 +302,3 @@ int poison_if_timed_out(const gvx_model* m, int B, int L, void* ws, const WsPlan
                         hipStream_t s);
 
 }  // namespace gvx
-
-namespace gvx_mg {
-// the entry `name` of a weight (or gradient) table, which must hold `numel` elements; NULL with rc set to the failure otherwise.  Defined in
-// melgan.hip; every vocoder and discriminator that packs by name uses it
-const gvx_weight_desc* mg_find(const gvx_weight_desc* table, int n, const std::string& name, size_t numel, int& rc);
-}  // namespace gvx_mg

@@ -15,7 +15,7 @@
 // A workgroup belongs to one batch row and computes nothing behind that row's length; tensors the caller sees are zero-filled there.
 //
 // The two kernels are in hifigan_kernels.h (the training path, hifigan_train.hip, runs its data gradients on them).
-// Order of this file: the mel transpose, the weight packer, the launches, the C ABI.
+// Order of this file: the mel transpose, the launches, the forward that BigVGAN shares, the C ABI.
 #include "hifigan_kernels.h"
 
 using gvx::fail;
@@ -29,52 +29,11 @@ __global__ void __launch_bounds__(256) hg_mel_transpose_kernel(const float* mel,
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (long)T * Cp) return;
     const int t = (int)(idx % T), c = (int)(idx / T);
-    const int Tb = hg_frames(lens, b, T);
+    const int Tb = gen_frames(lens, b, T);
     out[((size_t)b * T + t) * Cp + c] = (t < Tb && c < M) ? mel[((size_t)b * M + c) * T + t] : 0.f;
 }
 
-// Conv1d weight [Cout][Cin][k] -> dst[n][tau * Cp + c], zeros for the padded channels c >= Cin (a bias: Cin = Cp = k = 1)
-__global__ void __launch_bounds__(256) hg_pack_conv_kernel(float* dst, const float* src, int Cout, int Cin, int Cp, int k) {
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long)Cout * k * Cp) return;
-    const int c = (int)(idx % Cp), tau = (int)((idx / Cp) % k), n = (int)(idx / ((long)Cp * k));
-    dst[idx] = c < Cin ? src[((size_t)n * Cin + c) * k + tau] : 0.f;
-}
-
-// ConvTranspose1d weight [Cin][Cout][2r] -> dst[phase][n][tau * Cin + c]: the kernel tap that connects output r q + phase with its tap-tau input
-__global__ void __launch_bounds__(256) hg_pack_tconv_kernel(float* dst, const float* src, int Cin, int Cout, int r) {
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long)r * Cout * 2 * Cin) return;
-    const int c = (int)(idx % Cin), tau = (int)((idx / Cin) % 2), n = (int)((idx / (2l * Cin)) % Cout), phase = (int)(idx / (2l * Cin * Cout));
-    const int half = r / 2;
-    const int tap = tau == 0 ? phase + half : (phase < half ? phase + half + r : phase + half - r);
-    dst[idx] = src[((size_t)c * Cout + n) * (2 * r) + tap];
-}
-
 // ---- host side
-struct HgWs {   // byte offsets; every region is B times a per-row size that is a multiple of 256
-    size_t mel_t, buf[4], total;
-};
-
-HgWs hg_ws_plan(const gvx_hifigan_dims& d, int B, int T) {
-    size_t widest = d.upsample_initial_channel, mul = 1, C = d.upsample_initial_channel;   // floats per frame of the widest activation tensor
-    for (int i = 0; i < d.n_stages; ++i) {
-        mul *= d.upsample_rates[i];
-        C /= 2;
-        widest = std::max(widest, mul * C);
-    }
-    HgWs w{};
-    size_t at = 0;
-    w.mel_t = at;
-    at += (size_t)B * hg_round256((size_t)T * hg_cpad(d) * sizeof(float));
-    for (int i = 0; i < 4; ++i) {
-        w.buf[i] = at;
-        at += (size_t)B * hg_round256((size_t)T * widest * sizeof(float));
-    }
-    w.total = at;
-    return w;
-}
-
 template <int WR, int WC, int TM, int TN>
 int hg_launch_mfma(const HgLayer& p, int B, hipStream_t s) {
     constexpr int BM = WR * TM * 32, BN = WC * TN * 32;
@@ -102,15 +61,15 @@ int gvx_hg::hg_launch(const HgLayer& p, int B, hipStream_t s) {
 }
 
 // once per handle: the dynamic LDS of the largest window any layer of any supported configuration asks for
-int gvx_hg::hg_prepare(gvx_hifigan* h) {
-    if (!h->lds_ready) {
+int gvx_hg::hg_prepare(bool* ready) {
+    if (!*ready) {
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(hg_mfma_kernel<2, 2, 2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)hg_lds_bytes(GVX_HIFIGAN_MAX_WINDOW, 128)));
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(hg_mfma_kernel<4, 1, 1, 2>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)hg_lds_bytes(GVX_HIFIGAN_MAX_WINDOW, 64)));
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(hg_mfma_kernel<4, 1, 1, 1>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)hg_lds_bytes(GVX_HIFIGAN_MAX_WINDOW, 32)));
-        h->lds_ready = true;
+        *ready = true;
     }
     return GVX_OK;
 }
@@ -122,167 +81,59 @@ int gvx_hg::hg_mel_transpose(const float* mel, const int32_t* lens, int B, int M
     return GVX_OK;
 }
 
-namespace {
-
-const gvx_weight_desc* hg_find(const gvx_weight_desc* table, int n, const std::string& name, size_t numel, int& rc) {
-    for (int i = 0; i < n; ++i)
-        if (table[i].name && name == table[i].name) {
-            if (!table[i].data || table[i].numel != (int64_t)numel) {
-                rc = fail(GVX_ERR_SHAPE, "%s has %lld elements, the dims ask for %zu", name.c_str(), (long long)table[i].numel, numel);
-                return nullptr;
-            }
-            return &table[i];
-        }
-    rc = fail(GVX_ERR_MISSING_WEIGHT, "%s is missing", name.c_str());
-    return nullptr;
-}
-
-}  // namespace
-
-extern "C" {
-
-size_t gvx_hifigan_blob_floats(const gvx_hifigan_dims* dims) {
-    if (hg_dims_problem(dims)) return 0;
-    return hg_blob_layout(*dims).total;
-}
-
-size_t gvx_hifigan_workspace_bytes(const gvx_hifigan_dims* dims, int B, int T) {
-    if (hg_dims_problem(dims) || B < 1 || T < 1 || T > GVX_HIFIGAN_MAX_FRAMES) return 0;
-    return hg_ws_plan(*dims, B, T).total;
-}
-
-int gvx_hifigan_pack_weights_device(const gvx_hifigan_dims* dims, const gvx_weight_desc* table, int n, float* device_blob, void* stream) {
-    if (const char* why = hg_dims_problem(dims)) return fail(GVX_ERR_INVALID_ARG, "%s", why);
-    if (!table || n < 1 || !device_blob) return fail(GVX_ERR_INVALID_ARG, "null argument");
-    const gvx_hifigan_dims& d = *dims;
-    const HgBlob L = hg_blob_layout(d);
-    hipStream_t s = (hipStream_t)stream;
-    struct Job { int kind; size_t dst; const float* src; int a, b, c, k; };   // kind 0: conv (Cout a, Cin b, Cp c), 1: tconv (Cin a, Cout b, r c)
-    std::vector<Job> jobs;
-    int rc = GVX_OK;
-    auto conv = [&](const std::string& name, size_t dst_w, size_t dst_b, int Cout, int Cin, int Cp, int k) {
-        if (rc != GVX_OK) return;
-        if (const gvx_weight_desc* w = hg_find(table, n, name + ".weight", (size_t)Cout * Cin * k, rc)) jobs.push_back({0, dst_w, w->data, Cout, Cin, Cp, k});
-        if (rc != GVX_OK) return;
-        if (const gvx_weight_desc* w = hg_find(table, n, name + ".bias", (size_t)Cout, rc)) jobs.push_back({0, dst_b, w->data, Cout, 1, 1, 1});
-    };
-    int C = d.upsample_initial_channel;
-    conv("conv_pre", L.pre_w, L.pre_b, C, d.n_mels, hg_cpad(d), 7);
-    for (int i = 0; i < d.n_stages && rc == GVX_OK; ++i) {
-        const int Cn = C / 2;
-        const std::string up = "ups." + std::to_string(i);
-        if (const gvx_weight_desc* w = hg_find(table, n, up + ".weight", (size_t)C * Cn * 2 * d.upsample_rates[i], rc))
-            jobs.push_back({1, L.up_w[i], w->data, C, Cn, d.upsample_rates[i], 0});
-        if (rc != GVX_OK) break;
-        if (const gvx_weight_desc* w = hg_find(table, n, up + ".bias", (size_t)Cn, rc)) jobs.push_back({0, L.up_b[i], w->data, Cn, 1, 1, 1});
-        for (int j = 0; j < d.n_resblocks; ++j)
-            for (int m = 0; m < d.n_dilations; ++m)
-                for (int v = 0; v < hg_convs_per_dilation(d); ++v)
-                    conv(hg_conv_name(d, i * d.n_resblocks + j, m, v), L.conv_w[i][j][m][v], L.conv_b[i][j][m][v], Cn, Cn, Cn, d.resblock_kernel_sizes[j]);
-        C = Cn;
+HgWs gvx_hg::hg_ws_plan(const gvx_hifigan_dims& d, int B, int T, int n_bufs) {
+    size_t widest = d.upsample_initial_channel, mul = 1, C = d.upsample_initial_channel;   // floats per frame of the widest activation tensor
+    for (int i = 0; i < d.n_stages; ++i) {
+        mul *= d.upsample_rates[i];
+        C /= 2;
+        widest = std::max(widest, mul * C);
     }
-    conv("conv_post", L.post_w, L.post_b, 1, C, C, 7);
-    if (rc != GVX_OK) return rc;   // nothing was launched
-    HIP_TRY(hipMemsetAsync(device_blob, 0, L.total * sizeof(float), s));   // the padding between the tensors
-    for (const Job& j : jobs) {
-        if (j.kind == 0) {
-            const long count = (long)j.a * j.k * j.c;
-            hg_pack_conv_kernel<<<(unsigned)((count + 255) / 256), 256, 0, s>>>(device_blob + j.dst, j.src, j.a, j.b, j.c, j.k);
-        } else {
-            const long count = (long)j.c * j.b * 2 * j.a;
-            hg_pack_tconv_kernel<<<(unsigned)((count + 255) / 256), 256, 0, s>>>(device_blob + j.dst, j.src, j.a, j.b, j.c);
-        }
-        HIP_TRY(hipGetLastError());
-    }
-    return GVX_OK;
+    HgWs w{};
+    GenRows ws{B};
+    w.mel_t = ws.rows((size_t)T * hg_cpad(d));
+    for (int i = 0; i < n_bufs; ++i) w.buf[i] = ws.rows((size_t)T * widest);
+    w.total = ws.total;
+    return w;
 }
 
-int gvx_hifigan_create(const gvx_hifigan_dims* dims, gvx_hifigan** out) {
-    if (!out) return fail(GVX_ERR_INVALID_ARG, "null argument");
-    if (const char* why = hg_dims_problem(dims)) return fail(GVX_ERR_INVALID_ARG, "%s", why);
-    gvx_hifigan* h = new gvx_hifigan();
-    h->d = *dims;
-    *out = h;
-    return GVX_OK;
-}
-
-void gvx_hifigan_destroy(gvx_hifigan* h) {
-    if (!h) return;
-    for (int i = 0; i < h->n_ev; ++i) (void)hipEventDestroy(h->ev[i]);
-    for (int i = 0; i < h->n_ev_bwd; ++i) (void)hipEventDestroy(h->ev_bwd[i]);
-    delete h;
-}
-
-int gvx_hifigan_bind(gvx_hifigan* h, const float* device_blob) {
-    if (!h || !device_blob) return fail(GVX_ERR_INVALID_ARG, "null argument");
-    if ((uintptr_t)device_blob % 256) return fail(GVX_ERR_INVALID_ARG, "the blob must be 256-byte aligned");
-    h->blob = device_blob;
-    return GVX_OK;
-}
-
-int gvx_hifigan_timing_enable(gvx_hifigan* h, int enable) {
-    if (!h) return fail(GVX_ERR_INVALID_ARG, "null argument");
-    const int need = h->d.n_stages + 3;
-    while (enable && h->n_ev < need) HIP_TRY(hipEventCreate(&h->ev[h->n_ev++]));
-    while (enable && h->n_ev_bwd < need + 1) HIP_TRY(hipEventCreate(&h->ev_bwd[h->n_ev_bwd++]));
-    h->timing = enable != 0;
-    return GVX_OK;
-}
-
-int gvx_hifigan_stage_times_ms(gvx_hifigan* h, float* ms_out, int* n_out) {
-    if (!h || !ms_out || !n_out) return fail(GVX_ERR_INVALID_ARG, "null argument");
-    if (!h->timing) return fail(GVX_ERR_STATE, "timing is not enabled");
-    const int n = h->d.n_stages + 2;
-    HIP_TRY(hipEventSynchronize(h->ev[n]));
-    for (int i = 0; i < n; ++i) HIP_TRY(hipEventElapsedTime(&ms_out[i], h->ev[i], h->ev[i + 1]));
-    *n_out = n;
-    return GVX_OK;
-}
-
-int gvx_hifigan_forward(gvx_hifigan* h, const float* mel, const int32_t* frame_lengths, int B, int T, float* wav_out, float* const* stage_out,
-                        void* workspace, size_t workspace_bytes, void* stream) {
+int gvx_hg::hg_forward(const GenHandle* h, bool* lds_ready, const gvx_hifigan_dims& d, const HgWs& wp, const HgFront& front, const float* mel,
+                       const int32_t* frame_lengths, int B, int T, float* wav_out, float* const* stage_out, void* workspace, size_t workspace_bytes,
+                       hipStream_t s) {
     if (!h || !mel || !wav_out) return fail(GVX_ERR_INVALID_ARG, "null argument");
     if (!h->blob) return fail(GVX_ERR_STATE, "no weight blob is bound");
-    const gvx_hifigan_dims& d = h->d;
     if (B < 1 || B > 65535) return fail(GVX_ERR_INVALID_ARG, "B must be in [1, 65535]");
     if (T < 1) return fail(GVX_ERR_INVALID_ARG, "T = %d: a row needs at least 1 frame", T);
     if (T > GVX_HIFIGAN_MAX_FRAMES) return fail(GVX_ERR_UNSUPPORTED, "T = %d is beyond the limit of %d frames", T, GVX_HIFIGAN_MAX_FRAMES);
-    const HgWs wp = hg_ws_plan(d, B, T);
-    if (!workspace || (uintptr_t)workspace % 256 || workspace_bytes < wp.total)
-        return fail(GVX_ERR_WORKSPACE, "the workspace is missing, misaligned or smaller than %zu bytes", wp.total);
-    if (stage_out)
-        for (int i = 0; i < d.n_stages; ++i)
-            if (!stage_out[i] || (uintptr_t)stage_out[i] % 16) return fail(GVX_ERR_INVALID_ARG, "stage_out[%d] is null or not 16-byte aligned", i);
-    hipStream_t s = (hipStream_t)stream;
     int rc;
-    if ((rc = hg_prepare(h)) != GVX_OK) return rc;
+    if ((rc = gen_check_workspace(workspace, workspace_bytes, wp.total)) != GVX_OK) return rc;
+    if ((rc = gen_check_stage_out(stage_out, d.n_stages)) != GVX_OK) return rc;
+    if ((rc = hg_prepare(lds_ready)) != GVX_OK) return rc;
     const HgBlob L = hg_blob_layout(d);
     const float* blob = h->blob;
     float* pool[4];
     for (int i = 0; i < 4; ++i) pool[i] = gvx::ws_ptr<float>(workspace, wp.buf[i]);
     int ev = 0;
-    auto stamp = [&]() -> int {
-        if (h->timing) HIP_TRY(hipEventRecord(h->ev[ev++], s));
-        return GVX_OK;
-    };
-    if ((rc = stamp()) != GVX_OK) return rc;
+    if ((rc = gen_mark(h, ev++, s)) != GVX_OK) return rc;
 
     const int Cp = hg_cpad(d);
     float* mel_t = gvx::ws_ptr<float>(workspace, wp.mel_t);
     if ((rc = hg_mel_transpose(mel, frame_lengths, B, d.n_mels, T, Cp, mel_t, s)) != GVX_OK) return rc;
-    auto layer = [&](const float* src, size_t w, size_t bias, float* out, int in_mul, int Cin, int Cout, int taps, int dil, int phases, int act) {
-        HgLayer p{};
-        p.lens = frame_lengths; p.T = T; p.slope = d.slope;
+    // p = one layer's description but for the operand's treatment, then the model's front on it; the caller adds what the site needs and launches
+    HgLayer p;
+    auto layer = [&](const HgAt& at, const float* src, size_t w, size_t bias, float* out, int in_mul, int Cin, int Cout, int taps, int dil, int phases) {
+        p = HgLayer{};
+        p.lens = frame_lengths; p.T = T;
         p.src = src; p.W = blob + w; p.bias = blob + bias; p.out = out;
-        p.in_mul = in_mul; p.Cin = Cin; p.Cout = Cout; p.taps = taps; p.K = taps * Cin; p.dil = dil; p.phases = phases; p.act = act;
-        return p;
+        p.in_mul = in_mul; p.Cin = Cin; p.Cout = Cout; p.taps = taps; p.K = taps * Cin; p.dil = dil; p.phases = phases;
+        return front(at, p);
     };
     int C = d.upsample_initial_channel, mul = 1;
     float* cur = pool[0];
-    HgLayer p = layer(mel_t, L.pre_w, L.pre_b, cur, 1, Cp, C, 7, 1, 1, 0);   // conv_pre: no activation in front of it
+    if ((rc = layer({HG_PRE, 0, 0, 0}, mel_t, L.pre_w, L.pre_b, cur, 1, Cp, C, 7, 1, 1)) != GVX_OK) return rc;
     if ((rc = hg_launch(p, B, s)) != GVX_OK) return rc;
-    if ((rc = stamp()) != GVX_OK) return rc;
+    if ((rc = gen_mark(h, ev++, s)) != GVX_OK) return rc;
 
+    const int nv = hg_convs_per_dilation(d);
     for (int i = 0; i < d.n_stages; ++i) {
         const int Cn = C / 2, r = d.upsample_rates[i];
         // the stage's tensors: x, its sum, and a block's two.  The stage's input is free once ups has run; it is a pool tensor unless
@@ -295,7 +146,7 @@ int gvx_hifigan_forward(gvx_hifigan* h, const float* mel, const int32_t* frame_l
         float* sum = stage_out ? stage_out[i] : rest[1];
         float* t0 = rest[2];
         float* t1 = n_rest == 3 ? cur : rest[1];
-        p = layer(cur, L.up_w[i], L.up_b[i], x, mul, C, Cn, 2, 0, r, 1);
+        if ((rc = layer({HG_UPS, i, 0, 0}, cur, L.up_w[i], L.up_b[i], x, mul, C, Cn, 2, 0, r)) != GVX_OK) return rc;
         if ((rc = hg_launch(p, B, s)) != GVX_OK) return rc;
         mul *= r;
         for (int j = 0; j < d.n_resblocks; ++j) {
@@ -307,15 +158,16 @@ int gvx_hifigan_forward(gvx_hifigan* h, const float* mel, const int32_t* frame_l
                 const float* conv_in = in;
                 int conv_dil = dil, v = 0;
                 float* next;
-                if (d.resblock == 1) {   // t1 = convs1(lrelu(in)); next = in + convs2(lrelu(t1)): next may be `in` itself once that is t0
-                    p = layer(in, L.conv_w[i][j][m][0], L.conv_b[i][j][m][0], t1, mul, Cn, Cn, k, dil, 1, 1);
+                if (d.resblock == 1) {   // t1 = convs1(act(in)); next = in + convs2(act(t1)): next may be `in` itself once that is t0
+                    if ((rc = layer({HG_CONV, i, j, nv * m}, in, L.conv_w[i][j][m][0], L.conv_b[i][j][m][0], t1, mul, Cn, Cn, k, dil, 1)) != GVX_OK) return rc;
                     if ((rc = hg_launch(p, B, s)) != GVX_OK) return rc;
                     conv_in = t1; conv_dil = 1; v = 1;
                     next = t0;
-                } else {                 // next = in + convs(lrelu(in)): the convolution reads its neighbours, so next is another tensor
+                } else {                 // next = in + convs(act(in)): the convolution reads its neighbours, so next is another tensor
                     next = in == t0 ? t1 : t0;
                 }
-                p = layer(conv_in, L.conv_w[i][j][m][v], L.conv_b[i][j][m][v], last ? sum : next, mul, Cn, Cn, k, conv_dil, 1, 1);
+                if ((rc = layer({HG_CONV, i, j, nv * m + v}, conv_in, L.conv_w[i][j][m][v], L.conv_b[i][j][m][v], last ? sum : next, mul, Cn, Cn, k, conv_dil,
+                                1)) != GVX_OK) return rc;
                 p.res = in;
                 if (last) {   // y_j goes into the stage's sum: written by the first block, added by the later ones, the last divides
                     p.accumulate = j > 0;
@@ -328,12 +180,90 @@ int gvx_hifigan_forward(gvx_hifigan* h, const float* mel, const int32_t* frame_l
         }
         cur = sum;
         C = Cn;
-        if ((rc = stamp()) != GVX_OK) return rc;
+        if ((rc = gen_mark(h, ev++, s)) != GVX_OK) return rc;
     }
-    p = layer(cur, L.post_w, L.post_b, wav_out, mul, C, 1, 7, 1, 1, 1);
-    p.slope = d.post_slope; p.tanh_out = 1; p.zero_tail = 1;
-    if ((rc = hg_launch(p, B, s)) != GVX_OK) return rc;
-    return stamp();
+    if ((rc = layer({HG_POST, 0, 0, 0}, cur, L.post_w, L.post_b, wav_out, mul, C, 1, 7, 1, 1)) != GVX_OK) return rc;
+    p.zero_tail = 1;
+    return hg_launch(p, B, s);
+}
+
+extern "C" {
+
+size_t gvx_hifigan_blob_floats(const gvx_hifigan_dims* dims) {
+    if (hg_dims_problem(dims)) return 0;
+    return hg_blob_layout(*dims).total;
+}
+
+size_t gvx_hifigan_workspace_bytes(const gvx_hifigan_dims* dims, int B, int T) {
+    if (hg_dims_problem(dims) || B < 1 || T < 1 || T > GVX_HIFIGAN_MAX_FRAMES) return 0;
+    return hg_ws_plan(*dims, B, T, 4).total;
+}
+
+int gvx_hifigan_pack_weights_device(const gvx_hifigan_dims* dims, const gvx_weight_desc* table, int n, float* device_blob, void* stream) {
+    if (const char* why = hg_dims_problem(dims)) return fail(GVX_ERR_INVALID_ARG, "%s", why);
+    if (!table || n < 1 || !device_blob) return fail(GVX_ERR_INVALID_ARG, "null argument");
+    const gvx_hifigan_dims& d = *dims;
+    const HgBlob L = hg_blob_layout(d);
+    GenConvPacker P{{table, n}};
+    auto conv = [&](const std::string& name, size_t dst_w, size_t dst_b, int Cout, int Cin, int Cp, int k) {
+        P.conv(name + ".weight", dst_w, Cout, Cin, Cp, k, k * Cp, 0);
+        P.bias(name + ".bias", dst_b, Cout);
+    };
+    int C = d.upsample_initial_channel;
+    conv("conv_pre", L.pre_w, L.pre_b, C, d.n_mels, hg_cpad(d), 7);
+    for (int i = 0; i < d.n_stages; ++i) {
+        const int Cn = C / 2;
+        const std::string up = "ups." + std::to_string(i);
+        P.tconv(up + ".weight", L.up_w[i], C, Cn, d.upsample_rates[i]);
+        P.bias(up + ".bias", L.up_b[i], Cn);
+        for (int j = 0; j < d.n_resblocks; ++j)
+            for (int m = 0; m < d.n_dilations; ++m)
+                for (int v = 0; v < hg_convs_per_dilation(d); ++v)
+                    conv(hg_conv_name(d, i * d.n_resblocks + j, m, v), L.conv_w[i][j][m][v], L.conv_b[i][j][m][v], Cn, Cn, Cn, d.resblock_kernel_sizes[j]);
+        C = Cn;
+    }
+    conv("conv_post", L.post_w, L.post_b, 1, C, C, 7);
+    return P.run(device_blob, L.total, (hipStream_t)stream);
+}
+
+int gvx_hifigan_create(const gvx_hifigan_dims* dims, gvx_hifigan** out) {
+    if (!out) return fail(GVX_ERR_INVALID_ARG, "null argument");
+    if (const char* why = hg_dims_problem(dims)) return fail(GVX_ERR_INVALID_ARG, "%s", why);
+    gvx_hifigan* h = new gvx_hifigan();
+    h->d = *dims;
+    *out = h;
+    return GVX_OK;
+}
+
+void gvx_hifigan_destroy(gvx_hifigan* h) { delete h; }
+
+int gvx_hifigan_bind(gvx_hifigan* h, const float* device_blob) { return gen_bind(h, device_blob); }
+
+int gvx_hifigan_timing_enable(gvx_hifigan* h, int enable) {
+    if (!h) return fail(GVX_ERR_INVALID_ARG, "null argument");
+    const int need = h->d.n_stages + 3;
+    if (enable)
+        if (const int rc = gen_make_marks(h->bwd_marks, need + 1)) return rc;
+    return gen_timing_enable(h, enable, need);
+}
+
+int gvx_hifigan_stage_times_ms(gvx_hifigan* h, float* ms_out, int* n_out) { return gen_stage_times_ms(h, h ? h->d.n_stages + 2 : 0, ms_out, n_out); }
+
+int gvx_hifigan_forward(gvx_hifigan* h, const float* mel, const int32_t* frame_lengths, int B, int T, float* wav_out, float* const* stage_out,
+                        void* workspace, size_t workspace_bytes, void* stream) {
+    if (!h) return fail(GVX_ERR_INVALID_ARG, "null argument");
+    const gvx_hifigan_dims& d = h->d;
+    hipStream_t s = (hipStream_t)stream;
+    // LeakyReLU on every operand but conv_pre's, in the kernel; conv_post has a slope of its own and tanh behind it
+    const HgFront front = [&d](const HgAt& at, HgLayer& p) {
+        p.slope = at.site == HG_POST ? d.post_slope : d.slope;
+        p.act = at.site != HG_PRE;
+        p.tanh_out = at.site == HG_POST;
+        return (int)GVX_OK;
+    };
+    if (const int rc = hg_forward(h, &h->lds_ready, d, hg_ws_plan(d, B, T, 4), front, mel, frame_lengths, B, T, wav_out, stage_out, workspace, workspace_bytes, s))
+        return rc;
+    return gen_mark(h, d.n_stages + 2, s);
 }
 
 }  // C ABI

@@ -1,20 +1,19 @@
 // The HiFi-GAN generator's host-side description (csrc/hifigan.hip): the handle, the layer description of the windowed implicit GEMM
 // with its row arithmetic, the dims check and the blob layout.  The model is defined in include/genvox_amd.h, "HiFi-GAN generator".
 #pragma once
-#include "gvx_internal.h"
+#include "gen_host.h"
 
-struct gvx_hifigan {
+#include <functional>
+
+struct gvx_hifigan : gvx_gen::GenHandle {
     gvx_hifigan_dims d;
-    const float* blob = nullptr;
-    bool timing = false;
-    bool lds_ready = false;
-    hipEvent_t ev[GVX_HIFIGAN_MAX_STAGES + 3] = {};
-    int n_ev = 0;
-    hipEvent_t ev_bwd[GVX_HIFIGAN_MAX_STAGES + 4] = {};   // gvx_hifigan_backward's parts (hifigan_train.hip)
-    int n_ev_bwd = 0;
+    bool lds_ready = false;        // hg_prepare
+    gvx_gen::GenMarks bwd_marks;   // gvx_hifigan_backward's parts (hifigan_train.hip)
 };
 
 namespace gvx_hg {
+
+using namespace gvx_gen;
 
 // One layer:  out[b][phases * q + phase][n] = epilogue( bias[n] + sum over taps tau, channels c of
 //                                                       act(src[b][q - left + off0 + tau * step][c]) * W[phase][n][tau * Cin + c] )
@@ -47,16 +46,8 @@ __host__ __device__ __forceinline__ HgTaps hg_taps(int taps, int dil, int phases
     return 2 * phase < phases ? HgTaps{1, 1, 1, -1} : HgTaps{1, 0, 0, 1};
 }
 
-__device__ __forceinline__ int hg_frames(const int32_t* lens, int b, int T) {
-    int v = lens ? lens[b] : T;
-    v = v > T ? T : v;
-    return v < 1 ? 0 : v;   // rows the host should have refused produce silence, never a bad address
-}
-
 __device__ __forceinline__ float hg_lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
 
-inline size_t hg_round64(size_t floats) { return (floats + 63) & ~(size_t)63; }
-inline size_t hg_round256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 inline int hg_cpad(const gvx_hifigan_dims& d) { return (d.n_mels + 3) & ~3; }
 inline int hg_convs_per_dilation(const gvx_hifigan_dims& d) { return d.resblock == 1 ? 2 : 1; }
 
@@ -102,7 +93,7 @@ struct HgBlob {   // offsets in floats; conv_w[i][j][m][0 / 1]: convs1 / convs2 
 inline HgBlob hg_blob_layout(const gvx_hifigan_dims& d) {
     HgBlob L{};
     size_t at = 0;
-    auto take = [&](size_t floats) { const size_t o = at; at += hg_round64(floats); return o; };
+    auto take = [&](size_t floats) { const size_t o = at; at += gen_round64(floats); return o; };
     size_t C = d.upsample_initial_channel;
     L.pre_w = take(C * 7 * hg_cpad(d));
     L.pre_b = take(C);
@@ -131,9 +122,29 @@ inline std::string hg_conv_name(const gvx_hifigan_dims& d, int block, int m, int
     return base + (v == 0 ? ".convs1." : ".convs2.") + std::to_string(m);
 }
 
-// hifigan.hip, for the training path: one layer's launch, the handle's dynamic-LDS sizes, the mel transpose
+// hifigan.hip, for the training path and the generators built on these layers: one layer's launch, the dynamic-LDS sizes of its
+// kernels (once per handle: *ready is the handle's flag), the mel transpose
 int hg_launch(const HgLayer& p, int B, hipStream_t s);
-int hg_prepare(gvx_hifigan* h);
+int hg_prepare(bool* ready);
 int hg_mel_transpose(const float* mel, const int32_t* lens, int B, int M, int T, int Cp, float* out, hipStream_t s);
+
+// ---- the forward that HiFi-GAN and BigVGAN share (hifigan.hip)
+constexpr int HG_MAX_BUFS = 5;
+struct HgWs {   // byte offsets; n_bufs tensors of the widest activation's size behind the transposed mel
+    size_t mel_t, buf[HG_MAX_BUFS], total;
+};
+HgWs hg_ws_plan(const gvx_hifigan_dims& d, int B, int T, int n_bufs);
+
+// Where a layer of the forward stands.  A model's HgFront is called with every layer just before its launch, the layer's src being the
+// tensor the network's activation applies to, and makes the operand: HiFi-GAN sets the kernel's LeakyReLU and its slope, BigVGAN
+// launches its activation into a tensor of its own and points src there.  At HG_POST it also says what the output goes through.
+enum HgSite { HG_PRE, HG_UPS, HG_CONV, HG_POST };
+struct HgAt { HgSite site; int stage, block, act; };   // HG_UPS: stage; HG_CONV: the block's act-th activation
+using HgFront = std::function<int(const HgAt& at, HgLayer& p)>;
+
+// Everything of gvx_hifigan_forward but the last mark (n_stages + 2), which the caller records behind what it adds: the argument
+// checks, hg_prepare, marks 0 .. n_stages + 1, the launches.  The stage walk uses buf[0 .. 3] of wp.
+int hg_forward(const GenHandle* h, bool* lds_ready, const gvx_hifigan_dims& d, const HgWs& wp, const HgFront& front, const float* mel,
+               const int32_t* frame_lengths, int B, int T, float* wav_out, float* const* stage_out, void* workspace, size_t workspace_bytes, hipStream_t s);
 
 }  // namespace gvx_hg

@@ -42,7 +42,7 @@ __global__ void __launch_bounds__(256) hg_mfma_kernel(const HgLayer p) {
     const int nt = (int)blockIdx.y % n_tiles, phase = (int)blockIdx.y / n_tiles;
     const int q0 = (int)blockIdx.x * BM, n0 = nt * BN;
     const int Lmax = p.T * p.in_mul;
-    const int len = hg_frames(p.lens, b, p.T) * p.in_mul;
+    const int len = gen_frames(p.lens, b, p.T) * p.in_mul;
     float* out_b = p.out + (size_t)b * Lmax * p.phases * p.Cout;
     if (q0 >= len) {   // nothing of this row here
         if (p.zero_tail) {
@@ -196,7 +196,7 @@ template <int G, bool BWD = false>
 __global__ void __launch_bounds__(256) hg_valu_kernel(const HgLayer p) {
     const int b = blockIdx.z, phase = blockIdx.y;
     const int Lmax = p.T * p.in_mul;
-    const int len = hg_frames(p.lens, b, p.T) * p.in_mul;
+    const int len = gen_frames(p.lens, b, p.T) * p.in_mul;
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     const int g = (int)(idx % G);
     const long e = idx / G;

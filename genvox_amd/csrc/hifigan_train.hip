@@ -59,7 +59,7 @@ __global__ void __launch_bounds__(256, 2) hgb_wgrad_mfma_kernel(const HgbW p) {
     const int piece = blockIdx.x, n0 = (int)blockIdx.y * BMN, c0 = (int)blockIdx.z * 32;
     const int b = piece / p.ppr, q_base = (piece - b * p.ppr) * HGB_PIECE;
     const int Lmax = p.T * p.mul;
-    const int len = hg_frames(p.lens, b, p.T) * p.mul;
+    const int len = gen_frames(p.lens, b, p.T) * p.mul;
     const int K = p.taps * p.Cin;
     const int win = HGB_TP + (p.taps - 1) * p.dil;
     const float* src_b = p.src + (size_t)b * Lmax * p.Cin;
@@ -179,7 +179,7 @@ __global__ void __launch_bounds__(256) hgb_wgrad_valu_kernel(const HgbW p) {
     const int tau = k / p.Cin, c = k - tau * p.Cin;
     const int b = piece / p.ppr, q_base = (piece - b * p.ppr) * HGB_PIECE;
     const int Lmax = p.T * p.mul;
-    const int len = hg_frames(p.lens, b, p.T) * p.mul;
+    const int len = gen_frames(p.lens, b, p.T) * p.mul;
     const int q_end = min(q_base + HGB_PIECE, len);
     const float* src_b = p.src + (size_t)b * Lmax * p.Cin + c;
     const float* dy_b = p.dy + (size_t)b * Lmax * p.ldy + n;
@@ -201,7 +201,7 @@ __global__ void __launch_bounds__(256) hgb_colsum_kernel(const float* dy, int N,
     const int piece = blockIdx.x, tid = threadIdx.x;
     const int b = piece / ppr, q_base = (piece - b * ppr) * HGB_PIECE;
     const int Lmax = T * mul;
-    const int len = hg_frames(lens, b, T) * mul;
+    const int len = gen_frames(lens, b, T) * mul;
     const int count = min(HGB_PIECE, len - q_base);   // <= 0: the piece lies behind the row
     const float* dy_p = dy + ((size_t)b * Lmax + q_base) * N;
     float* out = part + (size_t)piece * N;
@@ -294,7 +294,7 @@ __global__ void __launch_bounds__(256) hgb_tanh_bwd_kernel(const float* d_wav, c
     if (idx >= (long)T * hop) return;
     const size_t at = (size_t)b * T * hop + idx;
     float v = 0.f;
-    if (idx < (long)hg_frames(lens, b, T) * hop) {
+    if (idx < (long)gen_frames(lens, b, T) * hop) {
         const float w = wav[at];
         v = d_wav[at] * (1.f - w * w);
     }
@@ -307,7 +307,7 @@ __global__ void __launch_bounds__(256) hgb_dmel_kernel(const float* dmel_t, cons
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (long)M * T) return;
     const int t = (int)(idx % T), c = (int)(idx / T);
-    d_mel[(size_t)b * M * T + idx] = t < hg_frames(lens, b, T) ? dmel_t[((size_t)b * T + t) * Cp + c] : 0.f;
+    d_mel[(size_t)b * M * T + idx] = t < gen_frames(lens, b, T) ? dmel_t[((size_t)b * T + t) * Cp + c] : 0.f;
 }
 
 // ---- plans
@@ -359,7 +359,7 @@ inline int hgb_ppr(int T, int mul) { return (int)(((long)T * mul + HGB_PIECE - 1
 HgBlob hgb_wt_layout(const gvx_hifigan_dims& d) {
     HgBlob L{};
     size_t at = 0;
-    auto take = [&](size_t floats) { const size_t o = at; at += hg_round64(floats); return o; };
+    auto take = [&](size_t floats) { const size_t o = at; at += gen_round64(floats); return o; };
     size_t C = d.upsample_initial_channel;
     L.pre_w = take(C * 7 * hg_cpad(d));
     for (int i = 0; i < d.n_stages; ++i) {
@@ -402,7 +402,7 @@ HgbWs hgb_ws_plan(const gvx_hifigan_dims& d, int B, int T) {
     }
     need(mul, 1, 7 * C);
     size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += hg_round256(bytes); return o; };
+    auto take = [&](size_t bytes) { const size_t o = at; at += gen_round256(bytes); return o; };
     w.wt = take(w.wt_at.total * sizeof(float));
     w.wav = take((size_t)B * T * mul * sizeof(float));
     w.dz = take((size_t)B * T * mul * sizeof(float));
@@ -554,7 +554,7 @@ int gvx_hifigan_forward_train(gvx_hifigan* h, const float* mel, const int32_t* f
     if ((rc = hgb_check_call(h, B, T, tape, tape_bytes)) != GVX_OK) return rc;
     const gvx_hifigan_dims& d = h->d;
     hipStream_t s = (hipStream_t)stream;
-    if ((rc = hg_prepare(h)) != GVX_OK) return rc;
+    if ((rc = hg_prepare(&h->lds_ready)) != GVX_OK) return rc;
     const HgTape tp = hgb_tape_plan(d, B, T);
     const HgBlob L = hg_blob_layout(d);
     const float* blob = h->blob;
@@ -645,7 +645,7 @@ int gvx_hifigan_backward(gvx_hifigan* h, const float* d_wav, const int32_t* fram
         if (rc != GVX_OK) return rc;   // nothing was launched
     }
     hipStream_t s = (hipStream_t)stream;
-    if ((rc = hg_prepare(h)) != GVX_OK) return rc;
+    if ((rc = hg_prepare(&h->lds_ready)) != GVX_OK) return rc;
     const HgTape tp = hgb_tape_plan(d, B, T);
     const HgBlob L = hg_blob_layout(d);
     const HgBlob& WL = wp.wt_at;
@@ -664,10 +664,8 @@ int gvx_hifigan_backward(gvx_hifigan* h, const float* d_wav, const int32_t* fram
     float* part_b = gvx::ws_ptr<float>(workspace, wp.part_b);   // bias pieces that a weight-gradient launch makes on its way
 
     int ev = 0;
-    auto stamp = [&]() -> int {   // with gvx_hifigan_timing_enable: the transposes, conv_post, every stage from the last, conv_pre
-        if (h->timing) HIP_TRY(hipEventRecord(h->ev_bwd[ev++], s));
-        return GVX_OK;
-    };
+    // with gvx_hifigan_timing_enable: the transposes, conv_post, every stage from the last, conv_pre
+    auto stamp = [&] { return gen_mark(h, ev++, s, &h->bwd_marks); };
     if ((rc = stamp()) != GVX_OK) return rc;
 
     // the transposed weights, from the blob the forward read
@@ -774,13 +772,8 @@ int gvx_hifigan_backward(gvx_hifigan* h, const float* d_wav, const int32_t* fram
 }
 
 int gvx_hifigan_backward_stage_times_ms(gvx_hifigan* h, float* ms_out, int* n_out) {
-    if (!h || !ms_out || !n_out) return fail(GVX_ERR_INVALID_ARG, "null argument");
-    if (!h->timing) return fail(GVX_ERR_STATE, "timing is not enabled");
-    const int n = h->d.n_stages + 3;
-    HIP_TRY(hipEventSynchronize(h->ev_bwd[n]));
-    for (int i = 0; i < n; ++i) HIP_TRY(hipEventElapsedTime(&ms_out[i], h->ev_bwd[i], h->ev_bwd[i + 1]));
-    *n_out = n;
-    return GVX_OK;
+    if (!h) return fail(GVX_ERR_INVALID_ARG, "null argument");
+    return gen_stage_times_ms(h, h->d.n_stages + 3, ms_out, n_out, &h->bwd_marks);
 }
 
 }  // C ABI

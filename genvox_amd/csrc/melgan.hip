@@ -245,14 +245,10 @@ MgWs mg_ws_plan(const gvx_melgan_dims& d, int B, int T) {
         widest = std::max(widest, mul * C);
     }
     MgWs w{};
-    size_t at = 0;
-    w.mel_t = at;
-    at += (size_t)B * mg_round256((size_t)T * mg_cpad(d) * sizeof(float));
-    for (int i = 0; i < 3; ++i) {
-        w.buf[i] = at;
-        at += (size_t)B * mg_round256((size_t)T * widest * sizeof(float));
-    }
-    w.total = at;
+    GenRows ws{B};
+    w.mel_t = ws.rows((size_t)T * mg_cpad(d));
+    for (size_t& buf : w.buf) buf = ws.rows((size_t)T * widest);
+    w.total = ws.total;
     return w;
 }
 
@@ -284,19 +280,6 @@ int mg_launch(const MgLayer& p, int B, hipStream_t s) {
     return GVX_OK;
 }
 
-const gvx_weight_desc* mg_find(const gvx_weight_desc* table, int n, const std::string& name, size_t numel, int& rc) {
-    for (int i = 0; i < n; ++i)
-        if (table[i].name && name == table[i].name) {
-            if (!table[i].data || table[i].numel != (int64_t)numel) {
-                rc = fail(GVX_ERR_SHAPE, "%s has %lld elements, the dims ask for %zu", name.c_str(), (long long)table[i].numel, numel);
-                return nullptr;
-            }
-            return &table[i];
-        }
-    rc = fail(GVX_ERR_MISSING_WEIGHT, "%s is missing", name.c_str());
-    return nullptr;
-}
-
 int mg_mel_transpose(const float* mel, const int32_t* lens, int B, int M, int T, int Cp, float* out, hipStream_t s) {
     const dim3 grid((unsigned)(((long)T * Cp + 255) / 256), (unsigned)B);
     mg_mel_transpose_kernel<<<grid, 256, 0, s>>>(mel, lens, M, T, Cp, out);
@@ -315,6 +298,23 @@ int mg_prepare(gvx_melgan* h) {
 
 }  // namespace gvx_mg
 
+// the relayouts of MelGAN's and HiFi-GAN's packers
+int gvx_gen::GenConvPacker::run(float* device_blob, size_t total, hipStream_t s) const {
+    if (rc != GVX_OK) return rc;   // nothing was launched
+    HIP_TRY(hipMemsetAsync(device_blob, 0, total * sizeof(float), s));   // the padding between the tensors
+    for (const Job& j : jobs) {
+        if (!j.tconv) {
+            const long count = (long)j.a * j.k * j.c;
+            mg_pack_conv_kernel<<<(unsigned)((count + 255) / 256), 256, 0, s>>>(device_blob + j.dst, j.src, j.a, j.b, j.c, j.k, j.ld, j.off);
+        } else {
+            const long count = (long)j.c * j.b * 2 * j.a;
+            mg_pack_tconv_kernel<<<(unsigned)((count + 255) / 256), 256, 0, s>>>(device_blob + j.dst, j.src, j.a, j.b, j.c);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    return GVX_OK;
+}
+
 extern "C" {
 
 size_t gvx_melgan_blob_floats(const gvx_melgan_dims* dims) {
@@ -332,49 +332,29 @@ int gvx_melgan_pack_weights_device(const gvx_melgan_dims* dims, const gvx_weight
     if (!table || n < 1 || !device_blob) return fail(GVX_ERR_INVALID_ARG, "null argument");
     const gvx_melgan_dims& d = *dims;
     const MgBlob L = mg_blob_layout(d);
-    hipStream_t s = (hipStream_t)stream;
-    struct Job { int kind; size_t dst; const float* src; int a, b, c, k, ld, off; };   // kind 0: conv (Cout a, Cin b, Cp c), 1: tconv (Cin a, Cout b, r c)
-    std::vector<Job> jobs;
-    int rc = GVX_OK;
-    auto conv = [&](const std::string& name, size_t dst, int Cout, int Cin, int Cp, int k, int ld, int off) {
-        if (rc != GVX_OK) return;
-        if (const gvx_weight_desc* w = mg_find(table, n, name, (size_t)Cout * Cin * k, rc)) jobs.push_back({0, dst, w->data, Cout, Cin, Cp, k, ld, off});
-    };
+    GenConvPacker P{{table, n}};
     int C = d.base_channels;
-    conv("pre.weight", L.pre_w, C, d.n_mels, mg_cpad(d), 7, 7 * mg_cpad(d), 0);
-    conv("pre.bias", L.pre_b, C, 1, 1, 1, 1, 0);
-    for (int i = 0; i < d.n_stages && rc == GVX_OK; ++i) {
+    P.conv("pre.weight", L.pre_w, C, d.n_mels, mg_cpad(d), 7, 7 * mg_cpad(d), 0);
+    P.bias("pre.bias", L.pre_b, C);
+    for (int i = 0; i < d.n_stages; ++i) {
         const int Cn = C / 2;
         const std::string up = "ups." + std::to_string(i);
-        if (const gvx_weight_desc* w = mg_find(table, n, up + ".weight", (size_t)C * Cn * 2 * d.ratios[i], rc))
-            jobs.push_back({1, L.up_w[i], w->data, C, Cn, d.ratios[i], 0, 0, 0});
-        conv(up + ".bias", L.up_b[i], Cn, 1, 1, 1, 1, 0);
+        P.tconv(up + ".weight", L.up_w[i], C, Cn, d.ratios[i]);
+        P.bias(up + ".bias", L.up_b[i], Cn);
         for (int j = 0; j < d.n_residual_layers; ++j) {
             const std::string res = "res." + std::to_string(i) + "." + std::to_string(j);
-            conv(res + ".conv.weight", L.conv_w[i][j], Cn, Cn, Cn, 3, 3 * Cn, 0);
-            conv(res + ".conv.bias", L.conv_b[i][j], Cn, 1, 1, 1, 1, 0);
-            conv(res + ".shortcut.weight", L.tail_w[i][j], Cn, Cn, Cn, 1, 2 * Cn, 0);
-            conv(res + ".mix.weight", L.tail_w[i][j], Cn, Cn, Cn, 1, 2 * Cn, Cn);
-            conv(res + ".shortcut.bias", L.sc_b[i][j], Cn, 1, 1, 1, 1, 0);
-            conv(res + ".mix.bias", L.mix_b[i][j], Cn, 1, 1, 1, 1, 0);
+            P.conv(res + ".conv.weight", L.conv_w[i][j], Cn, Cn, Cn, 3, 3 * Cn, 0);
+            P.bias(res + ".conv.bias", L.conv_b[i][j], Cn);
+            P.conv(res + ".shortcut.weight", L.tail_w[i][j], Cn, Cn, Cn, 1, 2 * Cn, 0);
+            P.conv(res + ".mix.weight", L.tail_w[i][j], Cn, Cn, Cn, 1, 2 * Cn, Cn);
+            P.bias(res + ".shortcut.bias", L.sc_b[i][j], Cn);
+            P.bias(res + ".mix.bias", L.mix_b[i][j], Cn);
         }
         C = Cn;
     }
-    conv("post.weight", L.post_w, 1, C, C, 7, 7 * C, 0);
-    conv("post.bias", L.post_b, 1, 1, 1, 1, 1, 0);
-    if (rc != GVX_OK) return rc;   // nothing was launched
-    HIP_TRY(hipMemsetAsync(device_blob, 0, L.total * sizeof(float), s));   // the padding between the tensors
-    for (const Job& j : jobs) {
-        if (j.kind == 0) {
-            const long count = (long)j.a * j.k * j.c;
-            mg_pack_conv_kernel<<<(unsigned)((count + 255) / 256), 256, 0, s>>>(device_blob + j.dst, j.src, j.a, j.b, j.c, j.k, j.ld, j.off);
-        } else {
-            const long count = (long)j.c * j.b * 2 * j.a;
-            mg_pack_tconv_kernel<<<(unsigned)((count + 255) / 256), 256, 0, s>>>(device_blob + j.dst, j.src, j.a, j.b, j.c);
-        }
-        HIP_TRY(hipGetLastError());
-    }
-    return GVX_OK;
+    P.conv("post.weight", L.post_w, 1, C, C, 7, 7 * C, 0);
+    P.bias("post.bias", L.post_b, 1);
+    return P.run(device_blob, L.total, (hipStream_t)stream);
 }
 
 int gvx_melgan_create(const gvx_melgan_dims* dims, gvx_melgan** out) {
@@ -386,36 +366,13 @@ int gvx_melgan_create(const gvx_melgan_dims* dims, gvx_melgan** out) {
     return GVX_OK;
 }
 
-void gvx_melgan_destroy(gvx_melgan* h) {
-    if (!h) return;
-    for (int i = 0; i < h->n_ev; ++i) (void)hipEventDestroy(h->ev[i]);
-    delete h;
-}
+void gvx_melgan_destroy(gvx_melgan* h) { delete h; }
 
-int gvx_melgan_bind(gvx_melgan* h, const float* device_blob) {
-    if (!h || !device_blob) return fail(GVX_ERR_INVALID_ARG, "null argument");
-    if ((uintptr_t)device_blob % 256) return fail(GVX_ERR_INVALID_ARG, "the blob must be 256-byte aligned");
-    h->blob = device_blob;
-    return GVX_OK;
-}
+int gvx_melgan_bind(gvx_melgan* h, const float* device_blob) { return gen_bind(h, device_blob); }
 
-int gvx_melgan_timing_enable(gvx_melgan* h, int enable) {
-    if (!h) return fail(GVX_ERR_INVALID_ARG, "null argument");
-    const int need = h->d.n_stages + 3;
-    while (enable && h->n_ev < need) HIP_TRY(hipEventCreate(&h->ev[h->n_ev++]));
-    h->timing = enable != 0;
-    return GVX_OK;
-}
+int gvx_melgan_timing_enable(gvx_melgan* h, int enable) { return gen_timing_enable(h, enable, h ? h->d.n_stages + 3 : 0); }
 
-int gvx_melgan_stage_times_ms(gvx_melgan* h, float* ms_out, int* n_out) {
-    if (!h || !ms_out || !n_out) return fail(GVX_ERR_INVALID_ARG, "null argument");
-    if (!h->timing) return fail(GVX_ERR_STATE, "timing is not enabled");
-    const int n = h->d.n_stages + 2;
-    HIP_TRY(hipEventSynchronize(h->ev[n]));
-    for (int i = 0; i < n; ++i) HIP_TRY(hipEventElapsedTime(&ms_out[i], h->ev[i], h->ev[i + 1]));
-    *n_out = n;
-    return GVX_OK;
-}
+int gvx_melgan_stage_times_ms(gvx_melgan* h, float* ms_out, int* n_out) { return gen_stage_times_ms(h, h ? h->d.n_stages + 2 : 0, ms_out, n_out); }
 
 int gvx_melgan_forward(gvx_melgan* h, const float* mel, const int32_t* frame_lengths, int B, int T, float* wav_out, float* const* stage_out,
                        void* workspace, size_t workspace_bytes, void* stream) {
@@ -426,13 +383,10 @@ int gvx_melgan_forward(gvx_melgan* h, const float* mel, const int32_t* frame_len
     if (T < GVX_MELGAN_MIN_FRAMES) return fail(GVX_ERR_INVALID_ARG, "T = %d: the first convolution's reflection needs at least %d frames", T, GVX_MELGAN_MIN_FRAMES);
     if (T > GVX_MELGAN_MAX_FRAMES) return fail(GVX_ERR_UNSUPPORTED, "T = %d is beyond the limit of %d frames", T, GVX_MELGAN_MAX_FRAMES);
     const MgWs wp = mg_ws_plan(d, B, T);
-    if (!workspace || (uintptr_t)workspace % 256 || workspace_bytes < wp.total)
-        return fail(GVX_ERR_WORKSPACE, "the workspace is missing, misaligned or smaller than %zu bytes", wp.total);
-    if (stage_out)
-        for (int i = 0; i < d.n_stages; ++i)
-            if (!stage_out[i] || (uintptr_t)stage_out[i] % 16) return fail(GVX_ERR_INVALID_ARG, "stage_out[%d] is null or not 16-byte aligned", i);
-    hipStream_t s = (hipStream_t)stream;
     int rc;
+    if ((rc = gen_check_workspace(workspace, workspace_bytes, wp.total)) != GVX_OK) return rc;
+    if ((rc = gen_check_stage_out(stage_out, d.n_stages)) != GVX_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
     if ((rc = mg_prepare(h)) != GVX_OK) return rc;
     const MgBlob L = mg_blob_layout(d);
     const float* blob = h->blob;
@@ -443,10 +397,7 @@ int gvx_melgan_forward(gvx_melgan* h, const float* mel, const int32_t* frame_len
         return pool[0];
     };
     int ev = 0;
-    auto stamp = [&]() -> int {
-        if (h->timing) HIP_TRY(hipEventRecord(h->ev[ev++], s));
-        return GVX_OK;
-    };
+    auto stamp = [&] { return gen_mark(h, ev++, s); };
     if ((rc = stamp()) != GVX_OK) return rc;
 
     const int Cp = mg_cpad(d);

@@ -334,11 +334,6 @@ __global__ void __launch_bounds__(256) md_db_kernel(const MdConv p, float* out, 
     if (threadIdx.x == 0) out[co] = (float)red[0];
 }
 
-__global__ void __launch_bounds__(256) md_copy_kernel(float* dst, const float* src, size_t n) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) dst[i] = src[i];
-}
-
 MdConv md_conv(const gvx_melgan_disc_dims& d, const MdLayer& l, const MdFeat& F, int k, int i, const int32_t* lens, int n_max) {
     MdConv p{};
     p.lens = lens; p.n_max = n_max; p.min_n = md_min_samples(d); p.shift = k; p.s = d.downsampling_factor;
@@ -437,26 +432,14 @@ int gvx_melgan_disc_pack_weights_device(const gvx_melgan_disc_dims* dims, const 
     MdLayer L[MD_MAX_LAYERS];
     size_t per_scale = 0;
     const int nl = md_layers(*dims, L, &per_scale);
-    struct Job { size_t dst; const float* src; size_t numel; };
-    std::vector<Job> jobs;
-    int rc = GVX_OK;
-    for (int k = 0; k < dims->n_scales && rc == GVX_OK; ++k)
-        for (int i = 0; i < nl && rc == GVX_OK; ++i) {
+    gvx_gen::GenPacker P{{table, n}};
+    for (int k = 0; k < dims->n_scales; ++k)
+        for (int i = 0; i < nl; ++i) {
             const std::string name = "scales." + std::to_string(k) + ".layers." + std::to_string(i);
-            const size_t wn = (size_t)L[i].cout * L[i].cig * L[i].k;
-            if (const gvx_weight_desc* w = gvx_mg::mg_find(table, n, name + ".weight", wn, rc)) jobs.push_back({k * per_scale + L[i].w_off, w->data, wn});
-            if (rc != GVX_OK) break;
-            if (const gvx_weight_desc* w = gvx_mg::mg_find(table, n, name + ".bias", (size_t)L[i].cout, rc))
-                jobs.push_back({k * per_scale + L[i].b_off, w->data, (size_t)L[i].cout});
+            P.take(name + ".weight", k * per_scale + L[i].w_off, (size_t)L[i].cout * L[i].cig * L[i].k);
+            P.take(name + ".bias", k * per_scale + L[i].b_off, (size_t)L[i].cout);
         }
-    if (rc != GVX_OK) return rc;   // nothing was launched
-    hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(hipMemsetAsync(device_blob, 0, per_scale * dims->n_scales * sizeof(float), s));   // the padding between the tensors
-    for (const Job& j : jobs) {
-        md_copy_kernel<<<(unsigned)((j.numel + 255) / 256), 256, 0, s>>>(device_blob + j.dst, j.src, j.numel);
-        HIP_TRY(hipGetLastError());
-    }
-    return GVX_OK;
+    return P.run(device_blob, 0, per_scale * dims->n_scales, (hipStream_t)stream);
 }
 
 int gvx_melgan_disc_create(const gvx_melgan_disc_dims* dims, gvx_melgan_disc** out) {
@@ -537,10 +520,10 @@ int gvx_melgan_disc_backward(gvx_melgan_disc* h, const float* wav, const int32_t
             for (int i = 0; i < nl; ++i) {
                 const std::string name = "scales." + std::to_string(k) + ".layers." + std::to_string(i);
                 rc = GVX_OK;
-                const gvx_weight_desc* w = gvx_mg::mg_find(table, n_grads, name + ".weight", (size_t)L[i].cout * L[i].cig * L[i].k, rc);
+                const gvx_weight_desc* w = gvx_gen::gen_find(table, n_grads, name + ".weight", (size_t)L[i].cout * L[i].cig * L[i].k, rc);
                 if (!w) return rc;
                 gw[k][i] = const_cast<float*>(w->data);
-                w = gvx_mg::mg_find(table, n_grads, name + ".bias", (size_t)L[i].cout, rc);
+                w = gvx_gen::gen_find(table, n_grads, name + ".bias", (size_t)L[i].cout, rc);
                 if (!w) return rc;
                 gb[k][i] = const_cast<float*>(w->data);
             }

@@ -2,18 +2,16 @@
 // implicit GEMM with its row arithmetic, the dims check and the blob layout.  The forward kernels live in melgan.hip and are reached
 // through mg_launch.
 #pragma once
-#include "gvx_internal.h"
+#include "gen_host.h"
 
-struct gvx_melgan {
+struct gvx_melgan : gvx_gen::GenHandle {
     gvx_melgan_dims d;
-    const float* blob = nullptr;
-    bool timing = false;
     bool lds_ready = false;
-    hipEvent_t ev[GVX_MELGAN_MAX_STAGES + 3] = {};
-    int n_ev = 0;
 };
 
 namespace gvx_mg {
+
+using namespace gvx_gen;
 
 struct MgLayer {
     const float* src0; const float* src1;   // tap sources (src1: tap 1 of the residual tail)
@@ -27,11 +25,7 @@ struct MgLayer {
     float slope;
 };
 
-__device__ __forceinline__ int mg_frames(const int32_t* lens, int b, int T) {
-    int v = lens ? lens[b] : T;
-    v = v > T ? T : v;
-    return v < GVX_MELGAN_MIN_FRAMES ? 0 : v;   // rows the host should have refused produce silence, never a bad address
-}
+__device__ __forceinline__ int mg_frames(const int32_t* lens, int b, int T) { return gen_frames(lens, b, T, GVX_MELGAN_MIN_FRAMES); }
 
 // source position of tap tau for output group q (q < len); zero: the tap lies outside the row and contributes nothing
 __device__ __forceinline__ int mg_src_row(const MgLayer& p, int q, int tau, int phase, int len, bool& zero) {
@@ -50,8 +44,6 @@ __device__ __forceinline__ int mg_src_row(const MgLayer& p, int q, int tau, int 
 
 __device__ __forceinline__ float mg_lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
 
-inline size_t mg_round64(size_t floats) { return (floats + 63) & ~(size_t)63; }
-inline size_t mg_round256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 inline int mg_cpad(const gvx_melgan_dims& d) { return (d.n_mels + 3) & ~3; }
 
 inline const char* mg_dims_problem(const gvx_melgan_dims* d) {
@@ -85,7 +77,7 @@ struct MgBlob {   // offsets in floats
 inline MgBlob mg_blob_layout(const gvx_melgan_dims& d) {
     MgBlob L{};
     size_t at = 0;
-    auto take = [&](size_t floats) { const size_t o = at; at += mg_round64(floats); return o; };
+    auto take = [&](size_t floats) { const size_t o = at; at += gen_round64(floats); return o; };
     size_t C = d.base_channels;
     L.pre_w = take(C * 7 * mg_cpad(d));
     L.pre_b = take(C);
@@ -111,6 +103,6 @@ inline MgBlob mg_blob_layout(const gvx_melgan_dims& d) {
 // defined in melgan.hip
 int mg_launch(const MgLayer& p, int B, hipStream_t s);   // one layer of the forward
 int mg_mel_transpose(const float* mel, const int32_t* lens, int B, int M, int T, int Cp, float* out, hipStream_t s);
-int mg_prepare(gvx_melgan* h);   // once per handle: the dynamic LDS size of the widest tile (mg_find: gvx_internal.h)
+int mg_prepare(gvx_melgan* h);   // once per handle: the dynamic LDS size of the widest tile 
 
 }  // namespace gvx_mg

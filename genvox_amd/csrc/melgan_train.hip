@@ -504,7 +504,7 @@ MgbWs mgb_ws_plan(const gvx_melgan_dims& d, int B, int T) {
     need(mul, 1, 1, 7 * C);
     widest = std::max(widest, (size_t)mg_cpad(d));
     size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += mg_round256(bytes); return o; };
+    auto take = [&](size_t bytes) { const size_t o = at; at += gen_round256(bytes); return o; };
     w.wt = take(w.wt_at.total * sizeof(float));
     w.wav = take((size_t)B * T * hop * sizeof(float));
     w.dz = take((size_t)B * T * hop * sizeof(float));

@@ -23,20 +23,16 @@
 
 #include <algorithm>
 
-using gvx::fail;
+using namespace gvx_gen;
 using gvx::GemmParams;
 using gvx::RowMap;
 using gvx_hg::HgLayer;
 
 namespace gvx { hipError_t gemm_init(); }
 
-struct gvx_univnet {
+struct gvx_univnet : GenHandle {
     gvx_univnet_dims d;
-    const float* blob = nullptr;
-    gvx_hifigan core;   // what hg_prepare keeps per handle: the dynamic-LDS flag
-    bool timing = false;
-    hipEvent_t ev[2 * GVX_UNIVNET_MAX_BLOCKS + 3] = {};
-    int n_ev = 0;
+    bool lds_ready = false;   // hg_prepare
 };
 
 namespace {
@@ -47,12 +43,7 @@ constexpr int UN_LDA = 36;    // floats per LDS row of the MFMA window: 32 chann
 constexpr int UN_LDW = 100;   // floats per LDS row of the MFMA weights: 96 k, the same residue modulo 32 banks as UN_LDA
 constexpr int UN_PW_MFMA = 128, UN_PW_VALU = 64;   // most positions per workgroup
 
-// `least`: GVX_UNIVNET_MIN_FRAMES where a reflection by 3 needs them, 1 for the LVC layer on its own
-__device__ __forceinline__ int un_frames(const int32_t* lens, int b, int T, int least) {
-    int v = lens ? lens[b] : T;
-    v = v > T ? T : v;
-    return v < least ? 0 : v;   // rows the host should have refused produce silence, never a bad address
-}
+// gen_frames' `least` is GVX_UNIVNET_MIN_FRAMES where a reflection by 3 needs them, 1 for the LVC layer on its own
 
 __device__ __forceinline__ float un_lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
 __device__ __forceinline__ float4 un_lrelu4(float4 v, float s) { return make_float4(un_lrelu(v.x, s), un_lrelu(v.y, s), un_lrelu(v.z, s), un_lrelu(v.w, s)); }
@@ -73,7 +64,7 @@ __global__ void __launch_bounds__(256) un_lvc_kernel(const UnLvc p) {
     extern __shared__ __attribute__((aligned(16))) float un_smem[];
     const int tid = threadIdx.x, nthr = blockDim.x;
     const int b = blockIdx.y, t = (int)blockIdx.x / p.tiles, st = (int)blockIdx.x - t * p.tiles;
-    const int len = un_frames(p.lens, b, p.T, 1);
+    const int len = gen_frames(p.lens, b, p.T, 1);
     if (t >= len) return;   // (uniform over the workgroup) nothing of this row here: x stays as the transposed convolution left it
     const int C = p.C, K = 3 * C;
     const int ldw = MFMA ? UN_LDW : K + 1, lda = MFMA ? UN_LDA : C + 1;
@@ -177,7 +168,7 @@ __global__ void __launch_bounds__(256) un_noise_reflect_kernel(const float* __re
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (long)(T + 6) * Np) return;
     const int r = (int)(idx % (T + 6)), c = (int)(idx / (T + 6));   // consecutive threads along t, as z lies
-    const int len = un_frames(lens, b, T, GVX_UNIVNET_MIN_FRAMES);
+    const int len = gen_frames(lens, b, T, GVX_UNIVNET_MIN_FRAMES);
     int t = r - 3;
     float v = 0.f;
     if (c < nd && t < len + 3 && len > 0) {
@@ -196,7 +187,7 @@ __global__ void __launch_bounds__(256) un_pair_kernel(const float* a, const floa
     const int rows = T + 2 * halo;
     if (idx >= (long)rows * H) return;
     const int r = (int)(idx / H), c = (int)(idx - (long)r * H), t = r - halo;
-    const int len = un_frames(lens, b, T, 1);
+    const int len = gen_frames(lens, b, T, 1);
     if (t >= 0 && t < len) {
         const size_t at = ((size_t)b * T + t) * H + c;
         const float av = a[at];
@@ -214,7 +205,7 @@ __global__ void __launch_bounds__(256) un_post_kernel(const float* __restrict__ 
     const int b = blockIdx.y;
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     const int g = (int)(idx & 7);
-    const long q = idx >> 3, Lmax = (long)T * hop, L = (long)un_frames(lens, b, T, GVX_UNIVNET_MIN_FRAMES) * hop;
+    const long q = idx >> 3, Lmax = (long)T * hop, L = (long)gen_frames(lens, b, T, GVX_UNIVNET_MIN_FRAMES) * hop;
     if (q >= Lmax) return;   // (the eight lanes of a sample leave together)
     float sum = 0.f;
     if (q < L) {
@@ -239,8 +230,6 @@ __global__ void __launch_bounds__(256) un_post_kernel(const float* __restrict__ 
 }
 
 // ---- dims, blob, workspace
-inline size_t un_round64(size_t floats) { return (floats + 63) & ~(size_t)63; }
-inline size_t un_round256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 inline int un_mp(const gvx_univnet_dims& d) { return (d.n_mels + 3) & ~3; }
 inline int un_np(const gvx_univnet_dims& d) { return (d.noise_dim + 3) & ~3; }
 inline size_t un_layer_floats(int C) { return (size_t)6 * C * C; }   // one layer's [2C][3C] weights
@@ -290,7 +279,7 @@ struct UnBlob {
 UnBlob un_blob_layout(const gvx_univnet_dims& d) {
     UnBlob L{};
     size_t at = 0;
-    auto take = [&](size_t floats) { const size_t o = at; at += un_round64(floats); return o; };
+    auto take = [&](size_t floats) { const size_t o = at; at += gen_round64(floats); return o; };
     const size_t C = d.channel_size, H = d.kpnet_hidden_channels, ld = un_ld(d.channel_size, d.n_dilations);
     L.pre_w = take(C * 7 * un_np(d)); L.pre_b = take(C);
     for (int i = 0; i < d.n_blocks; ++i) {
@@ -310,16 +299,15 @@ struct UnWs { size_t mel_t, noise_t, pc, pt, pu, hal, kern, xa, xb, y, total; };
 
 UnWs un_ws_plan(const gvx_univnet_dims& d, int B, int T) {
     UnWs w{};
-    size_t at = 0;
-    auto take = [&](size_t floats_per_row) { const size_t o = at; at += (size_t)B * un_round256(floats_per_row * sizeof(float)); return o; };
+    GenRows ws{B};
     const size_t H = d.kpnet_hidden_channels, wide = (size_t)T * un_hop(d) * d.channel_size;
-    w.mel_t = take((size_t)T * un_mp(d));
-    w.noise_t = take((size_t)(T + 6) * un_np(d));
-    w.pc = take(T * H); w.pt = take(T * H); w.pu = take(T * H);
-    w.hal = take((size_t)(T + 2) * H);
-    w.kern = take((size_t)T * un_ld(d.channel_size, d.n_dilations));
-    w.xa = take(wide); w.xb = take(wide); w.y = take(wide);
-    w.total = at;
+    w.mel_t = ws.rows((size_t)T * un_mp(d));
+    w.noise_t = ws.rows((size_t)(T + 6) * un_np(d));
+    w.pc = ws.rows(T * H); w.pt = ws.rows(T * H); w.pu = ws.rows(T * H);
+    w.hal = ws.rows((size_t)(T + 2) * H);
+    w.kern = ws.rows((size_t)T * un_ld(d.channel_size, d.n_dilations));
+    w.xa = ws.rows(wide); w.xb = ws.rows(wide); w.y = ws.rows(wide);
+    w.total = ws.total;
     return w;
 }
 
@@ -354,8 +342,8 @@ HgLayer un_layer(const float* src, const float* w, const float* bias, float* out
 
 // gvx_lvc_gated has no handle: the dynamic-LDS sizes of its hg_launch are set once per process (a static local: one thread runs it)
 int un_lone_prepare() {
-    static gvx_hifigan core;
-    static const int rc = gvx_hg::hg_prepare(&core);
+    static bool ready = false;
+    static const int rc = gvx_hg::hg_prepare(&ready);
     return rc;
 }
 
@@ -414,37 +402,24 @@ int gvx_univnet_pack_weights_device(const gvx_univnet_dims* dims, const gvx_weig
     if (!table || n < 1 || !device_blob) return fail(GVX_ERR_INVALID_ARG, "null argument");
     const gvx_univnet_dims& d = *dims;
     const UnBlob L = un_blob_layout(d);
-    hipStream_t s = (hipStream_t)stream;
-    struct Job { size_t dst; const float* src; size_t numel; };
-    std::vector<Job> jobs;
-    int rc = GVX_OK;
-    auto take = [&](const std::string& name, size_t dst, size_t numel) -> int {   // every name is looked up before anything is launched
-        const gvx_weight_desc* e = gvx_mg::mg_find(table, n, name, numel, rc);
-        if (!e) return rc;
-        jobs.push_back({dst, e->data, numel});
-        return GVX_OK;
-    };
-    auto pair = [&](const std::string& name, size_t dst_w, size_t numel_w, size_t dst_b, size_t numel_b) -> int {
-        if ((rc = take(name + ".weight", dst_w, numel_w)) != GVX_OK) return rc;
-        return take(name + ".bias", dst_b, numel_b);
+    GenPacker P{{table, n}};
+    auto pair = [&](const std::string& name, size_t dst_w, size_t numel_w, size_t dst_b, size_t numel_b) {
+        P.take(name + ".weight", dst_w, numel_w);
+        P.take(name + ".bias", dst_b, numel_b);
     };
     const size_t C = d.channel_size, H = d.kpnet_hidden_channels, ld = un_ld(d.channel_size, d.n_dilations);
-    if ((rc = pair("conv_pre", L.pre_w, C * 7 * un_np(d), L.pre_b, C)) != GVX_OK) return rc;
+    pair("conv_pre", L.pre_w, C * 7 * un_np(d), L.pre_b, C);
     for (int i = 0; i < d.n_blocks; ++i) {
         const std::string base = "res_stack." + std::to_string(i) + ".", kp = base + "kernel_predictor.";
         const UnBlock& k = L.block[i];
-        if ((rc = pair(base + "convt_pre", k.up_w, (size_t)d.strides[i] * C * 2 * C, k.up_b, C)) != GVX_OK) return rc;
-        if ((rc = pair(kp + "input_conv", k.in_w, H * 5 * un_mp(d), k.in_b, H)) != GVX_OK) return rc;
-        for (int j = 0; j < 6; ++j)
-            if ((rc = pair(kp + "residual_convs." + std::to_string(j / 2) + (j & 1 ? ".3" : ".1"), k.res_w[j], H * 3 * H, k.res_b[j], H)) != GVX_OK) return rc;
-        if ((rc = pair(kp + "kb", k.kb_w, ld * 3 * H, k.kb_b, ld)) != GVX_OK) return rc;
-        for (int m = 0; m < d.n_dilations; ++m)
-            if ((rc = pair(base + "conv_blocks." + std::to_string(m), k.conv_w[m], C * 3 * C, k.conv_b[m], C)) != GVX_OK) return rc;
+        pair(base + "convt_pre", k.up_w, (size_t)d.strides[i] * C * 2 * C, k.up_b, C);
+        pair(kp + "input_conv", k.in_w, H * 5 * un_mp(d), k.in_b, H);
+        for (int j = 0; j < 6; ++j) pair(kp + "residual_convs." + std::to_string(j / 2) + (j & 1 ? ".3" : ".1"), k.res_w[j], H * 3 * H, k.res_b[j], H);
+        pair(kp + "kb", k.kb_w, ld * 3 * H, k.kb_b, ld);
+        for (int m = 0; m < d.n_dilations; ++m) pair(base + "conv_blocks." + std::to_string(m), k.conv_w[m], C * 3 * C, k.conv_b[m], C);
     }
-    if ((rc = pair("conv_post", L.post_w, 7 * C, L.post_b, 1)) != GVX_OK) return rc;
-    HIP_TRY(hipMemsetAsync(device_blob, 0, L.total * sizeof(float), s));   // the padding between the tensors
-    for (const Job& j : jobs) HIP_TRY(hipMemcpyAsync(device_blob + j.dst, j.src, j.numel * sizeof(float), hipMemcpyDeviceToDevice, s));
-    return GVX_OK;
+    pair("conv_post", L.post_w, 7 * C, L.post_b, 1);
+    return P.run(device_blob, 0, L.total, (hipStream_t)stream);
 }
 
 int gvx_univnet_create(const gvx_univnet_dims* dims, gvx_univnet** out) {
@@ -456,37 +431,17 @@ int gvx_univnet_create(const gvx_univnet_dims* dims, gvx_univnet** out) {
     return GVX_OK;
 }
 
-void gvx_univnet_destroy(gvx_univnet* h) {
-    if (!h) return;
-    for (int i = 0; i < h->n_ev; ++i) (void)hipEventDestroy(h->ev[i]);
-    delete h;
-}
+void gvx_univnet_destroy(gvx_univnet* h) { delete h; }
 
 int gvx_univnet_bind(gvx_univnet* h, const float* device_blob) {
-    if (!h || !device_blob) return fail(GVX_ERR_INVALID_ARG, "null argument");
-    if ((uintptr_t)device_blob % 256) return fail(GVX_ERR_INVALID_ARG, "the blob must be 256-byte aligned");
-    h->blob = device_blob;
+    if (const int rc = gen_bind(h, device_blob)) return rc;
     HIP_TRY(gvx::gemm_init());   // the big tiles' dynamic LDS
-    return gvx_hg::hg_prepare(&h->core);
+    return gvx_hg::hg_prepare(&h->lds_ready);
 }
 
-int gvx_univnet_timing_enable(gvx_univnet* h, int enable) {
-    if (!h) return fail(GVX_ERR_INVALID_ARG, "null argument");
-    const int need = 2 * h->d.n_blocks + 3;
-    while (enable && h->n_ev < need) HIP_TRY(hipEventCreate(&h->ev[h->n_ev++]));
-    h->timing = enable != 0;
-    return GVX_OK;
-}
+int gvx_univnet_timing_enable(gvx_univnet* h, int enable) { return gen_timing_enable(h, enable, h ? 2 * h->d.n_blocks + 3 : 0); }
 
-int gvx_univnet_stage_times_ms(gvx_univnet* h, float* ms_out, int* n_out) {
-    if (!h || !ms_out || !n_out) return fail(GVX_ERR_INVALID_ARG, "null argument");
-    if (!h->timing) return fail(GVX_ERR_STATE, "timing is not enabled");
-    const int n = 2 * h->d.n_blocks + 2;
-    HIP_TRY(hipEventSynchronize(h->ev[n]));
-    for (int i = 0; i < n; ++i) HIP_TRY(hipEventElapsedTime(&ms_out[i], h->ev[i], h->ev[i + 1]));
-    *n_out = n;
-    return GVX_OK;
-}
+int gvx_univnet_stage_times_ms(gvx_univnet* h, float* ms_out, int* n_out) { return gen_stage_times_ms(h, h ? 2 * h->d.n_blocks + 2 : 0, ms_out, n_out); }
 
 int gvx_univnet_forward(gvx_univnet* h, const float* mel, const float* noise, const int32_t* frame_lengths, int B, int T, float* wav_out,
                         float* const* stage_out, void* workspace, size_t workspace_bytes, void* stream) {
@@ -496,12 +451,10 @@ int gvx_univnet_forward(gvx_univnet* h, const float* mel, const float* noise, co
     if (const char* why = un_shape_problem(B, T)) return fail(GVX_ERR_INVALID_ARG, "%s", why);
     if (T < GVX_UNIVNET_MIN_FRAMES) return fail(GVX_ERR_INVALID_ARG, "T = %d: a row needs at least %d frames", T, (int)GVX_UNIVNET_MIN_FRAMES);
     const UnWs wp = un_ws_plan(d, B, T);
-    if (!workspace || (uintptr_t)workspace % 256 || workspace_bytes < wp.total)
-        return fail(GVX_ERR_WORKSPACE, "the workspace is missing, misaligned or smaller than %zu bytes", wp.total);
     const int n_stage = d.n_blocks + 2;
-    if (stage_out)
-        for (int i = 0; i < n_stage; ++i)
-            if (!stage_out[i] || (uintptr_t)stage_out[i] % 16) return fail(GVX_ERR_INVALID_ARG, "stage_out[%d] is null or not 16-byte aligned", i);
+    int ev = 0, rc;
+    if ((rc = gen_check_workspace(workspace, workspace_bytes, wp.total)) != GVX_OK) return rc;
+    if ((rc = gen_check_stage_out(stage_out, n_stage)) != GVX_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     const UnBlob L = un_blob_layout(d);
     const float* blob = h->blob;
@@ -519,11 +472,7 @@ int gvx_univnet_forward(gvx_univnet* h, const float* mel, const float* noise, co
     float* xa = gvx::ws_ptr<float>(workspace, wp.xa);
     float* xb = gvx::ws_ptr<float>(workspace, wp.xb);
     float* y = gvx::ws_ptr<float>(workspace, wp.y);
-    int ev = 0, rc;
-    auto stamp = [&]() -> int {
-        if (h->timing) HIP_TRY(hipEventRecord(h->ev[ev++], s));
-        return GVX_OK;
-    };
+    auto stamp = [&] { return gen_mark(h, ev++, s); };
     auto hg = [&](const float* src, size_t w, size_t bias, float* out, int in_mul, int Cin, int Cout, int taps, int dil, int phases, int act, int zero_tail) {
         HgLayer p = un_layer(src, blob + w, blob + bias, out, lens, T, in_mul, Cin, Cout, taps, dil, phases, act, slope);
         p.zero_tail = zero_tail;

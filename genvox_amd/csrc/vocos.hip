@@ -22,22 +22,18 @@
 //
 // Order of this file: kernels, dims / blob / workspace layouts, the C ABI.
 #include "fft_lds.h"
-#include "gvx_internal.h"
+#include "gen_host.h"
 
 #include <algorithm>
 
-using gvx::fail;
+using namespace gvx_gen;
 using gvx::GemmParams;
 using gvx::RowMap;
 
 namespace gvx { hipError_t gemm_init(); }
 
-struct gvx_vocos {
+struct gvx_vocos : GenHandle {
     gvx_vocos_dims d;
-    const float* blob = nullptr;
-    bool timing = false;
-    hipEvent_t ev[5] = {};
-    int n_ev = 0;
 };
 
 namespace {
@@ -46,12 +42,6 @@ constexpr int VC_P = GVX_VOCOS_TILE;
 constexpr int VC_WAVES = 4;          // waves per workgroup of the filter + LayerNorm kernel and of the frame kernel
 constexpr float VC_LN_EPS = 1e-6f;
 constexpr float VC_MAG_MAX = 100.f;
-
-__device__ __forceinline__ int vc_frames(const int32_t* lens, int b, int T) {
-    int v = lens ? lens[b] : T;
-    v = v > T ? T : v;
-    return v < 1 ? 0 : v;   // rows the host should have refused produce silence, never a bad address
-}
 
 __device__ __forceinline__ float vc_wave_sum(float v) {   // a butterfly: every lane ends with the same bits
 #pragma unroll
@@ -66,7 +56,7 @@ __global__ void __launch_bounds__(256) vc_mel_transpose_kernel(const float* __re
     __shared__ float tile[32][33];
     const int b = blockIdx.z, r0 = (int)blockIdx.x * 32, c0 = (int)blockIdx.y * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    const int len = vc_frames(lens, b, T);
+    const int len = gen_frames(lens, b, T);
     for (int i = ty; i < 32; i += 8) {
         const int c = c0 + i, t = r0 + tx - 3;
         tile[i][tx] = (c < M && t >= 0 && t < len) ? mel[((size_t)b * M + c) * T + t] : 0.f;
@@ -92,7 +82,7 @@ __global__ void __launch_bounds__(VC_WAVES * 64) vc_dwconv_ln_kernel(const VcNor
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int b = blockIdx.y, t0 = (int)blockIdx.x * VC_P, C = p.C;
-    const int len = vc_frames(p.lens, b, p.T);
+    const int len = gen_frames(p.lens, b, p.T);
     const size_t row = (size_t)b * p.T;
     const int t_end = min(t0 + VC_P, p.T);
     const bool filter = p.taps != 0;
@@ -203,7 +193,7 @@ __global__ void __launch_bounds__(VC_WAVES * 64) vc_istft_kernel(const VcIstft p
     const int tid = threadIdx.x, j = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int b = blockIdx.y, t = (int)blockIdx.x * VC_WAVES + wave;
-    if (t >= vc_frames(p.lens, b, p.T)) return;   // behind the row's frames: the gather reads no such frame
+    if (t >= gen_frames(p.lens, b, p.T)) return;   // behind the row's frames: the gather reads no such frame
     const long f = (long)b * p.T + t;
     const float* c = p.coeffs + f * (N + 2);
     float2* buf = fsm + wave * fft_lds_words<H>();
@@ -250,7 +240,7 @@ __global__ void __launch_bounds__(256) vc_ola_kernel(const int32_t* __restrict__
     const int b = blockIdx.y;
     if (i_long >= n_max) return;
     const int i = (int)i_long;
-    const int len = vc_frames(lens, b, T);
+    const int len = gen_frames(lens, b, T);
     const int nb = center ? (len - 1) * hop : len * hop;   // (len = 0 or 1 under "center": nothing)
     float r = 0.f;
     if (i < nb) {
@@ -285,8 +275,6 @@ int vc_istft(const VcIstft& a, int B, int N, int hop, int center, float* wav, hi
 }
 
 // ---- dims, blob, workspace
-inline size_t vc_round64(size_t floats) { return (floats + 63) & ~(size_t)63; }
-inline size_t vc_round256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 inline int vc_cpad(const gvx_vocos_dims& d) { return (d.n_mels + 3) & ~3; }
 
 const char* vc_fft_problem(int n_fft, int hop, int center) {
@@ -317,7 +305,7 @@ struct VcBlob {
 VcBlob vc_blob_layout(const gvx_vocos_dims& d) {
     VcBlob L{};
     size_t at = 0;
-    auto take = [&](size_t floats) { const size_t o = at; at += vc_round64(floats); return o; };
+    auto take = [&](size_t floats) { const size_t o = at; at += gen_round64(floats); return o; };
     const size_t C = d.dim, I = d.intermediate_dim, N = d.n_fft;
     L.embed_w = take(C * 7 * vc_cpad(d)); L.embed_b = take(C); L.norm_w = take(C); L.norm_b = take(C);
     for (int i = 0; i < d.num_layers; ++i) {
@@ -335,15 +323,14 @@ struct VcWs { size_t mel_t, x, a, h, coeffs, frames, total; };
 
 VcWs vc_ws_plan(const gvx_vocos_dims& d, int B, int T) {
     VcWs w{};
-    size_t at = 0;
-    auto take = [&](size_t floats_per_row) { const size_t o = at; at += (size_t)B * vc_round256(floats_per_row * sizeof(float)); return o; };
-    w.mel_t = take((size_t)(T + 6) * vc_cpad(d));
-    w.x = take((size_t)T * d.dim);
-    w.a = take((size_t)T * d.dim);
-    w.h = take((size_t)T * d.intermediate_dim);
-    w.coeffs = take((size_t)T * (d.n_fft + 2));
-    w.frames = take((size_t)T * d.n_fft);
-    w.total = at;
+    GenRows ws{B};
+    w.mel_t = ws.rows((size_t)(T + 6) * vc_cpad(d));
+    w.x = ws.rows((size_t)T * d.dim);
+    w.a = ws.rows((size_t)T * d.dim);
+    w.h = ws.rows((size_t)T * d.intermediate_dim);
+    w.coeffs = ws.rows((size_t)T * (d.n_fft + 2));
+    w.frames = ws.rows((size_t)T * d.n_fft);
+    w.total = ws.total;
     return w;
 }
 
@@ -387,7 +374,7 @@ int gvx_dwconv_layernorm(const float* x, const int32_t* lens, int B, int T, int 
 
 size_t gvx_istft_head_workspace_bytes(int B, int T, int n_fft) {
     if (vc_shape_problem(B, T) || vc_fft_problem(n_fft, n_fft / 2, 0)) return 0;
-    return vc_round256((size_t)B * T * n_fft * sizeof(float)) + vc_round256((size_t)(n_fft + 1) * sizeof(float2));
+    return gen_round256((size_t)B * T * n_fft * sizeof(float)) + gen_round256((size_t)(n_fft + 1) * sizeof(float2));
 }
 
 int gvx_istft_head(const float* coeffs, const int32_t* lens, int B, int T, int n_fft, int hop, int center, const float* window, void* workspace,
@@ -402,7 +389,7 @@ int gvx_istft_head(const float* coeffs, const int32_t* lens, int B, int T, int n
     VcIstft a{};
     a.coeffs = coeffs; a.lens = lens; a.T = T; a.win = window;
     a.frames = static_cast<float*>(workspace);
-    float2* tw = gvx::ws_ptr<float2>(workspace, vc_round256((size_t)B * T * n_fft * sizeof(float)));
+    float2* tw = gvx::ws_ptr<float2>(workspace, gen_round256((size_t)B * T * n_fft * sizeof(float)));
     a.tw = tw; a.tw2 = tw + H;
     vc_tables_kernel<<<(unsigned)(n_fft / 256 + 1), 256, 0, s>>>(nullptr, tw, tw + H, n_fft);
     HIP_TRY(hipGetLastError());
@@ -425,35 +412,25 @@ int gvx_vocos_pack_weights_device(const gvx_vocos_dims* dims, const gvx_weight_d
     const gvx_vocos_dims& d = *dims;
     const VcBlob L = vc_blob_layout(d);
     hipStream_t s = (hipStream_t)stream;
-    struct Job { size_t dst; const float* src; size_t numel; };
-    std::vector<Job> jobs;
-    int rc = GVX_OK;
-    auto take = [&](const std::string& name, size_t dst, size_t numel) -> int {   // every name is looked up before anything is launched
-        const gvx_weight_desc* e = gvx_mg::mg_find(table, n, name, numel, rc);
-        if (!e) return rc;
-        jobs.push_back({dst, e->data, numel});
-        return GVX_OK;
-    };
+    GenPacker P{{table, n}};
     const size_t C = d.dim, I = d.intermediate_dim, N = d.n_fft;
-    if ((rc = take("embed.weight", L.embed_w, C * 7 * vc_cpad(d))) != GVX_OK) return rc;
-    if ((rc = take("embed.bias", L.embed_b, C)) != GVX_OK) return rc;
-    if ((rc = take("norm.weight", L.norm_w, C)) != GVX_OK) return rc;
-    if ((rc = take("norm.bias", L.norm_b, C)) != GVX_OK) return rc;
+    P.take("embed.weight", L.embed_w, C * 7 * vc_cpad(d));
+    P.take("embed.bias", L.embed_b, C);
+    P.take("norm.weight", L.norm_w, C);
+    P.take("norm.bias", L.norm_b, C);
     for (int i = 0; i < d.num_layers; ++i) {
         const std::string base = "convnext." + std::to_string(i) + ".";
         const VcLayer& l = L.layer[i];
         const struct { const char* name; size_t dst, numel; } parts[] = {
             {"dwconv.weight", l.dw_w, 7 * C}, {"dwconv.bias", l.dw_b, C}, {"norm.weight", l.ln_w, C}, {"norm.bias", l.ln_b, C},
             {"pwconv1.weight", l.pw1_w, I * C}, {"pwconv1.bias", l.pw1_b, I}, {"pwconv2.weight", l.pw2_w, C * I}, {"pwconv2.bias", l.pw2_b, C}};
-        for (const auto& part : parts)
-            if ((rc = take(base + part.name, part.dst, part.numel)) != GVX_OK) return rc;
+        for (const auto& part : parts) P.take(base + part.name, part.dst, part.numel);
     }
-    if ((rc = take("final_layer_norm.weight", L.fin_w, C)) != GVX_OK) return rc;
-    if ((rc = take("final_layer_norm.bias", L.fin_b, C)) != GVX_OK) return rc;
-    if ((rc = take("head.weight", L.head_w, (N + 2) * C)) != GVX_OK) return rc;
-    if ((rc = take("head.bias", L.head_b, N + 2)) != GVX_OK) return rc;
-    HIP_TRY(hipMemsetAsync(device_blob, 0, L.total * sizeof(float), s));   // the padding between the tensors
-    for (const Job& j : jobs) HIP_TRY(hipMemcpyAsync(device_blob + j.dst, j.src, j.numel * sizeof(float), hipMemcpyDeviceToDevice, s));
+    P.take("final_layer_norm.weight", L.fin_w, C);
+    P.take("final_layer_norm.bias", L.fin_b, C);
+    P.take("head.weight", L.head_w, (N + 2) * C);
+    P.take("head.bias", L.head_b, N + 2);
+    if (const int rc = P.run(device_blob, 0, L.total, s)) return rc;
     vc_tables_kernel<<<(unsigned)(d.n_fft / 256 + 1), 256, 0, s>>>(device_blob + L.window, reinterpret_cast<float2*>(device_blob + L.tw),
                                                                    reinterpret_cast<float2*>(device_blob + L.tw2), d.n_fft);
     HIP_TRY(hipGetLastError());
@@ -469,35 +446,17 @@ int gvx_vocos_create(const gvx_vocos_dims* dims, gvx_vocos** out) {
     return GVX_OK;
 }
 
-void gvx_vocos_destroy(gvx_vocos* h) {
-    if (!h) return;
-    for (int i = 0; i < h->n_ev; ++i) (void)hipEventDestroy(h->ev[i]);
-    delete h;
-}
+void gvx_vocos_destroy(gvx_vocos* h) { delete h; }
 
 int gvx_vocos_bind(gvx_vocos* h, const float* device_blob) {
-    if (!h || !device_blob) return fail(GVX_ERR_INVALID_ARG, "null argument");
-    if ((uintptr_t)device_blob % 256) return fail(GVX_ERR_INVALID_ARG, "the blob must be 256-byte aligned");
-    h->blob = device_blob;
+    if (const int rc = gen_bind(h, device_blob)) return rc;
     HIP_TRY(gvx::gemm_init());   // the big tiles' dynamic LDS
     return GVX_OK;
 }
 
-int gvx_vocos_timing_enable(gvx_vocos* h, int enable) {
-    if (!h) return fail(GVX_ERR_INVALID_ARG, "null argument");
-    while (enable && h->n_ev < 5) HIP_TRY(hipEventCreate(&h->ev[h->n_ev++]));
-    h->timing = enable != 0;
-    return GVX_OK;
-}
+int gvx_vocos_timing_enable(gvx_vocos* h, int enable) { return gen_timing_enable(h, enable, 5); }
 
-int gvx_vocos_stage_times_ms(gvx_vocos* h, float* ms_out, int* n_out) {
-    if (!h || !ms_out || !n_out) return fail(GVX_ERR_INVALID_ARG, "null argument");
-    if (!h->timing) return fail(GVX_ERR_STATE, "timing is not enabled");
-    HIP_TRY(hipEventSynchronize(h->ev[4]));
-    for (int i = 0; i < 4; ++i) HIP_TRY(hipEventElapsedTime(&ms_out[i], h->ev[i], h->ev[i + 1]));
-    *n_out = 4;
-    return GVX_OK;
-}
+int gvx_vocos_stage_times_ms(gvx_vocos* h, float* ms_out, int* n_out) { return gen_stage_times_ms(h, 4, ms_out, n_out); }
 
 int gvx_vocos_forward(gvx_vocos* h, const float* mel, const int32_t* frame_lengths, int B, int T, float* wav_out, float* const* stage_out,
                       void* workspace, size_t workspace_bytes, void* stream) {
@@ -507,12 +466,10 @@ int gvx_vocos_forward(gvx_vocos* h, const float* mel, const int32_t* frame_lengt
     if (const char* why = vc_shape_problem(B, T)) return fail(GVX_ERR_INVALID_ARG, "%s", why);
     if (T < 1 + d.center) return fail(GVX_ERR_INVALID_ARG, "T = %d: a row needs at least %d frames", T, 1 + d.center);
     const VcWs wp = vc_ws_plan(d, B, T);
-    if (!workspace || (uintptr_t)workspace % 256 || workspace_bytes < wp.total)
-        return fail(GVX_ERR_WORKSPACE, "the workspace is missing, misaligned or smaller than %zu bytes", wp.total);
     const int n_stage = d.num_layers + 3;
-    if (stage_out)
-        for (int i = 0; i < n_stage; ++i)
-            if (!stage_out[i] || (uintptr_t)stage_out[i] % 16) return fail(GVX_ERR_INVALID_ARG, "stage_out[%d] is null or not 16-byte aligned", i);
+    int ev = 0, rc;
+    if ((rc = gen_check_workspace(workspace, workspace_bytes, wp.total)) != GVX_OK) return rc;
+    if ((rc = gen_check_stage_out(stage_out, n_stage)) != GVX_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     const VcBlob L = vc_blob_layout(d);
     const float* blob = h->blob;
@@ -522,11 +479,7 @@ int gvx_vocos_forward(gvx_vocos* h, const float* mel, const int32_t* frame_lengt
     float* a = gvx::ws_ptr<float>(workspace, wp.a);
     float* hid = gvx::ws_ptr<float>(workspace, wp.h);
     float* coeffs = stage_out ? stage_out[n_stage - 1] : gvx::ws_ptr<float>(workspace, wp.coeffs);
-    int ev = 0, rc;
-    auto stamp = [&]() -> int {
-        if (h->timing) HIP_TRY(hipEventRecord(h->ev[ev++], s));
-        return GVX_OK;
-    };
+    auto stamp = [&] { return gen_mark(h, ev++, s); };
     auto norm = [&](const float* src, float* dst, int taps, size_t w, size_t b, size_t ln_w, size_t ln_b) {
         VcNorm p{};
         p.x = src; p.out = dst; p.lens = frame_lengths; p.T = T; p.C = C; p.taps = taps;
