@@ -23,6 +23,20 @@ has T * mul positions per row.  test_split_pieces runs B = 1 at
                          layers at mul = 8 / 16 (12 and 16 channels, and conv_post) run hgb_wgrad_valu_kernel over 8 to 33 pieces;
     T = 128, 129 (TWO)   512 and 516 positions at mul = 4: exactly one piece and one piece plus a tail for hgb_wgrad_mfma_kernel<1> and
                          the bias sums it makes, and for hgb_colsum_kernel on ups.0's bias.
+With B = 1, and in every other case of one piece per row, the piece index is the position's and the row index: piece p belongs to
+row p / ppr and starts at (p % ppr) * 512 only matters where B > 1 and ppr > 1.  test_pieces_across_rows runs those (shapes in
+tests/backward_piece_cases.py, all pinned):
+    NARROW, TWO 2 x 513                      ppr = 2 at mul = 1 with both rows full: pieces 1 and 3 hold one position;
+    NARROW, TWO 3 x 1030, (513, 1, 1030)     ppr = 3 at mul = 1: row 0 is a full piece / one position / a piece behind the row, row 1
+                                             one position / dead / dead, row 2 full / full / a tail of 6; ppr = 9 at mul = 4; a piece
+                                             behind its row (n_st <= 0, count <= 0) must write zeros over what the workspace held:
+                                             hgb_wgrad_mfma_kernel<2> on conv_pre and ups.0 with its part_b, <1> on TWO's 32-channel
+                                             layers, hgb_wgrad_valu_kernel, hgb_colsum_kernel;
+    MID 3 x 300, (300, 1, 129)               the matrix kernel everywhere; ppr = 3 at mul = 4, where row 2's 516 positions are a full
+                                             piece, a 4-position piece and a dead one; ppr = 5 at mul = 8;
+    V1 3 x 17, (17, 1, 16)                   the published widths; ppr = 3, 5, 9 at mul = 64, 128, 256; row 2 fills exactly two pieces
+                                             at mul = 64 and its third is dead.
+tests/test_backward_piece_layouts_cpu.py asserts from the lengths alone that each shape contains these situations.
 The sizes around the 128-position tile of the data gradients and the 64-position tile of the weight gradients are the pinned cases
 MID 2 x 16 / 2 x 17 (64 / 128 and 68 / 136 positions) and TWO 1 x 8 / 1 x 9 (128 and 144 positions at stage 1, under the 72-row window).
 
@@ -32,6 +46,7 @@ import functools
 import pytest
 import torch
 
+from tests import backward_piece_cases as PC
 from tests import hifigan_grad_ref64 as GR
 from tests import hifigan_ref64 as R
 from tests.hifigan_train_helpers import DEV, NAN, TrainNet, compare_grads, compare_tape, poisoned
@@ -94,23 +109,43 @@ def _check_tie_free(name, B, T, lens=None):
     return mel, G, ref, tape, grads
 
 
-def _check_pinned(name, B, T, mel_seed=1):
+def _check_pinned(name, B, T, lens=None, mel_seed=1):
     """The reference is pinned to the device's own LeakyReLU decisions, after asserting that each one that differs from float64's
-    is a true near-tie."""
+    is a true near-tie.  With lengths the signs are compared inside each row (behind it the device's tape holds NaN and the reference
+    0, and the restatement takes no decision from there), and the case asserts what test_ragged_rows asserts."""
     cfg, sd, net = _net(name)
     mel, G = R.random_mel(cfg, B, T, mel_seed), _cotangent(cfg, B, T)
-    wav, tape, grads = _device_run(name, mel, G, None)
+    wav, tape, grads = _device_run(name, mel, G, lens)
     views = [v.cpu() for v in net.tape_views(tape, B, T)]
-    free = GR.reference(sd, mel, None, cfg, G)   # float64's own decisions
+    free = GR.reference(sd, mel, lens, cfg, G)   # float64's own decisions
     flips = 0
-    for i in range(1, len(views)):
+    for i, mul in enumerate(GR.tape_muls_of(free)):
+        if i == 0:
+            continue
         differ = (views[i] > 0) != (free["tape"][i] > 0)
+        if lens is not None:
+            for b, t in enumerate(lens):
+                differ[b, :, t * mul:] = False
         flips += int(differ.sum())
         assert (free["tape"][i][differ].abs() <= GR.FACTOR * free["tape_err"][i]).all(), f"tape tensor {i}: a sign differs from float64 away from 0"
-    ref = GR.reference(sd, mel, None, cfg, G, GR.masks_from_tape(views, cfg))
-    what = f"{name} {B} x {T} pinned ({GR.near_ties(free)} near-ties, {flips} decided the other way)"
-    print(f"{what}: largest tape error / bound {compare_tape(views, ref, None, what):.3f}")
+    ref = GR.reference(sd, mel, lens, cfg, G, GR.masks_from_tape(views, cfg))
+    what = f"{name} {B} x {T}" + (f" lengths {lens}" if lens else "") + f" pinned ({GR.near_ties(free, lens)} near-ties, {flips} decided the other way)"
+    print(f"{what}: largest tape error / bound {compare_tape(views, ref, lens, what):.3f}")
     compare_grads(grads, ref, what)
+    if lens is not None:
+        _check_rows_alone(name, mel, G, lens, grads)
+
+
+def _check_rows_alone(name, mel, G, lens, grads):
+    """d_mel of every row is exactly 0 behind its length and bit-equal to that row run alone."""
+    cfg, _, net = _net(name)
+    hop = R.hop(cfg)
+    for b, t in enumerate(lens):
+        assert not grads["mel"][b, :, t:].any(), f"row {b}: d_mel is not 0 behind its {t} frames"
+        mel_d, G_d = poisoned(mel[b:b + 1, :, :t].contiguous(), G[b:b + 1, :t * hop].contiguous(), None, hop)
+        _, tape_b = net.forward_train(mel_d)
+        alone = net.backward(G_d, None, 1, t, tape_b)
+        assert torch.equal(alone["mel"][0], grads["mel"][b, :, :t]), f"row {b}: d_mel differs from that row run alone"
 
 
 @pytest.mark.parametrize("name,B,T", [("NARROW", 2, 5), ("NARROW", 1, 1), ("TWO", 2, 5), ("TWO", 1, 33), ("MID", 1, 3), ("MID", 1, 1)])
@@ -145,6 +180,13 @@ def test_split_pieces(name, T):
     """Reduction lengths of one piece, one piece plus one position, two pieces plus a tail, for every weight-gradient kernel and the
     bias sums (the module docstring names the layers)."""
     _check_pinned(name, 1, T)
+
+
+@pytest.mark.parametrize("name,B,T,lens", PC.HIFIGAN_CASES)
+def test_pieces_across_rows(name, B, T, lens):
+    """Several rows with several pieces each in one call, padded and ragged (the module docstring says what each shape reaches;
+    tests/test_backward_piece_layouts_cpu.py asserts that it does).  The ragged cases also assert what test_ragged_rows asserts."""
+    _check_pinned(name, B, T, lens)
 
 
 @pytest.mark.parametrize("name,T,lens", [("NARROW", 9, (4, 9, 5)), ("MID", 17, (4, 17, 8))])

@@ -17,12 +17,26 @@ Pieces.  The weight and bias gradients reduce over the positions of all rows lai
 at mul = 1 - exactly one piece, one piece plus one position, two pieces plus a tail of 6 - which are, per weight-gradient kernel:
 mgb_wgrad_valu_kernel NARROW's ups.0 (16 output channels), mgb_wgrad_mfma_kernel<1> NARROW's pre (32), mgb_wgrad_mfma_kernel<2>
 SHALLOW's pre and ups.0 (128 and 64), mgb_colsum_kernel every bias of those; the layers at mul = 4 and 8 run 4 to 17 pieces with and
-without a tail in the same calls."""
+without a tail in the same calls.  There B = 1: no piece meets a row boundary.  test_pieces_across_rows runs the same kernels with
+several rows and several pieces in one call (shapes in tests/backward_piece_cases.py, all pinned):
+    NARROW, SHALLOW 3 x 350                    rows begin at 350 and 700 of the line at mul = 1, inside pieces 0 and 1 and inside a
+                                               32-position k-tile of the matrix kernel, whose threads each decide their own row;
+    NARROW, SHALLOW 3 x 1030, (300, 4, 301)    7 pieces at mul = 1: piece 1 lies wholly behind row 0's length and must come out as
+                                               zeros, not as what the workspace held; rows 1 and 2 begin inside pieces 2 and 4 and
+                                               inside k-tiles that begin behind the previous row's length; the last piece has 18
+                                               positions, all dead; 25 and 49 pieces at mul = 4 and 8, several wholly dead;
+    DEFAULT 4 x 32                             the training benchmark's shape class: one piece holding four rows at mul = 1, pieces
+                                               of exactly two rows at mul = 8, four pieces per row at mul = 64;
+    DEFAULT 4 x 33, (33, 5, 32, 17)            Lmax = 33 and 264 at the 512- and 256-channel layers: k-tiles with live positions of
+                                               two rows; row 1 leaves whole pieces dead from mul = 64 on;
+and test_pieces_across_rows_without_kinks DEFAULT 4 x 32 at slope 1 against plain autograd.  tests/test_backward_piece_layouts_cpu.py
+asserts from the lengths alone that each shape contains these situations."""
 import functools
 
 import pytest
 import torch
 
+from tests import backward_piece_cases as PC
 from tests import melgan_grad_ref64 as GR
 from tests import melgan_ref64 as R
 from tests.melgan_train_helpers import DEV, NAN, TrainNet, compare_grads, compare_tape, poisoned
@@ -85,23 +99,43 @@ def _check_tie_free(name, B, T, lens=None):
     return mel, G, ref, tape, grads
 
 
-def _check_pinned(name, B, T, mel_seed=1):
+def _check_pinned(name, B, T, lens=None, mel_seed=1):
     """The reference is pinned to the device's own LeakyReLU decisions, after asserting that each one that differs from float64's
-    is a true near-tie."""
+    is a true near-tie.  With lengths the signs are compared inside each row (behind it the device's tape holds NaN and the reference
+    0, and the restatement takes no decision from there), and the case asserts what test_ragged_rows asserts."""
     cfg, sd, net = _net(name)
     mel, G = R.random_mel(cfg, B, T, mel_seed), _cotangent(cfg, B, T)
-    wav, tape, grads = _device_run(name, mel, G, None)
+    wav, tape, grads = _device_run(name, mel, G, lens)
     views = [v.cpu() for v in net.tape_views(tape, B, T)]
-    free = GR.reference(sd, mel, None, cfg, G)   # float64's own decisions
+    free = GR.reference(sd, mel, lens, cfg, G)   # float64's own decisions
     flips = 0
-    for i in range(1, len(views)):
+    for i, mul in enumerate(GR.tape_muls_of(free)):
+        if i == 0:
+            continue
         differ = (views[i] > 0) != (free["tape"][i] > 0)
+        if lens is not None:
+            for b, t in enumerate(lens):
+                differ[b, :, t * mul:] = False
         flips += int(differ.sum())
         assert (free["tape"][i][differ].abs() <= GR.FACTOR * free["tape_err"][i]).all(), f"tape tensor {i}: a sign differs from float64 away from 0"
-    ref = GR.reference(sd, mel, None, cfg, G, GR.masks_from_tape(views, cfg["slope"]))
-    what = f"{name} {B} x {T} pinned ({GR.near_ties(free)} near-ties, {flips} decided the other way)"
-    compare_tape(views, ref, None, what)
-    compare_grads(grads, ref, what)
+    ref = GR.reference(sd, mel, lens, cfg, G, GR.masks_from_tape(views, cfg["slope"]))
+    what = f"{name} {B} x {T}" + (f" lengths {lens}" if lens else "") + f" pinned ({GR.near_ties(free, lens)} near-ties, {flips} decided the other way)"
+    compare_tape(views, ref, lens, what)
+    print(f"{what}: largest gradient error / bound {compare_grads(grads, ref, what):.3f}")
+    if lens is not None:
+        _check_rows_alone(name, mel, G, lens, grads)
+
+
+def _check_rows_alone(name, mel, G, lens, grads):
+    """d_mel of every row is exactly 0 behind its length and bit-equal to that row run alone."""
+    cfg, _, net = _net(name)
+    hop = R.hop(cfg)
+    for b, t in enumerate(lens):
+        assert not grads["mel"][b, :, t:].any(), f"row {b}: d_mel is not 0 behind its {t} frames"
+        mel_d, G_d = poisoned(mel[b:b + 1, :, :t].contiguous(), G[b:b + 1, :t * hop].contiguous(), None, hop)
+        _, tape_b = net.forward_train(mel_d)
+        alone = net.backward(G_d, None, 1, t, tape_b)
+        assert torch.equal(alone["mel"][0], grads["mel"][b, :, :t]), f"row {b}: d_mel differs from that row run alone"
 
 
 @pytest.mark.parametrize("name,B,T", [("NARROW", 2, 4), ("NARROW", 2, 7), ("SHALLOW", 2, 5), ("TWO_DEEP", 1, 4), ("TWO_DEEP", 2, 17), ("WIDE", 2, 4)])
@@ -132,6 +166,25 @@ def test_split_pieces(name, T):
     """Reduction lengths of one piece, one piece plus one position, two pieces plus a tail, for every weight-gradient kernel (the
     module docstring names the layers)."""
     _check_pinned(name, 1, T)
+
+
+@pytest.mark.parametrize("name,B,T,lens", PC.MELGAN_CASES)
+def test_pieces_across_rows(name, B, T, lens):
+    """Several rows and several pieces in one call, padded and ragged (the module docstring says what each shape reaches;
+    tests/test_backward_piece_layouts_cpu.py asserts that it does).  The ragged cases also assert what test_ragged_rows asserts."""
+    _check_pinned(name, B, T, lens)
+
+
+def test_pieces_across_rows_without_kinks():
+    """slope = 1 at the default sizes, 4 x 32 frames: plain float64 autograd, no tape reading."""
+    name, B, T, lens = PC.MELGAN_LINEAR_CASE
+    cfg, sd, net = _net(name)
+    mel, G = R.random_mel(cfg, B, T, 1), _cotangent(cfg, B, T)
+    ref = GR.reference(sd, mel, lens, cfg, G)
+    wav, tape, grads = _device_run(name, mel, G, lens)
+    what = f"{name} {B} x {T}"
+    compare_tape(net.tape_views(tape, B, T), ref, lens, what)
+    print(f"{what}: largest gradient error / bound {compare_grads(grads, ref, what):.3f}")
 
 
 @pytest.mark.parametrize("name,T,lens", [("NARROW", 9, (4, 9, 5)), ("TWO_DEEP", 17, (4, 17, 8))])
