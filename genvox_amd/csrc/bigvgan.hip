@@ -174,7 +174,7 @@ inline int bv_acts_per_block(const gvx_hifigan_dims& d) { return d.n_dilations *
 BvBlob bv_blob_layout(const gvx_hifigan_dims& d) {
     BvBlob L{};
     size_t at = hg_blob_layout(d).total;
-    auto take = [&](size_t floats) { const size_t o = at; at += gen_round64(floats); return o; };
+    auto take = [&](size_t floats) { const size_t o = at; at += gvx::round64(floats); return o; };
     L.filter = take(BV_TAPS);
     size_t C = d.upsample_initial_channel;
     for (int i = 0; i < d.n_stages; ++i) {

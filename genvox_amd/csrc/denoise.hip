@@ -8,11 +8,12 @@
 //
 // Order of this file: kernels, workspace layout, the C ABI.
 #include "fft_lds.h"
-#include "gvx_internal.h"
+#include "stft_plan.h"
 
 #include <algorithm>
 
 using gvx::fail;
+using namespace gvx_plan;
 
 struct gvx_denoise_plan {
     int n_fft = 0, hop = 0;
@@ -159,14 +160,13 @@ struct DnLayout {
     size_t frames, total;
 };
 
-inline size_t dn_round256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-
 DnLayout dn_layout(const gvx_denoise_plan* p, int B, long n_max) {
     DnLayout L{};
     L.f_max = (int)(1 + n_max / p->hop);
     L.nwg = (L.f_max + DN_FRAMES - 1) / DN_FRAMES;
-    L.frames = 0;
-    L.total = dn_round256((size_t)B * L.f_max * p->n_fft * sizeof(float));
+    StftRegions ws;
+    L.frames = ws.take((size_t)B * L.f_max * p->n_fft * sizeof(float));
+    L.total = ws.total;
     return L;
 }
 
@@ -177,13 +177,6 @@ const char* dn_shape_problem(const gvx_denoise_plan* p, int B, long n_max) {
     return nullptr;
 }
 
-template <int H>
-int dn_launch(const float* wav, const int32_t* lens, int B, long n_max, int nwg, const DnArgs& a, hipStream_t s) {
-    dn_frame_kernel<H><<<dim3((unsigned)nwg, (unsigned)B), DN_FRAMES * 64, 0, s>>>(wav, lens, n_max, a);
-    HIP_TRY(hipGetLastError());
-    return GVX_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -192,17 +185,10 @@ int gvx_denoise_create(int n_fft, int hop, gvx_denoise_plan** out) {
     if (!out) return fail(GVX_ERR_INVALID_ARG, "null argument");
     if (n_fft != 512 && n_fft != 1024 && n_fft != 2048) return fail(GVX_ERR_UNSUPPORTED, "n_fft = %d, supported are 512, 1024 and 2048", n_fft);
     if (hop < 1 || hop > n_fft / 2) return fail(GVX_ERR_INVALID_ARG, "hop = %d is outside [1, n_fft / 2 = %d]", hop, n_fft / 2);
-    const int N = n_fft, H = N / 2;
     gvx_denoise_plan* p = new gvx_denoise_plan();
-    p->n_fft = n_fft; p->hop = hop; p->pad = H; p->n_min = H + 1;
-    std::vector<float>& h = p->host_tables;
-    h.assign(N, 0.f);
-    const double two_pi = 6.283185307179586476925286766559;
-    for (int k = 0; k < N; ++k) h[k] = (float)(0.5 - 0.5 * std::cos(two_pi * k / N));
-    p->tw_at = h.size();
-    for (int m = 0; m < H; ++m) { h.push_back((float)std::cos(two_pi * m / H)); h.push_back((float)-std::sin(two_pi * m / H)); }
-    p->tw2_at = h.size();
-    for (int k = 0; k <= H; ++k) { h.push_back((float)std::cos(two_pi * k / N)); h.push_back((float)-std::sin(two_pi * k / N)); }
+    p->n_fft = n_fft; p->hop = hop; p->pad = n_fft / 2; p->n_min = n_fft / 2 + 1;
+    const StftTables t = stft_tables(p->host_tables, n_fft, n_fft);   // the window first: t.win = 0
+    p->tw_at = t.tw; p->tw2_at = t.tw2;
     *out = p;
     return GVX_OK;
 }
@@ -227,17 +213,8 @@ int gvx_denoise(gvx_denoise_plan* p, const float* wav, const int32_t* sample_len
     if (strength > 0.f && !bias) return fail(GVX_ERR_INVALID_ARG, "strength = %g needs a bias spectrum", (double)strength);
     if (n_max < p->n_min) return fail(GVX_ERR_SHAPE, "n_max = %ld: a row needs at least n_fft / 2 + 1 = %d samples for the reflection", n_max, p->n_min);
     const DnLayout L = dn_layout(p, B, n_max);
-    if (!workspace || ((uintptr_t)workspace & 255)) return fail(GVX_ERR_WORKSPACE, "the workspace must be non-null and 256-byte aligned");
-    if (workspace_bytes < L.total) return fail(GVX_ERR_WORKSPACE, "workspace too small: %zu bytes, %zu needed", workspace_bytes, L.total);
-    if (!p->tables) {
-        const std::vector<float>& h = p->host_tables;
-        if (hipMalloc(&p->tables, h.size() * sizeof(float)) != hipSuccess ||
-            hipMemcpy(p->tables, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-            if (p->tables) (void)hipFree(p->tables);
-            p->tables = nullptr;
-            return fail(GVX_ERR_HIP, "window and twiddle table allocation failed");
-        }
-    }
+    if (const int rc = stft_check_workspace(workspace, workspace_bytes, L.total)) return rc;
+    if (!p->tables && !stft_upload(&p->tables, p->host_tables)) return fail(GVX_ERR_HIP, "window and twiddle table allocation failed");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     char* ws = reinterpret_cast<char*>(workspace);
     DnArgs a{};
@@ -249,30 +226,18 @@ int gvx_denoise(gvx_denoise_plan* p, const float* wav, const int32_t* sample_len
     a.hop = p->hop; a.f_max = L.f_max;
     a.frames = out ? reinterpret_cast<float*>(ws + L.frames) : nullptr;
     a.mag = mag_out;
-    int rc;
-    switch (p->n_fft) {
-        case 512: rc = dn_launch<256>(wav, sample_lengths, B, n_max, L.nwg, a, s); break;
-        case 1024: rc = dn_launch<512>(wav, sample_lengths, B, n_max, L.nwg, a, s); break;
-        default: rc = dn_launch<1024>(wav, sample_lengths, B, n_max, L.nwg, a, s); break;
-    }
+    const int rc = stft_dispatch(p->n_fft, [&](auto h) -> int {
+        dn_frame_kernel<decltype(h)::value><<<dim3((unsigned)L.nwg, (unsigned)B), DN_FRAMES * 64, 0, s>>>(wav, sample_lengths, n_max, a);
+        HIP_TRY(hipGetLastError());
+        return GVX_OK;
+    });
     if (rc != GVX_OK) return rc;
     if (out) {
         dn_gather_kernel<<<dim3((unsigned)((n_max + DN_GATHER - 1) / DN_GATHER), (unsigned)B), DN_GATHER, 0, s>>>(sample_lengths, n_max, a.frames, a.win,
                                                                                                                 p->n_fft, p->hop, L.f_max, out);
         HIP_TRY(hipGetLastError());
     }
-    if (sample_lengths) {
-        // the rows' lengths live on the device: the kernels above gave a refused row no frames (zero magnitudes, a zero row of out), and
-        // the host learns of it here, behind the launches, so that its wait overlaps their run
-        std::vector<int32_t> host(B);
-        HIP_TRY(hipMemcpyAsync(host.data(), sample_lengths, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        for (int b = 0; b < B; ++b) {
-            if (host[b] >= p->n_min && host[b] <= n_max) continue;
-            return fail(GVX_ERR_SHAPE, "row %d has %d samples: outside [n_fft / 2 + 1 = %d, n_max = %ld]", b, host[b], p->n_min, n_max);
-        }
-    }
-    return GVX_OK;
+    return stft_check_lengths(sample_lengths, B, n_max, p->n_min, "n_fft / 2 + 1", nullptr, s);
 }
 
 }  // extern "C"

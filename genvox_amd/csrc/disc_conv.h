@@ -8,6 +8,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include "rounding.h"
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -61,8 +62,6 @@ DC_HD inline int dc_length(int n, int period, const int* str, int count) {
     return n;
 }
 
-inline size_t dc_round64(size_t floats) { return (floats + 63) & ~(size_t)63; }
-inline size_t dc_round256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
 // pieces of one layer's weight gradient: rows are dealt `rows_per_piece` to a piece, or a row is cut into `chunks` runs of positions
 struct DcPieces { int chunks, rows_per_piece, n, run; size_t numel; };

@@ -471,7 +471,7 @@ template <typename F>
 FpBlob fp_blob_layout(const gvx_fastpitch_dims& d, F&& visit) {
     FpBlob L{};
     size_t at = 0;
-    auto take = [&](const std::string& name, size_t floats) { const size_t o = at; at += gen_round64(floats); if (!name.empty()) visit(name, o, floats); return o; };
+    auto take = [&](const std::string& name, size_t floats) { const size_t o = at; at += gvx::round64(floats); if (!name.empty()) visit(name, o, floats); return o; };
     const size_t C = d.d_model, F_ = d.pred_filter;
     L.emb = take("encoder.word_emb.weight", (size_t)d.n_tokens * C);
     for (int s = 0; s < 2; ++s) {

@@ -1,9 +1,10 @@
 // The host side that the generators share - csrc/melgan.hip, hifigan.hip, bigvgan.hip, vocos.hip, univnet.hip, fastpitch.hip: what a
-// handle holds besides its dims, the event marks and the stage times read off them, the roundings of the blob and workspace layouts
-// and a row's own length, the lookup of a tensor by name and the two packers built on it, and the argument checks that every forward
+// handle holds besides its dims, the event marks and the stage times read off them, a row's own length (the roundings of the layouts
+// are rounding.h's), the lookup of a tensor by name and the two packers built on it, and the argument checks that every forward
 // makes with the same words.  What only one model needs stays in that model's file.
 #pragma once
 #include "gvx_internal.h"
+#include "rounding.h"
 
 #include <string>
 #include <vector>
@@ -12,8 +13,6 @@ namespace gvx_gen {
 
 using gvx::fail;
 
-inline size_t gen_round64(size_t floats) { return (floats + 63) & ~(size_t)63; }    // every tensor of a blob starts on 256 bytes
-inline size_t gen_round256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }  // ... and every row of a workspace region
 
 // frames of row b: lens[b] (nullptr: T) clamped to T; a row of fewer than `least` produces silence, never a bad address
 __device__ __forceinline__ int gen_frames(const int32_t* lens, int b, int T, int least = 1) {
@@ -152,7 +151,7 @@ struct GenRows {
     size_t total = 0;
     size_t rows(size_t floats_per_row) {
         const size_t o = total;
-        total += (size_t)B * gen_round256(floats_per_row * sizeof(float));
+        total += (size_t)B * gvx::round256(floats_per_row * sizeof(float));
         return o;
     }
 };

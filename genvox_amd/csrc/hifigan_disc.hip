@@ -349,7 +349,7 @@ int gvx_hifigan_mpd_layer_times_ms(gvx_hifigan_mpd* h, float* forward_ms, float*
     return dc_layer_times_ms(h, h ? h->d.n_periods : 0, h ? h->d.n_layers + 1 : 0, forward_ms, backward_ms, n_layers_out);
 }
 
-int gvx_hifigan_mpd_bind(gvx_hifigan_mpd* h, const float* device_blob) { return dc_bind(h, device_blob); }
+int gvx_hifigan_mpd_bind(gvx_hifigan_mpd* h, const float* device_blob) { return gen_bind(h, device_blob); }
 
 int gvx_hifigan_mpd_forward(gvx_hifigan_mpd* h, const float* wav, const int32_t* sample_lengths, int B, int n_max, void* features,
                             size_t features_bytes, void* workspace, size_t workspace_bytes, void* stream) {
@@ -358,21 +358,21 @@ int gvx_hifigan_mpd_forward(gvx_hifigan_mpd* h, const float* wav, const int32_t*
     const gvx_hifigan_mpd_dims& d = h->d;
     const PdFeat F = pd_feat_layout(d, B, n_max);
     if ((rc = dc_check_features(features, features_bytes, F.total)) != GVX_OK) return rc;
-    if ((rc = dc_check_workspace(workspace, workspace_bytes, pd_ws_plan(d, B, n_max, false).total)) != GVX_OK) return rc;
+    if ((rc = gen_check_workspace(workspace, workspace_bytes, pd_ws_plan(d, B, n_max, false).total)) != GVX_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     PdLayer L[PD_MAX_MAPS];
     size_t per_period = 0;
     const int nl = pd_layers(d, L, &per_period);
     for (int j = 0; j < d.n_periods; ++j) {
         const float* in = wav;
-        if ((rc = dc_mark(h, h->fwd_ev, (size_t)j * (nl + 1), s)) != GVX_OK) return rc;
+        if ((rc = dc_mark(h, h->marks, (size_t)j * (nl + 1), s)) != GVX_OK) return rc;
         for (int i = 0; i < nl; ++i) {
             DcConv p = pd_conv(d, L[i], F, j, i, sample_lengths, n_max);
             p.src = in; p.W = h->blob + j * per_period + L[i].wf_off; p.bias = h->blob + j * per_period + L[i].b_off;
             p.out = gvx::ws_ptr<float>(features, F.off[j][i]);
             if ((rc = pd_launch_conv<false>(p, L[i].mfma != 0, B, s)) != GVX_OK) return rc;
             in = p.out;
-            if ((rc = dc_mark(h, h->fwd_ev, (size_t)j * (nl + 1) + i + 1, s)) != GVX_OK) return rc;
+            if ((rc = dc_mark(h, h->marks, (size_t)j * (nl + 1) + i + 1, s)) != GVX_OK) return rc;
         }
     }
     h->fwd_timed = h->timing;
@@ -388,7 +388,7 @@ int gvx_hifigan_mpd_backward(gvx_hifigan_mpd* h, const float* wav, const int32_t
     const gvx_hifigan_mpd_dims& d = h->d;
     const PdFeat F = pd_feat_layout(d, B, n_max);
     const PdWs wp = pd_ws_plan(d, B, n_max, true);
-    if ((rc = dc_check_workspace(workspace, workspace_bytes, wp.total)) != GVX_OK) return rc;
+    if ((rc = gen_check_workspace(workspace, workspace_bytes, wp.total)) != GVX_OK) return rc;
     PdLayer L[PD_MAX_MAPS];
     size_t per_period = 0;
     const int nl = pd_layers(d, L, &per_period);
@@ -402,7 +402,7 @@ int gvx_hifigan_mpd_backward(gvx_hifigan_mpd* h, const float* wav, const int32_t
     for (int j = 0; j < d.n_periods; ++j) {
         const float* blob = h->blob + j * per_period;
         const float* dcur = feat(d_features, j, nl - 1);   // the score has no activation: its cotangent is its pre-activation's
-        if ((rc = dc_mark(h, h->bwd_ev, (size_t)j * (nl + 1) + nl, s)) != GVX_OK) return rc;
+        if ((rc = dc_mark(h, h->bwd_marks, (size_t)j * (nl + 1) + nl, s)) != GVX_OK) return rc;
         for (int i = nl - 1; i >= 0; --i) {
             DcConv p = pd_conv(d, L[i], F, j, i, sample_lengths, n_max);
             if (n_grads > 0) {
@@ -425,7 +425,7 @@ int gvx_hifigan_mpd_backward(gvx_hifigan_mpd* h, const float* wav, const int32_t
                 pd_dwav_kernel<<<dim3((unsigned)((n_max + 255) / 256), (unsigned)B), 256, 0, s>>>(p, d_wav, j > 0);
                 HIP_TRY(hipGetLastError());
             }
-            if ((rc = dc_mark(h, h->bwd_ev, (size_t)j * (nl + 1) + i, s)) != GVX_OK) return rc;   // mark i: layer i is done
+            if ((rc = dc_mark(h, h->bwd_marks, (size_t)j * (nl + 1) + i, s)) != GVX_OK) return rc;   // mark i: layer i is done
         }
     }
     h->bwd_timed = h->timing;

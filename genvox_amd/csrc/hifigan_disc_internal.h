@@ -56,9 +56,9 @@ inline int pd_layers(const gvx_hifigan_mpd_dims& d, PdLayer* L, size_t* floats_o
     auto add = [&](int ci, int co, int k, int stride, int act) {
         PdLayer& l = L[n++];
         l = PdLayer{ci, co, k, stride, k / 2, act, (ci % PD_MFMA_MULT == 0 && co % PD_MFMA_MULT == 0) ? 1 : 0, 0, 0, 0};
-        l.wf_off = at; at += dc_round64(l.wn());
-        l.wb_off = at; at += dc_round64(l.wn());
-        l.b_off = at; at += dc_round64((size_t)co);
+        l.wf_off = at; at += gvx::round64(l.wn());
+        l.wb_off = at; at += gvx::round64(l.wn());
+        l.b_off = at; at += gvx::round64((size_t)co);
         params += l.wn() + co;
     };
     for (int i = 0; i < d.n_layers; ++i) {
@@ -96,7 +96,7 @@ inline PdFeat pd_feat_layout(const gvx_hifigan_mpd_dims& d, int B, int n_max) {
             F.channels[i] = L[i].cout;
             F.height[j][i] = dc_length(n_max, d.periods[j], str, i + 1);
             F.off[j][i] = at;
-            at += dc_round256((size_t)B * F.height[j][i] * d.periods[j] * L[i].cout * sizeof(float));
+            at += gvx::round256((size_t)B * F.height[j][i] * d.periods[j] * L[i].cout * sizeof(float));
         }
     F.total = at;
     return F;
@@ -130,7 +130,7 @@ struct PdWs : DcWs { size_t total; };   // byte offsets (backward only; the forw
 inline PdWs pd_ws_plan(const gvx_hifigan_mpd_dims& d, int B, int n_max, bool backward) {
     PdWs W{};
     size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += dc_round256(bytes); return o; };
+    auto take = [&](size_t bytes) { const size_t o = at; at += gvx::round256(bytes); return o; };
     if (backward) {
         PdLayer L[PD_MAX_MAPS];
         const int nl = pd_layers(d, L);

@@ -93,7 +93,7 @@ struct HgBlob {   // offsets in floats; conv_w[i][j][m][0 / 1]: convs1 / convs2 
 inline HgBlob hg_blob_layout(const gvx_hifigan_dims& d) {
     HgBlob L{};
     size_t at = 0;
-    auto take = [&](size_t floats) { const size_t o = at; at += gen_round64(floats); return o; };
+    auto take = [&](size_t floats) { const size_t o = at; at += gvx::round64(floats); return o; };
     size_t C = d.upsample_initial_channel;
     L.pre_w = take(C * 7 * hg_cpad(d));
     L.pre_b = take(C);

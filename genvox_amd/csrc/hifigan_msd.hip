@@ -372,7 +372,7 @@ int gvx_hifigan_msd_layer_times_ms(gvx_hifigan_msd* h, float* forward_ms, float*
     return dc_layer_times_ms(h, h ? h->d.n_scales : 0, h ? h->d.n_layers + 1 : 0, forward_ms, backward_ms, n_layers_out);
 }
 
-int gvx_hifigan_msd_bind(gvx_hifigan_msd* h, const float* device_blob) { return dc_bind(h, device_blob); }
+int gvx_hifigan_msd_bind(gvx_hifigan_msd* h, const float* device_blob) { return gen_bind(h, device_blob); }
 
 int gvx_hifigan_msd_forward(gvx_hifigan_msd* h, const float* wav, const int32_t* sample_lengths, int B, int n_max, void* features,
                             size_t features_bytes, void* workspace, size_t workspace_bytes, void* stream) {
@@ -382,7 +382,7 @@ int gvx_hifigan_msd_forward(gvx_hifigan_msd* h, const float* wav, const int32_t*
     const SdFeat F = sd_feat_layout(d, B, n_max);
     if ((rc = dc_check_features(features, features_bytes, F.total)) != GVX_OK) return rc;
     const SdWs wp = sd_ws_plan(d, B, n_max, false);
-    if ((rc = dc_check_workspace(workspace, workspace_bytes, wp.total)) != GVX_OK) return rc;
+    if ((rc = gen_check_workspace(workspace, workspace_bytes, wp.total)) != GVX_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     SdLayer L[SD_MAX_MAPS];
     size_t per_scale = 0;
@@ -390,14 +390,14 @@ int gvx_hifigan_msd_forward(gvx_hifigan_msd* h, const float* wav, const int32_t*
     if ((rc = sd_pool_all(d, F, wp, wav, sample_lengths, B, n_max, workspace, s)) != GVX_OK) return rc;
     for (int sc = 0; sc < d.n_scales; ++sc) {
         const float* in = sc == 0 ? wav : gvx::ws_ptr<float>(workspace, wp.pooled[sc]);
-        if ((rc = dc_mark(h, h->fwd_ev, (size_t)sc * (nl + 1), s)) != GVX_OK) return rc;
+        if ((rc = dc_mark(h, h->marks, (size_t)sc * (nl + 1), s)) != GVX_OK) return rc;
         for (int i = 0; i < nl; ++i) {
             DcConv p = sd_conv(d, L[i], F, sc, i, sample_lengths, n_max);
             p.src = in; p.W = h->blob + sc * per_scale + L[i].wf_off; p.bias = h->blob + sc * per_scale + L[i].b_off;
             p.out = gvx::ws_ptr<float>(features, F.off[sc][i]);
             if ((rc = sd_launch_conv<false>(p, L[i].mfma, B, s)) != GVX_OK) return rc;
             in = p.out;
-            if ((rc = dc_mark(h, h->fwd_ev, (size_t)sc * (nl + 1) + i + 1, s)) != GVX_OK) return rc;
+            if ((rc = dc_mark(h, h->marks, (size_t)sc * (nl + 1) + i + 1, s)) != GVX_OK) return rc;
         }
     }
     h->fwd_timed = h->timing;
@@ -413,7 +413,7 @@ int gvx_hifigan_msd_backward(gvx_hifigan_msd* h, const float* wav, const int32_t
     const gvx_hifigan_msd_dims& d = h->d;
     const SdFeat F = sd_feat_layout(d, B, n_max);
     const SdWs wp = sd_ws_plan(d, B, n_max, true);
-    if ((rc = dc_check_workspace(workspace, workspace_bytes, wp.total)) != GVX_OK) return rc;
+    if ((rc = gen_check_workspace(workspace, workspace_bytes, wp.total)) != GVX_OK) return rc;
     SdLayer L[SD_MAX_MAPS];
     size_t per_scale = 0;
     const int nl = sd_layers(d, L, &per_scale);
@@ -430,7 +430,7 @@ int gvx_hifigan_msd_backward(gvx_hifigan_msd* h, const float* wav, const int32_t
         const float* blob = h->blob + sc * per_scale;
         const float* wav_s = sc == 0 ? wav : gvx::ws_ptr<float>(workspace, wp.pooled[sc]);
         const float* dcur = feat(d_features, sc, nl - 1);   // the score has no activation: its cotangent is its pre-activation's
-        if ((rc = dc_mark(h, h->bwd_ev, (size_t)sc * (nl + 1) + nl, s)) != GVX_OK) return rc;
+        if ((rc = dc_mark(h, h->bwd_marks, (size_t)sc * (nl + 1) + nl, s)) != GVX_OK) return rc;
         for (int i = nl - 1; i >= 0; --i) {
             DcConv p = sd_conv(d, L[i], F, sc, i, sample_lengths, n_max);
             if (n_grads > 0) {
@@ -460,7 +460,7 @@ int gvx_hifigan_msd_backward(gvx_hifigan_msd* h, const float* wav, const int32_t
                     p, next, more ? F.n_scale[sc + 1] : 0, out);
                 HIP_TRY(hipGetLastError());
             }
-            if ((rc = dc_mark(h, h->bwd_ev, (size_t)sc * (nl + 1) + i, s)) != GVX_OK) return rc;   // mark i: layer i is done
+            if ((rc = dc_mark(h, h->bwd_marks, (size_t)sc * (nl + 1) + i, s)) != GVX_OK) return rc;   // mark i: layer i is done
         }
     }
     h->bwd_timed = h->timing;

@@ -56,9 +56,9 @@ inline int sd_layers(const gvx_hifigan_msd_dims& d, SdLayer* L, size_t* floats_o
     auto add = [&](int ci, int co, int k, int stride, int groups, int act) {
         SdLayer& l = L[n++];
         l = SdLayer{ci, co, k, stride, k / 2, groups, act, sd_mfma_kind(ci / groups, co / groups), 0, 0, 0};
-        l.wf_off = at; at += dc_round64(l.wn());
-        l.wb_off = at; at += dc_round64(l.wn());
-        l.b_off = at; at += dc_round64((size_t)co);
+        l.wf_off = at; at += gvx::round64(l.wn());
+        l.wb_off = at; at += gvx::round64(l.wn());
+        l.b_off = at; at += gvx::round64((size_t)co);
         params += l.wn() + co;
     };
     for (int i = 0; i < d.n_layers; ++i) {
@@ -98,7 +98,7 @@ inline SdFeat sd_feat_layout(const gvx_hifigan_msd_dims& d, int B, int n_max) {
             F.channels[i] = L[i].cout;
             F.length[s][i] = dc_length(F.n_scale[s], 1, str, i + 1);
             F.off[s][i] = at;
-            at += dc_round256((size_t)B * F.length[s][i] * L[i].cout * sizeof(float));
+            at += gvx::round256((size_t)B * F.length[s][i] * L[i].cout * sizeof(float));
         }
     }
     F.total = at;
@@ -157,7 +157,7 @@ struct SdWs : DcWs {   // byte offsets
 inline SdWs sd_ws_plan(const gvx_hifigan_msd_dims& d, int B, int n_max, bool backward) {
     SdWs W{};
     size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += dc_round256(bytes); return o; };
+    auto take = [&](size_t bytes) { const size_t o = at; at += gvx::round256(bytes); return o; };
     const SdFeat F = sd_feat_layout(d, B, n_max);
     for (int s = 1; s < d.n_scales; ++s) W.pooled[s] = take((size_t)B * F.n_scale[s] * sizeof(float));
     if (backward) {

@@ -25,6 +25,7 @@
 //
 // The transposed weights come from the bound blob at the start of every backward call (hgb_transpose_kernel), so they are the weights
 // the forward used.  Order of this file: descriptions, kernels, plans (tape, workspace), launches, the C ABI.
+#include "gen_backward.h"
 #include "hifigan_kernels.h"
 
 using gvx::fail;
@@ -287,34 +288,9 @@ __global__ void __launch_bounds__(256) hgb_transpose_kernel(float* dst, const fl
     }
 }
 
-// dz = d_wav * (1 - wav^2) inside a row, 0 behind it (d_wav is not read there)
-__global__ void __launch_bounds__(256) hgb_tanh_bwd_kernel(const float* d_wav, const float* wav, const int32_t* lens, int T, int hop, float* dz) {
-    const int b = blockIdx.y;
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long)T * hop) return;
-    const size_t at = (size_t)b * T * hop + idx;
-    float v = 0.f;
-    if (idx < (long)gen_frames(lens, b, T) * hop) {
-        const float w = wav[at];
-        v = d_wav[at] * (1.f - w * w);
-    }
-    dz[at] = v;
-}
-
-// d_mel [B][M][T] from its channels-last form [B][T][Cp]; exactly 0 at and behind a row's frames
-__global__ void __launch_bounds__(256) hgb_dmel_kernel(const float* dmel_t, const int32_t* lens, int M, int T, int Cp, float* d_mel) {
-    const int b = blockIdx.y;
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long)M * T) return;
-    const int t = (int)(idx % T), c = (int)(idx / T);
-    d_mel[(size_t)b * M * T + idx] = t < gen_frames(lens, b, T) ? dmel_t[((size_t)b * T + t) * Cp + c] : 0.f;
-}
-
 // ---- plans
-struct HgTapeSlot { size_t off; int mul, C; };   // offset in floats
-
 struct HgTape {
-    std::vector<HgTapeSlot> slots;
+    std::vector<GenTapeSlot> slots;
     // indices into slots: mel 0, conv_pre 1, per stage ups' output, per (block, dilation) the inner tensor (resblock 1) and the running
     // value after the dilation (every dilation but the last), the stage's average
     int up[GVX_HIFIGAN_MAX_STAGES], avg[GVX_HIFIGAN_MAX_STAGES];
@@ -359,7 +335,7 @@ inline int hgb_ppr(int T, int mul) { return (int)(((long)T * mul + HGB_PIECE - 1
 HgBlob hgb_wt_layout(const gvx_hifigan_dims& d) {
     HgBlob L{};
     size_t at = 0;
-    auto take = [&](size_t floats) { const size_t o = at; at += gen_round64(floats); return o; };
+    auto take = [&](size_t floats) { const size_t o = at; at += gvx::round64(floats); return o; };
     size_t C = d.upsample_initial_channel;
     L.pre_w = take(C * 7 * hg_cpad(d));
     for (int i = 0; i < d.n_stages; ++i) {
@@ -402,7 +378,7 @@ HgbWs hgb_ws_plan(const gvx_hifigan_dims& d, int B, int T) {
     }
     need(mul, 1, 7 * C);
     size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += gen_round256(bytes); return o; };
+    auto take = [&](size_t bytes) { const size_t o = at; at += gvx::round256(bytes); return o; };
     w.wt = take(w.wt_at.total * sizeof(float));
     w.wav = take((size_t)B * T * mul * sizeof(float));
     w.dz = take((size_t)B * T * mul * sizeof(float));
@@ -480,20 +456,6 @@ int hgb_transpose(float* dst, const float* src, int kind, int Cout, int Cin, int
     return GVX_OK;
 }
 
-float* hgb_grad(const gvx_grad_desc* table, int n, const std::string& name, size_t numel, int& rc) {
-    if (rc != GVX_OK) return nullptr;
-    for (int i = 0; i < n; ++i)
-        if (table[i].name && name == table[i].name) {
-            if (!table[i].data || table[i].numel != (int64_t)numel) {
-                rc = fail(GVX_ERR_SHAPE, "the gradient of %s has %lld elements, the dims ask for %zu", name.c_str(), (long long)table[i].numel, numel);
-                return nullptr;
-            }
-            return table[i].data;
-        }
-    rc = fail(GVX_ERR_MISSING_WEIGHT, "the gradient of %s has no destination", name.c_str());
-    return nullptr;
-}
-
 struct HgbGrads {
     float *pre_w, *pre_b, *post_w, *post_b;
     float *up_w[GVX_HIFIGAN_MAX_STAGES], *up_b[GVX_HIFIGAN_MAX_STAGES];
@@ -506,9 +468,7 @@ int hgb_check_call(const gvx_hifigan* h, int B, int T, const void* tape, size_t 
     if (B < 1 || B > 65535) return fail(GVX_ERR_INVALID_ARG, "B must be in [1, 65535]");
     if (T < 1) return fail(GVX_ERR_INVALID_ARG, "T = %d: a row needs at least 1 frame", T);
     if (T > GVX_HIFIGAN_MAX_FRAMES) return fail(GVX_ERR_UNSUPPORTED, "T = %d is beyond the limit of %d frames", T, GVX_HIFIGAN_MAX_FRAMES);
-    const size_t need = hgb_tape_plan(h->d, B, T).floats * sizeof(float);
-    if (!tape || (uintptr_t)tape % 256 || tape_bytes < need) return fail(GVX_ERR_WORKSPACE, "the tape is missing, misaligned or smaller than %zu bytes", need);
-    return GVX_OK;
+    return gen_check_tape(tape, tape_bytes, hgb_tape_plan(h->d, B, T).floats * sizeof(float));
 }
 
 HgLayer hgb_layer(const gvx_hifigan_dims& d, const int32_t* lens, int T, const float* src, const float* W, const float* bias, float* out, int in_mul,
@@ -531,14 +491,7 @@ size_t gvx_hifigan_tape_bytes(const gvx_hifigan_dims* dims, int B, int T) {
 
 int gvx_hifigan_tape_layout(const gvx_hifigan_dims* dims, int B, int T, gvx_hifigan_tape_entry* entries, int max_entries) {
     if (!hgb_shape_ok(dims, B, T)) return 0;
-    const HgTape t = hgb_tape_plan(*dims, B, T);
-    const int n = (int)t.slots.size();
-    for (int i = 0; entries && i < n && i < max_entries; ++i) {
-        entries[i].byte_offset = t.slots[i].off * sizeof(float);
-        entries[i].positions_per_frame = t.slots[i].mul;
-        entries[i].channels = t.slots[i].C;
-    }
-    return n;
+    return gen_tape_layout(hgb_tape_plan(*dims, B, T).slots, entries, max_entries);
 }
 
 size_t gvx_hifigan_backward_workspace_bytes(const gvx_hifigan_dims* dims, int B, int T) {
@@ -614,8 +567,7 @@ int gvx_hifigan_backward(gvx_hifigan* h, const float* d_wav, const int32_t* fram
     if ((rc = hgb_check_call(h, B, T, tape, tape_bytes)) != GVX_OK) return rc;
     const gvx_hifigan_dims& d = h->d;
     const HgbWs wp = hgb_ws_plan(d, B, T);
-    if (!workspace || (uintptr_t)workspace % 256 || workspace_bytes < wp.total)
-        return fail(GVX_ERR_WORKSPACE, "the workspace is missing, misaligned or smaller than %zu bytes", wp.total);
+    if ((rc = gen_check_workspace(workspace, workspace_bytes, wp.total)) != GVX_OK) return rc;
     const int S = d.n_stages, NK = d.n_resblocks, ND = d.n_dilations, NV = hg_convs_per_dilation(d), Cp = hg_cpad(d);
     int hop = 1, C_last = d.upsample_initial_channel;
     for (int i = 0; i < S; ++i) { hop *= d.upsample_rates[i]; C_last /= 2; }
@@ -624,24 +576,24 @@ int gvx_hifigan_backward(gvx_hifigan* h, const float* d_wav, const int32_t* fram
     HgbGrads g{};
     {
         size_t C = d.upsample_initial_channel;
-        g.pre_w = hgb_grad(grads, n_grads, "conv_pre.weight", C * d.n_mels * 7, rc);
-        g.pre_b = hgb_grad(grads, n_grads, "conv_pre.bias", C, rc);
+        g.pre_w = gen_grad(grads, n_grads, "conv_pre.weight", C * d.n_mels * 7, rc);
+        g.pre_b = gen_grad(grads, n_grads, "conv_pre.bias", C, rc);
         for (int i = 0; i < S; ++i) {
             const size_t Cn = C / 2;
             const std::string up = "ups." + std::to_string(i);
-            g.up_w[i] = hgb_grad(grads, n_grads, up + ".weight", C * Cn * 2 * d.upsample_rates[i], rc);
-            g.up_b[i] = hgb_grad(grads, n_grads, up + ".bias", Cn, rc);
+            g.up_w[i] = gen_grad(grads, n_grads, up + ".weight", C * Cn * 2 * d.upsample_rates[i], rc);
+            g.up_b[i] = gen_grad(grads, n_grads, up + ".bias", Cn, rc);
             for (int j = 0; j < NK; ++j)
                 for (int m = 0; m < ND; ++m)
                     for (int v = 0; v < NV; ++v) {
                         const std::string name = hg_conv_name(d, i * NK + j, m, v);
-                        g.conv_w[i][j][m][v] = hgb_grad(grads, n_grads, name + ".weight", Cn * Cn * d.resblock_kernel_sizes[j], rc);
-                        g.conv_b[i][j][m][v] = hgb_grad(grads, n_grads, name + ".bias", Cn, rc);
+                        g.conv_w[i][j][m][v] = gen_grad(grads, n_grads, name + ".weight", Cn * Cn * d.resblock_kernel_sizes[j], rc);
+                        g.conv_b[i][j][m][v] = gen_grad(grads, n_grads, name + ".bias", Cn, rc);
                     }
             C = Cn;
         }
-        g.post_w = hgb_grad(grads, n_grads, "conv_post.weight", 7 * C, rc);
-        g.post_b = hgb_grad(grads, n_grads, "conv_post.bias", 1, rc);
+        g.post_w = gen_grad(grads, n_grads, "conv_post.weight", 7 * C, rc);
+        g.post_b = gen_grad(grads, n_grads, "conv_post.bias", 1, rc);
         if (rc != GVX_OK) return rc;   // nothing was launched
     }
     hipStream_t s = (hipStream_t)stream;
@@ -711,7 +663,7 @@ int gvx_hifigan_backward(gvx_hifigan* h, const float* d_wav, const int32_t* fram
         HgLayer p = hgb_layer(d, frame_lengths, T, x_last, blob + L.post_w, blob + L.post_b, wav, hop, C_last, 1, 7, 1, 1, 1);
         p.slope = d.post_slope; p.tanh_out = 1;
         if ((rc = hg_launch(p, B, s)) != GVX_OK) return rc;
-        hgb_tanh_bwd_kernel<<<dim3((unsigned)(((long)T * hop + 255) / 256), (unsigned)B), 256, 0, s>>>(d_wav, wav, frame_lengths, T, hop, dz);
+        gen_tanh_bwd_kernel<1><<<dim3((unsigned)(((long)T * hop + 255) / 256), (unsigned)B), 256, 0, s>>>(d_wav, wav, frame_lengths, T, hop, dz);
         HIP_TRY(hipGetLastError());
         if ((rc = conv_grads(dz, x_last, hop, C_last, C_last, 1, 7, 1, 1, d.post_slope, g.post_w, g.post_b)) != GVX_OK) return rc;
         if ((rc = dgrad(dz, wt + WL.post_w, gs, hop, 1, C_last, 7, 1, x_last, d.post_slope, nullptr, nullptr, (float)NK)) != GVX_OK) return rc;
@@ -765,7 +717,7 @@ int gvx_hifigan_backward(gvx_hifigan* h, const float* d_wav, const int32_t* fram
     if ((rc = conv_grads(gs, slot(0), 1, Cp, d.n_mels, C, 7, 1, 0, d.slope, g.pre_w, g.pre_b)) != GVX_OK) return rc;
     if (d_mel_out) {
         if ((rc = dgrad(gs, wt + WL.pre_w, pb, 1, C, Cp, 7, 1, nullptr, d.slope, nullptr, nullptr, 0.f)) != GVX_OK) return rc;
-        hgb_dmel_kernel<<<dim3((unsigned)(((long)d.n_mels * T + 255) / 256), (unsigned)B), 256, 0, s>>>(pb, frame_lengths, d.n_mels, T, Cp, d_mel_out);
+        gen_dmel_kernel<1><<<dim3((unsigned)(((long)d.n_mels * T + 255) / 256), (unsigned)B), 256, 0, s>>>(pb, frame_lengths, d.n_mels, T, Cp, d_mel_out);
         HIP_TRY(hipGetLastError());
     }
     return stamp();

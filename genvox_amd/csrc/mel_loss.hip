@@ -9,11 +9,12 @@
 //
 // Order of this file: kernels, workspace layout, the C ABI.
 #include "fft_lds.h"
-#include "gvx_internal.h"
+#include "stft_plan.h"
 
 #include <algorithm>
 
 using gvx::fail;
+using namespace gvx_plan;
 
 struct gvx_mel_loss_plan {
     int n_fft = 0, hop = 0, win_length = 0, n_mels = 0;
@@ -265,18 +266,15 @@ struct MlLayout {
     size_t g, part, rows, total;
 };
 
-inline size_t ml_round256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-
 MlLayout ml_layout(const gvx_mel_loss_plan* p, int B, long n_max) {
     MlLayout L{};
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += ml_round256(bytes); return o; };
+    StftRegions ws;
     L.f_max = (int)(n_max / p->hop);
     L.nwg = (L.f_max + ML_FRAMES - 1) / ML_FRAMES;
-    L.g = take((size_t)B * L.f_max * p->n_fft * sizeof(float));
-    L.part = take((size_t)B * L.nwg * sizeof(double));
-    L.rows = take((size_t)B * sizeof(double));
-    L.total = at;
+    L.g = ws.take((size_t)B * L.f_max * p->n_fft * sizeof(float));
+    L.part = ws.take((size_t)B * L.nwg * sizeof(double));
+    L.rows = ws.take((size_t)B * sizeof(double));
+    L.total = ws.total;
     return L;
 }
 
@@ -285,13 +283,6 @@ const char* ml_shape_problem(const gvx_mel_loss_plan* p, int B, long n_max) {
     if (B < 1 || B > GVX_MEL_LOSS_MAX_ROWS) return "B must be in [1, GVX_MEL_LOSS_MAX_ROWS]";
     if (n_max < 1 || n_max > GVX_MEL_LOSS_MAX_SAMPLES) return "n_max must be in [1, GVX_MEL_LOSS_MAX_SAMPLES]";
     return nullptr;
-}
-
-template <int H>
-int ml_launch(const float* pred, const float* target, const int32_t* lens, int B, long n_max, int n_min, const MlArgs& a, hipStream_t s) {
-    ml_frame_kernel<H><<<dim3((unsigned)a.nwg, (unsigned)B), ML_FRAMES * 64, 0, s>>>(pred, target, lens, n_max, n_min, a);
-    HIP_TRY(hipGetLastError());
-    return GVX_OK;
 }
 
 }  // namespace
@@ -325,7 +316,7 @@ int gvx_mel_loss_create(int n_fft, int hop, int win_length, int n_mels, const fl
     if (n_mels < 1 || n_mels > ML_MAX_MELS) return fail(GVX_ERR_INVALID_ARG, "n_mels = %d is outside [1, %d]", n_mels, ML_MAX_MELS);
     if (!(clamp > 0.f) || std::isinf(clamp)) return fail(GVX_ERR_INVALID_ARG, "clamp must be finite and > 0");
     if (!(mag_eps > 0.f) || std::isinf(mag_eps)) return fail(GVX_ERR_INVALID_ARG, "mag_eps must be finite and > 0");
-    const int N = n_fft, H = N / 2, bins = H + 1;
+    const int bins = n_fft / 2 + 1;
     for (size_t i = 0; i < (size_t)n_mels * bins; ++i)
         if (!std::isfinite(mel_basis[i])) return fail(GVX_ERR_INVALID_ARG, "mel_basis[%zu][%zu] is not finite", i / bins, i % bins);
     gvx_mel_loss_plan* p = new gvx_mel_loss_plan();
@@ -337,14 +328,8 @@ int gvx_mel_loss_create(int n_fft, int hop, int win_length, int n_mels, const fl
     (void)gvx_mel_loss_bands(mel_basis, n_mels, bins, p->mel_lo.data(), p->mel_hi.data(), p->bin_lo.data(), p->bin_hi.data());
     std::vector<float>& h = p->host_tables;
     std::vector<int32_t>& bands = p->host_bands;
-    h.assign(N, 0.f);
-    const double two_pi = 6.283185307179586476925286766559;
-    const int off = (N - win_length) / 2;
-    for (int k = 0; k < win_length; ++k) h[off + k] = (float)(0.5 - 0.5 * std::cos(two_pi * k / win_length));
-    p->tw_at = h.size();
-    for (int m = 0; m < H; ++m) { h.push_back((float)std::cos(two_pi * m / H)); h.push_back((float)-std::sin(two_pi * m / H)); }
-    p->tw2_at = h.size();
-    for (int k = 0; k <= H; ++k) { h.push_back((float)std::cos(two_pi * k / N)); h.push_back((float)-std::sin(two_pi * k / N)); }
+    const StftTables t = stft_tables(h, n_fft, win_length);   // the window first: t.win = 0
+    p->tw_at = t.tw; p->tw2_at = t.tw2;
     p->fwd_at = h.size();
     for (int j = 0; j < n_mels; ++j) {
         const int cnt = p->mel_hi[j] - p->mel_lo[j] + 1;
@@ -381,19 +366,11 @@ int gvx_mel_loss(gvx_mel_loss_plan* p, const float* pred, const float* target, c
     if (n_max < p->n_min)
         return fail(GVX_ERR_SHAPE, "n_max = %ld: a row needs at least max(hop, (n_fft - hop) / 2 + 1) = %d samples", n_max, p->n_min);
     const MlLayout L = ml_layout(p, B, n_max);
-    if (!workspace || ((uintptr_t)workspace & 255)) return fail(GVX_ERR_WORKSPACE, "the workspace must be non-null and 256-byte aligned");
-    if (workspace_bytes < L.total) return fail(GVX_ERR_WORKSPACE, "workspace too small: %zu bytes, %zu needed", workspace_bytes, L.total);
-    if (!p->tables) {
-        const std::vector<float>& h = p->host_tables;
-        const std::vector<int32_t>& bands = p->host_bands;
-        if (hipMalloc(&p->tables, h.size() * sizeof(float)) != hipSuccess || hipMalloc(&p->bands, bands.size() * sizeof(int32_t)) != hipSuccess ||
-            hipMemcpy(p->tables, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(p->bands, bands.data(), bands.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
-            if (p->tables) (void)hipFree(p->tables);
-            if (p->bands) (void)hipFree(p->bands);
-            p->tables = nullptr; p->bands = nullptr;
-            return fail(GVX_ERR_HIP, "window, twiddle and band table allocation failed");
-        }
+    if (const int rc = stft_check_workspace(workspace, workspace_bytes, L.total)) return rc;
+    if (!p->tables && (!stft_upload(&p->tables, p->host_tables) || !stft_upload(&p->bands, p->host_bands))) {
+        if (p->tables) (void)hipFree(p->tables);   // the bands were refused
+        p->tables = nullptr;
+        return fail(GVX_ERR_HIP, "window, twiddle and band table allocation failed");
     }
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     char* ws = reinterpret_cast<char*>(workspace);
@@ -411,12 +388,11 @@ int gvx_mel_loss(gvx_mel_loss_plan* p, const float* pred, const float* target, c
     a.part = reinterpret_cast<double*>(ws + L.part);
     a.dbg_p = dbg ? dbg->log_mel_pred : nullptr;
     a.dbg_t = dbg ? dbg->log_mel_target : nullptr;
-    int rc;
-    switch (p->n_fft) {
-        case 512: rc = ml_launch<256>(pred, target, sample_lengths, B, n_max, p->n_min, a, s); break;
-        case 1024: rc = ml_launch<512>(pred, target, sample_lengths, B, n_max, p->n_min, a, s); break;
-        default: rc = ml_launch<1024>(pred, target, sample_lengths, B, n_max, p->n_min, a, s); break;
-    }
+    const int rc = stft_dispatch(p->n_fft, [&](auto h) -> int {
+        ml_frame_kernel<decltype(h)::value><<<dim3((unsigned)a.nwg, (unsigned)B), ML_FRAMES * 64, 0, s>>>(pred, target, sample_lengths, n_max, p->n_min, a);
+        HIP_TRY(hipGetLastError());
+        return GVX_OK;
+    });
     if (rc != GVX_OK) return rc;
     ml_reduce_kernel<<<1, 256, 0, s>>>(sample_lengths, n_max, p->n_min, B, p->hop, p->n_mels, L.nwg, a.part, reinterpret_cast<double*>(ws + L.rows),
                                        parts_out, loss_out);
@@ -426,19 +402,7 @@ int gvx_mel_loss(gvx_mel_loss_plan* p, const float* pred, const float* target, c
                                                                                                                 p->n_fft, p->hop, p->pad, L.f_max, d_pred);
         HIP_TRY(hipGetLastError());
     }
-    if (sample_lengths) {
-        // the rows' lengths live on the device: the kernels above gave a refused row no frames (NaN part, NaN loss, zero gradient), and
-        // the host learns of it here, behind the launches, so that its wait overlaps their run
-        std::vector<int32_t> host(B);
-        HIP_TRY(hipMemcpyAsync(host.data(), sample_lengths, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        for (int b = 0; b < B; ++b) {
-            if (host[b] >= p->n_min && host[b] <= n_max) continue;
-            if (grad) HIP_TRY(hipMemsetAsync(d_pred, 0, (size_t)B * n_max * sizeof(float), s));
-            return fail(GVX_ERR_SHAPE, "row %d has %d samples: outside [max(hop, (n_fft - hop) / 2 + 1) = %d, n_max = %ld]", b, host[b], p->n_min, n_max);
-        }
-    }
-    return GVX_OK;
+    return stft_check_lengths(sample_lengths, B, n_max, p->n_min, "max(hop, (n_fft - hop) / 2 + 1)", d_pred, s);
 }
 
 }  // extern "C"

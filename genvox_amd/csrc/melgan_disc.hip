@@ -13,18 +13,17 @@
 //                  md_reduce_kernel adds the pieces in their order.  No atomics anywhere: two calls give the same bits.
 // Dot products are summed in runs of at most 32 input channels whose sums are then added, so the dense layer's 5120 terms never form one
 // chain.  Rows are ragged: every length derives from the row's own n_b, and a map is exact zeros behind it.
-#include "gvx_internal.h"
+#include "disc_handle.h"
 #include "melgan_disc_internal.h"
-#include "melgan_internal.h"
 
 #include <climits>
 
 using gvx::fail;
 using namespace gvx_md;
+using namespace gvx_dc;
 
-struct gvx_melgan_disc {
+struct gvx_melgan_disc : gvx_gen::GenHandle {
     gvx_melgan_disc_dims d;
-    const float* blob = nullptr;
 };
 
 namespace {
@@ -385,13 +384,17 @@ int md_launch_pool(const float* x, float* y, const int32_t* lens, int B, int n_m
 }
 
 int md_check_call(const gvx_melgan_disc* h, const float* wav, const void* features, int B, int n_max) {
-    if (!h || !wav || !features) return fail(GVX_ERR_INVALID_ARG, "null argument");
-    if (!h->blob) return fail(GVX_ERR_STATE, "no weight blob is bound");
-    if (B < 1 || B > 65535) return fail(GVX_ERR_INVALID_ARG, "B must be in [1, 65535]");
+    if (const int rc = dc_check_call(h, wav, features, B)) return rc;
     if (n_max < md_min_samples(h->d))
         return fail(GVX_ERR_INVALID_ARG, "n_max = %d: the last scale's reflection needs at least %d samples", n_max, md_min_samples(h->d));
     if (n_max > GVX_MELGAN_DISC_MAX_SAMPLES) return fail(GVX_ERR_UNSUPPORTED, "n_max = %d is beyond the limit of %d samples", n_max, GVX_MELGAN_DISC_MAX_SAMPLES);
     return GVX_OK;
+}
+
+std::string md_name(int k, int i, int) { return "scales." + std::to_string(k) + ".layers." + std::to_string(i); }
+
+bool md_shape_ok(const gvx_melgan_disc_dims* d, int B, int n_max) {
+    return !md_dims_problem(d) && B >= 1 && B <= 65535 && n_max >= md_min_samples(*d) && n_max <= GVX_MELGAN_DISC_MAX_SAMPLES;
 }
 
 }  // namespace
@@ -407,7 +410,7 @@ size_t gvx_melgan_disc_blob_floats(const gvx_melgan_disc_dims* dims) {
 }
 
 int gvx_melgan_disc_layout(const gvx_melgan_disc_dims* dims, int B, int n_max, gvx_melgan_disc_entry* entries, int max_entries) {
-    if (md_dims_problem(dims) || B < 1 || B > 65535 || n_max < md_min_samples(*dims) || n_max > GVX_MELGAN_DISC_MAX_SAMPLES) return 0;
+    if (!md_shape_ok(dims, B, n_max)) return 0;
     const MdFeat F = md_feat_layout(*dims, B, n_max);
     int n = 0;
     for (int k = 0; k < dims->n_scales; ++k)
@@ -417,12 +420,12 @@ int gvx_melgan_disc_layout(const gvx_melgan_disc_dims* dims, int B, int n_max, g
 }
 
 size_t gvx_melgan_disc_features_bytes(const gvx_melgan_disc_dims* dims, int B, int n_max) {
-    if (md_dims_problem(dims) || B < 1 || B > 65535 || n_max < md_min_samples(*dims) || n_max > GVX_MELGAN_DISC_MAX_SAMPLES) return 0;
+    if (!md_shape_ok(dims, B, n_max)) return 0;
     return md_feat_layout(*dims, B, n_max).total;
 }
 
 size_t gvx_melgan_disc_workspace_bytes(const gvx_melgan_disc_dims* dims, int B, int n_max, int backward) {
-    if (md_dims_problem(dims) || B < 1 || B > 65535 || n_max < md_min_samples(*dims) || n_max > GVX_MELGAN_DISC_MAX_SAMPLES) return 0;
+    if (!md_shape_ok(dims, B, n_max)) return 0;
     return md_ws_plan(*dims, B, n_max, backward != 0).total;
 }
 
@@ -435,8 +438,8 @@ int gvx_melgan_disc_pack_weights_device(const gvx_melgan_disc_dims* dims, const 
     gvx_gen::GenPacker P{{table, n}};
     for (int k = 0; k < dims->n_scales; ++k)
         for (int i = 0; i < nl; ++i) {
-            const std::string name = "scales." + std::to_string(k) + ".layers." + std::to_string(i);
-            P.take(name + ".weight", k * per_scale + L[i].w_off, (size_t)L[i].cout * L[i].cig * L[i].k);
+            const std::string name = md_name(k, i, nl);
+            P.take(name + ".weight", k * per_scale + L[i].w_off, L[i].wn());
             P.take(name + ".bias", k * per_scale + L[i].b_off, (size_t)L[i].cout);
         }
     return P.run(device_blob, 0, per_scale * dims->n_scales, (hipStream_t)stream);
@@ -453,12 +456,7 @@ int gvx_melgan_disc_create(const gvx_melgan_disc_dims* dims, gvx_melgan_disc** o
 
 void gvx_melgan_disc_destroy(gvx_melgan_disc* h) { delete h; }
 
-int gvx_melgan_disc_bind(gvx_melgan_disc* h, const float* device_blob) {
-    if (!h || !device_blob) return fail(GVX_ERR_INVALID_ARG, "null argument");
-    if ((uintptr_t)device_blob % 256) return fail(GVX_ERR_INVALID_ARG, "the blob must be 256-byte aligned");
-    h->blob = device_blob;
-    return GVX_OK;
-}
+int gvx_melgan_disc_bind(gvx_melgan_disc* h, const float* device_blob) { return gen_bind(h, device_blob); }
 
 int gvx_melgan_disc_forward(gvx_melgan_disc* h, const float* wav, const int32_t* sample_lengths, int B, int n_max, void* features,
                             size_t features_bytes, void* workspace, size_t workspace_bytes, void* stream) {
@@ -466,11 +464,9 @@ int gvx_melgan_disc_forward(gvx_melgan_disc* h, const float* wav, const int32_t*
     if ((rc = md_check_call(h, wav, features, B, n_max)) != GVX_OK) return rc;
     const gvx_melgan_disc_dims& d = h->d;
     const MdFeat F = md_feat_layout(d, B, n_max);
-    if ((uintptr_t)features % 256 || features_bytes < F.total)
-        return fail(GVX_ERR_WORKSPACE, "the features buffer is misaligned or smaller than %zu bytes", F.total);
+    if ((rc = dc_check_features(features, features_bytes, F.total)) != GVX_OK) return rc;
     const MdWs wp = md_ws_plan(d, B, n_max, false);
-    if (!workspace || (uintptr_t)workspace % 256 || workspace_bytes < wp.total)
-        return fail(GVX_ERR_WORKSPACE, "the workspace is missing, misaligned or smaller than %zu bytes", wp.total);
+    if ((rc = gen_check_workspace(workspace, workspace_bytes, wp.total)) != GVX_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     MdLayer L[MD_MAX_LAYERS];
     size_t per_scale = 0;
@@ -499,35 +495,16 @@ int gvx_melgan_disc_backward(gvx_melgan_disc* h, const float* wav, const int32_t
                              void* workspace, size_t workspace_bytes, void* stream) {
     int rc;
     if ((rc = md_check_call(h, wav, features, B, n_max)) != GVX_OK) return rc;
-    if (!d_features) return fail(GVX_ERR_INVALID_ARG, "null argument");
-    if (n_grads < 0 || (n_grads > 0 && !grads)) return fail(GVX_ERR_INVALID_ARG, "n_grads = %d without a table", n_grads);
-    if (n_grads == 0 && !d_wav) return fail(GVX_ERR_INVALID_ARG, "neither parameter gradients nor d_wav are asked for");
+    if ((rc = dc_check_backward(features, d_features, grads, n_grads, d_wav)) != GVX_OK) return rc;
     const gvx_melgan_disc_dims& d = h->d;
     const MdFeat F = md_feat_layout(d, B, n_max);
-    if ((uintptr_t)features % 256 || (uintptr_t)d_features % 256) return fail(GVX_ERR_WORKSPACE, "features or d_features is not 256-byte aligned");
     const MdWs wp = md_ws_plan(d, B, n_max, true);
-    if (!workspace || (uintptr_t)workspace % 256 || workspace_bytes < wp.total)
-        return fail(GVX_ERR_WORKSPACE, "the workspace is missing, misaligned or smaller than %zu bytes", wp.total);
+    if ((rc = gen_check_workspace(workspace, workspace_bytes, wp.total)) != GVX_OK) return rc;
     MdLayer L[MD_MAX_LAYERS];
     size_t per_scale = 0;
     const int nl = md_layers(d, L, &per_scale);
-    float* gw[GVX_MELGAN_DISC_MAX_SCALES][MD_MAX_LAYERS] = {};
-    float* gb[GVX_MELGAN_DISC_MAX_SCALES][MD_MAX_LAYERS] = {};
-    if (n_grads > 0) {
-        const gvx_weight_desc* table = reinterpret_cast<const gvx_weight_desc*>(grads);   // same fields, the data pointer writable
-        static_assert(sizeof(gvx_weight_desc) == sizeof(gvx_grad_desc), "the two tables share a layout");
-        for (int k = 0; k < d.n_scales; ++k)
-            for (int i = 0; i < nl; ++i) {
-                const std::string name = "scales." + std::to_string(k) + ".layers." + std::to_string(i);
-                rc = GVX_OK;
-                const gvx_weight_desc* w = gvx_gen::gen_find(table, n_grads, name + ".weight", (size_t)L[i].cout * L[i].cig * L[i].k, rc);
-                if (!w) return rc;
-                gw[k][i] = const_cast<float*>(w->data);
-                w = gvx_gen::gen_find(table, n_grads, name + ".bias", (size_t)L[i].cout, rc);
-                if (!w) return rc;
-                gb[k][i] = const_cast<float*>(w->data);
-            }
-    }
+    DcParam g[GVX_MELGAN_DISC_MAX_SCALES * MD_MAX_LAYERS] = {};
+    if ((rc = dc_find_grads(grads, n_grads, d.n_scales, L, nl, g, md_name)) != GVX_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int min_n = md_min_samples(d);
     for (int k = 1; k < d.n_scales; ++k)   // the pooled waveforms again: the forward's workspace is not the backward's
@@ -552,9 +529,9 @@ int gvx_melgan_disc_backward(gvx_melgan_disc* h, const float* wav, const int32_t
                 if (cpt == 4) md_dw_kernel<4><<<grid, 256, 0, s>>>(p, parts, B, P.chunks, P.rows_per_piece);
                 else md_dw_kernel<1><<<grid, 256, 0, s>>>(p, parts, B, P.chunks, P.rows_per_piece);
                 HIP_TRY(hipGetLastError());
-                md_reduce_kernel<<<(unsigned)((P.numel + 255) / 256), 256, 0, s>>>(parts, gw[k][i], P.numel, P.n);
+                md_reduce_kernel<<<(unsigned)((P.numel + 255) / 256), 256, 0, s>>>(parts, g[k * nl + i].w, P.numel, P.n);
                 HIP_TRY(hipGetLastError());
-                md_db_kernel<<<(unsigned)L[i].cout, 256, 0, s>>>(p, gb[k][i], B);
+                md_db_kernel<<<(unsigned)L[i].cout, 256, 0, s>>>(p, g[k * nl + i].b, B);
                 HIP_TRY(hipGetLastError());
             }
             if (i > 0) {

@@ -3,6 +3,7 @@
 // that a stand-alone program can check it without a device.
 #pragma once
 #include "../../include/genvox_amd.h"
+#include "rounding.h"
 
 #include <cstddef>
 #include <cstdint>
@@ -24,6 +25,7 @@ struct MdLayer {
     int down_in, down_out;   // how many strided layers lie in front of the input / the output: their lengths follow from the row's own n
     int reflect, act;
     size_t w_off, b_off;     // floats, inside one scale's part of the blob
+    size_t wn() const { return (size_t)cout * cig * k; }
 };
 
 // length after `down` strided layers of a row of n samples at this scale (0 stays 0: a refused row is silent)
@@ -32,8 +34,6 @@ MD_HD inline int md_chain(int n, int s, int down) {
     return n;
 }
 
-inline size_t md_round64(size_t floats) { return (floats + 63) & ~(size_t)63; }
-inline size_t md_round256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 inline int md_min_samples(const gvx_melgan_disc_dims& d) { return 8 << (d.n_scales - 1); }
 
 inline const char* md_dims_problem(const gvx_melgan_disc_dims* d) {
@@ -63,9 +63,9 @@ inline int md_layers(const gvx_melgan_disc_dims& d, MdLayer* L, size_t* floats_o
     auto add = [&](int cin, int cout, int k, int stride, int pad, int groups, int down_in, int down_out, int reflect, int act) {
         MdLayer& l = L[n++];
         l = MdLayer{cin, cout, k, stride, pad, groups, cin / groups, cout / groups, down_in, down_out, reflect, act, 0, 0};
-        l.w_off = at; at += md_round64((size_t)cout * l.cig * k);
-        l.b_off = at; at += md_round64((size_t)cout);
-        params += (size_t)cout * l.cig * k + cout;
+        l.w_off = at; at += gvx::round64(l.wn());
+        l.b_off = at; at += gvx::round64((size_t)cout);
+        params += l.wn() + cout;
     };
     int c = d.base_channels;
     add(1, c, 15, 1, 7, 1, 0, 0, 1, 1);
@@ -100,7 +100,7 @@ inline MdFeat md_feat_layout(const gvx_melgan_disc_dims& d, int B, int n_max) {
             F.channels[i] = L[i].cout;
             F.positions[k][i] = md_chain(n_max >> k, d.downsampling_factor, L[i].down_out);
             F.off[k][i] = at;
-            at += md_round256((size_t)B * L[i].cout * F.positions[k][i] * sizeof(float));
+            at += gvx::round256((size_t)B * L[i].cout * F.positions[k][i] * sizeof(float));
         }
     F.total = at;
     return F;
@@ -111,7 +111,7 @@ struct MdPieces { int chunks, rows_per_piece, n; size_t numel; };
 
 inline MdPieces md_pieces(const MdLayer& l, int B, int positions) {
     MdPieces P{};
-    P.numel = (size_t)l.cout * l.cig * l.k;
+    P.numel = l.wn();
     const size_t out_blocks = (P.numel / ((l.cog % 4) ? 1 : 4) + 255) / 256;
     size_t want = (1024 + out_blocks - 1) / out_blocks;            // about 1024 workgroups per launch
     const size_t cap = MD_PART_FLOATS / P.numel ? MD_PART_FLOATS / P.numel : 1;
@@ -138,7 +138,7 @@ struct MdWs {   // byte offsets
 inline MdWs md_ws_plan(const gvx_melgan_disc_dims& d, int B, int n_max, bool backward) {
     MdWs W{};
     size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += md_round256(bytes); return o; };
+    auto take = [&](size_t bytes) { const size_t o = at; at += gvx::round256(bytes); return o; };
     for (int k = 1; k < d.n_scales; ++k) W.pooled[k] = take((size_t)B * (n_max >> k) * sizeof(float));
     if (backward) {
         for (int k = 1; k < d.n_scales; ++k) W.d_pooled[k] = take((size_t)B * (n_max >> k) * sizeof(float));

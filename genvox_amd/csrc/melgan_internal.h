@@ -77,7 +77,7 @@ struct MgBlob {   // offsets in floats
 inline MgBlob mg_blob_layout(const gvx_melgan_dims& d) {
     MgBlob L{};
     size_t at = 0;
-    auto take = [&](size_t floats) { const size_t o = at; at += gen_round64(floats); return o; };
+    auto take = [&](size_t floats) { const size_t o = at; at += gvx::round64(floats); return o; };
     size_t C = d.base_channels;
     L.pre_w = take(C * 7 * mg_cpad(d));
     L.pre_b = take(C);

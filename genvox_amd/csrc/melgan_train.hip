@@ -25,6 +25,7 @@
 //
 // The transposed weights Wt come from the bound blob at the start of every backward call (mgb_transpose_kernel), so they are the
 // weights the forward used.  Order of this file: descriptions, kernels, plans (tape, workspace), launches, the C ABI.
+#include "gen_backward.h"
 #include "melgan_internal.h"
 
 using gvx::fail;
@@ -421,34 +422,9 @@ __global__ void __launch_bounds__(256) mgb_transpose_kernel(float* dst, const fl
     }
 }
 
-// dz = d_wav * (1 - wav^2) inside a row, 0 behind it (d_wav is not read there)
-__global__ void __launch_bounds__(256) mgb_tanh_bwd_kernel(const float* d_wav, const float* wav, const int32_t* lens, int T, int hop, float* dz) {
-    const int b = blockIdx.y;
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long)T * hop) return;
-    const size_t at = (size_t)b * T * hop + idx;
-    float v = 0.f;
-    if (idx < (long)mg_frames(lens, b, T) * hop) {
-        const float w = wav[at];
-        v = d_wav[at] * (1.f - w * w);
-    }
-    dz[at] = v;
-}
-
-// d_mel [B][M][T] from its channels-last form [B][T][Cp]; exactly 0 at and behind a row's frames
-__global__ void __launch_bounds__(256) mgb_dmel_kernel(const float* dmel_t, const int32_t* lens, int M, int T, int Cp, float* d_mel) {
-    const int b = blockIdx.y;
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long)M * T) return;
-    const int t = (int)(idx % T), c = (int)(idx / T);
-    d_mel[(size_t)b * M * T + idx] = t < mg_frames(lens, b, T) ? dmel_t[((size_t)b * T + t) * Cp + c] : 0.f;
-}
-
 // ---- plans
-struct MgTapeSlot { size_t off; int mul, C; };   // offset in floats
-
 struct MgTape {
-    std::vector<MgTapeSlot> slots;   // the transposed mel, x after the first convolution, per stage: the transposed convolution's output, per layer h and x
+    std::vector<GenTapeSlot> slots;   // the transposed mel, x after the first convolution, per stage: the transposed convolution's output, per layer h and x
     size_t floats;
 };
 
@@ -504,7 +480,7 @@ MgbWs mgb_ws_plan(const gvx_melgan_dims& d, int B, int T) {
     need(mul, 1, 1, 7 * C);
     widest = std::max(widest, (size_t)mg_cpad(d));
     size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += gen_round256(bytes); return o; };
+    auto take = [&](size_t bytes) { const size_t o = at; at += gvx::round256(bytes); return o; };
     w.wt = take(w.wt_at.total * sizeof(float));
     w.wav = take((size_t)B * T * hop * sizeof(float));
     w.dz = take((size_t)B * T * hop * sizeof(float));
@@ -590,20 +566,6 @@ int mgb_transpose(float* dst, const float* src, int kind, int Cout, int Cin, int
     return GVX_OK;
 }
 
-float* mgb_grad(const gvx_grad_desc* table, int n, const std::string& name, size_t numel, int& rc) {
-    if (rc != GVX_OK) return nullptr;
-    for (int i = 0; i < n; ++i)
-        if (table[i].name && name == table[i].name) {
-            if (!table[i].data || table[i].numel != (int64_t)numel) {
-                rc = fail(GVX_ERR_SHAPE, "the gradient of %s has %lld elements, the dims ask for %zu", name.c_str(), (long long)table[i].numel, numel);
-                return nullptr;
-            }
-            return table[i].data;
-        }
-    rc = fail(GVX_ERR_MISSING_WEIGHT, "the gradient of %s has no destination", name.c_str());
-    return nullptr;
-}
-
 struct MgbGrads {
     float *pre_w, *pre_b, *post_w, *post_b;
     float *up_w[GVX_MELGAN_MAX_STAGES], *up_b[GVX_MELGAN_MAX_STAGES];
@@ -616,9 +578,7 @@ int mgb_check_call(const gvx_melgan* h, int B, int T, const void* tape, size_t t
     if (B < 1 || B > 65535) return fail(GVX_ERR_INVALID_ARG, "B must be in [1, 65535]");
     if (T < GVX_MELGAN_MIN_FRAMES) return fail(GVX_ERR_INVALID_ARG, "T = %d: the first convolution's reflection needs at least %d frames", T, GVX_MELGAN_MIN_FRAMES);
     if (T > GVX_MELGAN_MAX_FRAMES) return fail(GVX_ERR_UNSUPPORTED, "T = %d is beyond the limit of %d frames", T, GVX_MELGAN_MAX_FRAMES);
-    const size_t need = mgb_tape_plan(h->d, B, T).floats * sizeof(float);
-    if (!tape || (uintptr_t)tape % 256 || tape_bytes < need) return fail(GVX_ERR_WORKSPACE, "the tape is missing, misaligned or smaller than %zu bytes", need);
-    return GVX_OK;
+    return gen_check_tape(tape, tape_bytes, mgb_tape_plan(h->d, B, T).floats * sizeof(float));
 }
 
 }  // namespace
@@ -632,14 +592,7 @@ size_t gvx_melgan_tape_bytes(const gvx_melgan_dims* dims, int B, int T) {
 
 int gvx_melgan_tape_layout(const gvx_melgan_dims* dims, int B, int T, gvx_melgan_tape_entry* entries, int max_entries) {
     if (!mgb_shape_ok(dims, B, T)) return 0;
-    const MgTape t = mgb_tape_plan(*dims, B, T);
-    const int n = (int)t.slots.size();
-    for (int i = 0; entries && i < n && i < max_entries; ++i) {
-        entries[i].byte_offset = t.slots[i].off * sizeof(float);
-        entries[i].positions_per_frame = t.slots[i].mul;
-        entries[i].channels = t.slots[i].C;
-    }
-    return n;
+    return gen_tape_layout(mgb_tape_plan(*dims, B, T).slots, entries, max_entries);
 }
 
 size_t gvx_melgan_backward_workspace_bytes(const gvx_melgan_dims* dims, int B, int T) {
@@ -714,8 +667,7 @@ int gvx_melgan_backward(gvx_melgan* h, const float* d_wav, const int32_t* frame_
     if ((rc = mgb_check_call(h, B, T, tape, tape_bytes)) != GVX_OK) return rc;
     const gvx_melgan_dims& d = h->d;
     const MgbWs wp = mgb_ws_plan(d, B, T);
-    if (!workspace || (uintptr_t)workspace % 256 || workspace_bytes < wp.total)
-        return fail(GVX_ERR_WORKSPACE, "the workspace is missing, misaligned or smaller than %zu bytes", wp.total);
+    if ((rc = gen_check_workspace(workspace, workspace_bytes, wp.total)) != GVX_OK) return rc;
     const int S = d.n_stages, R = d.n_residual_layers, Cp = mg_cpad(d);
     {
         int hop_ = 1;
@@ -725,26 +677,26 @@ int gvx_melgan_backward(gvx_melgan* h, const float* d_wav, const int32_t* frame_
     MgbGrads g{};
     {
         size_t C = d.base_channels;
-        g.pre_w = mgb_grad(grads, n_grads, "pre.weight", C * d.n_mels * 7, rc);
-        g.pre_b = mgb_grad(grads, n_grads, "pre.bias", C, rc);
+        g.pre_w = gen_grad(grads, n_grads, "pre.weight", C * d.n_mels * 7, rc);
+        g.pre_b = gen_grad(grads, n_grads, "pre.bias", C, rc);
         for (int i = 0; i < S; ++i) {
             const size_t Cn = C / 2;
             const std::string up = "ups." + std::to_string(i);
-            g.up_w[i] = mgb_grad(grads, n_grads, up + ".weight", C * Cn * 2 * d.ratios[i], rc);
-            g.up_b[i] = mgb_grad(grads, n_grads, up + ".bias", Cn, rc);
+            g.up_w[i] = gen_grad(grads, n_grads, up + ".weight", C * Cn * 2 * d.ratios[i], rc);
+            g.up_b[i] = gen_grad(grads, n_grads, up + ".bias", Cn, rc);
             for (int j = 0; j < R; ++j) {
                 const std::string res = "res." + std::to_string(i) + "." + std::to_string(j);
-                g.conv_w[i][j] = mgb_grad(grads, n_grads, res + ".conv.weight", Cn * Cn * 3, rc);
-                g.conv_b[i][j] = mgb_grad(grads, n_grads, res + ".conv.bias", Cn, rc);
-                g.sc_w[i][j] = mgb_grad(grads, n_grads, res + ".shortcut.weight", Cn * Cn, rc);
-                g.sc_b[i][j] = mgb_grad(grads, n_grads, res + ".shortcut.bias", Cn, rc);
-                g.mix_w[i][j] = mgb_grad(grads, n_grads, res + ".mix.weight", Cn * Cn, rc);
-                g.mix_b[i][j] = mgb_grad(grads, n_grads, res + ".mix.bias", Cn, rc);
+                g.conv_w[i][j] = gen_grad(grads, n_grads, res + ".conv.weight", Cn * Cn * 3, rc);
+                g.conv_b[i][j] = gen_grad(grads, n_grads, res + ".conv.bias", Cn, rc);
+                g.sc_w[i][j] = gen_grad(grads, n_grads, res + ".shortcut.weight", Cn * Cn, rc);
+                g.sc_b[i][j] = gen_grad(grads, n_grads, res + ".shortcut.bias", Cn, rc);
+                g.mix_w[i][j] = gen_grad(grads, n_grads, res + ".mix.weight", Cn * Cn, rc);
+                g.mix_b[i][j] = gen_grad(grads, n_grads, res + ".mix.bias", Cn, rc);
             }
             C = Cn;
         }
-        g.post_w = mgb_grad(grads, n_grads, "post.weight", 7 * C, rc);
-        g.post_b = mgb_grad(grads, n_grads, "post.bias", 1, rc);
+        g.post_w = gen_grad(grads, n_grads, "post.weight", 7 * C, rc);
+        g.post_b = gen_grad(grads, n_grads, "post.bias", 1, rc);
         if (rc != GVX_OK) return rc;   // nothing was launched
     }
     hipStream_t s = (hipStream_t)stream;
@@ -794,7 +746,7 @@ int gvx_melgan_backward(gvx_melgan* h, const float* d_wav, const int32_t* frame_
         p.src0 = x_last; p.W = blob + L.post_w; p.bias = blob + L.post_b; p.out = wav;
         p.in_mul = hop; p.Cin = C_last; p.Cout = 1; p.taps = 7; p.K = 7 * C_last; p.dil = 1; p.phases = 1; p.act_mask = 0x7f; p.tanh_out = 1;
         if ((rc = mg_launch(p, B, s)) != GVX_OK) return rc;
-        mgb_tanh_bwd_kernel<<<dim3((unsigned)(((long)T * hop + 255) / 256), (unsigned)B), 256, 0, s>>>(d_wav, wav, frame_lengths, T, hop, dz);
+        gen_tanh_bwd_kernel<GVX_MELGAN_MIN_FRAMES><<<dim3((unsigned)(((long)T * hop + 255) / 256), (unsigned)B), 256, 0, s>>>(d_wav, wav, frame_lengths, T, hop, dz);
         HIP_TRY(hipGetLastError());
         w = MgbW{p, dz, 1, part, B};
         if ((rc = mgb_wgrad(w, pieces, s)) != GVX_OK) return rc;
@@ -869,7 +821,7 @@ int gvx_melgan_backward(gvx_melgan* h, const float* d_wav, const int32_t* frame_
             dg.dy = G; dg.ldy = C; dg.Wt = wt + L.pre_w; dg.out = G2; dg.ldo = Cp;
             dg.in_mul = 1; dg.N = Cp; dg.Cy = C; dg.taps = 7; dg.K = 7 * C; dg.dil = 1;
             if ((rc = mgb_dgrad(dg, B, s)) != GVX_OK) return rc;
-            mgb_dmel_kernel<<<dim3((unsigned)(((long)d.n_mels * T + 255) / 256), (unsigned)B), 256, 0, s>>>(G2, frame_lengths, d.n_mels, T, Cp, d_mel_out);
+            gen_dmel_kernel<GVX_MELGAN_MIN_FRAMES><<<dim3((unsigned)(((long)d.n_mels * T + 255) / 256), (unsigned)B), 256, 0, s>>>(G2, frame_lengths, d.n_mels, T, Cp, d_mel_out);
             HIP_TRY(hipGetLastError());
         }
     }

@@ -692,7 +692,7 @@ int gvx_mrd_layer_times_ms(gvx_mrd* h, float* forward_ms, float* backward_ms, in
     return dc_layer_times_ms(h, h ? h->d.n_resolutions : 0, h ? MR_MAPS : 0, forward_ms, backward_ms, n_layers_out);
 }
 
-int gvx_mrd_bind(gvx_mrd* h, const float* device_blob) { return dc_bind(h, device_blob); }
+int gvx_mrd_bind(gvx_mrd* h, const float* device_blob) { return gen_bind(h, device_blob); }
 
 int gvx_mrd_forward(gvx_mrd* h, const float* wav, const int32_t* sample_lengths, int B, int n_max, void* features, size_t features_bytes,
                     void* workspace, size_t workspace_bytes, void* stream) {
@@ -702,14 +702,14 @@ int gvx_mrd_forward(gvx_mrd* h, const float* wav, const int32_t* sample_lengths,
     const MrFeat F = mr_feat_layout(d, B, n_max);
     if ((rc = dc_check_features(features, features_bytes, F.total)) != GVX_OK) return rc;
     const MrWs wp = mr_ws_plan(d, B, n_max, false);
-    if ((rc = dc_check_workspace(workspace, workspace_bytes, wp.total)) != GVX_OK) return rc;
+    if ((rc = gen_check_workspace(workspace, workspace_bytes, wp.total)) != GVX_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     MrLayer L[MR_MAPS];
     size_t per_res = 0;
     const int nl = mr_layers(d, L, &per_res);
     float* mag = gvx::ws_ptr<float>(workspace, wp.mag);
     for (int r = 0; r < d.n_resolutions; ++r) {
-        if ((rc = dc_mark(h, h->fwd_ev, (size_t)r * (nl + 1), s)) != GVX_OK) return rc;
+        if ((rc = dc_mark(h, h->marks, (size_t)r * (nl + 1), s)) != GVX_OK) return rc;
         if ((rc = mr_launch_spec(mr_spec(h, per_res, r, sample_lengths, n_max), d.n_fft[r], wav, B, mag, nullptr, nullptr, s)) != GVX_OK) return rc;
         const float* in = mag;
         for (int i = 0; i < nl; ++i) {
@@ -718,7 +718,7 @@ int gvx_mrd_forward(gvx_mrd* h, const float* wav, const int32_t* sample_lengths,
             p.out = gvx::ws_ptr<float>(features, F.off[r][i]);
             if ((rc = mr_launch_conv<false>(p, B, s)) != GVX_OK) return rc;
             in = p.out;
-            if ((rc = dc_mark(h, h->fwd_ev, (size_t)r * (nl + 1) + i + 1, s)) != GVX_OK) return rc;
+            if ((rc = dc_mark(h, h->marks, (size_t)r * (nl + 1) + i + 1, s)) != GVX_OK) return rc;
         }
     }
     h->fwd_timed = h->timing;
@@ -734,7 +734,7 @@ int gvx_mrd_backward(gvx_mrd* h, const float* wav, const int32_t* sample_lengths
     const gvx_mrd_dims& d = h->d;
     const MrFeat F = mr_feat_layout(d, B, n_max);
     const MrWs wp = mr_ws_plan(d, B, n_max, true);
-    if ((rc = dc_check_workspace(workspace, workspace_bytes, wp.total)) != GVX_OK) return rc;
+    if ((rc = gen_check_workspace(workspace, workspace_bytes, wp.total)) != GVX_OK) return rc;
     MrLayer L[MR_MAPS];
     size_t per_res = 0;
     const int nl = mr_layers(d, L, &per_res);
@@ -752,7 +752,7 @@ int gvx_mrd_backward(gvx_mrd* h, const float* wav, const int32_t* sample_lengths
         const float* blob = h->blob + r * per_res;
         const MrSpec sp = mr_spec(h, per_res, r, sample_lengths, n_max);
         const float* dcur = feat(d_features, r, nl - 1);   // the score has no activation: its cotangent is its pre-activation's
-        if ((rc = dc_mark(h, h->bwd_ev, (size_t)r * (nl + 1) + nl, s)) != GVX_OK) return rc;
+        if ((rc = dc_mark(h, h->bwd_marks, (size_t)r * (nl + 1) + nl, s)) != GVX_OK) return rc;
         if (n_grads > 0 && (rc = mr_launch_spec(sp, d.n_fft[r], wav, B, mag, nullptr, nullptr, s)) != GVX_OK) return rc;   // the first layer's operand
         for (int i = nl - 1; i >= 0; --i) {
             MrConv p = mr_conv(d, L[i], F, r, i, sample_lengths, n_max);
@@ -784,7 +784,7 @@ int gvx_mrd_backward(gvx_mrd* h, const float* wav, const int32_t* sample_lengths
                 mr_dwav_kernel<<<dim3((unsigned)((n_max + 255) / 256), (unsigned)B), 256, 0, s>>>(sp, d.n_fft[r], frame_grads, d_wav, r > 0);
                 HIP_TRY(hipGetLastError());
             }
-            if ((rc = dc_mark(h, h->bwd_ev, (size_t)r * (nl + 1) + i, s)) != GVX_OK) return rc;   // mark i: layer i is done
+            if ((rc = dc_mark(h, h->bwd_marks, (size_t)r * (nl + 1) + i, s)) != GVX_OK) return rc;   // mark i: layer i is done
         }
     }
     h->bwd_timed = h->timing;

@@ -73,9 +73,9 @@ inline int mr_layers(const gvx_mrd_dims& d, MrLayer* L, size_t* floats_out = nul
         MrLayer& l = L[i];
         const int kt = i < 4 ? 9 : 3;
         l = MrLayer{i == 0 ? 1 : C, i == MR_MAPS - 1 ? 1 : C, kt, mr_stride(i), kt / 2, i < MR_MAPS - 1, i > 0 && i < MR_MAPS - 1, 0, 0, 0};
-        l.wf_off = at; at += dc_round64(l.wn());
-        l.wb_off = at; at += dc_round64(l.wn());
-        l.b_off = at; at += dc_round64((size_t)l.cout);
+        l.wf_off = at; at += gvx::round64(l.wn());
+        l.wb_off = at; at += gvx::round64(l.wn());
+        l.b_off = at; at += gvx::round64((size_t)l.cout);
     }
     if (floats_out) *floats_out = at;
     return MR_MAPS;
@@ -83,13 +83,13 @@ inline int mr_layers(const gvx_mrd_dims& d, MrLayer* L, size_t* floats_out = nul
 
 // behind the resolutions' weights the blob holds, per resolution, the padded window [n_fft], w_H^m [H] and w_N^k [H + 1] as float2
 struct MrTables { size_t win, tw, tw2; };
-inline size_t mr_table_floats(int n_fft) { return dc_round64((size_t)n_fft) + dc_round64((size_t)n_fft) + dc_round64((size_t)n_fft + 2); }
+inline size_t mr_table_floats(int n_fft) { return gvx::round64((size_t)n_fft) + gvx::round64((size_t)n_fft) + gvx::round64((size_t)n_fft + 2); }
 inline MrTables mr_tables(const gvx_mrd_dims& d, size_t per_res, int r) {
     size_t at = per_res * d.n_resolutions;
     for (int q = 0; q < r; ++q) at += mr_table_floats(d.n_fft[q]);
     MrTables T{};
-    T.win = at; at += dc_round64((size_t)d.n_fft[r]);
-    T.tw = at; at += dc_round64((size_t)d.n_fft[r]);
+    T.win = at; at += gvx::round64((size_t)d.n_fft[r]);
+    T.tw = at; at += gvx::round64((size_t)d.n_fft[r]);
     T.tw2 = at;
     return T;
 }
@@ -129,7 +129,7 @@ inline MrFeat mr_feat_layout(const gvx_mrd_dims& d, int B, int n_max) {
             F.channels[i] = L[i].cout;
             F.frames[r][i] = mr_width(n_max, d.n_fft[r], d.hop[r], i + 1);
             F.off[r][i] = at;
-            at += dc_round256((size_t)B * F.frames[r][i] * F.bins[r] * L[i].cout * sizeof(float));
+            at += gvx::round256((size_t)B * F.frames[r][i] * F.bins[r] * L[i].cout * sizeof(float));
         }
     }
     F.total = at < 256 ? 256 : at;
@@ -159,7 +159,7 @@ struct MrWs { size_t mag, dmag, g, grad[2], parts, db_parts, total; };
 inline MrWs mr_ws_plan(const gvx_mrd_dims& d, int B, int n_max, bool backward) {
     MrWs W{};
     size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += dc_round256(bytes); return o; };
+    auto take = [&](size_t bytes) { const size_t o = at; at += gvx::round256(bytes); return o; };
     MrLayer L[MR_MAPS];
     mr_layers(d, L);
     const MrFeat F = mr_feat_layout(d, B, n_max);

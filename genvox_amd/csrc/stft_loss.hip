@@ -8,11 +8,12 @@
 //
 // Order of this file: kernels, workspace layout, the C ABI.
 #include "fft_lds.h"
-#include "gvx_internal.h"
+#include "stft_plan.h"
 
 #include <algorithm>
 
 using gvx::fail;
+using namespace gvx_plan;
 
 struct gvx_stft_loss_plan {
     int R = 0;
@@ -278,25 +279,22 @@ struct SlLayout {
     size_t coef, terms, total;
 };
 
-inline size_t sl_round256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-
 SlLayout sl_layout(const gvx_stft_loss_plan* p, int B, long n_max) {
     SlLayout L{};
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += sl_round256(bytes); return o; };
+    StftRegions ws;
     for (int r = 0; r < p->R; ++r) {
         const size_t N = (size_t)p->res[r].n_fft, bins = N / 2 + 1;
         L.f_max[r] = (int)(1 + n_max / p->res[r].hop);
         L.nwg[r] = (L.f_max[r] + SL_FRAMES - 1) / SL_FRAMES;
         const size_t frames = (size_t)B * L.f_max[r];
-        L.X[r] = take(frames * bins * sizeof(float2));
-        L.Mt[r] = take(frames * bins * sizeof(float));
-        L.g[r] = take(frames * N * sizeof(float));
-        L.part[r] = take((size_t)B * L.nwg[r] * 3 * sizeof(double));
+        L.X[r] = ws.take(frames * bins * sizeof(float2));
+        L.Mt[r] = ws.take(frames * bins * sizeof(float));
+        L.g[r] = ws.take(frames * N * sizeof(float));
+        L.part[r] = ws.take((size_t)B * L.nwg[r] * 3 * sizeof(double));
     }
-    L.coef = take((size_t)B * p->R * sizeof(float2));
-    L.terms = take((size_t)B * p->R * sizeof(double));
-    L.total = at;
+    L.coef = ws.take((size_t)B * p->R * sizeof(float2));
+    L.terms = ws.take((size_t)B * p->R * sizeof(double));
+    L.total = ws.total;
     return L;
 }
 
@@ -305,16 +303,6 @@ const char* sl_shape_problem(const gvx_stft_loss_plan* p, int B, long n_max) {
     if (B < 1 || B > GVX_STFT_LOSS_MAX_ROWS) return "B must be in [1, GVX_STFT_LOSS_MAX_ROWS]";
     if (n_max < 1 || n_max > GVX_STFT_LOSS_MAX_SAMPLES) return "n_max must be in [1, GVX_STFT_LOSS_MAX_SAMPLES]";
     return nullptr;
-}
-
-template <int H>
-int sl_launch_res(bool grad_pass, const float* pred, const float* target, const int32_t* lens, int B, long n_max, int n_min, float eps,
-                  const float2* coef, const SlRes& r, hipStream_t s) {
-    const dim3 grid((unsigned)r.nwg, (unsigned)B);
-    if (grad_pass) sl_grad_kernel<H><<<grid, SL_FRAMES * 64, 0, s>>>(lens, n_max, n_min, eps, coef, r);
-    else sl_forward_kernel<H><<<grid, SL_FRAMES * 64, 0, s>>>(pred, target, lens, n_max, n_min, eps, r);
-    HIP_TRY(hipGetLastError());
-    return GVX_OK;
 }
 
 }  // namespace
@@ -338,23 +326,14 @@ int gvx_stft_loss_create(const gvx_stft_resolution* res, int R, float w_sc, floa
     gvx_stft_loss_plan* p = new gvx_stft_loss_plan();
     p->R = R; p->w_sc = w_sc; p->w_mag = w_mag; p->eps = eps;
     std::vector<float> h;
-    const double two_pi = 6.283185307179586476925286766559;
     for (int r = 0; r < R; ++r) {
         p->res[r] = res[r];
-        const int N = res[r].n_fft, H = N / 2, wl = res[r].win_length, off = (N - wl) / 2;
-        p->n_min = std::max(p->n_min, H + 1);
-        p->win_at[r] = h.size();
-        h.resize(h.size() + N, 0.f);
-        for (int k = 0; k < wl; ++k) h[p->win_at[r] + off + k] = (float)(0.5 - 0.5 * std::cos(two_pi * k / wl));
-        p->tw_at[r] = h.size();
-        for (int m = 0; m < H; ++m) { h.push_back((float)std::cos(two_pi * m / H)); h.push_back((float)-std::sin(two_pi * m / H)); }
-        p->tw2_at[r] = h.size();
-        for (int k = 0; k <= H; ++k) { h.push_back((float)std::cos(two_pi * k / N)); h.push_back((float)-std::sin(two_pi * k / N)); }
+        p->n_min = std::max(p->n_min, res[r].n_fft / 2 + 1);
+        const StftTables t = stft_tables(h, res[r].n_fft, res[r].win_length);
+        p->win_at[r] = t.win; p->tw_at[r] = t.tw; p->tw2_at[r] = t.tw2;
         h.resize((h.size() + 3) & ~(size_t)3, 0.f);   // the next table starts on 16 bytes
     }
-    if (hipMalloc(&p->tables, h.size() * sizeof(float)) != hipSuccess ||
-        hipMemcpy(p->tables, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-        if (p->tables) (void)hipFree(p->tables);
+    if (!stft_upload(&p->tables, h)) {
         delete p;
         return fail(GVX_ERR_HIP, "window and twiddle table allocation failed");
     }
@@ -381,8 +360,7 @@ int gvx_stft_loss(gvx_stft_loss_plan* p, const float* pred, const float* target,
     if (n_max < p->n_min)
         return fail(GVX_ERR_SHAPE, "n_max = %ld: a row needs at least n_fft / 2 + 1 = %d samples for the reflection", n_max, p->n_min);
     const SlLayout L = sl_layout(p, B, n_max);
-    if (!workspace || ((uintptr_t)workspace & 255)) return fail(GVX_ERR_WORKSPACE, "the workspace must be non-null and 256-byte aligned");
-    if (workspace_bytes < L.total) return fail(GVX_ERR_WORKSPACE, "workspace too small: %zu bytes, %zu needed", workspace_bytes, L.total);
+    if (const int rc = stft_check_workspace(workspace, workspace_bytes, L.total)) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     char* ws = reinterpret_cast<char*>(workspace);
     const bool grad = d_pred != nullptr;
@@ -410,12 +388,14 @@ int gvx_stft_loss(gvx_stft_loss_plan* p, const float* pred, const float* target,
     red.parts = parts_out; red.coef = coef; red.terms = reinterpret_cast<double*>(ws + L.terms); red.loss = loss_out;
     auto pass = [&](bool grad_pass) {
         for (int r = 0; r < p->R; ++r) {
-            int rc;
-            switch (p->res[r].n_fft) {
-                case 512: rc = sl_launch_res<256>(grad_pass, pred, target, sample_lengths, B, n_max, p->n_min, p->eps, coef, rr[r], s); break;
-                case 1024: rc = sl_launch_res<512>(grad_pass, pred, target, sample_lengths, B, n_max, p->n_min, p->eps, coef, rr[r], s); break;
-                default: rc = sl_launch_res<1024>(grad_pass, pred, target, sample_lengths, B, n_max, p->n_min, p->eps, coef, rr[r], s); break;
-            }
+            const int rc = stft_dispatch(p->res[r].n_fft, [&](auto h) -> int {
+                constexpr int H = decltype(h)::value;
+                const dim3 grid((unsigned)rr[r].nwg, (unsigned)B);
+                if (grad_pass) sl_grad_kernel<H><<<grid, SL_FRAMES * 64, 0, s>>>(sample_lengths, n_max, p->n_min, p->eps, coef, rr[r]);
+                else sl_forward_kernel<H><<<grid, SL_FRAMES * 64, 0, s>>>(pred, target, sample_lengths, n_max, p->n_min, p->eps, rr[r]);
+                HIP_TRY(hipGetLastError());
+                return GVX_OK;
+            });
             if (rc != GVX_OK) return rc;
         }
         return (int)GVX_OK;
@@ -431,19 +411,7 @@ int gvx_stft_loss(gvx_stft_loss_plan* p, const float* pred, const float* target,
                                                                                                                 d_pred);
         HIP_TRY(hipGetLastError());
     }
-    if (sample_lengths) {
-        // the rows' lengths live on the device: the kernels above gave a refused row no frames (NaN parts, NaN loss, zero gradient), and
-        // the host learns of it here, behind the launches, so that its wait overlaps their run
-        std::vector<int32_t> host(B);
-        HIP_TRY(hipMemcpyAsync(host.data(), sample_lengths, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        for (int b = 0; b < B; ++b) {
-            if (host[b] >= p->n_min && host[b] <= n_max) continue;
-            if (grad) HIP_TRY(hipMemsetAsync(d_pred, 0, (size_t)B * n_max * sizeof(float), s));
-            return fail(GVX_ERR_SHAPE, "row %d has %d samples: outside [n_fft / 2 + 1 = %d, n_max = %ld]", b, host[b], p->n_min, n_max);
-        }
-    }
-    return GVX_OK;
+    return stft_check_lengths(sample_lengths, B, n_max, p->n_min, "n_fft / 2 + 1", d_pred, s);
 }
 
 }  // extern "C"

@@ -279,7 +279,7 @@ struct UnBlob {
 UnBlob un_blob_layout(const gvx_univnet_dims& d) {
     UnBlob L{};
     size_t at = 0;
-    auto take = [&](size_t floats) { const size_t o = at; at += gen_round64(floats); return o; };
+    auto take = [&](size_t floats) { const size_t o = at; at += gvx::round64(floats); return o; };
     const size_t C = d.channel_size, H = d.kpnet_hidden_channels, ld = un_ld(d.channel_size, d.n_dilations);
     L.pre_w = take(C * 7 * un_np(d)); L.pre_b = take(C);
     for (int i = 0; i < d.n_blocks; ++i) {

@@ -305,7 +305,7 @@ struct VcBlob {
 VcBlob vc_blob_layout(const gvx_vocos_dims& d) {
     VcBlob L{};
     size_t at = 0;
-    auto take = [&](size_t floats) { const size_t o = at; at += gen_round64(floats); return o; };
+    auto take = [&](size_t floats) { const size_t o = at; at += gvx::round64(floats); return o; };
     const size_t C = d.dim, I = d.intermediate_dim, N = d.n_fft;
     L.embed_w = take(C * 7 * vc_cpad(d)); L.embed_b = take(C); L.norm_w = take(C); L.norm_b = take(C);
     for (int i = 0; i < d.num_layers; ++i) {
@@ -374,7 +374,7 @@ int gvx_dwconv_layernorm(const float* x, const int32_t* lens, int B, int T, int 
 
 size_t gvx_istft_head_workspace_bytes(int B, int T, int n_fft) {
     if (vc_shape_problem(B, T) || vc_fft_problem(n_fft, n_fft / 2, 0)) return 0;
-    return gen_round256((size_t)B * T * n_fft * sizeof(float)) + gen_round256((size_t)(n_fft + 1) * sizeof(float2));
+    return gvx::round256((size_t)B * T * n_fft * sizeof(float)) + gvx::round256((size_t)(n_fft + 1) * sizeof(float2));
 }
 
 int gvx_istft_head(const float* coeffs, const int32_t* lens, int B, int T, int n_fft, int hop, int center, const float* window, void* workspace,
@@ -389,7 +389,7 @@ int gvx_istft_head(const float* coeffs, const int32_t* lens, int B, int T, int n
     VcIstft a{};
     a.coeffs = coeffs; a.lens = lens; a.T = T; a.win = window;
     a.frames = static_cast<float*>(workspace);
-    float2* tw = gvx::ws_ptr<float2>(workspace, gen_round256((size_t)B * T * n_fft * sizeof(float)));
+    float2* tw = gvx::ws_ptr<float2>(workspace, gvx::round256((size_t)B * T * n_fft * sizeof(float)));
     a.tw = tw; a.tw2 = tw + H;
     vc_tables_kernel<<<(unsigned)(n_fft / 256 + 1), 256, 0, s>>>(nullptr, tw, tw + H, n_fft);
     HIP_TRY(hipGetLastError());
