@@ -300,6 +300,7 @@ SIGNATURES = {
     "gvx_vocos_timing_enable": (_i, [_vp, _i]),
     "gvx_vocos_stage_times_ms": (_i, [_vp, C.POINTER(_f), C.POINTER(_i)]),
     "gvx_self_attention": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "gvx_add_layer_norm": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "gvx_fastpitch_blob_floats": (_sz, [C.POINTER(gvx_fastpitch_dims)]),
     "gvx_fastpitch_workspace_bytes": (_sz, [C.POINTER(gvx_fastpitch_dims), _i, _i]),
     "gvx_fastpitch_pack_weights_device": (_i, [C.POINTER(gvx_fastpitch_dims), C.POINTER(gvx_weight_desc), _i, _vp, _vp]),

@@ -39,7 +39,7 @@ namespace {
 typedef __attribute__((ext_vector_type(16))) float fp_f32x16;
 
 constexpr int FP_WAVES = 4;
-constexpr int FP_P = 16;             // positions per workgroup of the LayerNorm kernel
+constexpr int FP_P = GVX_ADD_LN_POSITIONS;             // positions per workgroup of the LayerNorm kernel
 constexpr float FP_LN_EPS = 1e-5f;
 constexpr int FP_BQ = GVX_ATTN_Q_TILE, FP_BK = GVX_ATTN_K_TILE;
 
@@ -612,6 +612,25 @@ int gvx_self_attention(const float* qkv, const int32_t* lens, int B, int T, int 
     if (n_head < 1 || n_head > GVX_FASTPITCH_MAX_HEADS) return fail(GVX_ERR_INVALID_ARG, "n_head = %d must be in [1, %d]", n_head, (int)GVX_FASTPITCH_MAX_HEADS);
     if (((uintptr_t)qkv | (uintptr_t)out) & 15) return fail(GVX_ERR_INVALID_ARG, "qkv and out must be 16-byte aligned");
     return fp_attention(qkv, lens, B, T, n_head, d_head, out, (hipStream_t)stream);
+}
+
+int gvx_add_layer_norm(const float* x, const float* y, const int32_t* lens, int B, int N, int C, const float* ln_w, const float* ln_b, float* out_haloed,
+                       float* out_plain, void* stream) {
+    if (!x || !ln_w || !ln_b || !out_haloed) return fail(GVX_ERR_INVALID_ARG, "null argument");
+    if (C < 32 || C > GVX_FASTPITCH_MAX_DIM || C % 32) return fail(GVX_ERR_INVALID_ARG, "C = %d must be a multiple of 32 in [32, %d]", C, (int)GVX_FASTPITCH_MAX_DIM);
+    if (const char* why = fp_shape_problem(B, N)) return fail(GVX_ERR_INVALID_ARG, "%s", why);
+    const size_t plain = (size_t)B * N * C, haloed = (size_t)B * (N + 2) * C;
+    auto overlap = [](const float* a, size_t na, const float* b, size_t nb) { return a && b && (uintptr_t)a < (uintptr_t)(b + nb) && (uintptr_t)b < (uintptr_t)(a + na); };
+    const float* const outs[2] = {out_haloed, out_plain};
+    const size_t out_n[2] = {haloed, plain};
+    for (int i = 0; i < 2; ++i)
+        if (overlap(outs[i], out_n[i], x, plain) || overlap(outs[i], out_n[i], y, plain) || overlap(outs[i], out_n[i], ln_w, (size_t)C) ||
+            overlap(outs[i], out_n[i], ln_b, (size_t)C))
+            return fail(GVX_ERR_INVALID_ARG, "an output overlaps an input");
+    if (overlap(out_haloed, haloed, out_plain, plain)) return fail(GVX_ERR_INVALID_ARG, "out_haloed and out_plain overlap");
+    FpNorm p{};
+    p.x = x; p.x_bs = (long)N * C; p.y = y; p.lens = lens; p.N = N; p.C = C; p.ln_w = ln_w; p.ln_b = ln_b; p.out = out_haloed; p.out2 = out_plain;
+    return fp_norm(p, B, (hipStream_t)stream);
 }
 
 size_t gvx_fastpitch_blob_floats(const gvx_fastpitch_dims* dims) {

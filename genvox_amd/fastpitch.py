@@ -20,7 +20,7 @@ rate control, pitch tracking, every vocoder - works unchanged."""
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Tuple
 
 import torch
 from torch import nn
@@ -31,6 +31,7 @@ from .configs import AudioConfig, BaseConfig, FastPitchConfig, TextConfig
 
 Q_TILE, K_TILE = 128, 64   # GVX_ATTN_Q_TILE, GVX_ATTN_K_TILE: queries per workgroup, keys per LDS tile
 LN_EPS = 1e-5
+LN_POSITIONS, MAX_DIM = 16, 512   # GVX_ADD_LN_POSITIONS: positions per workgroup of the LayerNorm kernel; GVX_FASTPITCH_MAX_DIM
 PACE_MIN, PACE_MAX = 0.125, 8.0
 
 
@@ -60,6 +61,44 @@ def self_attention(qkv: torch.Tensor, lengths=None, n_head: int = 1, d_head: int
     _lib.check(_lib.load().gvx_self_attention(qkv.data_ptr(), _ptr(lens), B, T, int(n_head), int(d_head), out.data_ptr(),
                                               torch.cuda.current_stream(dev).cuda_stream))
     return out
+
+
+def add_layernorm(x: torch.Tensor, ln_weight: torch.Tensor, ln_bias: torch.Tensor, y: Optional[torch.Tensor] = None, lengths=None,
+                  out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The residual + LayerNorm launch on its own (gvx_add_layer_norm): x and ``y`` (or None) float32 [B, N, C] on the device,
+    ``ln_weight`` and ``ln_bias`` float32 [C] on the device -> ``(haloed, plain)``: ``LN(x + y) * ln_weight + ln_bias`` with eps 1e-5 as
+    [B, N + 2, C] between two rows of exact zeros (the layout the k-tap products read) and as [B, N, C], the same bits.  ``C`` must be a
+    multiple of 32 in [32, MAX_DIM].  ``lengths`` ([B], host or device): every row at its own length - bit for bit that row run alone;
+    both results are exact zeros at and behind a row's length, and ``x`` and ``y`` are never read there.  ``out``: the two tensors to
+    write, every element of them."""
+    if x.dim() != 3 or x.device.type != "cuda" or x.dtype != torch.float32:
+        raise ValueError(f"x must be float32 [B, N, C] on the device, got {x.dtype} {tuple(x.shape)} on {x.device}")
+    B, N, Cm = x.shape
+    dev = x.device
+    if B < 1 or N < 1 or Cm < 32 or Cm > MAX_DIM or Cm % 32:
+        raise ValueError(f"x is {tuple(x.shape)}: B and N must be >= 1 and C a multiple of 32 in [32, {MAX_DIM}]")
+    if y is not None and (y.shape != x.shape or y.dtype != torch.float32 or y.device != dev):
+        raise ValueError(f"y must be float32 {tuple(x.shape)} on {dev}, got {y.dtype} {tuple(y.shape)} on {y.device}")
+    for name, t in (("ln_weight", ln_weight), ("ln_bias", ln_bias)):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != (Cm,) or t.dtype != torch.float32 or t.device != dev:
+            raise ValueError(f"{name} must be a float32 tensor [{Cm}] on {dev}")
+    lens = None
+    if lengths is not None:
+        host = [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+        if len(host) != B or any(not 0 <= n <= N for n in host):
+            raise ValueError(f"lengths must be {B} values in [0, {N}]")
+        lens = torch.tensor(host, dtype=torch.int32, device=dev)
+    x, y = x.contiguous(), None if y is None else y.contiguous()
+    lw, lb = ln_weight.detach().contiguous(), ln_bias.detach().contiguous()
+    if out is None:
+        out = (torch.empty(B, N + 2, Cm, dtype=torch.float32, device=dev), torch.empty(B, N, Cm, dtype=torch.float32, device=dev))
+    haloed, plain = out
+    for t, shape in ((haloed, (B, N + 2, Cm)), (plain, (B, N, Cm))):
+        if tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"out must be contiguous float32 [{B}, {N + 2}, {Cm}] and [{B}, {N}, {Cm}] on {dev}")
+    _lib.check(_lib.load().gvx_add_layer_norm(x.data_ptr(), _ptr(y), _ptr(lens), B, N, Cm, lw.data_ptr(), lb.data_ptr(), haloed.data_ptr(),
+                                              plain.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+    return haloed, plain
 
 
 def dims_from_config(mc: FastPitchConfig, ac: AudioConfig, n_tokens: int) -> _lib.gvx_fastpitch_dims:
@@ -303,8 +342,8 @@ class FastPitch(DeviceModule):
         [B, n_mels, T], exact zeros behind a row's frames), ``gate_outputs`` [B, T] (-1e3 on a row's frames but its last, +1e3 on the last
         and behind), ``alignments`` [B, T, L] (the exact 0 / 1 matrix of the durations), ``mel_lengths`` int32 [B] for B > 1 - and
         ``durations`` int32 [B, L] (the frames every token got, after ``pace``, ``min_token_frames`` and the cut at
-        ``max_decoder_steps``), ``log_durations``, ``pitch_pred`` and ``energy_pred`` float32 [B, L].  ``attention_window`` raises
-        ValueError.  The call waits for the device once, for the frame counts."""
+        ``max_decoder_steps``), ``log_durations``, ``pitch_pred`` and ``energy_pred`` float32 [B, L].  A token id outside
+        ``[0, n_tokens)`` is read as id 0.  ``attention_window`` raises ValueError.  The call waits for the device once, for the frame counts."""
         return self._run(inputs)
 
     def forward(self, inputs: Dict) -> Dict[str, torch.Tensor]:

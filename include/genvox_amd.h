@@ -2087,6 +2087,16 @@ int gvx_denoise(gvx_denoise_plan* plan, const float* wav, const int32_t* sample_
  * as zeros.  The order of the sum over keys is the tile walk's: the same row gives the same bits whatever B and T are.  No atomics.
  * D must be 32 or 64, H in [1, GVX_FASTPITCH_MAX_HEADS], B in [1, 65535], T in [1, GVX_FASTPITCH_MAX_POSITIONS]; qkv and out 16-byte aligned.
  *
+ * gvx_add_layer_norm is the residual + LayerNorm on its own, the launch both LNs of a layer and every predictor layer are: x fp32
+ * [B][N][C], y fp32 [B][N][C] or NULL, lens int32 [B] on the device or NULL, ln_w and ln_b fp32 [C] -> out_haloed fp32 [B][N + 2][C], position
+ * t of a row at row t + 1 between two rows of exact zeros (the layout the k-tap products read), and out_plain fp32 [B][N][C] or NULL, the
+ * same bits without the halo rows.  out[t] = LN(x[t] + y[t]) * ln_w + ln_b with eps 1e-5; a wave per position, lanes along the channels,
+ * the mean, the mean of what is left and the squared deviations as butterflies, GVX_ADD_LN_POSITIONS = 16 positions per workgroup.
+ * Positions at or behind N_b are written as zeros in both outputs, and x and y are never read there.  A position depends on nothing but
+ * itself: the same row gives the same bits whatever B and N are.  Refused before any launch (GVX_ERR_INVALID_ARG, with the reason): a
+ * NULL x, ln_w, ln_b or out_haloed; C that is not a multiple of 32 in [32, GVX_FASTPITCH_MAX_DIM]; B outside [1, 65535], N outside
+ * [1, GVX_FASTPITCH_MAX_POSITIONS] or B N beyond 2^24; an output that overlaps x, y, ln_w, ln_b or the other output.
+ *
  * Weights.  gvx_fastpitch_pack_weights_device copies DEVICE tensors by name into the blob, every tensor starting at a multiple of 64
  * floats: encoder.word_emb.weight [n_tokens][C]; per stack and layer dec_attn.qkv_net.weight [3 H D][C], .bias, dec_attn.o_net.weight
  * [C][H D], dec_attn.layer_norm.weight, .bias, pos_ff.CoreNet.0.weight [I][k][C] and pos_ff.CoreNet.2.weight [C][k][I] (TAP-major rows:
@@ -2107,7 +2117,7 @@ int gvx_denoise(gvx_denoise_plan* plan, const float* wav, const int32_t* sample_
  * T); any contents when a call starts, nothing is cleared.  gvx_fastpitch_stage_times_ms: four durations - embedding + encoder,
  * predictors + plan + regulator, decoder, projection.  Every dims field is checked: a bad one gives blob_floats == 0 and
  * create == GVX_ERR_INVALID_ARG with the reason.  There is no backward. */
-enum { GVX_ATTN_Q_TILE = 128, GVX_ATTN_K_TILE = 64, GVX_FASTPITCH_MAX_DIM = 512, GVX_FASTPITCH_MAX_INNER = 8192, GVX_FASTPITCH_MAX_LAYERS = 32,
+enum { GVX_ATTN_Q_TILE = 128, GVX_ATTN_K_TILE = 64, GVX_ADD_LN_POSITIONS = 16, GVX_FASTPITCH_MAX_DIM = 512, GVX_FASTPITCH_MAX_INNER = 8192, GVX_FASTPITCH_MAX_LAYERS = 32,
        GVX_FASTPITCH_MAX_HEADS = 16, GVX_FASTPITCH_MAX_TOKENS = 4096, GVX_FASTPITCH_MAX_POSITIONS = 1 << 16 };
 typedef struct gvx_fft_stack_dims {
     int32_t n_layers;      /* in [1, GVX_FASTPITCH_MAX_LAYERS] */
@@ -2131,6 +2141,8 @@ typedef struct gvx_fastpitch_dims {
 } gvx_fastpitch_dims;
 typedef struct gvx_fastpitch gvx_fastpitch;
 int gvx_self_attention(const float* qkv, const int32_t* lens, int B, int T, int n_head, int d_head, float* out, void* stream);
+int gvx_add_layer_norm(const float* x, const float* y, const int32_t* lens, int B, int N, int C, const float* ln_w, const float* ln_b,
+                       float* out_haloed, float* out_plain, void* stream);
 size_t gvx_fastpitch_blob_floats(const gvx_fastpitch_dims* dims);
 size_t gvx_fastpitch_workspace_bytes(const gvx_fastpitch_dims* dims, int B, int N);
 int gvx_fastpitch_pack_weights_device(const gvx_fastpitch_dims* dims, const gvx_weight_desc* table, int n, float* device_blob, void* stream);

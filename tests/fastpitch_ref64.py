@@ -16,6 +16,15 @@ NARROW = dict(n_tokens=24, n_mels=20, d_model=32, enc_n_layers=2, enc_n_head=1, 
 TWOHEAD = dict(n_tokens=40, n_mels=80, d_model=128, enc_n_layers=2, enc_n_head=2, enc_d_head=64, enc_d_inner=256, dec_n_layers=2, dec_n_head=2,
                dec_d_head=64, dec_d_inner=256)
 DEFAULT = dict(n_tokens=148, n_mels=80)
+# unequal stacks, a kernel-1 encoder, three predictor layers, no energy branch; widths whose last 64-lane chunk is partly idle (96, 160)
+ASYM = dict(n_tokens=30, n_mels=33, d_model=96, enc_n_layers=1, enc_n_head=1, enc_d_head=32, enc_d_inner=96, enc_kernel_size=1, dec_n_layers=3,
+            dec_n_head=4, dec_d_head=32, dec_d_inner=160, dec_kernel_size=3, predictor_filter_size=160, predictor_n_layers=3, energy_conditioning=False)
+# the widest model over the narrowest inner widths, a kernel-1 decoder, one predictor layer of 288
+WIDE = dict(n_tokens=24, n_mels=7, d_model=512, enc_n_layers=1, enc_n_head=2, enc_d_head=64, enc_d_inner=64, enc_kernel_size=3, dec_n_layers=1,
+            dec_n_head=1, dec_d_head=32, dec_d_inner=32, dec_kernel_size=1, predictor_filter_size=288, predictor_n_layers=1)
+# n_head * d_head above d_model, 16 heads, min_token_frames above 1 and a max_duration the predicted durations reach
+TOPHEAVY = dict(n_tokens=24, n_mels=20, d_model=32, enc_n_layers=2, enc_n_head=2, enc_d_head=64, enc_d_inner=32, dec_n_layers=1, dec_n_head=16,
+                dec_d_head=32, dec_d_inner=64, predictor_filter_size=32, min_token_frames=2, max_duration=3)
 _DEFAULTS = dict(d_model=384, enc_n_layers=6, enc_n_head=1, enc_d_head=64, enc_d_inner=1536, enc_kernel_size=3, dec_n_layers=6, dec_n_head=1,
                  dec_d_head=64, dec_d_inner=1536, dec_kernel_size=3, predictor_filter_size=256, predictor_n_layers=2, energy_conditioning=True,
                  max_duration=75, min_token_frames=0, max_decoder_steps=2000, max_tokens=512)
@@ -263,13 +272,48 @@ def reference_pair(ref, tokens, lens=None, pace=1.0, durations=None, pitch=None,
 ULP = 2.0 ** -23
 FACTOR = 8.0
 CASES = {"narrow 2 x 5": ("NARROW", 2, 5, None), "twohead ragged": ("TWOHEAD", 3, 33, (33, 2, 17)), "default 1 x 12": ("DEFAULT", 1, 12, None),
-         "default 2 x 70": ("DEFAULT", 2, 70, None)}
+         "default 2 x 70": ("DEFAULT", 2, 70, None), "asym ragged": ("ASYM", 3, 17, (17, 1, 16)), "wide 2 x 15": ("WIDE", 2, 15, None),
+         "topheavy ragged": ("TOPHEAVY", 2, 33, (33, 31)), "narrow 1 x 1": ("NARROW", 1, 1, None), "narrow long": ("NARROW", 2, 300, (300, 257))}
 MODEL_SEED = 11
+
+
+# "narrow 1 x 1" draws its token from a seed of its own.  With one token log_durations, pitch_pred and energy_pred are ONE number each,
+# and the float32 restatement's error on one number is a single draw of its rounding, which depends on the order in which the host's
+# library sums: for the token of seed 1011 (id 19, pitch_pred -0.2953) it is 4.6e-07 on one host and 1.1e-08 on another, while float32
+# evaluated in 300 summation orders is off by 1.1e-08 .. 2.0e-06 - so the 8 x rule passed or failed by the host.  The rule's other term, one
+# ulp at the number's scale, does not depend on the host.  Seed 7 draws id 15, whose three numbers (2.03, 0.87, -1.41) are large against
+# what the encoder output's float32 error moves them, so that term decides: tests/test_fastpitch_cpu.py asserts it
+# (``one_token_movement``), in float64, for whatever token this seed draws.
+TOKEN_SEEDS = {"narrow 1 x 1": 7}
 
 
 def case_tokens(name):
     cfg_name, B, L, _ = CASES[name]
-    return random_tokens(globals()[cfg_name], B, L, seed=1000 + 10 * B + L)
+    return random_tokens(globals()[cfg_name], B, L, seed=TOKEN_SEEDS.get(name, 1000 + 10 * B + L))
+
+
+def one_token_movement(ref, token, draws=200, seed=0):
+    """For a row of ONE token: (the float64 log_durations, pitch_pred and energy_pred [3], and the 90th percentile [3] of how far they move
+    when the encoder's output is perturbed, element by element and uniformly, by up to the float32 restatement's largest error on it)."""
+    with torch.no_grad():
+        tok = torch.tensor([int(token)])
+        want = ref(tok)
+        ref32 = copy.deepcopy(ref).float()
+        ref32.cfg = ref.cfg
+        x = want["enc_stages"][-1]
+        err = (ref32(tok)["enc_stages"][-1].double() - x).abs().max().item()
+
+        def tail(x):
+            log_dur, pitch = ref.duration_predictor(x), ref.pitch_predictor(x)
+            out = [log_dur[0], pitch[0]]
+            if ref.cfg["energy_conditioning"]:
+                out.append(ref.energy_predictor(x + ref.pitch_emb(pitch[None, None])[0].t())[0])
+            return torch.stack(out)
+
+        base = tail(x)
+        g = torch.Generator().manual_seed(seed)
+        moved = torch.stack([(tail(x + (2.0 * torch.rand(x.shape, generator=g, dtype=torch.float64) - 1.0) * err) - base).abs() for _ in range(draws)])
+    return base, moved.quantile(0.9, dim=0)
 
 
 def case_durations(name):

@@ -1,7 +1,8 @@
 """CPU: the float64 restatement of FastPitch (tests/fastpitch_ref64.py) against torch's own attention and against itself row by row,
 the regulator's integer plan against a numpy restatement worked by hand, the state-dict conversion and the config ranges of
-``genvox_amd.fastpitch``, the C ABI's host arithmetic for refused dims, and the tie condition of tests/test_fastpitch_gpu.py: no token
-of any case it runs has a duration inside the margin of a rounding decision."""
+``genvox_amd.fastpitch``, the C ABI's host arithmetic for refused dims, the blob's size for unequal stacks (ASYM: no energy branch, three
+predictor layers; WIDE: one) against the sum over the restatement's state dict, and the tie condition of tests/test_fastpitch_gpu.py: no
+token of any of the nine cases it runs has a duration inside the margin of a rounding decision."""
 import ctypes as C
 import functools
 
@@ -22,7 +23,8 @@ def _ref(name):
 
 
 def _module(cfg):
-    ac = AudioConfig(n_mels=cfg["n_mels"])
+    ac = AudioConfig()
+    ac.n_mels = cfg["n_mels"]   # WIDE's 7 bins: below what AudioConfig's constructor takes (a mel front end's range), inside the model's [1, 4096]
     return FastPitch(FastPitchConfig(**R.model_kwargs(cfg)), ac, TextConfig(n_tokens=cfg["n_tokens"]))
 
 
@@ -190,6 +192,42 @@ def test_accepted_dims_sizes_and_refused_shapes():
     h = C.c_void_p()
     assert lib.gvx_fastpitch_create(C.byref(d), C.byref(h)) == 0
     lib.gvx_fastpitch_destroy(h)
+
+
+@pytest.mark.parametrize("name", ["ASYM", "WIDE"])
+def test_blob_floats_of_unequal_stacks_equal_the_sum_over_the_state_dict(name):
+    """Unequal stacks, kernel sizes 1 and 3, one and three predictor layers, with and without the energy branch: the blob is every tensor of
+    the restatement's state dict (each stack's layers at that stack's own sizes; no ``energy_*`` tensor without energy conditioning) and
+    the position table, each rounded up to 64 floats."""
+    cfg = R.full(getattr(R, name))
+    sd = {k: v for k, v in _ref(name).state_dict().items() if k not in ("pitch_mean", "pitch_std")}
+    r = lambda n: (n + 63) // 64 * 64
+    want = sum(r(v.numel()) for v in sd.values()) + r(max(cfg["max_tokens"], cfg["max_decoder_steps"]) * cfg["d_model"])
+    model = _module(getattr(R, name))
+    assert _lib.load().gvx_fastpitch_blob_floats(C.byref(model.dims())) == want
+    assert set(model.state_dict()) == set(_ref(name).state_dict())
+    assert dict(model._pack_items()).keys() == sd.keys()
+    assert all(tuple(v.shape) == tuple(sd[k].shape) for k, v in model.state_dict().items() if k in sd)
+    has_energy = any(k.startswith("energy_") for k in model.state_dict())
+    assert has_energy == cfg["energy_conditioning"] and has_energy == (name == "WIDE")
+    # by hand for the tensors whose sizes differ between the stacks
+    k_enc, k_dec = cfg["enc_kernel_size"], cfg["dec_kernel_size"]
+    assert sd["encoder.layers.0.pos_ff.CoreNet.0.weight"].shape == (cfg["enc_d_inner"], cfg["d_model"], k_enc)
+    assert sd["decoder.layers.0.pos_ff.CoreNet.2.weight"].shape == (cfg["d_model"], cfg["dec_d_inner"], k_dec)
+    assert sd["decoder.layers.0.dec_attn.qkv_net.weight"].shape == (3 * cfg["dec_n_head"] * cfg["dec_d_head"], cfg["d_model"])
+    assert len([k for k in sd if k.startswith("duration_predictor.layers.") and k.endswith("conv.weight")]) == cfg["predictor_n_layers"]
+
+
+def test_the_one_token_case_is_decided_by_the_ulp_at_scale_not_by_the_hosts_rounding():
+    """"narrow 1 x 1": each predictor's output is one number, so the float32 restatement's error on it is one draw of the host library's
+    rounding.  For the token the case draws, 8 ulp at each number's scale - the term of the rule that no host changes - is at least twice
+    the 90th percentile of what the encoder output's float32 error moves the number, in float64."""
+    cfg_name, B, L, _ = R.CASES["narrow 1 x 1"]
+    assert (B, L) == (1, 1)
+    values, moved = R.one_token_movement(_ref(cfg_name), R.case_tokens("narrow 1 x 1")[0, 0])
+    floor = R.FACTOR * R.ULP * values.abs()
+    print(f"values {values.tolist()}, 90th percentile of the movement over 8 ulp at scale {(moved / floor).tolist()}")
+    assert (2.0 * moved <= floor).all()
 
 
 @pytest.mark.parametrize("name", list(R.CASES))

@@ -11,6 +11,22 @@ than 8 x max(float32 restatement's error on dur, one ulp at its scale); tests/te
 cases lies inside that margin, so nothing is excluded unless the device is wrong.  The decoder is then checked on the device's own
 durations.
 
+The cases (tests/fastpitch_ref64.py, ``CASES``): NARROW, TWOHEAD and DEFAULT share equal stacks, kernel size 3, two predictor layers,
+energy conditioning and widths of 32, 128 and 384.  ASYM (d_model 96: a kernel-1 one-layer encoder, a kernel-3 three-layer decoder of four
+heads, inner widths 96 and 160, three predictor layers of 160, no energy branch, 33 mel bins), WIDE (d_model 512: inner widths 64 and 32, a
+kernel-1 decoder, one predictor layer of 288, 7 mel bins) and TOPHEAVY (d_model 32 under 2 x 64 and 16 x 32 heads, ``min_token_frames`` 2,
+``max_duration`` 3, which the predicted durations reach at both ends) run what those never do: the haloed row offset of ``pad = 0``, the
+workspace's maxima over unequal stacks, the blob without the third predictor, the predictors' ping-pong ending in either buffer, and
+LayerNorm widths whose last 64-lane chunk is partly idle.  "narrow 1 x 1" is one token (drawn from a seed of its own, ``TOKEN_SEEDS``:
+the predictors' outputs are then one number each, and the token is one at which the rule is decided by its ulp term, not by the order in
+which the host's library sums in float32); "narrow long" (300 and 257 tokens, 700 - 850
+frames) takes the plan kernel's strided loops through a second pass and the attention through 14 key tiles and 7 query tiles.  With
+energy conditioning off, ``energy_pred`` is all zeros in float64: the device's must be exact zeros.
+
+Beyond the cases: bit equality of ragged rows with the rows alone (TWOHEAD and ASYM), one token with one frame, a cut on a token boundary
+and a cut row beside a whole one, the predicted path at both clamps and through the empty-row rule (``duration_predictor.fc`` set to a
+constant), and token ids outside the table.
+
 Largest ratios seen on an MI355X: see README.md, "FastPitch"."""
 import functools
 
@@ -30,7 +46,9 @@ NAN = float("nan")
 
 
 def _build(cfg, **more):
-    return FastPitch(FastPitchConfig(**R.model_kwargs(cfg), **more), AudioConfig(n_mels=cfg["n_mels"]), TextConfig(n_tokens=cfg["n_tokens"]))
+    ac = AudioConfig()
+    ac.n_mels = cfg["n_mels"]   # WIDE's 7 bins: below what AudioConfig's constructor takes (a mel front end's range), inside the model's [1, 4096]
+    return FastPitch(FastPitchConfig(**{**R.model_kwargs(cfg), **more}), ac, TextConfig(n_tokens=cfg["n_tokens"]))
 
 
 @functools.lru_cache(maxsize=None)
@@ -83,6 +101,10 @@ def _compare(got, want, errs, names, what):
     assert len(got) == len(want) == len(names)
     for name, g, w, e in zip(names, got, want, errs):
         assert g.shape == w.shape, (what, name, g.shape, w.shape)
+        if not w.any():   # (energy_pred without energy conditioning) the rule's base is 0: exact zeros, and no ratio to print
+            assert not g.any(), f"{what}: {name} is all zeros in float64 and not on the device"
+            print(f"{what}: {name}: all zeros in float64, exact zeros on the device")
+            continue
         d = (g.double().cpu() - w).abs().max().item()
         base = max(e, ULP * w.abs().max().item())
         print(f"{what}: {name}: device error {d:.3e}, float32 restatement error {e:.3e}, one ulp at scale {ULP * w.abs().max().item():.3e}, ratio {d / base:.2f}")
@@ -116,7 +138,8 @@ def _alignment_of(durations, T):
 @pytest.mark.parametrize("name", list(R.CASES))
 def test_every_stage_and_the_mel_on_given_durations(name):
     """NARROW 2 x 5: one 32-wide head, half-idle waves in the LayerNorm; TWOHEAD ragged (33, 2, 17); DEFAULT 1 x 12 and 2 x 70: the published
-    sizes.  The durations are given, so the decoder's length is the plan's."""
+    sizes; ASYM ragged (17, 1, 16), WIDE 2 x 15, TOPHEAVY ragged (33, 31), NARROW 1 x 1 and NARROW long (300, 257): the module docstring.
+    The durations are given, so the decoder's length is the plan's."""
     cfg_name = R.CASES[name][0]
     cfg, _, model = _net(cfg_name)
     tokens, lens, durations, want, errs = _given(name)
@@ -154,23 +177,135 @@ def test_predicted_durations_and_the_decoder_on_the_devices_own(name):
 
 
 def test_ragged_rows_equal_the_rows_alone_bit_for_bit():
-    """Through the whole model, on predicted durations: rows of 33, 2 and 17 tokens, NaN-free padding tokens that must not matter."""
-    cfg, _, model = _net("TWOHEAD")
-    tokens, lens = R.case_tokens("twohead ragged"), (33, 2, 17)
-    out, stages = _run(model, _inputs(tokens, lens))
-    other = tokens.clone()
-    for b, n in enumerate(lens):
-        other[b, n:] = (other[b, n:] + 7) % cfg["n_tokens"]   # the padded tokens are never read
-    out2, _ = _run(model, _inputs(other, lens))
-    assert torch.equal(out["mel_outputs"], out2["mel_outputs"])
-    for b, n in enumerate(lens):
-        alone, alone_stages = _run(model, _inputs(tokens[b:b + 1, :n], None))
-        t = alone["mel_outputs"].shape[2]
-        assert out["mel_lengths"][b].item() == t
-        assert torch.equal(out["mel_outputs"][b, :, :t], alone["mel_outputs"][0]), f"row {b}"
-        assert torch.equal(out["durations"][b, :n], alone["durations"][0]) and torch.equal(out["alignments"][b, :t, :n], alone["alignments"][0])
-        for s, a in zip(stages[:-1], alone_stages[:-1]):
-            assert torch.equal(s[b, :a.shape[1]], a[0]), f"row {b}"
+    """Through the whole model, on predicted durations: rows of 33, 2 and 17 tokens (TWOHEAD) and of 17, 1 and 16 (ASYM: a kernel-1 and a
+    kernel-3 stack, three predictor layers, no energy branch), NaN-free padding tokens that must not matter."""
+    for cfg_name, case in (("TWOHEAD", "twohead ragged"), ("ASYM", "asym ragged")):
+        cfg, _, model = _net(cfg_name)
+        tokens, lens = R.case_tokens(case), R.CASES[case][3]
+        out, stages = _run(model, _inputs(tokens, lens))
+        other = tokens.clone()
+        for b, n in enumerate(lens):
+            other[b, n:] = (other[b, n:] + 7) % cfg["n_tokens"]   # the padded tokens are never read
+        out2, _ = _run(model, _inputs(other, lens))
+        assert torch.equal(out["mel_outputs"], out2["mel_outputs"])
+        for b, n in enumerate(lens):
+            alone, alone_stages = _run(model, _inputs(tokens[b:b + 1, :n], None))
+            t = alone["mel_outputs"].shape[2]
+            assert out["mel_lengths"][b].item() == t
+            assert torch.equal(out["mel_outputs"][b, :, :t], alone["mel_outputs"][0]), f"{case}: row {b}"
+            assert torch.equal(out["durations"][b, :n], alone["durations"][0]) and torch.equal(out["alignments"][b, :t, :n], alone["alignments"][0])
+            for s, a in zip(stages[:-1], alone_stages[:-1]):
+                assert torch.equal(s[b, :a.shape[1]], a[0]), f"{case}: row {b}"
+
+
+def test_one_token_one_frame():
+    """B = L = T = 1: in every LayerNorm launch one wave writes the position and both halo rows, every product has one row, the softmax one
+    key.  Every stage against float64, on a NaN-filled, exactly sized workspace.
+
+    The token is the one "narrow 1 x 1" draws: tests/fastpitch_ref64.py, ``TOKEN_SEEDS``, says why that case has a seed of its own."""
+    cfg, ref, model = _net("NARROW")
+    tokens = R.case_tokens("narrow 1 x 1")
+    durations = torch.tensor([[1]])
+    want, errs, _ = R.reference_pair(ref, tokens, None, durations=durations)
+    assert want["frames"] == [1]
+    out, stages = _run(model, _inputs(tokens, None, durations=durations), frames=1)
+    _compare(stages, want["stages"], errs, R.stage_names(cfg), "1 token, 1 frame")
+    assert out["mel_outputs"].shape == (1, cfg["n_mels"], 1) and out["durations"].tolist() == [[1]]
+    assert out["alignments"].tolist() == [[[1.0]]] and out["gate_outputs"].tolist() == [[1e3]]
+
+
+def test_a_cut_on_a_token_boundary_and_a_cut_row_beside_a_whole_one():
+    cfg, _, shared = _net("NARROW")
+    cut_cfg = {**cfg, "max_decoder_steps": 6}
+    ref = R.Model(cut_cfg, seed=R.MODEL_SEED)   # (the same weights: the seed draws them in the same order)
+    cut = _build(cut_cfg).to(DEV)
+    cut.load_state_dict(shared.state_dict())
+    tokens = R.random_tokens(cfg, 2, 5, seed=31)
+    # the cut lands exactly behind the second token: the third gets nothing
+    durations = torch.tensor([[2, 4, 5]])
+    assert R.plan(durations[0].double(), 1.0, 0, 6)[0].tolist() == [2, 4, 0]
+    out = cut.inference(_inputs(tokens[:1, :3], None, durations=durations))
+    assert out["durations"].tolist() == [[2, 4, 0]] and out["mel_outputs"].shape[2] == 6
+    assert torch.equal(out["alignments"].cpu(), _alignment_of(out["durations"], 6))
+    # a ragged batch: row 0 is cut (on a token boundary as well), row 1 (3 tokens, 4 frames) is not
+    lens = (5, 3)
+    durations = torch.tensor([[3, 3, 3, 3, 3], [1, 2, 1, 9, 9]])
+    want, errs, _ = R.reference_pair(ref, tokens, lens, durations=durations)
+    assert want["durations"].tolist() == [[3, 3, 0, 0, 0], [1, 2, 1, 0, 0]] and want["frames"] == [6, 4]
+    out, stages = _run(cut, _inputs(tokens, lens, durations=durations), frames=6)
+    assert torch.equal(out["durations"].cpu().long(), want["durations"]) and out["mel_lengths"].tolist() == [6, 4]
+    assert torch.equal(out["alignments"].cpu(), _alignment_of(out["durations"], 6)) and torch.equal(out["alignments"].cpu().double(), want["alignments"])
+    _compare(stages, want["stages"], errs, R.stage_names(cfg), "cut at 6 frames, ragged")
+    _zeros_behind(out, stages, lens, want["frames"], R.full(cfg)["enc_n_layers"])
+
+
+def _constant_log_duration(cfg, shared, b, **more):
+    """The model with ``duration_predictor.fc`` at weight 0 and bias ``b``: ``log_durations == b`` on every token."""
+    model = _build({**cfg, **more}).to(DEV)
+    sd = {k: v.clone() for k, v in shared.state_dict().items()}
+    sd["duration_predictor.fc.weight"].zero_()
+    sd["duration_predictor.fc.bias"].fill_(b)
+    model.load_state_dict(sd)
+    return model
+
+
+def _planned(b, lens, L, pace, cfg):
+    """The float64 plan of ``log_durations == fl32(b)`` for rows of ``lens`` tokens -> (durations [B, L] int64, the least distance of
+    ``dur / pace + 0.5`` from an integer)."""
+    cfg = R.full(cfg)
+    b64 = torch.tensor(b, dtype=torch.float32).double()
+    dur = torch.clamp(torch.exp(b64) - 1.0, 0.0, float(cfg["max_duration"]))
+    x = dur / pace + 0.5
+    out = torch.zeros(len(lens), L, dtype=torch.int64)
+    for i, n in enumerate(lens):
+        out[i, :n] = R.plan(dur.expand(n), pace, cfg["min_token_frames"], cfg["max_decoder_steps"])[0]
+    return out, (x - torch.round(x)).abs().item()
+
+
+def test_both_clamps_and_the_empty_row_on_the_predicted_path():
+    """The predicted durations at ``max_duration`` and at 0 (where the last token of each row's own length gets the row's one frame), and a
+    duration in between under a pace, with ``min_token_frames`` 0 and 2.  The expected durations are the float64 plan's."""
+    import math
+
+    cfg, _, shared = _net("NARROW")
+    tokens = R.random_tokens(cfg, 2, 5, seed=32)
+    lens = (5, 3)
+
+    def run(b, pace, **more):
+        model = _constant_log_duration(cfg, shared, b, **more)
+        out = model.inference(_inputs(tokens, lens, pace=pace))
+        want, margin = _planned(b, lens, 5, pace, {**cfg, **more})
+        assert margin >= 0.1, "float32 arithmetic must not be able to round the other way"
+        valid = torch.arange(5)[None, :] < torch.tensor(lens)[:, None]
+        assert (out["log_durations"].cpu()[valid] == torch.tensor(b, dtype=torch.float32)).all() and not out["log_durations"].cpu()[~valid].any()
+        assert torch.equal(out["durations"].cpu().long(), want), (b, pace, more, out["durations"].tolist())
+        T = int(want.sum(1).max())
+        assert out["mel_lengths"].tolist() == want.sum(1).tolist() and out["mel_outputs"].shape[2] == T
+        assert torch.equal(out["alignments"].cpu(), _alignment_of(out["durations"], T))
+        assert torch.isfinite(out["mel_outputs"]).all()
+        for i, t in enumerate(want.sum(1).tolist()):
+            assert not out["mel_outputs"][i, :, t:].any()
+        return want
+
+    assert run(math.log(76.0) + 0.5, 1.0).tolist() == [[75] * 5, [75] * 3 + [0, 0]]      # the clamp at max_duration = 75
+    assert run(-2.0, 1.0).tolist() == [[0, 0, 0, 0, 1], [0, 0, 1, 0, 0]]                 # the clamp at 0, then the empty row's one frame
+    # exp(0.9) - 1 = 1.4596; under pace 1.25: 1.1677 + 0.5 = 1.6677, 0.33 from an integer
+    assert run(0.9, 1.25).tolist() == [[1] * 5, [1] * 3 + [0, 0]]
+    assert run(0.9, 1.25, min_token_frames=2).tolist() == [[2] * 5, [2] * 3 + [0, 0]]
+
+
+def test_a_token_id_outside_the_table_is_read_as_id_0():
+    """include/genvox_amd.h: "a token outside [0, n_tokens) reads row 0"."""
+    cfg, _, model = _net("NARROW")
+    tokens = R.random_tokens(cfg, 2, 5, seed=33)
+    tokens[0, 1], tokens[1, 0], tokens[1, 4] = cfg["n_tokens"], -1, 10 ** 6
+    zeroed = tokens.clone()
+    zeroed[0, 1] = zeroed[1, 0] = zeroed[1, 4] = 0
+    out, stages = _run(model, _inputs(tokens, None))
+    want, want_stages = _run(model, _inputs(zeroed, None))
+    for key in ("mel_outputs", "alignments", "gate_outputs", "log_durations", "pitch_pred", "energy_pred", "durations", "mel_lengths"):
+        assert torch.equal(out[key], want[key]), key
+    assert all(torch.equal(a, b) for a, b in zip(stages, want_stages)) and torch.isfinite(out["mel_outputs"]).all()
 
 
 def test_rows_do_not_depend_on_the_gemm_tile_shape():
