@@ -267,6 +267,7 @@ SIGNATURES = {
     "gvx_hifigan_backward_workspace_bytes": (_sz, [C.POINTER(gvx_hifigan_dims), _i, _i]),
     "gvx_hifigan_forward_train": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _sz, _vp, _sz, _vp]),
     "gvx_hifigan_backward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, C.POINTER(gvx_weight_desc), _i, _vp, _vp, _sz, _vp]),
+    "gvx_hifigan_layer": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _f, _i, _vp]),
     "gvx_melgan_disc_blob_floats": (_sz, [C.POINTER(gvx_melgan_disc_dims)]),
     "gvx_melgan_disc_pack_weights_device": (_i, [C.POINTER(gvx_melgan_disc_dims), C.POINTER(gvx_weight_desc), _i, _vp, _vp]),
     "gvx_melgan_disc_create": (_i, [C.POINTER(gvx_melgan_disc_dims), C.POINTER(_vp)]),

@@ -728,4 +728,55 @@ int gvx_hifigan_backward_stage_times_ms(gvx_hifigan* h, float* ms_out, int* n_ou
     return gen_stage_times_ms(h, h->d.n_stages + 3, ms_out, n_out, &h->bwd_marks);
 }
 
+// One layer on its own: the arguments fill an HgLayer, hg_launch (forward) or hgb_dgrad (data gradient) picks the kernel as the models'
+// layers have it picked.  Everything the kernels take for granted is checked here, before a launch.
+int gvx_hifigan_layer(const float* src, const float* W, const float* bias, const float* res, const float* mask, const float* add2, float* out,
+                      const int32_t* lens, int B, int T, int in_mul, int Cin, int Cout, int taps, int dil, int phases, int act, int accumulate,
+                      float divide, int zero_tail, int tanh_out, float slope, int gradient, void* stream) {
+    if (!src || !W || !out) return fail(GVX_ERR_INVALID_ARG, "null argument");
+    if (((uintptr_t)src | (uintptr_t)W | (uintptr_t)bias | (uintptr_t)res | (uintptr_t)mask | (uintptr_t)add2 | (uintptr_t)out) & 15)
+        return fail(GVX_ERR_INVALID_ARG, "src, W, bias, res, mask, add2 and out must be 16-byte aligned");
+    if ((uintptr_t)lens & 3) return fail(GVX_ERR_INVALID_ARG, "lens must be 4-byte aligned");
+    if (out == src) return fail(GVX_ERR_INVALID_ARG, "out must not be src: a position's window reads its neighbours' positions of src");
+    if (B < 1 || B > 65535) return fail(GVX_ERR_INVALID_ARG, "B must be in [1, 65535]");
+    if (T < 1 || in_mul < 1 || (long)T * in_mul > (1L << 24)) return fail(GVX_ERR_INVALID_ARG, "T and in_mul must be >= 1 and T * in_mul at most 2^24 positions");
+    if (Cin < 1 || Cin > 4096 || Cout < 1 || Cout > 4096) return fail(GVX_ERR_INVALID_ARG, "Cin and Cout must be in [1, 4096]");
+    if (phases < 1 || phases > 64) return fail(GVX_ERR_INVALID_ARG, "phases must be in [1, 64]");
+    if ((long)T * in_mul * Cout > (1L << 28)) return fail(GVX_ERR_INVALID_ARG, "T * in_mul * Cout is beyond 2^28 elements per phase");
+    if (phases > 1) {
+        if (taps != 2) return fail(GVX_ERR_INVALID_ARG, "phases > 1 is the two-tap phase split: taps must be 2");
+        if (phases & 1) return fail(GVX_ERR_INVALID_ARG, "phases > 1 must be even");
+        if (res) return fail(GVX_ERR_INVALID_ARG, "a residual comes with phases = 1 only");
+    } else {
+        if (taps < 1 || !(taps & 1)) return fail(GVX_ERR_INVALID_ARG, "taps must be odd and >= 1 (the window is centred)");
+        if (dil < 1) return fail(GVX_ERR_INVALID_ARG, "the dilation must be >= 1");
+        if ((long)(taps - 1) * dil > GVX_HIFIGAN_MAX_WINDOW) return fail(GVX_ERR_INVALID_ARG, "(taps - 1) * dilation must not pass GVX_HIFIGAN_MAX_WINDOW (72)");
+    }
+    if (!(slope >= 0.f && slope <= 1.f)) return fail(GVX_ERR_INVALID_ARG, "slope must be in [0, 1]");
+    if (!(divide >= 0.f) || !std::isfinite(divide)) return fail(GVX_ERR_INVALID_ARG, "divide must be finite and >= 0 (0: no division)");
+    const bool matrix = Cout >= 32 && Cin % 4 == 0;   // hg_launch's and hgb_dgrad's split; every other layer runs on the dot-product kernel
+    if (gradient) {
+        if (phases != 1) return fail(GVX_ERR_INVALID_ARG, "a data gradient has phases = 1 (a transposed convolution's is its 3-tap form)");
+        if (bias || act || accumulate || zero_tail || tanh_out)
+            return fail(GVX_ERR_INVALID_ARG, "a data gradient takes no bias, act, accumulate, zero_tail or tanh_out");
+    } else {
+        if (!bias) return fail(GVX_ERR_INVALID_ARG, "the forward layer needs a bias");
+        if (mask || add2) return fail(GVX_ERR_INVALID_ARG, "mask and add2 belong to the data gradient");
+        if (tanh_out && matrix) return fail(GVX_ERR_INVALID_ARG, "tanh_out is the dot-product kernel's: Cout < 32 or Cin not a multiple of 4");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    // no handle: the dynamic-LDS sizes of hg_launch's kernels once per process (a static local: one thread runs it), on the device that is
+    // current at the first call; a failure of that first preparation is what every later call returns (as un_lone_prepare, univnet.hip)
+    static bool ready = false;
+    static const int prepared = hg_prepare(&ready);
+    if ((rc = prepared) != GVX_OK) return rc;
+    HgLayer p{};
+    p.src = src; p.W = W; p.bias = bias; p.res = res; p.out = out; p.lens = lens; p.T = T; p.in_mul = in_mul;
+    p.Cin = Cin; p.Cout = Cout; p.K = taps * Cin; p.taps = taps; p.dil = phases > 1 ? 0 : dil; p.phases = phases;
+    p.act = act != 0; p.accumulate = accumulate != 0; p.divide = divide; p.zero_tail = zero_tail != 0; p.tanh_out = tanh_out != 0; p.slope = slope;
+    p.mask = mask; p.add2 = add2;
+    return gradient ? hgb_dgrad(p, B, s) : hg_launch(p, B, s);
+}
+
 }  // C ABI

@@ -14,11 +14,69 @@ from __future__ import annotations
 
 from typing import Dict, List, Optional
 
+import torch
 from torch import nn
 
 from . import _lib
-from ._device_module import DeviceGenerator, _Layer
+from ._device_module import DeviceGenerator, _Layer, _ptr
 from .configs import AudioConfig, HiFiGANConfig
+
+
+def conv_layer(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, *, dilation: int = 1, stride: int = 1, lengths=None,
+               in_mul: int = 1, act: bool = False, slope: float = 0.1, res: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+               accumulate: bool = False, divide: float = 0.0, zero_tail: bool = False, tanh_out: bool = False, gradient: bool = False,
+               mask: Optional[torch.Tensor] = None, add2: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One layer of the generators on its own (gvx_hifigan_layer, which states the arithmetic): x float32 [B, L, C] channels-last on the
+    device -> [B, L * stride, Cout].  ``weight`` is in PyTorch's layout and brought into the device order here, in torch (this wrapper is
+    for tests): ``Conv1d`` [Cout, Cin, k] with ``dilation`` and padding (k - 1) dilation / 2; with ``stride`` r > 1 ``ConvTranspose1d``
+    [Cin, Cout, 2 r] of stride r and padding r / 2; with ``gradient`` the FORWARD convolution's [N, C, k], x being dY [B, L, N] and the
+    result dX [B, L, C] = (lrelu'(mask) * conv^T(dY) + res + add2) / divide.  ``lengths`` ([B], host or device) count units of ``in_mul``
+    positions.  ``out``: the tensor to write (what it holds behind a row stays unless ``zero_tail``; ``accumulate`` adds to what it holds),
+    or None for a new one.  The library refuses what the kernels cannot take."""
+    if x.dim() != 3 or x.device.type != "cuda" or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError(f"x must be contiguous float32 [B, L, C] on the device, got {x.dtype} {tuple(x.shape)} on {x.device}")
+    if weight.dim() != 3:
+        raise ValueError(f"weight must have three dimensions, got {tuple(weight.shape)}")
+    B, L, C = x.shape
+    dev = x.device
+    prep = lambda t: t.detach().to(dev, torch.float32).contiguous()
+    phases, taps = 1, weight.shape[2]
+    if gradient:
+        if stride != 1 or weight.shape[0] != C:
+            raise ValueError(f"a gradient takes stride 1 and the forward weight [{C}, C, k], got {tuple(weight.shape)}")
+        w, c_out = prep(weight.flip(2).permute(1, 2, 0)), weight.shape[1]               # [C][k][N], the taps reversed
+    elif stride > 1:
+        if stride % 2 or tuple(weight.shape[::2]) != (C, 2 * stride):
+            raise ValueError(f"with stride {stride} (even) weight must be [{C}, Cout, {2 * stride}], got {tuple(weight.shape)}")
+        half = stride // 2
+        tap = torch.tensor([[ph + half, ph + half + stride if ph < half else ph + half - stride] for ph in range(stride)])
+        w, c_out = prep(weight.permute(2, 1, 0)[tap].permute(0, 2, 1, 3)), weight.shape[1]   # [r][Cout][2][Cin]
+        phases, taps = stride, 2
+    else:
+        if weight.shape[1] != C:
+            raise ValueError(f"weight must be [Cout, {C}, k], got {tuple(weight.shape)}")
+        w, c_out = prep(weight.permute(0, 2, 1)), weight.shape[0]                         # [Cout][k][Cin]
+    if bias is not None and tuple(bias.shape) != (c_out,):
+        raise ValueError(f"bias must be [{c_out}], got {tuple(bias.shape)}")
+    if in_mul < 1 or L % in_mul:
+        raise ValueError(f"in_mul must divide the {L} positions")
+    T = L // in_mul
+    lens = None
+    if lengths is not None:
+        host = [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+        if len(host) != B or any(not 0 <= n <= T for n in host):
+            raise ValueError(f"lengths must be {B} values in [0, {T}]")
+        lens = torch.tensor(host, dtype=torch.int32, device=dev)
+    for name, t, shape in (("res", res, (B, L, c_out)), ("mask", mask, (B, L, c_out)), ("add2", add2, (B, L, c_out)), ("out", out, (B, L * phases, c_out))):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous()):
+            raise ValueError(f"{name} must be contiguous float32 {list(shape)} on {dev}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    if out is None:
+        out = torch.empty(B, L * phases, c_out, device=dev)
+    b = prep(bias) if bias is not None else None
+    _lib.check(_lib.load().gvx_hifigan_layer(x.data_ptr(), w.data_ptr(), _ptr(b), _ptr(res), _ptr(mask), _ptr(add2), out.data_ptr(), _ptr(lens), B, T,
+                                             int(in_mul), C, c_out, taps, int(dilation), phases, int(act), int(accumulate), float(divide), int(zero_tail),
+                                             int(tanh_out), float(slope), int(gradient), torch.cuda.current_stream(dev).cuda_stream))
+    return out
 
 
 def structure_dims(mc: HiFiGANConfig, ac: AudioConfig) -> _lib.gvx_hifigan_dims:

@@ -1222,6 +1222,44 @@ int gvx_hifigan_backward(gvx_hifigan* handle, const float* d_wav, const int32_t*
                          size_t workspace_bytes, void* stream);
 int gvx_hifigan_backward_stage_times_ms(gvx_hifigan* handle, float* ms_out, int* n_out);
 
+/* gvx_hifigan_layer is ONE layer of the generators above on its own - the launch that gvx_hifigan_forward, gvx_bigvgan_forward,
+ * gvx_univnet_forward's convolutions and gvx_hifigan_backward's data gradients are chains of - with the kernel picked as they have it
+ * picked: Cout >= 32 and Cin a multiple of 4 run on v_mfma_f32_32x32x2_f32 with 128 positions x 128 (Cout >= 128), 64 (Cout > 32) or 32
+ * channels per workgroup, every other layer on fmaf dot products (8 lanes per element where Cout == 1).  No handle, no workspace; the
+ * launch goes to `stream`.  All tensors are fp32, channels-last, on the device, 16-byte aligned; L = T * in_mul positions per row.
+ *
+ * gradient == 0, a forward layer:  src [B][L][Cin] -> out [B][L * phases][Cout],
+ *     out[b][phases q + phase][n] = E( bias[n] + sum over taps tau, channels c of a(src[b][pos(q, phase, tau)][c]) * W[phase][n][tau][c] )
+ * with a = lrelu(., slope) if act, else the identity; zeros for positions outside the row's own [0, len_b), len_b = min(lens[b], T) *
+ * in_mul (lens int32 [B] on the device, counted in units of in_mul positions; NULL: every row has L); and the epilogue E, in this order:
+ * + res[b][q][n] (res [B][L][Cout] or NULL), + what out held (accumulate), / divide (divide > 0), tanh (tanh_out).
+ *   phases == 1, a convolution: taps odd, pos = q - (taps - 1) dil / 2 + tau dil.  From PyTorch's Conv1d weight w [Cout][Cin][taps]:
+ *       W[0][n][tau][c] = w[n][c][tau], that is w.permute(0, 2, 1).
+ *   phases == r > 1, ConvTranspose1d(kernel 2 r, stride r, padding r / 2), r even: taps = 2 (dil is not read); tap 0 reads position q,
+ *       tap 1 position q - 1 where phase < r / 2 and q + 1 otherwise.  From PyTorch's weight w [Cin][Cout][2 r]:
+ *       W[phase][n][0][c] = w[c][n][phase + r / 2];  W[phase][n][1][c] = w[c][n][phase + r / 2 + r] (phase < r / 2), w[c][n][phase - r / 2] (else).
+ * Behind a row (positions >= len_b) out is written with exact zeros if zero_tail, and left as it was otherwise; src, res and out are not
+ * read there.  out may be res (an element is read and written by one lane); out must not be src.
+ *
+ * gradient != 0, a data gradient (phases == 1; bias NULL; act, accumulate, zero_tail, tanh_out 0): src is dY [B][L][Cin], out is dX
+ * [B][L][Cout], the same windowed product without a bias on the TRANSPOSED, tap-reversed weights - for a forward convolution w [N][C][k]
+ * (dY has Cin = N channels, dX has Cout = C):  W[0][c][tau][n] = w[n][c][k - 1 - tau], that is w.flip(2).permute(1, 2, 0) - and the epilogue
+ *     dX = ( (mask ? (mask > 0 ? v : v * slope) : v) + res + add2 ) / divide
+ * with mask (the raw tensor whose LeakyReLU the gradient passes through), res and add2 each [B][L][Cout] or NULL; nothing is written
+ * behind a row.
+ *
+ * Refused with GVX_ERR_INVALID_ARG before anything is launched: a NULL src, W or out (or bias, forward); a misaligned pointer; out == src;
+ * B outside [1, 65535]; T or in_mul below 1, T * in_mul above 2^24 or T * in_mul * Cout above 2^28; Cin or Cout outside [1, 4096]; phases
+ * outside [1, 64] or odd above 1; phases > 1 with taps != 2 or with a residual; phases == 1 with even taps, dil < 1 or (taps - 1) * dil >
+ * GVX_HIFIGAN_MAX_WINDOW; slope outside [0, 1]; divide negative or not finite; tanh_out on the matrix kernels (which have none: it is
+ * the output layer's); mask or add2 in a forward call; anything a data gradient does not take.  Cin that is no multiple of 4 is NOT
+ * refused at any Cout: such a layer runs on the dot-product kernel.  The kernels' dynamic-LDS sizes are set once per process, at the
+ * first call and on the device current then: the entry is for one device per process, and if that first preparation fails every later
+ * call returns its error. */
+int gvx_hifigan_layer(const float* src, const float* W, const float* bias, const float* res, const float* mask, const float* add2, float* out,
+                      const int32_t* lens, int B, int T, int in_mul, int Cin, int Cout, int taps, int dil, int phases, int act, int accumulate,
+                      float divide, int zero_tail, int tanh_out, float slope, int gradient, void* stream);
+
 /* ---- BigVGAN generator, mel -> waveform (Lee et al. 2023; bigvgan_base_22khz_80band, bigvgan_22khz_80band and their kin): inference.
  * The reference ships no such model; the network below is the published implementation's, under its names.  It is HiFi-GAN's
  * generator (above) with every LeakyReLU replaced by an anti-aliased periodic activation A, and no activation in front of the

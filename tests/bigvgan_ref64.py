@@ -26,6 +26,10 @@ MID, NARROW, TWO = _cfg(H.MID), _cfg(H.NARROW), _cfg(H.TWO)              # tests
 MID_CLAMP = _cfg(H.MID, tanh=False)
 NARROW_NOBIAS = _cfg(H.NARROW, bias=False)
 TWO_SNAKE = _cfg(H.TWO, activation="snake", logscale=False)
+ODD_BETA = _cfg(H.ODD)                                                   # tests/hifigan_ref64.py's three that no published shape reaches
+FOUR_SNAKE = _cfg(H.FOUR, activation="snake", logscale=False)
+ONE_CLAMP = _cfg(H.ONE, tanh=False, bias=False)
+NEVER_RUN = ("ODD_BETA", "FOUR_SNAKE", "ONE_CLAMP")
 
 hop = H.hop
 

@@ -13,6 +13,19 @@ MID = dict(n_mels=20, c0=256, rates=(4, 2), resblock="1", kernels=(3, 7, 11), di
 NARROW = dict(n_mels=12, c0=48, rates=(4, 2), resblock="1", kernels=(3, 7, 11), dilations=_D135, slope=0.1, post_slope=0.01)   # 24 and 12 channels: N tails, conv_pre's K tail, dot products
 TWO = dict(n_mels=12, c0=64, rates=(4, 4), resblock="2", kernels=(3, 5, 7), dilations=_D2, slope=0.1, post_slope=0.01)         # 32 and 16 channels; the widest window, 72
 
+# What no published shape reaches (tests/test_generator_configs_cpu.py asserts the path of every layer):
+# ODD   37 mels padded to 40; conv_pre's 144 columns on the 128-wide tile with a 16-column tail; 6 phases on the 64-wide tile (72 columns, a
+#       tail of 8) and 2 more on it (36, a tail of 4); K tails of 16 (144), 8 (40, 72) and 4 (36) in a 32-channel block; two blocks per stage;
+#       the window limit 72 by k = 9, d = 9; an even dilation in resblock "1"
+# ONE   5 mels padded to 8; one stage of 10 phases on the 32-wide tile; one block (no accumulate, a division by 1); left = 36; ReLU
+#       (slope 0) inside and the identity (slope 1) in front of conv_post
+# FOUR  the dot-product kernel throughout (16 and 8 channels; conv_pre's 32 columns on the 32-wide tile), four blocks per stage
+ODD = dict(n_mels=37, c0=144, rates=(6, 2), resblock="1", kernels=(5, 9), dilations=((1, 2, 4), (1, 7, 9)), slope=0.2, post_slope=0.05)
+ONE = dict(n_mels=5, c0=64, rates=(10,), resblock="2", kernels=(3,), dilations=((1, 36),), slope=0.0, post_slope=1.0)
+FOUR = dict(n_mels=12, c0=32, rates=(2, 2), resblock="1", kernels=(3, 5, 7, 9), dilations=((1, 1, 1), (1, 2, 3), (2, 4, 6), (1, 5, 8)),
+            slope=0.1, post_slope=0.01)
+NEVER_RUN = ("ODD", "ONE", "FOUR")
+
 
 def hop(cfg) -> int:
     out = 1

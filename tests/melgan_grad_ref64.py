@@ -136,3 +136,18 @@ def tie_free_case(sd, cfg, B, T, lengths, G_seed, seeds=range(1, 9)):
         if near_ties(ref, lengths) == 0:
             return seed, mel, G, ref
     raise AssertionError(f"no tie-free mel among seeds {list(seeds)} for {B} x {T}")
+
+
+def one_number_movement(sd, cfg, mel, G, name="post.bias", draws=24, seed=0):
+    """For a gradient that is ONE number: (its float64 value, the 90th percentile of |float32 restatement - float64| over ``draws``
+    evaluations whose mel is moved by up to one float32 ulp, element by element).  The float32 restatement's error on one number is a
+    single draw of the host library's rounding; the percentile says how far float32 arithmetic moves the number whatever the host."""
+    _, _, g64 = run(sd, mel, None, cfg, G, None, torch.float64)
+    gen, ds = torch.Generator().manual_seed(seed), []
+    for i in range(draws):
+        m = mel.float()
+        if i:
+            m = m * (1 + (torch.randint(0, 3, m.shape, generator=gen) - 1).float() * ULP)
+        _, _, g32 = run(sd, m.double(), None, cfg, G, None, torch.float32)
+        ds.append((g32[name].double() - g64[name]).abs().item())
+    return g64[name].item(), torch.tensor(ds).quantile(0.9).item()

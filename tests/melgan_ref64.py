@@ -8,6 +8,21 @@ DEFAULT = dict(n_mels=80, base_channels=512, ratios=(8, 8, 2, 2), n_res=3, dil_b
 NARROW = dict(n_mels=10, base_channels=32, ratios=(4, 2), n_res=3, dil_base=3, slope=0.2)    # channels 16 and 8: below a matrix tile; K = 70
 SHALLOW = dict(n_mels=20, base_channels=128, ratios=(4, 2), n_res=1, dil_base=2, slope=0.2)  # layer count and dilation come from the dims
 TWO_DEEP = dict(n_mels=20, base_channels=128, ratios=(4, 2), n_res=2, dil_base=2, slope=0.2)
+# What no other configuration reaches (tests/test_generator_configs_cpu.py asserts the path of every layer):
+# ODD   37 mels padded to 40; pre's 136 columns on the 128-wide tile; 68 channels on the 64-wide tile under 6 phases (a column tail of 4, K
+#       tails of 8 and 4); ups.1 with 34 columns on the 64-wide tile; then 34 input channels: the dot-product kernel although Cout >= 32, and
+#       in the backward tensors whose rows are no multiple of 16 bytes; dilations 1 and 5
+# DEEP  5 mels padded to 8; eight residual layers (the most) at dilation 1; slope 1, the identity
+ODD = dict(n_mels=37, base_channels=136, ratios=(6, 2), n_res=2, dil_base=5, slope=0.2)
+DEEP = dict(n_mels=5, base_channels=64, ratios=(2,), n_res=8, dil_base=1, slope=1.0)
+NEVER_RUN = ("ODD", "DEEP")
+# The backward case ODD 1 x 11 draws its mel from a seed of its own.  d post.bias is ONE number, the sum of 132 terms of magnitude 1
+# that cancel to about 2: the float32 restatement's error on it is a single draw of the host library's rounding (1.7e-08 on one host,
+# 7.0e-07 on another, for seed 1), while float32 evaluated on mels moved by one ulp is off by 2.4e-06 at the 90th percentile - so the
+# 8 x rule passed or failed by the host (the device: 7.0e-06).  Of the seeds 1 .. 199 none makes 8 ulp at the number's scale, the term
+# no host changes, twice that percentile; seed 7 (d post.bias = 2.56) is the one where it is largest against it, 1.6 times:
+# tests/test_generator_configs_cpu.py asserts that it is above the percentile.
+BACKWARD_MEL_SEEDS = {("ODD", 1, 11): 7}
 
 
 def hop(cfg) -> int:

@@ -10,7 +10,7 @@ from tests import hifigan_grad_ref64 as GR
 from tests import hifigan_ref64 as R
 from tests.hifigan_train_helpers import dims_of, layout_of
 
-CFGS = ("V1", "V2", "V3", "NARROW", "TWO", "MID")
+CFGS = ("V1", "V2", "V3", "NARROW", "TWO", "MID", "ODD", "ONE", "FOUR")   # the last three: 37 and 5 mels, padded to 40 and 8 on the tape
 
 
 def _cotangent(cfg, B, T):

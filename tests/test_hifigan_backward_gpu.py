@@ -62,7 +62,8 @@ def _release_cached_blocks():
 
 
 CFGS = dict(NARROW=R.NARROW, TWO=R.TWO, MID=R.MID, V1=R.V1,
-            V1_LINEAR=dict(R.V1, slope=1.0, post_slope=1.0))   # no kinks: the same kernels against plain autograd at V1's sizes
+            V1_LINEAR=dict(R.V1, slope=1.0, post_slope=1.0),   # no kinks: the same kernels against plain autograd at V1's sizes
+            ODD=R.ODD, ONE=R.ONE, FOUR=R.FOUR)
 
 
 @functools.lru_cache(maxsize=None)
@@ -160,6 +161,23 @@ def test_gradients_pinned(name, B, T):
     """MID: 64 / 128 and 68 / 136 positions, both sides of the 128-position tile.  TWO: 128 and 144 positions at stage 1 with the
     72-row window.  V1: 512 to 32 channels, every matrix tile."""
     _check_pinned(name, B, T)
+
+
+@pytest.mark.parametrize("name,B,T,lens,tie_free", [
+    ("ODD", 2, 5, None, False), ("ODD", 1, 11, None, False), ("ODD", 3, 11, (11, 1, 5), False),
+    ("ONE", 2, 5, None, True), ("ONE", 1, 11, None, True), ("ONE", 3, 11, (11, 1, 5), True),
+    ("FOUR", 2, 5, None, True), ("FOUR", 1, 11, None, True), ("FOUR", 3, 11, (11, 1, 5), True)])
+def test_configurations_no_published_shape_reaches(name, B, T, lens, tie_free):
+    """ODD, ONE and FOUR of tests/hifigan_ref64.py: 37 mels in 40 padded channels through conv_pre's weight gradient and d_mel, 72 and
+    36 channels (K tails of 8 and 4 in the data gradients, ups in its 3-tap form at 432 and 72 columns), 6 and 10 phases, two, one
+    and four blocks per stage, slopes 0 and 1.  ONE and FOUR are small enough for a tie-free mel (with slope 0 a float64 pre-activation
+    within its tensor's bound of 0 is a tie like any other); ODD's 10^5 tape elements are pinned."""
+    if tie_free:
+        mel, G, _, _, grads = _check_tie_free(name, B, T, lens)
+        if lens is not None:
+            _check_rows_alone(name, mel, G, lens, grads)
+    else:
+        _check_pinned(name, B, T, lens)
 
 
 def test_gradients_v1_sizes_without_kinks():

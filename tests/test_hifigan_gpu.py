@@ -149,11 +149,22 @@ def test_published_configurations(name, B, T):
     assert wav.abs().max().item() < 1.0
 
 
-@pytest.mark.parametrize("name,lens", [("MID", (33, 1, 32, 17)), ("NARROW", (33, 1, 32, 7))])
+@pytest.mark.parametrize("B,T", [(1, 1), (2, 11), (1, 22)])
+@pytest.mark.parametrize("name", R.NEVER_RUN)
+def test_configurations_no_published_shape_reaches(name, B, T):
+    """ODD, ONE and FOUR (tests/hifigan_ref64.py says what each reaches; tests/test_generator_configs_cpu.py asserts the path of every
+    layer).  11 and 22 frames put 66 / 132 and 132 / 264 positions into ODD's two stages, either side of a 128-position tile; at 1 frame
+    ONE's row of 10 positions is shorter than the 36 positions of its window's left half."""
+    wav, _ = _check(name, B, T)
+    assert wav.abs().max().item() < 1.0
+
+
+@pytest.mark.parametrize("name,lens", [("MID", (33, 1, 32, 17)), ("NARROW", (33, 1, 32, 7)), ("ODD", (22, 1, 11)), ("ONE", (22, 1, 11)),
+                                       ("FOUR", (22, 1, 11))])
 def test_ragged_rows_equal_the_rows_alone(name, lens):
     """Every row against the restatement of that row alone; the mel behind a row's frames is NaN, so a read past the row's end shows;
     samples and stage rows behind a row's own length are exact zeros."""
-    cfg, T = getattr(R, name), 33
+    cfg, T = getattr(R, name), max(lens)
     wav, stages = _check(name, len(lens), T, lens)
     for b, t in enumerate(lens):
         assert not wav[b, t * R.hop(cfg):].any()
@@ -164,12 +175,13 @@ def test_ragged_rows_equal_the_rows_alone(name, lens):
     # a row of a ragged batch has the bits of that row run alone
     _, _, net = _net(name)
     mel = _case(name, len(lens), T, lens)[0].to(DEV, torch.float32)
-    b = 3
+    b = len(lens) - 1
     alone, _ = net.run(mel[b:b + 1, :, :lens[b]].contiguous())
     assert torch.equal(alone[0], wav[b, :lens[b] * R.hop(cfg)])
 
 
-@pytest.mark.parametrize("name,B,T,lens", [("MID", 2, 9, (5, 9)), ("NARROW", 3, 7, None)])
+@pytest.mark.parametrize("name,B,T,lens", [("MID", 2, 9, (5, 9)), ("NARROW", 3, 7, None), ("ODD", 2, 11, (5, 11)), ("ONE", 1, 22, None),
+                                           ("FOUR", 2, 11, (11, 3))])
 def test_workspace_contract(name, B, T, lens):
     """Exactly the stated size, all NaN before, a NaN guard behind it that stays NaN; one byte short is refused before anything is
     written; a reused (dirty) workspace gives the same bits; stage_out changes no bit of the waveform."""

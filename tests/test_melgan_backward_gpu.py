@@ -52,7 +52,8 @@ def _release_cached_blocks():
 
 CFGS = dict(NARROW=R.NARROW, SHALLOW=R.SHALLOW, TWO_DEEP=R.TWO_DEEP, DEFAULT=R.DEFAULT,
             WIDE=dict(R.SHALLOW, base_channels=512),      # channels 256 and 128: the 128-wide tile of the data gradients
-            DEFAULT_LINEAR=dict(R.DEFAULT, slope=1.0))    # no kinks: the same kernels against plain autograd at the default sizes
+            DEFAULT_LINEAR=dict(R.DEFAULT, slope=1.0),    # no kinks: the same kernels against plain autograd at the default sizes
+            ODD=R.ODD, DEEP=R.DEEP)
 
 
 @functools.lru_cache(maxsize=None)
@@ -143,6 +144,22 @@ def test_gradients_tie_free(name, B, T):
     """NARROW: fmaf layers, K = 70 in the first convolution; at T = 4 both reflections of the dilation-9 layer fold onto the same
     positions of a 16-position row.  TWO_DEEP 2 x 17: lengths 68 and 136 cross a 128-position tile.  WIDE: the 128-wide tile."""
     _check_tie_free(name, B, T)
+
+
+@pytest.mark.parametrize("name,B,T,lens,tie_free", [
+    ("ODD", 2, 5, None, False), ("ODD", 1, 11, None, False), ("ODD", 3, 11, (11, 4, 6), False),
+    ("DEEP", 2, 5, None, True), ("DEEP", 1, 11, None, True), ("DEEP", 3, 11, (11, 4, 6), True)])
+def test_configurations_no_other_case_reaches(name, B, T, lens, tie_free):
+    """ODD and DEEP of tests/melgan_ref64.py.  ODD: 37 mels in 40 padded channels, 136 and 68 channels on the matrix kernels, and 34
+    channels - tensors whose rows are no multiple of 16 bytes - through mgb_wide's three conditions: every gradient of stage 1 and the
+    data gradient into stage 0 run on the dot-product kernels.  DEEP: eight residual layers at dilation 1 under slope 1.  DEEP is small
+    enough for a tie-free mel; ODD is pinned (most mel seeds leave a near-tie or two among its 10^5 tape elements)."""
+    if tie_free:
+        mel, G, _, _, grads = _check_tie_free(name, B, T, lens)
+        if lens is not None:
+            _check_rows_alone(name, mel, G, lens, grads)
+    else:
+        _check_pinned(name, B, T, lens, mel_seed=R.BACKWARD_MEL_SEEDS.get((name, B, T), 1))   # tests/melgan_ref64.py says why 1 x 11 has its own
 
 
 @pytest.mark.parametrize("T", [4, 5])

@@ -126,7 +126,17 @@ def test_layer_count_and_dilation_come_from_the_dims(name):
     _check(name, 2, 9)
 
 
-@pytest.mark.parametrize("name,T,lens", [("DEFAULT", 33, (33, 4, 32, 17)), ("DEFAULT", 9, (5, 9)), ("NARROW", 64, (64, 4, 63, 32))])
+@pytest.mark.parametrize("B,T", [(1, 4), (2, 11), (1, 22)])
+@pytest.mark.parametrize("name", R.NEVER_RUN)
+def test_configurations_no_other_case_reaches(name, B, T):
+    """ODD and DEEP (tests/melgan_ref64.py says what each reaches; tests/test_generator_configs_cpu.py asserts the path of every layer).
+    11 and 22 frames put 66 / 132 and 132 / 264 positions into ODD's two stages, either side of a 128-position tile."""
+    wav, _ = _check(name, B, T)
+    assert wav.abs().max().item() <= 1.0   # tanh; DEEP's eight layers at slope 1 reach values that float32 rounds to 1 exactly
+
+
+@pytest.mark.parametrize("name,T,lens", [("DEFAULT", 33, (33, 4, 32, 17)), ("DEFAULT", 9, (5, 9)), ("NARROW", 64, (64, 4, 63, 32)),
+                                         ("ODD", 22, (22, 4, 11)), ("DEEP", 22, (22, 4, 11))])
 def test_ragged_rows_equal_the_rows_alone(name, T, lens):
     """Every row against the restatement of that row alone; the mel behind a row's frames is NaN, so a read past the row's end shows;
     samples and stage rows behind a row's own length are exact zeros."""
@@ -146,7 +156,7 @@ def test_ragged_rows_equal_the_rows_alone(name, T, lens):
     assert torch.equal(alone[0], wav[b, :lens[b] * R.hop(cfg)])
 
 
-@pytest.mark.parametrize("name,B,T,lens", [("DEFAULT", 2, 9, (5, 9)), ("NARROW", 3, 7, None)])
+@pytest.mark.parametrize("name,B,T,lens", [("DEFAULT", 2, 9, (5, 9)), ("NARROW", 3, 7, None), ("ODD", 2, 11, (5, 11)), ("DEEP", 1, 22, None)])
 def test_workspace_contract(name, B, T, lens):
     """Exactly the stated size, all NaN before, a NaN guard behind it that stays NaN; one byte short is refused before anything is
     written; a reused (dirty) workspace gives the same bits; stage_out changes no bit of the waveform."""
