@@ -203,8 +203,9 @@ class _VocodeWithGrad(torch.autograd.Function):
         dev = mel.device
         wav = torch.empty(B, T * model.hop, dtype=torch.float32, device=dev)
         tape = torch.empty(model._c("tape_bytes")(C.byref(dims), B, T), dtype=torch.uint8, device=dev)
-        _lib.check(model._c("forward_train")(h, mel.data_ptr(), _ptr(lens_dev), B, T, wav.data_ptr(), tape.data_ptr(), tape.numel(), None, 0,
-                                             model._stream(dev)))
+        scratch = model._forward_train_scratch(B, T, dev)
+        _lib.check(model._c("forward_train")(h, mel.data_ptr(), _ptr(lens_dev), B, T, wav.data_ptr(), tape.data_ptr(), tape.numel(), _ptr(scratch),
+                                             scratch.numel() if scratch is not None else 0, model._stream(dev)))
         ctx.model, ctx.lens_dev, ctx.shape, ctx.tape, ctx.packed_key = model, lens_dev, (B, T), tape, model._packed_key
         ctx.save_for_backward(*params)
         return wav
@@ -222,8 +223,9 @@ class _VocodeWithGrad(torch.autograd.Function):
         table, n = _weight_table(zip((k for k, _ in model.named_parameters()), grads))
         d_mel = torch.empty(B, model.audio_config.n_mels, T, dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
         ws = model._scratch("_train_workspace", model._c("backward_workspace_bytes")(C.byref(dims), B, T), dev)
-        _lib.check(model._c("backward")(model._handle, d_wav.data_ptr(), _ptr(ctx.lens_dev), B, T, ctx.tape.data_ptr(), ctx.tape.numel(), table, n,
-                                        _ptr(d_mel), ws.data_ptr(), ws.numel(), model._stream(dev)))
+        extra = model._backward_extra(params)
+        _lib.check(model._c("backward")(model._handle, d_wav.data_ptr(), _ptr(ctx.lens_dev), B, T, ctx.tape.data_ptr(), ctx.tape.numel(), *extra,
+                                        table, n, _ptr(d_mel), ws.data_ptr(), ws.numel(), model._stream(dev)))
         return (None, d_mel, None, *grads)
 
 
@@ -308,6 +310,15 @@ class DeviceGenerator(DeviceModule):
     def _forward_extra(self, extra, lo: int, n: int):
         """The arguments of ``<_abi>_forward`` between ``mel`` and the frame lengths for rows [lo, lo + n) of ``vocode``'s ``_extra``:
         none, unless the model takes a second per-row input (UnivNet's noise)."""
+        return ()
+
+    def _forward_train_scratch(self, B: int, T: int, dev: torch.device) -> Optional[torch.Tensor]:
+        """The scratch ``<_abi>_forward_train`` needs besides its tape: none, unless the model says otherwise (Vocos)."""
+        return None
+
+    def _backward_extra(self, params):
+        """The arguments of ``<_abi>_backward`` in front of the gradient table, from the node's saved parameters (``named_parameters()``
+        order): none, unless the kernels see something other than the parameters (Vocos folds ``gamma`` into ``pwconv2``)."""
         return ()
 
     def vocode(self, mel: torch.Tensor, mel_lengths=None, stage_outputs: bool = False, workspace: Optional[torch.Tensor] = None, _extra=None):

@@ -70,6 +70,10 @@ class gvx_melgan_tape_entry(C.Structure):
 gvx_hifigan_tape_entry = gvx_melgan_tape_entry   # the header's typedef
 
 
+class gvx_vocos_tape_entry(C.Structure):
+    _fields_ = [("byte_offset", C.c_uint64), ("rows", C.c_int32), ("channels", C.c_int32)]
+
+
 class gvx_melgan_disc_dims(C.Structure):
     _fields_ = [("n_scales", C.c_int32), ("base_channels", C.c_int32), ("n_layers", C.c_int32), ("downsampling_factor", C.c_int32),
                 ("max_channels", C.c_int32), ("slope", C.c_float)]
@@ -300,6 +304,16 @@ SIGNATURES = {
     "gvx_vocos_forward": (_i, [_vp, _vp, _vp, _i, _i, _vp, C.POINTER(_vp), _vp, _sz, _vp]),
     "gvx_vocos_timing_enable": (_i, [_vp, _i]),
     "gvx_vocos_stage_times_ms": (_i, [_vp, C.POINTER(_f), C.POINTER(_i)]),
+    "gvx_dwconv_layernorm_backward_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "gvx_dwconv_layernorm_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gvx_istft_head_backward_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "gvx_istft_head_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _vp]),
+    "gvx_vocos_tape_bytes": (_sz, [C.POINTER(gvx_vocos_dims), _i, _i]),
+    "gvx_vocos_tape_layout": (_i, [C.POINTER(gvx_vocos_dims), _i, _i, C.POINTER(gvx_vocos_tape_entry), _i]),
+    "gvx_vocos_backward_workspace_bytes": (_sz, [C.POINTER(gvx_vocos_dims), _i, _i]),
+    "gvx_vocos_forward_train": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "gvx_vocos_backward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, C.POINTER(gvx_weight_desc), _i, C.POINTER(gvx_weight_desc), _i, _vp, _vp, _sz, _vp]),
+    "gvx_vocos_backward_stage_times_ms": (_i, [_vp, C.POINTER(_f), C.POINTER(_i)]),
     "gvx_self_attention": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "gvx_add_layer_norm": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "gvx_fastpitch_blob_floats": (_sz, [C.POINTER(gvx_fastpitch_dims)]),

@@ -16,7 +16,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgenvox_amd.so")
-SOURCES = ["gemm_f32.hip", "winograd_conv.hip", "skinny.hip", "dec_resident.hip", "attention.hip", "attn_persist.hip", "misc.hip", "griffinlim.hip", "wav_finalize.hip", "wav_to_mel.hip", "resample.hip", "eval_metrics.hip", "mas.hip", "time_warp.hip", "melgan.hip", "melgan_train.hip", "melgan_disc.hip", "hifigan.hip", "hifigan_train.hip", "hifigan_disc.hip", "hifigan_msd.hip", "mrd.hip", "bigvgan.hip", "vocos.hip", "univnet.hip", "fastpitch.hip", "pitch.hip", "psola.hip", "stft_loss.hip", "mel_loss.hip", "denoise.hip",
+SOURCES = ["gemm_f32.hip", "winograd_conv.hip", "skinny.hip", "dec_resident.hip", "attention.hip", "attn_persist.hip", "misc.hip", "griffinlim.hip", "wav_finalize.hip", "wav_to_mel.hip", "resample.hip", "eval_metrics.hip", "mas.hip", "time_warp.hip", "melgan.hip", "melgan_train.hip", "melgan_disc.hip", "hifigan.hip", "hifigan_train.hip", "hifigan_disc.hip", "hifigan_msd.hip", "mrd.hip", "bigvgan.hip", "vocos.hip", "vocos_train.hip", "univnet.hip", "fastpitch.hip", "pitch.hip", "psola.hip", "stft_loss.hip", "mel_loss.hip", "denoise.hip",
            "train_conv.hip", "train_ops.hip", "train_bptt_decoder.hip", "train_bptt_encoder.hip", "train_guided.hip", "gvx_pack.hip", "gvx_decoder.hip", "gvx_api.hip"]
 ARCH = "gfx950"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

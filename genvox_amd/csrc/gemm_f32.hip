@@ -31,6 +31,7 @@
 // MFMA operand trick: one float4 per lane feeds four k-steps (k = 8*kg + 4*(lane>>5) + s), so both
 // operands are read as 16-byte vectors from K-contiguous rows; the k order inside a group of 8 is
 // permuted, which only reorders the fp32 summation.
+#include "gelu.h"
 #include "gvx_kernels.h"
 
 #include <cstdlib>
@@ -64,9 +65,7 @@ __device__ __forceinline__ long row_off(const RowMap& m, int row) {
 //   EPI_RES      C = acc + bias[n] + res(m, n)                     (res set, with a bias; pwconv2 and the block's residual)
 enum Epi : int { EPI_PARENT = 0, EPI_GENERAL = 1, EPI_PLAIN = 2, EPI_BIAS = 3, EPI_GELU = 4, EPI_RES = 5 };
 
-// nn.GELU(): x Phi(x) with the library's erff (1 ulp; the 1 + erf cancellation for x < 0 costs an absolute 6e-8 |x|, below an ulp of
-// the tensor's scale)
-__device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752f)); }
+// (gelu_erf: gelu.h, shared with the GELU backward of vocos_train.hip)
 
 // KMAJ: both operands are K-major - element (m, k) of A at A + amap(k) + m, element (n, k) of W at W + wmap(k) + n - the
 // form of a weight gradient (sum over the rows of two activation matrices) without transposed copies.

@@ -20,34 +20,19 @@
 //                            behind the row's samples.
 // No atomics anywhere.  Frames at and behind a row's length are written as zeros by every launch and never read by one.
 //
-// Order of this file: kernels, dims / blob / workspace layouts, the C ABI.
+// Order of this file: kernels and their launches, dims / blob / workspace layouts (what vocos_train.hip shares is declared in
+// vocos_internal.h), the C ABI.
 #include "fft_lds.h"
-#include "gen_host.h"
+#include "vocos_internal.h"
 
 #include <algorithm>
 
 using namespace gvx_gen;
+using namespace gvx_vc;
 using gvx::GemmParams;
 using gvx::RowMap;
 
-namespace gvx { hipError_t gemm_init(); }
-
-struct gvx_vocos : GenHandle {
-    gvx_vocos_dims d;
-};
-
 namespace {
-
-constexpr int VC_P = GVX_VOCOS_TILE;
-constexpr int VC_WAVES = 4;          // waves per workgroup of the filter + LayerNorm kernel and of the frame kernel
-constexpr float VC_LN_EPS = 1e-6f;
-constexpr float VC_MAG_MAX = 100.f;
-
-__device__ __forceinline__ float vc_wave_sum(float v) {   // a butterfly: every lane ends with the same bits
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 // mel [B][M][T] -> out [B][T + 6][Cp]: frame t at row t + 3, zeros in the halo rows, at and behind the row's length and in the
 // channel padding.  32 x 32 tiles through LDS: reads run along t, writes along c
@@ -67,14 +52,6 @@ __global__ void __launch_bounds__(256) vc_mel_transpose_kernel(const float* __re
         if (r < T + 6 && c < Cp) out[((size_t)b * (T + 6) + r) * Cp + c] = tile[tx][i];
     }
 }
-
-struct VcNorm {
-    const float* x; float* out;
-    const int32_t* lens;
-    int T, C, taps;
-    const float* w; const float* b; const float* ln_w; const float* ln_b;
-    float eps;
-};
 
 template <int NC>   // channels per lane: C <= 64 NC
 __global__ void __launch_bounds__(VC_WAVES * 64) vc_dwconv_ln_kernel(const VcNorm p) {
@@ -157,7 +134,9 @@ __global__ void __launch_bounds__(VC_WAVES * 64) vc_dwconv_ln_kernel(const VcNor
     }
 }
 
-int vc_norm(const VcNorm& p, int B, hipStream_t s) {
+}  // namespace
+
+int gvx_vc::vc_norm(const VcNorm& p, int B, hipStream_t s) {
     const dim3 grid((unsigned)((p.T + VC_P - 1) / VC_P), (unsigned)B);
     const size_t lds = p.taps ? (size_t)(VC_P + 6) * p.C * sizeof(float) : 0;
     const int nc = (p.C + 63) / 64;
@@ -169,6 +148,8 @@ int vc_norm(const VcNorm& p, int B, hipStream_t s) {
     return GVX_OK;
 }
 
+namespace {
+
 // window [N] (if asked for), w_H^m [H] and w_N^k [H + 1], in float64
 __global__ void vc_tables_kernel(float* win, float2* tw, float2* tw2, int N) {
     const int i = (int)blockIdx.x * 256 + threadIdx.x, H = N / 2;
@@ -177,14 +158,6 @@ __global__ void vc_tables_kernel(float* win, float2* tw, float2* tw2, int N) {
     if (i < H) { sincospi(2.0 * (double)i / (double)H, &sn, &cs); tw[i] = make_float2((float)cs, (float)-sn); }
     if (i <= H) { sincospi(2.0 * (double)i / (double)N, &sn, &cs); tw2[i] = make_float2((float)cs, (float)-sn); }
 }
-
-struct VcIstft {
-    const float* coeffs;   // [B][T][N + 2]: m[0 .. H], p[0 .. H]
-    const int32_t* lens;
-    int T;
-    const float* win; const float2* tw; const float2* tw2;
-    float* frames;         // [B][T][N]
-};
 
 template <int H>
 __global__ void __launch_bounds__(VC_WAVES * 64) vc_istft_kernel(const VcIstft p) {
@@ -260,6 +233,22 @@ __global__ void __launch_bounds__(256) vc_ola_kernel(const int32_t* __restrict__
     out[(long)b * n_max + i] = r;
 }
 
+}  // namespace
+
+namespace gvx_vc {
+
+int vc_tables(float* win, float2* tw, float2* tw2, int N, hipStream_t s) {
+    vc_tables_kernel<<<(unsigned)(N / 256 + 1), 256, 0, s>>>(win, tw, tw2, N);
+    HIP_TRY(hipGetLastError());
+    return GVX_OK;
+}
+
+int vc_mel_transpose(const float* mel, const int32_t* lens, int B, int M, int T, int Cp, float* out, hipStream_t s) {
+    vc_mel_transpose_kernel<<<dim3((unsigned)((T + 6 + 31) / 32), (unsigned)((Cp + 31) / 32), (unsigned)B), 256, 0, s>>>(mel, lens, M, T, Cp, out);
+    HIP_TRY(hipGetLastError());
+    return GVX_OK;
+}
+
 int vc_istft(const VcIstft& a, int B, int N, int hop, int center, float* wav, hipStream_t s) {
     const dim3 grid((unsigned)((a.T + VC_WAVES - 1) / VC_WAVES), (unsigned)B);
     switch (N) {
@@ -275,8 +264,6 @@ int vc_istft(const VcIstft& a, int B, int N, int hop, int center, float* wav, hi
 }
 
 // ---- dims, blob, workspace
-inline int vc_cpad(const gvx_vocos_dims& d) { return (d.n_mels + 3) & ~3; }
-
 const char* vc_fft_problem(int n_fft, int hop, int center) {
     if (n_fft != 512 && n_fft != 1024 && n_fft != 2048) return "n_fft must be 512, 1024 or 2048";
     if (hop < n_fft / 8 || hop > n_fft / 2) return "hop_length must be in [n_fft / 8, n_fft / 2]";
@@ -295,13 +282,6 @@ const char* vc_dims_problem(const gvx_vocos_dims* d) {
     return vc_fft_problem(d->n_fft, d->hop_length, d->center);
 }
 
-struct VcLayer { size_t dw_w, dw_b, ln_w, ln_b, pw1_w, pw1_b, pw2_w, pw2_b; };
-struct VcBlob {
-    size_t embed_w, embed_b, norm_w, norm_b;
-    VcLayer layer[GVX_VOCOS_MAX_LAYERS];
-    size_t fin_w, fin_b, head_w, head_b, window, tw, tw2, total;
-};
-
 VcBlob vc_blob_layout(const gvx_vocos_dims& d) {
     VcBlob L{};
     size_t at = 0;
@@ -318,8 +298,6 @@ VcBlob vc_blob_layout(const gvx_vocos_dims& d) {
     L.total = at;
     return L;
 }
-
-struct VcWs { size_t mel_t, x, a, h, coeffs, frames, total; };
 
 VcWs vc_ws_plan(const gvx_vocos_dims& d, int B, int T) {
     VcWs w{};
@@ -354,7 +332,7 @@ int vc_gemm(const float* A, const RowMap& amap, int K, const float* W, const flo
     return GVX_OK;
 }
 
-}  // namespace
+}  // namespace gvx_vc
 
 extern "C" {
 
@@ -454,7 +432,12 @@ int gvx_vocos_bind(gvx_vocos* h, const float* device_blob) {
     return GVX_OK;
 }
 
-int gvx_vocos_timing_enable(gvx_vocos* h, int enable) { return gen_timing_enable(h, enable, 5); }
+int gvx_vocos_timing_enable(gvx_vocos* h, int enable) {
+    if (!h) return fail(GVX_ERR_INVALID_ARG, "null argument");
+    if (enable)
+        if (const int rc = gen_make_marks(h->bwd_marks, 5)) return rc;
+    return gen_timing_enable(h, enable, 5);
+}
 
 int gvx_vocos_stage_times_ms(gvx_vocos* h, float* ms_out, int* n_out) { return gen_stage_times_ms(h, 4, ms_out, n_out); }
 

@@ -59,13 +59,21 @@ class HiFiGANTrainer:
 
     def train_step(self, mel: torch.Tensor, wav: torch.Tensor, mel_lengths=None) -> Dict[str, float]:
         """mel float32 [B, n_mels, T] and the recordings wav float32 [B, T * hop] on the device; ``mel_lengths`` ([B], host) for ragged
-        rows, row b then counting ``mel_lengths[b] * hop`` samples.  The discriminators take one optimizer step together, then the
-        generator takes one; the loss terms come back as floats."""
+        rows, row b then counting the samples the generator delivers for ``mel_lengths[b]`` frames (``G.sample_counts``; ``* hop`` where
+        the generator has none).  A generator whose full rows deliver fewer than ``T * hop`` samples (Vocos with "center" padding) gets
+        those counts without ``mel_lengths`` too: the discriminators and the spectral term would otherwise set a hop of recording against
+        a hop of zeros.  The discriminators take one optimizer step together, then the generator takes one; the loss terms come back as
+        floats."""
         G, tc = self.generator, self.training_config
+        counts = getattr(G, "sample_counts", None) or (lambda frames: [int(t) * G.hop for t in frames])
         sample_lengths = map_lengths = None
+        T = int(mel.shape[2])
         if mel_lengths is not None:
             host = [int(v) for v in (mel_lengths.tolist() if isinstance(mel_lengths, torch.Tensor) else mel_lengths)]
-            sample_lengths = [t * G.hop for t in host]
+            sample_lengths = [int(n) for n in counts(host)]
+        elif int(counts([T])[0]) != T * G.hop:
+            sample_lengths = [int(counts([T])[0])] * int(mel.shape[0])
+        if sample_lengths is not None:
             map_lengths = [D.map_lengths(sample_lengths) for D in self.discriminators]
         fake = G.vocode_with_grad(mel, mel_lengths)
 

@@ -7,8 +7,10 @@ published implementation's names (``backbone.embed``, ``backbone.norm``, ``backb
 carries (``head.istft.window``) is compared with the Hann window computed here and dropped, its ``feature_extractor.*`` buffers are
 dropped, and the conditioned ``AdaLayerNorm`` of the EnCodec variant (``backbone.norm.scale`` / ``.shift``) is refused by name.  The
 kernels read a packed blob that is rebuilt on the device whenever the parameters change; ``gamma`` is folded into ``pwconv2`` in float64
-at that point.  The calls are ``DeviceGenerator``'s.  There is no backward yet: ``vocode_with_grad`` is ``vocode`` when nothing asks for
-a gradient and raises ``NotImplementedError`` otherwise.  There is no CPU or eager path.
+at that point.  The calls are ``DeviceGenerator``'s.  The backward (gvx_vocos_forward_train / gvx_vocos_backward, csrc/vocos_train.hip)
+is opt-in: with ``trainable=False``, the default, ``vocode_with_grad`` is ``vocode`` when nothing asks for a gradient and raises
+``NotImplementedError`` otherwise; with ``trainable=True`` it is ``DeviceGenerator``'s autograd node, and the gradients of ``gamma`` and
+``pwconv2`` are unfolded on the device from those of the folded tensors.  There is no CPU or eager path.
 
 As with the other vocoders, the model vocodes whatever mel scale its checkpoint was trained on; no conversion is part of this module."""
 from __future__ import annotations
@@ -20,7 +22,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from ._device_module import DeviceGenerator, _Layer, _ptr
+from ._device_module import DeviceGenerator, _Layer, _ptr, _weight_table
 from .configs import AudioConfig, VocosConfig
 
 TILE = 16          # GVX_VOCOS_TILE: frames per workgroup of the filter + LayerNorm kernel
@@ -92,6 +94,81 @@ def istft_head(coeffs: torch.Tensor, n_fft: int, hop_length: int, padding: str =
     return wav
 
 
+def dwconv_layernorm_backward(x: torch.Tensor, dy: torch.Tensor, ln_weight: torch.Tensor, weight: Optional[torch.Tensor] = None,
+                              bias: Optional[torch.Tensor] = None, d_res: Optional[torch.Tensor] = None, lengths=None, eps: float = LN_EPS,
+                              workspace: Optional[torch.Tensor] = None, out=None):
+    """The backward of ``dwconv_layernorm`` on its own (gvx_dwconv_layernorm_backward): x (the layer's input) and dy (the gradient at the
+    LayerNorm's output) float32 [B, T, C] on the device, ``d_res`` the residual path's gradient or None -> (dx [B, T, C], d ln_weight,
+    d ln_bias, d weight [C, 1, 7] or None, d bias or None).  Rows are ragged as in the forward: dx is exact zeros at and behind a row's
+    length and neither x, dy nor d_res is read there.  ``workspace``: a uint8 tensor to use as it is; ``out``: the five results' own
+    tensors (contiguous float32 on the device, None where the result is None), written in place and returned (tests fill them first)."""
+    if x.dim() != 3 or x.device.type != "cuda" or x.dtype != torch.float32 or dy.shape != x.shape or dy.dtype != torch.float32 or dy.device != x.device:
+        raise ValueError(f"x and dy must be float32 [B, T, C] on the device, got {tuple(x.shape)} and {tuple(dy.shape)}")
+    B, T, C = x.shape
+    dev = x.device
+    taps = 0 if weight is None else 7
+    if (weight is None) != (bias is None) or (weight is not None and (tuple(weight.shape) != (C, 1, 7) or tuple(bias.shape) != (C,))):
+        raise ValueError(f"weight and bias must be [{C}, 1, 7] and [{C}], or both None")
+    if d_res is not None and (d_res.shape != x.shape or d_res.dtype != torch.float32 or d_res.device != dev):
+        raise ValueError("d_res must be like x")
+    if tuple(ln_weight.shape) != (C,):
+        raise ValueError(f"ln_weight must be [{C}], got {tuple(ln_weight.shape)}")
+    prep = lambda t: t.detach().to(dev, torch.float32).contiguous()
+    w = prep(weight.reshape(C, 7).t()) if taps else None
+    b = prep(bias) if taps else None
+    lw = prep(ln_weight)
+    lens = _lens_on(lengths, B, T, dev)
+    lib = _lib.load()
+    need = lib.gvx_dwconv_layernorm_backward_workspace_bytes(B, T, C, taps)
+    if need == 0:
+        raise ValueError(f"no filter + LayerNorm backward for B = {B}, T = {T}, C = {C}")
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if workspace is None else workspace
+    x, dy = x.contiguous(), dy.contiguous()
+    d_res = d_res.contiguous() if d_res is not None else None
+    new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+    shapes = [(B, T, C), (C,), (C,)] + ([(C, 1, 7), (C,)] if taps else [None, None])
+    if out is None:
+        out = [None if sh is None else new(*sh) for sh in shapes]
+    for t, sh in zip(out, shapes):
+        if (t is None) != (sh is None) or (t is not None and (tuple(t.shape) != sh or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous())):
+            raise ValueError(f"out must be contiguous float32 tensors of shapes {shapes} on {dev}")
+    dx, d_lw, d_lb, d_w, d_b = out
+    _lib.check(lib.gvx_dwconv_layernorm_backward(x.data_ptr(), dy.data_ptr(), _ptr(d_res), _ptr(lens), B, T, C, taps, _ptr(w), _ptr(b), lw.data_ptr(),
+                                                 float(eps), dx.data_ptr(), _ptr(d_w), _ptr(d_b), d_lw.data_ptr(), d_lb.data_ptr(), ws.data_ptr(),
+                                                 ws.numel(), torch.cuda.current_stream(dev).cuda_stream))
+    return dx, d_lw, d_lb, d_w, d_b
+
+
+def istft_head_backward(coeffs: torch.Tensor, d_wav: torch.Tensor, n_fft: int, hop_length: int, padding: str = "center", lengths=None,
+                        workspace: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The backward of ``istft_head`` on its own (gvx_istft_head_backward): coeffs float32 [B, T, n_fft + 2] and the waveform's gradient
+    d_wav [B, T * hop_length] on the device -> d_coeffs [B, T, n_fft + 2], exact zeros at and behind a row's frames; d_wav is not read
+    behind a row's delivered samples.  ``out``: the result's own tensor, written in place and returned (tests fill it first)."""
+    if coeffs.dim() != 3 or coeffs.device.type != "cuda" or coeffs.dtype != torch.float32 or coeffs.shape[2] != n_fft + 2:
+        raise ValueError(f"coeffs must be float32 [B, T, {n_fft + 2}] on the device, got {coeffs.dtype} {tuple(coeffs.shape)} on {coeffs.device}")
+    if padding not in ("center", "same"):
+        raise ValueError(f"padding must be 'center' or 'same', not {padding!r}")
+    B, T, _ = coeffs.shape
+    dev = coeffs.device
+    if tuple(d_wav.shape) != (B, T * int(hop_length)) or d_wav.dtype != torch.float32 or d_wav.device != dev:
+        raise ValueError(f"d_wav must be float32 [{B}, {T * int(hop_length)}] on {dev}")
+    lib = _lib.load()
+    need = lib.gvx_istft_head_backward_workspace_bytes(B, T, int(n_fft), int(hop_length))
+    if need == 0:
+        raise ValueError(f"no ISTFT backward for B = {B}, T = {T}, n_fft = {n_fft}, hop = {hop_length}")
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if workspace is None else workspace
+    win = hann_window(int(n_fft)).to(dev, torch.float32)
+    lens = _lens_on(lengths, B, T, dev)
+    coeffs, d_wav = coeffs.contiguous(), d_wav.contiguous()
+    if out is None:
+        out = torch.empty_like(coeffs)
+    elif out.shape != coeffs.shape or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+        raise ValueError(f"out must be contiguous float32 {tuple(coeffs.shape)} on {dev}")
+    _lib.check(lib.gvx_istft_head_backward(coeffs.data_ptr(), d_wav.data_ptr(), _ptr(lens), B, T, int(n_fft), int(hop_length), int(padding == "center"),
+                                           win.data_ptr(), ws.data_ptr(), ws.numel(), out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+    return out
+
+
 def dims_from_config(mc: VocosConfig, ac: AudioConfig) -> _lib.gvx_vocos_dims:
     d = _lib.gvx_vocos_dims()
     d.n_mels, d.dim, d.intermediate_dim, d.num_layers = int(ac.n_mels), mc.dim, mc.intermediate_dim, mc.num_layers
@@ -142,10 +219,11 @@ class VocosGenerator(DeviceGenerator):
     _abi, _config_class = "gvx_vocos", VocosConfig
     _range_hint = ""
 
-    def __init__(self, model_config: VocosConfig, audio_config: AudioConfig) -> None:
+    def __init__(self, model_config: VocosConfig, audio_config: AudioConfig, trainable: bool = False) -> None:
         super().__init__(model_config, audio_config)
         self.backbone = _Backbone(model_config, int(audio_config.n_mels))
         self.head = _Head(model_config)
+        self.trainable = bool(trainable)   # opt-in: vocode_with_grad builds an autograd node only when this is set
 
     @property
     def _min_frames(self) -> int:
@@ -218,11 +296,24 @@ class VocosGenerator(DeviceGenerator):
             out[k] = v
         return out
 
+    def _forward_train_scratch(self, B: int, T: int, dev: torch.device):
+        return self._scratch("_workspace", self.workspace_bytes(B, T), dev)
+
+    def _backward_extra(self, params):
+        """The raw ``gamma``, ``pwconv2.weight`` and ``pwconv2.bias`` of every block: the blob holds only their product."""
+        wanted = re.compile(r"\.convnext\.\d+\.(gamma|pwconv2\.weight|pwconv2\.bias)$")
+        return _weight_table((k, p) for (k, _), p in zip(self.named_parameters(), params) if wanted.search(k))
+
     def vocode_with_grad(self, mel: torch.Tensor, mel_lengths=None) -> torch.Tensor:
-        """``vocode`` when gradients are off or nothing requires one; otherwise NotImplementedError: Vocos's backward is not built."""
+        """``trainable=True``: ``DeviceGenerator.vocode_with_grad`` - the waveform with ``vocode``'s bits, whose ``backward()`` fills
+        ``.grad`` of every parameter (``gamma`` and ``pwconv2`` unfolded) and of ``mel`` on the device's own kernels.  ``trainable=False``
+        (the default): ``vocode`` when gradients are off or nothing requires one; otherwise NotImplementedError."""
+        if self.trainable:
+            return super().vocode_with_grad(mel, mel_lengths)
         if torch.is_grad_enabled() and (mel.requires_grad or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError("VocosGenerator has no backward on the device yet: vocode_with_grad runs only under torch.no_grad() or "
-                                      "when neither the mel nor a parameter requires a gradient")
+            raise NotImplementedError("this VocosGenerator was built without its backward: vocode_with_grad runs only under torch.no_grad() or "
+                                      "when neither the mel nor a parameter requires a gradient. Construct it with trainable=True, or set "
+                                      "model.trainable = True, to train it on the device")
         return self.vocode(mel, mel_lengths)
 
     def load_checkpoint_statedicts(self, statedicts: Dict, save_optimizer_dict: bool = False, optimizer: Optional[Dict] = None) -> None:

@@ -1387,7 +1387,8 @@ int gvx_bigvgan_stage_times_ms(gvx_bigvgan* handle, float* ms_out, int* n_out);
  * 1 + center: GVX_ERR_INVALID_ARG; the workspace missing, misaligned or short: GVX_ERR_WORKSPACE.  Launches: one transpose, the embed
  * product, per LayerNorm or filter + LayerNorm one, per product one (two where the GEMM's plan covers the rows with two tile shapes),
  * the frame kernel and the gather.  gvx_vocos_stage_times_ms: four durations - embed + norm, the blocks, final norm + head product,
- * the ISTFT.  Every dims field is checked: a bad one gives blob_floats == 0 and create == GVX_ERR_INVALID_ARG.  There is no backward. */
+ * the ISTFT.  Every dims field is checked: a bad one gives blob_floats == 0 and create == GVX_ERR_INVALID_ARG.  The backward is
+ * "Vocos generator: training" below. */
 enum { GVX_VOCOS_TILE = 16, GVX_VOCOS_MAX_DIM = 512, GVX_VOCOS_MAX_INTERMEDIATE = 8192, GVX_VOCOS_MAX_LAYERS = 64, GVX_VOCOS_MAX_FRAMES = 1 << 20 };
 typedef struct gvx_vocos_dims {
     int32_t n_mels;             /* >= 1 */
@@ -1414,6 +1415,99 @@ int gvx_vocos_forward(gvx_vocos* handle, const float* mel, const int32_t* frame_
                       float* const* stage_out, void* workspace, size_t workspace_bytes, void* stream);
 int gvx_vocos_timing_enable(gvx_vocos* handle, int enable);
 int gvx_vocos_stage_times_ms(gvx_vocos* handle, float* ms_out, int* n_out);
+
+/* Vocos generator: training.  A forward that keeps a tape, and the backward: the calls of "HiFi-GAN generator: training" above, with
+ * their argument order and error codes, for the network of gvx_vocos_forward.  Kernels: csrc/vocos_train.hip on the dense fp32 GEMM
+ * (csrc/gemm_f32.hip) and the in-LDS FFT (csrc/fft_lds.h); all arithmetic is fp32 (sums ACROSS pieces and launch_col_reduce's add in
+ * float64, in a fixed order); no float atomics: two calls give the same bits.  Every launch treats ragged rows as its forward twin
+ * does: frames at and behind a row's length are written as exact zeros and nothing is read there, in the activations or in the incoming
+ * gradient.  The inference blob, the inference workspace and gvx_vocos_forward are as above, bit for bit.
+ *
+ * gvx_dwconv_layernorm_backward is the twin of gvx_dwconv_layernorm on its own.  x (the layer's input), dy (the gradient at the
+ * LayerNorm's output) and dx fp32 [B][T][C]; d_res (the residual path's gradient, added to dx) [B][T][C] or NULL, and may be dx itself; w
+ * fp32 [7][C] TAP-major and b [C] as the forward takes them, ln_w [C]; taps 7 or 0 (0: the plain LayerNorm backward; w, b, d_w, d_b are not
+ * used).  It recomputes u = dwconv(x) + b and its statistics with the forward's own two passes over registers (an offset of 1e3 does not
+ * cost the digits of xh), forms du = rstd (dxh - mean(dxh) - xh mean(dxh xh)) with dxh = dy ln_w, and writes
+ *     dx[t] = d_res[t] + sum_j w[j] du[t + 3 - j],   d_ln_w = sum dy xh,   d_ln_b = sum dy,   d_w[c][0][j] = sum_t du[t] x[t + j - 3],   d_b = sum_t du
+ * d_w in PyTorch's layout [C][1][7].  Decomposition: vcb_ln_kernel - a workgroup of four waves per piece of GVX_VOCOS_GRAD_PIECE frames of
+ * one row (not per GVX_VOCOS_TILE frames as the forward: the piece's sums stay in registers), wave w taking frames w, w + 4, .. of the
+ * piece, lanes along the channels, 1 / 2 / 4 / 8 channels per lane, the filter's inputs read from memory without an LDS tile - writes du
+ * (taps 0: dx) and the piece's partial sums; vcb_dw_kernel - a wave per 64 channels of a piece - the filter's adjoint and the piece's d_w;
+ * vcb_sum_kernel adds the pieces in piece order.  A piece wholly behind its row writes zeros over whatever the workspace held.
+ * GVX_VOCOS_GRAD_PIECE is 128: at 32 x 800 frames that is 224 workgroups for the 256 compute units, where 256 frames would give 128.
+ * Workspace (gvx_dwconv_layernorm_backward_workspace_bytes, host arithmetic, exact, 0 for refused shapes):
+ *     round256(4 * B * ceil(T / GVX_VOCOS_GRAD_PIECE) * 10 * C) + (taps ? round256(4 * B * T * C) : 0)        the partials, then du
+ *
+ * gvx_istft_head_backward is the twin of gvx_istft_head on its own: coeffs [B][T][N + 2] and d_wav [B][T * hop] -> d_coeffs [B][T][N + 2].
+ * The adjoint of the overlap-add is a gather: vcb_env_kernel writes d_wav / envelope inside a row's delivered samples and 0 behind them
+ * (d_wav is not read there); vcb_istft_kernel takes a frame per wave, reads its n_fft positions through the trim of the padding mode,
+ * applies the window and 1 / N, runs the forward real transform X in LDS, and with c_0 = c_H = 1, c_k = 2 otherwise
+ *     dRe = c_k Re X_k,  dIm = c_k Im X_k (0 at DC and Nyquist);   d p = mag (-dRe sin p + dIm cos p);
+ *     d m = (dRe cos p + dIm sin p) mag  where the device's own expf(m) <= 100, else 0                        (torch.clip's gradient)
+ * mag, cos and sin recomputed from coeffs as the forward computes them.  No spectrum goes to memory.  Workspace
+ * (gvx_istft_head_backward_workspace_bytes): round256(4 * B * T * hop) + round256(8 * (N + 1)), d_wav / envelope and the twiddles.
+ *
+ * Tape: the caller's memory, 256-byte aligned, gvx_vocos_tape_bytes (host arithmetic, exact) long; gvx_vocos_tape_layout lists its
+ * tensors in forward order as (byte offset, rows per batch row, channels), each fp32 [B][rows][channels], one starting where the one
+ * before it ends:
+ *     the transposed mel with its 3-frame zero halo [T + 6][Cp];  the embedding's output [T][dim];  x in front of the first block [T][dim];
+ *     per block: its pre-GELU p [T][I], then x behind it [T][dim];  the head product [T][N + 2]
+ *     tape_bytes = 4 * B * ( (T + 6) Cp + T ( (L + 2) dim + L I + N + 2 ) )
+ * - 4 + 2 L entries; 74,136 bytes per frame and row for the default model with 100 mels (and 2,400 per row for the halo).  The LayerNorm
+ * outputs and h = gelu(p) are NOT kept: the backward recomputes each into its workspace with the forward's own kernel (one more
+ * elementwise launch per block, against 8,192 more bytes per frame, row and block).  Every tape tensor holds exact zeros at and behind a
+ * row's length.  Both calls return 0 for refused dims, B outside [1, 65535], T outside [1 + center, GVX_VOCOS_MAX_FRAMES].
+ *
+ * gvx_vocos_forward_train is the forward with every kept tensor written into its tape slot - the same kernels with the same arguments,
+ * except that pwconv1 runs with its bias only into the tape and one elementwise launch of the same gelu function (csrc/gelu.h) follows it -
+ * so wav_out has the bits of gvx_vocos_forward.  Its workspace is gvx_vocos_workspace_bytes (the LayerNorm output, h and the frames).
+ *
+ * gvx_vocos_backward: d_wav fp32 [B][T * hop], never read at or behind a row's delivered samples.  grads is a HOST table that names DEVICE
+ * destinations under the PUBLISHED state-dict names (backbone.embed.weight .. head.out.bias: what named_parameters() gives); every
+ * parameter gradient is WRITTEN (not accumulated) in PyTorch's own layout: embed.weight [dim][n_mels][7] without the channel padding,
+ * dwconv.weight [dim][1][7].  The blob holds only gamma (.) pwconv2, so `raw` - a HOST table in front of grads - names the DEVICE tensors
+ * of the three unfolded parameters of every block (backbone.convnext.<i>.gamma, .pwconv2.weight, .pwconv2.bias); the products give dW2'
+ * and db2' with respect to the folded tensors and vcb_unfold_kernel turns them into
+ *     dW2 = gamma (.) dW2',   db2 = gamma (.) db2',   d gamma[c] = sum_i dW2'[c][i] W2[c][i] + db2'[c] b2[c]
+ * without a division: a gamma element of 0 gives the right gradient.  d_mel_out is NULL (the embedding's data gradient is skipped; no
+ * parameter gradient changes a bit) or fp32 [B][n_mels][T], exactly 0 at and behind a row's frames; row b of it has the bits of that row
+ * run alone.  Refused before anything is launched: a missing name (GVX_ERR_MISSING_WEIGHT), a wrong element count or NULL destination
+ * (GVX_ERR_SHAPE), a NULL, short or misaligned tape or workspace (GVX_ERR_WORKSPACE), B or T as the forward refuses them, T below
+ * 1 + center (GVX_ERR_INVALID_ARG).
+ *
+ * The backward is a chain of ordinary launches.  Data gradients are launch_gemm with row_len on weights transposed from the bound blob at
+ * the start of every call (never stale); the head's K of N + 2 is padded to a multiple of 4 with zero columns in d_coeffs and in the
+ * transposed head weight.  Weight gradients are the GEMM's K-major form over all B * T frames with split-K partials in the workspace,
+ * added in split order; the embedding's reads the haloed mel through a two-level row map.  Bias gradients are launch_col_reduce.
+ * gvx_vocos_backward_workspace_bytes is host arithmetic and exact, any contents when the call starts: with Np = N + 2 rounded up to 4,
+ * the transposed weights (dim Np + 2 L dim I + 7 dim Cp floats), d_wav / envelope, d_coeffs [B T][Np], the recomputed LayerNorm output and
+ * h, dp, three [B T][dim] gradient tensors, the embedding's gradient with its halo, d_mel channels-last, (L + 2) sets of LayerNorm
+ * partials, dW2' and db2' of every block, one padded weight gradient and the split-K partials, each rounded up to 256 bytes.
+ *
+ * Timing (measurement only): with gvx_vocos_timing_enable on, gvx_vocos_backward_stage_times_ms gives the last backward call's four
+ * durations in the order they ran: the weight transposes + ISTFT + head, the blocks, embed + norm, the pieces' sums and the unfold. */
+enum { GVX_VOCOS_GRAD_PIECE = 128 };
+typedef struct gvx_vocos_tape_entry {
+    uint64_t byte_offset;
+    int32_t rows;       /* per batch row: T, or T + 6 for the haloed mel */
+    int32_t channels;
+} gvx_vocos_tape_entry;
+size_t gvx_dwconv_layernorm_backward_workspace_bytes(int B, int T, int C, int taps);
+int gvx_dwconv_layernorm_backward(const float* x, const float* dy, const float* d_res, const int32_t* lens, int B, int T, int C, int taps,
+                                  const float* w, const float* b, const float* ln_w, float eps, float* dx, float* d_w, float* d_b,
+                                  float* d_ln_w, float* d_ln_b, void* workspace, size_t workspace_bytes, void* stream);
+size_t gvx_istft_head_backward_workspace_bytes(int B, int T, int n_fft, int hop);
+int gvx_istft_head_backward(const float* coeffs, const float* d_wav, const int32_t* lens, int B, int T, int n_fft, int hop, int center,
+                            const float* window, void* workspace, size_t workspace_bytes, float* d_coeffs, void* stream);
+size_t gvx_vocos_tape_bytes(const gvx_vocos_dims* dims, int B, int T);
+int gvx_vocos_tape_layout(const gvx_vocos_dims* dims, int B, int T, gvx_vocos_tape_entry* entries, int max_entries);
+size_t gvx_vocos_backward_workspace_bytes(const gvx_vocos_dims* dims, int B, int T);
+int gvx_vocos_forward_train(gvx_vocos* handle, const float* mel, const int32_t* frame_lengths, int B, int T, float* wav_out, void* tape,
+                            size_t tape_bytes, void* workspace, size_t workspace_bytes, void* stream);
+int gvx_vocos_backward(gvx_vocos* handle, const float* d_wav, const int32_t* frame_lengths, int B, int T, const void* tape,
+                       size_t tape_bytes, const gvx_weight_desc* raw, int n_raw, const gvx_grad_desc* grads, int n_grads, float* d_mel_out,
+                       void* workspace, size_t workspace_bytes, void* stream);
+int gvx_vocos_backward_stage_times_ms(gvx_vocos* handle, float* ms_out, int* n_out);
 
 /* ---- UnivNet generator, (mel, noise) -> waveform (Jang et al. 2021; the maum-ai/univnet implementation, c32 and c16): inference.  The
  * reference ships no such model; the network below is a statement of the published implementation, under its names, and the float64

@@ -53,6 +53,10 @@ stage, summed, as a share of one call;
 events, median of 7 with the spread: ours, the float32 restatement of tests/vocos_ref64.py on the same device and parameters ("torch"),
 the four stage times (embed + norm, the blocks, final norm + head product, ISTFT), and the share of the fp32 matrix rate (157.3 TFLOP/s)
 that the blocks' time amounts to for their MLP products;
+`vocos_train` (on request): the Vocos generator's `vocode_with_grad` + `backward()` (gvx_vocos_forward_train + gvx_vocos_backward), default
+configuration with 100 mels, at 16 x 32, 8 x 128 and 32 x 800 frames between device events, median and range of 7, against torch autograd
+of the float32 restatement on the same device, with the backward's four part times, the blocks' product rate against 157.3 TFLOP/s and
+the tape's and the workspace's size;
 `fastpitch` (on request): the FastPitch acoustic model, published sizes, on given durations - 32 x 128 tokens -> 800 frames, 1 x 100 tokens
 -> 568 frames, 8 x 40 tokens -> 200 frames - between device events, median of 7 with the spread: ours (both phases and the read-back of
 the frame counts), the float32 restatement of tests/fastpitch_ref64.py run as a batch on the same device with the same weights ("torch":
@@ -1249,6 +1253,71 @@ def main():
                 want = ref(mel)[0]
             res[key]["max_abs_difference_from_torch"] = float((want - wav[:, :want.shape[1]]).abs().max())
             res[key]["verdict"] = "faster" if res[key]["ours"]["median_ms"] < res[key]["torch_float32_restatement"]["median_ms"] else "SLOWER"
+            print(json.dumps({key: res[key]}), flush=True)
+        del voc, ref
+    if "vocos_train" in which:
+        import statistics
+
+        from genvox_amd.configs import VocosConfig
+        from genvox_amd.vocos import VocosGenerator
+        from tests import vocos_grad_ref64 as GR
+        from tests import vocos_ref64 as R
+
+        def ev_spread(fn, warm=2, reps=7):
+            for _ in range(warm):
+                fn()
+            out = []
+            for _ in range(reps):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                e1.synchronize()
+                out.append(e0.elapsed_time(e1))
+            return {"median_ms": round(statistics.median(out), 3), "min_ms": round(min(out), 3), "max_ms": round(max(out), 3), "runs": reps}
+
+        cfg = R.DEFAULT
+        vac = AudioConfig(filter_length=1024, hop_length=256, log_func="np.log")
+        vac.n_mels = cfg["n_mels"]
+        ref = R.Generator(cfg, seed=0).float().to("cuda:0")
+        voc = VocosGenerator(VocosConfig(), vac, trainable=True)
+        voc.load_state_dict(ref.state_dict())
+        voc.to("cuda:0")
+        gen = torch.Generator(device="cuda").manual_seed(0)
+        # the blocks' products: pwconv1 and pwconv2 forward (2), and per block two data and two weight gradients backward (4)
+        block_flops_per_frame = 2.0 * cfg["num_layers"] * cfg["dim"] * cfg["intermediate_dim"]
+        for B, T in ((16, 32), (8, 128), (32, 800)):
+            key = f"vocos_train_{B}x{T}"
+            mel = (1.5 * torch.randn(B, cfg["n_mels"], T, device="cuda", generator=gen) - 3.0).contiguous()
+            G = torch.randn(B, T * cfg["hop_length"], device="cuda", generator=gen)
+
+            def ours():
+                voc.zero_grad(set_to_none=True)
+                voc.vocode_with_grad(mel).backward(G)
+
+            def torchs():
+                ref.zero_grad(set_to_none=True)
+                wav, _ = GR.forward(ref, mel)
+                wav.backward(G[:, :wav.shape[1]])
+
+            d = voc.dims()
+            res[key] = {"ours_forward_train_plus_backward": ev_spread(ours), "torch_autograd_float32_restatement": ev_spread(torchs, warm=1),
+                        "tape_bytes": voc._c("tape_bytes")(__import__("ctypes").byref(d), B, T),
+                        "backward_workspace_bytes": voc._c("backward_workspace_bytes")(__import__("ctypes").byref(d), B, T)}
+            voc.enable_stage_timing(True)
+            per = []
+            for _ in range(7):
+                ours()
+                per.append(voc._times_ms("backward_stage_times_ms", 4))
+            voc.enable_stage_timing(False)
+            stage = [statistics.median(col) for col in zip(*per)]
+            res[key]["backward_stage_ms_median"] = [round(v, 3) for v in stage]   # transposes + ISTFT + head, the blocks, embed + norm, sums + unfold
+            res[key]["backward_stage_ms_range"] = [[round(min(col), 3), round(max(col), 3)] for col in zip(*per)]
+            tflops = 4 * block_flops_per_frame * B * T / (stage[1] * 1e-3) / 1e12
+            res[key]["backward_blocks_products_tflops"] = round(tflops, 1)   # the elementwise and LayerNorm launches count towards the time
+            res[key]["backward_blocks_fraction_of_157TF_fp32_mfma"] = round(tflops / 157.3, 3)
+            res[key]["verdict"] = ("faster" if res[key]["ours_forward_train_plus_backward"]["median_ms"] < res[key]["torch_autograd_float32_restatement"]["median_ms"]
+                                   else "SLOWER")
             print(json.dumps({key: res[key]}), flush=True)
         del voc, ref
     if "fastpitch" in which:
