@@ -222,6 +222,7 @@ SIGNATURES = {
     "gvx_wav_trim_bounds": (_i, [_vp, _i, _i, C.c_long, _vp, _i, _f, _vp, _vp]),
     "gvx_wav_to_mel_ragged": (_i, [_vp, _vp, _i, _vp, _vp, _i, C.c_long, _vp, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "gvx_resample_uses_lds_table": (_i, [_i, _i, _i]),
+    "gvx_resample_block_shape": (_i, [_i, _i, _i, _vp, _vp]),
     "gvx_wav_mixdown": (_i, [_vp, _i, _i, C.c_long, _i, _vp, _vp]),
     "gvx_wav_resample_ragged": (_i, [_vp, _i, _i, C.c_long, _vp, _i, _i, _vp, _i, _vp, C.c_long, _vp, _vp]),
     "gvx_alignment_stats": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -229,6 +229,14 @@ int gvx_resample_uses_lds_table(int up, int taps_per_phase, int pcm_kind) {
     return (pcm_kind == GVX_PCM_FLOAT64 ? rs_table_fits<double>(up, taps_per_phase) : rs_table_fits<float>(up, taps_per_phase)) ? 1 : 0;
 }
 
+int gvx_resample_block_shape(int up, int down, int taps_per_phase, int* S_out, int* R_out) {
+    if (up < 1 || up > GVX_RESAMPLE_MAX_UP || down < 1 || down > GVX_RESAMPLE_MAX_DOWN || !rs_taps_ok(taps_per_phase) || !S_out || !R_out) return -1;
+    const RsShape sh = rs_shape(up, down, taps_per_phase);
+    *S_out = sh.S;
+    *R_out = sh.R;
+    return 0;
+}
+
 int gvx_wav_mixdown(const void* pcm, int pcm_kind, int B, long n_max, int channels, float* mono_out, void* stream) {
     const int rc = rs_check_batch(pcm, pcm_kind, B, n_max);
     if (rc != GVX_OK) return rc;

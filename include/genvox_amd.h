@@ -614,7 +614,10 @@ int gvx_wav_to_mel_ragged(gvx_gl_plan* plan, const void* pcm, int pcm_kind, cons
  * unknown pcm_kind, up or down < 1, a bad taps_per_phase: GVX_ERR_INVALID_ARG; all of it checked before anything is launched.
  * The kernel stages the table in LDS when it fits beside its input tile and reads it through the cache from global memory when
  * not; the resample_uses_lds_table query says which (1 / 0) for a table of `up` rows and the output type of pcm_kind, and returns -1
- * for an up, taps_per_phase or pcm_kind the call would refuse.
+ * for an up, taps_per_phase or pcm_kind the call would refuse.  An output block of a workgroup is R * S consecutive samples of a row
+ * (S a multiple of up, R in {1, 2, 4}; a function of up, down and taps_per_phase alone): the resample_block_shape query writes S and R
+ * and returns 0, or writes nothing and returns -1 for an up, down or taps_per_phase the call would refuse or a NULL pointer.  Neither
+ * query makes a HIP call.
  *
  * The mix-down call: interleaved pcm [B][n_max][channels] (what scipy.io.wavfile.read gives per file), channels in [2, 8], to
  * float32 mono_out [B][n_max]: the arithmetic mean of a frame's channels, summed in double in ascending channel order and
@@ -622,6 +625,7 @@ int gvx_wav_to_mel_ragged(gvx_gl_plan* plan, const void* pcm, int pcm_kind, cons
 enum { GVX_PCM_FLOAT64 = 2 };
 enum { GVX_RESAMPLE_MAX_UP = 2048, GVX_RESAMPLE_MAX_DOWN = 2048, GVX_RESAMPLE_MAX_TAPS = 1024 };
 int gvx_resample_uses_lds_table(int up, int taps_per_phase, int pcm_kind);
+int gvx_resample_block_shape(int up, int down, int taps_per_phase, int* S_out, int* R_out);
 int gvx_wav_mixdown(const void* pcm, int pcm_kind, int B, long n_max, int channels, float* mono_out, void* stream);
 int gvx_wav_resample_ragged(const void* pcm, int pcm_kind, int B, long n_max, const int32_t* bounds, int up, int down,
                             const void* table, int taps_per_phase, void* out, long n_out_stride, int32_t* out_lengths, void* stream);

@@ -1,5 +1,7 @@
 """CPU: the host side of the GPU resampler - rate ratios, the filter's measured response for every supported pair, the polyphase
 table's layout, the float64 restatement against scipy's polyphase resampler, the grouping of a mixed batch."""
+import ctypes
+
 import numpy as np
 import pytest
 import scipy.signal
@@ -44,6 +46,72 @@ def test_library_says_which_pairs_stage_the_table_and_which_it_refuses():
     assert lib.gvx_wav_resample_ragged(None, 1, 1, 10, None, 1, 2, None, 68, None, 5, None, None) == -1
     assert b"null" in lib.gvx_last_error()
     assert lib.gvx_wav_mixdown(None, 1, 1, 10, 2, None, None) == -1
+
+
+def block_shape(lib, up, down, K):
+    """(rc, S, R) of gvx_resample_block_shape; S and R stay -7 where the query writes nothing."""
+    S, R = ctypes.c_int(-7), ctypes.c_int(-7)
+    rc = lib.gvx_resample_block_shape(up, down, K, ctypes.addressof(S), ctypes.addressof(R))
+    return rc, S.value, R.value
+
+
+def test_library_says_which_block_shape_a_ratio_takes():
+    lib = _lib.load()   # a host-side query as well
+    assert block_shape(lib, 1, 2, 4) == (0, 256, 4)             # 44100 -> 22050 with the shortest table: 256 phases' worth of one phase
+    assert block_shape(lib, 147, 320, 148) == (0, 294, 4)       # 48000 -> 22050: two sweeps of the 147 phases
+    assert block_shape(lib, 1, 2048, 4) == (0, 1, 2)            # 4 * 2048 + 4 inputs pass the 6144-sample tile: R = 2, and c = 1
+    assert block_shape(lib, 1280, 441, 68) == (0, 1280, 4) and block_shape(lib, 2048, 2047, 1024) == (0, 2048, 2)
+    for up, down, K in [(0, 2, 4), (rs.MAX_UP + 1, 2, 4), (1, 0, 4), (1, rs.MAX_DOWN + 1, 4), (1, 2, 0), (1, 2, 6), (1, 2, rs.MAX_TAPS + 4), (-1, -1, -4)]:
+        assert block_shape(lib, up, down, K) == (-1, -7, -7), (up, down, K)
+    one = ctypes.c_int(-7)
+    assert lib.gvx_resample_block_shape(1, 2, 4, None, ctypes.addressof(one)) == -1 and lib.gvx_resample_block_shape(1, 2, 4, ctypes.addressof(one), None) == -1
+    assert one.value == -7
+    # R = 1 cannot be asked for: it needs 2 * down + K > 6144 (span(2 * up) = floor((2 * up - 1) * down / up) + 1 + K <= 2 * down + K),
+    # and the limits stop at 2 * 2048 + 1024 = 5120
+    assert 2 * rs.MAX_DOWN + rs.MAX_TAPS <= 6144
+    for up in (1, 2, 3, 2047, 2048):
+        for down in (2047, 2048):
+            assert block_shape(lib, up, down, rs.MAX_TAPS)[2] == 2, (up, down)
+
+
+@pytest.mark.parametrize("up,down,K", [(3, 2, 8), (1, 2048, 4), (7, 5, 12), (147, 320, 148), (2048, 1, 4), (5, 5, 4)])
+def test_vectorised_restatement_is_the_loop_form(up, down, K):
+    """``resample_vec`` against ``resample`` on rows of 1, K - 1, K and about 500 samples.  The two sum the same terms (the vectorised
+    form adds the exact zeros outside the row and the prototype) in different orders, so the bits may differ: both stay within
+    1e-15 * (sum of magnitudes) of each other, the magnitudes themselves within the same, and the lengths are equal."""
+    rng = np.random.default_rng(up * 4096 + down)
+    if (up, down, K) == (147, 320, 148):
+        h = rs.resample_filter(up, down)                 # the designer's prototype: its half is no multiple of up
+        assert rs.taps_per_phase(len(h), up) == K
+    else:
+        h = ref.prototype(rng.uniform(-1.0, 1.0, size=(up, K)))
+    for n in (1, K - 1, K, 503 if up < 2048 else 9):     # up = 2048, down = 1: 2048 outputs per sample
+        x = rng.uniform(-1.0, 1.0, size=n)
+        want, want_mag = ref.resample(x, h, up, down)
+        got, got_mag = ref.resample_vec(x, h, up, down)
+        assert got.shape == want.shape == got_mag.shape == (ref.resampled_length(n, up, down),)
+        assert (np.abs(got - want) <= 1e-15 * want_mag).all(), (n, np.abs(got - want).max())
+        assert (np.abs(got_mag - want_mag) <= 1e-15 * want_mag).all(), n
+        wide, wide_mag = ref.resample_vec(x, h, up, down, wide=True)      # the same sums carried in long double, rounded once
+        assert wide.dtype == wide_mag.dtype == np.float64 and (np.abs(wide - want) <= 1e-15 * want_mag).all() and (np.abs(wide_mag - want_mag) <= 1e-15 * want_mag).all()
+    assert ref.resample_vec(np.zeros(0), h, up, down)[0].shape == (0,)
+
+
+@pytest.mark.parametrize("up,K", [(1, 4), (3, 8), (7, 12), (160, 68), (2048, 4), (2, 1020)])
+def test_full_table_and_prototype_round_trip(up, K):
+    """``prototype`` is the inverse of the designer's ``polyphase_table`` for a table with every tap in use.  The prototype has
+    K * up + 1 taps (the last a zero), for which the designer lays out K + 4 columns: the table between two columns of zeros."""
+    table = np.random.default_rng(up + K).uniform(-1.0, 1.0, size=(up, K))
+    h = ref.prototype(table)
+    assert h.shape == (K * up + 1,) and h[-1] == 0.0 and np.count_nonzero(h) == up * K
+    back = rs.polyphase_table(h, up, np.float64)
+    assert back.shape == (up, K + 4) and np.array_equal(back[:, 2:-2], table) and not back[:, :2].any() and not back[:, -2:].any()
+    # the header's own statement of the layout: table[p][k] = h[p + (K / 2 - 1 - k) * up], h centred
+    half = (K // 2) * up
+    for p, k in [(0, 0), (up - 1, K - 1), (up // 2, K // 2), (0, K - 1), (up - 1, 0)]:
+        assert table[p, k] == h[half + p + (K // 2 - 1 - k) * up]
+    # the designer's own inverse wraps around at the one tap the table does not hold
+    assert rs.prototype_from_table(table, len(h))[-1] == table[0, -1] != 0.0
 
 
 @pytest.mark.parametrize("src,dst", PAIRS)
